@@ -13,13 +13,23 @@ slices).  Rows are sharded over the N ranks (strong scaling: total work fixed).
     value = (algorithmic CSR bytes of the WHOLE matrix, reference byte model
              src/bandwidth.cpp:34-42) x steps / wall time          [GB/s, whole job]
 
-also reported: GFLOPS, PageRank iterations/s, the roofline of the dominant kernel
-(HIP events around the step kernel alone), the drop-in spmv_csr() numbers per kernel
-type for BASELINE configs 2-5 (reference protocol: 5 warm-up + 20 timed calls,
-kernel-only event time), and the CPU baseline (the reference's spmv_cpu_csr on the same
-matrix, one host thread).
+also reported: GFLOPS and PageRank iterations/s (from the same timed steps).
 
-usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--nnz-per-row k] [--no-extras]
+A plain run does only what that headline needs: set up, W warm-up steps, K timed steps,
+the outputs (--dump-outputs), the line.  --full adds what takes runs of its own: the
+roofline of the dominant kernel (HIP events around the step kernel alone), the drop-in
+spmv_csr() numbers per kernel type for BASELINE configs 2-5 (reference protocol: 5
+warm-up + 20 timed calls, kernel-only event time), the CPU baselines (the reference's
+spmv_cpu_csr on the same matrix, one host thread and all cores; its PageRank host loop),
+the parity report, the value-folded step and, for N > 1, the opt-in exchange trials
+(SPMV_PR_OVERLAP / SPMV_PR_EXCHANGE).  --no-extras keeps --full to the roofline.
+
+--dump-outputs DIR: after the timed steps, what the last one computed (the rank vector in
+node order, fp32, and its residual, fp64) as DIR/ranks.npy and DIR/residual.npy.  Same
+arguments, same inputs: the matrix is a pure function of --seed.
+
+usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--nnz-per-row k] [--seed S]
+                       [--dump-outputs DIR] [--full [--no-extras]]
        (N > 1: launched by torch.distributed.run, one rank per GPU)
 """
 from __future__ import annotations
@@ -47,7 +57,12 @@ def parse():
     p.add_argument("--rows", type=int, default=10_000_000)
     p.add_argument("--nnz-per-row", type=int, default=16)
     p.add_argument("--seed", type=int, default=42)
-    p.add_argument("--no-extras", action="store_true", help="skip the per-config spmv_csr table and the CPU baseline")
+    p.add_argument("--full", action="store_true",
+                   help="also the roofline, CPU baselines, spmv_csr table, parity report, folded step and exchange trials")
+    p.add_argument("--no-extras", action="store_true",
+                   help="with --full: skip the per-config spmv_csr table and the CPU baselines (the roofline stays)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed as DIR/<name>.npy")
     return p.parse_args()
 
 
@@ -55,13 +70,31 @@ def csr_bytes(rows, cols, nnz):
     return nnz * 8 + (rows + 1) * 4 + cols * 4 + rows * 4
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, pr, engine, steps_done):
+    """--dump-outputs: what the last timed step handed its caller — the new rank vector, in node order (fp32), and the
+    residual the step committed (fp64) — as DIR/ranks.npy and DIR/residual.npy.  A vector too large for the 64 MB
+    limit is written as every s-th node from node 0 (a fixed sample: the same nodes for the same --rows)."""
+    os.makedirs(directory, exist_ok=True)
+    vector = pr.r[steps_done & 1]                   # step k writes r[(k + 1) & 1]; the last timed step is k = W + K - 1
+    stride = -(-pr.n * 4 // (DUMP_LIMIT_BYTES - 4096))
+    ranks = vector[pr._pos[::stride]].cpu().numpy().astype(np.float32)
+    residual = np.array([engine.status()[1]], dtype=np.float64)
+    np.save(os.path.join(directory, "ranks.npy"), ranks)
+    np.save(os.path.join(directory, "residual.npy"), residual)
+    print("[bench] outputs: %s/ranks.npy (%d of %d nodes, every %d-th), %s/residual.npy"
+          % (directory, ranks.size, pr.n, stride, directory), file=sys.stderr, flush=True)
+
+
 
 # ------------------------------------------------------------------------------------------------
 # One JSON line, whatever happens after the measurement.
 #
-# The measurement itself (W + K steps of the one-collective loop, then the step kernel under HIP events)
-# comes first.  Everything after it — CPU baseline, spmv_csr table, parity report, folded plan, opt-in exchange
-# trials — can only ADD keys.  By default bench.py runs as a SUPERVISOR that never touches the GPU: it starts
+# The measurement itself (W + K steps of the one-collective loop; with --full, then the step kernel under HIP
+# events) comes first.  Everything after it — with --full: CPU baseline, spmv_csr table, parity report, folded plan,
+# opt-in exchange trials — can only ADD keys.  By default bench.py runs as a SUPERVISOR that never touches the GPU: it starts
 # the real run as a child (same interpreter, same arguments, SPMV_BENCH_CHILD=1) and reads the child's
 # stdout.  The child writes a complete line as soon as the measurement stands and again after every extra;
 # the supervisor prints the LAST line it received when the child ends — normally, by a Python exception, by
@@ -348,68 +381,15 @@ def main():
     if rank != 0 and os.environ.get("SPMV_BENCH_CHILD") == "1" and os.environ.get("SPMV_BENCH_SELF_LAUNCHED") != "1":
         os.write(result_fd, b"MEASURED\n")          # tells this rank's supervisor that the timed region is over
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, pr, engine, args.warmup + args.steps)
+
     bytes_per_step = csr_bytes(n, n, nnz_total)
     ms_per_step = elapsed / args.steps * 1e3
     value = bytes_per_step * args.steps / elapsed / 1e9
-
-    # ---- roofline of the dominant kernel: the fused step kernel alone, HIP events on its stream ----
-    local_bytes = csr_bytes(local_rows, n, local_rows * k)     # this rank's share of the algorithmic bytes
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(10)]
-    for a, b in ev:
-        a.record()
-        engine._check(spmv.lib().spmv_c_pr_step(engine._shard, pr.r[0].data_ptr(), pr.r[1].data_ptr(), damping,
-                                                engine._stream()), "pr_step")
-        b.record()
-    torch.cuda.synchronize()
-    kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
-    achieved = local_bytes / (kernel_ms * 1e-3) / 1e9
     tiled = spmv.csr_has_tiled_plan(engine._A)
     plan_info = spmv.csr_tiled_info(engine._A)
-    # roofline.traffic is NOT measured by this run: it is the PMC figure of a separate rocprofv3 pass over this
-    # same command (tools/pmc_traffic.sh -> profiles/pmc_traffic.json; FETCH_SIZE x 2 + WRITE_SIZE, see
-    # MI355X_MICROARCH.md).  It is reported only while that file describes the plan shape that ran here.
-    traffic, traffic_source = None, None
-    pmc_file = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-    if os.path.exists(pmc_file) and world == 1 and tiled:
-        try:
-            pmc = json.load(open(pmc_file))
-            same_shape = all(pmc.get("plan", {}).get(k) == plan_info.get(k)
-                             for k in ("strip_cols", "tile_rows", "num_strips", "num_tiles", "slots_in_cells"))
-            import hashlib
-            same_sources = all(
-                hashlib.sha256(open(os.path.join(ROOT, "gpu-spmv_amd", "csrc", name), "rb").read()).hexdigest() == digest
-                for name, digest in pmc.get("sources_sha256", {"missing": ""}).items()) if pmc.get("sources_sha256") else False
-            if same_shape and same_sources:
-                traffic = pmc.get("pr_step_kernel_bytes_per_launch")
-                traffic_source = "profiles/pmc_traffic.json (commit %s; %s)" % (pmc.get("commit", "?"), pmc.get("collected", "separate rocprofv3 --pmc passes"))
-            elif same_shape:
-                traffic_source = ("profiles/pmc_traffic.json was collected on other kernel sources (commit %s): not reported"
-                                  % pmc.get("commit", "?"))
-            else:
-                traffic_source = "profiles/pmc_traffic.json describes another plan shape: not reported"
-        except Exception:
-            traffic = None
-    step_kernels = ("tiled_expand_kernel + tiled_pagerank_reduce_kernel (two launches per step: bucketed-slot "
-                    "propagation-blocking engine, x strips and y tiles in LDS)"
-                    if tiled else "pr_step_kernel (fused vector-CSR direct-gather SpMV + PageRank update)")
-    # what the bound is: `frac` prices the ALGORITHMIC bytes; the engine moves `traffic` bytes
-    # (1.84x of them: the product round trip), and that traffic over the same time is what the memory system
-    # actually carried — a kernel saturated on wasted bytes, not an idle one
-    traffic_frac = round(traffic / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if traffic else None
-    roofline = {"bound": "hbm", "kernel": step_kernels,
-                "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
-                "traffic_frac": traffic_frac,
-                "floor_note": ("frac = algorithmic bytes / kernel time / peak; traffic_frac = the bytes the kernels really moved "
-                               "(PMC) over the same time: the two-phase engine streams 15 B per entry (7 B of bucketed matrix + "
-                               "a 4 B product written and read back) against the byte model's 8 B; both kernels run within ~10 % of "
-                               "what plain streams of their bytes take on the same box (profiles/r04_phase2_bound.txt: phase 1 "
-                               "307-312 us against 297, phase 2 157 against ~140-156), and running the phases side by side or part "
-                               "by part through the Infinity Cache does not pay (profiles/r04_parts_overlap_rejected.txt, "
-                               "r04_infinity_cache_parts_rejected.txt)")
-                              if tiled else None,
-                "kernel_ms": round(kernel_ms, 4), "algorithmic_bytes_per_launch": local_bytes,
-                "tiled_plan": plan_info}
+    roofline = full_roofline(spmv, torch, engine, pr, plan_info, tiled, local_rows, n, k, world, damping) if args.full else None
 
     result = {
         "metric": "spmv_effective_bandwidth", "value": round(value, 1), "unit": "GB/s",
@@ -432,13 +412,14 @@ def main():
                    "exchange": exchange,
                    "exchange_note": None if world == 1 else
                        "one RCCL all-gather per step (the recorded default); the overlapped and push exchanges are opt-in "
-                       "(SPMV_PR_OVERLAP / SPMV_PR_EXCHANGE), run after this line and report on stderr",
+                       "(--full with SPMV_PR_OVERLAP / SPMV_PR_EXCHANGE), run after this line and report on stderr",
                    "values_folded": bool(plan_info and plan_info.get("values_folded"))},
         "gflops": round(2.0 * nnz_total * args.steps / elapsed / 1e9, 1),
         "pagerank_iters_per_sec": round(args.steps / elapsed, 2),
         "frac_of_hbm_peak_whole_job": round(value / (HBM_PEAK_GBS * world), 4),
-        "roofline": roofline,
     }
+    if roofline is not None:
+        result["roofline"] = roofline
 
     child = os.environ.get("SPMV_BENCH_CHILD") == "1"
     printed = {"final": False}
@@ -469,7 +450,7 @@ def main():
 
     try:
         emit(False)                                   # the measurement stands from here on
-        if rank == 0 and world == 1 and not args.no_extras:
+        if rank == 0 and world == 1 and args.full and not args.no_extras:
             def do_cpu_baseline():
                 result["cpu_baseline"], result["cpu_baseline_all_cores"] = cpu_baseline(spmv, row_ptrs, cols_v, vals_v, n, nnz_total)
 
@@ -526,7 +507,7 @@ def main():
                 info_f = spmv.csr_tiled_info(folded._A)
                 folded_traffic = None
                 try:
-                    folded_traffic = json.load(open(pmc_file)).get("folded", {}).get("bytes_per_step")
+                    folded_traffic = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json"))).get("folded", {}).get("bytes_per_step")
                 except Exception:
                     pass
                 result["pagerank_step_values_folded"] = {
@@ -550,15 +531,15 @@ def main():
             result["cpu_baseline"] = None
         emit(True)
 
-        # ---- N > 1, opt-in, AFTER the line: other exchanges against the recorded all-gather.  Whatever happens in
+        # ---- --full, N > 1, opt-in, AFTER the line: other exchanges against the recorded all-gather.  Whatever happens in
         # here — an exception, a fault, a hung collective on hardware these paths have never seen — the line is out.
         overlap = [int(c) for c in os.environ.get("SPMV_PR_OVERLAP", "").split(",") if c.strip()]
         overlap = [c for c in overlap if c > 1]
-        if layout.exchange and overlap:
+        if args.full and layout.exchange and overlap:
             _fail_here("trial")
             overlap_trial(spmv, prd, dist, torch, device, args, layout, pr, engine, row_ptrs, cols, vals, vals_v, stream,
                           damping, never, timed, elapsed, overlap)
-        if world > 1 and os.environ.get("SPMV_PR_EXCHANGE", "gather") in ("push", "auto"):
+        if args.full and world > 1 and os.environ.get("SPMV_PR_EXCHANGE", "gather") in ("push", "auto"):
             push_trial(pr, dist, torch, device, world, rank, backend, damping, never, barrier, ms_per_step)
     finally:
         emit(True)
@@ -566,6 +547,67 @@ def main():
     pr.close()          # unmaps peers, barriers, then frees the rank vectors
     if world > 1 or force_exchange:
         dist.destroy_process_group()
+
+
+def full_roofline(spmv, torch, engine, pr, plan_info, tiled, local_rows, n, k, world, damping):
+    """--full: roofline of the dominant kernel — the step kernel alone, HIP events on its stream, 10 launches after the
+    timed steps (they overwrite the rank vectors, so --dump-outputs has written them already)."""
+    local_bytes = csr_bytes(local_rows, n, local_rows * k)     # this rank's share of the algorithmic bytes
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(10)]
+    for a, b in ev:
+        a.record()
+        engine._check(spmv.lib().spmv_c_pr_step(engine._shard, pr.r[0].data_ptr(), pr.r[1].data_ptr(), damping,
+                                                engine._stream()), "pr_step")
+        b.record()
+    torch.cuda.synchronize()
+    kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
+    achieved = local_bytes / (kernel_ms * 1e-3) / 1e9
+    # roofline.traffic is NOT measured by this run: it is the PMC figure of a separate rocprofv3 pass over this
+    # same command (tools/pmc_traffic.sh -> profiles/pmc_traffic.json; FETCH_SIZE x 2 + WRITE_SIZE, see
+    # MI355X_MICROARCH.md).  It is reported only while that file describes the plan shape that ran here.
+    traffic, traffic_source = None, None
+    pmc_file = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+    if os.path.exists(pmc_file) and world == 1 and tiled:
+        try:
+            pmc = json.load(open(pmc_file))
+            same_shape = all(pmc.get("plan", {}).get(k) == plan_info.get(k)
+                             for k in ("strip_cols", "tile_rows", "num_strips", "num_tiles", "slots_in_cells"))
+            import hashlib
+            same_sources = all(
+                hashlib.sha256(open(os.path.join(ROOT, "gpu-spmv_amd", "csrc", name), "rb").read()).hexdigest() == digest
+                for name, digest in pmc.get("sources_sha256", {"missing": ""}).items()) if pmc.get("sources_sha256") else False
+            if same_shape and same_sources:
+                traffic = pmc.get("pr_step_kernel_bytes_per_launch")
+                traffic_source = "profiles/pmc_traffic.json (commit %s; %s)" % (pmc.get("commit", "?"), pmc.get("collected", "separate rocprofv3 --pmc passes"))
+            elif same_shape:
+                traffic_source = ("profiles/pmc_traffic.json was collected on other kernel sources (commit %s): not reported"
+                                  % pmc.get("commit", "?"))
+            else:
+                traffic_source = "profiles/pmc_traffic.json describes another plan shape: not reported"
+        except Exception:
+            traffic = None
+    step_kernels = ("tiled_expand_kernel + tiled_pagerank_reduce_kernel (two launches per step: bucketed-slot "
+                    "propagation-blocking engine, x strips and y tiles in LDS)"
+                    if tiled else "pr_step_kernel (fused vector-CSR direct-gather SpMV + PageRank update)")
+    # what the bound is (VERDICT r02 item 7): `frac` prices the ALGORITHMIC bytes; the engine moves `traffic` bytes
+    # (1.84x of them: the product round trip), and that traffic over the same time is what the memory system
+    # actually carried — a kernel saturated on wasted bytes, not an idle one
+    traffic_frac = round(traffic / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if traffic else None
+    roofline = {"bound": "hbm", "kernel": step_kernels,
+                "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
+                "traffic_frac": traffic_frac,
+                "floor_note": ("frac = algorithmic bytes / kernel time / peak; traffic_frac = the bytes the kernels really moved "
+                               "(PMC) over the same time: the two-phase engine streams 15 B per entry (7 B of bucketed matrix + "
+                               "a 4 B product written and read back) against the byte model's 8 B; both kernels run within ~10 % of "
+                               "what plain streams of their bytes take on the same box (profiles/r04_phase2_bound.txt: phase 1 "
+                               "307-312 us against 297, phase 2 157 against ~140-156), and running the phases side by side or part "
+                               "by part through the Infinity Cache does not pay (profiles/r04_parts_overlap_rejected.txt, "
+                               "r04_infinity_cache_parts_rejected.txt)")
+                              if tiled else None,
+                "kernel_ms": round(kernel_ms, 4), "algorithmic_bytes_per_launch": local_bytes,
+                "tiled_plan": plan_info}
+    return roofline
 
 
 def overlap_trial(spmv, prd, dist, torch, device, args, layout, pr, engine, row_ptrs, cols, vals, vals_v, stream,

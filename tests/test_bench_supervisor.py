@@ -188,3 +188,43 @@ def test_cpu_pagerank_baseline_runs_the_reference_host_loop_for_the_asked_iterat
                                       {"iterations": 3, "seconds_total": 0.0025})
     assert out["iterations"] == 3 and out["cores"] == 1 and out["unit"] == "iterations/s" and out["value"] > 0
     assert out["kind"] == "port" and abs(out["rank_sum"] - 1.0) < 1e-3 and out["gpu_iterations_per_s_incl_setup"] == 1200.0
+
+
+def test_dump_outputs_writes_the_vector_of_the_last_step_in_node_order(tmp_path, monkeypatch):
+    """--dump-outputs: step k writes r[(k + 1) & 1], so after W + K steps the last result is r[(W + K) & 1]; nodes come
+    out in node order (positions in the padded vector); over the size limit a fixed stride sample; fp32 + fp64 only."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class Engine:
+        def status(self):
+            return 5, 0.25, False, False
+
+    class Loop:
+        n = 6
+        _pos = torch.tensor([1, 0, 3, 2, 5, 4])
+        r = [torch.zeros(8), torch.arange(8, dtype=torch.float32) + 0.5]
+
+    bench.dump_outputs(str(tmp_path / "a"), Loop(), Engine(), 5)
+    ranks, residual = np.load(tmp_path / "a" / "ranks.npy"), np.load(tmp_path / "a" / "residual.npy")
+    assert ranks.dtype == np.float32 and ranks.tolist() == [1.5, 0.5, 3.5, 2.5, 5.5, 4.5]
+    assert residual.dtype == np.float64 and residual.tolist() == [0.25]
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096 + 12)          # room for 3 of the 6 nodes: every 2nd
+    bench.dump_outputs(str(tmp_path / "b"), Loop(), Engine(), 4)
+    assert np.load(tmp_path / "b" / "ranks.npy").tolist() == [0.0, 0.0, 0.0]
+    Loop.r[0] = torch.arange(8, dtype=torch.float32)
+    bench.dump_outputs(str(tmp_path / "b"), Loop(), Engine(), 4)
+    assert np.load(tmp_path / "b" / "ranks.npy").tolist() == [1.0, 3.0, 5.0]
+
+
+def test_full_is_off_by_default_and_dump_outputs_takes_a_directory(monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    args = bench.parse()
+    assert not args.full and args.dump_outputs is None and args.steps == 7 and args.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    args = bench.parse()
+    assert args.full and args.dump_outputs == "out"

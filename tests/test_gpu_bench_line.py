@@ -1,4 +1,5 @@
-"""bench.py end to end on the GPU box (small matrix): stdout is exactly one JSON line with the contract's keys, and the
+"""bench.py end to end on the GPU box (small matrix): stdout is exactly one JSON line with the contract's keys, a plain
+run measures only its headline and writes what its last step computed (--dump-outputs), and under --full the
 line survives a failing extra and a failing exchange trial (protocol of the reference's
 include/spmv/benchmark.h:34-40: warm-up, timed iterations, one record out)."""
 import json
@@ -7,6 +8,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,7 +30,7 @@ def one_line(out):
 
 @pytest.mark.gpu
 def test_one_line_with_the_contract_keys(gpu):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-extras"] + SMALL,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-extras"] + SMALL,
                          capture_output=True, text=True, timeout=900)
     line = one_line(out)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -41,10 +43,34 @@ def test_one_line_with_the_contract_keys(gpu):
 
 
 @pytest.mark.gpu
+def test_plain_run_is_the_headline_and_dumps_the_last_step(gpu, oracle, tmp_path):
+    """No --full: the steps it was asked for and nothing after them (no roofline launches, no extras); --dump-outputs
+    holds the rank vector after the W + K steps, which is W + K PageRank iterations of the oracle on the same matrix."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dump-outputs", str(tmp_path / "out")] + SMALL,
+                         capture_output=True, text=True, timeout=900)
+    line = one_line(out)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line, key
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert "roofline" not in line and line["cpu_baseline"] is None and "extras_done" not in line
+    assert sorted(os.listdir(tmp_path / "out")) == ["ranks.npy", "residual.npy"]
+    ranks, residual = np.load(tmp_path / "out" / "ranks.npy"), np.load(tmp_path / "out" / "residual.npy")
+    assert ranks.dtype == np.float32 and residual.dtype == np.float64 and residual.shape == (1,)
+    n = line["config"]["rows"]
+    rp, ci, _ = gpu.synth.uniform_csr(42, 0, n, n, line["config"]["avg_nnz_per_row"])
+    va = gpu.synth.column_stochastic_values(ci, n)
+    want, *_ = oracle.pagerank(rp, ci, va, num_cols=n, tolerance=0.0, max_iterations=4, wide_sums=True)
+    got = ranks.astype(np.float64)
+    assert ranks.shape == (n,) and np.isfinite(residual).all() and residual[0] >= 0
+    worst = float(np.max(np.abs(got / got.sum() - want) / np.abs(want)))
+    assert worst <= 1e-5, worst
+
+
+@pytest.mark.gpu
 def test_an_extra_that_kills_the_process_costs_the_extra_only(gpu):
     env = dict(os.environ, SPMV_BENCH_FAIL_IN="cpu_baseline:abort")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + SMALL, capture_output=True, text=True,
-                         timeout=900, env=env)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + SMALL, capture_output=True,
+                         text=True, timeout=900, env=env)
     line = one_line(out)
     assert line["value"] > 0 and "incomplete" in line and line["roofline"]["frac"] > 0
 
@@ -56,7 +82,7 @@ def test_two_ranks_a_failing_exchange_trial_still_leaves_the_line(gpu, how):
     env = dict(os.environ, SPMV_BENCH_BACKEND="gloo", SPMV_PR_OVERLAP="2", SPMV_BENCH_FAIL_IN="trial:" + how)
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
-                          os.path.join(ROOT, "bench.py"), "--gpus", "2"] + SMALL,
+                          os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full"] + SMALL,
                          capture_output=True, text=True, timeout=1200, env=env)
     line = one_line(out)
     assert line["n_gpus"] == 2 and line["config"]["exchange"] == "gather" and line["value"] > 0

@@ -1,11 +1,12 @@
-"""Turns the CSVs of tools/pmc_traffic.sh (gpurun_out/pmc_traffic/) into profiles/pmc_traffic.json."""
+"""Turns the CSVs of tools/pmc_traffic.sh ($SPMV_PROFILE_OUT/pmc_traffic/, default profile_out/) into
+profiles/pmc_traffic.json."""
 import collections
 import csv
 import json
 import os
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "gpurun_out", "pmc_traffic")
+SRC = os.path.join(os.environ.get("SPMV_PROFILE_OUT", os.path.join(ROOT, "profile_out")), "pmc_traffic")
 
 
 def per_kernel(name):
@@ -22,7 +23,7 @@ def per_kernel(name):
 def main():
     out = {
         "command": "tools/pmc_traffic.sh: rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (separate passes) "
-                   "-- python3 bench.py --no-extras --steps 5 --warmup 1, with SPMV_TILED_FOLD=0 and =1",
+                   "-- python3 bench.py --full --no-extras --steps 5 --warmup 1, with SPMV_TILED_FOLD=0 and =1",
         "correction": "gfx950: FETCH_SIZE counts 1/2 of the bytes of coalesced streaming reads (MI355X_MICROARCH.md HBM "
                       "section; re-checked in round 1 on count_columns_kernel: 312 MB reported for a 640 MB "
                       "dword-per-lane stream), so read bytes = 2 x FETCH_SIZE; WRITE_SIZE taken as is; both in KB",
