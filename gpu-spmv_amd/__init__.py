@@ -195,7 +195,12 @@ _SIGNATURES = {
                                       c_void_p]),
     "spmv_c_spmv_ell_async": (c_int, [POINTER(ELLMatrix), c_void_p, c_void_p, POINTER(SpMVConfig), c_int,
                                       c_void_p]),
+    "spmv_c_spmv_csr_multi": (c_int, [POINTER(CSRMatrix), c_void_p, c_int, c_void_p, c_int, c_int,
+                                      POINTER(SpMVConfig), c_int, POINTER(SpMVResult)]),
+    "spmv_c_spmv_csr_multi_async": (c_int, [POINTER(CSRMatrix), c_void_p, c_int, c_void_p, c_int, c_int,
+                                            POINTER(SpMVConfig), c_int, c_void_p]),
     "spmv_c_compute_bandwidth_csr": (c_int, [POINTER(CSRMatrix), c_float, POINTER(BandwidthMetrics)]),
+    "spmv_c_compute_bandwidth_csr_multi": (c_int, [POINTER(CSRMatrix), c_int, c_float, POINTER(BandwidthMetrics)]),
     "spmv_c_compute_bandwidth_ell": (c_int, [POINTER(ELLMatrix), c_float, POINTER(BandwidthMetrics)]),
     "spmv_c_get_gpu_peak_bandwidth": (c_float, []),
     "spmv_c_pagerank": (c_int, [POINTER(CSRMatrix), POINTER(PageRankConfig), POINTER(_PageRankResultC)]),
@@ -664,6 +669,25 @@ def spmv_ell_async(A, d_x, d_y, config=None, vec_size=-1, stream=None) -> int:
                                        c_void_p(stream))
 
 
+def spmv_csr_multi(A, d_X, d_Y, k, ldx=None, ldy=None, config=None, vec_size=-1) -> SpMVResult:
+    """Y = A * X for k right-hand sides (include/spmv/spmv.h spmv_csr_multi): X num_cols x k and Y num_rows x k,
+    row-major device arrays with leading dimensions ldx, ldy (default k); Y's columns k..ldy-1 are never written."""
+    out = SpMVResult()
+    ldx = k if ldx is None else ldx
+    ldy = k if ldy is None else ldy
+    lib().spmv_c_spmv_csr_multi(A, _dev(d_X), int(ldx), _dev(d_Y), int(ldy), int(k),
+                                byref(config) if config is not None else None, vec_size, byref(out))
+    return out
+
+
+def spmv_csr_multi_async(A, d_X, d_Y, k, ldx=None, ldy=None, config=None, vec_size=-1, stream=None) -> int:
+    ldx = k if ldx is None else ldx
+    ldy = k if ldy is None else ldy
+    return lib().spmv_c_spmv_csr_multi_async(A, _dev(d_X), int(ldx), _dev(d_Y), int(ldy), int(k),
+                                             byref(config) if config is not None else None, vec_size,
+                                             c_void_p(stream))
+
+
 def spmv_auto_config(A) -> SpMVConfig:
     out = SpMVConfig()
     status = lib().spmv_c_auto_config(A, byref(out))
@@ -686,6 +710,13 @@ def compute_bandwidth_csr(A, elapsed_ms) -> BandwidthMetrics:
 def compute_bandwidth_ell(A, elapsed_ms) -> BandwidthMetrics:
     out = BandwidthMetrics()
     lib().spmv_c_compute_bandwidth_ell(A, elapsed_ms, byref(out))
+    return out
+
+
+def compute_bandwidth_csr_multi(A, k, elapsed_ms) -> BandwidthMetrics:
+    """Byte model of spmv_csr_multi: nnz*8 + (rows+1)*4 + k*cols*4 + k*rows*4."""
+    out = BandwidthMetrics()
+    lib().spmv_c_compute_bandwidth_csr_multi(A, int(k), elapsed_ms, byref(out))
     return out
 
 

@@ -39,6 +39,7 @@ void release(CsrAux* a) {
         if (c.row) (void)hipFree(c.row);
         if (c.val) (void)hipFree(c.val);
     }
+    release_multi_merge(a);
     a->tiled.reset();        // (users still holding the plan keep it alive)
     delete a;
 }

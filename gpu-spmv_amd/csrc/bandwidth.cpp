@@ -59,6 +59,16 @@ BandwidthMetrics compute_bandwidth_csr(const CSRMatrix* A, float elapsed_ms) {
     return from_bytes(bytes, elapsed_ms);
 }
 
+BandwidthMetrics compute_bandwidth_csr_multi(const CSRMatrix* A, int k, float elapsed_ms) {
+    if (!A || k < 1 || elapsed_ms <= 0.0f) return BandwidthMetrics();
+    const double nnz = A->nnz, rows = A->num_rows, cols = A->num_cols;
+    const double bytes = nnz * (sizeof(float) + sizeof(int))   // values + col_indices, read once for all k
+                       + (rows + 1) * sizeof(int)              // row_ptrs
+                       + k * cols * sizeof(float)              // X, counted once
+                       + k * rows * sizeof(float);             // Y
+    return from_bytes(bytes, elapsed_ms);
+}
+
 BandwidthMetrics compute_bandwidth_ell(const ELLMatrix* A, float elapsed_ms) {
     if (!A || elapsed_ms <= 0.0f) return BandwidthMetrics();
     const double slots = static_cast<double>(A->num_rows) * A->max_nnz_per_row;

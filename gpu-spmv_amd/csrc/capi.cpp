@@ -353,6 +353,18 @@ int spmv_c_spmv_ell_async(const spmv_c_ell* A, const float* d_x, float* d_y,
     return spmv_ell_async(cxx(A), d_x, d_y, cxx(config), vec_size, as_stream(hip_stream));
 }
 
+int spmv_c_spmv_csr_multi(const spmv_c_csr* A, const float* d_X, int ldx, float* d_Y, int ldy, int k,
+                          const spmv_c_config* config, int vec_size, spmv_c_result* out) {
+    const SpMVResult r = spmv_csr_multi(cxx(A), d_X, ldx, d_Y, ldy, k, cxx(config), vec_size);
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
+}
+
+int spmv_c_spmv_csr_multi_async(const spmv_c_csr* A, const float* d_X, int ldx, float* d_Y, int ldy, int k,
+                                const spmv_c_config* config, int vec_size, void* hip_stream) {
+    return spmv_csr_multi_async(cxx(A), d_X, ldx, d_Y, ldy, k, cxx(config), vec_size, as_stream(hip_stream));
+}
+
 // ---- bandwidth ----
 int spmv_c_compute_bandwidth_csr(const spmv_c_csr* A, float elapsed_ms, spmv_c_bandwidth* out) {
     if (!out) return kInvalidArgument;
@@ -367,6 +379,13 @@ int spmv_c_compute_bandwidth_ell(const spmv_c_ell* A, float elapsed_ms, spmv_c_b
     return 0;
 }
 float spmv_c_get_gpu_peak_bandwidth(void) { return get_gpu_peak_bandwidth(); }
+
+int spmv_c_compute_bandwidth_csr_multi(const spmv_c_csr* A, int k, float elapsed_ms, spmv_c_bandwidth* out) {
+    if (!out) return kInvalidArgument;
+    const BandwidthMetrics m = compute_bandwidth_csr_multi(cxx(A), k, elapsed_ms);
+    std::memcpy(out, &m, sizeof(m));
+    return 0;
+}
 
 // ---- PageRank ----
 int spmv_c_pagerank(const spmv_c_csr* adj, const spmv_c_pagerank_config* config,

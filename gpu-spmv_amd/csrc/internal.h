@@ -76,6 +76,20 @@ struct CsrAux {
     bool carry_taken = false;
     hipStream_t carry_stream = nullptr;
     std::vector<MergeCarry> extra_carry;
+    // spmv_csr_multi's merge path (spmm.hip): its own partition and k-wide carry slots, never shared with the
+    // single-vector fields above.  A stream keeps its pair (up to eight streams per matrix; beyond that a call
+    // borrows one from the stream-ordered allocator); a pair grows, after a synchronisation of its stream, when a
+    // call asks for more columns than it holds.
+    int*   d_multi_tile_rows = nullptr;   // [multi_num_tiles + 1]
+    int    multi_num_tiles = 0;
+    struct MultiCarry {
+        hipStream_t stream;
+        int* row;      // [multi_num_tiles]
+        float* val;    // [multi_num_tiles * cap_k]
+        int cap_k;
+    };
+    std::vector<MultiCarry> multi_carry;
+    std::mutex multi_lock;           // guards the multi fields and the tile + fix-up pair of launches
     // LDS-tiled engine: bucketed copy of the entries, built on first use (tiled.h)
     std::shared_ptr<TiledPlan> tiled;
     bool tiled_failed = false;       // build failed once (e.g. out of memory): do not retry
@@ -145,6 +159,16 @@ hipError_t launch_csr_merge(const CSRMatrix* A, CsrAux* aux, const float* d_x, f
                             hipStream_t s);
 hipError_t prepare_csr_merge(const CSRMatrix* A, CsrAux* aux, hipStream_t s);   // the merge tile table, ahead of a timed call
 hipError_t launch_ell(const ELLMatrix* A, const float* d_x, float* d_y, hipStream_t s);
+// multi-vector kernels (spmm.hip): X num_cols x k, Y num_rows x k, row-major, leading dimensions ldx / ldy
+hipError_t launch_csr_multi_zero(const CSRMatrix* A, float* d_Y, int ldy, int k, hipStream_t s);
+hipError_t launch_csr_multi_rows(const CSRMatrix* A, const float* d_X, int ldx, float* d_Y, int ldy, int k,
+                                 hipStream_t s);     // CPU summation order
+hipError_t launch_csr_multi_vector(const CSRMatrix* A, const float* d_X, int ldx, float* d_Y, int ldy, int k,
+                                   hipStream_t s);
+hipError_t launch_csr_multi_merge(const CSRMatrix* A, CsrAux* aux, const float* d_X, int ldx, float* d_Y, int ldy,
+                                  int k, hipStream_t s);
+hipError_t prepare_csr_multi_merge(const CSRMatrix* A, CsrAux* aux, int k, hipStream_t s);  // ahead of a timed call
+void release_multi_merge(CsrAux* aux);
 hipError_t launch_fill_zero(float* d_y, size_t n, hipStream_t s);
 hipError_t launch_ell_from_csr(const CSRMatrix* csr, int width, int* d_ell_cols, float* d_ell_vals,
                                hipStream_t s);

@@ -18,7 +18,9 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cstdint>
 #include <cstdlib>
+#include <utility>
 
 namespace spmv {
 
@@ -130,6 +132,50 @@ void prepare_csr(const CSRMatrix* A, const SpMVConfig* config, hipStream_t strea
     if (config->kernel_type == SpMVConfig::MERGE_PATH) (void)prepare_csr_merge(A, aux_lookup(A->d_row_ptrs, true), stream);
 }
 
+// front half of spmv_csr_multi / spmv_csr_multi_async, checks in the documented order (include/spmv/spmv.h)
+int check_csr_multi(const CSRMatrix* A, const float* d_X, int ldx, const float* d_Y, int ldy, int k, int vec_size,
+                    bool* nothing_to_do) {
+    *nothing_to_do = false;
+    if (!A || !d_X || !d_Y) return code(SpMVError::INVALID_ARGUMENT);
+    if (A->num_rows == 0) {
+        *nothing_to_do = true;
+        return code(SpMVError::SUCCESS);
+    }
+    if (k < 1) return code(SpMVError::INVALID_ARGUMENT);
+    if (vec_size >= 0 && !spmv_validate_dimensions(A->num_cols, vec_size)) {
+        return code(SpMVError::INVALID_DIMENSION);
+    }
+    if (ldx < k || ldy < k) return code(SpMVError::INVALID_DIMENSION);
+    if (!A->d_row_ptrs || (A->nnz > 0 && (!A->d_col_indices || !A->d_values))) {
+        return code(SpMVError::INVALID_FORMAT);
+    }
+    // the bytes a call reads from X and writes to Y (padding columns included between rows): disjoint
+    const auto span = [k](const float* base, long long rows, long long ld) {
+        const uintptr_t lo = reinterpret_cast<uintptr_t>(base);
+        const uintptr_t bytes = rows > 0 ? static_cast<uintptr_t>(((rows - 1) * ld + k) * sizeof(float)) : 0;
+        return std::make_pair(lo, lo + bytes);
+    };
+    const auto x = span(d_X, A->num_cols, ldx);
+    const auto y = span(d_Y, A->num_rows, ldy);
+    if (x.first < x.second && x.first < y.second && y.first < x.second) return code(SpMVError::INVALID_ARGUMENT);
+    return code(SpMVError::SUCCESS);
+}
+
+// Multi calls never look at the tiled plan or the promotion count: use_texture is ignored here.
+hipError_t enqueue_csr_multi(const CSRMatrix* A, const float* d_X, int ldx, float* d_Y, int ldy, int k,
+                             const SpMVConfig* config, hipStream_t stream) {
+    if (A->nnz == 0) return launch_csr_multi_zero(A, d_Y, ldy, k, stream);
+    switch (config->kernel_type) {
+        case SpMVConfig::VECTOR_CSR:
+            return launch_csr_multi_vector(A, d_X, ldx, d_Y, ldy, k, stream);
+        case SpMVConfig::MERGE_PATH:
+            return launch_csr_multi_merge(A, aux_lookup(A->d_row_ptrs, true), d_X, ldx, d_Y, ldy, k, stream);
+        case SpMVConfig::SCALAR_CSR:
+        default:
+            return launch_csr_multi_rows(A, d_X, ldx, d_Y, ldy, k, stream);
+    }
+}
+
 int check_ell(const ELLMatrix* A, const float* d_x, float* d_y, int vec_size, bool* nothing_to_do) {
     *nothing_to_do = false;
     if (!A || !d_x || !d_y) return code(SpMVError::INVALID_ARGUMENT);
@@ -233,6 +279,55 @@ int spmv_csr_async(const CSRMatrix* A, const float* d_x, float* d_y,
     if (!config) config = &fallback;
     if (!detail::block_size_ok(config)) return detail::code(SpMVError::KERNEL_LAUNCH);
     return detail::enqueue_csr(A, d_x, d_y, config, stream) == hipSuccess
+         ? detail::code(SpMVError::SUCCESS) : detail::code(SpMVError::KERNEL_LAUNCH);
+}
+
+SpMVResult spmv_csr_multi(const CSRMatrix* A, const float* d_X, int ldx, float* d_Y, int ldy, int k,
+                          const SpMVConfig* config, int vec_size) {
+    SpMVResult result;
+    bool nothing = false;
+    result.error_code = detail::check_csr_multi(A, d_X, ldx, d_Y, ldy, k, vec_size, &nothing);
+    if (result.error_code != 0) return result;
+    if (nothing) {
+        result.y = d_Y;
+        return result;
+    }
+
+    const SpMVConfig fallback;
+    if (!config) config = &fallback;
+    if (!detail::block_size_ok(config)) {
+        result.error_code = detail::code(SpMVError::KERNEL_LAUNCH);
+        return result;
+    }
+
+    const detail::TraceRange range("spmv:spmv_csr_multi");
+    hipStream_t stream = detail::current_stream();
+    // the merge-path partition and this stream's k-wide carry slots, before the start event (as in spmv_csr)
+    if (A->nnz > 0 && config->kernel_type == SpMVConfig::MERGE_PATH) {
+        (void)detail::prepare_csr_multi_merge(A, detail::aux_lookup(A->d_row_ptrs, true), k, stream);
+    }
+    result.error_code = detail::timed(stream, &result.elapsed_ms, [&] {
+        return detail::enqueue_csr_multi(A, d_X, ldx, d_Y, ldy, k, config, stream);
+    });
+    if (result.error_code != 0) return result;
+
+    if (result.elapsed_ms > 0.0f) {
+        result.gflops = static_cast<float>(2.0 * A->nnz * k / (result.elapsed_ms * 1e6));
+    }
+    result.bandwidth_gb_s = compute_bandwidth_csr_multi(A, k, result.elapsed_ms).achieved_bandwidth_gb_s;
+    result.y = d_Y;
+    return result;
+}
+
+int spmv_csr_multi_async(const CSRMatrix* A, const float* d_X, int ldx, float* d_Y, int ldy, int k,
+                         const SpMVConfig* config, int vec_size, hipStream_t stream) {
+    bool nothing = false;
+    const int status = detail::check_csr_multi(A, d_X, ldx, d_Y, ldy, k, vec_size, &nothing);
+    if (status != 0 || nothing) return status;
+    const SpMVConfig fallback;
+    if (!config) config = &fallback;
+    if (!detail::block_size_ok(config)) return detail::code(SpMVError::KERNEL_LAUNCH);
+    return detail::enqueue_csr_multi(A, d_X, ldx, d_Y, ldy, k, config, stream) == hipSuccess
          ? detail::code(SpMVError::SUCCESS) : detail::code(SpMVError::KERNEL_LAUNCH);
 }
 

@@ -72,6 +72,26 @@ int spmv_csr_async(const CSRMatrix* A, const float* d_x, float* d_y,
 int spmv_ell_async(const ELLMatrix* A, const float* d_x, float* d_y,
                    const SpMVConfig* config, int vec_size, hipStream_t stream);
 
+// Multi-vector SpMV (csrmm / SpMM): Y = A * X for k right-hand sides in one pass over the matrix.
+// Y[i*ldy + j] = sum_p A(i,p) * X[p*ldx + j] for 0 <= i < num_rows, 0 <= j < k.
+// X is num_cols x k, Y is num_rows x k, both row-major with leading dimensions ldx, ldy >= k (device pointers).
+// Y's columns k..ldy-1 are never written.  Offsets into X and Y are 64-bit (num_cols*ldx, num_rows*ldy may
+// exceed 2^31).  Checks, in this order: null A / d_X / d_Y -> INVALID_ARGUMENT; num_rows == 0 -> SUCCESS, nothing
+// written; k < 1 -> INVALID_ARGUMENT; vec_size >= 0 && vec_size != num_cols -> INVALID_DIMENSION; ldx < k or ldy < k
+// -> INVALID_DIMENSION; missing device arrays -> INVALID_FORMAT; the used ranges of X and Y overlap ->
+// INVALID_ARGUMENT; a bad block_size -> as spmv_csr.  nnz == 0 writes zeros to Y[i, 0:k].
+// Kernels: SCALAR_CSR (also config == nullptr and ELL_KERNEL) gives columns bit-identical to spmv_cpu_csr(A, X[:, j]);
+// VECTOR_CSR and MERGE_PATH may reorder a row's sum.  Every kernel type is bitwise reproducible from run to run.
+// use_texture is accepted and ignored: multi calls never build or use the LDS-tiled plan and never count toward
+// promotion.  elapsed_ms is device-event time, gflops = 2*nnz*k / time, bandwidth_gb_s from
+// compute_bandwidth_csr_multi; one-time preparation (MERGE_PATH's partition and carry slots) happens before the
+// start event.  The async variant follows spmv_csr_async's stream rules; a MERGE_PATH call that needs more carry
+// columns than its stream holds synchronises that stream once to grow them — do that one outside a graph capture.
+SpMVResult spmv_csr_multi(const CSRMatrix* A, const float* d_X, int ldx, float* d_Y, int ldy, int k,
+                          const SpMVConfig* config, int vec_size = -1);
+int spmv_csr_multi_async(const CSRMatrix* A, const float* d_X, int ldx, float* d_Y, int ldy, int k,
+                         const SpMVConfig* config, int vec_size, hipStream_t stream);
+
 // Promotion of callers that spell a reordering kernel without use_texture (the reference's own callers do:
 // benchmarks/main.cu:52-56, src/pagerank.cu:89-90): after `calls` spmv_csr() calls with VECTOR_CSR / MERGE_PATH on a
 // matrix the LDS-tiled engine would take (> 32768 columns, >= 1 M entries), the next call builds the matrix's plan in

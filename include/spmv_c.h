@@ -219,10 +219,19 @@ int spmv_c_spmv_csr_async(const spmv_c_csr* A, const float* d_x, float* d_y,
                           const spmv_c_config* config, int vec_size, void* hip_stream);
 int spmv_c_spmv_ell_async(const spmv_c_ell* A, const float* d_x, float* d_y,
                           const spmv_c_config* config, int vec_size, void* hip_stream);
+/* extension (spmv::spmv_csr_multi, include/spmv/spmv.h): Y = A * X for k right-hand sides in one matrix pass;
+ * X is num_cols x k, Y num_rows x k, row-major with leading dimensions ldx, ldy >= k; columns k..ldy-1 of Y are
+ * never written.  The return value equals out->error_code (out may be NULL). */
+int spmv_c_spmv_csr_multi(const spmv_c_csr* A, const float* d_X, int ldx, float* d_Y, int ldy, int k,
+                          const spmv_c_config* config, int vec_size, spmv_c_result* out);
+int spmv_c_spmv_csr_multi_async(const spmv_c_csr* A, const float* d_X, int ldx, float* d_Y, int ldy, int k,
+                                const spmv_c_config* config, int vec_size, void* hip_stream);
 
 /* ---- bandwidth model: reference include/spmv/bandwidth.h:21-27 ---- */
 int spmv_c_compute_bandwidth_csr(const spmv_c_csr* A, float elapsed_ms, spmv_c_bandwidth* out);
 int spmv_c_compute_bandwidth_ell(const spmv_c_ell* A, float elapsed_ms, spmv_c_bandwidth* out);
+/* extension: the byte model of spmv_c_spmv_csr_multi, nnz*8 + (rows+1)*4 + k*cols*4 + k*rows*4 */
+int spmv_c_compute_bandwidth_csr_multi(const spmv_c_csr* A, int k, float elapsed_ms, spmv_c_bandwidth* out);
 float spmv_c_get_gpu_peak_bandwidth(void);
 
 /* ---- PageRank: reference include/spmv/pagerank.h:29-43 ---- */
