@@ -165,6 +165,7 @@ _SIGNATURES = {
     "spmv_c_ell_from_dense": (c_int, [POINTER(ELLMatrix), c_void_p, c_int, c_int]),
     "spmv_c_ell_from_csr": (c_int, [POINTER(ELLMatrix), POINTER(CSRMatrix)]),
     "spmv_c_ell_from_csr_gpu": (c_int, [POINTER(ELLMatrix), POINTER(CSRMatrix)]),
+    "spmv_c_csr_transpose_gpu": (c_int, [POINTER(CSRMatrix), POINTER(CSRMatrix)]),
     "spmv_c_ell_to_dense": (c_int, [POINTER(ELLMatrix), c_void_p]),
     "spmv_c_ell_get_element": (c_float, [POINTER(ELLMatrix), c_int, c_int]),
     "spmv_c_ell_to_gpu": (c_int, [POINTER(ELLMatrix)]),
@@ -199,6 +200,10 @@ _SIGNATURES = {
                                       POINTER(SpMVConfig), c_int, POINTER(SpMVResult)]),
     "spmv_c_spmv_csr_multi_async": (c_int, [POINTER(CSRMatrix), c_void_p, c_int, c_void_p, c_int, c_int,
                                             POINTER(SpMVConfig), c_int, c_void_p]),
+    "spmv_c_spmv_csr_transpose": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(SpMVConfig), c_int,
+                                          POINTER(SpMVResult)]),
+    "spmv_c_spmv_csr_transpose_async": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(SpMVConfig), c_int,
+                                                c_void_p]),
     "spmv_c_compute_bandwidth_csr": (c_int, [POINTER(CSRMatrix), c_float, POINTER(BandwidthMetrics)]),
     "spmv_c_compute_bandwidth_csr_multi": (c_int, [POINTER(CSRMatrix), c_int, c_float, POINTER(BandwidthMetrics)]),
     "spmv_c_compute_bandwidth_ell": (c_int, [POINTER(ELLMatrix), c_float, POINTER(BandwidthMetrics)]),
@@ -513,6 +518,12 @@ def ell_from_csr(ell, csr) -> int:
     return lib().spmv_c_ell_from_csr(ell, csr)
 
 
+def csr_transpose_gpu(AT, A) -> int:
+    """Extension: AT = A^T built on the device, deterministic (csr_matrix.h csr_transpose_gpu); csr_from_gpu(AT)
+    fills AT's host arrays."""
+    return lib().spmv_c_csr_transpose_gpu(AT, A)
+
+
 def ell_from_csr_gpu(ell, csr) -> int:
     """Extension: CSR -> ELL on the device (device slabs only; ell_from_gpu mirrors them to the host)."""
     return lib().spmv_c_ell_from_csr_gpu(ell, csr)
@@ -686,6 +697,21 @@ def spmv_csr_multi_async(A, d_X, d_Y, k, ldx=None, ldy=None, config=None, vec_si
     return lib().spmv_c_spmv_csr_multi_async(A, _dev(d_X), int(ldx), _dev(d_Y), int(ldy), int(k),
                                              byref(config) if config is not None else None, vec_size,
                                              c_void_p(stream))
+
+
+def spmv_csr_transpose(A, d_x, d_y, config=None, vec_size=-1) -> SpMVResult:
+    """y = A^T * x (include/spmv/spmv.h spmv_csr_transpose): d_x has num_rows entries, d_y num_cols; the first call
+    on a matrix builds and caches its device transpose."""
+    out = SpMVResult()
+    lib().spmv_c_spmv_csr_transpose(A, _dev(d_x), _dev(d_y), byref(config) if config is not None else None,
+                                    vec_size, byref(out))
+    return out
+
+
+def spmv_csr_transpose_async(A, d_x, d_y, config=None, vec_size=-1, stream=None) -> int:
+    return lib().spmv_c_spmv_csr_transpose_async(A, _dev(d_x), _dev(d_y),
+                                                 byref(config) if config is not None else None, vec_size,
+                                                 c_void_p(stream))
 
 
 def spmv_auto_config(A) -> SpMVConfig:

@@ -219,6 +219,7 @@ int spmv_c_ell_from_dense(spmv_c_ell* ell, const float* dense, int rows, int col
 }
 int spmv_c_ell_from_csr(spmv_c_ell* ell, const spmv_c_csr* csr) { return ell_from_csr(cxx(ell), cxx(csr)); }
 int spmv_c_ell_from_csr_gpu(spmv_c_ell* ell, const spmv_c_csr* csr) { return ell_from_csr_gpu(cxx(ell), cxx(csr)); }
+int spmv_c_csr_transpose_gpu(spmv_c_csr* AT, const spmv_c_csr* A) { return csr_transpose_gpu(cxx(AT), cxx(A)); }
 int spmv_c_ell_to_dense(const spmv_c_ell* ell, float* dense) { return ell_to_dense(cxx(ell), dense); }
 float spmv_c_ell_get_element(const spmv_c_ell* mat, int row, int col) {
     return ell_get_element(cxx(mat), row, col);
@@ -363,6 +364,18 @@ int spmv_c_spmv_csr_multi(const spmv_c_csr* A, const float* d_X, int ldx, float*
 int spmv_c_spmv_csr_multi_async(const spmv_c_csr* A, const float* d_X, int ldx, float* d_Y, int ldy, int k,
                                 const spmv_c_config* config, int vec_size, void* hip_stream) {
     return spmv_csr_multi_async(cxx(A), d_X, ldx, d_Y, ldy, k, cxx(config), vec_size, as_stream(hip_stream));
+}
+
+int spmv_c_spmv_csr_transpose(const spmv_c_csr* A, const float* d_x, float* d_y,
+                              const spmv_c_config* config, int vec_size, spmv_c_result* out) {
+    const SpMVResult r = spmv_csr_transpose(cxx(A), d_x, d_y, cxx(config), vec_size);
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
+}
+
+int spmv_c_spmv_csr_transpose_async(const spmv_c_csr* A, const float* d_x, float* d_y,
+                                    const spmv_c_config* config, int vec_size, void* hip_stream) {
+    return spmv_csr_transpose_async(cxx(A), d_x, d_y, cxx(config), vec_size, as_stream(hip_stream));
 }
 
 // ---- bandwidth ----

@@ -198,6 +198,31 @@ void csr_invalidate_gpu_cache(const CSRMatrix* mat) {
     if (mat && mat->d_row_ptrs) detail::aux_drop(mat->d_row_ptrs);
 }
 
+// Extension: AT = A^T built on the device from A's device arrays (transpose.hip).  AT ends up as
+// ell_from_csr_gpu leaves its output: it owns fresh device arrays, and host arrays of the right size that
+// csr_from_gpu fills (they hold no data before).  AT may be A itself.
+int csr_transpose_gpu(CSRMatrix* AT, const CSRMatrix* A) {
+    if (!AT || !A) return detail::code(SpMVError::INVALID_ARGUMENT);
+    detail::TransposeArrays t;
+    const int status = detail::transpose_build(A, &t, detail::current_stream());
+    if (status != 0) return status;
+    const int rows = A->num_cols, cols = A->num_rows, nnz = A->nnz;     // (read before AT, maybe A, changes)
+    csr_free_gpu(AT);
+    release_host(AT);
+    AT->num_rows = rows;
+    AT->num_cols = cols;
+    AT->nnz = nnz;
+    AT->values = nnz > 0 ? new float[nnz] : nullptr;
+    AT->col_indices = nnz > 0 ? new int[nnz] : nullptr;
+    AT->row_ptrs = new int[static_cast<size_t>(rows) + 1];
+    AT->owns_host_memory = true;
+    AT->d_row_ptrs = t.row_ptrs;
+    AT->d_col_indices = t.col_indices;
+    AT->d_values = t.values;
+    AT->owns_device_memory = true;
+    return detail::code(SpMVError::SUCCESS);
+}
+
 int csr_serialize(const CSRMatrix* mat, const char* filename) {
     if (!mat || !filename) return detail::code(SpMVError::INVALID_ARGUMENT);
 

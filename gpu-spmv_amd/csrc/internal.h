@@ -54,6 +54,14 @@ struct PrWorkspace {
     void release();
 };
 
+// device arrays of a transpose built by transpose_build (transpose.hip); hipMalloc-owned
+struct TransposeArrays {
+    int*   row_ptrs = nullptr;      // [num_cols + 1] of the source
+    int*   col_indices = nullptr;   // [nnz]
+    float* values = nullptr;        // [nnz]
+    void release();
+};
+
 struct CsrAux {
     PrWorkspace pagerank;
     // row-length statistics computed once (host scan or device reduction)
@@ -90,6 +98,16 @@ struct CsrAux {
     };
     std::vector<MultiCarry> multi_carry;
     std::mutex multi_lock;           // guards the multi fields and the tile + fix-up pair of launches
+    // spmv_csr_transpose: the matrix's device transpose, built on first use, and what it was built from (two
+    // matrices may share one row-pointer array, and a handle's column / value arrays may be swapped under it).
+    // The transpose is a matrix of its own: its merge partition, tiled plan and promotion count live in ITS aux
+    // entry, dropped with it (the deleter is csr_free_gpu).
+    std::mutex transpose_lock;       // one build per matrix when threads race on the first call
+    std::shared_ptr<CSRMatrix> transpose;
+    const void* transpose_cols = nullptr;
+    const void* transpose_vals = nullptr;
+    long long transpose_nnz = 0;
+    int transpose_rows = 0, transpose_num_cols = 0;
     // LDS-tiled engine: bucketed copy of the entries, built on first use (tiled.h)
     std::shared_ptr<TiledPlan> tiled;
     bool tiled_failed = false;       // build failed once (e.g. out of memory): do not retry
@@ -170,6 +188,9 @@ hipError_t launch_csr_multi_merge(const CSRMatrix* A, CsrAux* aux, const float* 
 hipError_t prepare_csr_multi_merge(const CSRMatrix* A, CsrAux* aux, int k, hipStream_t s);  // ahead of a timed call
 void release_multi_merge(CsrAux* aux);
 hipError_t launch_fill_zero(float* d_y, size_t n, hipStream_t s);
+// device transpose (transpose.hip): validates A (INVALID_FORMAT before anything is allocated), then builds A^T on
+// `s` and returns after the build completed, its scratch freed.  The caller owns *out on SUCCESS.
+int transpose_build(const CSRMatrix* A, TransposeArrays* out, hipStream_t s);
 hipError_t launch_ell_from_csr(const CSRMatrix* csr, int width, int* d_ell_cols, float* d_ell_vals,
                                hipStream_t s);
 hipError_t device_count_ell_nnz(const ELLMatrix* A, long long* out, hipStream_t s);

@@ -20,6 +20,8 @@
 #include <atomic>
 #include <cstdint>
 #include <cstdlib>
+#include <memory>
+#include <mutex>
 #include <utility>
 
 namespace spmv {
@@ -176,6 +178,62 @@ hipError_t enqueue_csr_multi(const CSRMatrix* A, const float* d_X, int ldx, floa
     }
 }
 
+// front half of spmv_csr_transpose / spmv_csr_transpose_async, checks in the documented order (include/spmv/spmv.h)
+int check_csr_transpose(const CSRMatrix* A, const float* d_x, const float* d_y, int vec_size, bool* nothing_to_do) {
+    *nothing_to_do = false;
+    if (!A || !d_x || !d_y) return code(SpMVError::INVALID_ARGUMENT);
+    if (A->num_cols == 0) {
+        *nothing_to_do = true;
+        return code(SpMVError::SUCCESS);
+    }
+    if (vec_size >= 0 && !spmv_validate_dimensions(A->num_rows, vec_size)) {
+        return code(SpMVError::INVALID_DIMENSION);
+    }
+    if (A->num_rows < 0 || A->num_cols < 0 || A->nnz < 0 ||
+        (A->num_rows > 0 && (!A->d_row_ptrs || (A->nnz > 0 && (!A->d_col_indices || !A->d_values))))) {
+        return code(SpMVError::INVALID_FORMAT);
+    }
+    return code(SpMVError::SUCCESS);
+}
+
+// A's device transpose from A's aux entry: built on the first call and again when A's arrays or shape no longer
+// match what it was built from.  Null when there is nothing to transpose (no rows or no entries: y = 0).
+int transpose_for(const CSRMatrix* A, hipStream_t stream, std::shared_ptr<CSRMatrix>* out) {
+    out->reset();
+    if (A->num_rows == 0 || A->nnz == 0) return code(SpMVError::SUCCESS);
+    CsrAux* aux = aux_lookup(A->d_row_ptrs, true);
+    std::lock_guard<std::mutex> guard(aux->transpose_lock);
+    if (aux->transpose && aux->transpose_cols == A->d_col_indices && aux->transpose_vals == A->d_values &&
+        aux->transpose_nnz == A->nnz && aux->transpose_rows == A->num_rows && aux->transpose_num_cols == A->num_cols) {
+        *out = aux->transpose;
+        return code(SpMVError::SUCCESS);
+    }
+    aux->transpose.reset();
+    const TraceRange range("spmv:transpose_build");
+    TransposeArrays t;
+    const int status = transpose_build(A, &t, stream);
+    if (status != 0) return status;
+    CSRMatrix* at = new CSRMatrix{};
+    at->num_rows = A->num_cols;
+    at->num_cols = A->num_rows;
+    at->nnz = A->nnz;
+    at->d_row_ptrs = t.row_ptrs;
+    at->d_col_indices = t.col_indices;
+    at->d_values = t.values;
+    at->owns_device_memory = true;
+    aux->transpose = std::shared_ptr<CSRMatrix>(at, [](CSRMatrix* m) {
+        csr_free_gpu(m);        // (drops the transpose's own aux entry: merge partition, tiled plan)
+        delete m;
+    });
+    aux->transpose_cols = A->d_col_indices;
+    aux->transpose_vals = A->d_values;
+    aux->transpose_nnz = A->nnz;
+    aux->transpose_rows = A->num_rows;
+    aux->transpose_num_cols = A->num_cols;
+    *out = aux->transpose;
+    return code(SpMVError::SUCCESS);
+}
+
 int check_ell(const ELLMatrix* A, const float* d_x, float* d_y, int vec_size, bool* nothing_to_do) {
     *nothing_to_do = false;
     if (!A || !d_x || !d_y) return code(SpMVError::INVALID_ARGUMENT);
@@ -329,6 +387,65 @@ int spmv_csr_multi_async(const CSRMatrix* A, const float* d_X, int ldx, float* d
     if (!detail::block_size_ok(config)) return detail::code(SpMVError::KERNEL_LAUNCH);
     return detail::enqueue_csr_multi(A, d_X, ldx, d_Y, ldy, k, config, stream) == hipSuccess
          ? detail::code(SpMVError::SUCCESS) : detail::code(SpMVError::KERNEL_LAUNCH);
+}
+
+SpMVResult spmv_csr_transpose(const CSRMatrix* A, const float* d_x, float* d_y,
+                              const SpMVConfig* config, int vec_size) {
+    SpMVResult result;
+    bool nothing = false;
+    result.error_code = detail::check_csr_transpose(A, d_x, d_y, vec_size, &nothing);
+    if (result.error_code != 0) return result;
+    if (nothing) {
+        result.y = d_y;
+        return result;
+    }
+
+    const SpMVConfig fallback;
+    if (!config) config = &fallback;
+    if (!detail::block_size_ok(config)) {
+        result.error_code = detail::code(SpMVError::KERNEL_LAUNCH);
+        return result;
+    }
+
+    const detail::TraceRange range("spmv:spmv_csr_transpose");
+    hipStream_t stream = detail::current_stream();
+    // the transpose and what spmv_csr would prepare for it, before the start event
+    std::shared_ptr<CSRMatrix> AT;
+    result.error_code = detail::transpose_for(A, stream, &AT);
+    if (result.error_code != 0) return result;
+    if (AT) detail::prepare_csr(AT.get(), config, stream);
+    result.error_code = detail::timed(stream, &result.elapsed_ms, [&] {
+        return AT ? detail::enqueue_csr(AT.get(), d_x, d_y, config, stream)
+                  : detail::launch_fill_zero(d_y, A->num_cols, stream);
+    });
+    if (result.error_code != 0) return result;
+
+    if (result.elapsed_ms > 0.0f) {
+        result.gflops = (2.0f * A->nnz) / (result.elapsed_ms * 1e6f);
+    }
+    CSRMatrix shape{};                  // the byte model of spmv_csr on the transpose
+    shape.num_rows = A->num_cols;
+    shape.num_cols = A->num_rows;
+    shape.nnz = A->nnz;
+    result.bandwidth_gb_s = compute_bandwidth_csr(&shape, result.elapsed_ms).achieved_bandwidth_gb_s;
+    result.y = d_y;
+    return result;
+}
+
+int spmv_csr_transpose_async(const CSRMatrix* A, const float* d_x, float* d_y,
+                             const SpMVConfig* config, int vec_size, hipStream_t stream) {
+    bool nothing = false;
+    int status = detail::check_csr_transpose(A, d_x, d_y, vec_size, &nothing);
+    if (status != 0 || nothing) return status;
+    const SpMVConfig fallback;
+    if (!config) config = &fallback;
+    if (!detail::block_size_ok(config)) return detail::code(SpMVError::KERNEL_LAUNCH);
+    std::shared_ptr<CSRMatrix> AT;
+    status = detail::transpose_for(A, stream, &AT);
+    if (status != 0) return status;
+    const hipError_t e = AT ? detail::enqueue_csr(AT.get(), d_x, d_y, config, stream)
+                            : detail::launch_fill_zero(d_y, A->num_cols, stream);
+    return e == hipSuccess ? detail::code(SpMVError::SUCCESS) : detail::code(SpMVError::KERNEL_LAUNCH);
 }
 
 SpMVResult spmv_ell(const ELLMatrix* A, const float* d_x, float* d_y,

@@ -47,6 +47,18 @@ void csr_free_gpu(CSRMatrix* mat);
 // freed or re-uploaded.  After writing into d_values / d_col_indices / d_row_ptrs IN PLACE, call this
 // so that the next call rebuilds it.
 void csr_invalidate_gpu_cache(const CSRMatrix* mat);
+// extension: AT = A^T built on the device from A's device arrays (no host pass, no PCIe), deterministic: row c of
+// AT holds A's entries of column c in ascending source position, each with its row in A as column index and its
+// value bit for bit (-0.0, NaN payloads, explicit zeros and duplicates kept); row_ptrs[c] = entries with column < c.
+// A's rows need not be sorted.  AT ends up as ell_from_csr_gpu leaves its output: AT owns its device arrays; its host
+// arrays are allocated at the new size and hold no data until csr_from_gpu(AT).  AT may be A.
+// Checks: null AT or A -> INVALID_ARGUMENT; missing device arrays (num_rows > 0 and no d_row_ptrs, or nnz > 0 and
+// no d_col_indices / d_values) -> INVALID_FORMAT; then ONE device pass checks row_ptrs[0] == 0, row_ptrs
+// non-decreasing, row_ptrs[rows] == nnz and every column in [0, num_cols) -> INVALID_FORMAT, before AT's arrays or
+// any scratch are allocated (AT is left untouched); allocation failure -> CUDA_MALLOC (nothing leaked).
+// Runs on the library stream (spmv_set_stream) and returns after the build completed; its scratch (about
+// 16 B per entry) is freed before it returns.
+int csr_transpose_gpu(CSRMatrix* AT, const CSRMatrix* A);
 
 // File layout: int32 rows, cols, nnz; float[nnz]; int32[nnz]; int32[rows+1] (native endian).
 int csr_serialize(const CSRMatrix* mat, const char* filename);

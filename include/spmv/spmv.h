@@ -92,6 +92,27 @@ SpMVResult spmv_csr_multi(const CSRMatrix* A, const float* d_X, int ldx, float* 
 int spmv_csr_multi_async(const CSRMatrix* A, const float* d_X, int ldx, float* d_Y, int ldy, int k,
                          const SpMVConfig* config, int vec_size, hipStream_t stream);
 
+// Transposed SpMV: y = A^T * x, i.e. y[c] = sum_r A(r,c) * x[r]; d_x holds num_rows entries, d_y num_cols.
+// The first call on a matrix builds its device transpose (csr_transpose_gpu's result, before the start event) and
+// keeps it with the matrix, next to the other per-matrix data; every call then runs spmv_csr's kernels on it with the
+// caller's config (SCALAR_CSR / nullptr / ELL_KERNEL: CPU order, bit-identical to spmv_cpu_csr on the host
+// transpose, i.e. to the fp32 loop y[col[p]] += val[p] * x[row(p)] in p order; VECTOR_CSR, MERGE_PATH and
+// use_texture as spmv_csr on the transpose).  Every kernel type gives exactly the bits of
+// spmv_csr(csr_transpose_gpu(A), ...) with the same config.  Promotion counts on the transpose, never on A; a
+// transpose call leaves A's own plan, merge-path state and promotion count alone.
+// Checks, in this order: null A / d_x / d_y -> INVALID_ARGUMENT; num_cols == 0 -> SUCCESS, nothing written;
+// vec_size >= 0 && vec_size != num_rows -> INVALID_DIMENSION; missing device arrays -> INVALID_FORMAT; a bad
+// block_size -> as spmv_csr; then the build's own errors (csr_transpose_gpu).  num_rows == 0 or nnz == 0 writes
+// zeros to y[0:num_cols].  elapsed_ms times the SpMV only; gflops = 2*nnz / time; bandwidth_gb_s is
+// compute_bandwidth_csr of the transpose.  The cached transpose is a COPY: after writing into A's device arrays in
+// place call csr_invalidate_gpu_cache(A) (the same rule as for the tiled plan); swapped arrays, a re-upload and
+// csr_free_gpu are noticed on their own.  The async variant follows spmv_csr_async's rules; the call that builds
+// the transpose synchronises its stream — make that one outside a graph capture.
+SpMVResult spmv_csr_transpose(const CSRMatrix* A, const float* d_x, float* d_y,
+                              const SpMVConfig* config, int vec_size = -1);
+int spmv_csr_transpose_async(const CSRMatrix* A, const float* d_x, float* d_y,
+                             const SpMVConfig* config, int vec_size, hipStream_t stream);
+
 // Promotion of callers that spell a reordering kernel without use_texture (the reference's own callers do:
 // benchmarks/main.cu:52-56, src/pagerank.cu:89-90): after `calls` spmv_csr() calls with VECTOR_CSR / MERGE_PATH on a
 // matrix the LDS-tiled engine would take (> 32768 columns, >= 1 M entries), the next call builds the matrix's plan in

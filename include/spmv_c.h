@@ -166,6 +166,8 @@ int spmv_c_ell_from_dense(spmv_c_ell* ell, const float* dense, int rows, int col
 int spmv_c_ell_from_csr(spmv_c_ell* ell, const spmv_c_csr* csr);
 /* extension (device-side conversion, no host pass): see ell_from_csr_gpu in spmv/ell_matrix.h */
 int spmv_c_ell_from_csr_gpu(spmv_c_ell* ell, const spmv_c_csr* csr);
+/* extension (device-side transpose, deterministic): see csr_transpose_gpu in spmv/csr_matrix.h */
+int spmv_c_csr_transpose_gpu(spmv_c_csr* AT, const spmv_c_csr* A);
 int spmv_c_ell_to_dense(const spmv_c_ell* ell, float* dense);
 float spmv_c_ell_get_element(const spmv_c_ell* mat, int row, int col);
 int spmv_c_ell_to_gpu(spmv_c_ell* mat);
@@ -226,6 +228,13 @@ int spmv_c_spmv_csr_multi(const spmv_c_csr* A, const float* d_X, int ldx, float*
                           const spmv_c_config* config, int vec_size, spmv_c_result* out);
 int spmv_c_spmv_csr_multi_async(const spmv_c_csr* A, const float* d_X, int ldx, float* d_Y, int ldy, int k,
                                 const spmv_c_config* config, int vec_size, void* hip_stream);
+
+/* extension (spmv::spmv_csr_transpose, include/spmv/spmv.h): y = A^T * x; d_x has num_rows entries, d_y num_cols.
+ * The first call on a matrix builds and caches its device transpose.  The return value equals out->error_code. */
+int spmv_c_spmv_csr_transpose(const spmv_c_csr* A, const float* d_x, float* d_y,
+                              const spmv_c_config* config, int vec_size, spmv_c_result* out);
+int spmv_c_spmv_csr_transpose_async(const spmv_c_csr* A, const float* d_x, float* d_y,
+                                    const spmv_c_config* config, int vec_size, void* hip_stream);
 
 /* ---- bandwidth model: reference include/spmv/bandwidth.h:21-27 ---- */
 int spmv_c_compute_bandwidth_csr(const spmv_c_csr* A, float elapsed_ms, spmv_c_bandwidth* out);
