@@ -117,6 +117,22 @@ class PrStatus(Structure):
                 ("converged", c_int32), ("done", c_int32), ("reserved", c_int32)]
 
 
+class CGConfig(Structure):
+    """include/spmv/cg.h CGConfig (16 bytes): preconditioner 0 NONE / 1 JACOBI; engine -1 auto, 0 direct, 1 tiled"""
+    _fields_ = [("tolerance", c_float), ("max_iterations", c_int32), ("preconditioner", c_int32),
+                ("engine", c_int32)]
+    NONE, JACOBI = 0, 1
+
+    def __init__(self, tolerance=1e-6, max_iterations=1000, preconditioner=1, engine=-1):
+        super().__init__(tolerance, max_iterations, preconditioner, engine)
+
+
+class CGResult(Structure):
+    """include/spmv/cg.h CGResult (24 bytes)"""
+    _fields_ = [("error_code", c_int32), ("iterations", c_int32), ("relative_residual", c_float),
+                ("converged", c_int32), ("breakdown", c_int32), ("elapsed_ms", c_float)]
+
+
 class PageRankResult:
     """reference include/spmv/pagerank.h:18-25; `ranks` is a numpy copy (the C buffer is freed)."""
 
@@ -204,6 +220,7 @@ _SIGNATURES = {
                                           POINTER(SpMVResult)]),
     "spmv_c_spmv_csr_transpose_async": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(SpMVConfig), c_int,
                                                 c_void_p]),
+    "spmv_c_cg_solve": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(CGConfig), POINTER(CGResult)]),
     "spmv_c_compute_bandwidth_csr": (c_int, [POINTER(CSRMatrix), c_float, POINTER(BandwidthMetrics)]),
     "spmv_c_compute_bandwidth_csr_multi": (c_int, [POINTER(CSRMatrix), c_int, c_float, POINTER(BandwidthMetrics)]),
     "spmv_c_compute_bandwidth_ell": (c_int, [POINTER(ELLMatrix), c_float, POINTER(BandwidthMetrics)]),
@@ -712,6 +729,14 @@ def spmv_csr_transpose_async(A, d_x, d_y, config=None, vec_size=-1, stream=None)
     return lib().spmv_c_spmv_csr_transpose_async(A, _dev(d_x), _dev(d_y),
                                                  byref(config) if config is not None else None, vec_size,
                                                  c_void_p(stream))
+
+
+def cg_solve(A, d_b, d_x, config=None) -> CGResult:
+    """Preconditioned CG for A x = b on the device (include/spmv/cg.h cg_solve): d_b and d_x hold num_rows floats,
+    d_x is the initial guess on entry and the solution on exit."""
+    out = CGResult()
+    lib().spmv_c_cg_solve(A, _dev(d_b), _dev(d_x), byref(config) if config is not None else None, byref(out))
+    return out
 
 
 def spmv_auto_config(A) -> SpMVConfig:

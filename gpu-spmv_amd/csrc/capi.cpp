@@ -5,6 +5,7 @@
 #include "pagerank_engine.h"
 #include "tiled.h"
 #include "spmv/bandwidth.h"
+#include "spmv/cg.h"
 #include "spmv/pagerank.h"
 #include "spmv_c.h"
 
@@ -33,6 +34,16 @@ static_assert(sizeof(spmv_c_pagerank_result) == sizeof(PageRankResult) && sizeof
 static_assert(offsetof(spmv_c_pagerank_result, converged) == offsetof(PageRankResult, converged), "PageRankResult layout");
 static_assert(sizeof(spmv_c_topk_node) == sizeof(TopKNode) && sizeof(TopKNode) == 8, "TopKNode layout");
 static_assert(sizeof(spmv_c_pr_status) == sizeof(detail::PrState), "PrState layout");
+static_assert(sizeof(spmv_c_cg_config) == sizeof(CGConfig) && sizeof(CGConfig) == 16, "CGConfig layout");
+static_assert(offsetof(spmv_c_cg_config, max_iterations) == offsetof(CGConfig, max_iterations) &&
+              offsetof(spmv_c_cg_config, preconditioner) == offsetof(CGConfig, preconditioner) &&
+              offsetof(spmv_c_cg_config, engine) == offsetof(CGConfig, engine), "CGConfig layout");
+static_assert(sizeof(spmv_c_cg_result) == sizeof(CGResult) && sizeof(CGResult) == 24, "CGResult layout");
+static_assert(offsetof(spmv_c_cg_result, iterations) == offsetof(CGResult, iterations) &&
+              offsetof(spmv_c_cg_result, relative_residual) == offsetof(CGResult, relative_residual) &&
+              offsetof(spmv_c_cg_result, converged) == offsetof(CGResult, converged) &&
+              offsetof(spmv_c_cg_result, breakdown) == offsetof(CGResult, breakdown) &&
+              offsetof(spmv_c_cg_result, elapsed_ms) == offsetof(CGResult, elapsed_ms), "CGResult layout");
 
 namespace {
 
@@ -376,6 +387,13 @@ int spmv_c_spmv_csr_transpose(const spmv_c_csr* A, const float* d_x, float* d_y,
 int spmv_c_spmv_csr_transpose_async(const spmv_c_csr* A, const float* d_x, float* d_y,
                                     const spmv_c_config* config, int vec_size, void* hip_stream) {
     return spmv_csr_transpose_async(cxx(A), d_x, d_y, cxx(config), vec_size, as_stream(hip_stream));
+}
+
+int spmv_c_cg_solve(const spmv_c_csr* A, const float* d_b, float* d_x, const spmv_c_cg_config* config,
+                    spmv_c_cg_result* out) {
+    const CGResult r = cg_solve(cxx(A), d_b, d_x, reinterpret_cast<const CGConfig*>(config));
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
 }
 
 // ---- bandwidth ----

@@ -1,0 +1,509 @@
+// cg.hip — device-resident preconditioned conjugate gradient (include/spmv/cg.h).
+//
+// Built like pagerank.hip: alpha, beta, the residual and the stop test live in a device CgState, every loop
+// kernel returns at once when `done` is set, and the host reads a two-deep pinned mirror of the state so that it
+// enqueues step k+1 before it looks at the outcome of step k.  Per step on the direct engine, three launches:
+//   cg_spmv_dot<LANES>  q = A p (vector CSR) and the block partials of p.q
+//   cg_update_kernel    every workgroup folds the p.q partials (same order => same alpha everywhere), then
+//                       x += alpha p, r -= alpha q, and the block partials of r.z and r.r (z = r * dinv)
+//   cg_direction_kernel every workgroup folds those partials, gets beta and the stop test, p = z + beta p
+// On the tiled engine tiled_spmv(plan, p, q) and cg_dot_kernel (partials of p.q) replace the first launch.
+// Dot products accumulate fp64 products of the fp32 entries; no float atomics anywhere.
+#include "internal.h"
+#include "device_common.h"
+#include "tiled.h"
+#include "spmv/cg.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+
+namespace spmv {
+namespace detail {
+
+namespace {
+
+using namespace dev;
+
+// Lives in device memory; every loop kernel reads `done` first.  rz is double-buffered by step parity: step k
+// reads rz[k & 1] and its direction kernel writes rz[(k + 1) & 1], so no workgroup reads a slot another is writing.
+struct CgState {
+    double rz[2];             // r.z of the current residual
+    double bnorm;             // ||b||_2
+    double threshold;         // tolerance * ||b||_2
+    float  relative_residual; // ||r||_2 / ||b||_2 of the last committed step
+    int    iterations;        // committed steps
+    int    converged;
+    int    breakdown;
+    int    done;              // steps after this are no-ops
+    int    zero_b;            // ||b|| == 0: the host writes x = 0
+    int    bad_diagonal;      // JACOBI: some row's diagonal is missing or not > 0
+    int    reserved;
+};
+
+constexpr int kVecBlocks = 1024;      // workgroups of the element-wise kernels (4 per CU)
+
+// Sums part[i * stride] (and part[i * stride + 1] when stride > 1) over i < count in a fixed order, broadcast to
+// every thread: each thread folds a fixed strided subset, then block_sum2's fixed butterfly and wave order.
+__device__ __forceinline__ void fold_partials(const double* __restrict__ part, int count, int stride,
+                                              double& a, double& b) {
+    __shared__ double s_fold[2];
+    a = 0.0;
+    b = 0.0;
+    for (int i = threadIdx.x; i < count; i += kBlock) {
+        a += part[static_cast<long long>(i) * stride];
+        if (stride > 1) b += part[static_cast<long long>(i) * stride + 1];
+    }
+    block_sum2(a, b);
+    if (threadIdx.x == 0) {
+        s_fold[0] = a;
+        s_fold[1] = b;
+    }
+    __syncthreads();
+    a = s_fold[0];
+    b = s_fold[1];
+}
+
+__device__ __forceinline__ double prod64(float a, float b) {
+    return static_cast<double>(a) * static_cast<double>(b);   // exact: 24 + 24 bits fit in fp64
+}
+
+// dinv[i] = 1 / (sum of row i's stored (i,i) entries, fp32, storage order); flags rows where that is missing or
+// not > 0.  One thread per row: setup only.
+__global__ __launch_bounds__(kBlock)
+void cg_diag_kernel(int n, const int* __restrict__ row_ptrs, const int* __restrict__ cols,
+                    const float* __restrict__ vals, float* __restrict__ dinv, CgState* __restrict__ state) {
+    int bad = 0;
+    for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < n;
+         i += static_cast<long long>(gridDim.x) * kBlock) {
+        float d = 0.0f;
+        int found = 0;
+        for (int j = row_ptrs[i]; j < row_ptrs[i + 1]; ++j) {
+            if (cols[j] == i) {
+                d = __fadd_rn(d, vals[j]);
+                found = 1;
+            }
+        }
+        const bool ok = found && d > 0.0f;
+        dinv[i] = ok ? __fdiv_rn(1.0f, d) : 0.0f;
+        bad |= !ok;
+    }
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(&state->bad_diagonal, 1);
+}
+
+// r0 = b - A x0, p0 = z0 = r0 * dinv, and the block partials of r.z, r.r and b.b -> part[3 * block].
+template <int LANES>
+__global__ __launch_bounds__(kBlock)
+void cg_init_kernel(int n, long long nnz, const int* __restrict__ row_ptrs, const int* __restrict__ cols,
+                    const float* __restrict__ vals, const float* __restrict__ b, const float* __restrict__ x,
+                    const float* __restrict__ dinv, float* __restrict__ r, float* __restrict__ p,
+                    double* __restrict__ part) {
+    constexpr int kRowsPerBlock = kBlock / LANES;
+    const int lane = threadIdx.x % LANES;
+    const int slot = threadIdx.x / LANES;
+    double rz = 0.0, rr = 0.0, bb = 0.0, unused = 0.0;
+    for (long long first = static_cast<long long>(blockIdx.x) * kRowsPerBlock; first < n;
+         first += static_cast<long long>(gridDim.x) * kRowsPerBlock) {
+        const long long row = first + slot;
+        float acc = 0.0f;
+        if (row < n) acc = row_partial_dot<LANES>(row_ptrs[row], row_ptrs[row + 1], lane, nnz, cols, vals, x);
+        acc = group_sum<LANES>(acc);
+        if (lane == 0 && row < n) {
+            const float bi = b[row];
+            const float ri = __fsub_rn(bi, acc);
+            const float zi = dinv ? __fmul_rn(ri, dinv[row]) : ri;
+            r[row] = ri;
+            p[row] = zi;
+            rz += prod64(ri, zi);
+            rr += prod64(ri, ri);
+            bb += prod64(bi, bi);
+        }
+    }
+    block_sum2(rz, rr);
+    if (threadIdx.x == 0) {
+        part[3 * blockIdx.x] = rz;
+        part[3 * blockIdx.x + 1] = rr;
+    }
+    block_sum2(bb, unused);
+    if (threadIdx.x == 0) part[3 * blockIdx.x + 2] = bb;
+}
+
+// One workgroup: folds the init partials and sets up the state (rz[0], ||b||, the threshold, step-0 outcome).
+__global__ __launch_bounds__(kBlock)
+void cg_start_kernel(const double* __restrict__ part, int count, float tolerance, CgState* __restrict__ state) {
+    double rz = 0.0, rr = 0.0, bb = 0.0;
+    fold_partials(part, count, 3, rz, rr);
+    double unused = 0.0;
+    fold_partials(part + 2, count, 3, bb, unused);
+    if (threadIdx.x != 0) return;
+    const double bnorm = sqrt(bb);
+    const double res = sqrt(rr);
+    state->rz[0] = rz;
+    state->bnorm = bnorm;
+    state->threshold = static_cast<double>(tolerance) * bnorm;
+    state->iterations = 0;
+    if (bb == 0.0) {
+        state->zero_b = 1;
+        state->relative_residual = 0.0f;
+        state->converged = 1;
+        state->done = 1;
+        return;
+    }
+    state->relative_residual = static_cast<float>(res / bnorm);
+    if (res <= state->threshold) {
+        state->converged = 1;
+        state->done = 1;
+    } else if (!(rz > 0.0)) {
+        state->breakdown = 1;
+        state->done = 1;
+    }
+}
+
+// q = A p and the block partials of p.q -> part[block].  p_i is the row's own entry: q is not read back.
+template <int LANES>
+__global__ __launch_bounds__(kBlock)
+void cg_spmv_dot(int n, long long nnz, const int* __restrict__ row_ptrs, const int* __restrict__ cols,
+                 const float* __restrict__ vals, const float* __restrict__ p, float* __restrict__ q,
+                 const CgState* __restrict__ state, double* __restrict__ part) {
+    if (state->done) return;
+    constexpr int kRowsPerBlock = kBlock / LANES;
+    const int lane = threadIdx.x % LANES;
+    const int slot = threadIdx.x / LANES;
+    double pq = 0.0, unused = 0.0;
+    for (long long first = static_cast<long long>(blockIdx.x) * kRowsPerBlock; first < n;
+         first += static_cast<long long>(gridDim.x) * kRowsPerBlock) {
+        const long long row = first + slot;
+        float acc = 0.0f;
+        if (row < n) acc = row_partial_dot<LANES>(row_ptrs[row], row_ptrs[row + 1], lane, nnz, cols, vals, p);
+        acc = group_sum<LANES>(acc);
+        if (lane == 0 && row < n) {
+            q[row] = acc;
+            pq += prod64(p[row], acc);
+        }
+    }
+    block_sum2(pq, unused);
+    if (threadIdx.x == 0) part[blockIdx.x] = pq;
+}
+
+// Block partials of p.q -> part[block] (tiled engine: q came from tiled_spmv).
+__global__ __launch_bounds__(kBlock)
+void cg_dot_kernel(int n, const float* __restrict__ p, const float* __restrict__ q,
+                   const CgState* __restrict__ state, double* __restrict__ part) {
+    if (state->done) return;
+    double pq = 0.0, unused = 0.0;
+    for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < n;
+         i += static_cast<long long>(gridDim.x) * kBlock) {
+        pq += prod64(p[i], q[i]);
+    }
+    block_sum2(pq, unused);
+    if (threadIdx.x == 0) part[blockIdx.x] = pq;
+}
+
+// alpha = rz / p.q; x += alpha p; r -= alpha q; partials of r.z and r.r -> part_out[2 * block].
+__global__ __launch_bounds__(kBlock)
+void cg_update_kernel(int n, int step, const float* __restrict__ p, const float* __restrict__ q,
+                      const float* __restrict__ dinv, float* __restrict__ x, float* __restrict__ r,
+                      CgState* __restrict__ state, const double* __restrict__ pq_part, int pq_count,
+                      double* __restrict__ part_out) {
+    if (state->done) return;
+    double pq = 0.0, unused = 0.0;
+    fold_partials(pq_part, pq_count, 1, pq, unused);
+    if (!(pq > 0.0)) {             // A is not SPD (or p.q is not finite): x stays at the last good iterate
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            state->breakdown = 1;
+            state->done = 1;
+        }
+        return;
+    }
+    const float alpha = static_cast<float>(state->rz[step & 1] / pq);
+    double rz = 0.0, rr = 0.0;
+    for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < n;
+         i += static_cast<long long>(gridDim.x) * kBlock) {
+        const float pi = p[i];
+        const float qi = q[i];
+        x[i] = __builtin_fmaf(alpha, pi, x[i]);
+        const float ri = __builtin_fmaf(-alpha, qi, r[i]);
+        r[i] = ri;
+        const float zi = dinv ? __fmul_rn(ri, dinv[i]) : ri;
+        rz += prod64(ri, zi);
+        rr += prod64(ri, ri);
+    }
+    block_sum2(rz, rr);
+    if (threadIdx.x == 0) {
+        part_out[2 * blockIdx.x] = rz;
+        part_out[2 * blockIdx.x + 1] = rr;
+    }
+}
+
+// beta = rz_new / rz_old, the stop test, p = z + beta p.  Workgroup 0 commits the step to the state.
+__global__ __launch_bounds__(kBlock)
+void cg_direction_kernel(int n, int step, const float* __restrict__ r, const float* __restrict__ dinv,
+                         float* __restrict__ p, CgState* __restrict__ state, const double* __restrict__ part,
+                         int count) {
+    if (state->done) return;
+    double rz = 0.0, rr = 0.0;
+    fold_partials(part, count, 2, rz, rr);
+    const double res = sqrt(rr);
+    const bool converged = res <= state->threshold;
+    const bool breakdown = !converged && !(rz > 0.0);
+    const double rz_old = state->rz[step & 1];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        state->iterations = step + 1;
+        state->relative_residual = static_cast<float>(res / state->bnorm);
+        state->rz[(step + 1) & 1] = rz;
+        if (converged) state->converged = 1;
+        if (breakdown) state->breakdown = 1;
+        if (converged || breakdown) state->done = 1;
+    }
+    if (converged || breakdown) return;
+    const float beta = static_cast<float>(rz / rz_old);
+    for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < n;
+         i += static_cast<long long>(gridDim.x) * kBlock) {
+        const float ri = r[i];
+        const float zi = dinv ? __fmul_rn(ri, dinv[i]) : ri;
+        p[i] = __builtin_fmaf(beta, p[i], zi);
+    }
+}
+
+int grid_for_rows(long long rows, int rows_per_block) {
+    const long long blocks = (rows + rows_per_block - 1) / rows_per_block;
+    return static_cast<int>(std::max(1LL, std::min<long long>(blocks, kMaxResidentBlocks)));
+}
+
+int vec_grid(long long n) {
+    return static_cast<int>(std::max(1LL, std::min<long long>((n + kBlock - 1) / kBlock, kVecBlocks)));
+}
+
+template <int LANES>
+hipError_t launch_init(const CSRMatrix* A, const float* b, const float* x, const float* dinv, float* r, float* p,
+                       double* part, int grid, hipStream_t s) {
+    cg_init_kernel<LANES><<<grid, kBlock, 0, s>>>(A->num_rows, A->nnz, A->d_row_ptrs, A->d_col_indices,
+                                                  A->d_values, b, x, dinv, r, p, part);
+    return hipGetLastError();
+}
+
+template <int LANES>
+hipError_t launch_spmv_dot(const CSRMatrix* A, const float* p, float* q, const CgState* state, double* part,
+                           int grid, hipStream_t s) {
+    cg_spmv_dot<LANES><<<grid, kBlock, 0, s>>>(A->num_rows, A->nnz, A->d_row_ptrs, A->d_col_indices, A->d_values,
+                                               p, q, state, part);
+    return hipGetLastError();
+}
+
+hipError_t init(int lanes, const CSRMatrix* A, const float* b, const float* x, const float* dinv, float* r,
+                float* p, double* part, int grid, hipStream_t s) {
+#define CG_INIT(L) launch_init<L>(A, b, x, dinv, r, p, part, grid, s)
+    switch (lanes) {
+        case 1:  return CG_INIT(1);
+        case 2:  return CG_INIT(2);
+        case 4:  return CG_INIT(4);
+        case 8:  return CG_INIT(8);
+        case 16: return CG_INIT(16);
+        case 32: return CG_INIT(32);
+        default: return CG_INIT(64);
+    }
+#undef CG_INIT
+}
+
+hipError_t spmv_dot(int lanes, const CSRMatrix* A, const float* p, float* q, const CgState* state, double* part,
+                    int grid, hipStream_t s) {
+#define CG_SPMV(L) launch_spmv_dot<L>(A, p, q, state, part, grid, s)
+    switch (lanes) {
+        case 1:  return CG_SPMV(1);
+        case 2:  return CG_SPMV(2);
+        case 4:  return CG_SPMV(4);
+        case 8:  return CG_SPMV(8);
+        case 16: return CG_SPMV(16);
+        case 32: return CG_SPMV(32);
+        default: return CG_SPMV(64);
+    }
+#undef CG_SPMV
+}
+
+// Device memory of one solve, freed on every exit.
+struct Workspace {
+    float* vec = nullptr;          // r, p, q, dinv: n floats each
+    double* part = nullptr;        // partial sums
+    CgState* state = nullptr;
+    CgState* pinned = nullptr;     // [2] pinned host mirror
+    hipEvent_t seen[2] = {nullptr, nullptr};
+    ~Workspace() {
+        if (vec) (void)hipFree(vec);
+        if (part) (void)hipFree(part);
+        if (state) (void)hipFree(state);
+        if (pinned) (void)hipHostFree(pinned);
+        for (hipEvent_t e : seen) if (e) (void)hipEventDestroy(e);
+    }
+};
+
+bool ranges_overlap(const float* a, const float* b, long long n) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    const uintptr_t bytes = static_cast<uintptr_t>(n) * sizeof(float);
+    return a0 < b0 + bytes && b0 < a0 + bytes;
+}
+
+} // namespace
+} // namespace detail
+
+CGResult cg_solve(const CSRMatrix* A, const float* d_b, float* d_x, const CGConfig* config) {
+    using namespace detail;
+    CGResult result;
+    const auto fail = [&result](SpMVError e) {
+        result.error_code = code(e);
+        return result;
+    };
+    if (!A || !d_b || !d_x) return fail(SpMVError::INVALID_ARGUMENT);
+    if (A->num_rows != A->num_cols) return fail(SpMVError::INVALID_DIMENSION);
+    if (A->num_rows == 0) {
+        result.converged = 1;
+        return result;
+    }
+    if (A->num_rows < 0 || !A->d_row_ptrs || (A->nnz > 0 && (!A->d_col_indices || !A->d_values))) {
+        return fail(SpMVError::INVALID_FORMAT);
+    }
+    const CGConfig defaults;
+    const CGConfig& cfg = config ? *config : defaults;
+    if (!(cfg.tolerance >= 0.0f) || cfg.max_iterations < 0 ||
+        (cfg.preconditioner != CGConfig::NONE && cfg.preconditioner != CGConfig::JACOBI) ||
+        cfg.engine < -1 || cfg.engine > 1) {
+        return fail(SpMVError::INVALID_ARGUMENT);
+    }
+    const int n = A->num_rows;
+    if (ranges_overlap(d_b, d_x, n)) return fail(SpMVError::INVALID_ARGUMENT);
+
+    const TraceRange range("spmv:cg_solve");
+    hipStream_t stream = current_stream();
+    const bool jacobi = cfg.preconditioner == CGConfig::JACOBI;
+
+    // engine choice (pagerank()'s rule for -1: a cached plan from the start, else a build after 4 direct steps)
+    PlanRef plan;
+    int build_plan_at = -1;
+    if (cfg.engine == 1) {
+        plan = tiled_plan_for(A, stream);
+    } else if (cfg.engine == -1) {
+        plan = tiled_plan_if_cached(A);
+        if (!plan && tiled_eligible(A)) build_plan_at = 4;
+    }
+
+    const int lanes = pick_lanes_per_row(static_cast<float>(A->nnz) / n);
+    const int row_grid = grid_for_rows(n, kBlock / lanes);
+    const int vgrid = vec_grid(n);
+    const size_t pq_count = static_cast<size_t>(std::max(row_grid, vgrid));
+    const size_t rr_count = 2 * static_cast<size_t>(vgrid);
+    const size_t init_count = 3 * static_cast<size_t>(row_grid);
+
+    Workspace ws;
+    const size_t len = static_cast<size_t>(n);
+    if (hipMalloc(reinterpret_cast<void**>(&ws.vec), 4 * len * sizeof(float)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&ws.part), (pq_count + rr_count + init_count) * sizeof(double)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&ws.state), sizeof(CgState)) != hipSuccess ||
+        hipHostMalloc(reinterpret_cast<void**>(&ws.pinned), 2 * sizeof(CgState)) != hipSuccess ||
+        hipEventCreateWithFlags(&ws.seen[0], hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&ws.seen[1], hipEventDisableTiming) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(SpMVError::CUDA_MALLOC);
+    }
+    float* r = ws.vec;
+    float* p = ws.vec + len;
+    float* q = ws.vec + 2 * len;
+    float* dinv = jacobi ? ws.vec + 3 * len : nullptr;
+    double* pq_part = ws.part;
+    double* rr_part = ws.part + pq_count;
+    double* init_part = rr_part + rr_count;
+    CgState* pinned = ws.pinned;
+
+    // setup: diagonal (JACOBI), r0 / p0 and their dots, the state; one read-back
+    bool ok = hipMemsetAsync(ws.state, 0, sizeof(CgState), stream) == hipSuccess;
+    if (ok && jacobi) {
+        cg_diag_kernel<<<vec_grid(n), kBlock, 0, stream>>>(n, A->d_row_ptrs, A->d_col_indices, A->d_values, dinv,
+                                                            ws.state);
+        ok = hipGetLastError() == hipSuccess;
+    }
+    ok = ok && init(lanes, A, d_b, d_x, dinv, r, p, init_part, row_grid, stream) == hipSuccess;
+    if (ok) {
+        cg_start_kernel<<<1, kBlock, 0, stream>>>(init_part, row_grid, cfg.tolerance, ws.state);
+        ok = hipGetLastError() == hipSuccess;
+    }
+    ok = ok && hipMemcpyAsync(&pinned[0], ws.state, sizeof(CgState), hipMemcpyDeviceToHost, stream) == hipSuccess
+            && hipStreamSynchronize(stream) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        return fail(SpMVError::KERNEL_LAUNCH);
+    }
+    if (pinned[0].bad_diagonal) return fail(SpMVError::INVALID_ARGUMENT);
+    if (pinned[0].zero_b) {
+        if (hipMemsetAsync(d_x, 0, len * sizeof(float), stream) != hipSuccess ||
+            hipStreamSynchronize(stream) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(SpMVError::KERNEL_LAUNCH);
+        }
+        result.converged = 1;
+        return result;
+    }
+
+    CgState final_state = pinned[0];
+    if (!final_state.done) {
+        EventPair& ev = thread_events();
+        ok = hipEventRecord(ev.start, stream) == hipSuccess;
+        for (int iter = 0; ok && iter < cfg.max_iterations; ++iter) {
+            if (!plan && iter == build_plan_at) {
+                // enough direct steps paid: drain the queue (nothing is built for a loop that has ended), then plan
+                ok = hipStreamSynchronize(stream) == hipSuccess;
+                if (ok && iter >= 1 && pinned[(iter - 1) & 1].done) break;
+                plan = ok ? tiled_plan_for(A, stream) : nullptr;
+            }
+            const TraceRange step_range("spmv:cg_step");
+            int pq_parts = row_grid;
+            bool direct = !plan;
+            if (plan) {
+                const hipError_t e = tiled_spmv(*plan, p, q, stream);
+                if (e == hipErrorOutOfMemory) {        // no tiled scratch for this stream: direct kernels from here on
+                    (void)hipGetLastError();
+                    plan.reset();
+                    build_plan_at = -1;
+                    direct = true;
+                } else if (e != hipSuccess) {
+                    ok = false;
+                    break;
+                } else {
+                    cg_dot_kernel<<<vgrid, kBlock, 0, stream>>>(n, p, q, ws.state, pq_part);
+                    ok = hipGetLastError() == hipSuccess;
+                    pq_parts = vgrid;
+                }
+            }
+            if (ok && direct) ok = spmv_dot(lanes, A, p, q, ws.state, pq_part, row_grid, stream) == hipSuccess;
+            if (ok) {
+                cg_update_kernel<<<vgrid, kBlock, 0, stream>>>(n, iter, p, q, dinv, d_x, r, ws.state, pq_part,
+                                                               pq_parts, rr_part);
+                cg_direction_kernel<<<vgrid, kBlock, 0, stream>>>(n, iter, r, dinv, p, ws.state, rr_part, vgrid);
+                ok = hipGetLastError() == hipSuccess
+                  && hipMemcpyAsync(&pinned[iter & 1], ws.state, sizeof(CgState), hipMemcpyDeviceToHost,
+                                    stream) == hipSuccess
+                  && hipEventRecord(ws.seen[iter & 1], stream) == hipSuccess;
+            }
+            if (ok && iter >= 1) {
+                ok = hipEventSynchronize(ws.seen[(iter - 1) & 1]) == hipSuccess;
+                if (ok && pinned[(iter - 1) & 1].done) break;
+            }
+        }
+        ok = ok && hipEventRecord(ev.stop, stream) == hipSuccess
+                && hipMemcpyAsync(&pinned[0], ws.state, sizeof(CgState), hipMemcpyDeviceToHost, stream) == hipSuccess
+                && hipStreamSynchronize(stream) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            return fail(SpMVError::KERNEL_LAUNCH);
+        }
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, ev.start, ev.stop) == hipSuccess) result.elapsed_ms = ms;
+        final_state = pinned[0];
+    }
+    result.iterations = final_state.iterations;
+    result.relative_residual = final_state.relative_residual;
+    result.converged = final_state.converged;
+    result.breakdown = final_state.breakdown;
+    return result;
+}
+
+} // namespace spmv

@@ -1,0 +1,72 @@
+// spmv/cg.h — device-resident preconditioned conjugate gradient solver for A x = b (A symmetric positive definite).
+//
+// The whole iteration runs on the device (gpu-spmv_amd/csrc/cg.hip): no host round-trip for alpha or beta, no
+// device-to-host vector copies inside the loop.  Built on the same pattern as pagerank(): the scalars live in a
+// device state, every kernel of a step returns at once when the state says `done`, and the host enqueues step k+1
+// before it reads the outcome of step k.  See DESIGN.md §4.9.
+#ifndef SPMV_CG_H
+#define SPMV_CG_H
+
+#include "common.h"
+#include "csr_matrix.h"
+
+namespace spmv {
+
+struct CGConfig {
+    enum Preconditioner { NONE = 0, JACOBI = 1 };
+    float tolerance;       // stop when ||r_k||_2 <= tolerance * ||b||_2 (recurrence residual)
+    int   max_iterations;
+    int   preconditioner;  // Preconditioner
+    int   engine;          // -1 auto, 0 direct kernels only, 1 tiled plan from the start where tiled_eligible(A)
+    CGConfig() : tolerance(1e-6f), max_iterations(1000), preconditioner(JACOBI), engine(-1) {}
+};
+
+struct CGResult {
+    int   error_code;         // SpMVError as int
+    int   iterations;         // committed iterations
+    float relative_residual;  // ||r||/||b|| (recurrence) at exit
+    int   converged;
+    int   breakdown;          // p.Ap <= 0 or r.z <= 0 was met: A (or M) is not SPD; x holds the last good iterate
+    float elapsed_ms;         // device-event time of the iteration loop (setup excluded)
+    CGResult() : error_code(0), iterations(0), relative_residual(0.0f), converged(0), breakdown(0),
+                 elapsed_ms(0.0f) {}
+};
+
+// Solves A x = b by preconditioned CG (M = diag(A) with JACOBI, M = I with NONE):
+//     r0 = b - A x0;  z0 = M^-1 r0;  p0 = z0
+//     repeat: q = A p;  alpha = (r.z) / (p.q);  x += alpha p;  r -= alpha q;  z = M^-1 r;
+//             beta = (r.z)_new / (r.z)_old;  p = z + beta p
+// d_b: num_rows floats (device).  d_x: num_rows floats (device): the initial guess on entry, the solution on exit.
+// A must be square and resident on the device (csr_to_gpu / csr_wrap_device).  config == nullptr: CGConfig().
+//
+// Numerics: vectors are fp32.  Every dot product accumulates the per-element products in fp64 into per-workgroup
+// partials that are folded in a fixed order; nothing uses float atomics, so a solve is bitwise reproducible from
+// run to run on each engine.  alpha and beta are computed in fp64 on the device and applied to the vectors rounded
+// to fp32, with fmaf (x = fmaf(alpha, p, x), r = fmaf(-alpha, q, r), p = fmaf(beta, p, z)).  z is never stored: it
+// is recomputed as r * dinv, dinv = 1 / diag(A) in fp32 (1 with NONE).  After every iteration the device tests
+// sqrt(r.r) <= tolerance * ||b|| (r the recurrence residual); that iteration is the last one.  The diagonal of row i
+// is the fp32 sum of its stored (i,i) entries in storage order.
+//
+// Checks, in this order, before any device work; nothing is written to d_x when one fails:
+//   null A / d_b / d_x -> INVALID_ARGUMENT; num_rows != num_cols -> INVALID_DIMENSION; num_rows == 0 -> SUCCESS,
+//   converged, 0 iterations; missing device arrays -> INVALID_FORMAT; tolerance < 0 or NaN, max_iterations < 0, an
+//   unknown preconditioner or engine -> INVALID_ARGUMENT; overlapping d_b and d_x ranges -> INVALID_ARGUMENT; with
+//   JACOBI, a row whose diagonal is missing or not > 0 -> INVALID_ARGUMENT (checked on the device, read back once
+//   during setup).
+// ||b|| == 0 writes zeros to x and returns converged after 0 iterations.  An initial guess with
+// ||r0|| <= tolerance * ||b|| returns converged after 0 iterations and leaves x unchanged.  A breakdown (p.q <= 0,
+// or r.z <= 0 for a residual above the tolerance) ends the solve with breakdown = 1 and x at the last good iterate.
+//
+// Engines: 0 runs a fused vector-CSR SpMV + dot kernel per iteration; 1 runs the LDS-tiled engine (tiled_spmv)
+// from the first iteration when the matrix is eligible (> 32768 columns, >= 1 M entries; else as 0), falling back to
+// the direct kernel when the tiled engine has no scratch for this stream.  -1 (auto) follows pagerank()'s rule: a
+// plan A already holds is used from the start; otherwise an eligible matrix gets its plan after 4 direct iterations,
+// if the loop has not converged by then.  A plan cg_solve builds is cached on A, exactly as pagerank() caches its
+// plan (the plan build counts inside elapsed_ms).  cg_solve never touches A's promotion count or its merge-path
+// state.  It runs on spmv_get_stream() and returns after the solve completed; its setup (workspace, diagonal,
+// plan for engine 1) and its one setup read-back synchronise that stream — make the call outside a graph capture.
+CGResult cg_solve(const CSRMatrix* A, const float* d_b, float* d_x, const CGConfig* config = nullptr);
+
+} // namespace spmv
+
+#endif

@@ -236,6 +236,31 @@ int spmv_c_spmv_csr_transpose(const spmv_c_csr* A, const float* d_x, float* d_y,
 int spmv_c_spmv_csr_transpose_async(const spmv_c_csr* A, const float* d_x, float* d_y,
                                     const spmv_c_config* config, int vec_size, void* hip_stream);
 
+/* ---- preconditioned conjugate gradient (extension; spmv::cg_solve, include/spmv/cg.h) ---- */
+/* preconditioner: 0 NONE, 1 JACOBI; engine: -1 auto, 0 direct kernels, 1 tiled plan where eligible (16 bytes) */
+typedef struct spmv_c_cg_config {
+    float   tolerance;
+    int32_t max_iterations;
+    int32_t preconditioner;
+    int32_t engine;
+} spmv_c_cg_config;
+
+/* 24 bytes */
+typedef struct spmv_c_cg_result {
+    int32_t error_code;
+    int32_t iterations;
+    float   relative_residual;
+    int32_t converged;
+    int32_t breakdown;
+    float   elapsed_ms;
+} spmv_c_cg_result;
+
+/* Solves A x = b for a symmetric positive definite A on the device; d_b and d_x hold num_rows floats, d_x is the
+ * initial guess on entry and the solution on exit.  config NULL = defaults (1e-6, 1000, JACOBI, auto).  Argument
+ * checks and numerics as cg_solve in include/spmv/cg.h.  The return value equals out->error_code (out may be NULL). */
+int spmv_c_cg_solve(const spmv_c_csr* A, const float* d_b, float* d_x, const spmv_c_cg_config* config,
+                    spmv_c_cg_result* out);
+
 /* ---- bandwidth model: reference include/spmv/bandwidth.h:21-27 ---- */
 int spmv_c_compute_bandwidth_csr(const spmv_c_csr* A, float elapsed_ms, spmv_c_bandwidth* out);
 int spmv_c_compute_bandwidth_ell(const spmv_c_ell* A, float elapsed_ms, spmv_c_bandwidth* out);
