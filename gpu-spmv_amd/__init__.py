@@ -133,6 +133,27 @@ class CGResult(Structure):
                 ("converged", c_int32), ("breakdown", c_int32), ("elapsed_ms", c_float)]
 
 
+class BiCGStabConfig(Structure):
+    """include/spmv/bicgstab.h BiCGStabConfig (16 bytes): the fields, defaults and meanings of CGConfig"""
+    _fields_ = [("tolerance", c_float), ("max_iterations", c_int32), ("preconditioner", c_int32),
+                ("engine", c_int32)]
+    NONE, JACOBI = 0, 1
+
+    def __init__(self, tolerance=1e-6, max_iterations=1000, preconditioner=1, engine=-1):
+        super().__init__(tolerance, max_iterations, preconditioner, engine)
+
+
+# BiCGStabResult.breakdown codes (include/spmv/bicgstab.h BiCGStabResult::Breakdown)
+BICGSTAB_NO_BREAKDOWN, BICGSTAB_RHO, BICGSTAB_ALPHA, BICGSTAB_OMEGA = 0, 1, 2, 3
+
+
+class BiCGStabResult(Structure):
+    """include/spmv/bicgstab.h BiCGStabResult (24 bytes); breakdown is one of NONE, RHO, ALPHA, OMEGA"""
+    _fields_ = [("error_code", c_int32), ("iterations", c_int32), ("relative_residual", c_float),
+                ("converged", c_int32), ("breakdown", c_int32), ("elapsed_ms", c_float)]
+    NONE, RHO, ALPHA, OMEGA = BICGSTAB_NO_BREAKDOWN, BICGSTAB_RHO, BICGSTAB_ALPHA, BICGSTAB_OMEGA
+
+
 class PageRankResult:
     """reference include/spmv/pagerank.h:18-25; `ranks` is a numpy copy (the C buffer is freed)."""
 
@@ -221,6 +242,8 @@ _SIGNATURES = {
     "spmv_c_spmv_csr_transpose_async": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(SpMVConfig), c_int,
                                                 c_void_p]),
     "spmv_c_cg_solve": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(CGConfig), POINTER(CGResult)]),
+    "spmv_c_bicgstab_solve": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(BiCGStabConfig),
+                                      POINTER(BiCGStabResult)]),
     "spmv_c_compute_bandwidth_csr": (c_int, [POINTER(CSRMatrix), c_float, POINTER(BandwidthMetrics)]),
     "spmv_c_compute_bandwidth_csr_multi": (c_int, [POINTER(CSRMatrix), c_int, c_float, POINTER(BandwidthMetrics)]),
     "spmv_c_compute_bandwidth_ell": (c_int, [POINTER(ELLMatrix), c_float, POINTER(BandwidthMetrics)]),
@@ -736,6 +759,15 @@ def cg_solve(A, d_b, d_x, config=None) -> CGResult:
     d_x is the initial guess on entry and the solution on exit."""
     out = CGResult()
     lib().spmv_c_cg_solve(A, _dev(d_b), _dev(d_x), byref(config) if config is not None else None, byref(out))
+    return out
+
+
+def bicgstab_solve(A, d_b, d_x, config=None) -> BiCGStabResult:
+    """Jacobi-preconditioned BiCGSTAB for a square non-singular A x = b on the device (include/spmv/bicgstab.h
+    bicgstab_solve): d_b and d_x hold num_rows floats, d_x is the initial guess on entry and the solution on exit."""
+    out = BiCGStabResult()
+    lib().spmv_c_bicgstab_solve(A, _dev(d_b), _dev(d_x), byref(config) if config is not None else None,
+                                byref(out))
     return out
 
 

@@ -5,6 +5,7 @@
 #include "pagerank_engine.h"
 #include "tiled.h"
 #include "spmv/bandwidth.h"
+#include "spmv/bicgstab.h"
 #include "spmv/cg.h"
 #include "spmv/pagerank.h"
 #include "spmv_c.h"
@@ -44,6 +45,19 @@ static_assert(offsetof(spmv_c_cg_result, iterations) == offsetof(CGResult, itera
               offsetof(spmv_c_cg_result, converged) == offsetof(CGResult, converged) &&
               offsetof(spmv_c_cg_result, breakdown) == offsetof(CGResult, breakdown) &&
               offsetof(spmv_c_cg_result, elapsed_ms) == offsetof(CGResult, elapsed_ms), "CGResult layout");
+static_assert(sizeof(spmv_c_bicgstab_config) == sizeof(BiCGStabConfig) && sizeof(BiCGStabConfig) == 16,
+              "BiCGStabConfig layout");
+static_assert(offsetof(spmv_c_bicgstab_config, max_iterations) == offsetof(BiCGStabConfig, max_iterations) &&
+              offsetof(spmv_c_bicgstab_config, preconditioner) == offsetof(BiCGStabConfig, preconditioner) &&
+              offsetof(spmv_c_bicgstab_config, engine) == offsetof(BiCGStabConfig, engine), "BiCGStabConfig layout");
+static_assert(sizeof(spmv_c_bicgstab_result) == sizeof(BiCGStabResult) && sizeof(BiCGStabResult) == 24,
+              "BiCGStabResult layout");
+static_assert(offsetof(spmv_c_bicgstab_result, iterations) == offsetof(BiCGStabResult, iterations) &&
+              offsetof(spmv_c_bicgstab_result, relative_residual) == offsetof(BiCGStabResult, relative_residual) &&
+              offsetof(spmv_c_bicgstab_result, converged) == offsetof(BiCGStabResult, converged) &&
+              offsetof(spmv_c_bicgstab_result, breakdown) == offsetof(BiCGStabResult, breakdown) &&
+              offsetof(spmv_c_bicgstab_result, elapsed_ms) == offsetof(BiCGStabResult, elapsed_ms),
+              "BiCGStabResult layout");
 
 namespace {
 
@@ -392,6 +406,13 @@ int spmv_c_spmv_csr_transpose_async(const spmv_c_csr* A, const float* d_x, float
 int spmv_c_cg_solve(const spmv_c_csr* A, const float* d_b, float* d_x, const spmv_c_cg_config* config,
                     spmv_c_cg_result* out) {
     const CGResult r = cg_solve(cxx(A), d_b, d_x, reinterpret_cast<const CGConfig*>(config));
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
+}
+
+int spmv_c_bicgstab_solve(const spmv_c_csr* A, const float* d_b, float* d_x, const spmv_c_bicgstab_config* config,
+                          spmv_c_bicgstab_result* out) {
+    const BiCGStabResult r = bicgstab_solve(cxx(A), d_b, d_x, reinterpret_cast<const BiCGStabConfig*>(config));
     if (out) std::memcpy(out, &r, sizeof(r));
     return r.error_code;
 }

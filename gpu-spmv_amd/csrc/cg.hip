@@ -11,6 +11,7 @@
 // Dot products accumulate fp64 products of the fp32 entries; no float atomics anywhere.
 #include "internal.h"
 #include "device_common.h"
+#include "solver_common.h"
 #include "tiled.h"
 #include "spmv/cg.h"
 
@@ -18,7 +19,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdint>
 
 namespace spmv {
 namespace detail {
@@ -26,6 +26,7 @@ namespace detail {
 namespace {
 
 using namespace dev;
+using namespace solver;
 
 // Lives in device memory; every loop kernel reads `done` first.  rz is double-buffered by step parity: step k
 // reads rz[k & 1] and its direction kernel writes rz[(k + 1) & 1], so no workgroup reads a slot another is writing.
@@ -42,33 +43,6 @@ struct CgState {
     int    bad_diagonal;      // JACOBI: some row's diagonal is missing or not > 0
     int    reserved;
 };
-
-constexpr int kVecBlocks = 1024;      // workgroups of the element-wise kernels (4 per CU)
-
-// Sums part[i * stride] (and part[i * stride + 1] when stride > 1) over i < count in a fixed order, broadcast to
-// every thread: each thread folds a fixed strided subset, then block_sum2's fixed butterfly and wave order.
-__device__ __forceinline__ void fold_partials(const double* __restrict__ part, int count, int stride,
-                                              double& a, double& b) {
-    __shared__ double s_fold[2];
-    a = 0.0;
-    b = 0.0;
-    for (int i = threadIdx.x; i < count; i += kBlock) {
-        a += part[static_cast<long long>(i) * stride];
-        if (stride > 1) b += part[static_cast<long long>(i) * stride + 1];
-    }
-    block_sum2(a, b);
-    if (threadIdx.x == 0) {
-        s_fold[0] = a;
-        s_fold[1] = b;
-    }
-    __syncthreads();
-    a = s_fold[0];
-    b = s_fold[1];
-}
-
-__device__ __forceinline__ double prod64(float a, float b) {
-    return static_cast<double>(a) * static_cast<double>(b);   // exact: 24 + 24 bits fit in fp64
-}
 
 // dinv[i] = 1 / (sum of row i's stored (i,i) entries, fp32, storage order); flags rows where that is missing or
 // not > 0.  One thread per row: setup only.
@@ -267,15 +241,6 @@ void cg_direction_kernel(int n, int step, const float* __restrict__ r, const flo
     }
 }
 
-int grid_for_rows(long long rows, int rows_per_block) {
-    const long long blocks = (rows + rows_per_block - 1) / rows_per_block;
-    return static_cast<int>(std::max(1LL, std::min<long long>(blocks, kMaxResidentBlocks)));
-}
-
-int vec_grid(long long n) {
-    return static_cast<int>(std::max(1LL, std::min<long long>((n + kBlock - 1) / kBlock, kVecBlocks)));
-}
-
 template <int LANES>
 hipError_t launch_init(const CSRMatrix* A, const float* b, const float* x, const float* dinv, float* r, float* p,
                        double* part, int grid, hipStream_t s) {
@@ -294,54 +259,16 @@ hipError_t launch_spmv_dot(const CSRMatrix* A, const float* p, float* q, const C
 
 hipError_t init(int lanes, const CSRMatrix* A, const float* b, const float* x, const float* dinv, float* r,
                 float* p, double* part, int grid, hipStream_t s) {
-#define CG_INIT(L) launch_init<L>(A, b, x, dinv, r, p, part, grid, s)
-    switch (lanes) {
-        case 1:  return CG_INIT(1);
-        case 2:  return CG_INIT(2);
-        case 4:  return CG_INIT(4);
-        case 8:  return CG_INIT(8);
-        case 16: return CG_INIT(16);
-        case 32: return CG_INIT(32);
-        default: return CG_INIT(64);
-    }
-#undef CG_INIT
+    return with_lanes(lanes, [&](auto L) {
+        return launch_init<decltype(L)::value>(A, b, x, dinv, r, p, part, grid, s);
+    });
 }
 
 hipError_t spmv_dot(int lanes, const CSRMatrix* A, const float* p, float* q, const CgState* state, double* part,
                     int grid, hipStream_t s) {
-#define CG_SPMV(L) launch_spmv_dot<L>(A, p, q, state, part, grid, s)
-    switch (lanes) {
-        case 1:  return CG_SPMV(1);
-        case 2:  return CG_SPMV(2);
-        case 4:  return CG_SPMV(4);
-        case 8:  return CG_SPMV(8);
-        case 16: return CG_SPMV(16);
-        case 32: return CG_SPMV(32);
-        default: return CG_SPMV(64);
-    }
-#undef CG_SPMV
-}
-
-// Device memory of one solve, freed on every exit.
-struct Workspace {
-    float* vec = nullptr;          // r, p, q, dinv: n floats each
-    double* part = nullptr;        // partial sums
-    CgState* state = nullptr;
-    CgState* pinned = nullptr;     // [2] pinned host mirror
-    hipEvent_t seen[2] = {nullptr, nullptr};
-    ~Workspace() {
-        if (vec) (void)hipFree(vec);
-        if (part) (void)hipFree(part);
-        if (state) (void)hipFree(state);
-        if (pinned) (void)hipHostFree(pinned);
-        for (hipEvent_t e : seen) if (e) (void)hipEventDestroy(e);
-    }
-};
-
-bool ranges_overlap(const float* a, const float* b, long long n) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    const uintptr_t bytes = static_cast<uintptr_t>(n) * sizeof(float);
-    return a0 < b0 + bytes && b0 < a0 + bytes;
+    return with_lanes(lanes, [&](auto L) {
+        return launch_spmv_dot<decltype(L)::value>(A, p, q, state, part, grid, s);
+    });
 }
 
 } // namespace
@@ -349,6 +276,7 @@ bool ranges_overlap(const float* a, const float* b, long long n) {
 
 CGResult cg_solve(const CSRMatrix* A, const float* d_b, float* d_x, const CGConfig* config) {
     using namespace detail;
+    using namespace detail::solver;
     CGResult result;
     const auto fail = [&result](SpMVError e) {
         result.error_code = code(e);
@@ -394,17 +322,9 @@ CGResult cg_solve(const CSRMatrix* A, const float* d_b, float* d_x, const CGConf
     const size_t rr_count = 2 * static_cast<size_t>(vgrid);
     const size_t init_count = 3 * static_cast<size_t>(row_grid);
 
-    Workspace ws;
+    Workspace<CgState> ws;          // r, p, q, dinv
     const size_t len = static_cast<size_t>(n);
-    if (hipMalloc(reinterpret_cast<void**>(&ws.vec), 4 * len * sizeof(float)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&ws.part), (pq_count + rr_count + init_count) * sizeof(double)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&ws.state), sizeof(CgState)) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&ws.pinned), 2 * sizeof(CgState)) != hipSuccess ||
-        hipEventCreateWithFlags(&ws.seen[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ws.seen[1], hipEventDisableTiming) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(SpMVError::CUDA_MALLOC);
-    }
+    if (!ws.allocate(4 * len, pq_count + rr_count + init_count)) return fail(SpMVError::CUDA_MALLOC);
     float* r = ws.vec;
     float* p = ws.vec + len;
     float* q = ws.vec + 2 * len;

@@ -261,6 +261,32 @@ typedef struct spmv_c_cg_result {
 int spmv_c_cg_solve(const spmv_c_csr* A, const float* d_b, float* d_x, const spmv_c_cg_config* config,
                     spmv_c_cg_result* out);
 
+/* ---- Jacobi-preconditioned BiCGSTAB (extension; spmv::bicgstab_solve, include/spmv/bicgstab.h) ---- */
+/* 16 bytes; the fields, defaults and meanings of spmv_c_cg_config */
+typedef struct spmv_c_bicgstab_config {
+    float   tolerance;
+    int32_t max_iterations;
+    int32_t preconditioner;
+    int32_t engine;
+} spmv_c_bicgstab_config;
+
+/* breakdown: 0 none, 1 RHO (r^.r is 0 or not finite), 2 ALPHA (r^.v is 0 or not finite), 3 OMEGA (omega is 0 or
+ * not finite) (24 bytes) */
+typedef struct spmv_c_bicgstab_result {
+    int32_t error_code;
+    int32_t iterations;
+    float   relative_residual;
+    int32_t converged;
+    int32_t breakdown;
+    float   elapsed_ms;
+} spmv_c_bicgstab_result;
+
+/* Solves A x = b for a square non-singular A on the device; d_b and d_x hold num_rows floats, d_x is the initial
+ * guess on entry and the solution on exit.  config NULL = defaults (1e-6, 1000, JACOBI, auto).  Argument checks and
+ * numerics as bicgstab_solve in include/spmv/bicgstab.h.  The return value equals out->error_code (out may be NULL). */
+int spmv_c_bicgstab_solve(const spmv_c_csr* A, const float* d_b, float* d_x, const spmv_c_bicgstab_config* config,
+                          spmv_c_bicgstab_result* out);
+
 /* ---- bandwidth model: reference include/spmv/bandwidth.h:21-27 ---- */
 int spmv_c_compute_bandwidth_csr(const spmv_c_csr* A, float elapsed_ms, spmv_c_bandwidth* out);
 int spmv_c_compute_bandwidth_ell(const spmv_c_ell* A, float elapsed_ms, spmv_c_bandwidth* out);
