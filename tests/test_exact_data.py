@@ -1,0 +1,175 @@
+"""CPU tier of the exact-arithmetic tests: every matrix tests/test_gpu_lane_sweep.py runs is generated here and
+proved exact without a GPU.  Per matrix: the sum_j |a_ij| |x_j| < 2^24 bound holds, the lane rule gives the L its
+name claims, and the CPU oracle (CPU order, fp32) and the library's own spmv_cpu_csr equal the int64 reference
+bit for bit: the data are order-independent, so the GPU tests may demand bit equality from every kernel."""
+import importlib
+
+import numpy as np
+import pytest
+
+import exact_data as ed
+
+
+def host_library_y(spmv, rows, num_cols, rp, ci, va, x):
+    A = spmv.csr_from_arrays(rows, num_cols, rp, ci, va)
+    try:
+        return spmv.spmv_cpu_csr(A, x)
+    finally:
+        spmv.csr_destroy(A)
+
+
+def prove_exact(spmv, oracle, num_cols, rp, ci, va, x):
+    ed.check_exact(rp, ci, va, x)
+    want = ed.exact_reference(rp, ci, va, x)
+    np.testing.assert_array_equal(oracle.spmv_csr(rp, ci, va, x), want)
+    np.testing.assert_array_equal(host_library_y(spmv, len(rp) - 1, num_cols, rp, ci, va, x), want)
+    return want
+
+
+def test_lane_rule_restatement_at_every_threshold():
+    for L in ed.LANES:
+        for rows in (1, 7, 1003, 4099):
+            assert ed.lanes_for(4 * L * rows, rows) == L
+            assert ed.lanes_for(4 * L * rows + 1, rows) == min(2 * L, 64)
+    assert ed.lanes_for(0, 5) == 1 and ed.lanes_for(10**7, 3) == 64
+
+
+def test_exact_csr_data_and_its_bound():
+    rng = np.random.default_rng(1)
+    rp, ci, va, x = ed.exact_csr(rng, [3, 0, 32767, 5], 1000)
+    assert va.dtype == x.dtype == np.float32 and ci.dtype == rp.dtype == np.int32
+    assert np.all(va != 0) and np.abs(va).max() <= 8 and np.abs(x).max() <= 64
+    assert (va < 0).any() and (va > 0).any() and (x < 0).any() and np.unique(x).size > 100
+    assert np.unique(ci[rp[2]:rp[3]]).size < 32767                  # repeats allowed
+    assert np.any(np.diff(ci[rp[2]:rp[3]]) < 0)                     # unsorted
+    with pytest.raises(AssertionError):                             # a row the defaults cannot keep exact
+        ed.check_exact(np.array([0, 32768]), np.zeros(32768, np.int32), np.full(32768, 8, np.float32),
+                       np.full(10, 64, np.float32))
+    ed.check_exact(np.array([0, 32767]), np.zeros(32767, np.int32), np.full(32767, 8, np.float32),
+                   np.full(10, 64, np.float32))
+    ed.exact_csr(rng, [40000], 10, vmax=4, xmax=64)                 # smaller values: longer rows
+
+
+@pytest.mark.parametrize("rows,num,den", [(1003, 4, 1), (1003, 2 * 1003 + 1, 1003), (1003, 501, 1003), (300, 7, 2),
+                                          (4099, 200, 1)])
+def test_lens_for_average(rows, num, den):
+    lens = ed.lens_for_average(rows, num, den, np.random.default_rng(rows))
+    assert lens.size == rows and lens.min() == 0 and int(lens.sum()) * den == rows * num
+    assert (lens == 0).sum() >= rows // 11 and lens[-1] == 0
+    assert lens.max() >= 3 * num / den and (num < den or (lens % 4 != 0).sum() > rows // 4)
+
+
+@pytest.mark.parametrize("name", ed.SWEEP_NAMES)
+def test_sweep_matrix_is_exact_and_lands_on_its_lanes(spmv, oracle, name):
+    L, rp, ci, va, x = ed.sweep_matrix(name)
+    rows, nnz = ed.SWEEP_ROWS, int(rp[-1])
+    assert len(rp) - 1 == rows and rows % 4 != 0                    # idle row slots in the last workgroup at every L
+    assert nnz == dict((c[0], c[2]) for c in ed.sweep_counts(rows))[name]
+    assert ed.lanes_for(nnz, rows) == L == int(name[1:].split("_")[0])
+    if name.endswith("_top") and L < 64:
+        assert nnz == 4 * L * rows and ed.lanes_for(nnz + 1, rows) == 2 * L
+    if name.endswith("_low") and L > 1:
+        assert nnz == 2 * L * rows + 1 and ed.lanes_for(nnz - 1, rows) == L // 2
+    prove_exact(spmv, oracle, ed.SWEEP_COLS, rp, ci, va, x)
+    # the multi-vector sweep's X: every column under the same bound, every column's oracle result exact
+    X = ed.exact_x_matrix(np.random.default_rng(5), ed.SWEEP_COLS, 19)
+    ed.check_exact(rp, ci, va, X)
+    for j in (0, 18):
+        col = np.ascontiguousarray(X[:, j])
+        np.testing.assert_array_equal(oracle.spmv_csr(rp, ci, va, col), ed.exact_reference(rp, ci, va, col))
+
+
+@pytest.mark.parametrize("name", ed.SWEEP_NAMES)
+def test_ldsx_matrix_is_exact_and_meets_the_x_in_lds_conditions(spmv, oracle, name):
+    L, num_cols, rp, ci, va, x = ed.ldsx_matrix(name)
+    rows, nnz = len(rp) - 1, int(rp[-1])
+    assert ed.lanes_for(nnz, rows) == L
+    # vector_ldsx_grid (csrc/kernels.hip): rows >= 4096, columns <= 32768, min(256, nnz * 8 / (8 * 4 * cols)) >= 64;
+    # and below the tiled engine's column minimum (32769), so use_texture keeps the direct kernel
+    assert rows >= 4096 and 0 < num_cols <= 32768 and (nnz * 8) // (8 * 4 * num_cols) >= 64
+    prove_exact(spmv, oracle, num_cols, rp, ci, va, x)
+
+
+def test_ldsx_catalogue_takes_both_branches_of_the_copy_loop():
+    cols = [ed.ldsx_matrix(name)[1] for name in ed.SWEEP_NAMES]
+    assert any(c % 4 == 0 for c in cols) and any(c % 4 != 0 for c in cols)
+
+
+def merge_items(rp):
+    """Merge item index (0-based) of every row's end: the row's entries come first, then its end."""
+    rp = np.asarray(rp, np.int64)
+    return rp[1:] + np.arange(rp.size - 1)
+
+
+@pytest.mark.parametrize("name", ed.MERGE_CUT_NAMES)
+def test_merge_cut_matrix_is_exact_and_sits_where_its_name_says(spmv, oracle, name):
+    rp, ci, va, x = ed.merge_cut_matrix(name)
+    T = ed.MERGE_TILE
+    rows, nnz = len(rp) - 1, int(rp[-1])
+    ends, lens = merge_items(rp), np.diff(rp.astype(np.int64))
+    total = rows + nnz
+    if name.startswith("total_"):
+        assert total == {"T-1": T - 1, "T": T, "T+1": T + 1, "2T": 2 * T, "2T+1": 2 * T + 1}[name[6:]]
+    elif name.startswith("row_end_"):
+        assert {"T-2": T - 2, "T-1": T - 1, "T": T}[name[8:]] in ends and total > 2 * T
+    elif name.endswith("over_four_tiles"):
+        long_rows = np.flatnonzero(lens > 2 * T)
+        assert long_rows.size == (2 if name.startswith("two") else 1) and lens[0:long_rows[0]].max() < 9
+        for r in long_rows:              # first entry in tile t, row end in tile t + 3: three tiles carry into it
+            assert ends[r] // T - (ends[r] - lens[r]) // T == 3
+        assert np.all(np.diff(long_rows) == 1) and rows - long_rows[-1] > 100
+    elif name.startswith("empty_run"):
+        empty = np.flatnonzero(lens == 0)
+        run = np.split(empty, np.flatnonzero(np.diff(empty) > 1) + 1)
+        longest = max(run, key=len)
+        assert len(longest) >= 2000 > T
+        assert (longest[-1] == rows - 1) == name.endswith("at_the_end")
+    else:
+        r = int(np.flatnonzero(ends == 2 * T)[0])
+        assert (ends[r] - lens[r]) // T == 0                      # its first entry is in tile 0
+    prove_exact(spmv, oracle, ed.MERGE_CUT_COLS, rp, ci, va, x)
+    X = ed.exact_x_matrix(np.random.default_rng(6), ed.MERGE_CUT_COLS, 20)
+    ed.check_exact(rp, ci, va, X)
+
+
+@pytest.mark.parametrize("symmetric", [True, False], ids=["spd", "nonsym"])
+@pytest.mark.parametrize("name", ed.SOLVER_NAMES)
+def test_solver_system_is_exact_dominant_and_lands_on_its_lanes(spmv, oracle, name, symmetric):
+    L, n, rp, ci, va, x_star, b = ed.solver_system(name, symmetric)
+    nnz = int(rp[-1])
+    assert n <= 2000 and ed.lanes_for(nnz, n) == L == int(name[1:].split("_")[0])
+    if name.endswith("_top") and L < 64:
+        assert nnz == 4 * L * n
+    if name.endswith("_low") and L > 1:
+        assert nnz == 2 * L * n + 1
+    rows = np.repeat(np.arange(n), np.diff(rp))
+    dense = np.zeros((n, n), np.int64)
+    np.add.at(dense, (rows, ci), va.astype(np.int64))
+    off = np.abs(dense).sum(axis=1) - np.abs(np.diag(dense))
+    assert np.all(np.diag(dense) > off)                             # strictly diagonally dominant, positive diagonal
+    assert np.array_equal(dense, dense.T) == symmetric
+    for vec in (x_star, b):
+        want = prove_exact(spmv, oracle, n, rp, ci, va, vec)
+        np.testing.assert_array_equal(want.astype(np.int64), dense @ vec.astype(np.int64))
+    # what the one-step CG test predicts from: r.z = b.b and p.q = b.(A b) are integers below 2^53
+    q = dense @ b.astype(np.int64)
+    assert 0 < int(b.astype(np.int64) @ q) < 2**53
+
+
+@pytest.mark.parametrize("name,L,k", ed.PAGERANK_CASES)
+def test_pagerank_graph_lands_on_its_lanes(spmv, name, L, k):
+    graph = importlib.import_module("test_gpu_pagerank").graph
+    rp, ci, va = ed.pagerank_graph(spmv, graph, k, 40 + k)
+    assert np.all(np.isfinite(va)) and np.all(va > 0)
+    assert ed.lanes_for(int(rp[-1]), ed.PAGERANK_N) == L
+    assert not np.isin(ci, np.array(ed.PAGERANK_DANGLING)).any()
+
+
+def test_ell_cases_are_exact(oracle):
+    for width, rows, rp, ci, va, x in ed.ell_cases():
+        ed.check_exact(rp, ci, va, x)
+        kk, ecols, evals = oracle.ell_from_csr(rp, ci, va)
+        assert kk == width and len(rp) - 1 == rows
+        np.testing.assert_array_equal(oracle.spmv_ell(rows, kk, ecols, evals, x), ed.exact_reference(rp, ci, va, x))
+    shapes = {(w, r % 4) for w, r, *_ in ed.ell_cases()}
+    assert shapes == {(w, m) for w in range(1, 10) for m in range(4)}

@@ -13,22 +13,12 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 spmv = importlib.import_module("gpu-spmv_amd")
 oracle = importlib.import_module("oracle")
 from conftest import reorder_err  # noqa: E402
+import exact_data  # noqa: E402
 
 
-def run_case(rng, rows, cols, lens, fold, ell):
-    lens = np.minimum(lens, cols).astype(np.int64)
-    # distinct ascending columns per row (a draw with repeats, de-duplicated: rows may come out a little shorter)
-    per_row = [np.unique(rng.integers(0, cols, size=n)) if n < cols else np.arange(cols) for n in lens]
-    lens = np.array([r.size for r in per_row], dtype=np.int64)
-    rp = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
-    ci = (np.concatenate(per_row) if per_row else np.empty(0)).astype(np.int32)
-    if fold:      # every column one value: the plan folds the values away
-        weight = rng.uniform(0.1, 2.0, size=cols).astype(np.float32)
-        va = weight[ci]
-    else:
-        va = rng.uniform(-1, 1, size=ci.size).astype(np.float32)
-    x = rng.uniform(-1, 1, size=cols).astype(np.float32)
-    want = oracle.spmv_csr(rp, ci, va, x)
+def device_results(rows, cols, rp, ci, va, x, fold, ell):
+    """Every y the tiled engine produces for one case (ELL source: two calls; CSR: VECTOR_CSR and MERGE_PATH, two
+    calls each, the second reusing the plan and meeting whatever the first left behind), and whether a plan was built."""
     d_x, d_y = spmv.CudaBuffer(cols), spmv.CudaBuffer(rows)
     d_x.copyFromHost(x, cols)
     if ell:
@@ -43,26 +33,65 @@ def run_case(rng, rows, cols, lens, fold, ell):
             assert spmv.spmv_ell(E, d_x, d_y, cfg, cols).error_code == 0
         got = d_y.copyToHost(rows)
         spmv.ell_destroy(E)
-        return reorder_err(rp, ci, va, x, want, got), True
+        return [got], True
     A = spmv.csr_from_arrays(rows, cols, rp, ci, va)
     assert spmv.csr_to_gpu(A) == 0
-    worst, planned = 0.0, False
+    results, planned = [], False
     for kernel in (1, 2):
-        for _ in range(2):          # the second call reuses the plan (and meets whatever the first left behind)
+        for _ in range(2):
             res = spmv.spmv_csr(A, d_x, d_y, spmv.SpMVConfig(kernel_type=kernel, use_texture=True), cols)
             assert res.error_code == 0
-            worst = max(worst, reorder_err(rp, ci, va, x, want, d_y.copyToHost(rows)))
+            results.append(d_y.copyToHost(rows))
         planned = planned or bool(spmv.csr_has_tiled_plan(A))
     info = spmv.csr_tiled_info(A)
     if fold and info is not None and info["entries_in_cells"] > 0:
         assert info["values_folded"], (rows, cols, info)
     spmv.csr_destroy(A)
+    return results, planned
+
+
+def exact_pass(rng, rows, cols, rp, ci, fold, ell):
+    """The same structure with exact data (tests/exact_data.py: small integers, for `fold` one integer weight per
+    column): the engine adds in fp64 LDS and rounds once, so every y must equal the int64 reference bit for bit."""
+    if fold:
+        weight = (rng.integers(1, 9, size=cols) * rng.choice([-1, 1], size=cols)).astype(np.float32)
+        va = weight[ci]
+    else:
+        va = (rng.integers(1, 9, size=ci.size) * rng.choice([-1, 1], size=ci.size)).astype(np.float32)
+    x = rng.integers(-64, 65, size=cols).astype(np.float32)
+    exact_data.check_exact(rp, ci, va, x)
+    want = exact_data.exact_reference(rp, ci, va, x)
+    results, _ = device_results(rows, cols, rp, ci, va, x, fold, ell)
+    for call, got in enumerate(results):
+        bad = np.flatnonzero(got.view(np.uint32) != want.view(np.uint32))
+        assert bad.size == 0, (rows, cols, fold, ell, call, bad.size,
+                               [(int(r), float(got[r]), float(want[r]), int(rp[r + 1] - rp[r])) for r in bad[:8]])
+
+
+def run_case(rng, exact_rng, rows, cols, lens, fold, ell):
+    lens = np.minimum(lens, cols).astype(np.int64)
+    # distinct ascending columns per row (a draw with repeats, de-duplicated: rows may come out a little shorter)
+    per_row = [np.unique(rng.integers(0, cols, size=n)) if n < cols else np.arange(cols) for n in lens]
+    lens = np.array([r.size for r in per_row], dtype=np.int64)
+    rp = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    ci = (np.concatenate(per_row) if per_row else np.empty(0)).astype(np.int32)
+    if fold:      # every column one value: the plan folds the values away
+        weight = rng.uniform(0.1, 2.0, size=cols).astype(np.float32)
+        va = weight[ci]
+    else:
+        va = rng.uniform(-1, 1, size=ci.size).astype(np.float32)
+    x = rng.uniform(-1, 1, size=cols).astype(np.float32)
+    want = oracle.spmv_csr(rp, ci, va, x)
+    results, planned = device_results(rows, cols, rp, ci, va, x, fold, ell)
+    worst = max(reorder_err(rp, ci, va, x, want, got) for got in results)
+    exact_pass(exact_rng, rows, cols, rp, ci, fold, ell)      # second pass, after the tolerance pass
     return worst, planned
 
 
 def main():
     spmv.require_gpu()
     rng = np.random.default_rng(2024)
+    exact_rng = np.random.default_rng(2025)        # its own stream: the tolerance pass draws what it always drew
     shapes = [(1, 1), (1, 5000), (3, 4097), (64, 4096), (65, 8193), (1000, 70_000), (4999, 33_000),
               (20_000, 100), (9793, 9793), (130, 200_000)]
     cases = planned_cases = 0
@@ -83,7 +112,7 @@ def main():
                 for ell in (False, True):
                     if ell and (kind == "long" or rows * int(max(lens.max(), 1)) > 4_000_000):
                         continue
-                    err, planned = run_case(rng, rows, cols, lens, fold, ell)
+                    err, planned = run_case(rng, exact_rng, rows, cols, lens, fold, ell)
                     assert err <= 1e-5, (rows, cols, kind, fold, ell, err)
                     worst = max(worst, err)
                     cases += 1
