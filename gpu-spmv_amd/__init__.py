@@ -229,6 +229,9 @@ _SIGNATURES = {
     "spmv_c_csr_tiled_stats": (c_int, [POINTER(CSRMatrix), POINTER(c_double)]),
     "spmv_c_csr_tiled_checksum": (c_int, [POINTER(CSRMatrix), POINTER(c_uint64)]),
     "spmv_c_csr_tiled_folded": (c_int, [POINTER(CSRMatrix)]),
+    "spmv_c_csr_tiled_items": (c_int, [POINTER(CSRMatrix)]),
+    "spmv_c_ell_tiled_info": (c_int, [POINTER(ELLMatrix), POINTER(c_int64)]),
+    "spmv_c_csr_transpose_tiled_info": (c_int, [POINTER(CSRMatrix), POINTER(c_int64)]),
     "spmv_c_spmv_csr_async": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(SpMVConfig), c_int,
                                       c_void_p]),
     "spmv_c_spmv_ell_async": (c_int, [POINTER(ELLMatrix), c_void_p, c_void_p, POINTER(SpMVConfig), c_int,
@@ -706,6 +709,34 @@ def csr_tiled_info(A):
         info["plan_bytes"] = int(stats[1])
         info["entries_in_cells"] = int(stats[3])
     return info
+
+
+def csr_tiled_items(A) -> int:
+    """Number of phase-1 work items of the matrix's cached tiled plan, or -1 without a plan."""
+    return int(lib().spmv_c_csr_tiled_items(A))
+
+
+_PLAN_INFO10 = ("strip_cols", "tile_rows", "num_strips", "num_tiles", "slots_in_cells", "long_rows", "slots_per_lane",
+                "long_row_limit", "values_folded", "num_items")
+
+
+def _plan_info10(call, handle):
+    out = (c_int64 * 10)()
+    if not call(handle, out):
+        return None
+    info = dict(zip(_PLAN_INFO10, (int(v) for v in out)))
+    info["values_folded"] = bool(info["values_folded"])
+    return info
+
+
+def ell_tiled_info(E):
+    """dict describing the tiled plan built from the ELL matrix's slabs (spmv_ell with use_texture), or None."""
+    return _plan_info10(lib().spmv_c_ell_tiled_info, E)
+
+
+def csr_transpose_tiled_info(A):
+    """dict describing the tiled plan owned by A's cached transpose (spmv_csr_transpose with use_texture), or None."""
+    return _plan_info10(lib().spmv_c_csr_transpose_tiled_info, A)
 
 
 def spmv_csr_async(A, d_x, d_y, config=None, vec_size=-1, stream=None) -> int:

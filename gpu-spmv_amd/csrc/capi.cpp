@@ -369,6 +369,45 @@ int spmv_c_csr_tiled_folded(const spmv_c_csr* A_c) {
     return aux && aux->tiled && aux->tiled->col_weight ? 1 : 0;
 }
 
+int spmv_c_csr_tiled_items(const spmv_c_csr* A_c) {
+    const CSRMatrix* A = cxx(A_c);
+    if (!A || !A->d_row_ptrs) return -1;
+    detail::CsrAux* aux = detail::aux_lookup(A->d_row_ptrs, false);
+    return aux && aux->tiled ? aux->tiled->num_items : -1;
+}
+
+namespace {
+// out[10] = the eight numbers of spmv_c_csr_tiled_info, then values folded (0 / 1) and the phase-1 item count
+int plan_info10(const detail::TiledPlan& p, int64_t out[10]) {
+    const int64_t v[10] = {p.strip_cols, p.tile_rows, p.num_strips, p.num_tiles, p.nnz, p.num_long, 4, p.long_row,
+                           p.col_weight ? 1 : 0, p.num_items};
+    std::memcpy(out, v, sizeof(v));
+    return 1;
+}
+}  // namespace
+
+int spmv_c_ell_tiled_info(const spmv_c_ell* E_c, int64_t out[10]) {
+    const ELLMatrix* E = cxx(E_c);
+    if (!E || !E->d_col_indices || !out) return 0;
+    detail::EllAux* aux = detail::ell_aux_lookup(E->d_col_indices, false);
+    return aux && aux->tiled ? plan_info10(*aux->tiled, out) : 0;
+}
+
+int spmv_c_csr_transpose_tiled_info(const spmv_c_csr* A_c, int64_t out[10]) {
+    const CSRMatrix* A = cxx(A_c);
+    if (!A || !A->d_row_ptrs || !out) return 0;
+    detail::CsrAux* aux = detail::aux_lookup(A->d_row_ptrs, false);
+    if (!aux) return 0;
+    std::shared_ptr<CSRMatrix> at;
+    {
+        std::lock_guard<std::mutex> guard(aux->transpose_lock);
+        at = aux->transpose;
+    }
+    if (!at || !at->d_row_ptrs) return 0;
+    detail::CsrAux* at_aux = detail::aux_lookup(at->d_row_ptrs, false);
+    return at_aux && at_aux->tiled ? plan_info10(*at_aux->tiled, out) : 0;
+}
+
 int spmv_c_spmv_csr_async(const spmv_c_csr* A, const float* d_x, float* d_y,
                           const spmv_c_config* config, int vec_size, void* hip_stream) {
     return spmv_csr_async(cxx(A), d_x, d_y, cxx(config), vec_size, as_stream(hip_stream));

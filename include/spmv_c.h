@@ -216,6 +216,15 @@ int spmv_c_csr_tiled_checksum(const spmv_c_csr* A, uint64_t out[4]);
  * entry of a column bit-identical: adjacency / column-stochastic matrices), so that the tiled engine
  * streams no values; 0 otherwise or without a plan.  SPMV_TILED_FOLD=0 at build time disables it. */
 int spmv_c_csr_tiled_folded(const spmv_c_csr* A);
+/* extension: the number of phase-1 work items of the matrix's plan (every strip's slots cut into equal pieces of
+ * at most the item size; SPMV_DEBUG=item=N sets that size); -1 without a plan.  Read-only, for boundary-case tests. */
+int spmv_c_csr_tiled_items(const spmv_c_csr* A);
+/* extension: the plan the LDS-tiled engine built from an ELL matrix's slabs (spmv_ell with use_texture), and the one
+ * owned by the cached transpose of A (spmv_csr_transpose with use_texture) — out[10] = the eight numbers of
+ * spmv_c_csr_tiled_info, then values folded (0 / 1) and the phase-1 item count; returns 0 if there is none (not
+ * eligible, not built yet, or the build failed and the call took the direct kernels).  Read-only. */
+int spmv_c_ell_tiled_info(const spmv_c_ell* E, int64_t out[10]);
+int spmv_c_csr_transpose_tiled_info(const spmv_c_csr* A, int64_t out[10]);
 /* extension: enqueue on a caller stream without timing or synchronisation */
 int spmv_c_spmv_csr_async(const spmv_c_csr* A, const float* d_x, float* d_y,
                           const spmv_c_config* config, int vec_size, void* hip_stream);

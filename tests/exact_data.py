@@ -8,6 +8,8 @@ reduction step, a gather from a neighbour's entry or a lost carry shows as a wro
 The module also holds the catalogue of matrices the exact GPU tests run (tests/test_gpu_lane_sweep.py), so that
 tests/test_exact_data.py can prove, without a GPU, that each one is exact and lands on the kernel instantiation
 its name claims.  A plain module, imported by those tests; everything is built with numpy from fixed seeds."""
+import math
+
 import numpy as np
 
 EXACT_LIMIT = 1 << 24
@@ -305,3 +307,366 @@ def ell_cases():
             lens = rng.integers(0, width + 1, size=rows)
             lens[rng.integers(0, rows)] = width
             yield (width, rows) + exact_csr(rng, lens, 300)
+
+
+# ------------------------------------------------------------------------------------------ dyadic PageRank
+# With n = 2^k nodes, a dyadic damping factor (0.5), every out-degree a power of two (values 2^-j) and the start
+# vector 1/n, every quantity of pagerank()'s update r_new = d * (A r) + d * s / n + (1 - d) / n is a dyadic rational.
+# While each of them fits float32's 24 bits, every summation order and every rounding gives the same bits, and the
+# device result can be held to BIT EQUALITY with integer arithmetic.  The prover below counts the steps for which
+# that holds; nothing is assumed.
+def dyadic_graph(rng, n, out_degrees, dangling, hubs):
+    """(row_ptrs, cols, vals) of an n x n adjacency matrix, n a power of two: column c links to out-degree(c)
+    distinct rows, the degree drawn from `out_degrees` (powers of two) and stored as 2^-j in every entry of the
+    column (one value per column: the tiled plan folds them); the columns in `dangling` have no entries; `hubs` is
+    a list of (row, length): that row is linked from `length` columns; rows with row % 13 == 5 stay empty unless
+    they are hubs.  Columns inside a row are distinct and ascending."""
+    assert n & (n - 1) == 0 and all(g & (g - 1) == 0 for g in out_degrees)
+    deg = rng.choice(np.asarray(out_degrees, np.int64), size=n)
+    deg[np.asarray(dangling, np.int64)] = 0
+    hub_rows = np.array([h for h, _ in hubs], np.int64)
+    allowed = np.ones(n, bool)
+    allowed[5::13] = False
+    allowed[hub_rows] = False
+    perm = rng.permutation(np.flatnonzero(allowed))
+    m = perm.size
+    assert max(out_degrees) <= m
+    first = np.cumsum(deg) - deg
+    col_of = np.repeat(np.arange(n, dtype=np.int64), deg)
+    within = np.arange(col_of.size, dtype=np.int64) - np.repeat(first, deg)
+    row_of = perm[(rng.integers(0, m, size=n)[col_of] + within) % m]          # a window of the permutation: distinct rows
+    for k, (hub, length) in enumerate(hubs):                                    # link k of `length` columns goes to the hub
+        candidates = np.flatnonzero(deg > k)
+        assert candidates.size >= length
+        row_of[first[rng.choice(candidates, size=length, replace=False)] + k] = hub
+    order = np.lexsort((col_of, row_of))
+    ci = col_of[order].astype(np.int32)
+    rp = np.concatenate([[0], np.cumsum(np.bincount(row_of, minlength=n))]).astype(np.int32)
+    va = (1.0 / deg[ci]).astype(np.float32)
+    return rp, ci, va
+
+
+def _fits_float32(v):
+    """Whether each integer of v (any common power-of-two scale) has at most 24 significant bits."""
+    v = np.abs(np.asarray(v, np.int64))
+    return bool(np.all((v >> 24) < (v & -v) + (v == 0)))
+
+
+def _dyadic_run(rp, ci, va, n, damping, steps):
+    """pagerank()'s loop in int64 over a power-of-two quantum.  Yields per step (ranks float32, exact residual
+    float64, whether every operation of the step was exact in float32)."""
+    k = n.bit_length() - 1
+    assert n == 1 << k
+    d = float(np.float32(damping)).as_integer_ratio()
+    dn, dk = d[0], d[1].bit_length() - 1
+    assert d[1] == 1 << dk and 0 < dn < d[1]
+    mant, expo = np.frexp(np.asarray(va, np.float32))
+    assert np.all(mant == 0.5)
+    j = (1 - expo).astype(np.int64)
+    J = int(j.max())
+    rp64, ci = np.asarray(rp, np.int64), np.asarray(ci, np.int64)
+    dangling = np.bincount(ci, minlength=n) == 0
+    filled = np.flatnonzero(np.diff(rp64) > 0)
+    R, e = np.ones(n, np.int64), k                                   # ranks = R * 2^-e
+    for _ in range(steps):
+        E = e + J + dk + k                                           # every quantity of the step is a multiple of 2^-E
+        if E > 62:
+            raise OverflowError("the step does not fit int64: not provable here")
+        prod = R[ci] << (J - j)                                      # * 2^-(e + J)
+        run = np.concatenate([[0], np.cumsum(prod)])
+        acc = run[rp64[1:]] - run[rp64[:-1]]
+        any_bit = np.bitwise_or.reduceat(prod, rp64[filled]) if filled.size else np.zeros(0, np.int64)
+        quantum = any_bit & -any_bit                                 # per row: products are multiples of it ...
+        exact = bool(np.all((acc[filled] >> 24) < quantum))          # ... and the row's sum is below 2^24 of them
+        s = int(R[dangling].sum())                                   # * 2^-e: the dangling mass, float(double sum)
+        dacc = dn * acc                                              # * 2^-(e + J + dk)
+        ds = dn * s                                                  # d * s at 2^-(e + dk); d * s / n at 2^-(e + dk + k)
+        tele = (1 << dk) - dn                                        # 1 - d at 2^-dk; (1 - d) / n at 2^-(dk + k)
+        first = (dacc << k) + (ds << J)                              # d * acc + d * s / n
+        fresh = first + (tele << (e + J))
+        diff = fresh - (R << (E - e))
+        exact = exact and all(_fits_float32(v) for v in (s, dacc, ds, tele, first, fresh, diff))
+        exact = exact and int(fresh.sum()) == 1 << E                 # mass 1: the final r /= sum(r) divides by 1.0f
+        square_sum = sum(int(v) * int(v) for v in diff[diff != 0])
+        residual = math.ldexp(math.sqrt(square_sum), -E)
+        low = int(np.bitwise_or.reduce(fresh))
+        shift = (low & -low).bit_length() - 1
+        R, e = fresh >> shift, E - shift
+        yield np.ldexp(R.astype(np.float64), -e).astype(np.float32), residual, exact
+
+
+def dyadic_pagerank(rp, ci, va, n, damping, steps):
+    """(ranks float32, exact residual sqrt(sum (r_new - r_old)^2) of the last step as float64) after `steps` steps
+    of r_new = d * (A r) + d * s / n + (1 - d) / n from r = 1 / n, s = the old ranks summed over the dangling nodes:
+    the library's formula in integers."""
+    assert steps >= 1
+    for ranks, residual, _ in _dyadic_run(rp, ci, va, n, damping, steps):
+        pass
+    return ranks, residual
+
+
+def exact_steps(rp, ci, va, n, damping, max_steps=4):
+    """Number of leading steps (up to max_steps) in which everything the device computes is exact in float32: per
+    row all products and the row's sum are multiples of one quantum q with sum < 2^24 q (check_exact's condition,
+    scaled); s, d * acc, d * s, d * s / n, (1 - d), both partial sums of the update, r_new and r_new - r_old are
+    representable; the ranks sum to exactly 1."""
+    count = 0
+    try:
+        for _, _, exact in _dyadic_run(rp, ci, va, n, damping, max_steps):
+            if not exact:
+                break
+            count += 1
+    except OverflowError:
+        pass
+    return count
+
+
+DYADIC_DAMPING = 0.5
+DYADIC_DIRECT_N = 2048
+DYADIC_DIRECT_DANGLING = (3, 64, 700, 701, 1024, 1500, 2046, 2047)         # a power-of-two count: d * s / n stays short
+DYADIC_DIRECT = [("L%d" % L, L, (1, 2, 4) if L == 1 else (2 * L, 4 * L)) for L in LANES]
+# name -> (n, W, R, dangling nodes, fold, pr_plan_after, steps wanted at least)
+DYADIC_TILED = {
+    "n16_4096x64_dangling_fold": (1 << 16, 4096, 64, 1 << 10, True, 0, 1),
+    "n16_8192x1024_closed_fold": (1 << 16, 8192, 1024, 0, True, 0, 3),
+    "n16_16384x9984_dangling_stream": (1 << 16, 16384, 9984, 1 << 10, False, 0, 1),
+    "n18_4096x64_closed_stream": (1 << 18, 4096, 64, 0, False, 0, 3),
+    "n18_8192x1024_dangling_fold": (1 << 18, 8192, 1024, 1 << 12, True, 0, 1),
+    "n18_16384x9984_closed_fold": (1 << 18, 16384, 9984, 0, True, 0, 3),
+    "n16_8192x1024_closed_switch_after_1": (1 << 16, 8192, 1024, 0, True, 1, 3),
+}
+_dyadic_cache = {}
+
+
+def dyadic_case(name):
+    """(n, row_ptrs, cols, vals, steps, ranks, residual) of a direct ("L8") or tiled (DYADIC_TILED) case: steps =
+    exact_steps, ranks / residual = dyadic_pagerank at that count (None when steps == 0)."""
+    if name in _dyadic_cache:
+        return _dyadic_cache[name]
+    if name in DYADIC_TILED:
+        n, _, _, dangling_count, _, _, _ = DYADIC_TILED[name]
+        rng = np.random.default_rng(sum(name.encode()))
+        dangling = rng.choice(n, size=dangling_count, replace=False)
+        degrees = (2, 4, 8, 16) if dangling_count else (1, 2)
+        hubs = [(n // 3, 5000), (n - 1, 2600)]                             # beyond the long-row limit 8 * strips (<= 512 here)
+        if dangling_count:
+            hubs.append((n // 3 + 1, 700))                                 # (link 2 of a column: out-degree > 2 only)
+    else:
+        index, (_, L, degrees) = next((i, c) for i, c in enumerate(DYADIC_DIRECT) if c[0] == name)
+        n, dangling = DYADIC_DIRECT_N, np.array(DYADIC_DIRECT_DANGLING)
+        rng = np.random.default_rng(600 + index)
+        hubs = [(n // 3, 1500), (n - 1, 600)]
+    rp, ci, va = dyadic_graph(rng, n, degrees, dangling, hubs)
+    steps = exact_steps(rp, ci, va, n, DYADIC_DAMPING)
+    ranks, residual = dyadic_pagerank(rp, ci, va, n, DYADIC_DAMPING, steps) if steps else (None, None)
+    _dyadic_cache[name] = (n, rp, ci, va, steps, ranks, residual)
+    return _dyadic_cache[name]
+
+
+def tiled_debug(W, R, extra=""):
+    """The SPMV_DEBUG string that pushes a small matrix through the tiled engine at strip width W, tile height R."""
+    return "min_cols=1,min_nnz=1,strip=%d,tile=%d%s" % (W, R, "," + extra if extra else "")
+
+
+# ------------------------------------------------------------------------------------------ plan-geometry catalogue
+# Every case: a small matrix and the SPMV_DEBUG string under which the tiled engine must build the plan the case
+# claims (strip width W, tile height R, strips, tiles, long rows or none, folded values or a value stream, and where
+# the construction fixes them the slot, item and long-row counts).  tests/test_exact_data.py proves the data exact
+# and W / R from the host logic; tests/test_gpu_tiled_geometry.py asserts the rest from csr_tiled_info.
+def default_long_row(strips):
+    """build_plan (csrc/tiled.hip): rows with more entries than max(64, min(4096, 8 * strips)) are long."""
+    return max(64, min(4096, 8 * strips))
+
+
+def _scattered(rng, rows, cols, W, max_len=40):
+    """Ragged rows of up to max_len random columns, every 11th row empty, plus entries at local columns 0 and W - 1
+    of every strip, in the matrix's last column (the last, partial strip) and in its last row."""
+    lens = rng.integers(0, max_len + 1, size=rows)
+    lens[::11] = 0
+    rr = np.repeat(np.arange(rows), lens)
+    cc = rng.integers(0, cols, size=rr.size)
+    edges = sorted({c for s in range(-(-cols // W)) for c in (s * W, min(s * W + W - 1, cols - 1))} | {cols - 1})
+    er = np.concatenate([rng.integers(0, rows, size=3 * len(edges)), np.full(len(edges), rows - 1)])
+    ec = np.concatenate([np.repeat(edges, 3), edges])
+    return np.concatenate([rr, er]), np.concatenate([cc, ec])
+
+
+def _row_deltas(rng, R):
+    """Two tiles of R = 9984 rows, four strips of 4096 columns.  Strip 0: rows 1, 254, 255, 256, 509, 510, 511 apart
+    in one cell; strip 1: rows 0 and R - 1 (9983 apart: 39 skip markers); strip 2: its only entry in the tile's last
+    row (tile 0), an empty cell (tile 1); strip 3: a scattered background.  Tile 1 repeats it seven rows down."""
+    rr, cc = [], []
+    steps = np.cumsum([0, 1, 254, 255, 256, 509, 510, 511])
+    for tile, shift in ((0, 0), (1, 7)):
+        base = tile * R
+        for r in steps + shift:
+            for c in rng.choice(4096, size=int(rng.integers(1, 4)), replace=False):
+                rr.append(base + r), cc.append(c)
+        rr += [base + shift, base + shift, base + R - 1]
+        cc += [4096 + 5, 4096 + 4095, 4096 + 17]
+        if tile == 0:
+            rr.append(base + R - 1), cc.append(2 * 4096)
+    back_r = rng.integers(0, 2 * R, size=6000)
+    return np.concatenate([rr, back_r]), np.concatenate([cc, 3 * 4096 + rng.integers(0, 4096, size=6000)])
+
+
+ITEM_STRIP_ENTRIES = (1023, 1024, 1025, 4096, 0, 2048)     # per strip; the last one half in tile 0, half in tile 1
+ITEM_SLOTS = 1024 + 1024 + 1028 + 4096 + 0 + 2048          # cells are padded to multiples of four slots
+ITEMS_AT_1024 = 1 + 1 + 2 + 4 + 0 + 2                      # ceil(slots / 1024) per strip
+ITEMS_AT_DEFAULT = 5                                       # default item size max(4096, W): one per non-empty strip
+
+
+def _item_strips(rng):
+    """Two tiles of 1024 rows, six strips of 4096 columns holding ITEM_STRIP_ENTRIES entries in consecutive rows (no
+    skip markers), so that every strip's slot count is known: an item that ends at a cell end (strip 5 at item=1024),
+    a strip of several items, strips of exactly one, a strip shorter than one item and an empty strip."""
+    rr, cc = [], []
+    for strip, count in enumerate(ITEM_STRIP_ENTRIES):
+        i = np.arange(count)
+        rows = i % 1024 if strip < 5 else i            # strip 5: rows 0..2047, one entry each
+        rr.append(rows), cc.append(strip * 4096 + (i // 1024) * 7 + (rows * 13) % 5 + 100 * (i // 1024))
+    return np.concatenate(rr), np.concatenate(cc)
+
+
+LONG_LIMIT = 64                                            # long_cap=64,long_factor=1
+LONG_ROW_LENGTHS = {10: 64, 20: 65,                        # tile 0: exactly the limit (short), one more (long)
+                    70: 512, 80: 513, 100: 1024,           # tile 1: three long rows; 512-entry chunks: 1, 2, 2
+                    130: 65, 140: 100, 150: 200, 160: 66, 191: 90,      # tile 2: long rows only
+                    255: 5000}                             # tile 3: the matrix's last row
+
+
+def _long_rows(rng):
+    """Four tiles of 64 rows, three strips: LONG_ROW_LENGTHS, short ragged rows elsewhere except in tile 2."""
+    rows, cols = 256, 3 * 4096
+    lens = rng.integers(0, 20, size=rows)
+    lens[128:192] = 0
+    for r, n in LONG_ROW_LENGTHS.items():
+        lens[r] = n
+    rr = np.repeat(np.arange(rows), lens)
+    return rr, np.concatenate([rng.choice(cols, size=n, replace=False) for n in lens])      # distinct: lengths hold
+
+
+def _geometry_cases():
+    cases = {}
+
+    def add(name, rows, cols, W, R, structure, fold, extra="", **expect):
+        strips, tiles = -(-cols // W), -(-rows // R)
+        cases[name] = dict(name=name, rows=rows, cols=cols, W=W, R=R, strips=strips, tiles=tiles, fold=fold,
+                           debug=tiled_debug(W, R, extra), structure=structure, long_rows=0, **expect)
+
+    for W in (4096, 8192, 16384, 32768):                   # strip width x fold x columns around a strip end
+        s = 2 if W == 32768 else 3
+        for fold in (False, True):
+            for off in (-1, 0, 1):
+                cols = s * W + off
+                add("strip_%d_%s_cols%+d" % (W, "fold" if fold else "stream", off), 3000, cols, W, 1024,
+                    lambda rng, cols=cols, W=W: _scattered(rng, 3000, cols, W), fold)
+    for R, t in ((64, 3), (128, 3), (1024, 3), (4800, 2), (9984, 2)):      # tile height x rows around a tile end
+        for off in (-1, 0, 1):
+            rows = t * R + off
+            add("tile_%d_rows%+d" % (R, off), rows, 10000, 4096, R,
+                lambda rng, rows=rows: _scattered(rng, rows, 10000, 4096), fold=(off == 0))
+    for fold in (False, True):
+        tag = "fold" if fold else "stream"
+        add("row_deltas_" + tag, 2 * 9984, 4 * 4096, 4096, 9984, lambda rng: _row_deltas(rng, 9984), fold)
+        add("items_1024_" + tag, 2048, 6 * 4096, 4096, 1024, _item_strips, fold, extra="item=1024",
+            items=ITEMS_AT_1024, slots=ITEM_SLOTS)
+        add("items_default_" + tag, 2048, 6 * 4096, 4096, 1024, _item_strips, fold,
+            items=ITEMS_AT_DEFAULT, slots=ITEM_SLOTS)
+        add("long_rows_" + tag, 256, 3 * 4096, 4096, 64, _long_rows, fold, extra="long_cap=64,long_factor=1")
+        cases["long_rows_" + tag]["long_rows"] = sum(n > LONG_LIMIT for n in LONG_ROW_LENGTHS.values())
+    return cases
+
+
+GEOMETRY_CASES = _geometry_cases()
+GEOMETRY_NAMES = list(GEOMETRY_CASES)
+BUILDER_FORM_NAMES = ["strip_8192_stream_cols+1", "row_deltas_stream", "long_rows_fold"]
+ENTRY_POINT_GEOMETRIES = [(4096, 64), (16384, 9984)]
+_geometry_cache = {}
+
+
+def geometry_matrix(name):
+    """(case, row_ptrs, cols, vals, x): distinct (row, column) pairs in row-major order; values one integer weight
+    per column when the case folds, else drawn per entry; checked exact."""
+    if name not in _geometry_cache:
+        case = GEOMETRY_CASES[name]
+        rng = np.random.default_rng(sum(name.encode()))
+        rr, cc = case["structure"](rng)
+        keys = np.unique(np.asarray(rr, np.int64) * case["cols"] + np.asarray(cc, np.int64))
+        rr, ci = keys // case["cols"], (keys % case["cols"]).astype(np.int32)
+        rp = np.concatenate([[0], np.cumsum(np.bincount(rr, minlength=case["rows"]))]).astype(np.int32)
+        if case["fold"]:
+            weight = (rng.integers(1, 9, size=case["cols"]) * rng.choice([-1, 1], size=case["cols"])).astype(np.float32)
+            va = weight[ci]
+        else:
+            va = (rng.integers(1, 9, size=ci.size) * rng.choice([-1, 1], size=ci.size)).astype(np.float32)
+        x = rng.integers(-64, 65, size=case["cols"]).astype(np.float32)
+        check_exact(rp, ci, va, x)
+        _geometry_cache[name] = (case, rp, ci, va, x)
+    return _geometry_cache[name]
+
+
+def entry_point_systems(W):
+    """The integer SPD and non-symmetric systems the solvers' tiled route runs at strip width W: n = 20 011, so that
+    4096-column strips give five of them and 9984-row tiles three."""
+    n = 20011
+    return integer_spd(n, 50000, seed=W), integer_nonsym(n, 90000, seed=W + 1)
+
+
+BICG_ALPHA_INVERSE = 64
+
+
+def bicgstab_first_step_system(n, offdiagonal, seed, K=BICG_ALPHA_INVERSE):
+    """(n, row_ptrs, cols, vals, b) of a non-symmetric, strictly row diagonally dominant integer system S + D built so
+    that BiCGSTAB's first step from x0 = 0 without a preconditioner stays exact: b holds non-zero integers in
+    [-64, 64] and the diagonal is K + delta_i, |delta_i| <= 8, with sum_i delta_i b_i^2 == -b.(S b), so that
+    b.(A b) == K b.b and alpha = rho / (rhat.v) == 1 / K exactly (K a power of two).  Then s = b - (A b) / K is a
+    vector of multiples of 1 / K and t = A s is exact as well (bicgstab_first_step)."""
+    rng = np.random.default_rng(seed)
+    r, c, v = _integer_offdiagonal(rng, n, offdiagonal, 3)
+    b = rng.integers(1, 65, size=n) * rng.choice([-1, 1], size=n)
+    sb = np.bincount(r, weights=v * b[c], minlength=n).astype(np.int64)
+    target = -int(b @ sb)
+    delta = np.zeros(n, np.int64)
+    for m in range(64, 0, -1):                       # coin change over b_i^2, largest first; |b| == 1 takes the rest
+        rows = np.flatnonzero(np.abs(b) == m)
+        if rows.size == 0:
+            continue
+        q = max(-8 * rows.size, min(8 * rows.size, int(target / (m * m))))       # rounded towards zero
+        base, extra = divmod(abs(q), rows.size)
+        delta[rows] = np.sign(q) * base
+        delta[rows[:extra]] += np.sign(q)
+        target -= q * m * m
+    assert target == 0 and np.abs(delta).max() <= 8
+    d = K + delta
+    assert np.all(d > np.bincount(r, weights=np.abs(v), minlength=n))            # strictly dominant
+    diag = np.arange(n)
+    n, rp, ci, va = _csr_from_triplets(n, np.concatenate([r, diag]), np.concatenate([c, diag]), np.concatenate([v, d]))
+    return n, rp, ci, va, b.astype(np.float32)
+
+
+def bicgstab_first_step(rp, ci, va, b, K=BICG_ALPHA_INVERSE):
+    """x after ONE BiCGSTAB step from x0 = 0, no preconditioner, under bicgstab.h's rules, for a system of
+    bicgstab_first_step_system: p = rhat = r = b, v = A b (integers), alpha = fp32(b.b / b.v) = 1 / K, s = r - alpha v
+    (multiples of 1 / K, exact), t = A s (exact), omega = fp32(t.s / t.t) (integer dot products scaled by K^-2, below
+    2^53: exact in fp64 in any order, one division, one rounding), x = fma(omega, s, fma(alpha, p, 0)): alpha p is
+    exact and omega s + alpha p has fewer than 53 significant bits, so fp64 holds it exactly and the fp32 rounding of
+    that is the fused result.  Every claim is asserted here.  Returns (x float32, omega)."""
+    b64 = np.asarray(b).astype(np.int64)
+    check_exact(rp, ci, va, b)
+    v = exact_reference(rp, ci, va, b).astype(np.int64)
+    assert int(b64 @ v) == K * int(b64 @ b64)                                    # alpha == 1 / K
+    ks = K * b64 - v                                                             # K s
+    ks32 = ks.astype(np.float32)
+    check_exact(rp, ci, va, ks32)
+    kt = exact_reference(rp, ci, va, ks32).astype(np.int64)                      # K t
+    ts, tt = int(kt @ ks), int(kt @ kt)
+    assert 0 < tt < 2**53 and abs(ts) < 2**53 and ts != 0
+    omega = np.float32(np.float64(ts) / np.float64(tt))
+    mant, expo = np.frexp(np.float64(omega))
+    w_int, w_exp = int(mant * 2**24), int(expo) - 24                             # omega == w_int * 2^w_exp
+    assert np.float64(w_int) * 2.0**w_exp == np.float64(omega) and w_exp <= 0
+    scaled = w_int * ks.astype(object) + (b64.astype(object) << -w_exp)          # K 2^-w_exp (omega s + b / K)
+    assert max(abs(int(u)) for u in scaled) < 2**53
+    x = (np.float64(omega) * (ks.astype(np.float64) / K) + b64.astype(np.float64) / K).astype(np.float32)
+    return x, omega

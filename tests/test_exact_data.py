@@ -173,3 +173,90 @@ def test_ell_cases_are_exact(oracle):
         np.testing.assert_array_equal(oracle.spmv_ell(rows, kk, ecols, evals, x), ed.exact_reference(rp, ci, va, x))
     shapes = {(w, r % 4) for w, r, *_ in ed.ell_cases()}
     assert shapes == {(w, m) for w in range(1, 10) for m in range(4)}
+
+
+# ------------------------------------------------------------------------------------------ dyadic PageRank
+def test_dyadic_prover_on_a_graph_small_enough_to_do_by_hand():
+    """Two nodes linking to each other and a dangling third, n padded to 4 with a second dangling node, d = 0.5:
+    A r = (1/4, 1/4, 0, 0), s = 1/2, r_new = 1/8 + 1/16 + 1/8 for the first two, 1/16 + 1/8 for the others."""
+    rp, ci, va = np.array([0, 1, 2, 2, 2], np.int32), np.array([1, 0], np.int32), np.ones(2, np.float32)
+    ranks, residual = ed.dyadic_pagerank(rp, ci, va, 4, 0.5, 1)
+    np.testing.assert_array_equal(ranks, np.array([5, 5, 3, 3], np.float32) / 16)
+    assert residual == np.sqrt(4 * (1 / 16) ** 2) and ed.exact_steps(rp, ci, va, 4, 0.5) >= 1
+    # a value that needs more than 24 bits in the first step is noticed: 2^24 + 1 links of weight 1 cannot be built
+    # here, so shrink the budget instead: one rank of 25 significant bits fails the representability test
+    assert ed._fits_float32(np.array([(1 << 24) - 1, 1 << 40, 0, 3 << 50])) and not ed._fits_float32([(1 << 24) + 1])
+
+
+@pytest.mark.parametrize("name", [c[0] for c in ed.DYADIC_DIRECT] + list(ed.DYADIC_TILED))
+def test_dyadic_case_is_exact_and_restates_the_oracle(oracle, name):
+    """exact_steps >= 1 (>= 3 without dangling nodes): a case with 0 is a construction error.  The integer PageRank
+    agrees with the oracle's fp64-sum loop to 1e-6 relative at the same step count (a restatement check)."""
+    n, rp, ci, va, steps, ranks, residual = ed.dyadic_case(name)
+    lens = np.diff(rp.astype(np.int64))
+    dangling = np.flatnonzero(np.bincount(ci, minlength=n) == 0)
+    assert n & (n - 1) == 0 and (lens == 0).sum() >= n // 14 and np.all(np.frexp(va)[0] == 0.5)
+    for r in np.flatnonzero(lens > 1)[:200]:
+        assert np.all(np.diff(ci[rp[r]:rp[r + 1]]) > 0)                       # distinct ascending columns
+    if name in ed.DYADIC_TILED:
+        _, W, R, dangling_count, _, _, wanted = ed.DYADIC_TILED[name]
+        assert dangling.size == dangling_count and steps >= wanted
+        assert (lens > ed.default_long_row(-(-n // W))).sum() >= 2              # hubs beyond the long-row limit
+    else:
+        L = next(c[1] for c in ed.DYADIC_DIRECT if c[0] == name)
+        assert ed.lanes_for(int(rp[-1]), n) == L and dangling.size == len(ed.DYADIC_DIRECT_DANGLING)
+    assert steps >= 1, "not one exact step: the case is built wrongly"
+    assert ranks.dtype == np.float32 and abs(float(ranks.astype(np.float64).sum()) - 1.0) == 0.0
+    want, iters, res, _ = oracle.pagerank(rp, ci, va, num_cols=n, damping=ed.DYADIC_DAMPING, tolerance=0.0,
+                                          max_iterations=steps, wide_sums=True)
+    assert iters == steps
+    assert float(np.max(np.abs(ranks.astype(np.float64) - want) / want)) <= 1e-6
+    assert abs(res - residual) <= 1e-5 * residual
+
+
+# ------------------------------------------------------------------------------------------ plan geometry
+@pytest.mark.parametrize("name", ed.GEOMETRY_NAMES)
+def test_geometry_case_is_exact_and_the_host_logic_gives_its_shape(spmv, oracle, monkeypatch, name):
+    case, rp, ci, va, x = ed.geometry_matrix(name)
+    rows, cols, nnz = case["rows"], case["cols"], int(rp[-1])
+    assert len(rp) - 1 == rows and int(ci.max()) < cols and nnz > 0
+    prove_exact(spmv, oracle, cols, rp, ci, va, x)
+    monkeypatch.setenv("SPMV_DEBUG", case["debug"])
+    assert spmv.tiled_shape(rows, cols, nnz) == (True, case["W"], case["R"])
+    monkeypatch.delenv("SPMV_DEBUG")
+    assert not spmv.tiled_shape(rows, cols, nnz)[0]                             # only the override lets it in
+    # one value per column exactly when the case says the plan folds
+    order = np.argsort(ci, kind="stable")
+    same_column = ci[order][1:] == ci[order][:-1]
+    differs = bool(np.any(same_column & (va[order][1:] != va[order][:-1])))
+    assert differs != case["fold"] and same_column.any()
+    lens = np.diff(rp.astype(np.int64))
+    limit = ed.LONG_LIMIT if name.startswith("long_rows") else ed.default_long_row(case["strips"])
+    assert int((lens > limit).sum()) == case["long_rows"]
+    local = ci % case["W"]
+    if name.startswith(("strip_", "tile_")):
+        assert (local == 0).any() and (local == case["W"] - 1).any() and (ci == cols - 1).any() and lens[-1] > 0
+        assert np.unique(ci // case["W"]).size == case["strips"]                # entries in the last, partial strip too
+
+
+def test_geometry_catalogue_covers_what_it_claims():
+    cases = ed.GEOMETRY_CASES.values()
+    assert {(c["W"], c["fold"]) for c in cases} == {(w, f) for w in (4096, 8192, 16384, 32768) for f in (False, True)}
+    assert {c["R"] for c in cases} == {64, 128, 1024, 4800, 9984}
+    assert {c["cols"] % c["W"] for c in cases if c["name"].startswith("strip_")} >= {0, 1}
+    assert all(c["rows"] <= 20000 and c["strips"] <= 64 for c in cases)
+    # the row-delta case: gaps of exactly 1, 254, 255, 256, 509, 510, 511 and 9983 rows inside one cell
+    case, rp, ci, _, _ = ed.geometry_matrix("row_deltas_stream")
+    rows_of = np.repeat(np.arange(case["rows"]), np.diff(rp))
+    for tile in (0, 1):
+        in_tile = rows_of // 9984 == tile
+        gaps = set(np.diff(np.unique(rows_of[in_tile & (ci < 4096)])))
+        assert gaps == {1, 254, 255, 256, 509, 510, 511}, gaps
+        assert set(np.diff(np.unique(rows_of[in_tile & (ci // 4096 == 1)]))) == {9983 - 7 * tile}   # 39 skip markers
+    assert set(rows_of[ci // 4096 == 2]) == {9983}                              # first entry in the tile's last row
+    case, rp, ci, _, _ = ed.geometry_matrix("items_1024_stream")
+    assert tuple(np.bincount(ci // 4096, minlength=6)) == ed.ITEM_STRIP_ENTRIES
+    rows_of = np.repeat(np.arange(case["rows"]), np.diff(rp))
+    for strip in range(6):                                                      # consecutive rows: no skip markers
+        r = np.unique(rows_of[ci // 4096 == strip])
+        assert r.size == 0 or (r[0] == 0 and np.all(np.diff(r) == 1))

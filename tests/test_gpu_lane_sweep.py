@@ -269,3 +269,27 @@ def test_pagerank_lane_sweep(gpu, oracle, name, L, k):
         pagerank_tests.assert_parity(gpu, oracle, A, rp, ci, va, n, r)
     finally:
         gpu.csr_destroy(A)
+
+
+@pytest.mark.parametrize("name,L,degrees", ed.DYADIC_DIRECT)
+def test_pagerank_bit_exact_per_lane_count(gpu, name, L, degrees):
+    """pr_step_kernel<L> held to the BIT: n = 2048, damping 0.5, out-degrees powers of two, eight dangling nodes, two
+    hub rows, start 1 / n.  Every quantity of r_new = d * (A r) + d * s / n + (1 - d) / n is then a dyadic rational
+    of at most 24 bits for exact_steps steps (exact_data.exact_steps proves it on the CPU), so the ranks must equal
+    integer arithmetic whatever the summation order, the iteration count is exact and nothing converges at tolerance
+    0.  final_residual: the kernel rounds each (r_new - r_old)^2 to float32 (2^-24 relative), sums in fp64 (n * 2^-53),
+    takes one square root (halves the relative error) and rounds to float32 once: under 2 ulps; 4 are allowed."""
+    n, rp, ci, va, steps, want, residual = ed.dyadic_case(name)
+    assert ed.lanes_for(int(rp[-1]), n) == L and steps >= 1
+    A = pagerank_tests.upload(gpu, rp, ci, va, n)
+    try:
+        for _ in range(2):                                  # the second call finds mask and workspace cached
+            r = gpu.pagerank(A, gpu.PageRankConfig(ed.DYADIC_DAMPING, 0.0, steps))
+            print(name, "steps", steps, "residual", r.final_residual, residual)
+            assert r.iterations == steps and not r.converged, (name, r.iterations, steps)
+            assert not gpu.csr_has_tiled_plan(A)
+            assert_bits(rp, r.ranks, want, name)
+            got, exact = np.float32(r.final_residual), np.float32(residual)
+            assert abs(int(got.view(np.int32)) - int(exact.view(np.int32))) <= 4, (name, got, residual)
+    finally:
+        gpu.csr_destroy(A)
