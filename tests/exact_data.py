@@ -405,6 +405,11 @@ def dyadic_pagerank(rp, ci, va, n, damping, steps):
     return ranks, residual
 
 
+def dyadic_trajectory(rp, ci, va, n, damping, steps):
+    """[(ranks float32, exact residual)] after step 1, 2, ... `steps`: what a test that looks after EVERY step wants."""
+    return [(ranks, residual) for ranks, residual, _ in _dyadic_run(rp, ci, va, n, damping, steps)]
+
+
 def exact_steps(rp, ci, va, n, damping, max_steps=4):
     """Number of leading steps (up to max_steps) in which everything the device computes is exact in float32: per
     row all products and the row's sum are multiples of one quantum q with sum < 2^24 q (check_exact's condition,
@@ -434,8 +439,43 @@ DYADIC_TILED = {
     "n18_8192x1024_dangling_fold": (1 << 18, 8192, 1024, 1 << 12, True, 0, 1),
     "n18_16384x9984_closed_fold": (1 << 18, 16384, 9984, 0, True, 0, 3),
     "n16_8192x1024_closed_switch_after_1": (1 << 16, 8192, 1024, 0, True, 1, 3),
+    # dangling nodes drawn from the source-only nodes (DYADIC_SOURCES below): exact beyond step 1, so the dangling
+    # mass the DEVICE accumulated in step k enters step k + 1 under a bit-exact comparison
+    "n16_4096x64_sources_fold": (1 << 16, 4096, 64, 1 << 12, True, 0, 3),
+    "n16_8192x1024_sources_stream": (1 << 16, 8192, 1024, 1 << 12, False, 0, 2),
+    "n18_16384x9984_sources_fold": (1 << 18, 16384, 9984, 1 << 12, True, 0, 2),
+    "n16_4096x64_sources_switch_after_1": (1 << 16, 4096, 64, 1 << 12, True, 1, 3),
 }
+# name -> hubs of the cases whose dangling nodes are source-only nodes.  Out-degrees (2, 4).  Shorter hubs keep the
+# ranks short for one step more (three exact steps); the 5000 / 2500 pair is what the other tiled cases carry.
+DYADIC_SOURCES = {
+    "n16_4096x64_sources_fold": lambda n: [(n // 3, 700), (n - 1, 350)],
+    "n16_8192x1024_sources_stream": lambda n: [(n // 3, 5000), (n - 1, 2500)],
+    "n18_16384x9984_sources_fold": lambda n: [(n // 3, 5000), (n - 1, 2500)],
+    "n16_4096x64_sources_switch_after_1": lambda n: [(n // 3, 700), (n - 1, 350)],
+}
+# the same construction for the direct kernel (n = 2^16 stays below the tiled engine's 2^20 entries): (name, L, degrees)
+DYADIC_SOURCE_DIRECT = [("sources_L1", 1, (2, 4)), ("sources_L2", 2, (4, 8)), ("sources_L4", 4, (8, 16))]
+SHARDED_CASE = "n16_4096x64_sources_fold"         # the graph tests/test_gpu_sharded_exact.py cuts (three exact steps)
 _dyadic_cache = {}
+
+
+def source_only_nodes(n, hubs):
+    """The nodes dyadic_graph never links to: rows with row % 13 == 5 that are not hubs."""
+    nodes = np.arange(5, n, 13, dtype=np.int64)
+    return nodes[~np.isin(nodes, np.array([h for h, _ in hubs], np.int64))]
+
+
+def source_only_dangling(rng, n, hubs, count):
+    """`count` dangling nodes (a power of two) drawn from the source-only nodes.  Nobody links to them and they link
+    to nobody, so after every step all of them carry the same short rank d * s / n + (1 - d) / n and their sum s stays
+    short: the dangling term survives more than one exact step (a dangling node WITH in-links has a long rank after
+    step 1).  Drawn four times as densely at the top of the node range as at its bottom, so that shards of equal
+    rows own different numbers of them and a commit that reads one rank's partial mass for all shows."""
+    assert count & (count - 1) == 0
+    nodes = source_only_nodes(n, hubs)
+    weight = 1.0 + 3.0 * np.arange(nodes.size) / nodes.size
+    return np.sort(rng.choice(nodes, size=count, replace=False, p=weight / weight.sum()))
 
 
 def dyadic_case(name):
@@ -443,7 +483,19 @@ def dyadic_case(name):
     exact_steps, ranks / residual = dyadic_pagerank at that count (None when steps == 0)."""
     if name in _dyadic_cache:
         return _dyadic_cache[name]
-    if name in DYADIC_TILED:
+    if name in DYADIC_SOURCES:
+        n, _, _, dangling_count, _, _, _ = DYADIC_TILED[name]
+        rng = np.random.default_rng(sum(name.split("x")[0].encode()))       # cases that differ in W, R only share a graph
+        hubs = DYADIC_SOURCES[name](n)
+        dangling = source_only_dangling(rng, n, hubs, dangling_count)
+        degrees = (2, 4)
+    elif name.startswith("sources_L"):
+        index, (_, L, degrees) = next((i, c) for i, c in enumerate(DYADIC_SOURCE_DIRECT) if c[0] == name)
+        n = 1 << 16
+        rng = np.random.default_rng(300 + index)
+        hubs = [(n // 3, 700), (n - 1, 350)]
+        dangling = source_only_dangling(rng, n, hubs, 1 << 12)
+    elif name in DYADIC_TILED:
         n, _, _, dangling_count, _, _, _ = DYADIC_TILED[name]
         rng = np.random.default_rng(sum(name.encode()))
         dangling = rng.choice(n, size=dangling_count, replace=False)
@@ -466,6 +518,47 @@ def dyadic_case(name):
 def tiled_debug(W, R, extra=""):
     """The SPMV_DEBUG string that pushes a small matrix through the tiled engine at strip width W, tile height R."""
     return "min_cols=1,min_nnz=1,strip=%d,tile=%d%s" % (W, R, "," + extra if extra else "")
+
+
+# ------------------------------------------------------------------------------------------ sharded PageRank catalogue
+# How tests/test_gpu_sharded_exact.py cuts SHARDED_CASE.  tests/test_exact_data.py proves on the CPU what each cut
+# claims (an empty shard, a hub alone, a block boundary inside a strip ...) and that the dangling nodes are spread
+# over the ranks with different masses.
+SHARD_WORLDS = (1, 2, 3, 5, 8)
+SHARD_W, SHARD_R = 4096, 64                  # strip width / tile height where the shards run the tiled engine
+SHARD_ALIGNS = (4096, 8192, 1000)            # = W, a multiple of W, smaller than W and not dividing it
+SHARD_CHUNKS = (2, 3, 4, 7)
+
+
+def equal_row_bounds(n, world):
+    """Layout's default cut (pagerank_dist.py): ceil(n / world) rows per rank, rounded up to even when world > 1."""
+    shard_len = -(-n // world)
+    if world > 1 and shard_len % 2:
+        shard_len += 1
+    return np.minimum(np.arange(world + 1, dtype=np.int64) * shard_len, n)
+
+
+def shard_cut_edges(n, hub):
+    """name -> explicit bounds; `hub` is a hub row (n - 1 is the other one).  Row 5 is a source-only, empty row."""
+    return {
+        "empty_first": [0, 0, 30001, n], "empty_middle": [0, 30001, 30001, n], "empty_last": [0, 30001, n, n],
+        "one_empty_row": [0, 5, 6, n],                       # rows but no entries
+        "hub_alone": [0, hub, hub + 1, n], "last_hub_alone": [0, 30000, n - 1, n],
+        "cut_before_hub": [0, hub, n], "cut_after_hub": [0, hub + 1, n],
+        "odd_lengths": [0, 25539, 45540, n],                 # the longest shard is odd: rounded up to even
+    }
+
+
+def chunk_world(n, chunks):
+    """(world, bounds) of a chunk-major case: two equal shards for even chunk counts, else three shards of 30 000,
+    22 000 and the remaining rows (short shards: their last pieces hold no rows)."""
+    return (2, None) if chunks % 2 == 0 else (3, [0, 30000, 52000, n])
+
+
+def dangling_per_rank(bounds, dangling):
+    """Number of dangling nodes each rank owns (their ranks are all equal, so the masses are in this proportion)."""
+    bounds = np.asarray(bounds, np.int64)
+    return np.bincount(np.searchsorted(bounds[1:-1], np.asarray(dangling), side="right"), minlength=bounds.size - 1)
 
 
 # ------------------------------------------------------------------------------------------ plan-geometry catalogue

@@ -214,6 +214,231 @@ def test_dyadic_case_is_exact_and_restates_the_oracle(oracle, name):
     assert abs(res - residual) <= 1e-5 * residual
 
 
+SOURCE_NAMES = list(ed.DYADIC_SOURCES) + [c[0] for c in ed.DYADIC_SOURCE_DIRECT]
+
+
+@pytest.mark.parametrize("name", SOURCE_NAMES)
+def test_source_only_dangling_cases_stay_exact_beyond_the_first_step(name):
+    """The cases whose dangling nodes are source-only nodes: at least TWO exact steps with dangling nodes present
+    (so the mass the device accumulates in step 1 enters step 2 under a bit-exact comparison), the ranks summing to
+    exactly 1 after EVERY step, all dangling nodes without in-links, the hubs beyond the long-row limit at the strip
+    count of the unsharded matrix (the sharded layouts, whose padded vectors are wider, are checked in
+    test_hubs_stay_long_rows_in_every_sharded_layout)."""
+    n, rp, ci, va, steps, ranks, residual = ed.dyadic_case(name)
+    lens = np.diff(rp.astype(np.int64))
+    dangling = np.flatnonzero(np.bincount(ci, minlength=n) == 0)
+    assert dangling.size == 1 << 12 and np.all(lens[dangling] == 0) and np.all(dangling % 13 == 5)
+    assert steps >= 2 and steps == ed.exact_steps(rp, ci, va, n, ed.DYADIC_DAMPING)
+    trajectory = ed.dyadic_trajectory(rp, ci, va, n, ed.DYADIC_DAMPING, steps)
+    assert len(trajectory) == steps
+    for r, res in trajectory:
+        assert r.dtype == np.float32 and float(r.astype(np.float64).sum()) == 1.0 and res > 0
+        assert np.unique(r[dangling]).size == 1                                # one short rank for all of them
+    np.testing.assert_array_equal(trajectory[-1][0], ranks)
+    assert trajectory[-1][1] == residual
+    w = ed.DYADIC_TILED[name][1] if name in ed.DYADIC_TILED else ed.SHARD_W
+    assert (lens > ed.default_long_row(-(-n // w))).sum() >= 2
+    if name.startswith("sources_L"):
+        L = next(c[1] for c in ed.DYADIC_SOURCE_DIRECT if c[0] == name)
+        assert ed.lanes_for(int(rp[-1]), n) == L
+
+
+def test_some_source_only_case_has_three_exact_steps_and_the_sharded_one_does():
+    assert ed.dyadic_case(ed.SHARDED_CASE)[4] >= 3
+    assert sum(ed.dyadic_case(name)[4] >= 3 for name in SOURCE_NAMES) >= 1
+    assert ed.DYADIC_TILED[ed.SHARDED_CASE][1:3] == (ed.SHARD_W, ed.SHARD_R)
+
+
+def test_existing_dyadic_cases_keep_their_arrays():
+    """dyadic_case grew new branches; the cases that were there draw the same graphs (checksums of the arrays as they
+    were before the source-only cases were added)."""
+    import zlib
+    want = {"L1": (4763, 2663063358), "L2": (12272, 3988500013), "L4": (24464, 1090606460), "L8": (48992, 968007382),
+            "L16": (98016, 3587197183), "L32": (194752, 631239565), "L64": (391808, 2736269738),
+            "n16_4096x64_dangling_fold": (483458, 3412015588), "n16_8192x1024_closed_fold": (98247, 1151884295),
+            "n16_16384x9984_dangling_stream": (484422, 316532757), "n18_4096x64_closed_stream": (393584, 3752300066),
+            "n18_8192x1024_dangling_fold": (1939084, 683648082), "n18_16384x9984_closed_fold": (392861, 3523887001),
+            "n16_8192x1024_closed_switch_after_1": (98494, 4166476643)}
+    for name, (nnz, crc) in want.items():
+        _, rp, ci, va, *_ = ed.dyadic_case(name)
+        assert (int(rp[-1]), zlib.crc32(rp.tobytes() + ci.tobytes() + va.tobytes())) == (nnz, crc), name
+
+
+def sharded_graph():
+    n, rp, ci, va, steps, _, _ = ed.dyadic_case(ed.SHARDED_CASE)
+    dangling = np.flatnonzero(np.bincount(ci, minlength=n) == 0)
+    return n, rp, ci, va, dangling, ed.DYADIC_SOURCES[ed.SHARDED_CASE](n)
+
+
+def assert_spread(bounds, dangling, min_rows=100):
+    counts = ed.dangling_per_rank(bounds, dangling)
+    big = np.diff(np.asarray(bounds)) > min_rows
+    assert (counts[big] > 0).all() and np.unique(counts[big]).size == int(big.sum()), (bounds, counts)
+    return counts
+
+
+def test_every_rank_of_every_sharded_case_owns_dangling_nodes_of_a_different_mass(spmv):
+    """All dangling nodes carry the same rank, so a rank's partial mass is proportional to the number it owns: the
+    counts are positive and pairwise different for every world size under both cuts (Layout's and the native
+    loop's), for the chunk-major worlds, and among the shards of more than 100 rows of every explicit cut."""
+    import ctypes
+    prd = importlib.import_module("gpu-spmv_amd.pagerank_dist")
+    n, rp, ci, va, dangling, hubs = sharded_graph()
+    for world in ed.SHARD_WORLDS:
+        lay = prd.Layout(n, world)
+        np.testing.assert_array_equal(lay.bounds, ed.equal_row_bounds(n, world))
+        for bounds in (lay.bounds, prd.Layout.equal_nnz_bounds(rp, world)):
+            counts = assert_spread(bounds, dangling)
+            assert counts.size == world and counts.min() > 0 and np.unique(counts).size == world
+        native = np.zeros(world + 1, np.int32)
+        assert spmv.lib().spmv_c_pagerank_shard_bounds(rp.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n, world,
+                                                       native.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))) == 0
+        # the two partitions are separate code (csrc/pagerank_multi.cpp, pagerank_dist.py): they must cut alike
+        np.testing.assert_array_equal(native, prd.Layout.equal_nnz_bounds(rp, world))
+    for chunks in ed.SHARD_CHUNKS:
+        world, bounds = ed.chunk_world(n, chunks)
+        counts = assert_spread(prd.Layout(n, world, 0, bounds=bounds).bounds, dangling)
+        assert counts.size == world and counts.min() > 0
+    for name, bounds in ed.shard_cut_edges(n, hubs[0][0]).items():
+        counts = assert_spread(bounds, dangling)
+        assert (counts > 0).sum() >= 2 or name == "one_empty_row", (name, counts)
+
+
+def test_hubs_stay_long_rows_in_every_sharded_layout():
+    """The long-row limit (8 per strip) grows with the strip count, and a shard's matrix is as wide as the PADDED
+    vector, world * (longest shard + tail) and more in the chunk-major layouts.  Both hubs exceed the limit under the
+    equal-row and equal-nnz cuts of every world size; the uneven explicit cuts and the chunk-major layouts pad up to
+    48 strips of 4096 columns (limit 384), where only the 700-entry hub does: the GPU tests assert what holds
+    everywhere, at least one long row."""
+    prd = importlib.import_module("gpu-spmv_amd.pagerank_dist")
+    n, rp, ci, va, dangling, hubs = sharded_graph()
+    lengths = [length for _, length in hubs]
+    even = [prd.Layout(n, 1, 0, exchange=True)]
+    for world in ed.SHARD_WORLDS:
+        even += [prd.Layout(n, world), prd.Layout(n, world, 0, bounds=prd.Layout.equal_nnz_bounds(rp, world))]
+    assert min(lengths) > ed.default_long_row(max(-(-lay.padded // ed.SHARD_W) for lay in even))
+    other = [prd.Layout(n, len(b) - 1, 0, bounds=b) for b in ed.shard_cut_edges(n, hubs[0][0]).values()]
+    for chunks in ed.SHARD_CHUNKS:
+        world, bounds = ed.chunk_world(n, chunks)
+        other += [prd.Layout(n, world, 0, bounds=bounds, chunks=chunks, align=a) for a in ed.SHARD_ALIGNS]
+    most = max(-(-lay.padded // ed.SHARD_W) for lay in other)
+    assert 40 <= most <= 48 and max(lengths) > ed.default_long_row(most)
+
+
+def test_sharded_cut_edges_are_what_their_names_say():
+    prd = importlib.import_module("gpu-spmv_amd.pagerank_dist")
+    n, rp, ci, va, dangling, hubs = sharded_graph()
+    lens = np.diff(rp.astype(np.int64))
+    hub = hubs[0][0]
+    limit = ed.default_long_row(-(-n // ed.SHARD_W) + 1)
+    assert lens[hub] == hubs[0][1] > limit and lens[n - 1] == hubs[1][1] > limit
+    cuts = ed.shard_cut_edges(n, hub)
+    rows = {name: np.diff(b) for name, b in cuts.items()}
+    assert rows["empty_first"][0] == 0 and rows["empty_middle"][1] == 0 and rows["empty_last"][2] == 0
+    b = cuts["one_empty_row"]
+    assert rows["one_empty_row"][1] == 1 and rp[b[2]] - rp[b[1]] == 0
+    assert rows["hub_alone"][1] == 1 and cuts["hub_alone"][1] == hub
+    assert rows["last_hub_alone"][2] == 1 and cuts["last_hub_alone"][2] == n - 1
+    assert cuts["cut_before_hub"][1] == hub and cuts["cut_after_hub"][1] == hub + 1
+    assert rows["odd_lengths"].max() % 2 == 1
+    lay = prd.Layout(n, 3, 0, bounds=cuts["odd_lengths"])
+    assert lay.shard_len == rows["odd_lengths"].max() + 1 and lay.piece == lay.shard_len + prd.TAIL
+    for world in (3, 5):                                     # equal rows: world * shard_len overshoots n
+        lay = prd.Layout(n, world)
+        assert world * lay.shard_len > n and np.diff(lay.bounds)[-1] < lay.shard_len
+
+
+def test_chunk_major_cases_put_block_boundaries_where_they_claim():
+    """align = W and 2 W: every block boundary is a strip boundary; align = 1000: some boundary falls inside a strip
+    (pr_expand must round cols_ready / strip_cols down).  The tail sits in the last piece; at 7 chunks (and at a
+    wide align) the short shards' last pieces hold no rows; positions() is a bijection onto distinct slots that
+    miss every tail."""
+    prd = importlib.import_module("gpu-spmv_amd.pagerank_dist")
+    n = sharded_graph()[0]
+    W = ed.SHARD_W
+    assert [a % W == 0 for a in ed.SHARD_ALIGNS] == [True, True, False] and W % ed.SHARD_ALIGNS[2] != 0
+    empty_pieces = 0
+    for chunks in ed.SHARD_CHUNKS:
+        world, bounds = ed.chunk_world(n, chunks)
+        for align in ed.SHARD_ALIGNS:
+            lays = [prd.Layout(n, world, r, bounds=bounds, chunks=chunks, align=align) for r in range(world)]
+            lay = lays[0]
+            assert lay.chunks == chunks and lay.piece % align == 0 and lay.padded == chunks * world * lay.piece
+            inside = [c for c in range(1, chunks) if (c * lay.block) % W]
+            assert bool(inside) == (align % W != 0)
+            pos = lay.positions()
+            assert np.unique(pos).size == n and pos.max() < lay.padded
+            for r, l in enumerate(lays):
+                tail = lay.tail_slice(r)
+                assert tail.stop == (chunks - 1) * lay.block + (r + 1) * lay.piece
+                assert not np.isin(np.arange(tail.start, tail.stop), pos).any()
+                assert l.local_rows <= lay.shard_len
+                np.testing.assert_array_equal(l.local_positions(), pos[l.row_begin:l.row_end])
+                empty_pieces += sum(c * lay.piece >= l.local_rows for c in range(chunks))
+    assert empty_pieces > 10
+
+
+def cpu_world(oracle, world, **layout):
+    """shard_sim.Sim over the sharded graph with the CPU double of the shard engine (test_distributed_gloo.OracleEngine:
+    fp32 update, double partial sums, the same padded layout) in place of HipEngine."""
+    import torch
+    import shard_sim
+    prd = importlib.import_module("gpu-spmv_amd.pagerank_dist")
+    class double(importlib.import_module("test_distributed_gloo").OracleEngine):
+        """The promise of expand() checked on the bits: the vectors' padding holds a NaN pattern here."""
+
+        def expand(self, r_old, cols_ready):
+            assert 0 < cols_ready <= self.layout.padded and cols_ready % self.layout.block == 0
+            self.seen = getattr(self, "seen", []) + [(cols_ready, r_old[:cols_ready].view(torch.int32).clone())]
+
+        def step(self, r_old, r_new, damping, sums_out=None):
+            for cols_ready, seen in getattr(self, "seen", []):
+                assert torch.equal(r_old[:cols_ready].view(torch.int32), seen), "columns changed after expand()"
+            self.seen = []
+            return super().step(r_old, r_new, damping, sums_out)
+
+    n, rp, ci, va, _, _ = sharded_graph()
+    return shard_sim.Sim(None, prd, torch, rp, ci, va, n, world,
+                         make_engine=lambda lrp, lci, lva, lay: double(oracle, lrp, lci, lva, lay), **layout)
+
+
+def cpu_worlds():
+    n, hub = 1 << 16, (1 << 16) // 3
+    cuts = ed.shard_cut_edges(n, hub)
+    yield "world3_rows_gather", 3, {}, "gather", "blocks"
+    yield "world8_rows_sums", 8, {}, "sums", "blocks"
+    yield "world1_exchange", 1, dict(exchange=True), "gather", "blocks"
+    for name in ("empty_middle", "empty_last", "one_empty_row", "hub_alone", "odd_lengths"):
+        yield name, len(cuts[name]) - 1, dict(bounds=cuts[name]), "gather", "blocks"
+    for chunks, align, head_start in ((2, 4096, "blocks"), (3, 1000, "twice"), (7, 8192, "blocks"), (4, 1000, "never")):
+        world, bounds = ed.chunk_world(n, chunks)
+        yield "chunks%d_align%d" % (chunks, align), world, dict(bounds=bounds, chunks=chunks, align=align), "gather", head_start
+
+
+@pytest.mark.parametrize("what,world,layout,mode,head_start", list(cpu_worlds()), ids=[c[0] for c in cpu_worlds()])
+def test_shard_simulator_and_layout_reproduce_the_prover_on_the_cpu(oracle, what, world, layout, mode, head_start):
+    """The simulator the GPU tests use (tests/shard_sim.py: cutting, renumbering, exchange by pieces, tails, commit
+    forms, padding sentinel, the per-step checks) with a CPU engine: every rank's vector equals the integer prover's
+    bit for bit after every step.  On dyadic data the CPU double's row sums are exact in its order as in any other,
+    so this holds Layout, the catalogue and the simulator themselves to the bits before a GPU is involved; a failure
+    of the GPU tests is then the engine's."""
+    n, rp, ci, va, dangling, _ = sharded_graph()
+    steps = ed.dyadic_case(ed.SHARDED_CASE)[4]
+    trajectory = ed.dyadic_trajectory(rp, ci, va, n, ed.DYADIC_DAMPING, steps)
+    sim = cpu_world(oracle, world, **layout)
+    assert all(sp.num_dangling == dangling.size for sp in sim.loops)
+
+    def same_bits(_, got, want, where):
+        np.testing.assert_array_equal(np.asarray(got).view(np.uint32), np.asarray(want).view(np.uint32), err_msg=str(where))
+
+    try:
+        for k in range(steps):
+            sim.step(k, ed.DYADIC_DAMPING, 0.0, mode=mode, head_start=head_start)
+            sim.check(k, trajectory[k][0], trajectory[k][1], same_bits, what)
+    finally:
+        sim.close()
+
+
 # ------------------------------------------------------------------------------------------ plan geometry
 @pytest.mark.parametrize("name", ed.GEOMETRY_NAMES)
 def test_geometry_case_is_exact_and_the_host_logic_gives_its_shape(spmv, oracle, monkeypatch, name):

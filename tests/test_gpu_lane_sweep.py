@@ -293,3 +293,26 @@ def test_pagerank_bit_exact_per_lane_count(gpu, name, L, degrees):
             assert abs(int(got.view(np.int32)) - int(exact.view(np.int32))) <= 4, (name, got, residual)
     finally:
         gpu.csr_destroy(A)
+
+
+@pytest.mark.parametrize("name,L,degrees", ed.DYADIC_SOURCE_DIRECT)
+def test_pagerank_device_dangling_mass_bit_exact(gpu, name, L, degrees):
+    """pr_step_kernel<L>, L = 1, 2, 4, at n = 2^16 with 4096 dangling nodes that nobody links to: exact for three steps
+    (tests/test_exact_data.py), so the dangling term of steps 2 and 3 is the mass the kernel accumulated on the device
+    (mass += fresh -> block partials -> pr_reduce_commit -> state->dangling_sum); step 1 takes it from the host.
+    Checked after every step count, not only the last."""
+    n, rp, ci, va, steps, _, _ = ed.dyadic_case(name)
+    assert ed.lanes_for(int(rp[-1]), n) == L and steps >= 2
+    trajectory = ed.dyadic_trajectory(rp, ci, va, n, ed.DYADIC_DAMPING, steps)
+    A = pagerank_tests.upload(gpu, rp, ci, va, n)
+    try:
+        for k in list(range(1, steps + 1)) + [steps]:       # the last call finds mask and workspace cached
+            want, residual = trajectory[k - 1]
+            r = gpu.pagerank(A, gpu.PageRankConfig(ed.DYADIC_DAMPING, 0.0, k))
+            print(name, "L", L, "steps", k, "residual", r.final_residual, residual)
+            assert r.iterations == k and not r.converged and not gpu.csr_has_tiled_plan(A)
+            assert_bits(rp, r.ranks, want, (name, k))
+            got, exact = np.float32(r.final_residual), np.float32(residual)
+            assert abs(int(got.view(np.int32)) - int(exact.view(np.int32))) <= 4, (name, k, got, residual)
+    finally:
+        gpu.csr_destroy(A)

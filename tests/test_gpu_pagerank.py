@@ -16,6 +16,8 @@ import importlib
 import numpy as np
 import pytest
 
+import shard_sim
+
 pytestmark = pytest.mark.gpu
 
 
@@ -183,25 +185,13 @@ def test_two_shards_on_one_gpu_equal_one_shard(gpu, oracle):
     rp, ci, va = graph(gpu, n, 10, 8, dangling=(11,))
     dev = torch.device("cuda:0")
 
-    def engine(lay):
-        b, e = lay.row_begin, lay.row_end
-        lrp = torch.from_numpy((rp[b:e + 1] - rp[b]).astype(np.int32)).to(dev)
-        lci = torch.from_numpy(lay.remap_columns(ci[rp[b]:rp[e]]).astype(np.int32)).to(dev)
-        return prd.HipEngine(lrp, lci, torch.from_numpy(va[rp[b]:rp[e]]).to(dev), lay)
-
     whole_lay = prd.Layout(n)
     lays = [prd.Layout(n, 2, r) for r in range(2)]
-    whole = prd.ShardedPageRank(engine(whole_lay), whole_lay).prepare()
-    shards = [prd.ShardedPageRank(engine(l), l) for l in lays]
-    sums = shards[0].engine.column_sums() + shards[1].engine.column_sums()      # the all-reduce of prepare()
+    whole = prd.ShardedPageRank(shard_sim.shard_engine(prd, torch, dev, rp, ci, va, whole_lay), whole_lay).prepare()
+    shards = shard_sim.sharded_loops(prd, torch, dev, rp, ci, va, lays)        # masks from the summed column sums, reset
     num_dangling = int(oracle.dangling_mask(rp, ci, va, n).sum())
     for sp in shards:
-        mask = torch.zeros(sp.layout.padded, dtype=torch.uint8, device=dev)
-        mask[sp._pos] = (sums[sp._pos] == 0).to(torch.uint8)
-        sp.num_dangling = int(mask.sum().item())
         assert sp.num_dangling == whole.num_dangling == num_dangling >= 1
-        sp.engine.set_dangling_mask(mask)
-        sp.reset()
     whole.reset()
     for k in range(6):
         whole.iterate(k, 0.85, 0.0)
@@ -248,20 +238,7 @@ def test_head_start_on_a_chunk_major_vector(gpu, oracle, chunks, align, skewed):
     dev = torch.device("cuda:0")
 
     def sharded(lays):
-        out = []
-        for lay in lays:
-            b, e = lay.row_begin, lay.row_end
-            lrp = torch.from_numpy((rp[b:e + 1] - rp[b]).astype(np.int32)).to(dev)
-            lci = torch.from_numpy(lay.remap_columns(ci[rp[b]:rp[e]]).astype(np.int32)).to(dev)
-            out.append(prd.ShardedPageRank(prd.HipEngine(lrp, lci, torch.from_numpy(va[rp[b]:rp[e]]).to(dev), lay), lay))
-        sums = out[0].engine.column_sums() + out[1].engine.column_sums()
-        for sp in out:
-            mask = torch.zeros(sp.layout.padded, dtype=torch.uint8, device=dev)
-            mask[sp._pos] = (sums[sp._pos] == 0).to(torch.uint8)
-            sp.num_dangling = int(mask.sum().item())
-            sp.engine.set_dangling_mask(mask)
-            sp.reset()
-        return out
+        return shard_sim.sharded_loops(prd, torch, dev, rp, ci, va, lays)
 
     lays = [prd.Layout(n, 2, r, bounds=bounds, chunks=chunks, align=align) for r in range(2)]
     assert lays[0].chunks == chunks and (align is None or lays[0].block % align == 0)
@@ -522,23 +499,10 @@ def test_push_exchange_two_shards_on_one_gpu(gpu, oracle):
     rp, ci, va = graph(gpu, n, 10, 12, dangling=(5,))
     dev = torch.device("cuda:0")
 
-    def engine(lay):
-        b, e = lay.row_begin, lay.row_end
-        lrp = torch.from_numpy((rp[b:e + 1] - rp[b]).astype(np.int32)).to(dev)
-        lci = torch.from_numpy(lay.remap_columns(ci[rp[b]:rp[e]]).astype(np.int32)).to(dev)
-        return prd.HipEngine(lrp, lci, torch.from_numpy(va[rp[b]:rp[e]]).to(dev), lay)
-
     whole_lay = prd.Layout(n)
-    whole = prd.ShardedPageRank(engine(whole_lay), whole_lay).prepare()
+    whole = prd.ShardedPageRank(shard_sim.shard_engine(prd, torch, dev, rp, ci, va, whole_lay), whole_lay).prepare()
     lays = [prd.Layout(n, 2, r) for r in range(2)]
-    shards = [prd.ShardedPageRank(engine(l), l) for l in lays]
-    sums = shards[0].engine.column_sums() + shards[1].engine.column_sums()
-    for sp in shards:
-        mask = torch.zeros(sp.layout.padded, dtype=torch.uint8, device=dev)
-        mask[sp._pos] = (sums[sp._pos] == 0).to(torch.uint8)
-        sp.num_dangling = int(mask.sum().item())
-        sp.engine.set_dangling_mask(mask)
-        sp.reset()
+    shards = shard_sim.sharded_loops(prd, torch, dev, rp, ci, va, lays)
     whole.reset()
     for k in range(5):
         whole.iterate(k, 0.85, 0.0)

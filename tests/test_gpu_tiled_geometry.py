@@ -257,7 +257,10 @@ def test_pagerank_bit_exact_on_the_tiled_engine(gpu, monkeypatch, name):
     weights, long-row seeds of the hubs) at three plan geometries, n = 2^16 and 2^18, with dangling nodes (one exact
     step) and without (several), folded values and the value stream; and the switch from the direct kernel to the
     plan after the first step (pr_plan_after=1: only the first of the two calls switches; the second finds the plan
-    cached and runs tiled from step 0).  Two calls per graph: the second finds plan and workspace cached."""
+    cached and runs tiled from step 0).  Two calls per graph: the second finds plan and workspace cached.
+    The "sources" cases draw their dangling nodes from the nodes nobody links to and stay exact for two or three
+    steps: from step 2 on the dangling term is the mass the reduce kernel itself accumulated (block partials ->
+    pr_reduce_commit -> state->dangling_sum), which the one-step cases never reach."""
     n, W, R, _, fold, plan_after, _ = ed.DYADIC_TILED[name]
     _, rp, ci, va, steps, _, _ = ed.dyadic_case(name)
     assert steps > plan_after
