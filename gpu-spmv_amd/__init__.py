@@ -154,6 +154,23 @@ class BiCGStabResult(Structure):
     NONE, RHO, ALPHA, OMEGA = BICGSTAB_NO_BREAKDOWN, BICGSTAB_RHO, BICGSTAB_ALPHA, BICGSTAB_OMEGA
 
 
+class SpTRSVConfig(Structure):
+    """include/spmv/sptrsv.h SpTRSVConfig (16 bytes): uplo 0 LOWER / 1 UPPER; diag 0 NON_UNIT / 1 UNIT; ordered 1 = one
+    lane per row in the CPU's summation order"""
+    _fields_ = [("uplo", c_int32), ("diag", c_int32), ("ordered", c_int32), ("reserved", c_int32)]
+    LOWER, UPPER = 0, 1
+    NON_UNIT, UNIT = 0, 1
+
+    def __init__(self, uplo=0, diag=0, ordered=0, reserved=0):
+        super().__init__(uplo, diag, ordered, reserved)
+
+
+class SpTRSVResult(Structure):
+    """include/spmv/sptrsv.h SpTRSVResult (24 bytes)"""
+    _fields_ = [("error_code", c_int32), ("num_levels", c_int32), ("launches", c_int32),
+                ("lanes_per_row", c_int32), ("analysis_ms", c_float), ("elapsed_ms", c_float)]
+
+
 class PageRankResult:
     """reference include/spmv/pagerank.h:18-25; `ranks` is a numpy copy (the C buffer is freed)."""
 
@@ -247,6 +264,13 @@ _SIGNATURES = {
     "spmv_c_cg_solve": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(CGConfig), POINTER(CGResult)]),
     "spmv_c_bicgstab_solve": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(BiCGStabConfig),
                                       POINTER(BiCGStabResult)]),
+    "spmv_c_sptrsv_csr": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(SpTRSVConfig),
+                                  POINTER(SpTRSVResult)]),
+    "spmv_c_sptrsv_csr_async": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(SpTRSVConfig), c_void_p]),
+    "spmv_c_sptrsv_analyze": (c_int, [POINTER(CSRMatrix), c_int, POINTER(SpTRSVResult)]),
+    "spmv_c_sptrsv_cpu_csr": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(SpTRSVConfig)]),
+    "spmv_c_sptrsv_levels": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, POINTER(c_int32),
+                                     POINTER(c_int32)]),
     "spmv_c_compute_bandwidth_csr": (c_int, [POINTER(CSRMatrix), c_float, POINTER(BandwidthMetrics)]),
     "spmv_c_compute_bandwidth_csr_multi": (c_int, [POINTER(CSRMatrix), c_int, c_float, POINTER(BandwidthMetrics)]),
     "spmv_c_compute_bandwidth_ell": (c_int, [POINTER(ELLMatrix), c_float, POINTER(BandwidthMetrics)]),
@@ -800,6 +824,52 @@ def bicgstab_solve(A, d_b, d_x, config=None) -> BiCGStabResult:
     lib().spmv_c_bicgstab_solve(A, _dev(d_b), _dev(d_x), byref(config) if config is not None else None,
                                 byref(out))
     return out
+
+
+def sptrsv_csr(A, d_b, d_x, config=None) -> SpTRSVResult:
+    """Solves T x = b on the device, T the config.uplo triangle of the square matrix A (include/spmv/sptrsv.h
+    sptrsv_csr): d_b and d_x hold num_rows floats and may be the same buffer (the solve in place)."""
+    out = SpTRSVResult()
+    lib().spmv_c_sptrsv_csr(A, _dev(d_b), _dev(d_x), byref(config) if config is not None else None, byref(out))
+    return out
+
+
+def sptrsv_csr_async(A, d_b, d_x, config=None, stream=None) -> int:
+    return lib().spmv_c_sptrsv_csr_async(A, _dev(d_b), _dev(d_x), byref(config) if config is not None else None,
+                                         c_void_p(stream))
+
+
+def sptrsv_analyze(A, uplo=0) -> SpTRSVResult:
+    """Builds and caches the level schedule of A's `uplo` triangle ahead of a timed sptrsv_csr."""
+    out = SpTRSVResult()
+    lib().spmv_c_sptrsv_analyze(A, int(uplo), byref(out))
+    return out
+
+
+def sptrsv_cpu_csr(A, b, config=None) -> np.ndarray:
+    """Host forward / backward substitution on A's host arrays (include/spmv/sptrsv.h sptrsv_cpu_csr): returns x;
+    raises ValueError with the library's error string when the call is rejected."""
+    b = np.ascontiguousarray(b, dtype=np.float32)
+    x = np.zeros(A.contents.num_rows, dtype=np.float32)
+    status = lib().spmv_c_sptrsv_cpu_csr(A, _np_ptr(b), _np_ptr(x), byref(config) if config is not None else None)
+    if status != 0:
+        raise ValueError(spmv_error_string(status))
+    return x
+
+
+def sptrsv_levels(num_rows, row_ptrs, col_indices, uplo=0):
+    """The level analysis on the host (include/spmv/sptrsv.h sptrsv_levels):
+    (status, level_ptr[num_levels + 1], order[num_rows], num_levels, first_missing_diagonal)."""
+    rp = np.ascontiguousarray(row_ptrs, dtype=np.int32)
+    ci = np.ascontiguousarray(col_indices, dtype=np.int32)
+    level_ptr = np.zeros(max(int(num_rows), 0) + 1, dtype=np.int32)
+    order = np.zeros(max(int(num_rows), 0), dtype=np.int32)
+    levels, missing = c_int32(0), c_int32(-1)
+    status = lib().spmv_c_sptrsv_levels(int(num_rows), _np_ptr(rp), _np_ptr(ci), int(uplo), _np_ptr(level_ptr),
+                                        _np_ptr(order), byref(levels), byref(missing))
+    if status != 0:
+        return status, None, None, 0, -1
+    return status, level_ptr[:levels.value + 1].copy(), order, levels.value, missing.value
 
 
 def spmv_auto_config(A) -> SpMVConfig:

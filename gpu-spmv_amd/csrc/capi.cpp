@@ -8,6 +8,7 @@
 #include "spmv/bicgstab.h"
 #include "spmv/cg.h"
 #include "spmv/pagerank.h"
+#include "spmv/sptrsv.h"
 #include "spmv_c.h"
 
 #include <cstddef>
@@ -58,6 +59,16 @@ static_assert(offsetof(spmv_c_bicgstab_result, iterations) == offsetof(BiCGStabR
               offsetof(spmv_c_bicgstab_result, breakdown) == offsetof(BiCGStabResult, breakdown) &&
               offsetof(spmv_c_bicgstab_result, elapsed_ms) == offsetof(BiCGStabResult, elapsed_ms),
               "BiCGStabResult layout");
+static_assert(sizeof(spmv_c_sptrsv_config) == sizeof(SpTRSVConfig) && sizeof(SpTRSVConfig) == 16, "SpTRSVConfig layout");
+static_assert(offsetof(spmv_c_sptrsv_config, diag) == offsetof(SpTRSVConfig, diag) &&
+              offsetof(spmv_c_sptrsv_config, ordered) == offsetof(SpTRSVConfig, ordered) &&
+              offsetof(spmv_c_sptrsv_config, reserved) == offsetof(SpTRSVConfig, reserved), "SpTRSVConfig layout");
+static_assert(sizeof(spmv_c_sptrsv_result) == sizeof(SpTRSVResult) && sizeof(SpTRSVResult) == 24, "SpTRSVResult layout");
+static_assert(offsetof(spmv_c_sptrsv_result, num_levels) == offsetof(SpTRSVResult, num_levels) &&
+              offsetof(spmv_c_sptrsv_result, launches) == offsetof(SpTRSVResult, launches) &&
+              offsetof(spmv_c_sptrsv_result, lanes_per_row) == offsetof(SpTRSVResult, lanes_per_row) &&
+              offsetof(spmv_c_sptrsv_result, analysis_ms) == offsetof(SpTRSVResult, analysis_ms) &&
+              offsetof(spmv_c_sptrsv_result, elapsed_ms) == offsetof(SpTRSVResult, elapsed_ms), "SpTRSVResult layout");
 
 namespace {
 
@@ -454,6 +465,33 @@ int spmv_c_bicgstab_solve(const spmv_c_csr* A, const float* d_b, float* d_x, con
     const BiCGStabResult r = bicgstab_solve(cxx(A), d_b, d_x, reinterpret_cast<const BiCGStabConfig*>(config));
     if (out) std::memcpy(out, &r, sizeof(r));
     return r.error_code;
+}
+
+int spmv_c_sptrsv_csr(const spmv_c_csr* A, const float* d_b, float* d_x, const spmv_c_sptrsv_config* config,
+                      spmv_c_sptrsv_result* out) {
+    const SpTRSVResult r = sptrsv_csr(cxx(A), d_b, d_x, reinterpret_cast<const SpTRSVConfig*>(config));
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
+}
+
+int spmv_c_sptrsv_csr_async(const spmv_c_csr* A, const float* d_b, float* d_x, const spmv_c_sptrsv_config* config,
+                            void* hip_stream) {
+    return sptrsv_csr_async(cxx(A), d_b, d_x, reinterpret_cast<const SpTRSVConfig*>(config), as_stream(hip_stream));
+}
+
+int spmv_c_sptrsv_analyze(const spmv_c_csr* A, int uplo, spmv_c_sptrsv_result* out) {
+    const SpTRSVResult r = sptrsv_analyze(cxx(A), uplo);
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
+}
+
+int spmv_c_sptrsv_cpu_csr(const spmv_c_csr* A, const float* b, float* x, const spmv_c_sptrsv_config* config) {
+    return sptrsv_cpu_csr(cxx(A), b, x, reinterpret_cast<const SpTRSVConfig*>(config));
+}
+
+int spmv_c_sptrsv_levels(int num_rows, const int32_t* row_ptrs, const int32_t* col_indices, int uplo,
+                         int32_t* level_ptr, int32_t* order, int32_t* num_levels, int32_t* first_missing_diagonal) {
+    return sptrsv_levels(num_rows, row_ptrs, col_indices, uplo, level_ptr, order, num_levels, first_missing_diagonal);
 }
 
 // ---- bandwidth ----

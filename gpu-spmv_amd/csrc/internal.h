@@ -62,8 +62,32 @@ struct TransposeArrays {
     void release();
 };
 
+// sptrsv_csr's level schedule of one triangle (sptrsv_host.cpp): structure only, never the values.  Shared between
+// the side table and the solves in flight, like a tiled plan.
+struct SptrsvSchedule {
+    struct Group {                   // one launch
+        int level_begin, level_end;  // levels [level_begin, level_end)
+        int rows;                    // rows of the widest level in it
+    };
+    int* d_level_ptr = nullptr;      // [num_levels + 1]
+    int* d_order = nullptr;          // [num_rows] rows by level, ascending row index within a level
+    int  num_levels = 0;
+    std::vector<Group> groups;       // level_end - level_begin > 1 only for narrow levels: one workgroup walks them
+    long long triangle_nnz = 0;      // stored entries inside the triangle, diagonal included
+    int  first_missing_diagonal = -1;
+    // what it was built from (the transpose cache's rule)
+    const void* row_ptrs = nullptr;
+    const void* cols = nullptr;
+    long long nnz = 0;
+    int num_rows = 0, num_cols = 0, uplo = 0;
+    ~SptrsvSchedule();
+};
+
 struct CsrAux {
     PrWorkspace pagerank;
+    // sptrsv_csr: one schedule per triangle, built on first use
+    std::mutex sptrsv_lock;          // one analysis per matrix when threads race on the first call
+    std::shared_ptr<const SptrsvSchedule> sptrsv[2];
     // row-length statistics computed once (host scan or device reduction)
     bool   have_stats = false;
     CSRStats stats{};
@@ -155,6 +179,7 @@ void    ell_aux_drop(const void* key);
 //   place=scattered            placing pass of the plan build entry by entry (no LDS staging)
 //   pr_plan_after=N            direct steps pagerank() takes before it builds a plan (default 4)
 //   pr_copy=pageable           pagerank() copies its result into a pageable array (no pinned pool)
+//   sptrsv_lanes=N             lanes per row of sptrsv_csr with ordered = 0 (1, 2, 4, ... 64; anything else is ignored)
 // Everything else the library reads from the environment is listed in INTEGRATION.md.
 bool debug_option(const char* key, long long* value = nullptr, char* text = nullptr, size_t text_size = 0);
 // the same "key=value,key" syntax for another variable's value (SPMV_MULTI_GPU); `list` may be null
@@ -191,6 +216,14 @@ hipError_t launch_fill_zero(float* d_y, size_t n, hipStream_t s);
 // device transpose (transpose.hip): validates A (INVALID_FORMAT before anything is allocated), then builds A^T on
 // `s` and returns after the build completed, its scratch freed.  The caller owns *out on SUCCESS.
 int transpose_build(const CSRMatrix* A, TransposeArrays* out, hipStream_t s);
+// sparse triangular solve (sptrsv.hip): the launches of one solve, one per group of the schedule, in stream order;
+// kSptrsvNarrowRows is the widest level a single workgroup takes inside a run of levels
+constexpr int kSptrsvNarrowRows = 256;
+constexpr int kSptrsvMaxRunLevels = 8192;     // levels per single-workgroup launch at most (bounds one kernel's time)
+hipError_t launch_sptrsv(const SptrsvSchedule& schedule, const CSRMatrix* A, const float* d_b, float* d_x, int uplo,
+                         int unit_diagonal, bool ordered, int lanes_per_row, hipStream_t s);
+// b and x overlap without being the same array (solver_common.h ranges_overlap; the solve in place is allowed)
+bool sptrsv_partial_overlap(const float* d_b, const float* d_x, long long n);
 hipError_t launch_ell_from_csr(const CSRMatrix* csr, int width, int* d_ell_cols, float* d_ell_vals,
                                hipStream_t s);
 hipError_t device_count_ell_nnz(const ELLMatrix* A, long long* out, hipStream_t s);

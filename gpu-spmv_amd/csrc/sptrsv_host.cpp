@@ -1,0 +1,343 @@
+// sptrsv_host.cpp — host side of the sparse triangular solve (include/spmv/sptrsv.h): the level
+// analysis, the schedule kept with the matrix, the host substitution sptrsv_cpu_csr and the entry points.  The
+// kernels are in sptrsv.hip.  Built without FMA contraction: sptrsv_cpu_csr rounds the product, then the sum.
+#include "internal.h"
+#include "spmv/sptrsv.h"
+
+#include <algorithm>
+#include <chrono>
+#include <vector>
+
+namespace spmv {
+
+int sptrsv_levels(int num_rows, const int* row_ptrs, const int* col_indices, int uplo, int* level_ptr, int* order,
+                  int* num_levels, int* first_missing_diagonal) {
+    using detail::code;
+    if (num_rows < 0 || !row_ptrs || !level_ptr || !num_levels || (num_rows > 0 && !order) ||
+        (uplo != SpTRSVConfig::LOWER && uplo != SpTRSVConfig::UPPER)) {
+        return code(SpMVError::INVALID_ARGUMENT);
+    }
+    const int n = num_rows;
+    if (row_ptrs[0] < 0) return code(SpMVError::INVALID_FORMAT);
+    for (int i = 0; i < n; ++i) {
+        if (row_ptrs[i + 1] < row_ptrs[i]) return code(SpMVError::INVALID_FORMAT);
+    }
+    if (row_ptrs[n] > row_ptrs[0] && !col_indices) return code(SpMVError::INVALID_ARGUMENT);
+    for (int j = row_ptrs[0]; j < row_ptrs[n]; ++j) {
+        if (col_indices[j] < 0 || col_indices[j] >= n) return code(SpMVError::INVALID_FORMAT);
+    }
+
+    // level of every row, in the order the substitution visits them; `order` holds the levels until the sort
+    const bool upper = uplo == SpTRSVConfig::UPPER;
+    int missing = -1;
+    int levels = 0;
+    for (int step = 0; step < n; ++step) {
+        const int i = upper ? n - 1 - step : step;
+        int level = 0;
+        bool diagonal = false;
+        for (int j = row_ptrs[i]; j < row_ptrs[i + 1]; ++j) {
+            const int c = col_indices[j];
+            if (c == i) {
+                diagonal = true;
+            } else if (upper ? c > i : c < i) {
+                level = std::max(level, order[c] + 1);
+            }
+        }
+        order[i] = level;
+        levels = std::max(levels, level + 1);
+        if (!diagonal && (missing < 0 || i < missing)) missing = i;
+    }
+
+    // counting sort by level, rows ascending within a level
+    std::vector<int> level_of(order, order + n);
+    std::fill(level_ptr, level_ptr + levels + 1, 0);
+    for (int i = 0; i < n; ++i) ++level_ptr[level_of[i] + 1];
+    for (int l = 0; l < levels; ++l) level_ptr[l + 1] += level_ptr[l];
+    std::vector<int> next(level_ptr, level_ptr + levels);
+    for (int i = 0; i < n; ++i) order[next[level_of[i]]++] = i;
+
+    *num_levels = levels;
+    if (first_missing_diagonal) *first_missing_diagonal = missing;
+    return code(SpMVError::SUCCESS);
+}
+
+int sptrsv_cpu_csr(const CSRMatrix* A, const float* b, float* x, const SpTRSVConfig* config) {
+    using detail::code;
+    if (!A || !b || !x) return code(SpMVError::INVALID_ARGUMENT);
+    if (A->num_rows != A->num_cols) return code(SpMVError::INVALID_DIMENSION);
+    const int n = A->num_rows;
+    if (n == 0) return code(SpMVError::SUCCESS);
+    if (n < 0 || !A->row_ptrs || (A->nnz > 0 && (!A->col_indices || !A->values))) {
+        return code(SpMVError::INVALID_ARGUMENT);
+    }
+    const SpTRSVConfig defaults;
+    const SpTRSVConfig& cfg = config ? *config : defaults;
+    if ((cfg.uplo != SpTRSVConfig::LOWER && cfg.uplo != SpTRSVConfig::UPPER) ||
+        (cfg.diag != SpTRSVConfig::NON_UNIT && cfg.diag != SpTRSVConfig::UNIT)) {
+        return code(SpMVError::INVALID_ARGUMENT);
+    }
+    const bool upper = cfg.uplo == SpTRSVConfig::UPPER;
+    const bool unit = cfg.diag == SpTRSVConfig::UNIT;
+    const int* ptr = A->row_ptrs;
+    const int* col = A->col_indices;
+    // everything that can fail, before x is touched
+    if (ptr[0] < 0 || ptr[n] > A->nnz) return code(SpMVError::INVALID_FORMAT);
+    for (int i = 0; i < n; ++i) {
+        if (ptr[i + 1] < ptr[i]) return code(SpMVError::INVALID_FORMAT);
+    }
+    bool every_diagonal = true;
+    for (int i = 0; i < n; ++i) {
+        bool diagonal = false;
+        for (int j = ptr[i]; j < ptr[i + 1]; ++j) {
+            if (col[j] < 0 || col[j] >= n) return code(SpMVError::INVALID_FORMAT);
+            diagonal |= col[j] == i;
+        }
+        every_diagonal &= diagonal;
+    }
+    if (!unit && !every_diagonal) return code(SpMVError::INVALID_ARGUMENT);
+
+    for (int step = 0; step < n; ++step) {
+        const int i = upper ? n - 1 - step : step;
+        float s = 0.0f;
+        float d = 0.0f;
+        for (int j = ptr[i]; j < ptr[i + 1]; ++j) {
+            const int c = col[j];
+            if (c == i) {
+                d = d + A->values[j];
+            } else if (upper ? c > i : c < i) {
+                const float product = A->values[j] * x[c];
+                s = s + product;
+            }
+        }
+        x[i] = (b[i] - s) / (unit ? 1.0f : d);
+    }
+    return code(SpMVError::SUCCESS);
+}
+
+namespace detail {
+
+SptrsvSchedule::~SptrsvSchedule() {
+    if (d_level_ptr) (void)hipFree(d_level_ptr);
+    if (d_order) (void)hipFree(d_order);
+}
+
+namespace {
+
+using ScheduleRef = std::shared_ptr<const SptrsvSchedule>;
+
+// One launch per group: a level wider than kSptrsvNarrowRows alone, consecutive narrower ones together.
+void group_levels(const std::vector<int>& level_ptr, int num_levels, std::vector<SptrsvSchedule::Group>* groups) {
+    groups->clear();
+    bool open = false;       // the last group is a run that may take another narrow level
+    for (int l = 0; l < num_levels; ++l) {
+        const int rows = level_ptr[l + 1] - level_ptr[l];
+        const bool narrow = rows <= kSptrsvNarrowRows;
+        if (narrow && open && groups->back().level_end - groups->back().level_begin < kSptrsvMaxRunLevels) {
+            groups->back().level_end = l + 1;
+            groups->back().rows = std::max(groups->back().rows, rows);
+        } else {
+            groups->push_back({l, l + 1, rows});
+            open = narrow;
+        }
+    }
+}
+
+bool matches(const ScheduleRef& s, const CSRMatrix* A, int uplo) {
+    return s && s->row_ptrs == A->d_row_ptrs && s->cols == A->d_col_indices && s->nnz == A->nnz &&
+           s->num_rows == A->num_rows && s->num_cols == A->num_cols && s->uplo == uplo;
+}
+
+// A's schedule for `uplo` from its aux entry, built when it is not there or no longer matches A.  *analysis_ms is
+// the host time of a build, 0 for a cache hit.
+int schedule_for(const CSRMatrix* A, int uplo, hipStream_t stream, ScheduleRef* out, float* analysis_ms) {
+    *analysis_ms = 0.0f;
+    CsrAux* aux = aux_lookup(A->d_row_ptrs, true);
+    std::lock_guard<std::mutex> guard(aux->sptrsv_lock);
+    if (matches(aux->sptrsv[uplo], A, uplo)) {
+        *out = aux->sptrsv[uplo];
+        return code(SpMVError::SUCCESS);
+    }
+    aux->sptrsv[uplo].reset();
+    const TraceRange range("spmv:sptrsv_analysis");
+    const auto t0 = std::chrono::steady_clock::now();
+    const int n = A->num_rows;
+    const size_t nnz = static_cast<size_t>(std::max(A->nnz, 0));
+
+    // one read-back of the structure (the device arrays are what the kernels walk; host arrays may be absent)
+    std::vector<int> row_ptrs(static_cast<size_t>(n) + 1), cols(nnz);
+    bool ok = hipMemcpyAsync(row_ptrs.data(), A->d_row_ptrs, row_ptrs.size() * sizeof(int), hipMemcpyDeviceToHost,
+                             stream) == hipSuccess;
+    if (ok && nnz > 0) {
+        ok = hipMemcpyAsync(cols.data(), A->d_col_indices, nnz * sizeof(int), hipMemcpyDeviceToHost, stream) ==
+             hipSuccess;
+    }
+    if (!ok || hipStreamSynchronize(stream) != hipSuccess) {
+        (void)hipGetLastError();
+        return code(SpMVError::CUDA_MEMCPY);
+    }
+    if (row_ptrs[0] < 0 || row_ptrs[n] > A->nnz) return code(SpMVError::INVALID_FORMAT);
+    for (int i = 0; i < n; ++i) {        // (before sptrsv_levels reads cols[row_ptrs[0] .. row_ptrs[n]))
+        if (row_ptrs[i + 1] < row_ptrs[i]) return code(SpMVError::INVALID_FORMAT);
+    }
+
+    std::vector<int> level_ptr(static_cast<size_t>(n) + 1), order(static_cast<size_t>(n));
+    int num_levels = 0, missing = -1;
+    const int status = sptrsv_levels(n, row_ptrs.data(), cols.data(), uplo, level_ptr.data(), order.data(),
+                                     &num_levels, &missing);
+    if (status != 0) return status;
+
+    auto built = std::make_shared<SptrsvSchedule>();
+    built->num_levels = num_levels;
+    built->first_missing_diagonal = missing;
+    group_levels(level_ptr, num_levels, &built->groups);
+    const bool upper = uplo == SpTRSVConfig::UPPER;
+    for (int i = 0; i < n; ++i) {
+        for (int j = row_ptrs[i]; j < row_ptrs[i + 1]; ++j) {
+            built->triangle_nnz += upper ? cols[j] >= i : cols[j] <= i;
+        }
+    }
+    const size_t ptr_bytes = (static_cast<size_t>(num_levels) + 1) * sizeof(int);
+    const size_t order_bytes = static_cast<size_t>(n) * sizeof(int);
+    if (malloc_any_time(reinterpret_cast<void**>(&built->d_level_ptr), ptr_bytes) != hipSuccess ||
+        malloc_any_time(reinterpret_cast<void**>(&built->d_order), order_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return code(SpMVError::CUDA_MALLOC);
+    }
+    if (hipMemcpyAsync(built->d_level_ptr, level_ptr.data(), ptr_bytes, hipMemcpyHostToDevice, stream) != hipSuccess ||
+        hipMemcpyAsync(built->d_order, order.data(), order_bytes, hipMemcpyHostToDevice, stream) != hipSuccess ||
+        hipStreamSynchronize(stream) != hipSuccess) {       // (the host vectors go away with this frame)
+        (void)hipGetLastError();
+        return code(SpMVError::CUDA_MEMCPY);
+    }
+    built->row_ptrs = A->d_row_ptrs;
+    built->cols = A->d_col_indices;
+    built->nnz = A->nnz;
+    built->num_rows = A->num_rows;
+    built->num_cols = A->num_cols;
+    built->uplo = uplo;
+    aux->sptrsv[uplo] = built;
+    *out = built;
+    *analysis_ms = std::max(std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(),
+                            1e-6f);
+    return code(SpMVError::SUCCESS);
+}
+
+// checks 1-4 of sptrsv.h, shared by the solve and sptrsv_analyze
+int check_matrix(const CSRMatrix* A, bool* nothing_to_do) {
+    *nothing_to_do = false;
+    if (A->num_rows != A->num_cols) return code(SpMVError::INVALID_DIMENSION);
+    if (A->num_rows == 0) {
+        *nothing_to_do = true;
+        return code(SpMVError::SUCCESS);
+    }
+    if (A->num_rows < 0 || A->nnz < 0 || !A->d_row_ptrs || (A->nnz > 0 && (!A->d_col_indices || !A->d_values))) {
+        return code(SpMVError::INVALID_FORMAT);
+    }
+    return code(SpMVError::SUCCESS);
+}
+
+int lanes_for(const SptrsvSchedule& s, bool ordered) {
+    if (ordered) return 1;
+    long long forced = 0;
+    if (debug_option("sptrsv_lanes", &forced) && forced >= 1 && forced <= 64 && (forced & (forced - 1)) == 0) {
+        return static_cast<int>(forced);
+    }
+    return pick_lanes_per_row(static_cast<float>(s.triangle_nnz) / static_cast<float>(s.num_rows));
+}
+
+// Everything before the launches.  On SUCCESS with *schedule null there is nothing to do (no rows).
+int prepare(const CSRMatrix* A, const float* d_b, const float* d_x, const SpTRSVConfig& cfg, hipStream_t stream,
+            ScheduleRef* schedule, float* analysis_ms) {
+    schedule->reset();
+    *analysis_ms = 0.0f;
+    if (!A || !d_b || !d_x) return code(SpMVError::INVALID_ARGUMENT);
+    bool nothing = false;
+    const int status = check_matrix(A, &nothing);
+    if (status != 0 || nothing) return status;
+    if ((cfg.uplo != SpTRSVConfig::LOWER && cfg.uplo != SpTRSVConfig::UPPER) ||
+        (cfg.diag != SpTRSVConfig::NON_UNIT && cfg.diag != SpTRSVConfig::UNIT) ||
+        (cfg.ordered != 0 && cfg.ordered != 1)) {
+        return code(SpMVError::INVALID_ARGUMENT);
+    }
+    if (sptrsv_partial_overlap(d_b, d_x, A->num_rows)) return code(SpMVError::INVALID_ARGUMENT);
+    ScheduleRef found;
+    const int analysed = schedule_for(A, cfg.uplo, stream, &found, analysis_ms);
+    if (analysed != 0) return analysed;
+    if (cfg.diag == SpTRSVConfig::NON_UNIT && found->first_missing_diagonal >= 0) {
+        return code(SpMVError::INVALID_ARGUMENT);
+    }
+    *schedule = found;
+    return code(SpMVError::SUCCESS);
+}
+
+} // namespace
+} // namespace detail
+
+SpTRSVResult sptrsv_csr(const CSRMatrix* A, const float* d_b, float* d_x, const SpTRSVConfig* config) {
+    using namespace detail;
+    SpTRSVResult result;
+    const SpTRSVConfig defaults;
+    const SpTRSVConfig& cfg = config ? *config : defaults;
+    hipStream_t stream = current_stream();
+    ScheduleRef schedule;
+    result.error_code = prepare(A, d_b, d_x, cfg, stream, &schedule, &result.analysis_ms);
+    if (result.error_code != 0 || !schedule) return result;
+
+    const TraceRange range("spmv:sptrsv_csr");
+    const int lanes = lanes_for(*schedule, cfg.ordered == 1);
+    result.num_levels = schedule->num_levels;
+    result.launches = static_cast<int>(schedule->groups.size());
+    result.lanes_per_row = lanes;
+    EventPair& ev = thread_events();
+    if (!ev.start || !ev.stop || hipEventRecord(ev.start, stream) != hipSuccess) {
+        result.error_code = code(SpMVError::KERNEL_LAUNCH);
+        return result;
+    }
+    const hipError_t launched = launch_sptrsv(*schedule, A, d_b, d_x, cfg.uplo, cfg.diag == SpTRSVConfig::UNIT,
+                                              cfg.ordered == 1, lanes, stream);
+    const hipError_t recorded = hipEventRecord(ev.stop, stream);
+    const hipError_t waited = hipEventSynchronize(ev.stop);
+    if (launched != hipSuccess || recorded != hipSuccess || waited != hipSuccess || hipGetLastError() != hipSuccess ||
+        hipEventElapsedTime(&result.elapsed_ms, ev.start, ev.stop) != hipSuccess) {
+        result.error_code = code(SpMVError::KERNEL_LAUNCH);
+    }
+    return result;
+}
+
+int sptrsv_csr_async(const CSRMatrix* A, const float* d_b, float* d_x, const SpTRSVConfig* config,
+                     hipStream_t stream) {
+    using namespace detail;
+    const SpTRSVConfig defaults;
+    const SpTRSVConfig& cfg = config ? *config : defaults;
+    ScheduleRef schedule;
+    float analysis_ms = 0.0f;
+    const int status = prepare(A, d_b, d_x, cfg, stream, &schedule, &analysis_ms);
+    if (status != 0 || !schedule) return status;
+    const hipError_t e = launch_sptrsv(*schedule, A, d_b, d_x, cfg.uplo, cfg.diag == SpTRSVConfig::UNIT,
+                                       cfg.ordered == 1, lanes_for(*schedule, cfg.ordered == 1), stream);
+    return e == hipSuccess ? code(SpMVError::SUCCESS) : code(SpMVError::KERNEL_LAUNCH);
+}
+
+SpTRSVResult sptrsv_analyze(const CSRMatrix* A, int uplo) {
+    using namespace detail;
+    SpTRSVResult result;
+    if (!A) {
+        result.error_code = code(SpMVError::INVALID_ARGUMENT);
+        return result;
+    }
+    bool nothing = false;
+    result.error_code = check_matrix(A, &nothing);
+    if (result.error_code != 0 || nothing) return result;
+    if (uplo != SpTRSVConfig::LOWER && uplo != SpTRSVConfig::UPPER) {
+        result.error_code = code(SpMVError::INVALID_ARGUMENT);
+        return result;
+    }
+    ScheduleRef schedule;
+    result.error_code = schedule_for(A, uplo, current_stream(), &schedule, &result.analysis_ms);
+    if (result.error_code != 0) return result;
+    result.num_levels = schedule->num_levels;
+    result.launches = static_cast<int>(schedule->groups.size());
+    return result;
+}
+
+} // namespace spmv

@@ -296,6 +296,45 @@ typedef struct spmv_c_bicgstab_result {
 int spmv_c_bicgstab_solve(const spmv_c_csr* A, const float* d_b, float* d_x, const spmv_c_bicgstab_config* config,
                           spmv_c_bicgstab_result* out);
 
+/* ---- sparse triangular solve with level scheduling (extension; include/spmv/sptrsv.h) ---- */
+/* uplo: 0 LOWER, 1 UPPER; diag: 0 NON_UNIT, 1 UNIT; ordered: 1 = one lane per row in the CPU's summation order
+ * (bit-identical to spmv_c_sptrsv_cpu_csr), 0 = 1-64 lanes per row; reserved: 0 (16 bytes) */
+typedef struct spmv_c_sptrsv_config {
+    int32_t uplo;
+    int32_t diag;
+    int32_t ordered;
+    int32_t reserved;
+} spmv_c_sptrsv_config;
+
+/* 24 bytes */
+typedef struct spmv_c_sptrsv_result {
+    int32_t error_code;
+    int32_t num_levels;
+    int32_t launches;
+    int32_t lanes_per_row;
+    float   analysis_ms;   /* 0 when the cached schedule was used */
+    float   elapsed_ms;    /* the solve launches only */
+} spmv_c_sptrsv_result;
+
+/* Solves T x = b on the device, T the chosen triangle of the square matrix A (entries on the other side of the
+ * diagonal are ignored); d_b and d_x hold num_rows floats and may be the same array.  config NULL = defaults (LOWER,
+ * NON_UNIT, 0, 0).  Argument checks, analysis cache and numerics as sptrsv_csr in include/spmv/sptrsv.h.  The return
+ * value equals out->error_code (out may be NULL). */
+int spmv_c_sptrsv_csr(const spmv_c_csr* A, const float* d_b, float* d_x, const spmv_c_sptrsv_config* config,
+                      spmv_c_sptrsv_result* out);
+/* the same solve enqueued on a caller stream without timing or synchronisation (the first call per matrix and
+ * triangle still analyses and synchronises that stream: call spmv_c_sptrsv_analyze first) */
+int spmv_c_sptrsv_csr_async(const spmv_c_csr* A, const float* d_b, float* d_x, const spmv_c_sptrsv_config* config,
+                            void* hip_stream);
+/* builds and caches the schedule of A's uplo triangle ahead of a timed call; fills num_levels, launches, analysis_ms */
+int spmv_c_sptrsv_analyze(const spmv_c_csr* A, int uplo, spmv_c_sptrsv_result* out);
+/* host forward / backward substitution on A's host arrays (b and x host arrays, may be the same); returns the error code */
+int spmv_c_sptrsv_cpu_csr(const spmv_c_csr* A, const float* b, float* x, const spmv_c_sptrsv_config* config);
+/* the level analysis as a pure host function: level_ptr[num_rows + 1], order[num_rows]; *first_missing_diagonal (may
+ * be NULL) = lowest row without a stored diagonal entry, or -1 */
+int spmv_c_sptrsv_levels(int num_rows, const int32_t* row_ptrs, const int32_t* col_indices, int uplo,
+                         int32_t* level_ptr, int32_t* order, int32_t* num_levels, int32_t* first_missing_diagonal);
+
 /* ---- bandwidth model: reference include/spmv/bandwidth.h:21-27 ---- */
 int spmv_c_compute_bandwidth_csr(const spmv_c_csr* A, float elapsed_ms, spmv_c_bandwidth* out);
 int spmv_c_compute_bandwidth_ell(const spmv_c_ell* A, float elapsed_ms, spmv_c_bandwidth* out);
