@@ -286,6 +286,7 @@ _SIGNATURES = {
     "spmv_c_pr_expand": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "spmv_c_pr_reset": (c_int, [c_void_p, c_float, c_void_p]),
     "spmv_c_pr_step": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p]),
+    "spmv_c_pr_step_commit": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p]),
     "spmv_c_pr_step_push": (c_int, [c_void_p, c_void_p, c_void_p, c_float, POINTER(c_void_p), c_int, c_void_p]),
     "spmv_c_pr_reduce": (c_int, [c_void_p, c_void_p, c_void_p]),
     "spmv_c_pr_commit": (c_int, [c_void_p, c_void_p, c_float, c_void_p]),

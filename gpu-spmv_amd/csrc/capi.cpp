@@ -608,6 +608,10 @@ spmv_c_pr_shard* spmv_c_pr_shard_create_chunked(const spmv_c_csr* A_local, int b
 
 void spmv_c_pr_shard_destroy(spmv_c_pr_shard* h) {
     if (!h) return;
+    if (h->shard.commit_pending) {          // the state dies with the shard, but the rule has no exception: flush
+        (void)detail::pr_flush(h->shard, h->shard.pending_stream);
+        (void)hipGetLastError();
+    }
     if (h->shard.d_state) (void)hipFree(h->shard.d_state);
     if (h->shard.d_block_partials) (void)hipFree(h->shard.d_block_partials);
     delete h;
@@ -619,6 +623,7 @@ int spmv_c_pr_reset(spmv_c_pr_shard* h, float dangling_sum, void* hip_stream) {
     fresh.dangling_sum = dangling_sum;
     h->shard.expanded_strips = 0;          // a head start taken for a step that never ran is void
     h->shard.expanded_long = false;
+    detail::pr_drop_pending(h->shard);     // ... and so is a commit that nobody asked to see
     // pageable source: the copy is staged before the call returns
     return hipMemcpyAsync(h->shard.d_state, &fresh, sizeof(fresh), hipMemcpyHostToDevice,
                           as_stream(hip_stream)) == hipSuccess
@@ -630,6 +635,12 @@ int spmv_c_pr_step(spmv_c_pr_shard* h, const float* d_r_old, float* d_r_new, flo
     if (!h || !d_r_old || !d_r_new) return kInvalidArgument;
     return launch_code(detail::pr_step(h->shard, d_r_old, d_r_new, damping, detail::PushTargets{},
                                        as_stream(hip_stream)));
+}
+
+int spmv_c_pr_step_commit(spmv_c_pr_shard* h, const float* d_r_old, float* d_r_new, float damping,
+                          float tolerance, void* hip_stream) {
+    if (!h || !d_r_old || !d_r_new) return kInvalidArgument;
+    return launch_code(detail::pr_step_commit(h->shard, d_r_old, d_r_new, damping, tolerance, as_stream(hip_stream)));
 }
 
 int spmv_c_pr_expand(spmv_c_pr_shard* h, const float* d_r_old, int64_t cols_ready, void* hip_stream) {
@@ -678,8 +689,18 @@ int spmv_c_pr_commit_gathered(spmv_c_pr_shard* h, const float* d_gathered, int w
 int spmv_c_pr_status_get(spmv_c_pr_shard* h, spmv_c_pr_status* out, void* hip_stream) {
     if (!h || !out) return kInvalidArgument;
     hipStream_t s = as_stream(hip_stream);
-    if (hipMemcpyAsync(out, h->shard.d_state, sizeof(*out), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {
+    if (detail::pr_flush(h->shard, s) != hipSuccess) return kLaunch;
+    if (hipMemcpyAsync(out, h->shard.d_state, sizeof(*out), hipMemcpyDeviceToHost, s) != hipSuccess) {
+        return static_cast<int>(SpMVError::CUDA_MEMCPY);
+    }
+    // A stream that is being captured cannot be waited for: the flush and the copy become nodes of the graph,
+    // and `out` (pinned memory that outlives the graph) is filled by every replay.
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &capturing) != hipSuccess) {
+        (void)hipGetLastError();
+        capturing = hipStreamCaptureStatusNone;
+    }
+    if (capturing == hipStreamCaptureStatusNone && hipStreamSynchronize(s) != hipSuccess) {
         return static_cast<int>(SpMVError::CUDA_MEMCPY);
     }
     return 0;

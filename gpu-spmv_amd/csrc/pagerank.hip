@@ -20,6 +20,7 @@
 #include "internal.h"
 #include "device_common.h"
 #include "pagerank_engine.h"
+#include "pr_commit_device.h"
 #include "tiled.h"
 #include "spmv/pagerank.h"
 
@@ -114,23 +115,7 @@ void pr_reduce_kernel(const double* __restrict__ block_partials, int num_blocks,
 __global__ __launch_bounds__(kBlock)
 void pr_reduce_commit_kernel(const double* __restrict__ block_partials, int num_blocks, float tolerance,
                              PrState* __restrict__ state) {
-    if (state->done) return;
-    double res2 = 0.0, mass = 0.0;
-    for (int b = threadIdx.x; b < num_blocks; b += kBlock) {
-        res2 += block_partials[2 * b];
-        mass += block_partials[2 * b + 1];
-    }
-    block_sum2(res2, mass);
-    if (threadIdx.x == 0) {
-        const float residual = static_cast<float>(sqrt(res2));
-        state->iterations += 1;
-        state->final_residual = residual;
-        state->dangling_sum = static_cast<float>(mass);
-        if (residual < tolerance) {
-            state->converged = 1;
-            state->done = 1;
-        }
-    }
+    pr_fold_and_commit(block_partials, num_blocks, tolerance, state);
 }
 
 // Applies the (already globally reduced) sums: residual, iteration count,
@@ -303,8 +288,25 @@ int pr_shard_prepare(PrShard* sh, PlanRef tiled) {
     return std::max(sh->grid, kMaxResidentBlocks);
 }
 
+hipError_t pr_flush(const PrShard& sh, hipStream_t s) {
+    if (!sh.commit_pending) return hipSuccess;
+    sh.commit_pending = false;
+    return pr_reduce_commit(sh, sh.pending_tolerance, s);
+}
+
 hipError_t pr_step(const PrShard& sh, const float* r_old, float* r_new, float damping,
                    const PushTargets& push, hipStream_t s) {
+    // A pending commit rides in this step's phase-1 launch when that is a plain tiled one on the stream the
+    // commit's partials were written on; every other way of stepping gets it as a launch of its own first.
+    const bool plain = sh.tiled && sh.local_rows > 0 && push.count == 0 && sh.map.piece == 0x7fffffff
+                    && sh.expanded_strips == 0 && !sh.expanded_long;
+    CommitRider rider;
+    if (sh.commit_pending && plain && sh.pending_stream == s) {
+        rider = CommitRider{sh.d_block_partials, sh.grid, sh.pending_tolerance, sh.d_state};
+        sh.commit_pending = false;
+    } else if (const hipError_t e = pr_flush(sh, s); e != hipSuccess) {
+        return e;
+    }
     if (sh.local_rows <= 0) return hipSuccess;
     if (sh.tiled) {
         // phase 1 of whatever pr_expand has not run yet (all of it, normally), then phase 2
@@ -318,7 +320,7 @@ hipError_t pr_step(const PrShard& sh, const float* r_old, float* r_new, float da
         std::unique_lock<std::mutex> pair(sh.tiled->launch_lock, std::defer_lock);
         if (done == 0 && !long_done) pair.lock();
         if (done < sh.tiled->num_strips || !long_done) {
-            const hipError_t e = tiled_pagerank_expand(*sh.tiled, done, sh.tiled->num_strips, !long_done, r_old, sh.d_state, s);
+            const hipError_t e = tiled_pagerank_expand(*sh.tiled, done, sh.tiled->num_strips, !long_done, r_old, sh.d_state, rider, s);
             if (e != hipSuccess) return e;
         }
         return tiled_pagerank_finish(*sh.tiled, sh.map, sh.n_global, r_old, r_new, sh.d_dangling,
@@ -336,6 +338,7 @@ hipError_t pr_step(const PrShard& sh, const float* r_old, float* r_new, float da
 }
 
 hipError_t pr_expand(const PrShard& sh, const float* r_old, long long cols_ready, hipStream_t s) {
+    if (const hipError_t e = pr_flush(sh, s); e != hipSuccess) return e;
     if (sh.local_rows <= 0 || !sh.tiled) return hipSuccess;
     const TiledPlan& plan = *sh.tiled;
     const bool all = cols_ready >= plan.num_cols;
@@ -343,7 +346,7 @@ hipError_t pr_expand(const PrShard& sh, const float* r_old, long long cols_ready
     const int done = std::min(sh.expanded_strips, plan.num_strips);
     const bool want_long = all && !sh.expanded_long;       // the long rows read all of r_old
     if (ready <= done && !want_long) return hipSuccess;
-    const hipError_t e = tiled_pagerank_expand(plan, done, std::max(ready, done), want_long, r_old, sh.d_state, s);
+    const hipError_t e = tiled_pagerank_expand(plan, done, std::max(ready, done), want_long, r_old, sh.d_state, CommitRider{}, s);
     if (e == hipSuccess) {
         sh.expanded_strips = std::max(ready, done);
         sh.expanded_long = sh.expanded_long || want_long;
@@ -351,25 +354,47 @@ hipError_t pr_expand(const PrShard& sh, const float* r_old, long long cols_ready
     return e;
 }
 
+hipError_t pr_step_commit(const PrShard& sh, const float* r_old, float* r_new, float damping,
+                          float tolerance, hipStream_t s) {
+    const hipError_t e = pr_step(sh, r_old, r_new, damping, PushTargets{}, s);
+    if (e != hipSuccess) return e;
+    // Inside a hipGraph capture nothing is deferred: the host cannot know which captured step is the last one, and
+    // a commit left pending when the capture ends would be missing from every replay.
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &capturing) != hipSuccess) {
+        (void)hipGetLastError();
+        capturing = hipStreamCaptureStatusNone;
+    }
+    if (!sh.tiled || sh.local_rows <= 0 || capturing != hipStreamCaptureStatusNone) return pr_reduce_commit(sh, tolerance, s);
+    sh.commit_pending = true;
+    sh.pending_tolerance = tolerance;
+    sh.pending_stream = s;
+    return hipSuccess;
+}
+
 hipError_t pr_reduce(const PrShard& sh, double* d_sums, hipStream_t s) {
+    if (const hipError_t e = pr_flush(sh, s); e != hipSuccess) return e;
     pr_reduce_kernel<<<1, kBlock, 0, s>>>(sh.d_block_partials, sh.local_rows > 0 ? sh.grid : 0,
                                           sh.d_state, d_sums);
     return hipGetLastError();
 }
 
 hipError_t pr_reduce_commit(const PrShard& sh, float tolerance, hipStream_t s) {
+    if (const hipError_t e = pr_flush(sh, s); e != hipSuccess) return e;
     pr_reduce_commit_kernel<<<1, kBlock, 0, s>>>(sh.d_block_partials, sh.local_rows > 0 ? sh.grid : 0, tolerance,
                                                  sh.d_state);
     return hipGetLastError();
 }
 
 hipError_t pr_commit(const PrShard& sh, const double* d_sums, float tolerance, hipStream_t s) {
+    if (const hipError_t e = pr_flush(sh, s); e != hipSuccess) return e;
     pr_commit_kernel<<<1, 1, 0, s>>>(d_sums, tolerance, sh.d_state);
     return hipGetLastError();
 }
 
 hipError_t pr_commit_gathered(const PrShard& sh, const float* d_gathered, int world, long long stride,
                               long long shard_len, float tolerance, hipStream_t s) {
+    if (const hipError_t e = pr_flush(sh, s); e != hipSuccess) return e;
     pr_commit_gathered_kernel<<<1, 1, 0, s>>>(d_gathered, world, stride, shard_len, tolerance, sh.d_state);
     return hipGetLastError();
 }
@@ -739,8 +764,10 @@ PageRankResult pagerank(const CSRMatrix* adj, const PageRankConfig* config) {
         const detail::TraceRange step_range("spmv:pagerank_step");
         const float* r_old = bufs[iter & 1];
         float* r_new = bufs[(iter + 1) & 1];
-        ok = ok && detail::pr_step(shard, r_old, r_new, config->damping_factor, detail::PushTargets{}, stream) == hipSuccess
-          && detail::pr_reduce_commit(shard, config->tolerance, stream) == hipSuccess
+        // On the tiled engine the commit of step k rides in the phase-1 launch of step k + 1 (pr_step_commit), so the
+        // mirror copied here holds the commits up to step k - 1: the host learns of convergence one step later and
+        // enqueues one more no-op step; the device state, and with it the result, is what it always was.
+        ok = ok && detail::pr_step_commit(shard, r_old, r_new, config->damping_factor, config->tolerance, stream) == hipSuccess
           && hipMemcpyAsync(&pinned[iter & 1], ws->state, sizeof(PrState),
                             hipMemcpyDeviceToHost, stream) == hipSuccess
           && hipEventRecord(ws->seen[iter & 1], stream) == hipSuccess;
@@ -751,7 +778,8 @@ PageRankResult pagerank(const CSRMatrix* adj, const PageRankConfig* config) {
     }
 
     if (ok) {
-        ok = hipMemcpyAsync(&host_state, ws->state, sizeof(PrState), hipMemcpyDeviceToHost, stream) == hipSuccess
+        ok = detail::pr_flush(shard, stream) == hipSuccess       // the last step's commit, if still pending
+          && hipMemcpyAsync(&host_state, ws->state, sizeof(PrState), hipMemcpyDeviceToHost, stream) == hipSuccess
           && hipStreamSynchronize(stream) == hipSuccess;
     }
     trace.mark("iterations");

@@ -59,6 +59,20 @@ struct PrShard {
     PlanRef tiled;                               // set => steps run through the LDS-tiled engine (kept alive by the shard)
     mutable int expanded_strips = 0;             // tiled engine: strips of the coming step already expanded (pr_expand)
     mutable bool expanded_long = false;          // ... and its long rows
+    // Deferred commit (pr_step_commit on the tiled engine): the block partials of the last step are written but
+    // not yet folded into d_state.  The next phase-1 launch on `pending_stream` carries the fold in a workgroup
+    // at the head of its grid; anything else that comes next on the shard flushes it first (pr_flush).
+    mutable bool commit_pending = false;
+    mutable float pending_tolerance = 0.0f;
+    mutable hipStream_t pending_stream = nullptr;
+};
+
+// A pending commit riding in a phase-1 launch (passed to the kernel by value); partials == nullptr: none.
+struct CommitRider {
+    const double* partials = nullptr;
+    int num_blocks = 0;
+    float tolerance = 0.0f;
+    PrState* state = nullptr;
 };
 
 int pr_max_blocks();
@@ -74,6 +88,14 @@ hipError_t pr_expand(const PrShard& shard, const float* d_r_old, long long cols_
 hipError_t pr_reduce(const PrShard& shard, double* d_sums /*[2]*/, hipStream_t s);
 hipError_t pr_commit(const PrShard& shard, const double* d_sums, float tolerance, hipStream_t s);
 hipError_t pr_reduce_commit(const PrShard& shard, float tolerance, hipStream_t s);   // single rank: both in one launch
+// Single rank: the step, its commit deferred into the next step's phase-1 launch where the tiled engine runs
+// (otherwise pr_step + pr_reduce_commit).  d_state lags by this one commit until the next step or pr_flush.
+hipError_t pr_step_commit(const PrShard& shard, const float* d_r_old, float* d_r_new, float damping,
+                          float tolerance, hipStream_t s);
+// Enqueues a pending commit on `s` as a launch of its own (no-op when none is pending).  Every entry above other
+// than a carrying pr_step does this first; callers that read d_state themselves call it before they do.
+hipError_t pr_flush(const PrShard& shard, hipStream_t s);
+inline void pr_drop_pending(const PrShard& shard) { shard.commit_pending = false; }
 hipError_t pr_commit_gathered(const PrShard& shard, const float* d_gathered, int world, long long stride,
                               long long shard_len, float tolerance, hipStream_t s);
 hipError_t pr_fill(float* d_r, size_t n, float value, hipStream_t s);

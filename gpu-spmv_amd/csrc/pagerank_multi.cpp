@@ -382,12 +382,13 @@ PageRankResult pagerank_multi_gpu(const CSRMatrix* adj, const PageRankConfig* co
                     if (q != p) fine = hipStreamWaitEvent(d.stream, shards[q].gathered, 0) == hipSuccess;
                 }
             }
-            fine = fine && detail::pr_step(d.shard, r_old, r_new, config->damping_factor, detail::PushTargets{}, d.stream) == hipSuccess;
+            // one rank, no exchange: the step with its commit deferred into the next step's phase-1 launch
+            // (the mirror below then lags by that one commit: one more no-op step past convergence, same result)
+            fine = fine && (exchange ? detail::pr_step(d.shard, r_old, r_new, config->damping_factor, detail::PushTargets{}, d.stream)
+                                     : detail::pr_step_commit(d.shard, r_old, r_new, config->damping_factor, config->tolerance, d.stream)) == hipSuccess;
             if (fine && exchange) {      // the two partial sums go into the tail of this device's own slice
                 double* tail_slot = reinterpret_cast<double*>(r_new + last_block + (p + 1) * piece - kTail);
                 fine = detail::pr_reduce(d.shard, tail_slot, d.stream) == hipSuccess;
-            } else if (fine) {
-                fine = detail::pr_reduce_commit(d.shard, config->tolerance, d.stream) == hipSuccess;
             }
             if (fine && exchange) {
                 // The exchange: block by block (one block unless SPMV_MULTI_GPU=blocks=C), on the side stream when
@@ -449,6 +450,7 @@ PageRankResult pagerank_multi_gpu(const CSRMatrix* adj, const PageRankConfig* co
                 }
             }
         }
+        fine = detail::pr_flush(d.shard, d.stream) == hipSuccess && fine;      // the last step's commit, if still pending
         fine = hipStreamSynchronize(d.stream) == hipSuccess && fine;
         if (d.side_stream) fine = hipStreamSynchronize(d.side_stream) == hipSuccess && fine;
         return fine;

@@ -14,6 +14,7 @@ namespace spmv {
 namespace detail {
 
 struct PrState;
+struct CommitRider;
 struct PushTargets;
 struct RowMap;
 
@@ -102,8 +103,10 @@ hipError_t tiled_spmv(const TiledPlan& plan, const float* d_x, float* d_y, hipSt
 // Phase 1 for the strips [strip_begin, strip_end) — products of the entries whose columns lie there — and,
 // with_long, the long rows (which read all of r_old).  A step needs every strip and the long rows exactly
 // once, in any number of calls, before its finish.  No-op when state->done.
+// `commit`: the previous step's pending residual commit, folded by one workgroup at the head of this launch's grid
+// (CommitRider{}: none).
 hipError_t tiled_pagerank_expand(const TiledPlan& plan, int strip_begin, int strip_end, bool with_long,
-                                 const float* d_r_old, const PrState* d_state, hipStream_t s);
+                                 const float* d_r_old, const PrState* d_state, const CommitRider& commit, hipStream_t s);
 // Phase 2: r_new[map.at(i)] = d * (A r_old)_i + d*s/n + (1-d)/n, block partial sums of (r_new - r_old)^2
 // and of r_new over dangling nodes -> block_partials [2 * plan.num_tiles]; no-op when state->done.
 hipError_t tiled_pagerank_finish(const TiledPlan& plan, const RowMap& map, int n_global,

@@ -51,6 +51,7 @@
 #include "tiled.h"
 #include "device_common.h"
 #include "pagerank_engine.h"
+#include "pr_commit_device.h"
 
 #include <hip/hip_runtime.h>
 
@@ -1241,22 +1242,34 @@ __device__ __forceinline__ void expand_slots(const float* xs, int begin, int end
 // 347 / 359 / 433 against 320 us on C5 — fewer, longer workgroups balance worse than their saved strip loads are worth.)
 template <int W, int kExpandBlock, bool FOLD>
 __global__ __launch_bounds__(kExpandBlock)
-void tiled_expand_kernel(const int* __restrict__ items, int first_item, int num_items, int long_blocks,
+void tiled_expand_kernel(const int* __restrict__ items, int first_item, int num_items, int commit_blocks, int long_blocks,
                          const float* __restrict__ a_val,
                          const unsigned short* __restrict__ a_lcol,
                          const float* __restrict__ col_weight,
                          const float* __restrict__ x, int num_cols,
                          float* __restrict__ prod, LongRows long_rows,
-                         const PrState* __restrict__ state) {
-    // PageRank steps enqueued past convergence are no-ops
+                         const PrState* __restrict__ state, CommitRider commit) {
+    // The previous step's residual commit, when it was deferred into this launch: workgroup 0 of a head of
+    // commit_blocks (0 or 8, so that the XCD mapping below holds) folds that step's block partials into the state —
+    // the arithmetic of pr_reduce_commit_kernel, on its first kBlock threads.  The partials were written by the
+    // previous phase-2 launch, so the kernel boundary has made them visible to every XCD.
+    if (static_cast<int>(blockIdx.x) < commit_blocks) {
+        if (blockIdx.x == 0 && threadIdx.x < kBlock) pr_fold_and_commit(commit.partials, commit.num_blocks, commit.tolerance, commit.state);
+        return;
+    }
+    // PageRank steps enqueued past convergence are no-ops.  `done` is read once per workgroup, and the commit
+    // workgroup above may set it before or after that read.  Either order gives the same result: this launch
+    // writes scratch only (products, long-row chunk sums), which nothing reads after `done` is set — this
+    // step's phase 2 starts after this launch has completed, sees `done` and returns, as does every later step.
     if (state && state->done) return;
-    if (static_cast<int>(blockIdx.x) < long_blocks) {     // the long-row workgroups go first (latency-bound)
+    const int head_blocks = commit_blocks + long_blocks;
+    if (static_cast<int>(blockIdx.x) < head_blocks) {     // the long-row workgroups go first (latency-bound)
         constexpr int kPerBlock = kExpandBlock / 64;
-        long_row_chunk(long_rows, blockIdx.x * kPerBlock + (threadIdx.x >> 6), x);
+        long_row_chunk(long_rows, (blockIdx.x - commit_blocks) * kPerBlock + (threadIdx.x >> 6), x);
         return;
     }
     __shared__ float xs[W];
-    const int window = xcd_contiguous(blockIdx.x - long_blocks, num_items);   // long_blocks is a multiple of 8
+    const int window = xcd_contiguous(blockIdx.x - head_blocks, num_items);   // head_blocks is a multiple of 8
     if (window < 0) return;
     const int item = first_item + window;
     const int strip = items[3 * item];
@@ -1722,29 +1735,32 @@ hipError_t scratch_for(const TiledPlan& plan, hipStream_t s, Scratch* out) {
 // phase 1 for the items [first_item, first_item + num_items) and, with_long, the long-row chunks
 template <int W, int BLOCK>
 hipError_t launch_expand_as(const TiledPlan& plan, const Scratch& sc, int first_item, int num_items, bool with_long,
-                            const float* d_x, const PrState* d_state, hipStream_t s) {
+                            const float* d_x, const PrState* d_state, const CommitRider& commit, hipStream_t s) {
     const int chunks = with_long ? plan.num_long_chunks : 0;
     const LongRows lr{plan.long_chunks, chunks, plan.csr_nnz, plan.csr_cols, plan.csr_vals, sc.long_sums};
     const int long_blocks = xcd_grid((chunks + BLOCK / 64 - 1) / (BLOCK / 64));
-    const int grid = long_blocks + xcd_grid(num_items);
+    const int commit_blocks = commit.partials ? kXcds : 0;
+    const int grid = commit_blocks + long_blocks + xcd_grid(num_items);
     if (grid == 0) return hipSuccess;
     if (plan.col_weight) {
         tiled_expand_kernel<W, BLOCK, true><<<grid, BLOCK, 0, s>>>(
-            plan.items, first_item, num_items, long_blocks, nullptr, plan.a_lcol, plan.col_weight, d_x, plan.num_cols, sc.prod, lr, d_state);
+            plan.items, first_item, num_items, commit_blocks, long_blocks, nullptr, plan.a_lcol, plan.col_weight, d_x, plan.num_cols, sc.prod, lr,
+            d_state, commit);
     } else {
         tiled_expand_kernel<W, BLOCK, false><<<grid, BLOCK, 0, s>>>(
-            plan.items, first_item, num_items, long_blocks, plan.a_val, plan.a_lcol, nullptr, d_x, plan.num_cols, sc.prod, lr, d_state);
+            plan.items, first_item, num_items, commit_blocks, long_blocks, plan.a_val, plan.a_lcol, nullptr, d_x, plan.num_cols, sc.prod, lr,
+            d_state, commit);
     }
     return hipGetLastError();
 }
 
 hipError_t launch_expand(const TiledPlan& plan, const Scratch& sc, int first_item, int num_items, bool with_long,
-                         const float* d_x, const PrState* d_state, hipStream_t s) {
+                         const float* d_x, const PrState* d_state, const CommitRider& commit, hipStream_t s) {
     switch (plan.strip_cols) {
-        case 4096:  return launch_expand_as<4096, 512>(plan, sc, first_item, num_items, with_long, d_x, d_state, s);
-        case 8192:  return launch_expand_as<8192, 512>(plan, sc, first_item, num_items, with_long, d_x, d_state, s);
-        case 16384: return launch_expand_as<16384, 512>(plan, sc, first_item, num_items, with_long, d_x, d_state, s);
-        default:    return launch_expand_as<32768, 1024>(plan, sc, first_item, num_items, with_long, d_x, d_state, s);   // 128 KiB of LDS: one workgroup per CU
+        case 4096:  return launch_expand_as<4096, 512>(plan, sc, first_item, num_items, with_long, d_x, d_state, commit, s);
+        case 8192:  return launch_expand_as<8192, 512>(plan, sc, first_item, num_items, with_long, d_x, d_state, commit, s);
+        case 16384: return launch_expand_as<16384, 512>(plan, sc, first_item, num_items, with_long, d_x, d_state, commit, s);
+        default:    return launch_expand_as<32768, 1024>(plan, sc, first_item, num_items, with_long, d_x, d_state, commit, s);   // 128 KiB of LDS: one workgroup per CU
     }
 }
 
@@ -2351,7 +2367,7 @@ hipError_t tiled_spmv(const TiledPlan& plan, const float* d_x, float* d_y, hipSt
     if (e != hipSuccess) return e;
     // two host threads may call on the same stream: the pair of launches must not interleave with another pair
     std::lock_guard<std::mutex> pair(plan.launch_lock);
-    e = launch_expand(plan, sc, 0, plan.num_items, true, d_x, nullptr, s);       // phase 1 + the long rows
+    e = launch_expand(plan, sc, 0, plan.num_items, true, d_x, nullptr, CommitRider{}, s);       // phase 1 + the long rows
     if (e != hipSuccess) return e;
     return launch_reduce(plan, sc, d_y, s);
 }
@@ -2359,14 +2375,14 @@ hipError_t tiled_spmv(const TiledPlan& plan, const float* d_x, float* d_y, hipSt
 // After convergence the kernels of both parts return at once: r_new and the product stream stay as the last
 // committed step left them.
 hipError_t tiled_pagerank_expand(const TiledPlan& plan, int strip_begin, int strip_end, bool with_long,
-                                 const float* d_r_old, const PrState* d_state, hipStream_t s) {
+                                 const float* d_r_old, const PrState* d_state, const CommitRider& commit, hipStream_t s) {
     Scratch sc;
     const hipError_t e = scratch_for(plan, s, &sc);
     if (e != hipSuccess) return e;
     strip_begin = std::max(0, std::min(strip_begin, plan.num_strips));
     strip_end = std::max(strip_begin, std::min(strip_end, plan.num_strips));
     const int first = plan.strip_first_item[strip_begin];
-    return launch_expand(plan, sc, first, plan.strip_first_item[strip_end] - first, with_long, d_r_old, d_state, s);
+    return launch_expand(plan, sc, first, plan.strip_first_item[strip_end] - first, with_long, d_r_old, d_state, commit, s);
 }
 
 hipError_t tiled_pagerank_finish(const TiledPlan& plan, const RowMap& map, int n_global,

@@ -421,10 +421,10 @@ class HipEngine:
                     "pr_expand")
 
     def step_and_commit(self, r_old: torch.Tensor, r_new: torch.Tensor, damping: float, tolerance: float) -> None:
-        """Single-rank iteration: the step, then reduce + commit in one launch."""
-        self._check(lib().spmv_c_pr_step(self._shard, c_void_p(r_old.data_ptr()), c_void_p(r_new.data_ptr()),
-                                         damping, self._stream()), "pr_step")
-        self._check(lib().spmv_c_pr_reduce_commit(self._shard, tolerance, self._stream()), "pr_reduce_commit")
+        """Single-rank iteration: the step and its reduce + commit; on the tiled engine the commit rides in the
+        next step's first launch (spmv_c_pr_step_commit), and status() or any other call flushes it."""
+        self._check(lib().spmv_c_pr_step_commit(self._shard, c_void_p(r_old.data_ptr()), c_void_p(r_new.data_ptr()),
+                                                damping, tolerance, self._stream()), "pr_step_commit")
 
     def commit(self, sums: torch.Tensor, tolerance: float) -> None:
         self._check(lib().spmv_c_pr_commit(self._shard, c_void_p(sums.data_ptr()), tolerance, self._stream()),

@@ -403,11 +403,22 @@ int spmv_c_pr_reduce(spmv_c_pr_shard* shard, double* d_sums /*[2]*/, void* hip_s
 int spmv_c_pr_commit(spmv_c_pr_shard* shard, const double* d_sums, float tolerance, void* hip_stream);
 /* single rank: reduce + commit in one launch (no sums buffer leaves the engine) */
 int spmv_c_pr_reduce_commit(spmv_c_pr_shard* shard, float tolerance, void* hip_stream);
+/* single rank: spmv_c_pr_step followed by spmv_c_pr_reduce_commit, with the same results bit for bit.  On the
+ * LDS-tiled engine the commit is DEFERRED: one workgroup at the head of the next step's first launch on the same
+ * stream does it, so a loop of these calls pays two launches per step, not three.  Any other call on the shard
+ * (status_get, expand, reduce, the commit forms, a push step, a step on another stream, destroy) first enqueues
+ * the pending commit as a launch of its own on the stream it is given; spmv_c_pr_reset drops it.  Enqueue-only.
+ * On a stream that is being captured into a hipGraph nothing is deferred (a commit pending when the capture ends
+ * would be missing from the replays); flush (status_get) before a capture begins. */
+int spmv_c_pr_step_commit(spmv_c_pr_shard* shard, const float* d_r_old, float* d_r_new, float damping,
+                          float tolerance, void* hip_stream);
 /* multi-rank commit without an all-reduce: rank p's two partial sums (as doubles) sit in the 16-byte
  * tail of its slice, d_gathered[p * stride + shard_len ...]; stride >= shard_len + 4, both even */
 int spmv_c_pr_commit_gathered(spmv_c_pr_shard* shard, const float* d_gathered, int world, int64_t stride,
                               int64_t shard_len, float tolerance, void* hip_stream);
-int spmv_c_pr_status_get(spmv_c_pr_shard* shard, spmv_c_pr_status* out, void* hip_stream); /* syncs */
+/* syncs — unless hip_stream is being captured into a hipGraph: then the (flush and the) copy are enqueued only,
+ * and every replay fills `out`, which must be pinned host memory that outlives the graph */
+int spmv_c_pr_status_get(spmv_c_pr_shard* shard, spmv_c_pr_status* out, void* hip_stream);
 /* dangling-node detection on the device: accumulate this shard's column sums
  * (atomic adds into d_col_sums[n_global]); after the sums of all shards are
  * combined, mask[c] = (sum == 0). */
