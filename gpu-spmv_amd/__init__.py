@@ -171,6 +171,13 @@ class SpTRSVResult(Structure):
                 ("lanes_per_row", c_int32), ("analysis_ms", c_float), ("elapsed_ms", c_float)]
 
 
+class ILU0Result(Structure):
+    """include/spmv/ilu0.h ILU0Result (28 bytes); zero_pivot is the lowest row with a zero or non-finite u_ii, or -1"""
+    _fields_ = [("error_code", c_int32), ("num_levels", c_int32), ("launches", c_int32),
+                ("lanes_per_row", c_int32), ("zero_pivot", c_int32), ("analysis_ms", c_float),
+                ("elapsed_ms", c_float)]
+
+
 class PageRankResult:
     """reference include/spmv/pagerank.h:18-25; `ranks` is a numpy copy (the C buffer is freed)."""
 
@@ -264,6 +271,11 @@ _SIGNATURES = {
     "spmv_c_cg_solve": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(CGConfig), POINTER(CGResult)]),
     "spmv_c_bicgstab_solve": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(BiCGStabConfig),
                                       POINTER(BiCGStabResult)]),
+    "spmv_c_bicgstab_solve_lu": (c_int, [POINTER(CSRMatrix), POINTER(CSRMatrix), c_void_p, c_void_p,
+                                         POINTER(BiCGStabConfig), POINTER(BiCGStabResult)]),
+    "spmv_c_ilu0_csr": (c_int, [POINTER(CSRMatrix), c_void_p, POINTER(ILU0Result)]),
+    "spmv_c_ilu0_csr_async": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p]),
+    "spmv_c_ilu0_cpu_csr": (c_int, [POINTER(CSRMatrix), c_void_p, POINTER(c_int32)]),
     "spmv_c_sptrsv_csr": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(SpTRSVConfig),
                                   POINTER(SpTRSVResult)]),
     "spmv_c_sptrsv_csr_async": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(SpTRSVConfig), c_void_p]),
@@ -825,6 +837,39 @@ def bicgstab_solve(A, d_b, d_x, config=None) -> BiCGStabResult:
     lib().spmv_c_bicgstab_solve(A, _dev(d_b), _dev(d_x), byref(config) if config is not None else None,
                                 byref(out))
     return out
+
+
+def bicgstab_solve_lu(A, LU, d_b, d_x, config=None) -> BiCGStabResult:
+    """BiCGSTAB right-preconditioned by M = L U, the unit lower and the upper triangle of the device matrix LU
+    (include/spmv/bicgstab.h bicgstab_solve_lu); LU is usually ilu0_csr's output wrapped by csr_wrap_device over A's
+    structure arrays.  config.preconditioner is not read."""
+    out = BiCGStabResult()
+    lib().spmv_c_bicgstab_solve_lu(A, LU, _dev(d_b), _dev(d_x), byref(config) if config is not None else None,
+                                   byref(out))
+    return out
+
+
+def ilu0_csr(A, d_lu_values) -> ILU0Result:
+    """ILU(0) of the square device matrix A into d_lu_values (include/spmv/ilu0.h ilu0_csr): nnz floats in A's
+    pattern, L left of the diagonal, U on and right of it; d_lu_values may be A's own device values (in place)."""
+    out = ILU0Result()
+    lib().spmv_c_ilu0_csr(A, _dev(d_lu_values), byref(out))
+    return out
+
+
+def ilu0_csr_async(A, d_lu_values, stream=None) -> int:
+    return lib().spmv_c_ilu0_csr_async(A, _dev(d_lu_values), c_void_p(stream))
+
+
+def ilu0_cpu_csr(A):
+    """The factorisation on A's host arrays (include/spmv/ilu0.h ilu0_cpu_csr, the definition of the arithmetic):
+    returns (lu_values, zero_pivot); raises ValueError with the library's error string when the call is rejected."""
+    lu = np.zeros(max(int(A.contents.nnz), 0) if A else 0, dtype=np.float32)
+    pivot = c_int32(-1)
+    status = lib().spmv_c_ilu0_cpu_csr(A, _np_ptr(lu), byref(pivot))
+    if status != 0:
+        raise ValueError(spmv_error_string(status))
+    return lu, pivot.value
 
 
 def sptrsv_csr(A, d_b, d_x, config=None) -> SpTRSVResult:

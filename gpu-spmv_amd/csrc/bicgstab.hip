@@ -14,11 +14,17 @@
 // A step's outcome is committed to the state only by the last kernel that does work in it, so no workgroup of a
 // kernel that still has vector work to do can see `done` early.  Dot products accumulate fp64 products of the fp32
 // entries; no float atomics anywhere.
+//
+// bicgstab_solve_lu is the same loop with M = L U given as a factor matrix: the step kernels run as with NONE
+// (dinv == nullptr, no p^ / s^ outputs) and p^ = U^-1 (L^-1 p), s^ = U^-1 (L^-1 s) are two launch_sptrsv sequences each
+// (sptrsv.hip) into the stored p^ / s^ buffers, s^ after bicg_s_kernel and p^ after bicg_direction_kernel.  The solve
+// kernels do not read `done`: after it they still write p^ / s^, which nothing reads any more.
 #include "internal.h"
 #include "device_common.h"
 #include "solver_common.h"
 #include "tiled.h"
 #include "spmv/bicgstab.h"
+#include "spmv/sptrsv.h"
 
 #include <hip/hip_runtime.h>
 
@@ -350,39 +356,61 @@ hipError_t spmv_dot(int lanes, const CSRMatrix* A, const float* w, float* y, con
     });
 }
 
-} // namespace
-} // namespace detail
+bool device_arrays(const CSRMatrix* M) {
+    return M->num_rows >= 0 && M->d_row_ptrs && (M->nnz <= 0 || (M->d_col_indices && M->d_values));
+}
 
-BiCGStabResult bicgstab_solve(const CSRMatrix* A, const float* d_b, float* d_x, const BiCGStabConfig* config) {
-    using namespace detail;
-    using namespace detail::solver;
+// bicgstab_solve (with_lu false: LU is not looked at, cfg.preconditioner picks NONE or JACOBI) and bicgstab_solve_lu
+// (with_lu true: M = L U from LU, cfg.preconditioner is not read).
+BiCGStabResult solve(const CSRMatrix* A, const CSRMatrix* LU, bool with_lu, const float* d_b, float* d_x,
+                     const BiCGStabConfig* config) {
     BiCGStabResult result;
     const auto fail = [&result](SpMVError e) {
         result.error_code = code(e);
         return result;
     };
-    if (!A || !d_b || !d_x) return fail(SpMVError::INVALID_ARGUMENT);
+    if (!A || !d_b || !d_x || (with_lu && !LU)) return fail(SpMVError::INVALID_ARGUMENT);
     if (A->num_rows != A->num_cols) return fail(SpMVError::INVALID_DIMENSION);
+    if (with_lu && (LU->num_rows != LU->num_cols || LU->num_rows != A->num_rows)) {
+        return fail(SpMVError::INVALID_DIMENSION);
+    }
     if (A->num_rows == 0) {
         result.converged = 1;
         return result;
     }
-    if (A->num_rows < 0 || !A->d_row_ptrs || (A->nnz > 0 && (!A->d_col_indices || !A->d_values))) {
-        return fail(SpMVError::INVALID_FORMAT);
-    }
+    if (!device_arrays(A) || (with_lu && !device_arrays(LU))) return fail(SpMVError::INVALID_FORMAT);
     const BiCGStabConfig defaults;
     const BiCGStabConfig& cfg = config ? *config : defaults;
     if (!(cfg.tolerance >= 0.0f) || cfg.max_iterations < 0 ||
-        (cfg.preconditioner != CGConfig::NONE && cfg.preconditioner != CGConfig::JACOBI) ||
+        (!with_lu && cfg.preconditioner != CGConfig::NONE && cfg.preconditioner != CGConfig::JACOBI) ||
         cfg.engine < -1 || cfg.engine > 1) {
         return fail(SpMVError::INVALID_ARGUMENT);
     }
     const int n = A->num_rows;
     if (ranges_overlap(d_b, d_x, n)) return fail(SpMVError::INVALID_ARGUMENT);
 
-    const TraceRange range("spmv:bicgstab_solve");
+    const TraceRange range(with_lu ? "spmv:bicgstab_solve_lu" : "spmv:bicgstab_solve");
     hipStream_t stream = current_stream();
-    const bool jacobi = cfg.preconditioner == CGConfig::JACOBI;
+    const bool jacobi = !with_lu && cfg.preconditioner == CGConfig::JACOBI;
+    const bool stored = jacobi || with_lu;         // p^ and s^ are buffers of their own
+
+    // both schedules of LU, ahead of the timed loop (a build synchronises the stream); they validate LU's structure
+    // before any kernel walks it
+    std::shared_ptr<const SptrsvSchedule> lower, upper;
+    int lower_lanes = 1, upper_lanes = 1;
+    if (with_lu) {
+        float analysis_ms = 0.0f;
+        int status = sptrsv_schedule_for(LU, SpTRSVConfig::LOWER, stream, &lower, &analysis_ms);
+        if (status == 0) status = sptrsv_schedule_for(LU, SpTRSVConfig::UPPER, stream, &upper, &analysis_ms);
+        if (status != 0) return fail(static_cast<SpMVError>(status));
+        lower_lanes = sptrsv_lanes_for(*lower);
+        upper_lanes = sptrsv_lanes_for(*upper);
+    }
+    // out = U^-1 (L^-1 in): LOWER UNIT, then UPPER NON_UNIT in place
+    const auto apply_lu = [&](const float* in, float* out) -> bool {
+        return launch_sptrsv(*lower, LU, in, out, SpTRSVConfig::LOWER, 1, false, lower_lanes, stream) == hipSuccess &&
+               launch_sptrsv(*upper, LU, out, out, SpTRSVConfig::UPPER, 0, false, upper_lanes, stream) == hipSuccess;
+    };
 
     // engine choice (cg_solve's: -1 takes a cached plan from the start, else builds one after 4 direct steps)
     PlanRef plan;
@@ -404,10 +432,10 @@ BiCGStabResult bicgstab_solve(const CSRMatrix* A, const float* d_b, float* d_x, 
     const size_t rr_count = 2 * static_cast<size_t>(vgrid);
     const size_t init_count = 2 * static_cast<size_t>(row_grid);
 
-    // r (s in place), r^, p, v, t; with JACOBI also p^, s^, dinv (with NONE p^ is p and s^ is s)
+    // r (s in place), r^, p, v, t; with JACOBI or an LU also p^ and s^, with JACOBI dinv (with NONE p^ is p and s^ is s)
     Workspace<BicgState> ws;
     const size_t len = static_cast<size_t>(n);
-    if (!ws.allocate((jacobi ? 8 : 5) * len, rv_count + ss_count + ts_count + rr_count + init_count)) {
+    if (!ws.allocate((jacobi ? 8 : stored ? 7 : 5) * len, rv_count + ss_count + ts_count + rr_count + init_count)) {
         return fail(SpMVError::CUDA_MALLOC);
     }
     float* r = ws.vec;
@@ -415,8 +443,8 @@ BiCGStabResult bicgstab_solve(const CSRMatrix* A, const float* d_b, float* d_x, 
     float* p = ws.vec + 2 * len;
     float* v = ws.vec + 3 * len;
     float* t = ws.vec + 4 * len;
-    float* phat = jacobi ? ws.vec + 5 * len : p;
-    float* shat = jacobi ? ws.vec + 6 * len : r;
+    float* phat = stored ? ws.vec + 5 * len : p;
+    float* shat = stored ? ws.vec + 6 * len : r;
     float* dinv = jacobi ? ws.vec + 7 * len : nullptr;
     double* rv_part = ws.part;
     double* ss_part = rv_part + rv_count;
@@ -425,8 +453,13 @@ BiCGStabResult bicgstab_solve(const CSRMatrix* A, const float* d_b, float* d_x, 
     double* init_part = rr_part + rr_count;
     BicgState* pinned = ws.pinned;
 
-    // setup: diagonal (JACOBI), r0 / r^ / p0 / p^0 and their dots, the state; one read-back
+    // setup: diagonal (JACOBI; of LU, only its check: the reciprocals land in t, which the loop overwrites before it
+    // reads it), r0 / r^ / p0 / p^0 and their dots, the state; one read-back
     bool ok = hipMemsetAsync(ws.state, 0, sizeof(BicgState), stream) == hipSuccess;
+    if (ok && with_lu) {
+        bicg_diag_kernel<<<vgrid, kBlock, 0, stream>>>(n, LU->d_row_ptrs, LU->d_col_indices, LU->d_values, t, ws.state);
+        ok = hipGetLastError() == hipSuccess;
+    }
     if (ok && jacobi) {
         bicg_diag_kernel<<<vgrid, kBlock, 0, stream>>>(n, A->d_row_ptrs, A->d_col_indices, A->d_values, dinv,
                                                        ws.state);
@@ -435,6 +468,7 @@ BiCGStabResult bicgstab_solve(const CSRMatrix* A, const float* d_b, float* d_x, 
     float* phat_out = jacobi ? phat : nullptr;     // the kernels write p^ / s^ only with JACOBI
     float* shat_out = jacobi ? shat : nullptr;
     ok = ok && init(lanes, A, d_b, d_x, dinv, r, rhat, p, phat_out, init_part, row_grid, stream) == hipSuccess;
+    if (with_lu) ok = ok && apply_lu(p, phat);
     if (ok) {
         bicg_start_kernel<<<1, kBlock, 0, stream>>>(init_part, row_grid, cfg.tolerance, ws.state);
         ok = hipGetLastError() == hipSuccess;
@@ -497,13 +531,14 @@ BiCGStabResult bicgstab_solve(const CSRMatrix* A, const float* d_b, float* d_x, 
                                                             ss_part);
                 ok = hipGetLastError() == hipSuccess;
             }
+            if (with_lu) ok = ok && apply_lu(r, shat);
             ok = ok && spmv_and_dot(shat, t, r, 1, ts_part, ts_parts);
             if (ok) {
                 bicg_update_kernel<<<vgrid, kBlock, 0, stream>>>(n, phat, shat, t, rhat, d_x, r, ws.state, ss_part,
                                                                  vgrid, ts_part, ts_parts, rr_part);
                 bicg_direction_kernel<<<vgrid, kBlock, 0, stream>>>(n, iter, v, r, dinv, p, phat_out, ws.state, rr_part,
                                                                     vgrid);
-                ok = hipGetLastError() == hipSuccess
+                ok = hipGetLastError() == hipSuccess && (!with_lu || apply_lu(p, phat))
                   && hipMemcpyAsync(&pinned[iter & 1], ws.state, sizeof(BicgState), hipMemcpyDeviceToHost,
                                     stream) == hipSuccess
                   && hipEventRecord(ws.seen[iter & 1], stream) == hipSuccess;
@@ -529,6 +564,18 @@ BiCGStabResult bicgstab_solve(const CSRMatrix* A, const float* d_b, float* d_x, 
     result.converged = final_state.converged;
     result.breakdown = final_state.breakdown;
     return result;
+}
+
+} // namespace
+} // namespace detail
+
+BiCGStabResult bicgstab_solve(const CSRMatrix* A, const float* d_b, float* d_x, const BiCGStabConfig* config) {
+    return detail::solve(A, nullptr, false, d_b, d_x, config);
+}
+
+BiCGStabResult bicgstab_solve_lu(const CSRMatrix* A, const CSRMatrix* LU, const float* d_b, float* d_x,
+                                 const BiCGStabConfig* config) {
+    return detail::solve(A, LU, true, d_b, d_x, config);
 }
 
 } // namespace spmv

@@ -9,6 +9,7 @@
 #include "spmv/cg.h"
 #include "spmv/pagerank.h"
 #include "spmv/sptrsv.h"
+#include "spmv/ilu0.h"
 #include "spmv_c.h"
 
 #include <cstddef>
@@ -64,6 +65,13 @@ static_assert(offsetof(spmv_c_sptrsv_config, diag) == offsetof(SpTRSVConfig, dia
               offsetof(spmv_c_sptrsv_config, ordered) == offsetof(SpTRSVConfig, ordered) &&
               offsetof(spmv_c_sptrsv_config, reserved) == offsetof(SpTRSVConfig, reserved), "SpTRSVConfig layout");
 static_assert(sizeof(spmv_c_sptrsv_result) == sizeof(SpTRSVResult) && sizeof(SpTRSVResult) == 24, "SpTRSVResult layout");
+static_assert(sizeof(spmv_c_ilu0_result) == sizeof(ILU0Result) && sizeof(ILU0Result) == 28, "ILU0Result layout");
+static_assert(offsetof(spmv_c_ilu0_result, num_levels) == offsetof(ILU0Result, num_levels) &&
+              offsetof(spmv_c_ilu0_result, launches) == offsetof(ILU0Result, launches) &&
+              offsetof(spmv_c_ilu0_result, lanes_per_row) == offsetof(ILU0Result, lanes_per_row) &&
+              offsetof(spmv_c_ilu0_result, zero_pivot) == offsetof(ILU0Result, zero_pivot) &&
+              offsetof(spmv_c_ilu0_result, analysis_ms) == offsetof(ILU0Result, analysis_ms) &&
+              offsetof(spmv_c_ilu0_result, elapsed_ms) == offsetof(ILU0Result, elapsed_ms), "ILU0Result layout");
 static_assert(offsetof(spmv_c_sptrsv_result, num_levels) == offsetof(SpTRSVResult, num_levels) &&
               offsetof(spmv_c_sptrsv_result, launches) == offsetof(SpTRSVResult, launches) &&
               offsetof(spmv_c_sptrsv_result, lanes_per_row) == offsetof(SpTRSVResult, lanes_per_row) &&
@@ -465,6 +473,28 @@ int spmv_c_bicgstab_solve(const spmv_c_csr* A, const float* d_b, float* d_x, con
     const BiCGStabResult r = bicgstab_solve(cxx(A), d_b, d_x, reinterpret_cast<const BiCGStabConfig*>(config));
     if (out) std::memcpy(out, &r, sizeof(r));
     return r.error_code;
+}
+
+int spmv_c_bicgstab_solve_lu(const spmv_c_csr* A, const spmv_c_csr* LU, const float* d_b, float* d_x,
+                             const spmv_c_bicgstab_config* config, spmv_c_bicgstab_result* out) {
+    const BiCGStabResult r = bicgstab_solve_lu(cxx(A), cxx(LU), d_b, d_x,
+                                               reinterpret_cast<const BiCGStabConfig*>(config));
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
+}
+
+int spmv_c_ilu0_csr(const spmv_c_csr* A, float* d_lu_values, spmv_c_ilu0_result* out) {
+    const ILU0Result r = ilu0_csr(cxx(A), d_lu_values);
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
+}
+
+int spmv_c_ilu0_csr_async(const spmv_c_csr* A, float* d_lu_values, void* hip_stream) {
+    return ilu0_csr_async(cxx(A), d_lu_values, as_stream(hip_stream));
+}
+
+int spmv_c_ilu0_cpu_csr(const spmv_c_csr* A, float* lu_values, int32_t* zero_pivot) {
+    return ilu0_cpu_csr(cxx(A), lu_values, zero_pivot);
 }
 
 int spmv_c_sptrsv_csr(const spmv_c_csr* A, const float* d_b, float* d_x, const spmv_c_sptrsv_config* config,

@@ -75,6 +75,7 @@ struct SptrsvSchedule {
     std::vector<Group> groups;       // level_end - level_begin > 1 only for narrow levels: one workgroup walks them
     long long triangle_nnz = 0;      // stored entries inside the triangle, diagonal included
     int  first_missing_diagonal = -1;
+    int  first_unsorted_row = -1;    // lowest row whose columns are not strictly ascending, or -1 (ilu0_csr needs none)
     // what it was built from (the transpose cache's rule)
     const void* row_ptrs = nullptr;
     const void* cols = nullptr;
@@ -180,6 +181,7 @@ void    ell_aux_drop(const void* key);
 //   pr_plan_after=N            direct steps pagerank() takes before it builds a plan (default 4)
 //   pr_copy=pageable           pagerank() copies its result into a pageable array (no pinned pool)
 //   sptrsv_lanes=N             lanes per row of sptrsv_csr with ordered = 0 (1, 2, 4, ... 64; anything else is ignored)
+//   ilu0_lanes=N               lanes per row of ilu0_csr (1, 2, 4, ... 64; anything else is ignored)
 // Everything else the library reads from the environment is listed in INTEGRATION.md.
 bool debug_option(const char* key, long long* value = nullptr, char* text = nullptr, size_t text_size = 0);
 // the same "key=value,key" syntax for another variable's value (SPMV_MULTI_GPU); `list` may be null
@@ -224,6 +226,18 @@ hipError_t launch_sptrsv(const SptrsvSchedule& schedule, const CSRMatrix* A, con
                          int unit_diagonal, bool ordered, int lanes_per_row, hipStream_t s);
 // b and x overlap without being the same array (solver_common.h ranges_overlap; the solve in place is allowed)
 bool sptrsv_partial_overlap(const float* d_b, const float* d_x, long long n);
+// the schedule cache of sptrsv_host.cpp for the callers that solve or factor with it (ilu0_host.cpp, bicgstab.hip):
+// checks 2-4 of sptrsv.h (not square, no rows, missing device arrays); A's `uplo` schedule, built and cached when it
+// is not there (*analysis_ms = the host time of a build, 0 for a cache hit); the lanes per row of an ordered = 0 solve
+int sptrsv_check_matrix(const CSRMatrix* A, bool* nothing_to_do);
+int sptrsv_schedule_for(const CSRMatrix* A, int uplo, hipStream_t stream, std::shared_ptr<const SptrsvSchedule>* out,
+                        float* analysis_ms);
+int sptrsv_lanes_for(const SptrsvSchedule& schedule);
+// ILU(0) factorisation (ilu0.hip): the launches of one factorisation over A's LOWER schedule, in stream order, from
+// d_a (A's values) into d_lu (may be the same array); then, when d_zero_pivot is not null, the scan of the finished
+// diagonal that folds the lowest row with a zero or non-finite pivot into it (an unsigned min; preset to all ones)
+hipError_t launch_ilu0(const SptrsvSchedule& schedule, const CSRMatrix* A, const float* d_a, float* d_lu,
+                       int lanes_per_row, unsigned* d_zero_pivot, hipStream_t s);
 hipError_t launch_ell_from_csr(const CSRMatrix* csr, int width, int* d_ell_cols, float* d_ell_vals,
                                hipStream_t s);
 hipError_t device_count_ell_nnz(const ELLMatrix* A, long long* out, hipStream_t s);

@@ -194,6 +194,9 @@ int schedule_for(const CSRMatrix* A, int uplo, hipStream_t stream, ScheduleRef* 
     for (int i = 0; i < n; ++i) {
         for (int j = row_ptrs[i]; j < row_ptrs[i + 1]; ++j) {
             built->triangle_nnz += upper ? cols[j] >= i : cols[j] <= i;
+            if (j > row_ptrs[i] && cols[j] <= cols[j - 1] && built->first_unsorted_row < 0) {
+                built->first_unsorted_row = i;
+            }
         }
     }
     const size_t ptr_bytes = (static_cast<size_t>(num_levels) + 1) * sizeof(int);
@@ -271,6 +274,16 @@ int prepare(const CSRMatrix* A, const float* d_b, const float* d_x, const SpTRSV
 }
 
 } // namespace
+
+int sptrsv_check_matrix(const CSRMatrix* A, bool* nothing_to_do) { return check_matrix(A, nothing_to_do); }
+
+int sptrsv_schedule_for(const CSRMatrix* A, int uplo, hipStream_t stream, std::shared_ptr<const SptrsvSchedule>* out,
+                        float* analysis_ms) {
+    return schedule_for(A, uplo, stream, out, analysis_ms);
+}
+
+int sptrsv_lanes_for(const SptrsvSchedule& schedule) { return lanes_for(schedule, false); }
+
 } // namespace detail
 
 SpTRSVResult sptrsv_csr(const CSRMatrix* A, const float* d_b, float* d_x, const SpTRSVConfig* config) {

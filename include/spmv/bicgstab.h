@@ -80,6 +80,25 @@ struct BiCGStabResult {
 BiCGStabResult bicgstab_solve(const CSRMatrix* A, const float* d_b, float* d_x,
                               const BiCGStabConfig* config = nullptr);
 
+// The same iteration right-preconditioned by a given factorisation M = L U: L the unit lower triangle of LU (its
+// stored diagonal is U's), U the upper triangle of LU with the stored diagonal.  LU is any square device CSR matrix
+// with num_rows == A->num_rows; the usual one wraps the output of ilu0_csr (spmv/ilu0.h) over A's own structure
+// arrays, but its pattern need not be A's.  p^ = U^-1 (L^-1 p) and s^ = U^-1 (L^-1 s) are stored; each is two sparse
+// triangular solves of sptrsv_csr's kind (spmv/sptrsv.h: LOWER UNIT, then UPPER NON_UNIT in place, ordered = 0 with
+// the schedule's lane count), so a step costs four solves on top of bicgstab_solve's kernels with NONE.  Both level
+// schedules of LU are built (and cached with LU) during setup, before the timed loop.
+//
+// config->preconditioner is not read; tolerance, max_iterations and engine mean what they mean above, and the engine
+// choice applies to A only.  Breakdown codes, the half step, ||b|| == 0 and the good-initial-guess return are
+// bicgstab_solve's.  Checks, in bicgstab_solve's order with these additions; nothing is written to d_x when one fails:
+//   null LU -> INVALID_ARGUMENT (with the other nulls); LU not square or num_rows != A->num_rows -> INVALID_DIMENSION
+//   (after A's own); LU without device arrays -> INVALID_FORMAT (with A's); malformed row_ptrs / col_indices of LU ->
+//   INVALID_FORMAT (from the analysis); a row of LU whose diagonal is missing, zero or not finite -> INVALID_ARGUMENT
+//   (checked on the device, read back once with the setup state; the diagonal of a row is the fp32 sum of its stored
+//   (i,i) entries, the rule of sptrsv_csr).
+BiCGStabResult bicgstab_solve_lu(const CSRMatrix* A, const CSRMatrix* LU, const float* d_b, float* d_x,
+                                 const BiCGStabConfig* config = nullptr);
+
 } // namespace spmv
 
 #endif

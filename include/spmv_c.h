@@ -296,6 +296,13 @@ typedef struct spmv_c_bicgstab_result {
 int spmv_c_bicgstab_solve(const spmv_c_csr* A, const float* d_b, float* d_x, const spmv_c_bicgstab_config* config,
                           spmv_c_bicgstab_result* out);
 
+/* the same iteration right-preconditioned by M = L U, L the unit lower and U the upper triangle (with the stored
+ * diagonal) of the square device matrix LU (num_rows as A's; usually spmv_c_ilu0_csr's output wrapped over A's
+ * structure arrays).  config->preconditioner is not read.  Checks and numerics as bicgstab_solve_lu in
+ * include/spmv/bicgstab.h.  The return value equals out->error_code (out may be NULL). */
+int spmv_c_bicgstab_solve_lu(const spmv_c_csr* A, const spmv_c_csr* LU, const float* d_b, float* d_x,
+                             const spmv_c_bicgstab_config* config, spmv_c_bicgstab_result* out);
+
 /* ---- sparse triangular solve with level scheduling (extension; include/spmv/sptrsv.h) ---- */
 /* uplo: 0 LOWER, 1 UPPER; diag: 0 NON_UNIT, 1 UNIT; ordered: 1 = one lane per row in the CPU's summation order
  * (bit-identical to spmv_c_sptrsv_cpu_csr), 0 = 1-64 lanes per row; reserved: 0 (16 bytes) */
@@ -334,6 +341,28 @@ int spmv_c_sptrsv_cpu_csr(const spmv_c_csr* A, const float* b, float* x, const s
  * be NULL) = lowest row without a stored diagonal entry, or -1 */
 int spmv_c_sptrsv_levels(int num_rows, const int32_t* row_ptrs, const int32_t* col_indices, int uplo,
                          int32_t* level_ptr, int32_t* order, int32_t* num_levels, int32_t* first_missing_diagonal);
+
+/* ---- ILU(0) factorisation over the LOWER level schedule (extension; include/spmv/ilu0.h) ---- */
+/* 28 bytes */
+typedef struct spmv_c_ilu0_result {
+    int32_t error_code;
+    int32_t num_levels;
+    int32_t launches;
+    int32_t lanes_per_row;
+    int32_t zero_pivot;    /* lowest row whose u_ii is zero or not finite, or -1 */
+    float   analysis_ms;   /* 0 when the cached schedule was used */
+    float   elapsed_ms;    /* the factorisation launches only */
+} spmv_c_ilu0_result;
+
+/* Factors the square device matrix A (columns strictly ascending in every row, every diagonal stored) into
+ * d_lu_values: nnz floats in A's pattern, L left of the diagonal (unit diagonal not stored), U on and right of it;
+ * d_lu_values may be A's own device value array (in place).  Bit-identical to spmv_c_ilu0_cpu_csr.  Argument checks
+ * and arithmetic as ilu0_csr in include/spmv/ilu0.h.  The return value equals out->error_code (out may be NULL). */
+int spmv_c_ilu0_csr(const spmv_c_csr* A, float* d_lu_values, spmv_c_ilu0_result* out);
+/* the same factorisation enqueued on a caller stream without timing, pivot scan or synchronisation */
+int spmv_c_ilu0_csr_async(const spmv_c_csr* A, float* d_lu_values, void* hip_stream);
+/* the factorisation on A's host arrays (lu_values: nnz floats, may be A's host values); *zero_pivot may be NULL */
+int spmv_c_ilu0_cpu_csr(const spmv_c_csr* A, float* lu_values, int32_t* zero_pivot);
 
 /* ---- bandwidth model: reference include/spmv/bandwidth.h:21-27 ---- */
 int spmv_c_compute_bandwidth_csr(const spmv_c_csr* A, float elapsed_ms, spmv_c_bandwidth* out);
