@@ -1,5 +1,5 @@
-// device_common.h — device-side building blocks shared by kernels.hip and
-// pagerank.hip (gfx950, wave64).
+// device_common.h — device-side building blocks shared by kernels.hip,
+// pagerank.hip and the tiled engine (gfx950, wave64).
 #ifndef SPMV_AMD_DEVICE_COMMON_H
 #define SPMV_AMD_DEVICE_COMMON_H
 
@@ -35,6 +35,19 @@ __device__ __forceinline__ float group_sum(float v) {
     if constexpr (LANES >= 16) v += dpp<0x140>(v);   // row_mirror
     if constexpr (LANES >= 32) v += __shfl_xor(v, 16, 64);
     if constexpr (LANES >= 64) v += __shfl_xor(v, 32, 64);
+    return v;
+}
+
+// inclusive prefix sum over the 64 lanes of a wavefront: Hillis-Steele inside each 16-lane DPP row
+// (row_shr 1, 2, 4, 8; lanes shifted in from outside the row contribute 0), then the classic wave64 tail:
+// row_bcast:15 adds lane 15 of the previous row into rows 1 and 3, row_bcast:31 adds lane 31 into rows 2, 3
+__device__ __forceinline__ int wave_inclusive_scan(int v) {
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, true);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, true);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, true);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, true);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);
     return v;
 }
 

@@ -7,6 +7,7 @@
 #include "spmv/ell_matrix.h"
 #include "spmv/spmv.h"
 
+#include <algorithm>
 #include <atomic>
 #include <cstddef>
 #include <cstdint>
@@ -246,6 +247,21 @@ hipError_t device_row_stats(const int* d_row_ptrs, int num_rows, int* max_out, i
 
 // lanes-per-row choice for VECTOR_CSR from the mean row length (wave64 tuning)
 int pick_lanes_per_row(float avg_nnz_per_row);
+
+// Device memory with an owner: freed when the owner goes, on every path.  Move-only; pass .get() to a kernel.
+struct DevFree {
+    void operator()(void* p) const { (void)hipFree(p); }
+};
+template <typename T>
+using DevBuf = std::unique_ptr<T, DevFree>;
+// max(count, 1) elements of T; whatever *out held before is freed
+template <typename T>
+hipError_t dev_alloc(DevBuf<T>* out, long long count) {
+    T* p = nullptr;
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), static_cast<size_t>(std::max<long long>(count, 1)) * sizeof(T));
+    out->reset(e == hipSuccess ? p : nullptr);
+    return e;
+}
 
 // timing helper: a cached event pair per thread
 struct EventPair {

@@ -706,7 +706,7 @@ PageRankResult pagerank(const CSRMatrix* adj, const PageRankConfig* config) {
         ok = hipMemsetAsync(ws->mask, 0, len, stream) == hipSuccess
           && hipMemsetAsync(ws->dangling_count, 0, sizeof(unsigned long long), stream) == hipSuccess;
         if (ok && plan && plan->col_weight) {
-            ok = detail::pr_mask_from_column_sums(plan->col_weight, std::min(n, adj->num_cols), ws->mask,
+            ok = detail::pr_mask_from_column_sums(plan->col_weight.get(), std::min(n, adj->num_cols), ws->mask,
                                                   ws->dangling_count, stream) == hipSuccess
               && hipMemcpyAsync(&num_dangling, ws->dangling_count, sizeof(num_dangling),
                                 hipMemcpyDeviceToHost, stream) == hipSuccess

@@ -1,6 +1,7 @@
 // tiled.h — the LDS-tiled SpMV engine ("x staged into LDS tiles"): a two-phase,
 // propagation-blocking execution of y = A x for matrices whose x does not fit on chip.
-// See tiled.hip for the algorithm; this is the host-side plan object.
+// See tiled.hip for the algorithm and the two hot kernels, tiled_cells.hip and tiled_build.hip for the
+// plan builder, tiled_plan.cpp for the shape rules; this is the host-side plan object.
 #ifndef SPMV_AMD_TILED_H
 #define SPMV_AMD_TILED_H
 
@@ -17,9 +18,10 @@ struct PrState;
 struct CommitRider;
 struct PushTargets;
 struct RowMap;
+struct PassDesc;      // tiled_layout.h
 
 // Per-matrix bucketed copy of the entries (built once on the device, cached in the
-// side table, dropped by csr_free_gpu).
+// side table, dropped by csr_free_gpu).  The plan owns its device arrays: deleting it frees them.
 struct TiledPlan {
     int num_rows = 0, num_cols = 0;
     long long nnz = 0;              // SLOTS held in cells: the short rows' entries + row-skip markers + padding
@@ -30,31 +32,31 @@ struct TiledPlan {
 
     // slots sorted by cell (strip-major, tile inside a strip); inside a cell by (row, column).
     // Every cell's length is a multiple of 4 slots.
-    float*    a_val = nullptr;      // [nnz]; null when the values are folded into col_weight
-    float*    col_weight = nullptr; // [num_cols] the one value every entry of a column carries, or null
-    uint16_t* a_lcol = nullptr;     // [nnz] column - strip * W
-    uint8_t*  a_drow = nullptr;     // [nnz] row - (row of the cell's previous slot), 0..254; 255 = advance 255 rows, no entry
-    float*    prod = nullptr;       // [nnz] phase-1 output / phase-2 input, same order
-    int*      cells_t = nullptr;    // [2 * num_tiles * num_strips]: (begin, length) pairs, tile-major
-    // phase 2's work, laid out at build time (tiled.hip, pass_layout_kernel): the slots of wavefront w of tile t's workgroup
+    DevBuf<float>    a_val;      // [nnz]; null when the values are folded into col_weight
+    DevBuf<float>    col_weight; // [num_cols] the one value every entry of a column carries, or null
+    DevBuf<uint16_t> a_lcol;     // [nnz] column - strip * W
+    DevBuf<uint8_t>  a_drow;     // [nnz] row - (row of the cell's previous slot), 0..254; 255 = advance 255 rows, no entry
+    DevBuf<float>    prod;       // [nnz] phase-1 output / phase-2 input, same order
+    DevBuf<int>      cells_t;    // [2 * num_tiles * num_strips]: (begin, length) pairs, tile-major
+    // phase 2's work, laid out at build time (tiled_cells.hip, pass_layout_kernel): the slots of wavefront w of tile t's workgroup
     // are the passes [pass_first[16 t + w], pass_first[16 t + w + 1]), one 32-byte descriptor each
-    int*      pass_first = nullptr; // [16 * num_tiles + 1]
-    void*     pass_desc = nullptr;  // [num_passes] PassDesc
+    DevBuf<int>      pass_first; // [16 * num_tiles + 1]
+    DevBuf<PassDesc> pass_desc;  // [num_passes]
     long long num_passes = 0;
 
     // phase-1 work items: (strip, begin, end), at most kItemEntries slots each
-    int* items = nullptr;           // [3 * num_items]
+    DevBuf<int> items;           // [3 * num_items]
     int  num_items = 0;
-    int* strip_first_item = nullptr; // HOST [num_strips + 1]: the items are sorted by strip
+    std::vector<int> strip_first_item; // HOST [num_strips + 1]: the items are sorted by strip
     // rows longer than long_row: summed by one wavefront per 512-entry chunk from the CSR arrays
-    int*   long_rows = nullptr;     // [num_long] ascending
+    DevBuf<int>   long_rows;     // [num_long] ascending
     int    num_long = 0;
     int    long_row = 1024;         // rows with more entries than this are "long"
-    int*   long_chunks = nullptr;   // [3 * num_long_chunks] (row, begin, end) over the CSR arrays
+    DevBuf<int>   long_chunks;   // [3 * num_long_chunks] (row, begin, end) over the CSR arrays
     int    num_long_chunks = 0;
-    int*   long_first = nullptr;    // [num_long + 1] first chunk of every long row
-    float* long_sums = nullptr;     // [num_long_chunks] per-chunk partial sums of the current SpMV
-    int*   tile_long = nullptr;     // [num_tiles + 1] first long row of every tile (index into long_rows)
+    DevBuf<int>   long_first;    // [num_long + 1] first chunk of every long row
+    DevBuf<float> long_sums;     // [num_long_chunks] per-chunk partial sums of the current SpMV
+    DevBuf<int>   tile_long;     // [num_tiles + 1] first long row of every tile (index into long_rows)
     const int*   csr_row_ptrs = nullptr;   // borrowed from the matrix
     const int*   csr_cols = nullptr;
     const float* csr_vals = nullptr;
@@ -66,8 +68,8 @@ struct TiledPlan {
     // reference's kernels are stateless and its callers may rely on that.
     struct StreamScratch {
         hipStream_t stream;
-        float* prod;
-        float* long_sums;
+        DevBuf<float> prod;
+        DevBuf<float> long_sums;
     };
     mutable std::mutex scratch_lock;
     mutable std::mutex launch_lock;     // held across the two launches of one SpMV
@@ -83,6 +85,8 @@ struct TiledPlan {
 // the (strip columns, tile rows) the engine would pick for a matrix of this shape, and whether it
 // would take the matrix at all (pure host logic; exposed for tests and reports)
 bool tiled_shape_for(long long rows, long long cols, long long nnz, int* strip_cols, int* tile_rows);
+// the shape alone (what the builder asks; rows, cols, nnz > 0)
+void choose_shape(long long num_rows, long long num_cols, long long nnz, int* strip_cols, int* tile_rows);
 
 // true when the matrix is worth (and able) to run through the tiled engine
 bool tiled_eligible(const CSRMatrix* A);
@@ -91,7 +95,7 @@ bool tiled_eligible(const ELLMatrix* A);
 // builds the plan for A's device arrays (synchronises the stream a few times)
 hipError_t tiled_build(const CSRMatrix* A, TiledPlan** out, hipStream_t s);
 hipError_t tiled_build(const ELLMatrix* A, TiledPlan** out, hipStream_t s);   // from the ELL slabs (no long-row path)
-void tiled_free(TiledPlan* plan);
+void tiled_free(TiledPlan* plan);      // = delete: the plan's members own what it holds
 
 // position-weighted checksums of a_val / a_lcol / a_drow / cells_t (test aid: equal plans, equal numbers)
 hipError_t tiled_checksum(const TiledPlan& plan, unsigned long long out[4], hipStream_t s);

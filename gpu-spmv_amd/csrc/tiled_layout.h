@@ -1,0 +1,93 @@
+// tiled_layout.h — what the two sides of the LDS-tiled engine must agree on: the plan builder (tiled_cells.hip,
+// tiled_build.hip, the shape rules of tiled_plan.cpp) writes a layout that the hot path (tiled.hip) walks.
+#ifndef SPMV_AMD_TILED_LAYOUT_H
+#define SPMV_AMD_TILED_LAYOUT_H
+
+#include <type_traits>
+
+namespace spmv {
+namespace detail {
+
+// W (x columns per LDS strip) and R (y rows per LDS tile) are chosen per matrix
+// (choose_shape, tiled_plan.cpp):
+//   W in {4096, 8192, 16384, 32768} = 16 .. 128 KiB of static LDS in phase 1 (template instantiations)
+//   R = any multiple of 64 in [64, kMaxTileRows]: dynamic LDS in phase 2
+// Calls f(std::integral_constant<int, W>{}) for a plan's W.
+template <class F>
+auto with_strip_width(int strip_cols, F&& f) {
+    switch (strip_cols) {
+        case 4096:  return f(std::integral_constant<int, 4096>{});
+        case 8192:  return f(std::integral_constant<int, 8192>{});
+        case 16384: return f(std::integral_constant<int, 16384>{});
+        default:    return f(std::integral_constant<int, 32768>{});
+    }
+}
+
+constexpr int kSkip = 255;                  // row-delta byte: advance 255 rows, no entry
+constexpr int kLongChunk = 512;       // entries per wavefront of the long-row path
+constexpr long long kMaxCells = 1LL << 26;
+constexpr long long kResidentTiles = 512;    // phase-2 workgroups resident at once: 256 CUs x 2 (a tile of doubles is <= 78 KiB)
+constexpr int kMaxTileRows = 9984;           // 2 tiles of this many doubles (+ the reduction scratch) fit one CU's 160 KiB
+constexpr int kMaxBuildStrips = 3072;
+
+// ---- phase 2 as a list of PASSES laid out when the plan is built (round 4) ----
+// A tile's slots are one run per strip (cell table); a wavefront of the tile's workgroup owns a contiguous share of the
+// strips and walks its runs as ONE stream of slots, 256 per PASS whatever the run boundaries: a pass is up to kPassSegs
+// SEGMENTS (the end of one run, whole short runs, the start of the next), 4 slots per lane.  Round 3 derived the segments
+// inside the kernel, from the (begin, length) records of the runs — ~100 scalar instructions and ~18 branches per pass,
+// and with 8 wavefronts per SIMD sharing one scalar issue slot every 4 cycles that was the kernel's bound: a phase 2 that
+// only LOADS (no row rebuild, no LDS adds) took 192 us of the full kernel's 200, whatever the access pattern, the loads in
+// flight or the source array (profiles/r04_phase2_bound.txt).  Everything the scalar code computed is a function of the
+// plan alone, so it is computed ONCE, by pass_layout_kernel (tiled_cells.hip), into one 32-byte descriptor per pass:
+//     base[k]  slot index lane 0 WOULD read if it belonged to segment k (a lane reads base + 4 * lane)
+//     adj[k]   row of the slot in front of segment k's first slot (0 at a run's start) minus the sum of the delta bytes
+//              of all lanes in front of the segment: row of a slot = adj[segment] + (wave-wide exclusive prefix of the lanes'
+//              delta sums) + the in-lane prefix — no carry from pass to pass, nothing read back from the scan
+//     geom     first lane of segments 1 and 2, lanes in use
+// The hot loop is then: 8 v_readlane per pass, two loads, one wave scan, four ds_add_f64 — and passes are independent of
+// each other, so the next ones' loads are always in flight.  Same slots, same rows, same fp64 adds as the round-3 form:
+// bit-identical results (tests/tiled_small_shapes_worker.py: ~150 awkward shapes and the hand-picked run-length patterns —
+// every boundary case of a pass — against the oracle).
+constexpr int kPassSegs = 3;            // segments per pass: 2 / 3 / 4 measured 492 / 482 / 483 us on C5 in round 3
+constexpr int kPassSlots = 256;         // slots per pass: four per lane
+constexpr int kPassDepth = 3;           // passes in flight per wavefront (2 / 3 / 4: 158.7 / 157.0 / 156.9 us on C5)
+constexpr int kReduceThreads = 1024;
+constexpr int kReduceWaves = kReduceThreads / 64;
+
+struct PassDesc {                       // 32 bytes = two 16-byte loads
+    int base[kPassSegs];
+    int adj[kPassSegs];
+    unsigned int geom;                  // start[1] | start[2] << 8 | lanes in use << 16
+    unsigned int reserved;
+};
+static_assert(sizeof(PassDesc) == 32, "a lane loads its pass descriptor as two 16-byte words");
+
+// ---- device side (the host-only tiled_plan.cpp reads the constants above) ----
+#ifdef __HIP__
+// Workgroups are dealt round-robin over the 8 XCDs (blocks b and b + 8 share one, each XCD has its
+// own L2).  Both phases hand every XCD a CONTIGUOUS range of the work list, walked in order:
+// neighbours in the list then run on one XCD at about the same time and share what they both
+// touch through its L2 — the x strip of consecutive phase-1 items, the 128-byte lines that
+// adjacent runs of neighbouring tiles straddle in phase 2.  Returns -1 for the padding blocks of a
+// grid rounded up to a multiple of 8.  (Speed only: correctness never depends on placement.
+// Measured against the plain order on one box: C2 59.1 -> 55.0 us, C5 535.5 -> 530.1 us, 1/8 shard 84.5 -> 85.2 us.)
+constexpr int kXcds = 8;
+__device__ __forceinline__ int xcd_contiguous(int block, int count) {
+    const int per_xcd = (count + kXcds - 1) / kXcds;
+    const int which = (block % kXcds) * per_xcd + block / kXcds;
+    return block / kXcds < per_xcd && which < count ? which : -1;
+}
+__host__ __device__ inline int xcd_grid(int count) { return (count + kXcds - 1) / kXcds * kXcds; }
+
+// the strips (= runs of a tile) wavefront `wave` of a tile's workgroup owns
+__device__ __forceinline__ void wave_runs(int num_strips, int wave, int* lo, int* hi) {
+    const int per_wave = (num_strips + kReduceWaves - 1) / kReduceWaves;
+    *lo = min(num_strips, wave * per_wave);
+    *hi = min(num_strips, *lo + per_wave);
+}
+#endif
+
+} // namespace detail
+} // namespace spmv
+
+#endif

@@ -567,7 +567,7 @@ def dangling_per_rank(bounds, dangling):
 # the construction fixes them the slot, item and long-row counts).  tests/test_exact_data.py proves the data exact
 # and W / R from the host logic; tests/test_gpu_tiled_geometry.py asserts the rest from csr_tiled_info.
 def default_long_row(strips):
-    """build_plan (csrc/tiled.hip): rows with more entries than max(64, min(4096, 8 * strips)) are long."""
+    """build_plan (csrc/tiled_build.hip): rows with more entries than max(64, min(4096, 8 * strips)) are long."""
     return max(64, min(4096, 8 * strips))
 
 

@@ -285,7 +285,7 @@ def test_container_properties_random(spmv, tmp_path):
 
 
 def test_tiled_engine_shape_rules(spmv):
-    """Host logic of the LDS-tiled engine (csrc/tiled.hip choose_shape / eligibility), no GPU needed:
+    """Host logic of the LDS-tiled engine (csrc/tiled_plan.cpp choose_shape / eligibility), no GPU needed:
     which matrices it takes, and that strips / tiles stay inside the LDS budgets and index widths."""
     takes, w, r = spmv.tiled_shape(10_000_000, 10_000_000, 160_000_000)          # BASELINE config 5
     assert takes and w in (4096, 8192, 16384, 32768) and r % 64 == 0 and 1024 <= r <= 9984
