@@ -78,8 +78,8 @@ __global__ __launch_bounds__(kBlock)
 void max_row_kernel(Src src, int num_rows, int* __restrict__ out) {
     int best = 0;
     if constexpr (Src::kSearchRows) {
-        // CSR: four rows per thread and step — one 16-byte load of the row pointers + the one behind them (the pointer array
-        // is hipMalloc'd or a whole torch tensor in every caller; an unaligned base takes the plain loop below)
+        // CSR: four rows per thread and step — one 16-byte load of the row pointers + the one behind them; a base off the
+        // 16-byte boundary (a slice of a larger array) takes the plain loop below (tests/test_gpu_array_views.py)
         const int* rp = src.row_ptrs;
         if ((reinterpret_cast<unsigned long long>(rp) & 15) == 0) {
             const long long groups = num_rows / 4;

@@ -699,6 +699,20 @@ def geometry_matrix(name):
     return _geometry_cache[name]
 
 
+def entry_matrix(W, R):
+    """3 * R + 1 rows (a last tile of one row) x 2 * W + 1 columns (a last strip of one column), rows of up to 8
+    scattered entries plus the strip-edge entries (the last row holds one per strip edge on top): a width the ELL
+    slabs can carry."""
+    rows, cols = 3 * R + 1, 2 * W + 1
+    rng = np.random.default_rng(W + R)
+    rr, cc = _scattered(rng, rows, cols, W, max_len=8)
+    keys = np.unique(rr.astype(np.int64) * cols + cc)
+    rr, ci = keys // cols, (keys % cols).astype(np.int32)
+    rp = np.concatenate([[0], np.cumsum(np.bincount(rr, minlength=rows))]).astype(np.int32)
+    va = (rng.integers(1, 9, size=ci.size) * rng.choice([-1, 1], size=ci.size)).astype(np.float32)
+    return rows, cols, rp, ci, va
+
+
 def entry_point_systems(W):
     """The integer SPD and non-symmetric systems the solvers' tiled route runs at strip width W: n = 20 011, so that
     4096-column strips give five of them and 9984-row tiles three."""
@@ -763,3 +777,46 @@ def bicgstab_first_step(rp, ci, va, b, K=BICG_ALPHA_INVERSE):
     assert max(abs(int(u)) for u in scaled) < 2**53
     x = (np.float64(omega) * (ks.astype(np.float64) / K) + b64.astype(np.float64) / K).astype(np.float32)
     return x, omega
+
+
+# ------------------------------------------------------------------------------------------ array-view catalogue
+# The matrices tests/test_gpu_array_views.py hands to the library as VIEWS into larger device allocations: every array
+# starts 0..3 elements past a 16-byte boundary and is surrounded by poison that is legal to read (it can never fault)
+# but cannot pass unnoticed in a result.  x is drawn from NON-ZERO integers and no stored value is zero, so one stray
+# entry of any kind (a neighbour's live entry, the poison column num_cols - 1, the poison value 2^22, the x poison 2^22)
+# moves a row's sum by a non-zero integer; tests/test_exact_data.py proves that for every member.
+VIEW_NAMES = ["sweep:L1_low", "sweep:L4_top", "sweep:L16_low", "sweep:L64_top", "ldsx:L4_top",
+              "merge:row_end_T-1",                       # tile 0's last merge item is a row end
+              "merge:row_over_four_tiles",               # tiles 1 and 2 lie inside one long row
+              "tiled:4096x64"]                           # ENTRY_POINT_GEOMETRIES[0]: the tiled engine's smallest plan
+VIEW_OFFSETS = [(0, 0, 0), (1, 1, 1), (2, 3, 1), (3, 1, 2), (1, 2, 3)]      # (row_ptrs, cols, vals) elements past 16 bytes
+VIEW_POISON = float(1 << 22)                             # value and x poison
+
+
+def nonzero_x(rng, count, xmax=64):
+    """Non-zero integers in [-xmax, xmax] as float32."""
+    return (rng.integers(1, xmax + 1, size=count) * rng.choice([-1, 1], size=count)).astype(np.float32)
+
+
+def view_matrix(name):
+    """dict(kind, L, rows, num_cols, rp, ci, va, x) of one VIEW_NAMES member: the catalogue's matrix under a non-zero
+    x; L is what the lane rule gives it; "tiled" members carry W and R."""
+    kind, key = name.split(":")
+    extra = {}
+    if kind == "sweep":
+        _, rp, ci, va, _ = sweep_matrix(key)
+        num_cols = SWEEP_COLS
+    elif kind == "ldsx":
+        _, num_cols, rp, ci, va, _ = ldsx_matrix(key)
+    elif kind == "merge":
+        rp, ci, va, _ = merge_cut_matrix(key)
+        num_cols = MERGE_CUT_COLS
+    else:
+        W, R = (int(v) for v in key.split("x"))
+        _, num_cols, rp, ci, va = entry_matrix(W, R)
+        extra = dict(W=W, R=R)
+    rows = len(rp) - 1
+    x = nonzero_x(np.random.default_rng(sum(name.encode())), num_cols)
+    check_exact(rp, ci, va, x)
+    return dict(kind=kind, key=key, L=lanes_for(int(rp[-1]), rows), rows=rows, num_cols=num_cols, rp=rp, ci=ci, va=va,
+                x=x, **extra)

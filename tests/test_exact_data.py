@@ -485,3 +485,72 @@ def test_geometry_catalogue_covers_what_it_claims():
     for strip in range(6):                                                      # consecutive rows: no skip markers
         r = np.unique(rows_of[ci // 4096 == strip])
         assert r.size == 0 or (r[0] == 0 and np.all(np.diff(r) == 1))
+
+
+# ------------------------------------------------------------------------------------------ array-view catalogue
+def test_view_catalogue_picks_what_it_claims():
+    names = ed.VIEW_NAMES
+    assert [n for n in names if n.startswith("sweep:")] == ["sweep:L1_low", "sweep:L4_top", "sweep:L16_low", "sweep:L64_top"]
+    assert sum(n.startswith("ldsx:") for n in names) == 1 and sum(n.startswith("merge:") for n in names) == 2
+    assert "tiled:%dx%d" % min(ed.ENTRY_POINT_GEOMETRIES) in names
+    T = ed.MERGE_TILE
+    ends = {n: merge_items(ed.view_matrix(n)["rp"]) for n in names if n.startswith("merge:")}
+    assert T - 1 in ends["merge:row_end_T-1"]                                   # tile 0 ends on a row end
+    long_row = ends["merge:row_over_four_tiles"]
+    assert not np.any((long_row >= T) & (long_row < 3 * T))                     # tiles 1 and 2: inside one row
+    # every array meets every residue; cols and vals part ways
+    for k in range(3):
+        assert {t[k] for t in ed.VIEW_OFFSETS} == {0, 1, 2, 3}
+    assert any(t[1] != t[2] for t in ed.VIEW_OFFSETS)
+
+
+@pytest.mark.parametrize("name", ed.VIEW_NAMES)
+def test_view_matrix_is_exact_and_no_stray_entry_can_hide(spmv, oracle, monkeypatch, name):
+    """Per member: exact under the non-zero x; one stray entry of any kind added to any row changes the int64
+    reference (by at least 2^22 when it carries the value or the x poison) while every true row sum stays below
+    2^24; the lane rule (and for the tiled member the shape rule) lands where the GPU test expects."""
+    m = ed.view_matrix(name)
+    rp, ci, va, x, num_cols, rows = m["rp"], m["ci"], m["va"], m["x"], m["num_cols"], m["rows"]
+    nnz = int(rp[-1])
+    want = prove_exact(spmv, oracle, num_cols, rp, ci, va, x).astype(np.int64)
+    assert np.all(x != 0) and np.all(va != 0) and np.abs(x).min() >= 1 and np.abs(va).min() >= 1
+    assert int(ed.row_abs_sums(rp, ci, va, x).max()) < ed.EXACT_LIMIT
+    poison = np.int64(ed.VIEW_POISON)
+    assert poison == 1 << 22 and np.float32(ed.VIEW_POISON) == ed.VIEW_POISON
+    x64, v64 = x.astype(np.int64), va.astype(np.int64)
+    poison_col = num_cols - 1
+    # the stray entry (column, value) a row may pick up: a live neighbour, the column poison with a live or the
+    # poison value, a live column with the poison value; and a live entry multiplied by the x poison
+    deltas = [v64 * x64[ci], v64 * x64[poison_col], poison * x64[ci], v64 * poison, np.array([poison * x64[poison_col]])]
+    for d in deltas:
+        assert np.all(d != 0)
+    for d in deltas[2:]:
+        assert np.abs(d).min() >= 1 << 22
+    # spelled out on the reference: appending any one of them to any row changes that row and no other
+    stray = np.array([int(d[np.argmin(np.abs(d))]) for d in deltas], np.int64)          # the smallest of each kind
+    for s in stray:
+        assert np.all(want + s != want)
+    lens = np.diff(rp.astype(np.int64))
+    for r in (0, int(np.argmax(lens)), int(np.flatnonzero(lens == 0)[0]), rows - 1):    # ... and literally, on four rows
+        for col, val in ((poison_col, np.float32(va[0])), (int(ci[0]), np.float32(ed.VIEW_POISON)),
+                         (poison_col, np.float32(ed.VIEW_POISON))):
+            rp2 = rp.astype(np.int64).copy()
+            rp2[r + 1:] += 1
+            at = int(rp[r + 1])
+            got = ed.row_abs_sums(rp2, np.insert(ci, at, col), np.insert(va, at, val), x)      # bound not asserted: poison
+            run = np.concatenate([[0], np.cumsum(np.insert(va, at, val).astype(np.int64) * x64[np.insert(ci, at, col)])])
+            y = run[rp2[1:]] - run[rp2[:-1]]
+            assert y[r] != want[r] and np.array_equal(np.delete(y, r), np.delete(want, r)) and got[r] > 0
+    # row-pointer poison nnz: in range for both entry arrays' extents
+    assert 0 <= nnz <= ci.size
+    # the kernels the GPU test expects
+    assert ed.lanes_for(nnz, rows) == m["L"]
+    if m["kind"] == "sweep":
+        assert m["L"] == int(m["key"][1:].split("_")[0]) and rows == ed.SWEEP_ROWS
+    elif m["kind"] == "ldsx":
+        assert rows >= 4096 and 0 < num_cols <= 32768 and (nnz * 8) // (8 * 4 * num_cols) >= 64
+        assert num_cols % 4 != 0                                     # the 16-byte copy loop has a tail
+    elif m["kind"] == "tiled":
+        monkeypatch.setenv("SPMV_DEBUG", ed.tiled_debug(m["W"], m["R"]))
+        assert spmv.tiled_shape(rows, num_cols, nnz) == (True, m["W"], m["R"])
+        assert int(lens.max()) <= ed.default_long_row(-(-num_cols // m["W"]))

@@ -96,18 +96,7 @@ def test_both_builder_forms_against_the_reference(gpu, monkeypatch, name):
 
 
 # ------------------------------------------------------------------------------------------ other entry points
-def entry_matrix(W, R):
-    """3 * R + 1 rows (a last tile of one row) x 2 * W + 1 columns (a last strip of one column), rows of up to 8
-    scattered entries plus the strip-edge entries (the last row holds one per strip edge on top): a width the ELL
-    slabs can carry."""
-    rows, cols = 3 * R + 1, 2 * W + 1
-    rng = np.random.default_rng(W + R)
-    rr, cc = ed._scattered(rng, rows, cols, W, max_len=8)
-    keys = np.unique(rr.astype(np.int64) * cols + cc)
-    rr, ci = keys // cols, (keys % cols).astype(np.int32)
-    rp = np.concatenate([[0], np.cumsum(np.bincount(rr, minlength=rows))]).astype(np.int32)
-    va = (rng.integers(1, 9, size=ci.size) * rng.choice([-1, 1], size=ci.size)).astype(np.float32)
-    return rows, cols, rp, ci, va
+entry_matrix = ed.entry_matrix
 
 
 def entry_case(what, W, R, rows, cols):
