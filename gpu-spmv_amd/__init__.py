@@ -178,6 +178,13 @@ class ILU0Result(Structure):
                 ("elapsed_ms", c_float)]
 
 
+class IC0Result(Structure):
+    """include/spmv/ic0.h IC0Result (28 bytes); bad_pivot is the lowest row whose l_ii is not > 0 or not finite, or -1"""
+    _fields_ = [("error_code", c_int32), ("num_levels", c_int32), ("launches", c_int32),
+                ("lanes_per_row", c_int32), ("bad_pivot", c_int32), ("analysis_ms", c_float),
+                ("elapsed_ms", c_float)]
+
+
 class PageRankResult:
     """reference include/spmv/pagerank.h:18-25; `ranks` is a numpy copy (the C buffer is freed)."""
 
@@ -276,6 +283,11 @@ _SIGNATURES = {
     "spmv_c_ilu0_csr": (c_int, [POINTER(CSRMatrix), c_void_p, POINTER(ILU0Result)]),
     "spmv_c_ilu0_csr_async": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p]),
     "spmv_c_ilu0_cpu_csr": (c_int, [POINTER(CSRMatrix), c_void_p, POINTER(c_int32)]),
+    "spmv_c_cg_solve_ic": (c_int, [POINTER(CSRMatrix), POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(CGConfig),
+                                   POINTER(CGResult)]),
+    "spmv_c_ic0_csr": (c_int, [POINTER(CSRMatrix), c_void_p, POINTER(IC0Result)]),
+    "spmv_c_ic0_csr_async": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p]),
+    "spmv_c_ic0_cpu_csr": (c_int, [POINTER(CSRMatrix), c_void_p, POINTER(c_int32)]),
     "spmv_c_sptrsv_csr": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(SpTRSVConfig),
                                   POINTER(SpTRSVResult)]),
     "spmv_c_sptrsv_csr_async": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(SpTRSVConfig), c_void_p]),
@@ -870,6 +882,38 @@ def ilu0_cpu_csr(A):
     if status != 0:
         raise ValueError(spmv_error_string(status))
     return lu, pivot.value
+
+
+def cg_solve_ic(A, F, d_b, d_x, config=None) -> CGResult:
+    """CG preconditioned by M = L L^T, L the lower and L^T the upper triangle of the device matrix F
+    (include/spmv/cg.h cg_solve_ic); F is usually ic0_csr's output wrapped by csr_wrap_device over A's structure
+    arrays.  config.preconditioner is not read."""
+    out = CGResult()
+    lib().spmv_c_cg_solve_ic(A, F, _dev(d_b), _dev(d_x), byref(config) if config is not None else None, byref(out))
+    return out
+
+
+def ic0_csr(A, d_l_values) -> IC0Result:
+    """IC(0) of the square device matrix A into d_l_values (include/spmv/ic0.h ic0_csr): nnz floats in A's pattern,
+    L on and left of the diagonal, L^T right of it; d_l_values may be A's own device values (in place)."""
+    out = IC0Result()
+    lib().spmv_c_ic0_csr(A, _dev(d_l_values), byref(out))
+    return out
+
+
+def ic0_csr_async(A, d_l_values, stream=None) -> int:
+    return lib().spmv_c_ic0_csr_async(A, _dev(d_l_values), c_void_p(stream))
+
+
+def ic0_cpu_csr(A):
+    """The factorisation on A's host arrays (include/spmv/ic0.h ic0_cpu_csr, the definition of the arithmetic):
+    returns (l_values, bad_pivot); raises ValueError with the library's error string when the call is rejected."""
+    l = np.zeros(max(int(A.contents.nnz), 0) if A else 0, dtype=np.float32)
+    pivot = c_int32(-1)
+    status = lib().spmv_c_ic0_cpu_csr(A, _np_ptr(l), byref(pivot))
+    if status != 0:
+        raise ValueError(spmv_error_string(status))
+    return l, pivot.value
 
 
 def sptrsv_csr(A, d_b, d_x, config=None) -> SpTRSVResult:

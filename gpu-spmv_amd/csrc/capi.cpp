@@ -9,6 +9,7 @@
 #include "spmv/cg.h"
 #include "spmv/pagerank.h"
 #include "spmv/sptrsv.h"
+#include "spmv/ic0.h"
 #include "spmv/ilu0.h"
 #include "spmv_c.h"
 
@@ -72,6 +73,13 @@ static_assert(offsetof(spmv_c_ilu0_result, num_levels) == offsetof(ILU0Result, n
               offsetof(spmv_c_ilu0_result, zero_pivot) == offsetof(ILU0Result, zero_pivot) &&
               offsetof(spmv_c_ilu0_result, analysis_ms) == offsetof(ILU0Result, analysis_ms) &&
               offsetof(spmv_c_ilu0_result, elapsed_ms) == offsetof(ILU0Result, elapsed_ms), "ILU0Result layout");
+static_assert(sizeof(spmv_c_ic0_result) == sizeof(IC0Result) && sizeof(IC0Result) == 28, "IC0Result layout");
+static_assert(offsetof(spmv_c_ic0_result, num_levels) == offsetof(IC0Result, num_levels) &&
+              offsetof(spmv_c_ic0_result, launches) == offsetof(IC0Result, launches) &&
+              offsetof(spmv_c_ic0_result, lanes_per_row) == offsetof(IC0Result, lanes_per_row) &&
+              offsetof(spmv_c_ic0_result, bad_pivot) == offsetof(IC0Result, bad_pivot) &&
+              offsetof(spmv_c_ic0_result, analysis_ms) == offsetof(IC0Result, analysis_ms) &&
+              offsetof(spmv_c_ic0_result, elapsed_ms) == offsetof(IC0Result, elapsed_ms), "IC0Result layout");
 static_assert(offsetof(spmv_c_sptrsv_result, num_levels) == offsetof(SpTRSVResult, num_levels) &&
               offsetof(spmv_c_sptrsv_result, launches) == offsetof(SpTRSVResult, launches) &&
               offsetof(spmv_c_sptrsv_result, lanes_per_row) == offsetof(SpTRSVResult, lanes_per_row) &&
@@ -468,6 +476,13 @@ int spmv_c_cg_solve(const spmv_c_csr* A, const float* d_b, float* d_x, const spm
     return r.error_code;
 }
 
+int spmv_c_cg_solve_ic(const spmv_c_csr* A, const spmv_c_csr* F, const float* d_b, float* d_x,
+                       const spmv_c_cg_config* config, spmv_c_cg_result* out) {
+    const CGResult r = cg_solve_ic(cxx(A), cxx(F), d_b, d_x, reinterpret_cast<const CGConfig*>(config));
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
+}
+
 int spmv_c_bicgstab_solve(const spmv_c_csr* A, const float* d_b, float* d_x, const spmv_c_bicgstab_config* config,
                           spmv_c_bicgstab_result* out) {
     const BiCGStabResult r = bicgstab_solve(cxx(A), d_b, d_x, reinterpret_cast<const BiCGStabConfig*>(config));
@@ -495,6 +510,20 @@ int spmv_c_ilu0_csr_async(const spmv_c_csr* A, float* d_lu_values, void* hip_str
 
 int spmv_c_ilu0_cpu_csr(const spmv_c_csr* A, float* lu_values, int32_t* zero_pivot) {
     return ilu0_cpu_csr(cxx(A), lu_values, zero_pivot);
+}
+
+int spmv_c_ic0_csr(const spmv_c_csr* A, float* d_l_values, spmv_c_ic0_result* out) {
+    const IC0Result r = ic0_csr(cxx(A), d_l_values);
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
+}
+
+int spmv_c_ic0_csr_async(const spmv_c_csr* A, float* d_l_values, void* hip_stream) {
+    return ic0_csr_async(cxx(A), d_l_values, as_stream(hip_stream));
+}
+
+int spmv_c_ic0_cpu_csr(const spmv_c_csr* A, float* l_values, int32_t* bad_pivot) {
+    return ic0_cpu_csr(cxx(A), l_values, bad_pivot);
 }
 
 int spmv_c_sptrsv_csr(const spmv_c_csr* A, const float* d_b, float* d_x, const spmv_c_sptrsv_config* config,

@@ -9,11 +9,21 @@
 //   cg_direction_kernel every workgroup folds those partials, gets beta and the stop test, p = z + beta p
 // On the tiled engine tiled_spmv(plan, p, q) and cg_dot_kernel (partials of p.q) replace the first launch.
 // Dot products accumulate fp64 products of the fp32 entries; no float atomics anywhere.
+//
+// cg_solve_ic is the same loop with M = L L^T given as a factor matrix.  z is a stored vector
+// there, so the second half of a step is
+//   cg_ic_update_kernel     as cg_update_kernel, but only the block partials of r.r (z does not exist yet)
+//   launch_sptrsv x 2       z = L^-1 r (LOWER NON_UNIT), then z = L^-T z in place (UPPER NON_UNIT); they do not read
+//                           `done`: after it r no longer changes and they rewrite the same z
+//   cg_rz_kernel            the block partials of r.z
+//   cg_ic_direction_kernel  as cg_direction_kernel with z read from memory
+// and the SpMV half is the one above, kernel for kernel.
 #include "internal.h"
 #include "device_common.h"
 #include "solver_common.h"
 #include "tiled.h"
 #include "spmv/cg.h"
+#include "spmv/sptrsv.h"
 
 #include <hip/hip_runtime.h>
 
@@ -241,6 +251,96 @@ void cg_direction_kernel(int n, int step, const float* __restrict__ r, const flo
     }
 }
 
+// IC: some row of the factor has no stored diagonal, or one that is not > 0 or not finite.  One thread per row: setup.
+__global__ __launch_bounds__(kBlock)
+void cg_ic_diag_kernel(int n, const int* __restrict__ row_ptrs, const int* __restrict__ cols,
+                       const float* __restrict__ vals, CgState* __restrict__ state) {
+    int bad = 0;
+    for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < n;
+         i += static_cast<long long>(gridDim.x) * kBlock) {
+        float d = 0.0f;
+        int found = 0;
+        for (int j = row_ptrs[i]; j < row_ptrs[i + 1]; ++j) {
+            if (cols[j] == i) {
+                d = __fadd_rn(d, vals[j]);
+                found = 1;
+            }
+        }
+        bad |= !(found && d > 0.0f && isfinite(d));
+    }
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(&state->bad_diagonal, 1);
+}
+
+// IC: alpha = rz / p.q; x += alpha p; r -= alpha q; partials of r.r -> part_out[2 * block + 1] (cg_update_kernel's
+// slot; r.z follows from cg_rz_kernel once z is solved for).
+__global__ __launch_bounds__(kBlock)
+void cg_ic_update_kernel(int n, int step, const float* __restrict__ p, const float* __restrict__ q,
+                         float* __restrict__ x, float* __restrict__ r, CgState* __restrict__ state,
+                         const double* __restrict__ pq_part, int pq_count, double* __restrict__ part_out) {
+    if (state->done) return;
+    double pq = 0.0, unused = 0.0;
+    fold_partials(pq_part, pq_count, 1, pq, unused);
+    if (!(pq > 0.0)) {             // A is not SPD (or p.q is not finite): x stays at the last good iterate
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            state->breakdown = 1;
+            state->done = 1;
+        }
+        return;
+    }
+    const float alpha = static_cast<float>(state->rz[step & 1] / pq);
+    double rr = 0.0;
+    for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < n;
+         i += static_cast<long long>(gridDim.x) * kBlock) {
+        x[i] = __builtin_fmaf(alpha, p[i], x[i]);
+        const float ri = __builtin_fmaf(-alpha, q[i], r[i]);
+        r[i] = ri;
+        rr += prod64(ri, ri);
+    }
+    block_sum2(rr, unused);
+    if (threadIdx.x == 0) part_out[2 * blockIdx.x + 1] = rr;
+}
+
+// IC: block partials of r.z -> part[stride * block] (stride 2 inside the loop, 3 over the init partials).
+__global__ __launch_bounds__(kBlock)
+void cg_rz_kernel(int n, const float* __restrict__ r, const float* __restrict__ z,
+                  const CgState* __restrict__ state, double* __restrict__ part, int stride) {
+    if (state->done) return;
+    double rz = 0.0, unused = 0.0;
+    for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < n;
+         i += static_cast<long long>(gridDim.x) * kBlock) {
+        rz += prod64(r[i], z[i]);
+    }
+    block_sum2(rz, unused);
+    if (threadIdx.x == 0) part[static_cast<long long>(stride) * blockIdx.x] = rz;
+}
+
+// IC: cg_direction_kernel with the stored z.
+__global__ __launch_bounds__(kBlock)
+void cg_ic_direction_kernel(int n, int step, const float* __restrict__ z, float* __restrict__ p,
+                            CgState* __restrict__ state, const double* __restrict__ part, int count) {
+    if (state->done) return;
+    double rz = 0.0, rr = 0.0;
+    fold_partials(part, count, 2, rz, rr);
+    const double res = sqrt(rr);
+    const bool converged = res <= state->threshold;
+    const bool breakdown = !converged && !(rz > 0.0);
+    const double rz_old = state->rz[step & 1];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        state->iterations = step + 1;
+        state->relative_residual = static_cast<float>(res / state->bnorm);
+        state->rz[(step + 1) & 1] = rz;
+        if (converged) state->converged = 1;
+        if (breakdown) state->breakdown = 1;
+        if (converged || breakdown) state->done = 1;
+    }
+    if (converged || breakdown) return;
+    const float beta = static_cast<float>(rz / rz_old);
+    for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < n;
+         i += static_cast<long long>(gridDim.x) * kBlock) {
+        p[i] = __builtin_fmaf(beta, p[i], z[i]);
+    }
+}
+
 template <int LANES>
 hipError_t launch_init(const CSRMatrix* A, const float* b, const float* x, const float* dinv, float* r, float* p,
                        double* part, int grid, hipStream_t s) {
@@ -271,12 +371,14 @@ hipError_t spmv_dot(int lanes, const CSRMatrix* A, const float* p, float* q, con
     });
 }
 
-} // namespace
-} // namespace detail
+bool device_arrays(const CSRMatrix* M) {
+    return M->num_rows >= 0 && M->d_row_ptrs && (M->nnz <= 0 || (M->d_col_indices && M->d_values));
+}
 
-CGResult cg_solve(const CSRMatrix* A, const float* d_b, float* d_x, const CGConfig* config) {
-    using namespace detail;
-    using namespace detail::solver;
+// cg_solve (with_ic false: F is not looked at, cfg.preconditioner picks NONE or JACOBI) and cg_solve_ic (with_ic
+// true: M = L L^T from F, cfg.preconditioner is not read).
+CGResult solve(const CSRMatrix* A, const CSRMatrix* F, bool with_ic, const float* d_b, float* d_x,
+               const CGConfig* config) {
     CGResult result;
     const auto fail = [&result](SpMVError e) {
         result.error_code = code(e);
@@ -294,16 +396,39 @@ CGResult cg_solve(const CSRMatrix* A, const float* d_b, float* d_x, const CGConf
     const CGConfig defaults;
     const CGConfig& cfg = config ? *config : defaults;
     if (!(cfg.tolerance >= 0.0f) || cfg.max_iterations < 0 ||
-        (cfg.preconditioner != CGConfig::NONE && cfg.preconditioner != CGConfig::JACOBI) ||
+        (!with_ic && cfg.preconditioner != CGConfig::NONE && cfg.preconditioner != CGConfig::JACOBI) ||
         cfg.engine < -1 || cfg.engine > 1) {
         return fail(SpMVError::INVALID_ARGUMENT);
     }
     const int n = A->num_rows;
     if (ranges_overlap(d_b, d_x, n)) return fail(SpMVError::INVALID_ARGUMENT);
+    if (with_ic) {
+        if (!F) return fail(SpMVError::INVALID_ARGUMENT);
+        if (F->num_rows != F->num_cols || F->num_rows != n) return fail(SpMVError::INVALID_DIMENSION);
+        if (!device_arrays(F)) return fail(SpMVError::INVALID_FORMAT);
+    }
 
-    const TraceRange range("spmv:cg_solve");
+    const TraceRange range(with_ic ? "spmv:cg_solve_ic" : "spmv:cg_solve");
     hipStream_t stream = current_stream();
-    const bool jacobi = cfg.preconditioner == CGConfig::JACOBI;
+    const bool jacobi = !with_ic && cfg.preconditioner == CGConfig::JACOBI;
+
+    // both schedules of F, ahead of the timed loop (a build synchronises the stream); they validate F's structure
+    // before any kernel walks it
+    std::shared_ptr<const SptrsvSchedule> lower, upper;
+    int lower_lanes = 1, upper_lanes = 1;
+    if (with_ic) {
+        float analysis_ms = 0.0f;
+        int status = sptrsv_schedule_for(F, SpTRSVConfig::LOWER, stream, &lower, &analysis_ms);
+        if (status == 0) status = sptrsv_schedule_for(F, SpTRSVConfig::UPPER, stream, &upper, &analysis_ms);
+        if (status != 0) return fail(static_cast<SpMVError>(status));
+        lower_lanes = sptrsv_lanes_for(*lower);
+        upper_lanes = sptrsv_lanes_for(*upper);
+    }
+    // out = L^-T (L^-1 in): LOWER NON_UNIT, then UPPER NON_UNIT in place
+    const auto apply_ic = [&](const float* in, float* out) -> bool {
+        return launch_sptrsv(*lower, F, in, out, SpTRSVConfig::LOWER, 0, false, lower_lanes, stream) == hipSuccess &&
+               launch_sptrsv(*upper, F, out, out, SpTRSVConfig::UPPER, 0, false, upper_lanes, stream) == hipSuccess;
+    };
 
     // engine choice (pagerank()'s rule for -1: a cached plan from the start, else a build after 4 direct steps)
     PlanRef plan;
@@ -322,26 +447,40 @@ CGResult cg_solve(const CSRMatrix* A, const float* d_b, float* d_x, const CGConf
     const size_t rr_count = 2 * static_cast<size_t>(vgrid);
     const size_t init_count = 3 * static_cast<size_t>(row_grid);
 
-    Workspace<CgState> ws;          // r, p, q, dinv
+    Workspace<CgState> ws;          // r, p, q, and dinv (JACOBI) or z (IC)
     const size_t len = static_cast<size_t>(n);
     if (!ws.allocate(4 * len, pq_count + rr_count + init_count)) return fail(SpMVError::CUDA_MALLOC);
     float* r = ws.vec;
     float* p = ws.vec + len;
     float* q = ws.vec + 2 * len;
     float* dinv = jacobi ? ws.vec + 3 * len : nullptr;
+    float* z = with_ic ? ws.vec + 3 * len : nullptr;
     double* pq_part = ws.part;
     double* rr_part = ws.part + pq_count;
     double* init_part = rr_part + rr_count;
     CgState* pinned = ws.pinned;
 
-    // setup: diagonal (JACOBI), r0 / p0 and their dots, the state; one read-back
+    // setup: diagonal (JACOBI; of F, only its check), r0 / p0 and their dots, the state; one read-back
     bool ok = hipMemsetAsync(ws.state, 0, sizeof(CgState), stream) == hipSuccess;
+    if (ok && with_ic) {
+        cg_ic_diag_kernel<<<vgrid, kBlock, 0, stream>>>(n, F->d_row_ptrs, F->d_col_indices, F->d_values, ws.state);
+        ok = hipGetLastError() == hipSuccess;
+    }
     if (ok && jacobi) {
         cg_diag_kernel<<<vec_grid(n), kBlock, 0, stream>>>(n, A->d_row_ptrs, A->d_col_indices, A->d_values, dinv,
                                                             ws.state);
         ok = hipGetLastError() == hipSuccess;
     }
     ok = ok && init(lanes, A, d_b, d_x, dinv, r, p, init_part, row_grid, stream) == hipSuccess;
+    if (ok && with_ic) {
+        // the init kernel left p0 = r0 and r0.r0 in the r.z slot: z0 = M^-1 r0, the true r0.z0 over it, p0 = z0
+        ok = apply_ic(r, z);
+        if (ok) {
+            cg_rz_kernel<<<row_grid, kBlock, 0, stream>>>(n, r, z, ws.state, init_part, 3);
+            ok = hipGetLastError() == hipSuccess &&
+                 hipMemcpyAsync(p, z, len * sizeof(float), hipMemcpyDeviceToDevice, stream) == hipSuccess;
+        }
+    }
     if (ok) {
         cg_start_kernel<<<1, kBlock, 0, stream>>>(init_part, row_grid, cfg.tolerance, ws.state);
         ok = hipGetLastError() == hipSuccess;
@@ -394,10 +533,20 @@ CGResult cg_solve(const CSRMatrix* A, const float* d_b, float* d_x, const CGConf
                 }
             }
             if (ok && direct) ok = spmv_dot(lanes, A, p, q, ws.state, pq_part, row_grid, stream) == hipSuccess;
+            if (ok && with_ic) {
+                cg_ic_update_kernel<<<vgrid, kBlock, 0, stream>>>(n, iter, p, q, d_x, r, ws.state, pq_part, pq_parts,
+                                                                  rr_part);
+                ok = hipGetLastError() == hipSuccess && apply_ic(r, z);
+            }
             if (ok) {
-                cg_update_kernel<<<vgrid, kBlock, 0, stream>>>(n, iter, p, q, dinv, d_x, r, ws.state, pq_part,
-                                                               pq_parts, rr_part);
-                cg_direction_kernel<<<vgrid, kBlock, 0, stream>>>(n, iter, r, dinv, p, ws.state, rr_part, vgrid);
+                if (with_ic) {
+                    cg_rz_kernel<<<vgrid, kBlock, 0, stream>>>(n, r, z, ws.state, rr_part, 2);
+                    cg_ic_direction_kernel<<<vgrid, kBlock, 0, stream>>>(n, iter, z, p, ws.state, rr_part, vgrid);
+                } else {
+                    cg_update_kernel<<<vgrid, kBlock, 0, stream>>>(n, iter, p, q, dinv, d_x, r, ws.state, pq_part,
+                                                                   pq_parts, rr_part);
+                    cg_direction_kernel<<<vgrid, kBlock, 0, stream>>>(n, iter, r, dinv, p, ws.state, rr_part, vgrid);
+                }
                 ok = hipGetLastError() == hipSuccess
                   && hipMemcpyAsync(&pinned[iter & 1], ws.state, sizeof(CgState), hipMemcpyDeviceToHost,
                                     stream) == hipSuccess
@@ -424,6 +573,17 @@ CGResult cg_solve(const CSRMatrix* A, const float* d_b, float* d_x, const CGConf
     result.converged = final_state.converged;
     result.breakdown = final_state.breakdown;
     return result;
+}
+
+} // namespace
+} // namespace detail
+
+CGResult cg_solve(const CSRMatrix* A, const float* d_b, float* d_x, const CGConfig* config) {
+    return detail::solve(A, nullptr, false, d_b, d_x, config);
+}
+
+CGResult cg_solve_ic(const CSRMatrix* A, const CSRMatrix* F, const float* d_b, float* d_x, const CGConfig* config) {
+    return detail::solve(A, F, true, d_b, d_x, config);
 }
 
 } // namespace spmv

@@ -77,6 +77,9 @@ struct SptrsvSchedule {
     long long triangle_nnz = 0;      // stored entries inside the triangle, diagonal included
     int  first_missing_diagonal = -1;
     int  first_unsorted_row = -1;    // lowest row whose columns are not strictly ascending, or -1 (ilu0_csr needs none)
+    // LOWER schedules of a sorted matrix with every diagonal: a row holding a stored (i,k) whose (k,i) is not stored,
+    // or -1 when the pattern is structurally symmetric (ic0_csr needs that); -1 where it was not tested
+    int  one_sided_row = -1;
     // what it was built from (the transpose cache's rule)
     const void* row_ptrs = nullptr;
     const void* cols = nullptr;
@@ -183,6 +186,7 @@ void    ell_aux_drop(const void* key);
 //   pr_copy=pageable           pagerank() copies its result into a pageable array (no pinned pool)
 //   sptrsv_lanes=N             lanes per row of sptrsv_csr with ordered = 0 (1, 2, 4, ... 64; anything else is ignored)
 //   ilu0_lanes=N               lanes per row of ilu0_csr (1, 2, 4, ... 64; anything else is ignored)
+//   ic0_lanes=N                lanes per row of ic0_csr (1, 2, 4, ... 64; anything else is ignored)
 // Everything else the library reads from the environment is listed in INTEGRATION.md.
 bool debug_option(const char* key, long long* value = nullptr, char* text = nullptr, size_t text_size = 0);
 // the same "key=value,key" syntax for another variable's value (SPMV_MULTI_GPU); `list` may be null
@@ -239,6 +243,33 @@ int sptrsv_lanes_for(const SptrsvSchedule& schedule);
 // diagonal that folds the lowest row with a zero or non-finite pivot into it (an unsigned min; preset to all ones)
 hipError_t launch_ilu0(const SptrsvSchedule& schedule, const CSRMatrix* A, const float* d_a, float* d_lu,
                        int lanes_per_row, unsigned* d_zero_pivot, hipStream_t s);
+// IC(0) factorisation (ic0.hip): as launch_ilu0, from the lower triangle and diagonal of d_a into d_l (L on and left
+// of the diagonal, L^T right of it; may be the same array); the scan folds the lowest row whose l_ii is not > 0 or
+// not finite into d_bad_pivot
+hipError_t launch_ic0(const SptrsvSchedule& schedule, const CSRMatrix* A, const float* d_a, float* d_l,
+                      int lanes_per_row, unsigned* d_bad_pivot, hipStream_t s);
+// A row of the square, valid CSR pattern (rows strictly ascending, every diagonal stored) that holds one side only of
+// some pair (i,k) / (k,i), or -1 when the pattern is structurally symmetric.  One pass: row k's upper entries must be
+// met in their stored order as the rows below it are walked downwards.
+inline int one_sided_row(int n, const int* row_ptrs, const int* cols) {
+    std::vector<int> next(static_cast<size_t>(n));      // first upper position of row k not yet matched
+    for (int k = 0; k < n; ++k) {
+        int p = row_ptrs[k];
+        while (p < row_ptrs[k + 1] && cols[p] <= k) ++p;
+        next[k] = p;
+    }
+    for (int i = 0; i < n; ++i) {
+        for (int p = row_ptrs[i]; p < row_ptrs[i + 1] && cols[p] < i; ++p) {
+            const int k = cols[p];
+            if (next[k] >= row_ptrs[k + 1] || cols[next[k]] != i) return i;
+            ++next[k];
+        }
+    }
+    for (int k = 0; k < n; ++k) {
+        if (next[k] != row_ptrs[k + 1]) return k;
+    }
+    return -1;
+}
 hipError_t launch_ell_from_csr(const CSRMatrix* csr, int width, int* d_ell_cols, float* d_ell_vals,
                                hipStream_t s);
 hipError_t device_count_ell_nnz(const ELLMatrix* A, long long* out, hipStream_t s);

@@ -199,6 +199,9 @@ int schedule_for(const CSRMatrix* A, int uplo, hipStream_t stream, ScheduleRef* 
             }
         }
     }
+    if (!upper && missing < 0 && built->first_unsorted_row < 0) {
+        built->one_sided_row = one_sided_row(n, row_ptrs.data(), cols.data());
+    }
     const size_t ptr_bytes = (static_cast<size_t>(num_levels) + 1) * sizeof(int);
     const size_t order_bytes = static_cast<size_t>(n) * sizeof(int);
     if (malloc_any_time(reinterpret_cast<void**>(&built->d_level_ptr), ptr_bytes) != hipSuccess ||

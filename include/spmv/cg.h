@@ -67,6 +67,28 @@ struct CGResult {
 // plan for engine 1) and its one setup read-back synchronise that stream — make the call outside a graph capture.
 CGResult cg_solve(const CSRMatrix* A, const float* d_b, float* d_x, const CGConfig* config = nullptr);
 
+// cg_solve preconditioned by M = L L^T: L is the lower triangle of the square device matrix F with its stored
+// diagonal, L^T is F's upper triangle with its stored diagonal (entries are taken as stored: nothing tests that the
+// two triangles are each other's transpose).  F has num_rows == A->num_rows; the usual one wraps the output of
+// ic0_csr (spmv/ic0.h) over A's own structure arrays.
+//     r0 = b - A x0;  z0 = L^-T (L^-1 r0);  p0 = z0
+//     repeat: q = A p;  alpha = (r.z) / (p.q);  x += alpha p;  r -= alpha q;  stop test on ||r||;
+//             z = L^-T (L^-1 r);  beta = (r.z)_new / (r.z)_old;  p = z + beta p
+// Numerics as above, except that z is a stored vector: per step two sptrsv_csr launch sequences with ordered = 0
+// (LOWER NON_UNIT from r into z, then UPPER NON_UNIT in place) fill it, r.z is a dot product of its own, and
+// p = fmaf(beta, p, z) reads it.  The SpMV half of a step, the engines, the plan caching and the stop rules are
+// cg_solve's; a solve is bitwise reproducible from run to run on each engine.
+//
+// Checks, before any write to d_x: cg_solve's, in their order (config->preconditioner is not read), then: null F ->
+// INVALID_ARGUMENT; F not square or of another size than A -> INVALID_DIMENSION; F's device arrays missing ->
+// INVALID_FORMAT; setup builds (or finds) both of F's sptrsv_csr schedules: malformed structure -> INVALID_FORMAT; a
+// row of F whose diagonal is missing, not > 0 or not finite -> INVALID_ARGUMENT (checked on the device, read back
+// once during setup).  cg_solve itself keeps rejecting preconditioner values other than NONE and JACOBI.
+// The first call with a factor builds its schedules and synchronises the stream for them; the workspace is four
+// vectors (r, p, q, z).
+CGResult cg_solve_ic(const CSRMatrix* A, const CSRMatrix* F, const float* d_b, float* d_x,
+                     const CGConfig* config = nullptr);
+
 } // namespace spmv
 
 #endif

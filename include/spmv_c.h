@@ -270,6 +270,13 @@ typedef struct spmv_c_cg_result {
 int spmv_c_cg_solve(const spmv_c_csr* A, const float* d_b, float* d_x, const spmv_c_cg_config* config,
                     spmv_c_cg_result* out);
 
+/* the same iteration preconditioned by M = L L^T, L the lower triangle (with the stored diagonal) of the square
+ * device matrix F and L^T its upper triangle (num_rows as A's; usually spmv_c_ic0_csr's output wrapped over A's
+ * structure arrays).  config->preconditioner is not read.  Checks and numerics as cg_solve_ic in include/spmv/cg.h.
+ * The return value equals out->error_code (out may be NULL). */
+int spmv_c_cg_solve_ic(const spmv_c_csr* A, const spmv_c_csr* F, const float* d_b, float* d_x,
+                       const spmv_c_cg_config* config, spmv_c_cg_result* out);
+
 /* ---- Jacobi-preconditioned BiCGSTAB (extension; spmv::bicgstab_solve, include/spmv/bicgstab.h) ---- */
 /* 16 bytes; the fields, defaults and meanings of spmv_c_cg_config */
 typedef struct spmv_c_bicgstab_config {
@@ -363,6 +370,29 @@ int spmv_c_ilu0_csr(const spmv_c_csr* A, float* d_lu_values, spmv_c_ilu0_result*
 int spmv_c_ilu0_csr_async(const spmv_c_csr* A, float* d_lu_values, void* hip_stream);
 /* the factorisation on A's host arrays (lu_values: nnz floats, may be A's host values); *zero_pivot may be NULL */
 int spmv_c_ilu0_cpu_csr(const spmv_c_csr* A, float* lu_values, int32_t* zero_pivot);
+
+/* ---- IC(0) factorisation over the LOWER level schedule (extension; include/spmv/ic0.h) ---- */
+/* 28 bytes */
+typedef struct spmv_c_ic0_result {
+    int32_t error_code;
+    int32_t num_levels;
+    int32_t launches;
+    int32_t lanes_per_row;
+    int32_t bad_pivot;     /* lowest row whose l_ii is not > 0 or not finite, or -1 */
+    float   analysis_ms;   /* 0 when the cached schedule was used */
+    float   elapsed_ms;    /* the factorisation launches only */
+} spmv_c_ic0_result;
+
+/* Factors the square device matrix A (columns strictly ascending in every row, every diagonal stored, a structurally
+ * symmetric pattern; only the lower triangle's values are read) into d_l_values: nnz floats in A's pattern, L on and
+ * left of the diagonal, L^T right of it; d_l_values may be A's own device value array (in place).  Bit-identical to
+ * spmv_c_ic0_cpu_csr.  Argument checks and arithmetic as ic0_csr in include/spmv/ic0.h.  The return value equals
+ * out->error_code (out may be NULL). */
+int spmv_c_ic0_csr(const spmv_c_csr* A, float* d_l_values, spmv_c_ic0_result* out);
+/* the same factorisation enqueued on a caller stream without timing, pivot scan or synchronisation */
+int spmv_c_ic0_csr_async(const spmv_c_csr* A, float* d_l_values, void* hip_stream);
+/* the factorisation on A's host arrays (l_values: nnz floats, may be A's host values); *bad_pivot may be NULL */
+int spmv_c_ic0_cpu_csr(const spmv_c_csr* A, float* l_values, int32_t* bad_pivot);
 
 /* ---- bandwidth model: reference include/spmv/bandwidth.h:21-27 ---- */
 int spmv_c_compute_bandwidth_csr(const spmv_c_csr* A, float elapsed_ms, spmv_c_bandwidth* out);
