@@ -154,6 +154,28 @@ class BiCGStabResult(Structure):
     NONE, RHO, ALPHA, OMEGA = BICGSTAB_NO_BREAKDOWN, BICGSTAB_RHO, BICGSTAB_ALPHA, BICGSTAB_OMEGA
 
 
+class GMRESConfig(Structure):
+    """include/spmv/gmres.h GMRESConfig (20 bytes): restart 1..64; the other fields as CGConfig"""
+    _fields_ = [("tolerance", c_float), ("max_iterations", c_int32), ("restart", c_int32),
+                ("preconditioner", c_int32), ("engine", c_int32)]
+    NONE, JACOBI = 0, 1
+
+    def __init__(self, tolerance=1e-6, max_iterations=1000, restart=30, preconditioner=1, engine=-1):
+        super().__init__(tolerance, max_iterations, restart, preconditioner, engine)
+
+
+# GMRESResult.breakdown codes (include/spmv/gmres.h GMRESResult::Breakdown)
+GMRES_NO_BREAKDOWN, GMRES_SINGULAR, GMRES_NOT_FINITE = 0, 1, 2
+
+
+class GMRESResult(Structure):
+    """include/spmv/gmres.h GMRESResult (28 bytes); breakdown is one of NONE, SINGULAR, NOT_FINITE"""
+    _fields_ = [("error_code", c_int32), ("iterations", c_int32), ("restarts", c_int32),
+                ("relative_residual", c_float), ("converged", c_int32), ("breakdown", c_int32),
+                ("elapsed_ms", c_float)]
+    NONE, SINGULAR, NOT_FINITE = GMRES_NO_BREAKDOWN, GMRES_SINGULAR, GMRES_NOT_FINITE
+
+
 class SpTRSVConfig(Structure):
     """include/spmv/sptrsv.h SpTRSVConfig (16 bytes): uplo 0 LOWER / 1 UPPER; diag 0 NON_UNIT / 1 UNIT; ordered 1 = one
     lane per row in the CPU's summation order"""
@@ -280,6 +302,10 @@ _SIGNATURES = {
                                       POINTER(BiCGStabResult)]),
     "spmv_c_bicgstab_solve_lu": (c_int, [POINTER(CSRMatrix), POINTER(CSRMatrix), c_void_p, c_void_p,
                                          POINTER(BiCGStabConfig), POINTER(BiCGStabResult)]),
+    "spmv_c_gmres_solve": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(GMRESConfig),
+                                   POINTER(GMRESResult)]),
+    "spmv_c_gmres_solve_lu": (c_int, [POINTER(CSRMatrix), POINTER(CSRMatrix), c_void_p, c_void_p,
+                                      POINTER(GMRESConfig), POINTER(GMRESResult)]),
     "spmv_c_ilu0_csr": (c_int, [POINTER(CSRMatrix), c_void_p, POINTER(ILU0Result)]),
     "spmv_c_ilu0_csr_async": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p]),
     "spmv_c_ilu0_cpu_csr": (c_int, [POINTER(CSRMatrix), c_void_p, POINTER(c_int32)]),
@@ -858,6 +884,25 @@ def bicgstab_solve_lu(A, LU, d_b, d_x, config=None) -> BiCGStabResult:
     out = BiCGStabResult()
     lib().spmv_c_bicgstab_solve_lu(A, LU, _dev(d_b), _dev(d_x), byref(config) if config is not None else None,
                                    byref(out))
+    return out
+
+
+def gmres_solve(A, d_b, d_x, config=None) -> GMRESResult:
+    """Restarted GMRES(m) for a square non-singular A x = b on the device (include/spmv/gmres.h gmres_solve): d_b and
+    d_x hold num_rows floats, d_x is the initial guess on entry and the solution on exit; relative_residual and
+    converged come from the recomputed b - A x."""
+    out = GMRESResult()
+    lib().spmv_c_gmres_solve(A, _dev(d_b), _dev(d_x), byref(config) if config is not None else None, byref(out))
+    return out
+
+
+def gmres_solve_lu(A, LU, d_b, d_x, config=None) -> GMRESResult:
+    """GMRES(m) right-preconditioned by M = L U, the unit lower and the upper triangle of the device matrix LU
+    (include/spmv/gmres.h gmres_solve_lu); LU is usually ilu0_csr's output wrapped by csr_wrap_device over A's
+    structure arrays.  config.preconditioner is not read."""
+    out = GMRESResult()
+    lib().spmv_c_gmres_solve_lu(A, LU, _dev(d_b), _dev(d_x), byref(config) if config is not None else None,
+                                byref(out))
     return out
 
 

@@ -6,6 +6,7 @@
 #include "tiled.h"
 #include "spmv/bandwidth.h"
 #include "spmv/bicgstab.h"
+#include "spmv/gmres.h"
 #include "spmv/cg.h"
 #include "spmv/pagerank.h"
 #include "spmv/sptrsv.h"
@@ -48,6 +49,18 @@ static_assert(offsetof(spmv_c_cg_result, iterations) == offsetof(CGResult, itera
               offsetof(spmv_c_cg_result, converged) == offsetof(CGResult, converged) &&
               offsetof(spmv_c_cg_result, breakdown) == offsetof(CGResult, breakdown) &&
               offsetof(spmv_c_cg_result, elapsed_ms) == offsetof(CGResult, elapsed_ms), "CGResult layout");
+static_assert(sizeof(spmv_c_gmres_config) == sizeof(GMRESConfig) && sizeof(GMRESConfig) == 20, "GMRESConfig layout");
+static_assert(offsetof(spmv_c_gmres_config, max_iterations) == offsetof(GMRESConfig, max_iterations) &&
+              offsetof(spmv_c_gmres_config, restart) == offsetof(GMRESConfig, restart) &&
+              offsetof(spmv_c_gmres_config, preconditioner) == offsetof(GMRESConfig, preconditioner) &&
+              offsetof(spmv_c_gmres_config, engine) == offsetof(GMRESConfig, engine), "GMRESConfig layout");
+static_assert(sizeof(spmv_c_gmres_result) == sizeof(GMRESResult) && sizeof(GMRESResult) == 28, "GMRESResult layout");
+static_assert(offsetof(spmv_c_gmres_result, iterations) == offsetof(GMRESResult, iterations) &&
+              offsetof(spmv_c_gmres_result, restarts) == offsetof(GMRESResult, restarts) &&
+              offsetof(spmv_c_gmres_result, relative_residual) == offsetof(GMRESResult, relative_residual) &&
+              offsetof(spmv_c_gmres_result, converged) == offsetof(GMRESResult, converged) &&
+              offsetof(spmv_c_gmres_result, breakdown) == offsetof(GMRESResult, breakdown) &&
+              offsetof(spmv_c_gmres_result, elapsed_ms) == offsetof(GMRESResult, elapsed_ms), "GMRESResult layout");
 static_assert(sizeof(spmv_c_bicgstab_config) == sizeof(BiCGStabConfig) && sizeof(BiCGStabConfig) == 16,
               "BiCGStabConfig layout");
 static_assert(offsetof(spmv_c_bicgstab_config, max_iterations) == offsetof(BiCGStabConfig, max_iterations) &&
@@ -494,6 +507,20 @@ int spmv_c_bicgstab_solve_lu(const spmv_c_csr* A, const spmv_c_csr* LU, const fl
                              const spmv_c_bicgstab_config* config, spmv_c_bicgstab_result* out) {
     const BiCGStabResult r = bicgstab_solve_lu(cxx(A), cxx(LU), d_b, d_x,
                                                reinterpret_cast<const BiCGStabConfig*>(config));
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
+}
+
+int spmv_c_gmres_solve(const spmv_c_csr* A, const float* d_b, float* d_x, const spmv_c_gmres_config* config,
+                       spmv_c_gmres_result* out) {
+    const GMRESResult r = gmres_solve(cxx(A), d_b, d_x, reinterpret_cast<const GMRESConfig*>(config));
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
+}
+
+int spmv_c_gmres_solve_lu(const spmv_c_csr* A, const spmv_c_csr* LU, const float* d_b, float* d_x,
+                          const spmv_c_gmres_config* config, spmv_c_gmres_result* out) {
+    const GMRESResult r = gmres_solve_lu(cxx(A), cxx(LU), d_b, d_x, reinterpret_cast<const GMRESConfig*>(config));
     if (out) std::memcpy(out, &r, sizeof(r));
     return r.error_code;
 }

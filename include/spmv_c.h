@@ -310,6 +310,41 @@ int spmv_c_bicgstab_solve(const spmv_c_csr* A, const float* d_b, float* d_x, con
 int spmv_c_bicgstab_solve_lu(const spmv_c_csr* A, const spmv_c_csr* LU, const float* d_b, float* d_x,
                              const spmv_c_bicgstab_config* config, spmv_c_bicgstab_result* out);
 
+/* ---- restarted GMRES(m) (extension; spmv::gmres_solve, include/spmv/gmres.h) ---- */
+/* 20 bytes; restart in [1, 64]; the other fields as spmv_c_cg_config */
+typedef struct spmv_c_gmres_config {
+    float   tolerance;
+    int32_t max_iterations;
+    int32_t restart;
+    int32_t preconditioner;
+    int32_t engine;
+} spmv_c_gmres_config;
+
+/* breakdown: 0 none, 1 SINGULAR (the rotated Hessenberg column is 0), 2 NOT_FINITE; relative_residual and converged
+ * come from b - A x recomputed with the returned x (28 bytes) */
+typedef struct spmv_c_gmres_result {
+    int32_t error_code;
+    int32_t iterations;
+    int32_t restarts;
+    float   relative_residual;
+    int32_t converged;
+    int32_t breakdown;
+    float   elapsed_ms;
+} spmv_c_gmres_result;
+
+/* Solves A x = b for a square non-singular A on the device by GMRES(restart); d_b and d_x hold num_rows floats, d_x is
+ * the initial guess on entry and the solution on exit.  config NULL = defaults (1e-6, 1000, 30, JACOBI, auto).
+ * Argument checks and numerics as gmres_solve in include/spmv/gmres.h.  The return value equals out->error_code (out
+ * may be NULL). */
+int spmv_c_gmres_solve(const spmv_c_csr* A, const float* d_b, float* d_x, const spmv_c_gmres_config* config,
+                       spmv_c_gmres_result* out);
+
+/* the same iteration right-preconditioned by M = L U as spmv_c_bicgstab_solve_lu.  config->preconditioner is not read.
+ * Checks and numerics as gmres_solve_lu in include/spmv/gmres.h.  The return value equals out->error_code (out may be
+ * NULL). */
+int spmv_c_gmres_solve_lu(const spmv_c_csr* A, const spmv_c_csr* LU, const float* d_b, float* d_x,
+                          const spmv_c_gmres_config* config, spmv_c_gmres_result* out);
+
 /* ---- sparse triangular solve with level scheduling (extension; include/spmv/sptrsv.h) ---- */
 /* uplo: 0 LOWER, 1 UPPER; diag: 0 NON_UNIT, 1 UNIT; ordered: 1 = one lane per row in the CPU's summation order
  * (bit-identical to spmv_c_sptrsv_cpu_csr), 0 = 1-64 lanes per row; reserved: 0 (16 bytes) */
