@@ -820,3 +820,189 @@ def view_matrix(name):
     check_exact(rp, ci, va, x)
     return dict(kind=kind, key=key, L=lanes_for(int(rp[-1]), rows), rows=rows, num_cols=num_cols, rp=rp, ci=ci, va=va,
                 x=x, **extra)
+
+
+# ------------------------------------------------------------------------------------------ one-hot Krylov systems
+# GMRES (csrc/gmres.hip) held to the bit along the whole basis walk.  A = D + B, D diagonal, B one entry per column i
+# at row (i + s) mod n, every stored value +- a power of two, b = 2^a e_p.  Then A e_i = d_i e_i + beta_i e_(i+s): from
+# x0 = 0 the Arnoldi vectors of the FIRST cycle are v_j = +- e_(q_j), q_j = (p + j s) mod n, as long as the walk does
+# not come back to a position: h1 holds d_(q_j) at i = j and exact zeros elsewhere, h2 is exactly zero, h_j+1 =
+# |beta_(q_j)|, every dot product has at most one non-zero term.  The small problem (rotations, back-substitution) is a
+# fixed sequence of rounded fp64 operations, the same on the host and on the device.  At a close, A x touches at most
+# two non-zero products per row, both exact (powers of two), so one rounded addition whatever the order.
+#
+# From the SECOND cycle on the vectors are no longer one-hot: r = b - A x is supported on q_0..q_k, and every later
+# vector on the positions walked so far (after `it` steps: q_0..q_it).  Dot products then sum up to it + 1 exact fp64
+# products and their last fp64 bits depend on the order; what the solver takes from them is rounded to fp32 (h1, h2,
+# 1 / beta, 1 / h_j+1, y), which hides that unless a value sits within a few fp64 ulps of an fp32 rounding boundary.
+# tests/test_exact_data.py probes this per case with three summation orders (numpy's, its reverse, the correctly
+# rounded sum) and demands the same bits from all of them.  |d| is 1 or 2 and |beta| 1/2, 1 or 2: the solution neither
+# decays nor grows along the walk by more than a few powers of ten in 129 steps, so nothing comes near fp32's
+# subnormal range, and the small problem stays well enough conditioned that an order change is not amplified.
+ONEHOT_CHUNK = 1024                  # kChunk (csrc/gmres.hip): elements of w a workgroup of a basis kernel holds
+ONEHOT_ORTHO_BLOCKS = 256            # kOrthoBlocks: beyond 256 chunks the basis kernels take a second grid-stride trip
+ONEHOT_FOLD_LANES = 64               # fold_columns: beyond 64 workgroups a lane folds a second partial
+ONEHOT_ROW_BLOCKS = 2048             # kMaxResidentBlocks: gmres_spmv<L> / gmres_residual<L> run at most that many
+ONEHOT_RHS = 4.0                     # b = 2^2 e_p
+
+
+def gmres_onehot_system(n, p, s, steps, seed, empty_column=None):
+    """dict(n, rp, ci, va, b, walk, d, beta): the one-hot system above.  `walk` holds q_0..q_steps, the positions
+    anything can reach within `steps` Arnoldi steps; asserted distinct, and nothing off the walk feeds into it.  Each
+    row stores its diagonal entry and the entry of column (row - s) mod n, in an order drawn per row.
+    empty_column = j: B's column q_j stays empty, so A e_(q_j) = d e_(q_j) and step j finds h_j+1 == 0."""
+    assert 0 <= p < n and 0 < s < n and steps + 1 <= n
+    rng = np.random.default_rng(seed)
+    walk = (p + s * np.arange(steps + 1, dtype=np.int64)) % n
+    assert np.unique(walk).size == steps + 1, "the walk revisits a position"
+    assert (p - s) % n not in set(walk.tolist())
+    d = np.ldexp(rng.choice([-1.0, 1.0], size=n), rng.integers(0, 2, size=n)).astype(np.float32)
+    beta = np.ldexp(rng.choice([-1.0, 1.0], size=n), rng.integers(-1, 2, size=n)).astype(np.float32)
+    idx = np.arange(n, dtype=np.int64)
+    rows = np.concatenate([idx, (idx + s) % n])
+    cols = np.concatenate([idx, idx])
+    vals = np.concatenate([d, beta])
+    keep = np.ones(2 * n, bool)
+    if empty_column is not None:
+        keep[n + int(walk[empty_column])] = False
+    first = rng.integers(0, 2, size=n)                         # 1: the off-diagonal entry is stored first
+    key = 2 * rows + (np.concatenate([np.zeros(n, np.int64), np.ones(n, np.int64)]) ^ first[rows])
+    order = np.argsort(key[keep], kind="stable")
+    rows, cols, vals = rows[keep][order], cols[keep][order], vals[keep][order]
+    rp = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=n))]).astype(np.int32)
+    b = np.zeros(n, np.float32)
+    b[p] = ONEHOT_RHS
+    return dict(n=n, rp=rp, ci=cols.astype(np.int32), va=vals.astype(np.float32), b=b, walk=walk, d=d, beta=beta,
+                empty_column=empty_column)
+
+
+def onehot_compact(system):
+    """(m, rp, ci, va, b) of the system restricted to its walk, in walk order: row j is row q_j with its entries in
+    storage order, those whose column lies off the walk dropped (x is 0 there from start to end)."""
+    walk = system["walk"]
+    at = {int(q): j for j, q in enumerate(walk)}
+    rp, ci, va = system["rp"], system["ci"], system["va"]
+    c_rp, c_ci, c_va = [0], [], []
+    for q in walk:
+        for e in range(int(rp[q]), int(rp[q + 1])):
+            if int(ci[e]) in at:
+                c_ci.append(at[int(ci[e])])
+                c_va.append(va[e])
+        c_rp.append(len(c_ci))
+    return (walk.size, np.array(c_rp, np.int32), np.array(c_ci, np.int32), np.array(c_va, np.float32),
+            system["b"][walk].copy())
+
+
+def gmres_onehot_reference(system, restart, max_iterations, precond):
+    """gmres_cases.restate on the walk positions only, scattered back: (x, iterations, restarts, converged, breakdown,
+    relative residual) for tolerance 0 from x0 = 0.  tests/test_exact_data.py shows that it equals restate on the
+    whole system in every field at small n."""
+    import gmres_cases as gc
+    m, rp, ci, va, b = onehot_compact(system)
+    out = gc.restate(m, rp, ci, va, b, np.zeros(m, np.float32), 0.0, max_iterations, restart, precond)
+    x = np.zeros(system["n"], np.float32)
+    x[system["walk"]] = out[0]
+    return (x,) + tuple(out[1:])
+
+
+def _onehot_cases():
+    cases = {}
+
+    def add(name, n, p, s, restart, visits=(), chunks=(), empty_column=None, max_iterations=None):
+        it = 2 * restart + 1 if max_iterations is None else max_iterations
+        cases[name] = dict(name=name, n=n, p=p, s=s, restart=restart, max_iterations=it, visits=tuple(visits),
+                           chunks=tuple(chunks), empty_column=empty_column, seed=len(cases) + 17)
+
+    # groups of eight: two full cycles and one column more, n = 4103 (3 mod 4; 4 * 1026 = n + 1, so every fourth step
+    # moves one element on: n-3, 1023, 2049, 3075, n-2, 1024, ...)
+    for m in (1, 2, 7, 8, 9, 30, 64):
+        add("restart_%d" % m, 4103, 4100, 1026, m, visits=(4100, 1023) if m < 7 else (4100, 4101, 4102, 0, 1023, 1024))
+    # vector tails at n mod 4 = 1 and 2 (3 * 1026 = 3077 + 1, 3 * 1025 = 3074 + 1)
+    add("tail_n3077", 3077, 3074, 1026, 9, visits=(3074, 3075, 3076, 0, 1023, 1024))
+    add("tail_n3074", 3074, 3071, 1025, 9, visits=(3071, 3072, 3073, 0, 1023, 1024))
+    # 129 workgroups: fold_columns' lanes 0 fold partials 0, 64 and 128
+    add("fold_second_trip", 131587, 5, 65540, 9, visits=(5, 65545, 131085), chunks=(0, 64, 128))
+    # 259 chunks on 256 workgroups: the chunks below, at and past 256 (element 262 144), and the last, partial f32x4
+    add("grid_second_trip", 264195, 260102, 1023, 9, visits=(261125, 262148, 263171, 264194), chunks=(254, 255, 256, 257, 258, 0))
+    # L = 1: 2048 workgroups of 256 rows; rows 524 291 and 525 314 belong to the second trip of the row loops
+    add("rows_second_trip", 525315, 523268, 1023, 9, visits=(523268, 524291, 525314, 1022))
+    # B's column q_5 empty: six exact columns, then h_6 == 0 closes the cycle three steps before the host expects it
+    add("early_close", 4103, 4100, 1026, 9, visits=(4100, 1023, 4101), empty_column=5)
+    return cases
+
+
+ONEHOT_CASES = _onehot_cases()
+ONEHOT_NAMES = list(ONEHOT_CASES)
+_onehot_cache = {}
+
+
+def onehot_case(name):
+    """(case, system) of one ONEHOT_CASES member; the system is built once."""
+    if name not in _onehot_cache:
+        c = ONEHOT_CASES[name]
+        _onehot_cache[name] = (c, gmres_onehot_system(c["n"], c["p"], c["s"], c["max_iterations"], c["seed"],
+                                                      c["empty_column"]))
+    return _onehot_cache[name]
+
+
+# ------------------------------------------------------------------------------------------ GMRES, first step
+def pm_one_rhs(n, k, seed):
+    """+-1 on exactly 4^k positions, 0 elsewhere: ||b|| = 2^k."""
+    assert 4 ** k <= n
+    rng = np.random.default_rng(seed)
+    b = np.zeros(n, np.float32)
+    b[rng.choice(n, size=4 ** k, replace=False)] = rng.choice([-1.0, 1.0], size=4 ** k)
+    return b
+
+
+def gmres_first_step(rp, ci, va, b, k):
+    """x after ONE GMRES step from x0 = 0 without a preconditioner under gmres.h's rules, for an integer matrix and a
+    +-1 / 0 right-hand side with 4^k non-zeros (pm_one_rhs).  beta = 2^k and v_0 = b / 2^k exactly; w = A b / 2^k holds
+    integers over 2^k; h1_0 = b.A b / 4^k is an exact fp32 value; fmaf(-h1_0, v_0, w) = (4^k (A b)_i - b_i (b.A b)) / 8^k
+    with a numerator below 2^24: exact; h2_0 = (b.A b - (b.A b)(b.b) / 4^k) / 4^k == 0; w.w is a sum of integers over
+    64^k that stays below 2^53: exact in fp64 in any order.  What follows is the one-column small problem in fp64 (one
+    square root, rounded products and sums, two divisions) and x1 = fp32(y_0) v_0, an exact product.  Every claim is
+    asserted.  Returns (x1 float32, y_0 float64)."""
+    b = np.asarray(b, np.float32)
+    check_exact(rp, ci, va, b)
+    b64 = b.astype(np.int64)
+    scale = 4 ** k
+    assert set(np.unique(b64).tolist()) <= {-1, 0, 1} and int(np.abs(b64).sum()) == scale == int(b64 @ b64)
+    ab = exact_reference(rp, ci, va, b).astype(np.int64)                         # 2^k w
+    bab = int(b64 @ ab)
+    h1 = np.float32(np.float64(bab) / np.float64(scale))
+    assert np.float64(h1) * scale == bab and abs(bab) < EXACT_LIMIT             # an exact fp32 value
+    num = scale * ab - b64 * bab                                                 # 8^k (w after the first update)
+    assert int(np.abs(num).max()) < EXACT_LIMIT                                  # ... which fp32 holds: the fmaf is exact
+    assert int(b64 @ num) == 0                                                   # h2_0 == 0: the second update changes nothing
+    ww_int = sum(int(v) * int(v) for v in num[num != 0])                         # 64^k w.w
+    assert 0 < ww_int < 2 ** 53
+    one = np.float64(1.0)
+    ww = np.float64(ww_int) / np.float64(64 ** k)
+    beta = np.float64(2 ** k)
+    hn = np.sqrt(ww)
+    a = np.float64(h1) + np.float64(np.float32(0.0))
+    d = np.sqrt(a * a + hn * hn)
+    assert np.isfinite(d) and d > 0 and hn > 0
+    c = a / d
+    g0 = c * beta
+    y0 = g0 / d
+    x1 = (np.float64(np.float32(y0)) * (b.astype(np.float64) / beta)).astype(np.float32)
+    assert np.array_equal(x1.astype(np.float64) * beta, np.float64(np.float32(y0)) * b.astype(np.float64) * one)
+    return x1, y0
+
+
+GMRES_STEP_K = 5                              # 1024 of the 1201 / 1202 rows of solver_system
+GMRES_TILED_STEP_K = 7                        # 16 384 of the 20 011 rows of entry_point_systems
+
+
+def gmres_step_system(name):
+    """(L, n, rp, ci, va, b) of solver_system(name, symmetric=False) with the +-1 / 0 right-hand side."""
+    L, n, rp, ci, va, _, _ = solver_system(name, symmetric=False)
+    return L, n, rp, ci, va, pm_one_rhs(n, GMRES_STEP_K, 1300 + SOLVER_NAMES.index(name))
+
+
+def gmres_tiled_step_system(W):
+    """(n, rp, ci, va, b): the non-symmetric system of entry_point_systems(W) with the +-1 / 0 right-hand side."""
+    n, rp, ci, va = entry_point_systems(W)[1]
+    return n, rp, ci, va, pm_one_rhs(n, GMRES_TILED_STEP_K, 1400 + W)

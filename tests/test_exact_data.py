@@ -3,11 +3,13 @@ proved exact without a GPU.  Per matrix: the sum_j |a_ij| |x_j| < 2^24 bound hol
 name claims, and the CPU oracle (CPU order, fp32) and the library's own spmv_cpu_csr equal the int64 reference
 bit for bit: the data are order-independent, so the GPU tests may demand bit equality from every kernel."""
 import importlib
+import math
 
 import numpy as np
 import pytest
 
 import exact_data as ed
+import gmres_cases as gc
 
 
 def host_library_y(spmv, rows, num_cols, rp, ci, va, x):
@@ -554,3 +556,171 @@ def test_view_matrix_is_exact_and_no_stray_entry_can_hide(spmv, oracle, monkeypa
         monkeypatch.setenv("SPMV_DEBUG", ed.tiled_debug(m["W"], m["R"]))
         assert spmv.tiled_shape(rows, num_cols, nnz) == (True, m["W"], m["R"])
         assert int(lens.max()) <= ed.default_long_row(-(-num_cols // m["W"]))
+
+
+# ------------------------------------------------------------------------------------------ one-hot Krylov systems
+bits = lambda a: np.asarray(a, np.float32).view(np.uint32)
+DOTS = {
+    "numpy": gc.dot,
+    "reversed": lambda a, c: np.float64(np.dot(a.astype(np.float64)[::-1], c.astype(np.float64)[::-1])),
+    "correctly rounded": lambda a, c: np.float64(math.fsum((a.astype(np.float64) * c.astype(np.float64)).tolist())),
+}
+
+
+def same_outcome(got, want):
+    """every field restate returns, x and the residual on the bits"""
+    return (np.array_equal(bits(got[0]), bits(want[0])) and tuple(got[1:5]) == tuple(want[1:5])
+            and bits(got[5]) == bits(want[5]))
+
+
+def onehot_first_cycle(system, columns, precond):
+    """The first cycle's Arnoldi steps on the walk positions, spelled out, with the module comment's claims asserted
+    per column: h1 is d_(q_j) (JACOBI: d * fp32(1 / d) == 1) at i = j and 0.0 elsewhere, the updated w is one-hot at
+    q_j+1 with +-beta, h2 is all 0.0, sqrt(w.w) == |beta| and v_j+1 == +- e_(q_j+1)."""
+    m, rp, ci, va, b = ed.onehot_compact(system)
+    walk, d, beta = system["walk"], system["d"], system["beta"]
+    dinv = (np.float32(1.0) / gc.diag_of(m, rp, ci, va)).astype(np.float32)
+    assert np.array_equal(dinv, np.float32(1.0) / d[walk]) and np.array_equal(np.frexp(dinv)[0], np.copysign(0.5, dinv))
+    bnorm = np.sqrt(gc.dot(b, b))
+    assert bnorm == ed.ONEHOT_RHS
+    V = [(b * np.float32(1.0 / bnorm)).astype(np.float32)]
+    assert V[0][0] == 1.0 and np.count_nonzero(V[0]) == 1
+    for j in range(columns):
+        z = (V[j] * dinv).astype(np.float32) if precond == gc.JACOBI else V[j]
+        for spmv in (gc.spmv_round_once, gc.spmv_sequential):
+            w = spmv(rp, ci, va, z)
+            assert np.count_nonzero(w) <= 2
+        h1 = [np.float32(gc.dot(v, w)) for v in V]
+        expect = np.float32(1.0) if precond == gc.JACOBI else d[walk[j]]
+        assert h1[j] == expect and all(h == 0.0 for h in h1[:j])
+        for hi, v in zip(h1, V):
+            w = gc.fma(-hi, v, w)
+        bj = beta[walk[j]] * (dinv[j] if precond == gc.JACOBI else np.float32(1.0))
+        if system["empty_column"] == j:
+            assert np.count_nonzero(w) == 0                      # the lucky breakdown: h_j+1 == 0
+            return j + 1
+        assert np.count_nonzero(w) == 1 and w[j + 1] == V[j][j] * bj
+        assert all(np.float32(gc.dot(v, w)) == 0.0 for v in V)      # h2
+        hn = np.sqrt(gc.dot(w, w))
+        assert hn == abs(bj)
+        V.append((w * np.float32(1.0 / hn)).astype(np.float32))
+        assert np.count_nonzero(V[-1]) == 1 and abs(V[-1][j + 1]) == 1.0
+    return columns
+
+
+@pytest.mark.parametrize("name", ed.ONEHOT_NAMES)
+def test_onehot_case_is_what_it_claims(monkeypatch, name):
+    """No revisit, the required positions, powers of two, L = 1, the first cycle's exactness claims column by column,
+    and the same bits from three dot-product orders and two SpMV orders over the whole run (both preconditioners)."""
+    c, s = ed.onehot_case(name)
+    n, walk = s["n"], s["walk"]
+    assert walk.size == c["max_iterations"] + 1 == np.unique(walk).size and walk[0] == c["p"]
+    assert set(c["visits"]) <= set(walk.tolist()) and set(c["chunks"]) <= set((walk // ed.ONEHOT_CHUNK).tolist())
+    assert n % 64 != 0 and n % 4 != 0
+    nnz = int(s["rp"][-1])
+    assert nnz == 2 * n - (c["empty_column"] is not None) and ed.lanes_for(nnz, n) == 1
+    assert np.all(np.frexp(np.abs(s["va"]))[0] == 0.5) and np.abs(np.frexp(s["va"])[1] - 1).max() <= 1
+    assert np.count_nonzero(s["b"]) == 1 and s["b"][c["p"]] == ed.ONEHOT_RHS
+    rows = np.repeat(np.arange(n), np.diff(s["rp"]))
+    off = s["ci"] != rows
+    assert np.array_equal((s["ci"][off] + c["s"]) % n, rows[off])              # B: column i feeds row (i + s) mod n
+    assert np.array_equal(np.sort(s["ci"][~off]), np.arange(n))               # D: every diagonal entry, once
+    for precond in (gc.NONE, gc.JACOBI):
+        columns = onehot_first_cycle(s, min(c["restart"], c["max_iterations"]), precond)
+        outs = {}
+        for order, dot in DOTS.items():
+            monkeypatch.setattr(gc, "dot", dot)
+            outs[order] = ed.gmres_onehot_reference(s, c["restart"], c["max_iterations"], precond)
+        monkeypatch.setattr(gc, "dot", DOTS["numpy"])
+        m, rp, ci, va, b = ed.onehot_compact(s)
+        seq = gc.restate(m, rp, ci, va, b, np.zeros(m), 0.0, c["max_iterations"], c["restart"], precond,
+                         spmv=gc.spmv_sequential)
+        want = outs["numpy"]
+        for order in DOTS:
+            assert same_outcome(outs[order], want), (name, precond, order)
+        assert np.array_equal(bits(seq[0]), bits(want[0][walk])) and tuple(seq[1:]) == tuple(want[1:]), (name, precond)
+        x, it, restarts, conv, brk, rel = want
+        assert brk == gc.NO_BREAKDOWN and np.all(x[np.setdiff1d(np.arange(n), walk)] == 0)
+        nz = np.abs(x[x != 0])
+        assert nz.min() > 2.0 ** -100 and nz.max() < 2.0 ** 100               # far from fp32's subnormals and its top
+        if c["empty_column"] is None:
+            assert (it, restarts, conv) == (c["max_iterations"], 2, False) and rel > 2.0 ** -100
+        else:
+            # six exact columns solve the closed 6 x 6 system: y is dyadic, x exact, r == 0 and 0 <= 0 converges
+            k = c["empty_column"] + 1
+            assert columns == k and (it, restarts, conv, rel) == (k, 0, True, 0.0)
+            exact = np.zeros(k)
+            for j in range(k):
+                exact[j] = ((ed.ONEHOT_RHS if j == 0 else 0.0) - (s["beta"][walk[j - 1]] * exact[j - 1] if j else 0.0)) \
+                    / s["d"][walk[j]]
+            assert np.array_equal(x[walk[:k]], exact.astype(np.float32)) and np.count_nonzero(x) == k
+
+
+@pytest.mark.parametrize("name", [nm for nm in ed.ONEHOT_NAMES if ed.ONEHOT_CASES[nm]["n"] < 5000])
+def test_onehot_reference_on_the_walk_equals_the_restatement_on_the_whole_system(name):
+    c, s = ed.onehot_case(name)
+    for precond in (gc.NONE, gc.JACOBI):
+        full = gc.restate(s["n"], s["rp"], s["ci"], s["va"], s["b"], np.zeros(s["n"]), 0.0, c["max_iterations"],
+                          c["restart"], precond)
+        assert same_outcome(ed.gmres_onehot_reference(s, c["restart"], c["max_iterations"], precond), full), \
+            (name, precond)
+
+
+def test_onehot_catalogue_reaches_the_paths_it_names():
+    C = ed.ONEHOT_CASES
+    chunk, blocks = ed.ONEHOT_CHUNK, ed.ONEHOT_ORTHO_BLOCKS
+    # groups of eight: every restart of gmres_cases.RESTARTS, two full cycles and one column (closes with k = m, m, 1)
+    assert {C["restart_%d" % m]["restart"] for m in gc.RESTARTS} == set(gc.RESTARTS)
+    assert all(C["restart_%d" % m]["max_iterations"] == 2 * m + 1 for m in gc.RESTARTS)
+    # vector tails: n mod 4 = 1, 2, 3; n-1, n-2, n-3, 0 and both sides of the first chunk edge
+    tails = [C["tail_n3077"], C["tail_n3074"], C["restart_9"]]
+    assert sorted(c["n"] % 4 for c in tails) == [1, 2, 3]
+    for c in tails:
+        assert {c["n"] - 1, c["n"] - 2, c["n"] - 3, 0, chunk - 1, chunk} <= set(c["visits"])
+    # fold_columns: more than 64 and at most 256 workgroups, a ragged last chunk; first, 65th and last workgroup
+    c = C["fold_second_trip"]
+    groups = -(-c["n"] // chunk)
+    assert ed.ONEHOT_FOLD_LANES * chunk < c["n"] <= blocks * chunk and c["n"] % chunk != 0
+    assert {0, ed.ONEHOT_FOLD_LANES, groups - 1} <= set(c["chunks"]) and groups - 1 >= 2 * ed.ONEHOT_FOLD_LANES
+    # basis kernels: more than 257 chunks; the chunk on either side of the wrap, and the last partial f32x4
+    c = C["grid_second_trip"]
+    assert c["n"] > (blocks + 1) * chunk and c["n"] % 4 != 0
+    assert {blocks - 1, blocks, -(-c["n"] // chunk) - 1} <= set(c["chunks"])
+    assert any(v >= c["n"] - c["n"] % 4 for v in c["visits"]) and any(v >= blocks * chunk for v in c["visits"])
+    # the element-wise kernels (gmres_normalize) cap at kVecBlocks * 256 = 262 144 elements: the same case
+    assert c["n"] > 1024 * 256
+    # row loops at L = 1: 256 rows per workgroup, 2048 workgroups
+    c = C["rows_second_trip"]
+    edge = ed.ONEHOT_ROW_BLOCKS * 256
+    assert c["n"] > edge and any(v >= edge for v in c["visits"]) and any(v < edge for v in c["visits"])
+    # large cases keep the small basis
+    assert all(c["restart"] <= 9 for c in C.values() if c["n"] > 5000)
+    c = C["early_close"]
+    assert 2 <= c["empty_column"] + 1 < c["restart"] - 1 and c["max_iterations"] > c["restart"]
+
+
+# ------------------------------------------------------------------------------------------ GMRES, first step
+@pytest.mark.parametrize("name", ed.SOLVER_NAMES)
+def test_gmres_first_step_is_exact_per_lane_count(name):
+    """exact_data.gmres_first_step asserts its derivation; here it runs for every lane count's system, and the
+    prediction is the restatement's x after one step, bit for bit (the restatement rounds where the derivation says
+    nothing is lost)."""
+    L, n, rp, ci, va, b = ed.gmres_step_system(name)
+    assert ed.lanes_for(int(rp[-1]), n) == L == int(name[1:].split("_")[0])
+    assert np.count_nonzero(b) == 4 ** ed.GMRES_STEP_K <= n
+    x1, y0 = ed.gmres_first_step(rp, ci, va, b, ed.GMRES_STEP_K)
+    ref = gc.restate(n, rp, ci, va, b, np.zeros(n), 0.0, 1, 30, gc.NONE)
+    assert np.array_equal(bits(ref[0]), bits(x1)) and ref[1:5] == (1, 0, False, gc.NO_BREAKDOWN)
+    assert np.array_equal(x1 != 0, b != 0) and np.unique(np.abs(x1[x1 != 0])).size == 1
+
+
+@pytest.mark.parametrize("W,R", ed.ENTRY_POINT_GEOMETRIES)
+def test_gmres_first_tiled_step_system_is_exact(spmv, monkeypatch, W, R):
+    n, rp, ci, va, b = ed.gmres_tiled_step_system(W)
+    assert np.count_nonzero(b) == 4 ** ed.GMRES_TILED_STEP_K <= n == 20011
+    x1, y0 = ed.gmres_first_step(rp, ci, va, b, ed.GMRES_TILED_STEP_K)
+    ref = gc.restate(n, rp, ci, va, b, np.zeros(n), 0.0, 1, 2, gc.NONE)
+    assert np.array_equal(bits(ref[0]), bits(x1)) and ref[1:5] == (1, 0, False, gc.NO_BREAKDOWN)
+    monkeypatch.setenv("SPMV_DEBUG", ed.tiled_debug(W, R))
+    assert spmv.tiled_shape(n, n, int(rp[-1])) == (True, W, R)
+    assert int(np.diff(rp).max()) <= ed.default_long_row(-(-n // W))

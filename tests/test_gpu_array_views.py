@@ -26,6 +26,7 @@ import pytest
 import array_views as av
 import exact_data as ed
 import exact_triangles
+import ic0_cases as ic_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -35,6 +36,8 @@ transpose_tests = importlib.import_module("test_gpu_transpose")
 cg_tests = importlib.import_module("test_gpu_cg")
 bicg_tests = importlib.import_module("test_gpu_bicgstab")
 lu_tests = importlib.import_module("test_gpu_bicgstab_lu")
+ic_tests = importlib.import_module("test_gpu_cg_ic")
+gmres_tests = importlib.import_module("test_gpu_gmres")
 spd = importlib.import_module("gpu-spmv_amd.spd")
 nonsym = importlib.import_module("gpu-spmv_amd.nonsym")
 assert_bits = sweep.assert_bits
@@ -511,3 +514,89 @@ def test_ilu0_and_lu_preconditioned_bicgstab_on_views(gpu, monkeypatch, offsets)
         got = (res.error_code, res.iterations, res.converged, res.breakdown, res.relative_residual)
         assert got == (0, ref.iterations, ref.converged, ref.breakdown, ref.relative_residual), (offsets, got)
         assert_bits(rp, vx.download(), x_ref, ("bicgstab_solve_lu", offsets))
+
+
+# ------------------------------------------------------------------------------------------ ic0, IC-CG, GMRES
+@pytest.mark.parametrize("offsets", OFFSETS, ids=OFFSET_IDS)
+def test_ic0_and_ic_preconditioned_cg_on_views(gpu, offsets):
+    """ic0_csr of a view-backed A into a view and in place over the values view, against the factor of the aligned copy
+    (which test_gpu_cg_ic.ICSystem holds to ic0_cpu_csr) at zero tolerance; then cg_solve_ic with A, the factor, b and
+    x all views: iterations, flags, residual and every bit of x as on aligned copies.  1203 rows: 3 mod 4."""
+    n, rp, ci, va = ic_cases.sorted_random_spd(1203, 7, seed=21)
+    nnz = int(ci.size)
+    assert n % 4 == 3
+    b = np.random.default_rng(6).uniform(-1.0, 1.0, n).astype(np.float32)
+    s = ic_tests.ICSystem(gpu, n, rp, ci, va, b=b)
+    try:
+        want = s.l.copy()
+        ref, x_ref = s.solve_ic(tolerance=1e-6, engine=DIRECT)
+    finally:
+        s.close()
+    assert ref.error_code == 0 and ref.converged and ref.iterations >= 2
+    with av.Views(gpu) as V:
+        A, (v_rp, v_ci, v_va) = V.csr(n, n, rp, ci, va, offsets)
+        d_l = V.out(nnz, (offsets[0] + 1) % 4)
+        res = gpu.ic0_csr(A, d_l.ptr)
+        assert res.error_code == 0 and res.bad_pivot == -1, offsets
+        np.testing.assert_array_equal(d_l.download().view(np.uint32), want.view(np.uint32), err_msg=str(offsets))
+        V.check_guards(("ic0_csr", offsets))
+        res = gpu.ic0_csr(A, v_va.ptr)                                        # in place over the values view
+        assert res.error_code == 0 and res.bad_pivot == -1, offsets
+        np.testing.assert_array_equal(v_va.download().view(np.uint32), want.view(np.uint32), err_msg=str(offsets))
+        V.check_guards(("ic0_csr in place", offsets))
+        v_va.upload(va)
+        gpu.csr_invalidate_gpu_cache(A)
+        F = gpu.csr_wrap_device(n, n, nnz, v_rp.ptr, v_ci.ptr, d_l.ptr)
+        V.csr_handles.append(F)
+        vb, vx = V.x(b, offsets[2]), V.view(np.zeros(n, np.float32), offsets[1], SENTINEL)
+        res = gpu.cg_solve_ic(A, F, vb.ptr, vx.ptr, gpu.CGConfig(tolerance=1e-6, engine=DIRECT))
+        got = (res.error_code, res.iterations, res.converged, res.breakdown, res.relative_residual)
+        assert got == (0, ref.iterations, ref.converged, ref.breakdown, ref.relative_residual), (offsets, got)
+        assert_bits(rp, vx.download(), x_ref, ("cg_solve_ic", offsets))
+        V.check_guards(("cg_solve_ic", offsets))
+
+
+@pytest.mark.parametrize("offsets", OFFSETS, ids=OFFSET_IDS)
+def test_gmres_and_lu_preconditioned_gmres_on_views(gpu, offsets):
+    """gmres_solve (NONE, JACOBI) and gmres_solve_lu on the convection-diffusion system (ascending columns, which
+    ilu0_csr wants) with A's three arrays, the factor's values, b and x all views: iterations, restarts, flags, the
+    bits of relative_residual and every bit of x as on aligned copies.  1089 rows: 1 mod 4; restart 9 restarts."""
+    n, rp, ci, va = nonsym.convdiff2d(33, 3.0)
+    nnz = int(ci.size)
+    same_row = np.diff(np.repeat(np.arange(n), np.diff(rp))) == 0
+    assert n % 4 == 1 and np.all(np.diff(ci)[same_row] > 0)
+    s = gmres_tests.System(gpu, n, rp, ci, va)
+    b = s.b
+    try:
+        lu = s.factor()
+        want_lu = s.d_lu.copyToHost(nnz)
+        plain = {}
+        for kind in ("none", "jacobi", "lu"):
+            plain[kind] = s.solve(LU=lu if kind == "lu" else None, tolerance=1e-6, restart=9, engine=DIRECT,
+                                  preconditioner=JACOBI if kind == "jacobi" else NONE)
+            assert plain[kind][0].error_code == 0 and plain[kind][0].converged, kind
+        assert plain["none"][0].restarts >= 1
+    finally:
+        s.close()
+    with av.Views(gpu) as V:
+        A, (v_rp, v_ci, v_va) = V.csr(n, n, rp, ci, va, offsets)
+        d_lu = V.out(nnz, (offsets[0] + 2) % 4)
+        res = gpu.ilu0_csr(A, d_lu.ptr)
+        assert res.error_code == 0 and res.zero_pivot == -1, offsets
+        np.testing.assert_array_equal(d_lu.download().view(np.uint32), want_lu.view(np.uint32), err_msg=str(offsets))
+        LU = gpu.csr_wrap_device(n, n, nnz, v_rp.ptr, v_ci.ptr, d_lu.ptr)
+        V.csr_handles.append(LU)
+        for i, kind in enumerate(("none", "jacobi", "lu")):
+            cfg = gpu.GMRESConfig(tolerance=1e-6, restart=9, engine=DIRECT,
+                                  preconditioner=JACOBI if kind == "jacobi" else NONE)
+            vb = V.x(b, (i + offsets[2]) % 4)
+            vx = V.view(np.zeros(n, np.float32), (i + offsets[1]) % 4, SENTINEL)
+            res = gpu.gmres_solve_lu(A, LU, vb.ptr, vx.ptr, cfg) if kind == "lu" else \
+                gpu.gmres_solve(A, vb.ptr, vx.ptr, cfg)
+            ref, x_ref = plain[kind]
+            got = (res.error_code, res.iterations, res.restarts, res.converged, res.breakdown)
+            assert got == (0, ref.iterations, ref.restarts, ref.converged, ref.breakdown), (kind, offsets, got)
+            assert np.float32(res.relative_residual).view(np.uint32) == np.float32(ref.relative_residual).view(np.uint32)
+            assert_bits(rp, vx.download(), x_ref, ("gmres", kind, offsets))
+            V.check_guards(("gmres", kind, offsets))
+        assert not gpu.csr_has_tiled_plan(A)

@@ -11,7 +11,7 @@ test_gpu_lane_sweep.test_pagerank_bit_exact_per_lane_count).
 spmv_ell builds its plan from the ELL slabs and spmv_csr_transpose's plan belongs to the cached transpose: those two
 are read through ell_tiled_info / csr_transpose_tiled_info (a failed build falls back to the direct kernels, which
 give the same bits on exact data, so "a plan exists and has this shape" is asserted, not assumed).  The solvers'
-tiled route is tested by steps that run tiled_spmv: the first CG and the first BiCGSTAB step, both predictable to
+tiled route is tested by steps that run tiled_spmv: the first CG, BiCGSTAB and GMRES step, all predictable to
 the bit; the r0 == 0 check of the lane sweep is not repeated here, because the init kernels are the direct ones
 whatever the engine."""
 import importlib
@@ -219,6 +219,48 @@ def test_bicgstab_first_tiled_step_on_a_forced_geometry(gpu, monkeypatch, W, R):
             else:
                 assert not gpu.csr_has_tiled_plan(s.A)
             assert_bits(rp, x, want, what)
+    finally:
+        s.close()
+
+
+@pytest.mark.parametrize("W,R", ed.ENTRY_POINT_GEOMETRIES)
+def test_gmres_first_tiled_step_on_a_forced_geometry(gpu, monkeypatch, W, R):
+    """gmres_solve with engine = tiled on the integer non-symmetric system under b = +-1 on 16 384 rows: w = A v_0
+    comes from tiled_spmv on the forced plan and x1 must equal exact_data.gmres_first_step's prediction bit for bit
+    (test_gpu_gmres_exact.test_gmres_first_step_is_predictable_to_the_bit); the direct engine runs first and must give
+    the same bits.  Then restart 2 for four steps: every close runs tiled_spmv into the u buffer and
+    gmres_residual_ew, and the cycle after it is opened from that residual.  Past the first step the data are not
+    exact, so the engines must agree in iterations and restarts, and in relative_residual within
+    test_gpu_gmres.test_engines_agree's rule: SPREAD = 4e-4 of the residual (four times the spread measured between
+    two SpMV summation orders, see that module's docstring) plus the rounding bounds of the two recomputed residuals
+    (gmres_cases.residual_rounding_bound)."""
+    gmres_tests = importlib.import_module("test_gpu_gmres")
+    n, rp, ci, va, b = ed.gmres_tiled_step_system(W)
+    want, y0 = ed.gmres_first_step(rp, ci, va, b, ed.GMRES_TILED_STEP_K)
+    case = solver_case(W, R)
+    assert int(np.diff(rp).max()) <= ed.default_long_row(case["strips"])
+    monkeypatch.setenv("SPMV_DEBUG", ed.tiled_debug(W, R))
+    s = gmres_tests.System(gpu, n, rp, ci, va, b=b)
+    try:
+        for engine in (0, TILED, TILED):                     # the second tiled solve finds the plan cached
+            res, x = s.solve(tolerance=0.0, preconditioner=NONE, engine=engine, max_iterations=1)
+            what = ("gmres first step", W, R, engine, float(y0), res.iterations)
+            assert (res.error_code, res.iterations, res.restarts, res.converged, res.breakdown) == (0, 1, 0, 0, 0), what
+            if engine == TILED:
+                assert_plan(gpu, s.A, case)
+            else:
+                assert not gpu.csr_has_tiled_plan(s.A)
+            assert_bits(rp, x, want, what)
+            gmres_tests.check_honest(s, res, x)
+        out = {}
+        for engine in (0, TILED):
+            res, x = s.solve(tolerance=0.0, preconditioner=NONE, engine=engine, max_iterations=4, restart=2)
+            assert (res.error_code, res.iterations, res.restarts, res.converged, res.breakdown) == (0, 4, 1, 0, 0), \
+                (W, R, engine, res.iterations, res.restarts)
+            gmres_tests.check_honest(s, res, x)
+            out[engine] = (float(res.relative_residual), s.bound(x))
+        print("gmres restart 2, four steps", W, R, out)
+        assert abs(out[TILED][0] - out[0][0]) <= gmres_tests.SPREAD * out[0][0] + out[TILED][1] + out[0][1], out
     finally:
         s.close()
 
