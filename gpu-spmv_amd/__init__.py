@@ -207,6 +207,14 @@ class IC0Result(Structure):
                 ("elapsed_ms", c_float)]
 
 
+class SpGEMMResult(Structure):
+    """include/spmv/spgemm.h SpGEMMResult (104 bytes); symbolic_rows / numeric_rows count the rows per accumulator
+    class of each pass, [0] the rows without products"""
+    _fields_ = [("error_code", c_int32), ("nnz", c_int32), ("products", c_int64), ("max_row_products", c_int32),
+                ("max_row_nnz", c_int32), ("symbolic_rows", c_int32 * 8), ("numeric_rows", c_int32 * 8),
+                ("lanes", c_int32), ("symbolic_ms", c_float), ("numeric_ms", c_float)]
+
+
 class PageRankResult:
     """reference include/spmv/pagerank.h:18-25; `ranks` is a numpy copy (the C buffer is freed)."""
 
@@ -314,6 +322,11 @@ _SIGNATURES = {
     "spmv_c_ic0_csr": (c_int, [POINTER(CSRMatrix), c_void_p, POINTER(IC0Result)]),
     "spmv_c_ic0_csr_async": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p]),
     "spmv_c_ic0_cpu_csr": (c_int, [POINTER(CSRMatrix), c_void_p, POINTER(c_int32)]),
+    "spmv_c_spgemm_csr": (c_int, [POINTER(CSRMatrix), POINTER(CSRMatrix), POINTER(CSRMatrix), POINTER(SpGEMMResult)]),
+    "spmv_c_spgemm_csr_numeric": (c_int, [POINTER(CSRMatrix), POINTER(CSRMatrix), POINTER(CSRMatrix),
+                                          POINTER(SpGEMMResult)]),
+    "spmv_c_spgemm_cpu_csr": (c_int, [POINTER(CSRMatrix), POINTER(CSRMatrix), POINTER(CSRMatrix)]),
+    "spmv_c_spgemm_class_capacity": (c_int, [c_int]),
     "spmv_c_sptrsv_csr": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(SpTRSVConfig),
                                   POINTER(SpTRSVResult)]),
     "spmv_c_sptrsv_csr_async": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(SpTRSVConfig), c_void_p]),
@@ -640,6 +653,32 @@ def csr_transpose_gpu(AT, A) -> int:
     """Extension: AT = A^T built on the device, deterministic (csr_matrix.h csr_transpose_gpu); csr_from_gpu(AT)
     fills AT's host arrays."""
     return lib().spmv_c_csr_transpose_gpu(AT, A)
+
+
+def spgemm_csr(C, A, B) -> SpGEMMResult:
+    """C = A*B of two device matrices (include/spmv/spgemm.h spgemm_csr), bit-identical to spgemm_cpu_csr; C owns new
+    device arrays afterwards and csr_from_gpu(C) fills its host arrays.  result.error_code is the return value."""
+    out = SpGEMMResult()
+    out.error_code = lib().spmv_c_spgemm_csr(C, A, B, byref(out))
+    return out
+
+
+def spgemm_csr_numeric(C, A, B) -> SpGEMMResult:
+    """Only C's device values again, into the pattern an earlier spgemm_csr produced (spgemm.h spgemm_csr_numeric)."""
+    out = SpGEMMResult()
+    out.error_code = lib().spmv_c_spgemm_csr_numeric(C, A, B, byref(out))
+    return out
+
+
+def spgemm_cpu_csr(C, A, B) -> int:
+    """The product on host arrays, the definition of the arithmetic (spgemm.h spgemm_cpu_csr); C gets new host
+    arrays (csr_host_arrays(C) reads them)."""
+    return lib().spmv_c_spgemm_cpu_csr(C, A, B)
+
+
+def spgemm_class_capacity(cls) -> int:
+    """Most distinct columns of a row in accumulator class cls (1-based); INT_MAX for the dense class, -1 past it."""
+    return lib().spmv_c_spgemm_class_capacity(int(cls))
 
 
 def ell_from_csr_gpu(ell, csr) -> int:

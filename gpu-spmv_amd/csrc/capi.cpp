@@ -12,6 +12,7 @@
 #include "spmv/sptrsv.h"
 #include "spmv/ic0.h"
 #include "spmv/ilu0.h"
+#include "spmv/spgemm.h"
 #include "spmv_c.h"
 
 #include <cstddef>
@@ -98,6 +99,17 @@ static_assert(offsetof(spmv_c_sptrsv_result, num_levels) == offsetof(SpTRSVResul
               offsetof(spmv_c_sptrsv_result, lanes_per_row) == offsetof(SpTRSVResult, lanes_per_row) &&
               offsetof(spmv_c_sptrsv_result, analysis_ms) == offsetof(SpTRSVResult, analysis_ms) &&
               offsetof(spmv_c_sptrsv_result, elapsed_ms) == offsetof(SpTRSVResult, elapsed_ms), "SpTRSVResult layout");
+
+static_assert(sizeof(spmv_c_spgemm_result) == sizeof(SpGEMMResult) && sizeof(SpGEMMResult) == 104, "SpGEMMResult layout");
+static_assert(offsetof(spmv_c_spgemm_result, nnz) == offsetof(SpGEMMResult, nnz) &&
+              offsetof(spmv_c_spgemm_result, products) == offsetof(SpGEMMResult, products) &&
+              offsetof(spmv_c_spgemm_result, max_row_products) == offsetof(SpGEMMResult, max_row_products) &&
+              offsetof(spmv_c_spgemm_result, max_row_nnz) == offsetof(SpGEMMResult, max_row_nnz) &&
+              offsetof(spmv_c_spgemm_result, symbolic_rows) == offsetof(SpGEMMResult, symbolic_rows) &&
+              offsetof(spmv_c_spgemm_result, numeric_rows) == offsetof(SpGEMMResult, numeric_rows) &&
+              offsetof(spmv_c_spgemm_result, lanes) == offsetof(SpGEMMResult, lanes) &&
+              offsetof(spmv_c_spgemm_result, symbolic_ms) == offsetof(SpGEMMResult, symbolic_ms) &&
+              offsetof(spmv_c_spgemm_result, numeric_ms) == offsetof(SpGEMMResult, numeric_ms), "SpGEMMResult layout");
 
 namespace {
 
@@ -552,6 +564,26 @@ int spmv_c_ic0_csr_async(const spmv_c_csr* A, float* d_l_values, void* hip_strea
 int spmv_c_ic0_cpu_csr(const spmv_c_csr* A, float* l_values, int32_t* bad_pivot) {
     return ic0_cpu_csr(cxx(A), l_values, bad_pivot);
 }
+
+int spmv_c_spgemm_csr(spmv_c_csr* C, const spmv_c_csr* A, const spmv_c_csr* B, spmv_c_spgemm_result* out) {
+    SpGEMMResult r;
+    const int status = spgemm_csr(cxx(C), cxx(A), cxx(B), &r);
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return status;
+}
+
+int spmv_c_spgemm_csr_numeric(spmv_c_csr* C, const spmv_c_csr* A, const spmv_c_csr* B, spmv_c_spgemm_result* out) {
+    SpGEMMResult r;
+    const int status = spgemm_csr_numeric(cxx(C), cxx(A), cxx(B), &r);
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return status;
+}
+
+int spmv_c_spgemm_cpu_csr(spmv_c_csr* C, const spmv_c_csr* A, const spmv_c_csr* B) {
+    return spgemm_cpu_csr(cxx(C), cxx(A), cxx(B));
+}
+
+int spmv_c_spgemm_class_capacity(int cls) { return spgemm_class_capacity(cls); }
 
 int spmv_c_sptrsv_csr(const spmv_c_csr* A, const float* d_b, float* d_x, const spmv_c_sptrsv_config* config,
                       spmv_c_sptrsv_result* out) {

@@ -187,6 +187,10 @@ void    ell_aux_drop(const void* key);
 //   sptrsv_lanes=N             lanes per row of sptrsv_csr with ordered = 0 (1, 2, 4, ... 64; anything else is ignored)
 //   ilu0_lanes=N               lanes per row of ilu0_csr (1, 2, 4, ... 64; anything else is ignored)
 //   ic0_lanes=N                lanes per row of ic0_csr (1, 2, 4, ... 64; anything else is ignored)
+//   spgemm_lanes=N             lanes per row of C in spgemm_csr (1, 2, 4, ... 64; anything else is ignored)
+//   spgemm_class=N             accumulator class every row of spgemm_csr takes (1 .. 5); a row too large for it takes
+//                              the first class that holds it
+//   spgemm_dense_groups=G      workgroups (and scratch slices) of spgemm_csr's dense class, instead of the scratch cap
 // Everything else the library reads from the environment is listed in INTEGRATION.md.
 bool debug_option(const char* key, long long* value = nullptr, char* text = nullptr, size_t text_size = 0);
 // the same "key=value,key" syntax for another variable's value (SPMV_MULTI_GPU); `list` may be null
@@ -223,6 +227,15 @@ hipError_t launch_fill_zero(float* d_y, size_t n, hipStream_t s);
 // device transpose (transpose.hip): validates A (INVALID_FORMAT before anything is allocated), then builds A^T on
 // `s` and returns after the build completed, its scratch freed.  The caller owns *out on SUCCESS.
 int transpose_build(const CSRMatrix* A, TransposeArrays* out, hipStream_t s);
+// the scan of transpose.hip for other builders (spgemm.hip): device_scan_levels(n) gives the level sizes n,
+// ceil(n / 4096), ... 1; device_exclusive_scan scans data[0, n) in place on `s`, with `sums` holding the sum of
+// levels[1 ..] ints plus one
+std::vector<long long> device_scan_levels(long long n);
+hipError_t device_exclusive_scan(int* data, const std::vector<long long>& levels, int* sums, hipStream_t s);
+// spgemm_csr's accumulator classes (spgemm.hip, spgemm_host.cpp): classes 1 .. kSpgemmClasses - 1 are LDS hash tables
+// of kSpgemmSlots slots (a power of two; a row may fill half of them), the last class is the dense accumulator
+constexpr int kSpgemmClasses = 5;
+constexpr int kSpgemmSlots[kSpgemmClasses - 1] = {32, 256, 2048, 16384};
 // sparse triangular solve (sptrsv.hip): the launches of one solve, one per group of the schedule, in stream order;
 // kSptrsvNarrowRows is the widest level a single workgroup takes inside a run of levels
 constexpr int kSptrsvNarrowRows = 256;

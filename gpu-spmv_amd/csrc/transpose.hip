@@ -280,6 +280,12 @@ struct Scratch {
 
 } // namespace
 
+std::vector<long long> device_scan_levels(long long n) { return scan_levels(n); }
+
+hipError_t device_exclusive_scan(int* data, const std::vector<long long>& levels, int* sums, hipStream_t s) {
+    return exclusive_scan(data, levels, 0, sums, s);
+}
+
 void TransposeArrays::release() {
     if (row_ptrs) (void)hipFree(row_ptrs);
     if (col_indices) (void)hipFree(col_indices);

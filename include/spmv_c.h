@@ -429,6 +429,33 @@ int spmv_c_ic0_csr_async(const spmv_c_csr* A, float* d_l_values, void* hip_strea
 /* the factorisation on A's host arrays (l_values: nnz floats, may be A's host values); *bad_pivot may be NULL */
 int spmv_c_ic0_cpu_csr(const spmv_c_csr* A, float* l_values, int32_t* bad_pivot);
 
+/* ---- sparse matrix-matrix product C = A*B (extension; include/spmv/spgemm.h) ---- */
+/* 104 bytes */
+typedef struct spmv_c_spgemm_result {
+    int32_t error_code;
+    int32_t nnz;                /* entries of C */
+    int64_t products;           /* sum over A's entries of the length of the B row they point at */
+    int32_t max_row_products;   /* clamped to INT32_MAX */
+    int32_t max_row_nnz;
+    int32_t symbolic_rows[8];   /* rows per accumulator class in the symbolic pass ([0] = rows without products) */
+    int32_t numeric_rows[8];    /* the same for the numeric pass */
+    int32_t lanes;              /* lanes that share one row of C */
+    float   symbolic_ms;
+    float   numeric_ms;
+} spmv_c_spgemm_result;
+
+/* C = A*B of two device matrices, bit-identical to spmv_c_spgemm_cpu_csr; B's columns strictly ascending in every
+ * row.  C owns new device arrays afterwards (as spmv_c_csr_transpose_gpu leaves AT); spmv_c_csr_from_gpu(C) fills its
+ * host arrays.  Checks and arithmetic as spgemm_csr in include/spmv/spgemm.h.  The return value equals
+ * out->error_code (out may be NULL). */
+int spmv_c_spgemm_csr(spmv_c_csr* C, const spmv_c_csr* A, const spmv_c_csr* B, spmv_c_spgemm_result* out);
+/* only C's device values again, into the pattern an earlier spmv_c_spgemm_csr produced; the pattern is checked */
+int spmv_c_spgemm_csr_numeric(spmv_c_csr* C, const spmv_c_csr* A, const spmv_c_csr* B, spmv_c_spgemm_result* out);
+/* the product on host arrays, the definition of the arithmetic; C gets new host arrays */
+int spmv_c_spgemm_cpu_csr(spmv_c_csr* C, const spmv_c_csr* A, const spmv_c_csr* B);
+/* most distinct columns of a row in accumulator class cls (1-based); INT32_MAX for the dense class, -1 past it */
+int spmv_c_spgemm_class_capacity(int cls);
+
 /* ---- bandwidth model: reference include/spmv/bandwidth.h:21-27 ---- */
 int spmv_c_compute_bandwidth_csr(const spmv_c_csr* A, float elapsed_ms, spmv_c_bandwidth* out);
 int spmv_c_compute_bandwidth_ell(const spmv_c_ell* A, float elapsed_ms, spmv_c_bandwidth* out);
