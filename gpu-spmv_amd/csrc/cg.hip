@@ -120,7 +120,7 @@ void cg_start_kernel(const double* __restrict__ part, int count, float tolerance
     double rz = 0.0, rr = 0.0, bb = 0.0;
     fold_partials(part, count, 3, rz, rr);
     double unused = 0.0;
-    fold_partials(part + 2, count, 3, bb, unused);
+    fold_partials(part + 2, count, 3, bb, unused, false);    // part[3 * count] is past the end: b.b alone
     if (threadIdx.x != 0) return;
     const double bnorm = sqrt(bb);
     const double res = sqrt(rr);

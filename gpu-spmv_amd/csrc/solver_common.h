@@ -21,16 +21,18 @@ using dev::kMaxResidentBlocks;
 
 constexpr int kVecBlocks = 1024;      // workgroups of the element-wise kernels (4 per CU)
 
-// Sums part[i * stride] (and part[i * stride + 1] when stride > 1) over i < count in a fixed order, broadcast to
-// every thread: each thread folds a fixed strided subset, then block_sum2's fixed butterfly and wave order.
+// Sums part[i * stride] (and part[i * stride + 1] when stride > 1 and `pair`) over i < count in a fixed order,
+// broadcast to every thread: each thread folds a fixed strided subset, then block_sum2's fixed butterfly and wave
+// order.  pair = false reads nothing but part[i * stride] (b comes back 0): for a single value per group whose
+// neighbour may lie past the end of the array.
 __device__ __forceinline__ void fold_partials(const double* __restrict__ part, int count, int stride,
-                                              double& a, double& b) {
+                                              double& a, double& b, bool pair = true) {
     __shared__ double s_fold[2];
     a = 0.0;
     b = 0.0;
     for (int i = threadIdx.x; i < count; i += kBlock) {
         a += part[static_cast<long long>(i) * stride];
-        if (stride > 1) b += part[static_cast<long long>(i) * stride + 1];
+        if (stride > 1 && pair) b += part[static_cast<long long>(i) * stride + 1];
     }
     dev::block_sum2(a, b);
     if (threadIdx.x == 0) {

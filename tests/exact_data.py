@@ -1006,3 +1006,240 @@ def gmres_tiled_step_system(W):
     """(n, rp, ci, va, b): the non-symmetric system of entry_point_systems(W) with the +-1 / 0 right-hand side."""
     n, rp, ci, va = entry_point_systems(W)[1]
     return n, rp, ci, va, pm_one_rhs(n, GMRES_TILED_STEP_K, 1400 + W)
+
+
+# ------------------------------------------------------------------------------------------ two-eigenvalue systems
+# cg_solve / bicgstab_solve held to the bit to their LAST step, past the grid caps of csrc/solver_common.h
+# (tests/test_gpu_solver_trips.py).  The rows fall into two sets S1 and S2, dealt by a fixed pseudo-random permutation;
+# off-diagonal entries are integers and connect rows of one set only; every diagonal entry is d = 2^14; the
+# off-diagonal row sums are prescribed, so the vector that is constant on a set and zero elsewhere is an eigenvector.
+# b is constant on each set: a sum of two eigenvectors, and both Krylov methods end after two steps with r == 0.
+#   CG        symmetric, row sums d/4 on S1 and d on S2, |b1|^2 == 2 |b2|^2:
+#             alpha = 2/d, 2/d and beta = 1/2 (NONE); alpha = 2, 2 and beta = 1/2 (JACOBI, z = r / d)
+#   BiCGSTAB  non-symmetric, row sums d/4 on S1 and -d/4 on S2, |b1|^2 == 3 |b2|^2:
+#             alpha = 8/d, omega = -2/d, beta = 3, alpha = -2/d (NONE; times d with JACOBI), s == 0 at the half step
+# A set's rows are cut into groups of g rows; inside a group, row q holds c_k at the rows q + k (and q - k when
+# symmetric) mod g for k = 1..t, with t and g drawn per group (ragged rows) and sum_k c_k the prescribed value.  A +-1
+# similarity A' = S A S, b' = S b varies the signs.  The scaled variant A' = T A T, b' = T b, T a power of two per row,
+# has the diagonal d T^2: JACOBI's dinv then differs from row to row, and diag(sqrt(d) T) is an exact IC factor, diag(d T^2)
+# an exact U (L = I).  CG's r.z and p.q do not see T; BiCGSTAB's dot products do, so there T is 2 on exactly three
+# times as many rows of S1 as of S2, and the weights T^2 b^2 keep the ratio 3.
+# n is padded with diagonal-only rows: for CG up to two rows of S2 with b = +-3 (n = 3 n2 + 19 f, f = n mod 3), for
+# BiCGSTAB up to three rows with b = 0 (a diagonal-only row has the eigenvalue 1 under JACOBI, which no set shares).
+# tests/test_exact_data.py runs cg.h's and bicgstab.h's algorithms in integers on every system and asserts each claim.
+VEC_TRIP = 1024 * 256                        # kVecBlocks * kBlock: elements per trip of the element-wise kernels
+ROW_TRIP_THREADS = 2048 * 256                # kMaxResidentBlocks * kBlock: a row kernel's trip is this / L rows
+TWO_EIG_D = 1 << 14                          # the common diagonal; lambda = d / 4
+
+
+def row_trip(L):
+    return ROW_TRIP_THREADS // L
+
+
+TRIP_SIZES = [257, 1201, VEC_TRIP, VEC_TRIP + 1, VEC_TRIP + 257, 2 * VEC_TRIP + 3, row_trip(1) + 257]
+LANE_SIZES = {L: row_trip(L) + 256 // L + 1 for L in LANES[1:]}
+TILED_TRIP_SIZE = VEC_TRIP + 257
+
+
+def _circulant_rows(rng, members, t_choices, target, symmetric):
+    """(rows, cols, vals) of one set's off-diagonal entries: `members` cut into groups, each with its own t (entries
+    per direction) and g >= 2 t + 1 (t + 1 when not symmetric) rows, so that a row's columns are distinct; the weights
+    c_1..c_t of a group are non-zero integers, +-1..3 but for the last, which brings their sum to `target` (half of it
+    per direction when symmetric).  t == 0: rows without off-diagonal entries (target 0 only)."""
+    m = members.size
+    empty = np.zeros(0, np.int64)
+    if m == 0:
+        return empty, empty, empty
+    per = target // 2 if symmetric else target
+    assert not symmetric or target % 2 == 0
+    need = lambda t: np.where(t == 0, 1, 2 * t + 1 if symmetric else t + 1)
+    count = m // int(need(np.array(min(t_choices)))) + 1
+    t = rng.choice(np.asarray(t_choices, np.int64), size=count)
+    g = need(t) + rng.integers(0, 4, size=count)
+    ends = np.cumsum(g)
+    k = int(np.searchsorted(ends, m, side="right"))
+    assert k >= 1, "the set is smaller than one group"
+    t, g = t[:k].copy(), g[:k].copy()
+    g[-1] += m - int(ends[k - 1])                                    # the last group takes the rest
+    start = np.cumsum(g) - g
+    grp = np.repeat(np.arange(k), g)
+    q = np.arange(m) - start[grp]
+    wstart = np.cumsum(t) - t
+    total = int(t.sum())
+    if total == 0:
+        assert per == 0
+        return empty, empty, empty
+    w = rng.integers(1, 4, size=total) * rng.choice([-1, 1], size=total)
+    has = t > 0
+    assert per == 0 or has.all()
+    last = (wstart + t - 1)[has]
+    w[last] = 0
+    w[last] = per - np.add.reduceat(w, wstart[has])
+    zero = w[last] == 0
+    if zero.any():                                                   # move the first weight by 1 (2 from -1): no zero weight
+        assert np.all(t[has][zero] >= 2)
+        first = wstart[has][zero]
+        moved = np.where(w[first] == -1, 1, w[first] + 1)
+        w[last[zero]] = w[first] - moved
+        w[first] = moved
+    assert np.all(w != 0) and np.array_equal(np.add.reduceat(w, wstart[has]), np.full(int(has.sum()), per))
+    tr = t[grp]
+    pos = np.repeat(np.arange(m), tr)
+    kk = np.arange(pos.size) - np.repeat(np.cumsum(tr) - tr, tr) + 1          # 1..t within a row
+    gg, st, qq = g[grp][pos], start[grp][pos], q[pos]
+    wt = w[wstart[grp][pos] + kk - 1]
+    rows, cols = members[pos], members[st + (qq + kk) % gg]
+    if not symmetric:
+        return rows, cols, wt
+    return np.concatenate([rows, rows]), np.concatenate([cols, members[st + (qq - kk) % gg]]), np.concatenate([wt, wt])
+
+
+def two_eig_lengths(solver, L):
+    """(t choices of S1, of S2) that put the average row length inside L's range of the lane rule."""
+    if solver == "cg":                                               # a row holds 2 t + 1 entries
+        if L == 1:
+            return [1], [0, 2, 2, 2, 3]
+        both = list(range(66, 91)) if L == 64 else list(range(L, 2 * L))
+        return both, both
+    if L == 1:                                                       # a row holds t + 1 entries
+        return [1, 2, 3], [1, 2, 3]
+    both = list(range(130, 181)) if L == 64 else list(range(2 * L, 4 * L - 1))
+    return both, both
+
+
+def two_eig_sets(solver, n):
+    """(rows of S1, rows of S2, diagonal-only rows, their |b|) that meet the weight condition at this n."""
+    if solver == "cg":
+        f = n % 3
+        n2 = (n - 19 * f) // 3
+        n1 = 2 * (n2 + 9 * f)
+        fill_b = 3
+    else:
+        f = n % 4
+        n2 = n // 4
+        n1 = 3 * n2
+        fill_b = 0
+    assert n1 > 0 and n2 > 0 and n1 + n2 + f == n
+    return n1, n2, f, fill_b
+
+
+_two_eig_cache = {}
+
+
+def _two_eig_structure(solver, n, L):
+    """What the scaled and the unscaled system of one (solver, n, L) share; the last two are kept."""
+    key = (solver, n, L)
+    if key in _two_eig_cache:
+        return _two_eig_cache[key]
+    symmetric = solver == "cg"
+    d = TWO_EIG_D
+    rng = np.random.default_rng([n, L, int(symmetric)])
+    n1, n2, f, fill_b = two_eig_sets(solver, n)
+    perm = rng.permutation(n)
+    for row, slot in ((n - 1, 0), (n - 2, n1)):                      # the last row in S1, the one before it in S2: a last
+        at = int(np.flatnonzero(perm == row)[0])                     # trip of two rows or more still holds both sets
+        perm[at], perm[slot] = perm[slot], perm[at]
+    S1, S2 = perm[:n1], perm[n1:n1 + n2]
+    sets = np.zeros(n, np.int64)
+    sets[S1], sets[S2] = 1, 2
+    t1, t2 = two_eig_lengths(solver, L)
+    r1, c1, v1 = _circulant_rows(rng, S1, t1, -3 * d // 4, symmetric)
+    r2, c2, v2 = _circulant_rows(rng, S2, t2, 0 if symmetric else -5 * d // 4, symmetric)
+    idx = np.arange(n)
+    rows, cols = np.concatenate([r1, r2, idx]), np.concatenate([c1, c2, idx])
+    vals = np.concatenate([v1, v2, np.full(n, d, np.int64)])
+    order = np.lexsort((rng.random(rows.size), rows))                # storage order inside a row is drawn
+    rows, cols, vals = rows[order], cols[order], vals[order]
+    sign = rng.choice([-1, 1], size=n)
+    vals = vals * sign[rows] * sign[cols]
+    if symmetric:
+        e = rng.integers(-1, 3, size=n)
+    else:
+        e, k1 = np.zeros(n, np.int64), n2 // 2
+        e[S1[:3 * k1]] = 1
+        e[S2[:k1]] = 1
+    rp = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=n))]).astype(np.int32)
+    assert lanes_for(int(rp[-1]), n) == L, (solver, n, L, int(rp[-1]) / n)
+    b_u = np.where(sets == 0, fill_b, 1).astype(np.float64) * sign + 0.0       # + 0.0: a zero entry is +0
+    while len(_two_eig_cache) >= 2:
+        _two_eig_cache.pop(next(iter(_two_eig_cache)))
+    _two_eig_cache[key] = (rp, rows, cols.astype(np.int32), vals, sets, e, b_u)
+    return _two_eig_cache[key]
+
+
+def two_eig_system(solver, n, L, scaled):
+    """dict(n, L, rp, ci, va, b, x1, x2, rel1, sets, e, diag, symmetric): the system above for solver "cg" or "bicgstab";
+    x1 / x2 the iterates after one and two steps from x0 = 0 (x2 == A^-1 b), rel1 = ||r1|| / ||b|| rounded to float32
+    from fp64, sets[i] = 1, 2 (0: a diagonal-only row), e the exponents of T (zeros when not scaled), diag the stored
+    diagonal d T^2."""
+    symmetric = solver == "cg"
+    rp, rows, ci, vals, sets, e, b_u = _two_eig_structure(solver, n, L)
+    d, lam = TWO_EIG_D, TWO_EIG_D / 4
+    if scaled:
+        va = np.ldexp(vals.astype(np.float64), e[rows] + e[ci]).astype(np.float32)
+    else:
+        va, e = vals.astype(np.float32), np.zeros(n, np.int64)
+    T = np.ldexp(1.0, e)
+    in1 = sets == 1
+    if symmetric:
+        x1_u, x2_u = b_u / (2 * lam), np.where(in1, b_u / lam, b_u / (4 * lam))
+        res_u = np.where(in1, b_u / 2, -b_u)
+    else:
+        x1_u, x2_u = np.where(in1, 2.5, 0.5) * b_u / lam, np.where(in1, 1.0, -1.0) * b_u / lam
+        res_u = np.where(in1, -1.5, 1.5) * b_u
+    x1_u, x2_u = x1_u + 0.0, x2_u + 0.0                              # -0 -> +0: the solvers never produce a -0 from b = +0
+    b64, res = b_u * T, res_u * T
+    rel1 = np.float32(np.sqrt(np.sum(res * res)) / np.sqrt(np.sum(b64 * b64)))
+    return dict(solver=solver, n=n, L=L, scaled=bool(scaled), symmetric=symmetric, rp=rp, ci=ci, va=va,
+                b=b64.astype(np.float32), x1=(x1_u / T).astype(np.float32), x2=(x2_u / T).astype(np.float32), rel1=rel1,
+                sets=sets, e=e, diag=np.ldexp(float(d), 2 * e).astype(np.float32))
+
+
+def diagonal_csr(values):
+    """(row_ptrs, cols, vals) of diag(values): the IC factor diag(sqrt(A_ii)) and the LU factor (L = I, U = diag(A_ii))."""
+    n = len(values)
+    return np.arange(n + 1, dtype=np.int32), np.arange(n, dtype=np.int32), np.asarray(values, np.float32)
+
+
+def init_solution(system):
+    """(x*, b = A x*) for the exact init test on an UNSCALED system: x* integers in [-8, 8]."""
+    assert not system["scaled"]
+    x_star = np.random.default_rng(system["n"]).integers(-8, 9, size=system["n"]).astype(np.float32)
+    check_exact(system["rp"], system["ci"], system["va"], x_star)
+    return x_star, exact_reference(system["rp"], system["ci"], system["va"], x_star)
+
+
+# ------------------------------------------------------------------------------------------ two wide levels
+# sptrsv_kernel<L, ORDERED> past its grid cap: a triangular integer system of exactly two levels, each wider than the
+# row_trip(L) rows one trip of 2048 workgroups takes.  Half the rows hold their diagonal entry only; every row of the
+# other half holds 1..2 L + 2 entries at random rows of the first half, so a row of either trip reads x of both.
+SPTRSV_TRIP_LANES = (1, 8)
+
+
+def two_level_triangle(L, uplo, unit):
+    """dict(n, rp, ci, va, b, x): n = 2 row_trip(L) + 2 (256 / L) + 2; values +-1..8, the diagonal a power of two
+    (the stored 3 that a UNIT solve ignores), x integers in [-100, 100], b = T x in integers."""
+    half = row_trip(L) + 256 // L + 1
+    n = 2 * half
+    rng = np.random.default_rng([L, uplo, unit])
+    lens = rng.integers(1, 2 * L + 3, size=half)
+    rows = np.repeat(np.arange(half, n), lens)
+    cols = rng.integers(0, half, size=rows.size)
+    vals = rng.integers(1, 9, size=rows.size) * rng.choice([-1, 1], size=rows.size)
+    keys = np.unique(rows * n + cols, return_index=True)[1]          # distinct columns inside a row
+    rows, cols, vals = rows[keys], cols[keys], vals[keys]
+    diag = np.full(n, 3, np.int64) if unit else 1 << rng.integers(0, 4, size=n)
+    idx = np.arange(n)
+    rows, cols, vals = np.concatenate([rows, idx]), np.concatenate([cols, idx]), np.concatenate([vals, diag])
+    x = rng.integers(-100, 101, size=n)
+    if uplo == 1:                                                    # mirror: row i -> n - 1 - i
+        rows, cols, x = n - 1 - rows, n - 1 - cols, x[::-1].copy()
+    order = np.lexsort((rng.random(rows.size), rows))
+    rows, cols, vals = rows[order], cols[order], vals[order]
+    eff = np.where((rows == cols) & bool(unit), 1, vals)
+    prod = eff * x[cols]
+    b = np.bincount(rows, weights=prod.astype(np.float64), minlength=n).astype(np.int64)
+    assert int(np.bincount(rows, weights=np.abs(prod).astype(np.float64), minlength=n).max()) < EXACT_LIMIT
+    rp = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=n))]).astype(np.int32)
+    return dict(n=n, half=half, L=L, uplo=uplo, unit=unit, rp=rp, ci=cols.astype(np.int32), va=vals.astype(np.float32),
+                b=b.astype(np.float32), x=x.astype(np.float32))

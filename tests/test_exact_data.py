@@ -724,3 +724,313 @@ def test_gmres_first_tiled_step_system_is_exact(spmv, monkeypatch, W, R):
     monkeypatch.setenv("SPMV_DEBUG", ed.tiled_debug(W, R))
     assert spmv.tiled_shape(n, n, int(rp[-1])) == (True, W, R)
     assert int(np.diff(rp).max()) <= ed.default_long_row(-(-n // W))
+
+
+# ------------------------------------------------------------------------------------------ two-eigenvalue systems
+# cg.h's and bicgstab.h's algorithms in exact arithmetic: a vector is (int64 numerators, e) standing for num * 2^-e, a
+# scalar a Fraction.  Every operation asserts what makes its fp32 / fp64 counterpart on the device exact.
+from fractions import Fraction
+
+
+def dy(num, e):
+    """Normal form: the common trailing zero bits of the numerators moved into the exponent."""
+    num = np.asarray(num, np.int64)
+    low = int(np.bitwise_or.reduce(num)) if num.size else 0
+    if low == 0:
+        return np.zeros_like(num), 0
+    shift = (low & -low).bit_length() - 1
+    return num >> shift, e - shift
+
+
+def dy_from(values):
+    """A float array as a dyadic vector (every value a multiple of 2^-40 below 2^22: asserted)."""
+    scaled = np.asarray(values, np.float64) * 2.0 ** 40
+    assert np.array_equal(scaled, np.rint(scaled)) and np.abs(scaled).max(initial=0.0) < 2.0 ** 62
+    return dy(scaled.astype(np.int64), 40)
+
+
+def dy_float32(v):
+    assert ed._fits_float32(v[0]), "an entry does not fit fp32's 24 bits"
+    return np.ldexp(v[0].astype(np.float64), -v[1]).astype(np.float32)
+
+
+def dy_frac(value, e):
+    return Fraction(int(value), 1 << e) if e >= 0 else Fraction(int(value) << -e)
+
+
+def dy_add(a, b):
+    e = max(a[1], b[1])
+    assert max(e - a[1], e - b[1]) < 40
+    return dy((a[0] << (e - a[1])) + (b[0] << (e - b[1])), e)
+
+
+def dyadic32(f):
+    """A Fraction that fp32 holds: a power-of-two denominator, at most 24 significant bits."""
+    den = f.denominator
+    assert den & (den - 1) == 0, f
+    num = abs(f.numerator)
+    assert num != 0 and (num >> ((num & -num).bit_length() - 1)) < 1 << 24, f
+    return f
+
+
+def dy_scale(f, v):
+    """f * v for a dyadic scalar."""
+    den = f.denominator
+    assert den & (den - 1) == 0
+    assert abs(f.numerator) * int(np.abs(v[0]).max(initial=0)) < 1 << 62
+    return dy(v[0] * f.numerator, v[1] + den.bit_length() - 1)
+
+
+def dy_shift(v, k):
+    """v[i] * 2^-k[i]: a multiplication by a power of two per row (dinv, or the diagonal factors' divisions)."""
+    top = int(k.max())
+    return dy(v[0] << (top - k), v[1] + top)
+
+
+def dy_dot(a, b):
+    """a.b as a Fraction; the sum of |terms| stays below 2^53 units: every partial sum is exact in fp64, any order."""
+    bound = float(np.abs(a[0]).max(initial=0)) * float(np.abs(b[0]).max(initial=0)) * max(a[0].size, 1)
+    assert bound < 2.0 ** 53, bound
+    return dy_frac(int(np.dot(a[0], b[0])), a[1] + b[1])
+
+
+def dy_spmv(matrix, x):
+    """A x; per row the products are multiples of one quantum and their absolute sum is below 2^24 quanta, so every
+    partial sum of the row, fused or not, in any order, is exact in fp32."""
+    rp, ci, (num, e) = matrix
+    prod = num * x[0][ci]
+    assert float(np.abs(num).max()) * float(np.abs(x[0]).max(initial=0)) < 2.0 ** 62
+    starts = rp[:-1].astype(np.int64)
+    assert np.all(np.diff(rp) > 0)                                   # every row stores its diagonal
+    any_bit = np.bitwise_or.reduceat(np.abs(prod), starts)
+    quantum = any_bit & -any_bit
+    assert np.all((np.add.reduceat(np.abs(prod), starts) >> 24) < quantum + (any_bit == 0))
+    return dy(np.add.reduceat(prod, starts), e + x[1])
+
+
+def two_eig_matrix(s):
+    return s["rp"], s["ci"].astype(np.int64), dy_from(s["va"])
+
+
+def dinv_shift(s):
+    """k with dinv[i] = 2^-k[i], or None without a preconditioner: the stored diagonal is a power of two."""
+    if not s["scaled"]:
+        return None
+    mant, expo = np.frexp(s["diag"])
+    assert np.all(mant == 0.5)
+    return (expo - 1).astype(np.int64)
+
+
+def prove_cg(s, k):
+    """cg.h from x0 = 0 in exact arithmetic; returns (x per step as float32, ||r|| / ||b|| per step, alphas, betas)."""
+    A = two_eig_matrix(s)
+    pre = (lambda v: v) if k is None else (lambda v: dy_shift(v, k))
+    b = dy_from(s["b"])
+    r = b
+    z = pre(r)
+    dy_float32(z)
+    p, x = z, (np.zeros(s["n"], np.int64), 0)
+    rz, bb = dy_dot(r, z), dy_dot(b, b)
+    assert rz > 0
+    xs, rels, alphas, betas = [], [], [], []
+    for step in range(4):
+        q = dy_spmv(A, p)
+        dy_float32(q)
+        pq = dy_dot(p, q)
+        assert pq > 0
+        alpha = dyadic32(rz / pq)
+        x = dy_add(x, dy_scale(alpha, p))
+        r = dy_add(r, dy_scale(-alpha, q))
+        z = pre(r)
+        xs.append(dy_float32(x)), dy_float32(r), dy_float32(z)
+        rz_new, rr = dy_dot(r, z), dy_dot(r, r)
+        alphas.append(alpha), rels.append(math.sqrt(rr / bb))
+        if rr == 0:
+            break
+        assert rz_new > 0
+        beta = dyadic32(rz_new / rz)
+        betas.append(beta)
+        p = dy_add(z, dy_scale(beta, p))
+        dy_float32(p)
+        rz = rz_new
+    return xs, rels, alphas, betas
+
+
+def prove_bicgstab(s, k):
+    """bicgstab.h from x0 = 0 in exact arithmetic; returns (x per step as float32, residual per step, the scalars)."""
+    A = two_eig_matrix(s)
+    pre = (lambda v: v) if k is None else (lambda v: dy_shift(v, k))
+    b = dy_from(s["b"])
+    r = rhat = p = b
+    x = (np.zeros(s["n"], np.int64), 0)
+    rho, bb = dy_dot(r, r), dy_dot(b, b)
+    xs, rels, scalars = [], [], []
+    for step in range(4):
+        ph = pre(p)
+        v = dy_spmv(A, ph)
+        dy_float32(ph), dy_float32(v)
+        rv = dy_dot(rhat, v)
+        assert rv != 0
+        alpha = dyadic32(rho / rv)
+        sv = dy_add(r, dy_scale(-alpha, v))
+        sh = pre(sv)
+        dy_float32(sv), dy_float32(sh)
+        ss = dy_dot(sv, sv)
+        half = dy_add(x, dy_scale(alpha, ph))                        # the inner multiply-add of the x update
+        dy_float32(half)
+        if ss == 0:
+            xs.append(dy_float32(half)), rels.append(0.0), scalars.append((alpha,))
+            break
+        t = dy_spmv(A, sh)
+        dy_float32(t)
+        omega = dyadic32(dy_dot(t, sv) / dy_dot(t, t))
+        x = dy_add(half, dy_scale(omega, sh))
+        r = dy_add(sv, dy_scale(-omega, t))
+        xs.append(dy_float32(x)), dy_float32(r)
+        rr, rho_new = dy_dot(r, r), dy_dot(rhat, r)
+        rels.append(math.sqrt(rr / bb))
+        assert rr != 0 and rho_new != 0
+        dyadic32(rho_new / rho), dyadic32(alpha / omega)             # both fp64 quotients of beta are exact
+        beta = dyadic32((rho_new / rho) * (alpha / omega))
+        scalars.append((alpha, omega, beta))
+        inner = dy_add(p, dy_scale(-omega, v))
+        dy_float32(inner)
+        p = dy_add(r, dy_scale(beta, inner))
+        dy_float32(p)
+        rho = rho_new
+    return xs, rels, scalars
+
+
+def assert_two_eig_structure(s):
+    """Sets, symmetry, dominance, raggedness, the lane count and what the grid-stride trips see, on the UNSCALED
+    system (the scaled one is T A T entry by entry: asserted by the caller)."""
+    assert not s["scaled"]
+    n, L, rp, ci = s["n"], s["L"], s["rp"], s["ci"]
+    rows = np.repeat(np.arange(n), np.diff(rp))
+    vals = s["va"].astype(np.float64)
+    assert ed.lanes_for(int(rp[-1]), n) == L
+    assert np.unique(np.diff(rp)).size >= 3                                       # ragged
+    assert np.array_equal(s["sets"][rows], s["sets"][ci]) and np.count_nonzero(s["sets"] == 0) <= 3
+    assert np.unique(rows.astype(np.int64) * n + ci).size == ci.size              # no (row, column) twice
+    on = rows == ci
+    assert np.count_nonzero(on) == n and np.array_equal(vals[on], s["diag"][rows[on]].astype(np.float64))
+    key = rows.astype(np.int64) * n + ci
+    forward, backward = np.argsort(key), np.argsort(ci.astype(np.int64) * n + rows)
+    mirrored = np.array_equal(key[forward], (ci.astype(np.int64) * n + rows)[backward])
+    if s["symmetric"]:
+        assert mirrored and np.array_equal(vals[forward], vals[backward])
+        off = np.bincount(rows[~on], weights=np.abs(vals[~on]), minlength=n)
+        assert np.all(off < ed.TWO_EIG_D)                                         # strictly diagonally dominant: SPD
+    else:
+        assert not mirrored                                                       # not even the pattern is symmetric
+    for trip in {ed.VEC_TRIP, ed.row_trip(L)}:
+        if n > trip:
+            trips = -(-n // trip)
+            for t in range(trips):                                                # (a last trip of ONE row holds one set)
+                want = {1, 2} if min(n, (t + 1) * trip) - t * trip >= 2 else {1}
+                assert set(np.unique(s["sets"][t * trip:(t + 1) * trip])) >= want, (trip, t)
+            assert np.count_nonzero((rows // trip != ci // trip) & ~on) > 0
+            other = np.unique(rows[(rows // trip) != (ci // trip)] // trip)
+            assert other.size == trips                                            # rows of every trip read another trip
+
+
+TWO_EIG_CASES = [(solver, n, L) for solver in ("cg", "bicgstab")
+                 for n, L in [(n, 1) for n in ed.TRIP_SIZES] + [(ed.LANE_SIZES[L], L) for L in ed.LANES[1:]]]
+
+
+@pytest.mark.parametrize("solver,n,L", TWO_EIG_CASES)
+def test_two_eig_system_is_exact_to_its_last_step(solver, n, L):
+    """Every system tests/test_gpu_solver_trips.py runs, unscaled (NONE) and scaled (JACOBI, IC, LU): the documented
+    algorithm in integers ends at step 2 with r == 0, every stored vector fits fp32, every row sum and dot product is
+    exact in any order, alpha / beta / omega are dyadic, and x1, x2 and the one-step residual are the builder's."""
+    for scaled in (False, True):
+        s = ed.two_eig_system(solver, n, L, scaled)
+        if not scaled:
+            assert_two_eig_structure(s)
+            plain = s
+        else:                                                                      # A' = T A T, b' = T b, same pattern
+            rows = np.repeat(np.arange(n), np.diff(s["rp"]))
+            assert np.array_equal(s["ci"], plain["ci"]) and np.unique(s["e"]).size >= 2
+            assert np.array_equal(s["va"], np.ldexp(plain["va"], s["e"][rows] + s["e"][s["ci"]]))
+            assert np.array_equal(s["b"], np.ldexp(plain["b"], s["e"]))
+            assert np.array_equal(s["diag"], np.ldexp(np.float32(ed.TWO_EIG_D), 2 * s["e"]))
+        k = dinv_shift(s)
+        if solver == "cg":
+            xs, rels, alphas, betas = prove_cg(s, k)
+            top = Fraction(2) if scaled else Fraction(2, ed.TWO_EIG_D)
+            assert alphas == [top, top] and betas == [Fraction(1, 2)]
+        else:
+            xs, rels, scalars = prove_bicgstab(s, k)
+            unit = Fraction(1) if scaled else Fraction(1, ed.TWO_EIG_D)
+            assert scalars == [(8 * unit, -2 * unit, Fraction(3)), (-2 * unit,)]
+        assert len(xs) == 2 and rels[1] == 0.0 and rels[0] > 1e-3                  # no early stop at tolerance 1e-6
+        assert np.array_equal(bits(xs[0]), bits(s["x1"])) and np.array_equal(bits(xs[1]), bits(s["x2"]))
+        got, want = np.float32(rels[0]), s["rel1"]
+        assert abs(int(got.view(np.int32)) - int(want.view(np.int32))) <= 1        # two roundings apart at most
+        if scaled:                                                                 # the diagonal factors of IC and LU
+            root = np.sqrt(s["diag"])
+            assert np.array_equal(root * root, s["diag"]) and np.all(np.frexp(root)[0] == 0.5)
+
+
+@pytest.mark.parametrize("solver", ["cg", "bicgstab"])
+@pytest.mark.parametrize("n", [257, 1201])
+def test_two_eig_prediction_is_the_restatement_bit_for_bit(solver, n):
+    """test_gpu_cg.restate / test_gpu_bicgstab.restate in plain floating point give the predicted x, counts and flags:
+    the prediction is tied to the documented algorithm, not to a second derivation."""
+    restate = importlib.import_module("test_gpu_cg" if solver == "cg" else "test_gpu_bicgstab").restate
+    for scaled in (False, True):
+        s = ed.two_eig_system(solver, n, 1, scaled)
+        args = (n, s["rp"], s["ci"], s["va"], s["b"], np.zeros(n, np.float32))
+        x, it, conv, brk, rel = restate(*args, 1e-6, 50, int(scaled))
+        assert (it, bool(conv), int(brk), float(rel)) == (2, True, 0, 0.0)
+        assert np.array_equal(bits(x), bits(s["x2"]))
+        x, it, conv, brk, rel = restate(*args, 0.0, 1, int(scaled))
+        assert (it, bool(conv), int(brk)) == (1, False, 0) and np.float32(rel) == s["rel1"]
+        assert np.array_equal(bits(x), bits(s["x1"]))
+
+
+@pytest.mark.parametrize("L", ed.LANES[1:])
+def test_init_solution_is_exact_at_the_lane_sweep_sizes(L):
+    for solver in ("cg", "bicgstab"):
+        s = ed.two_eig_system(solver, ed.LANE_SIZES[L], L, scaled=False)
+        x_star, b = ed.init_solution(s)                                            # check_exact inside
+        assert s["n"] > ed.row_trip(L) and np.count_nonzero(b) > 0.9 * s["n"]
+
+
+def test_trip_sizes_reach_the_edges_they_name():
+    V, sizes = ed.VEC_TRIP, ed.TRIP_SIZES
+    assert V == 262144 and ed.row_trip(1) == 524288
+    assert sizes[:2] == [257, 1201] and sizes[2:] == [V, V + 1, V + 257, 2 * V + 3, ed.row_trip(1) + 257]
+    assert sum(n > 2 * V for n in sizes) == 2                                      # a third element-wise trip twice
+    for L, n in ed.LANE_SIZES.items():
+        assert n == ed.row_trip(L) + 256 // L + 1                                  # one full workgroup and one row more
+
+
+@pytest.mark.parametrize("L", ed.SPTRSV_TRIP_LANES)
+def test_two_level_triangle_has_two_wide_levels_and_an_integer_solution(spmv, L):
+    for uplo in (0, 1):
+        for unit in (0, 1):
+            c = ed.two_level_triangle(L, uplo, unit)
+            n, rp, ci, half = c["n"], c["rp"], c["ci"], c["half"]
+            assert n == 2 * ed.row_trip(L) + 2 * (256 // L) + 2 and half > ed.row_trip(L)
+            _, level_ptr, order, levels, _ = spmv.sptrsv_levels(n, rp, ci, uplo)
+            assert levels == 2 and list(np.diff(level_ptr)) == [half, half]
+            rows = np.repeat(np.arange(n), np.diff(rp))
+            inside = (ci < rows) if uplo == 0 else (ci > rows)
+            assert np.all((ci == rows) | inside)                                   # nothing in the other triangle
+            on = ci == rows
+            d = np.ones(n) if unit else c["va"][on][np.argsort(rows[on])].astype(np.float64)
+            assert np.all(np.frexp(d)[0] == 0.5)                                   # powers of two
+            eff = np.where(on & bool(unit), 1.0, c["va"].astype(np.float64))
+            x = c["x"].astype(np.float64)
+            assert np.array_equal(np.bincount(rows, weights=eff * x[ci], minlength=n), c["b"].astype(np.float64))
+            assert np.bincount(rows, weights=np.abs(eff * x[ci]), minlength=n).max() < ed.EXACT_LIMIT
+            # position k of the second level lies in trip k // R_L; its columns lie in both trips of the first level
+            second = np.asarray(order)[half:]
+            place = np.empty(n, np.int64)
+            place[np.asarray(order)[:half]] = np.arange(half)
+            trip_of_row = np.empty(n, np.int64)
+            trip_of_row[second] = np.arange(half) // ed.row_trip(L)
+            dep = inside
+            assert np.count_nonzero(trip_of_row[rows[dep]] != place[ci[dep]] // ed.row_trip(L)) > 0
+            assert np.unique(np.diff(rp)).size >= 3
