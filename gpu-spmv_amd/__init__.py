@@ -215,6 +215,23 @@ class SpGEMMResult(Structure):
                 ("lanes", c_int32), ("symbolic_ms", c_float), ("numeric_ms", c_float)]
 
 
+class AMGConfig(Structure):
+    """include/spmv/amg.h AMGConfig (28 bytes), with its defaults"""
+    _fields_ = [("max_levels", c_int32), ("coarse_rows", c_int32), ("strength", c_float), ("pre_sweeps", c_int32),
+                ("post_sweeps", c_int32), ("jacobi_weight", c_float), ("coarse_sweeps", c_int32)]
+
+    def __init__(self, max_levels=10, coarse_rows=64, strength=0.08, pre_sweeps=1, post_sweeps=1,
+                 jacobi_weight=2.0 / 3.0, coarse_sweeps=4):
+        super().__init__(max_levels, coarse_rows, strength, pre_sweeps, post_sweeps, jacobi_weight, coarse_sweeps)
+
+
+class AMGResult(Structure):
+    """include/spmv/amg.h AMGResult (48 bytes); bad_level / bad_row name the row a diagonal or pivot check failed at"""
+    _fields_ = [("error_code", c_int32), ("levels", c_int32), ("coarse_solver", c_int32), ("bad_row", c_int32),
+                ("bad_level", c_int32), ("grid_complexity", c_double), ("operator_complexity", c_double),
+                ("setup_ms", c_float)]
+
+
 class PageRankResult:
     """reference include/spmv/pagerank.h:18-25; `ranks` is a numpy copy (the C buffer is freed)."""
 
@@ -327,6 +344,16 @@ _SIGNATURES = {
                                           POINTER(SpGEMMResult)]),
     "spmv_c_spgemm_cpu_csr": (c_int, [POINTER(CSRMatrix), POINTER(CSRMatrix), POINTER(CSRMatrix)]),
     "spmv_c_spgemm_class_capacity": (c_int, [c_int]),
+    "spmv_c_amg_setup": (c_int, [POINTER(c_void_p), POINTER(CSRMatrix), POINTER(AMGConfig), c_int,
+                                 POINTER(c_void_p), POINTER(AMGResult)]),
+    "spmv_c_amg_update": (c_int, [c_void_p, POINTER(CSRMatrix), POINTER(AMGResult)]),
+    "spmv_c_amg_destroy": (None, [c_void_p]),
+    "spmv_c_amg_num_levels": (c_int, [c_void_p]),
+    "spmv_c_amg_level": (c_int, [c_void_p, c_int, POINTER(CSRMatrix), POINTER(c_void_p), POINTER(c_int32)]),
+    "spmv_c_amg_apply": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "spmv_c_amg_aggregate_cpu_csr": (c_int, [POINTER(CSRMatrix), c_float, c_void_p, POINTER(c_int32)]),
+    "spmv_c_cg_solve_amg": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, c_void_p, POINTER(CGConfig),
+                                    POINTER(CGResult)]),
     "spmv_c_sptrsv_csr": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(SpTRSVConfig),
                                   POINTER(SpTRSVResult)]),
     "spmv_c_sptrsv_csr_async": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(SpTRSVConfig), c_void_p]),
@@ -974,6 +1001,88 @@ def cg_solve_ic(A, F, d_b, d_x, config=None) -> CGResult:
     arrays.  config.preconditioner is not read."""
     out = CGResult()
     lib().spmv_c_cg_solve_ic(A, F, _dev(d_b), _dev(d_x), byref(config) if config is not None else None, byref(out))
+    return out
+
+
+def amg_setup(A, config=None, aggregates=None):
+    """(AMGResult, hierarchy handle or None): the aggregation AMG hierarchy of the device matrix A (include/spmv/amg.h
+    amg_setup).  aggregates: None, or a list of int32 arrays, aggregates[l][i] = the aggregate of row i of level l.
+    Release the handle with amg_destroy."""
+    out, handle = AMGResult(), c_void_p()
+    maps, table = None, None
+    if aggregates is not None:
+        maps = [np.ascontiguousarray(a, dtype=np.int32) for a in aggregates]
+        table = (c_void_p * max(len(maps), 1))(*[a.ctypes.data for a in maps])
+    lib().spmv_c_amg_setup(byref(handle), A, byref(config) if config is not None else None,
+                           len(maps) if maps is not None else 0, table, byref(out))
+    return out, (handle.value if handle.value else None)
+
+
+def amg_update(H, A) -> AMGResult:
+    """New values in the same pattern: every level of H refilled, the aggregates kept (amg.h amg_update)."""
+    out = AMGResult()
+    lib().spmv_c_amg_update(H, A, byref(out))
+    return out
+
+
+def amg_destroy(H) -> None:
+    if H:
+        lib().spmv_c_amg_destroy(H)
+
+
+def amg_num_levels(H) -> int:
+    return lib().spmv_c_amg_num_levels(H)
+
+
+def amg_level(H, level):
+    """(status, view, d_aggregate, num_aggregates): level `level` of H as a CSRMatrix header over device arrays that
+    owns nothing (a ctypes structure, not a pointer), the device address of its aggregate map (None on the coarsest
+    level) and the number of aggregates."""
+    view, d_agg, count = CSRMatrix(), c_void_p(), c_int32(0)
+    status = lib().spmv_c_amg_level(H, int(level), byref(view), byref(d_agg), byref(count))
+    return status, view, d_agg.value, count.value
+
+
+def amg_level_arrays(H, level):
+    """(n, row_ptrs, col_indices, values, aggregate or None): numpy copies of level `level` of H, read back from the
+    device."""
+    status, view, d_agg, _ = amg_level(H, level)
+    if status != 0:
+        raise ValueError(spmv_error_string(status))
+
+    def down(ptr, count, dtype):
+        host = np.empty(count, dtype)
+        if count and lib().spmv_c_memcpy_d2h(_np_ptr(host), c_void_p(ptr), host.nbytes) != 0:
+            raise CudaException("device-to-host copy failed")
+        return host
+
+    n, nnz = view.num_rows, view.nnz
+    cast = lambda p: ctypes.cast(p, c_void_p).value
+    rp = down(cast(view.d_row_ptrs), n + 1, np.int32)
+    ci = down(cast(view.d_col_indices), nnz, np.int32)
+    va = down(cast(view.d_values), nnz, np.float32)
+    return n, rp, ci, va, (down(d_agg, n, np.int32) if d_agg else None)
+
+
+def amg_apply(H, d_r, d_z) -> int:
+    """d_z = one V-cycle of H on d_r from a zero guess (amg.h amg_apply)."""
+    return lib().spmv_c_amg_apply(H, _dev(d_r), _dev(d_z))
+
+
+def amg_aggregate_cpu_csr(A, strength=0.08):
+    """(status, aggregate int32[num_rows], count): the aggregation of one level on A's host arrays, the definition
+    (amg.h amg_aggregate_cpu_csr)."""
+    agg = np.full(max(A.contents.num_rows, 0), -7, np.int32)
+    count = c_int32(-7)
+    status = lib().spmv_c_amg_aggregate_cpu_csr(A, float(strength), _np_ptr(agg), byref(count))
+    return status, agg, count.value
+
+
+def cg_solve_amg(A, H, d_b, d_x, config=None) -> CGResult:
+    """Solves A x = b by CG preconditioned with one V-cycle of the AMG hierarchy H per iteration (include/spmv/cg.h
+    cg_solve_amg)."""
+    out = CGResult()
+    lib().spmv_c_cg_solve_amg(A, H, _dev(d_b), _dev(d_x), byref(config) if config is not None else None, byref(out))
     return out
 
 

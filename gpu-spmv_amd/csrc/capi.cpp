@@ -13,6 +13,7 @@
 #include "spmv/ic0.h"
 #include "spmv/ilu0.h"
 #include "spmv/spgemm.h"
+#include "spmv/amg.h"
 #include "spmv_c.h"
 
 #include <cstddef>
@@ -111,8 +112,21 @@ static_assert(offsetof(spmv_c_spgemm_result, nnz) == offsetof(SpGEMMResult, nnz)
               offsetof(spmv_c_spgemm_result, symbolic_ms) == offsetof(SpGEMMResult, symbolic_ms) &&
               offsetof(spmv_c_spgemm_result, numeric_ms) == offsetof(SpGEMMResult, numeric_ms), "SpGEMMResult layout");
 
+static_assert(sizeof(spmv_c_amg_config) == sizeof(AMGConfig) && sizeof(AMGConfig) == 28, "AMGConfig layout");
+static_assert(offsetof(spmv_c_amg_config, strength) == offsetof(AMGConfig, strength) &&
+              offsetof(spmv_c_amg_config, post_sweeps) == offsetof(AMGConfig, post_sweeps) &&
+              offsetof(spmv_c_amg_config, jacobi_weight) == offsetof(AMGConfig, jacobi_weight) &&
+              offsetof(spmv_c_amg_config, coarse_sweeps) == offsetof(AMGConfig, coarse_sweeps), "AMGConfig layout");
+static_assert(sizeof(spmv_c_amg_result) == sizeof(AMGResult) && sizeof(AMGResult) == 48, "AMGResult layout");
+static_assert(offsetof(spmv_c_amg_result, bad_level) == offsetof(AMGResult, bad_level) &&
+              offsetof(spmv_c_amg_result, grid_complexity) == offsetof(AMGResult, grid_complexity) &&
+              offsetof(spmv_c_amg_result, operator_complexity) == offsetof(AMGResult, operator_complexity) &&
+              offsetof(spmv_c_amg_result, setup_ms) == offsetof(AMGResult, setup_ms), "AMGResult layout");
+
 namespace {
 
+inline AMGHierarchy* cxx(spmv_c_amg* h) { return reinterpret_cast<AMGHierarchy*>(h); }
+inline const AMGHierarchy* cxx(const spmv_c_amg* h) { return reinterpret_cast<const AMGHierarchy*>(h); }
 inline CSRMatrix* cxx(spmv_c_csr* m) { return reinterpret_cast<CSRMatrix*>(m); }
 inline const CSRMatrix* cxx(const spmv_c_csr* m) { return reinterpret_cast<const CSRMatrix*>(m); }
 inline ELLMatrix* cxx(spmv_c_ell* m) { return reinterpret_cast<ELLMatrix*>(m); }
@@ -584,6 +598,45 @@ int spmv_c_spgemm_cpu_csr(spmv_c_csr* C, const spmv_c_csr* A, const spmv_c_csr* 
 }
 
 int spmv_c_spgemm_class_capacity(int cls) { return spgemm_class_capacity(cls); }
+
+int spmv_c_amg_setup(spmv_c_amg** out, const spmv_c_csr* A, const spmv_c_amg_config* config, int aggregate_levels,
+                     const int32_t* const* aggregates, spmv_c_amg_result* result) {
+    const AMGAggregates given{aggregate_levels, aggregates};
+    AMGHierarchy* H = nullptr;
+    const AMGResult r = amg_setup(out ? &H : nullptr, cxx(A), reinterpret_cast<const AMGConfig*>(config),
+                                  aggregates ? &given : nullptr);
+    if (out) *out = reinterpret_cast<spmv_c_amg*>(H);
+    if (result) std::memcpy(result, &r, sizeof(r));
+    return r.error_code;
+}
+
+int spmv_c_amg_update(spmv_c_amg* H, const spmv_c_csr* A, spmv_c_amg_result* result) {
+    const AMGResult r = amg_update(cxx(H), cxx(A));
+    if (result) std::memcpy(result, &r, sizeof(r));
+    return r.error_code;
+}
+
+void spmv_c_amg_destroy(spmv_c_amg* H) { amg_destroy(cxx(H)); }
+
+int spmv_c_amg_num_levels(const spmv_c_amg* H) { return amg_num_levels(cxx(H)); }
+
+int spmv_c_amg_level(const spmv_c_amg* H, int level, spmv_c_csr* view, const int32_t** d_aggregate,
+                     int32_t* num_aggregates) {
+    return amg_level(cxx(H), level, cxx(view), d_aggregate, num_aggregates);
+}
+
+int spmv_c_amg_apply(const spmv_c_amg* H, const float* d_r, float* d_z) { return amg_apply(cxx(H), d_r, d_z); }
+
+int spmv_c_amg_aggregate_cpu_csr(const spmv_c_csr* A, float strength, int32_t* aggregate, int32_t* num_aggregates) {
+    return amg_aggregate_cpu_csr(cxx(A), strength, aggregate, num_aggregates);
+}
+
+int spmv_c_cg_solve_amg(const spmv_c_csr* A, const spmv_c_amg* H, const float* d_b, float* d_x,
+                        const spmv_c_cg_config* config, spmv_c_cg_result* out) {
+    const CGResult r = cg_solve_amg(cxx(A), cxx(H), d_b, d_x, reinterpret_cast<const CGConfig*>(config));
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
+}
 
 int spmv_c_sptrsv_csr(const spmv_c_csr* A, const float* d_b, float* d_x, const spmv_c_sptrsv_config* config,
                       spmv_c_sptrsv_result* out) {

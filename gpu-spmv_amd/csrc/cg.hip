@@ -18,6 +18,10 @@
 //   cg_rz_kernel            the block partials of r.z
 //   cg_ic_direction_kernel  as cg_direction_kernel with z read from memory
 // and the SpMV half is the one above, kernel for kernel.
+//
+// cg_solve_amg is cg_solve_ic's loop with z = one V-cycle of an AMG hierarchy on r (amg_vcycle, amg.hip, DESIGN.md
+// §4.16) in place of the two triangular solves; its kernels read `done` themselves.
+#include "amg_impl.h"
 #include "internal.h"
 #include "device_common.h"
 #include "solver_common.h"
@@ -375,10 +379,16 @@ bool device_arrays(const CSRMatrix* M) {
     return M->num_rows >= 0 && M->d_row_ptrs && (M->nnz <= 0 || (M->d_col_indices && M->d_values));
 }
 
-// cg_solve (with_ic false: F is not looked at, cfg.preconditioner picks NONE or JACOBI) and cg_solve_ic (with_ic
-// true: M = L L^T from F, cfg.preconditioner is not read).
-CGResult solve(const CSRMatrix* A, const CSRMatrix* F, bool with_ic, const float* d_b, float* d_x,
-               const CGConfig* config) {
+// What gives z: the diagonal inside the step kernels (cg_solve: cfg.preconditioner picks NONE or JACOBI), or a stored z
+// from M = L L^T of the factor matrix F (cg_solve_ic) or from one V-cycle of the hierarchy H (cg_solve_amg); the last
+// two do not read cfg.preconditioner.
+enum class Precond { DIAGONAL, IC, AMG };
+
+CGResult solve(const CSRMatrix* A, Precond precond, const CSRMatrix* F, const AMGHierarchy* H, const float* d_b,
+               float* d_x, const CGConfig* config) {
+    const bool with_ic = precond == Precond::IC;
+    const bool with_amg = precond == Precond::AMG;
+    const bool stored_z = with_ic || with_amg;
     CGResult result;
     const auto fail = [&result](SpMVError e) {
         result.error_code = code(e);
@@ -396,7 +406,7 @@ CGResult solve(const CSRMatrix* A, const CSRMatrix* F, bool with_ic, const float
     const CGConfig defaults;
     const CGConfig& cfg = config ? *config : defaults;
     if (!(cfg.tolerance >= 0.0f) || cfg.max_iterations < 0 ||
-        (!with_ic && cfg.preconditioner != CGConfig::NONE && cfg.preconditioner != CGConfig::JACOBI) ||
+        (!stored_z && cfg.preconditioner != CGConfig::NONE && cfg.preconditioner != CGConfig::JACOBI) ||
         cfg.engine < -1 || cfg.engine > 1) {
         return fail(SpMVError::INVALID_ARGUMENT);
     }
@@ -407,10 +417,15 @@ CGResult solve(const CSRMatrix* A, const CSRMatrix* F, bool with_ic, const float
         if (F->num_rows != F->num_cols || F->num_rows != n) return fail(SpMVError::INVALID_DIMENSION);
         if (!device_arrays(F)) return fail(SpMVError::INVALID_FORMAT);
     }
+    if (with_amg) {
+        if (!H || H->levels.empty()) return fail(SpMVError::INVALID_ARGUMENT);
+        if (H->num_rows != n) return fail(SpMVError::INVALID_DIMENSION);
+        if (H->config.pre_sweeps != H->config.post_sweeps) return fail(SpMVError::INVALID_ARGUMENT);
+    }
 
-    const TraceRange range(with_ic ? "spmv:cg_solve_ic" : "spmv:cg_solve");
+    const TraceRange range(with_ic ? "spmv:cg_solve_ic" : with_amg ? "spmv:cg_solve_amg" : "spmv:cg_solve");
     hipStream_t stream = current_stream();
-    const bool jacobi = !with_ic && cfg.preconditioner == CGConfig::JACOBI;
+    const bool jacobi = !stored_z && cfg.preconditioner == CGConfig::JACOBI;
 
     // both schedules of F, ahead of the timed loop (a build synchronises the stream); they validate F's structure
     // before any kernel walks it
@@ -424,11 +439,7 @@ CGResult solve(const CSRMatrix* A, const CSRMatrix* F, bool with_ic, const float
         lower_lanes = sptrsv_lanes_for(*lower);
         upper_lanes = sptrsv_lanes_for(*upper);
     }
-    // out = L^-T (L^-1 in): LOWER NON_UNIT, then UPPER NON_UNIT in place
-    const auto apply_ic = [&](const float* in, float* out) -> bool {
-        return launch_sptrsv(*lower, F, in, out, SpTRSVConfig::LOWER, 0, false, lower_lanes, stream) == hipSuccess &&
-               launch_sptrsv(*upper, F, out, out, SpTRSVConfig::UPPER, 0, false, upper_lanes, stream) == hipSuccess;
-    };
+    const int amg_lanes = with_amg ? amg_forced_lanes() : 0;
 
     // engine choice (pagerank()'s rule for -1: a cached plan from the start, else a build after 4 direct steps)
     PlanRef plan;
@@ -447,18 +458,24 @@ CGResult solve(const CSRMatrix* A, const CSRMatrix* F, bool with_ic, const float
     const size_t rr_count = 2 * static_cast<size_t>(vgrid);
     const size_t init_count = 3 * static_cast<size_t>(row_grid);
 
-    Workspace<CgState> ws;          // r, p, q, and dinv (JACOBI) or z (IC)
+    Workspace<CgState> ws;          // r, p, q, and dinv (JACOBI) or z (IC, AMG)
     const size_t len = static_cast<size_t>(n);
     if (!ws.allocate(4 * len, pq_count + rr_count + init_count)) return fail(SpMVError::CUDA_MALLOC);
     float* r = ws.vec;
     float* p = ws.vec + len;
     float* q = ws.vec + 2 * len;
     float* dinv = jacobi ? ws.vec + 3 * len : nullptr;
-    float* z = with_ic ? ws.vec + 3 * len : nullptr;
+    float* z = stored_z ? ws.vec + 3 * len : nullptr;
     double* pq_part = ws.part;
     double* rr_part = ws.part + pq_count;
     double* init_part = rr_part + rr_count;
     CgState* pinned = ws.pinned;
+    // out = M^-1 in.  IC: LOWER NON_UNIT, then UPPER NON_UNIT in place.  AMG: one V-cycle, whose kernels read `done`.
+    const auto apply_stored = [&](const float* in, float* out) -> bool {
+        if (with_amg) return amg_vcycle(*H, in, out, &ws.state->done, amg_lanes, stream) == hipSuccess;
+        return launch_sptrsv(*lower, F, in, out, SpTRSVConfig::LOWER, 0, false, lower_lanes, stream) == hipSuccess &&
+               launch_sptrsv(*upper, F, out, out, SpTRSVConfig::UPPER, 0, false, upper_lanes, stream) == hipSuccess;
+    };
 
     // setup: diagonal (JACOBI; of F, only its check), r0 / p0 and their dots, the state; one read-back
     bool ok = hipMemsetAsync(ws.state, 0, sizeof(CgState), stream) == hipSuccess;
@@ -472,9 +489,9 @@ CGResult solve(const CSRMatrix* A, const CSRMatrix* F, bool with_ic, const float
         ok = hipGetLastError() == hipSuccess;
     }
     ok = ok && init(lanes, A, d_b, d_x, dinv, r, p, init_part, row_grid, stream) == hipSuccess;
-    if (ok && with_ic) {
+    if (ok && stored_z) {
         // the init kernel left p0 = r0 and r0.r0 in the r.z slot: z0 = M^-1 r0, the true r0.z0 over it, p0 = z0
-        ok = apply_ic(r, z);
+        ok = apply_stored(r, z);
         if (ok) {
             cg_rz_kernel<<<row_grid, kBlock, 0, stream>>>(n, r, z, ws.state, init_part, 3);
             ok = hipGetLastError() == hipSuccess &&
@@ -533,13 +550,13 @@ CGResult solve(const CSRMatrix* A, const CSRMatrix* F, bool with_ic, const float
                 }
             }
             if (ok && direct) ok = spmv_dot(lanes, A, p, q, ws.state, pq_part, row_grid, stream) == hipSuccess;
-            if (ok && with_ic) {
+            if (ok && stored_z) {
                 cg_ic_update_kernel<<<vgrid, kBlock, 0, stream>>>(n, iter, p, q, d_x, r, ws.state, pq_part, pq_parts,
                                                                   rr_part);
-                ok = hipGetLastError() == hipSuccess && apply_ic(r, z);
+                ok = hipGetLastError() == hipSuccess && apply_stored(r, z);
             }
             if (ok) {
-                if (with_ic) {
+                if (stored_z) {
                     cg_rz_kernel<<<vgrid, kBlock, 0, stream>>>(n, r, z, ws.state, rr_part, 2);
                     cg_ic_direction_kernel<<<vgrid, kBlock, 0, stream>>>(n, iter, z, p, ws.state, rr_part, vgrid);
                 } else {
@@ -579,11 +596,15 @@ CGResult solve(const CSRMatrix* A, const CSRMatrix* F, bool with_ic, const float
 } // namespace detail
 
 CGResult cg_solve(const CSRMatrix* A, const float* d_b, float* d_x, const CGConfig* config) {
-    return detail::solve(A, nullptr, false, d_b, d_x, config);
+    return detail::solve(A, detail::Precond::DIAGONAL, nullptr, nullptr, d_b, d_x, config);
 }
 
 CGResult cg_solve_ic(const CSRMatrix* A, const CSRMatrix* F, const float* d_b, float* d_x, const CGConfig* config) {
-    return detail::solve(A, F, true, d_b, d_x, config);
+    return detail::solve(A, detail::Precond::IC, F, nullptr, d_b, d_x, config);
+}
+
+CGResult cg_solve_amg(const CSRMatrix* A, const AMGHierarchy* H, const float* d_b, float* d_x, const CGConfig* config) {
+    return detail::solve(A, detail::Precond::AMG, nullptr, H, d_b, d_x, config);
 }
 
 } // namespace spmv

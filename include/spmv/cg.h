@@ -89,6 +89,21 @@ CGResult cg_solve(const CSRMatrix* A, const float* d_b, float* d_x, const CGConf
 CGResult cg_solve_ic(const CSRMatrix* A, const CSRMatrix* F, const float* d_b, float* d_x,
                      const CGConfig* config = nullptr);
 
+// cg_solve preconditioned by one V-cycle of the aggregation AMG hierarchy H (spmv/amg.h: amg_setup on A):
+// cg_solve_ic's iteration with z = amg_apply(r) in place of the two triangular solves.  z is a stored vector; the
+// stored-z step kernels, the SpMV half of a step, the engines, the plan caching, the stop rules and the breakdown rule
+// are cg_solve_ic's, and the V-cycle's kernels return at once when the state says `done`, like every loop kernel.  A
+// solve is bitwise reproducible from run to run on each engine.  The hierarchy's workspace is used: one solve per
+// hierarchy at a time.
+//
+// Checks, before any write to d_x: cg_solve's, in their order (config->preconditioner is not read), then: null H ->
+// INVALID_ARGUMENT; H built for another number of rows than A's -> INVALID_DIMENSION; H->config.pre_sweeps !=
+// post_sweeps (the cycle is not symmetric, so M is not) -> INVALID_ARGUMENT.  A cycle that is not positive definite
+// (jacobi_weight too large for the matrix) surfaces as a breakdown, x at the last good iterate.
+struct AMGHierarchy;
+CGResult cg_solve_amg(const CSRMatrix* A, const AMGHierarchy* H, const float* d_b, float* d_x,
+                      const CGConfig* config = nullptr);
+
 } // namespace spmv
 
 #endif

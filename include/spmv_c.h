@@ -456,6 +456,52 @@ int spmv_c_spgemm_cpu_csr(spmv_c_csr* C, const spmv_c_csr* A, const spmv_c_csr* 
 /* most distinct columns of a row in accumulator class cls (1-based); INT32_MAX for the dense class, -1 past it */
 int spmv_c_spgemm_class_capacity(int cls);
 
+/* ---- aggregation AMG and AMG-preconditioned CG (extension; include/spmv/amg.h, include/spmv/cg.h) ---- */
+/* 28 bytes; the defaults of AMGConfig are 10, 64, 0.08, 1, 1, 2/3, 4 */
+typedef struct spmv_c_amg_config {
+    int32_t max_levels;      /* >= 1 */
+    int32_t coarse_rows;     /* 1 .. 1024 */
+    float   strength;        /* theta >= 0 */
+    int32_t pre_sweeps;      /* >= 1 */
+    int32_t post_sweeps;     /* >= 0 */
+    float   jacobi_weight;   /* omega in (0, 2) */
+    int32_t coarse_sweeps;   /* >= 1 */
+} spmv_c_amg_config;
+/* 48 bytes */
+typedef struct spmv_c_amg_result {
+    int32_t error_code;
+    int32_t levels;
+    int32_t coarse_solver;   /* 0 dense inverse, 1 Jacobi sweeps */
+    int32_t bad_row;         /* -1 when no diagonal / pivot check failed */
+    int32_t bad_level;
+    double  grid_complexity;
+    double  operator_complexity;
+    float   setup_ms;
+} spmv_c_amg_result;
+typedef struct spmv_c_amg spmv_c_amg;             /* opaque: the hierarchy; one hierarchy serves one stream at a time */
+
+/* Builds the hierarchy of the square device matrix A; *out is NULL on failure.  config may be NULL (the defaults).
+ * aggregates may be NULL (the library aggregates), else aggregate_levels host arrays, aggregates[l][i] = the aggregate
+ * of row i of level l.  Checks and arithmetic as amg_setup in include/spmv/amg.h.  The return value equals
+ * result->error_code (result may be NULL). */
+int spmv_c_amg_setup(spmv_c_amg** out, const spmv_c_csr* A, const spmv_c_amg_config* config, int aggregate_levels,
+                     const int32_t* const* aggregates, spmv_c_amg_result* result);
+/* new values in the same pattern: every level refilled, aggregates kept, nothing allocated again */
+int spmv_c_amg_update(spmv_c_amg* H, const spmv_c_csr* A, spmv_c_amg_result* result);
+void spmv_c_amg_destroy(spmv_c_amg* H);
+int spmv_c_amg_num_levels(const spmv_c_amg* H);
+/* level `level` as a non-owning device view; *d_aggregate (n_l ints on the device) is NULL on the coarsest level */
+int spmv_c_amg_level(const spmv_c_amg* H, int level, spmv_c_csr* view, const int32_t** d_aggregate,
+                     int32_t* num_aggregates);
+/* d_z = one V-cycle on d_r from a zero guess */
+int spmv_c_amg_apply(const spmv_c_amg* H, const float* d_r, float* d_z);
+/* the aggregation of one level on A's host arrays: aggregate[num_rows], *num_aggregates */
+int spmv_c_amg_aggregate_cpu_csr(const spmv_c_csr* A, float strength, int32_t* aggregate, int32_t* num_aggregates);
+/* CG preconditioned by one V-cycle of H per iteration; config->preconditioner is not read.  Checks and numerics as
+ * cg_solve_amg in include/spmv/cg.h. */
+int spmv_c_cg_solve_amg(const spmv_c_csr* A, const spmv_c_amg* H, const float* d_b, float* d_x,
+                        const spmv_c_cg_config* config, spmv_c_cg_result* out);
+
 /* ---- bandwidth model: reference include/spmv/bandwidth.h:21-27 ---- */
 int spmv_c_compute_bandwidth_csr(const spmv_c_csr* A, float elapsed_ms, spmv_c_bandwidth* out);
 int spmv_c_compute_bandwidth_ell(const spmv_c_ell* A, float elapsed_ms, spmv_c_bandwidth* out);
