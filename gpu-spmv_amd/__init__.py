@@ -334,6 +334,8 @@ _SIGNATURES = {
     "spmv_c_ilu0_csr": (c_int, [POINTER(CSRMatrix), c_void_p, POINTER(ILU0Result)]),
     "spmv_c_ilu0_csr_async": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p]),
     "spmv_c_ilu0_cpu_csr": (c_int, [POINTER(CSRMatrix), c_void_p, POINTER(c_int32)]),
+    "spmv_c_cg_solve_multi": (c_int, [POINTER(CSRMatrix), c_void_p, c_int, c_void_p, c_int, c_int, POINTER(CGConfig),
+                                      POINTER(CGResult)]),
     "spmv_c_cg_solve_ic": (c_int, [POINTER(CSRMatrix), POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(CGConfig),
                                    POINTER(CGResult)]),
     "spmv_c_ic0_csr": (c_int, [POINTER(CSRMatrix), c_void_p, POINTER(IC0Result)]),
@@ -932,6 +934,23 @@ def cg_solve(A, d_b, d_x, config=None) -> CGResult:
     out = CGResult()
     lib().spmv_c_cg_solve(A, _dev(d_b), _dev(d_x), byref(config) if config is not None else None, byref(out))
     return out
+
+
+def cg_solve_multi(A, d_B, d_X, k, ldb=None, ldx=None, config=None) -> list:
+    """cg_solve for k right-hand sides in one matrix pass per step (include/spmv/cg.h cg_solve_multi): d_B and d_X
+    are num_rows x k row-major with leading dimensions ldb, ldx >= k (default k); returns one CGResult per column
+    (at least one, so that a rejected call always has somewhere to report its error_code)."""
+    k = int(k)
+    ldb = k if ldb is None else int(ldb)
+    ldx = k if ldx is None else int(ldx)
+    out = (CGResult * max(k, 1))()
+    rc = lib().spmv_c_cg_solve_multi(A, _dev(d_B), ldb, _dev(d_X), ldx, k,
+                                     byref(config) if config is not None else None, out)
+    results = list(out)
+    if rc != 0:
+        for r in results:
+            r.error_code = rc
+    return results
 
 
 def bicgstab_solve(A, d_b, d_x, config=None) -> BiCGStabResult:

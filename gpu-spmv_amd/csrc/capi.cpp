@@ -515,6 +515,12 @@ int spmv_c_cg_solve(const spmv_c_csr* A, const float* d_b, float* d_x, const spm
     return r.error_code;
 }
 
+int spmv_c_cg_solve_multi(const spmv_c_csr* A, const float* d_B, int ldb, float* d_X, int ldx, int k,
+                          const spmv_c_cg_config* config, spmv_c_cg_result* results) {
+    return cg_solve_multi(cxx(A), d_B, ldb, d_X, ldx, k, reinterpret_cast<const CGConfig*>(config),
+                          reinterpret_cast<CGResult*>(results));
+}
+
 int spmv_c_cg_solve_ic(const spmv_c_csr* A, const spmv_c_csr* F, const float* d_b, float* d_x,
                        const spmv_c_cg_config* config, spmv_c_cg_result* out) {
     const CGResult r = cg_solve_ic(cxx(A), cxx(F), d_b, d_x, reinterpret_cast<const CGConfig*>(config));

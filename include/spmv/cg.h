@@ -67,6 +67,37 @@ struct CGResult {
 // plan for engine 1) and its one setup read-back synchronise that stream — make the call outside a graph capture.
 CGResult cg_solve(const CSRMatrix* A, const float* d_b, float* d_x, const CGConfig* config = nullptr);
 
+// cg_solve for k right-hand sides on one matrix, the matrix read once per step for all of them.
+// d_B and d_X are num_rows x k, row-major, on the device, with leading dimensions ldb, ldx >= k (spmv_csr_multi's
+// layout); d_X holds the k initial guesses on entry and the k solutions on exit.  results: k CGResult on the host,
+// one per column.  Returns a SpMVError as int.  1 <= k <= 32.
+//
+// Column j runs exactly cg_solve's iteration and numerics above (NONE or JACOBI; dinv is computed once and shared),
+// and the contract is bitwise: X[:, j] and results[j].iterations / converged / breakdown / relative_residual /
+// error_code equal what cg_solve(A, B[:, j], X0[:, j], config) with engine = 0 gives, whatever the other columns do
+// (the row sums, the per-workgroup fp64 partials and their fold depend on the thread-to-row mapping and the grids
+// alone, and the k-wide kernels keep both).  max_iterations applies per column.  elapsed_ms is the time of the
+// batched loop, the same in every result.
+//
+// Columns finish independently: one that has converged, broken down or started converged is frozen (its x is not
+// written again, its result stands) while the others go on; a column with ||b_j|| == 0 gets x_j = 0, converged, 0
+// iterations.  The loop ends when every column is done or max_iterations steps are enqueued.  Columns k..ldx-1 of
+// d_X are never written and d_B is never written.
+//
+// Checks, in this order, before any device work; when one fails nothing is written to d_X, and of `results` only
+// error_code (of all k entries; of none when k itself is out of range: the return value carries the code):
+//   null A / d_B / d_X / results -> INVALID_ARGUMENT; k < 1 or k > 32 -> INVALID_ARGUMENT; ldb < k or ldx < k ->
+//   INVALID_ARGUMENT; num_rows != num_cols -> INVALID_DIMENSION; num_rows == 0 -> SUCCESS, every column converged
+//   after 0 iterations; missing device arrays -> INVALID_FORMAT; cg_solve's config checks, with engine -1 or 0 only
+//   (both run the direct kernels; engine = 1 -> INVALID_ARGUMENT: the LDS-tiled engine has no k-wide form); the
+//   ranges d_B[0, (num_rows - 1) * ldb + k) and d_X[0, (num_rows - 1) * ldx + k) overlap -> INVALID_ARGUMENT; with
+//   JACOBI, a bad diagonal -> INVALID_ARGUMENT (on the device, in the one setup read-back, d_X untouched).
+// Runs on spmv_get_stream() and returns after the solve; call it outside a graph capture.  It never touches A's
+// promotion count, merge-path state or tiled plan.  The workspace is three arrays of num_rows x k floats, k rounded up
+// to 4 (k <= 4) or to a multiple of 8.
+int cg_solve_multi(const CSRMatrix* A, const float* d_B, int ldb, float* d_X, int ldx, int k,
+                   const CGConfig* config, CGResult* results);
+
 // cg_solve preconditioned by M = L L^T: L is the lower triangle of the square device matrix F with its stored
 // diagonal, L^T is F's upper triangle with its stored diagonal (entries are taken as stored: nothing tests that the
 // two triangles are each other's transpose).  F has num_rows == A->num_rows; the usual one wraps the output of

@@ -270,6 +270,12 @@ typedef struct spmv_c_cg_result {
 int spmv_c_cg_solve(const spmv_c_csr* A, const float* d_b, float* d_x, const spmv_c_cg_config* config,
                     spmv_c_cg_result* out);
 
+/* spmv_c_cg_solve for k right-hand sides (1..32) in one matrix pass per step: d_B and d_X are num_rows x k row-major
+ * with leading dimensions ldb, ldx >= k; results holds k entries.  Column j is bit for bit spmv_c_cg_solve with
+ * engine 0 on that column.  Checks and numerics as cg_solve_multi in include/spmv/cg.h.  Returns the error code. */
+int spmv_c_cg_solve_multi(const spmv_c_csr* A, const float* d_B, int ldb, float* d_X, int ldx, int k,
+                          const spmv_c_cg_config* config, spmv_c_cg_result* results);
+
 /* the same iteration preconditioned by M = L L^T, L the lower triangle (with the stored diagonal) of the square
  * device matrix F and L^T its upper triangle (num_rows as A's; usually spmv_c_ic0_csr's output wrapped over A's
  * structure arrays).  config->preconditioner is not read.  Checks and numerics as cg_solve_ic in include/spmv/cg.h.
