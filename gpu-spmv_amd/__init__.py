@@ -133,6 +133,12 @@ class CGResult(Structure):
                 ("converged", c_int32), ("breakdown", c_int32), ("elapsed_ms", c_float)]
 
 
+class PersonalizedResult(Structure):
+    """include/spmv/pagerank.h PersonalizedResult (20 bytes), one per teleport vector"""
+    _fields_ = [("error_code", c_int32), ("iterations", c_int32), ("final_residual", c_float),
+                ("converged", c_int32), ("elapsed_ms", c_float)]
+
+
 class BiCGStabConfig(Structure):
     """include/spmv/bicgstab.h BiCGStabConfig (16 bytes): the fields, defaults and meanings of CGConfig"""
     _fields_ = [("tolerance", c_float), ("max_iterations", c_int32), ("preconditioner", c_int32),
@@ -372,6 +378,10 @@ _SIGNATURES = {
     "spmv_c_pagerank_top_k": (None, [POINTER(_PageRankResultC), c_int, c_int, POINTER(TopKNode)]),
     "spmv_c_pagerank_multi_gpu": (c_int, [POINTER(CSRMatrix), POINTER(PageRankConfig), c_int, POINTER(_PageRankResultC)]),
     "spmv_c_pagerank_shard_bounds": (c_int, [POINTER(c_int32), c_int, c_int, POINTER(c_int32)]),
+    "spmv_c_pagerank_personalized": (c_int, [POINTER(CSRMatrix), c_void_p, c_int, c_void_p, c_int, c_int,
+                                             POINTER(PageRankConfig), POINTER(PersonalizedResult)]),
+    "spmv_c_pagerank_personalized_seeds": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                                   POINTER(PageRankConfig), POINTER(PersonalizedResult)]),
     "spmv_c_pr_shard_create": (c_void_p, [POINTER(CSRMatrix), c_int, c_int, c_void_p]),
     "spmv_c_pr_shard_create_chunked": (c_void_p, [POINTER(CSRMatrix), c_int, c_int, c_int, c_int, c_void_p]),
     "spmv_c_pr_shard_destroy": (None, [c_void_p]),
@@ -1239,6 +1249,43 @@ def pagerank_multi_gpu(adj_matrix, config=None, num_gpus=1) -> PageRankResult:
     ranks = np.ctypeslib.as_array(raw.ranks, shape=(n,)).copy()
     lib().spmv_c_pagerank_free(byref(raw))
     return PageRankResult(ranks, raw.iterations, float(raw.final_residual), bool(raw.converged))
+
+
+def pagerank_personalized(adj_matrix, d_V, d_R, k, ldv=None, ldr=None, config=None) -> list:
+    """Personalized PageRank for k teleport vectors in one matrix pass per step (include/spmv/pagerank.h
+    pagerank_personalized): d_V (read only) and d_R are num_rows x k row-major device arrays with leading dimensions
+    ldv, ldr >= k (default k); returns one PersonalizedResult per column (at least one, so that a rejected call always
+    has somewhere to report its error_code)."""
+    k = int(k)
+    ldv = k if ldv is None else int(ldv)
+    ldr = k if ldr is None else int(ldr)
+    out = (PersonalizedResult * max(k, 1))()
+    rc = lib().spmv_c_pagerank_personalized(adj_matrix, _dev(d_V), ldv, _dev(d_R), ldr, k,
+                                            byref(config) if config is not None else None, out)
+    results = list(out)
+    if rc != 0:
+        for r in results:
+            r.error_code = rc
+    return results
+
+
+def pagerank_personalized_seeds(adj_matrix, seed_sets, d_R, ldr=None, config=None) -> list:
+    """pagerank_personalized with column j teleporting uniformly to the nodes of seed_sets[j] (a sequence of k
+    sequences of node ids); one PersonalizedResult per set."""
+    k = len(seed_sets)
+    ldr = k if ldr is None else int(ldr)
+    ptrs = np.zeros(k + 1, np.int32)
+    ptrs[1:] = np.cumsum([len(s) for s in seed_sets], dtype=np.int64)
+    # (one spare entry: never an empty array)
+    nodes = np.concatenate([np.asarray(s, np.int64).ravel() for s in seed_sets] + [np.zeros(1, np.int64)]).astype(np.int32)
+    out = (PersonalizedResult * max(k, 1))()
+    rc = lib().spmv_c_pagerank_personalized_seeds(adj_matrix, _np_ptr(ptrs), _np_ptr(nodes), k, _dev(d_R), ldr,
+                                                  byref(config) if config is not None else None, out)
+    results = list(out)
+    if rc != 0:
+        for r in results:
+            r.error_code = rc
+    return results
 
 
 def pagerank_top_k(result: PageRankResult, num_nodes: int, k: int):

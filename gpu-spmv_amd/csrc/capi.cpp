@@ -45,6 +45,13 @@ static_assert(sizeof(spmv_c_cg_config) == sizeof(CGConfig) && sizeof(CGConfig) =
 static_assert(offsetof(spmv_c_cg_config, max_iterations) == offsetof(CGConfig, max_iterations) &&
               offsetof(spmv_c_cg_config, preconditioner) == offsetof(CGConfig, preconditioner) &&
               offsetof(spmv_c_cg_config, engine) == offsetof(CGConfig, engine), "CGConfig layout");
+static_assert(sizeof(spmv_c_personalized_result) == sizeof(PersonalizedResult) && sizeof(PersonalizedResult) == 20,
+              "PersonalizedResult layout");
+static_assert(offsetof(spmv_c_personalized_result, iterations) == offsetof(PersonalizedResult, iterations) &&
+              offsetof(spmv_c_personalized_result, final_residual) == offsetof(PersonalizedResult, final_residual) &&
+              offsetof(spmv_c_personalized_result, converged) == offsetof(PersonalizedResult, converged) &&
+              offsetof(spmv_c_personalized_result, elapsed_ms) == offsetof(PersonalizedResult, elapsed_ms),
+              "PersonalizedResult layout");
 static_assert(sizeof(spmv_c_cg_result) == sizeof(CGResult) && sizeof(CGResult) == 24, "CGResult layout");
 static_assert(offsetof(spmv_c_cg_result, iterations) == offsetof(CGResult, iterations) &&
               offsetof(spmv_c_cg_result, relative_residual) == offsetof(CGResult, relative_residual) &&
@@ -733,6 +740,20 @@ void spmv_c_pagerank_top_k(const spmv_c_pagerank_result* result, int num_nodes, 
                            spmv_c_topk_node* top_k) {
     pagerank_top_k(reinterpret_cast<const PageRankResult*>(result), num_nodes, k,
                    reinterpret_cast<TopKNode*>(top_k));
+}
+
+int spmv_c_pagerank_personalized(const spmv_c_csr* adj, const float* d_V, int ldv, float* d_R, int ldr, int k,
+                                 const spmv_c_pagerank_config* config, spmv_c_personalized_result* results) {
+    return pagerank_personalized(cxx(adj), d_V, ldv, d_R, ldr, k, reinterpret_cast<const PageRankConfig*>(config),
+                                 reinterpret_cast<PersonalizedResult*>(results));
+}
+
+int spmv_c_pagerank_personalized_seeds(const spmv_c_csr* adj, const int32_t* seed_ptrs, const int32_t* seed_nodes,
+                                       int k, float* d_R, int ldr, const spmv_c_pagerank_config* config,
+                                       spmv_c_personalized_result* results) {
+    return pagerank_personalized_seeds(cxx(adj), seed_ptrs, seed_nodes, k, d_R, ldr,
+                                       reinterpret_cast<const PageRankConfig*>(config),
+                                       reinterpret_cast<PersonalizedResult*>(results));
 }
 
 // ---- PageRank shard engine ----

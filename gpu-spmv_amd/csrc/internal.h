@@ -193,6 +193,7 @@ void    ell_aux_drop(const void* key);
 //   spgemm_dense_groups=G      workgroups (and scratch slices) of spgemm_csr's dense class, instead of the scratch cap
 //   amg_lanes=N                lanes per row (and per aggregate) of every level of the AMG V-cycle (1, 2, 4, ... 64;
 //                              anything else is ignored)
+//   ppr_lanes=N                lanes per row of pagerank_personalized's step (1, 2, 4, ... 64; anything else is ignored)
 // Everything else the library reads from the environment is listed in INTEGRATION.md.
 bool debug_option(const char* key, long long* value = nullptr, char* text = nullptr, size_t text_size = 0);
 // the same "key=value,key" syntax for another variable's value (SPMV_MULTI_GPU); `list` may be null

@@ -531,6 +531,25 @@ int spmv_c_pagerank_shard_bounds(const int32_t* row_ptrs, int num_rows, int num_
 void spmv_c_pagerank_top_k(const spmv_c_pagerank_result* result, int num_nodes, int k,
                            spmv_c_topk_node* top_k);
 
+/* extension (spmv::pagerank_personalized, include/spmv/pagerank.h): personalized PageRank for k teleport vectors
+ * (1..32) in one matrix pass per step.  d_V (read only) and d_R are num_rows x k row-major device arrays with leading
+ * dimensions ldv, ldr >= k; results holds k entries (20 bytes each).  Column j is bit for bit the k = 1 call on that
+ * column.  Checks and numerics as pagerank_personalized in include/spmv/pagerank.h.  Returns the error code. */
+typedef struct spmv_c_personalized_result {
+    int32_t error_code;
+    int32_t iterations;
+    float   final_residual;
+    int32_t converged;
+    float   elapsed_ms;
+} spmv_c_personalized_result;
+int spmv_c_pagerank_personalized(const spmv_c_csr* adj, const float* d_V, int ldv, float* d_R, int ldr, int k,
+                                 const spmv_c_pagerank_config* config, spmv_c_personalized_result* results);
+/* the same with column j teleporting uniformly to the nodes seed_nodes[seed_ptrs[j] .. seed_ptrs[j + 1]) (host
+ * arrays): an empty set, a node out of range or a node twice in one set is -8 (INVALID_ARGUMENT) */
+int spmv_c_pagerank_personalized_seeds(const spmv_c_csr* adj, const int32_t* seed_ptrs, const int32_t* seed_nodes,
+                                       int k, float* d_R, int ldr, const spmv_c_pagerank_config* config,
+                                       spmv_c_personalized_result* results);
+
 /* ---- PageRank shard engine (extension: the row-sharded multi-GPU loop) ----
  * One rank owns A_local->num_rows consecutive rows of the n_global-node matrix (A_local: device
  * CSR, row_ptrs rebased to 0) and full-length device vectors of A_local->num_cols floats, which
