@@ -367,6 +367,14 @@ _SIGNATURES = {
     "spmv_c_sptrsv_csr_async": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(SpTRSVConfig), c_void_p]),
     "spmv_c_sptrsv_analyze": (c_int, [POINTER(CSRMatrix), c_int, POINTER(SpTRSVResult)]),
     "spmv_c_sptrsv_cpu_csr": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(SpTRSVConfig)]),
+    "spmv_c_sptrsv_csr_multi": (c_int, [POINTER(CSRMatrix), c_void_p, c_int, c_void_p, c_int, c_int,
+                                        POINTER(SpTRSVConfig), POINTER(SpTRSVResult)]),
+    "spmv_c_sptrsv_csr_multi_async": (c_int, [POINTER(CSRMatrix), c_void_p, c_int, c_void_p, c_int, c_int,
+                                              POINTER(SpTRSVConfig), c_void_p]),
+    "spmv_c_sptrsv_cpu_csr_multi": (c_int, [POINTER(CSRMatrix), c_void_p, c_int, c_void_p, c_int, c_int,
+                                            POINTER(SpTRSVConfig)]),
+    "spmv_c_cg_solve_multi_ic": (c_int, [POINTER(CSRMatrix), POINTER(CSRMatrix), c_void_p, c_int, c_void_p, c_int,
+                                         c_int, POINTER(CGConfig), POINTER(CGResult)]),
     "spmv_c_sptrsv_levels": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, POINTER(c_int32),
                                      POINTER(c_int32)]),
     "spmv_c_compute_bandwidth_csr": (c_int, [POINTER(CSRMatrix), c_float, POINTER(BandwidthMetrics)]),
@@ -1167,6 +1175,57 @@ def sptrsv_cpu_csr(A, b, config=None) -> np.ndarray:
     if status != 0:
         raise ValueError(spmv_error_string(status))
     return x
+
+
+def sptrsv_csr_multi(A, d_B, d_X, k, ldb=None, ldx=None, config=None) -> SpTRSVResult:
+    """sptrsv_csr for k right-hand sides in one launch sequence (include/spmv/sptrsv.h sptrsv_csr_multi): d_B and d_X
+    are num_rows x k row-major with leading dimensions ldb, ldx >= k (default k) and may be the same buffer when
+    ldb == ldx."""
+    k = int(k)
+    out = SpTRSVResult()
+    lib().spmv_c_sptrsv_csr_multi(A, _dev(d_B), k if ldb is None else int(ldb), _dev(d_X),
+                                  k if ldx is None else int(ldx), k, byref(config) if config is not None else None,
+                                  byref(out))
+    return out
+
+
+def sptrsv_csr_multi_async(A, d_B, d_X, k, ldb=None, ldx=None, config=None, stream=None) -> int:
+    k = int(k)
+    return lib().spmv_c_sptrsv_csr_multi_async(A, _dev(d_B), k if ldb is None else int(ldb), _dev(d_X),
+                                               k if ldx is None else int(ldx), k,
+                                               byref(config) if config is not None else None, c_void_p(stream))
+
+
+def sptrsv_cpu_csr_multi(A, B, config=None) -> np.ndarray:
+    """sptrsv_cpu_csr column by column on the num_rows x k host array B (include/spmv/sptrsv.h
+    sptrsv_cpu_csr_multi): returns X (num_rows x k); raises ValueError with the library's error string when the call
+    is rejected."""
+    B = np.ascontiguousarray(B, dtype=np.float32)
+    if B.ndim != 2:
+        raise ValueError("B must be num_rows x k")
+    k = B.shape[1]
+    X = np.zeros_like(B)
+    status = lib().spmv_c_sptrsv_cpu_csr_multi(A, _np_ptr(B), k, _np_ptr(X), k, k,
+                                               byref(config) if config is not None else None)
+    if status != 0:
+        raise ValueError(spmv_error_string(status))
+    return X
+
+
+def cg_solve_multi_ic(A, F, d_B, d_X, k, ldb=None, ldx=None, config=None) -> list:
+    """cg_solve_ic for k right-hand sides (include/spmv/cg.h cg_solve_multi_ic): cg_solve_multi's arrays and results,
+    preconditioned by M = L L^T of the factor matrix F with one k-wide launch sequence per triangular solve."""
+    k = int(k)
+    ldb = k if ldb is None else int(ldb)
+    ldx = k if ldx is None else int(ldx)
+    out = (CGResult * max(k, 1))()
+    rc = lib().spmv_c_cg_solve_multi_ic(A, F, _dev(d_B), ldb, _dev(d_X), ldx, k,
+                                        byref(config) if config is not None else None, out)
+    results = list(out)
+    if rc != 0:
+        for r in results:
+            r.error_code = rc
+    return results
 
 
 def sptrsv_levels(num_rows, row_ptrs, col_indices, uplo=0):

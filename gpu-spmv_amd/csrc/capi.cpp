@@ -528,6 +528,12 @@ int spmv_c_cg_solve_multi(const spmv_c_csr* A, const float* d_B, int ldb, float*
                           reinterpret_cast<CGResult*>(results));
 }
 
+int spmv_c_cg_solve_multi_ic(const spmv_c_csr* A, const spmv_c_csr* F, const float* d_B, int ldb, float* d_X, int ldx,
+                             int k, const spmv_c_cg_config* config, spmv_c_cg_result* results) {
+    return cg_solve_multi_ic(cxx(A), cxx(F), d_B, ldb, d_X, ldx, k, reinterpret_cast<const CGConfig*>(config),
+                             reinterpret_cast<CGResult*>(results));
+}
+
 int spmv_c_cg_solve_ic(const spmv_c_csr* A, const spmv_c_csr* F, const float* d_b, float* d_x,
                        const spmv_c_cg_config* config, spmv_c_cg_result* out) {
     const CGResult r = cg_solve_ic(cxx(A), cxx(F), d_b, d_x, reinterpret_cast<const CGConfig*>(config));
@@ -673,7 +679,26 @@ int spmv_c_sptrsv_cpu_csr(const spmv_c_csr* A, const float* b, float* x, const s
     return sptrsv_cpu_csr(cxx(A), b, x, reinterpret_cast<const SpTRSVConfig*>(config));
 }
 
-int spmv_c_sptrsv_levels(int num_rows, const int32_t* row_ptrs, const int32_t* col_indices, int uplo,
+int spmv_c_sptrsv_csr_multi(const spmv_c_csr* A, const float* d_B, int ldb, float* d_X, int ldx, int k,
+                            const spmv_c_sptrsv_config* config, spmv_c_sptrsv_result* out) {
+    const SpTRSVResult r = sptrsv_csr_multi(cxx(A), d_B, ldb, d_X, ldx, k,
+                                            reinterpret_cast<const SpTRSVConfig*>(config));
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
+}
+
+int spmv_c_sptrsv_csr_multi_async(const spmv_c_csr* A, const float* d_B, int ldb, float* d_X, int ldx, int k,
+                                  const spmv_c_sptrsv_config* config, void* hip_stream) {
+    return sptrsv_csr_multi_async(cxx(A), d_B, ldb, d_X, ldx, k, reinterpret_cast<const SpTRSVConfig*>(config),
+                                  as_stream(hip_stream));
+}
+
+int spmv_c_sptrsv_cpu_csr_multi(const spmv_c_csr* A, const float* B, int ldb, float* X, int ldx, int k,
+                                const spmv_c_sptrsv_config* config) {
+    return sptrsv_cpu_csr_multi(cxx(A), B, ldb, X, ldx, k, reinterpret_cast<const SpTRSVConfig*>(config));
+}
+
+int spmv_c_sptrsv_levels(int num_rows,const int32_t* row_ptrs, const int32_t* col_indices, int uplo,
                          int32_t* level_ptr, int32_t* order, int32_t* num_levels, int32_t* first_missing_diagonal) {
     return sptrsv_levels(num_rows, row_ptrs, col_indices, uplo, level_ptr, order, num_levels, first_missing_diagonal);
 }

@@ -14,10 +14,23 @@
 // kernels owns row i of the k-wide vectors where cg.hip's owns element i, and each column's partials are laid out
 // and folded as cg.hip lays out and folds its own.  A column that is done is frozen: no kernel writes its x, r, p
 // or state again.  No float atomics, no waiting between workgroups.
+//
+// cg_solve_multi_ic is cg.hip's stored-z loop, k-wide: Z is a fourth windowed array, the SpMV half
+// of a step is cgm_spmv_dot unchanged, and the second half is
+//   cgm_ic_update_kernel<W>     as cgm_update_kernel, but only the partials of r.r (z does not exist yet)
+//   launch_sptrsv_multi x 2     Z = L^-1 R (LOWER NON_UNIT), then Z = L^-T Z in place (UPPER NON_UNIT): ONE k-wide
+//                               launch sequence each (sptrsv_multi.hip on the windowed workspace, no copy)
+//   cgm_rz_kernel<W>            per column the partials of r.z
+//   cgm_ic_direction_kernel<W>  as cgm_direction_kernel with z read from memory
+// so a step has cg_solve_ic's launches whatever k.  The triangular solves do not read `done`, as cg.hip's do not: they
+// recompute Z for all k columns (the padding columns of the last window included) from an R that no longer changes
+// for a frozen column.  A frozen column's Z is never read: cgm_rz_kernel and cgm_ic_direction_kernel skip it.
 #include "internal.h"
 #include "device_common.h"
+#include "multi_window.h"
 #include "solver_common.h"
 #include "spmv/cg.h"
+#include "spmv/sptrsv.h"
 
 #include <hip/hip_runtime.h>
 
@@ -57,40 +70,6 @@ struct CgMultiState {
 };
 
 constexpr size_t kHeaderBytes = offsetof(CgMultiState, col);
-
-// W floats of row `row` of the row-major array V (leading dimension ld), from column j0 (a multiple of 4) on;
-// columns at or past `limit` come back 0.  vec: V is 16-byte aligned and ld % 4 == 0, so every group of four
-// columns that lies below `limit` loads as dwordx4; the rest are guarded scalar loads.
-template <int W>
-__device__ __forceinline__ void load_window(const float* __restrict__ V, long long ld, long long row, int j0,
-                                            int limit, bool vec, float (&out)[W]) {
-    const float* p = V + row * ld + j0;
-#pragma unroll
-    for (int g = 0; g < W; g += 4) {
-        if (vec && j0 + g + 4 <= limit) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(p + g);
-            out[g] = v[0]; out[g + 1] = v[1]; out[g + 2] = v[2]; out[g + 3] = v[3];
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) out[g + e] = j0 + g + e < limit ? p[g + e] : 0.0f;
-        }
-    }
-}
-
-// load_window on the solver's own arrays: they are 16-byte aligned with ld a multiple of 4 and padded to ld, so every
-// group of four columns below ld loads as dwordx4 (the padding columns hold nothing that is ever used).  The loop
-// kernels pass one window (ld = W, j0 = 0): W / 4 unconditional loads.
-template <int W>
-__device__ __forceinline__ void load_own(const float* __restrict__ V, long long ld, long long row, int j0,
-                                         float (&out)[W]) {
-    const float* p = V + row * ld + j0;
-#pragma unroll
-    for (int g = 0; g < W; g += 4) {
-        f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (j0 + g < ld) v = *reinterpret_cast<const f32x4*>(p + g);
-        out[g] = v[0]; out[g + 1] = v[1]; out[g + 2] = v[2]; out[g + 3] = v[3];
-    }
-}
 
 // block_sum2's sum of N values at once behind two barriers in all: the same xor butterfly inside each wavefront,
 // then the wavefronts' totals added in wave order, so thread c (< N) returns for v[c] the very bits block_sum2 leaves
@@ -519,6 +498,200 @@ void cgm_direction_kernel(int n, int step, int k, const float* __restrict__ r, c
     if (commits && finished == k) state->done = 1;
 }
 
+// cg.hip's cg_ic_diag_kernel on the k-wide state: some row of the factor has no stored diagonal, or one that is not
+// > 0 or not finite.
+__global__ __launch_bounds__(kBlock)
+void cgm_ic_diag_kernel(int n, const int* __restrict__ row_ptrs, const int* __restrict__ cols,
+                        const float* __restrict__ vals, CgMultiState* __restrict__ state) {
+    int bad = 0;
+    for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < n;
+         i += static_cast<long long>(gridDim.x) * kBlock) {
+        float d = 0.0f;
+        int found = 0;
+        for (int j = row_ptrs[i]; j < row_ptrs[i + 1]; ++j) {
+            if (cols[j] == i) {
+                d = __fadd_rn(d, vals[j]);
+                found = 1;
+            }
+        }
+        bad |= !(found && d > 0.0f && isfinite(d));
+    }
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(&state->bad_diagonal, 1);
+}
+
+// IC: cgm_update_kernel without z: per column alpha, x += alpha p, r -= alpha q, and the partials of r.r alone ->
+// part_out[(2 * gridDim.x) * column + 2 * block + 1] (cgm_update_kernel's slot; r.z follows from cgm_rz_kernel).
+template <int W>
+__global__ __launch_bounds__(kBlock)
+void cgm_ic_update_kernel(int n, int step, int k, const float* __restrict__ p, const float* __restrict__ q,
+                          float* __restrict__ X, long long ldx, float* __restrict__ r,
+                          CgMultiState* __restrict__ state, const double* __restrict__ pq_part, int pq_count,
+                          long long pq_stride, double* __restrict__ part_out) {
+    const unsigned active = active_columns(state, k);
+    if (!active) return;
+    const long long out_stride = 2LL * gridDim.x;
+    for (int j0 = 0; j0 < k; j0 += W) {
+        const unsigned running = (active >> j0) & ((1u << W) - 1u);
+        if (!running) continue;
+        double pq[W];
+#pragma unroll
+        for (int c = 0; c < W; ++c) pq[c] = 0.0;
+        for (int i = threadIdx.x; i < pq_count; i += kBlock) {
+#pragma unroll
+            for (int c = 0; c < W; ++c) pq[c] += pq_part[pq_stride * (j0 + c) + i];   // (all W: the array is padded)
+        }
+        fold_values<W>(pq);
+        float alpha[W];
+        unsigned m = 0;
+#pragma unroll
+        for (int c = 0; c < W; ++c) {
+            alpha[c] = 0.0f;
+            if (!((running >> c) & 1u)) continue;
+            const int j = j0 + c;
+            if (!(pq[c] > 0.0)) {          // this column's A is not SPD (or p.q is not finite): its x stays as it is
+                if (blockIdx.x == 0 && threadIdx.x == 0) {
+                    state->col[j].breakdown = 1;
+                    state->col[j].done = 1;
+                }
+            } else {
+                alpha[c] = static_cast<float>(state->col[j].rz[step & 1] / pq[c]);
+                m |= 1u << c;
+            }
+        }
+        if (!m) continue;
+        double sums[W];               // r.r of column j0 + c
+#pragma unroll
+        for (int c = 0; c < W; ++c) sums[c] = 0.0;
+        const long long window = static_cast<long long>(j0 / W) * n * W;
+        const float* pw = p + window;
+        const float* qw = q + window;
+        float* rw = r + window;
+        for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < n;
+             i += static_cast<long long>(gridDim.x) * kBlock) {
+            float pv[W], qv[W], rv[W];
+            load_own<W>(pw, W, i, 0, pv);
+            load_own<W>(qw, W, i, 0, qv);
+            load_own<W>(rw, W, i, 0, rv);
+#pragma unroll
+            for (int c = 0; c < W; ++c) {
+                if ((m >> c) & 1u) {
+                    float* xi = X + i * ldx + j0 + c;
+                    *xi = __builtin_fmaf(alpha[c], pv[c], *xi);
+                    const float ri = __builtin_fmaf(-alpha[c], qv[c], rv[c]);
+                    rw[i * W + c] = ri;
+                    sums[c] += prod64(ri, ri);
+                }
+            }
+        }
+        const double total = block_sum_columns<W>(sums);
+        const int c = threadIdx.x;
+        if (c < W && ((m >> c) & 1u)) part_out[out_stride * (j0 + c) + 2LL * blockIdx.x + 1] = total;
+    }
+}
+
+// IC: per column the block partials of r.z -> part[col_stride * column + stride * block] (stride 2 and the loop's
+// grid inside the loop, stride 3 and the row grid over the init partials, as cg.hip's cg_rz_kernel).
+template <int W>
+__global__ __launch_bounds__(kBlock)
+void cgm_rz_kernel(int n, int k, const float* __restrict__ r, const float* __restrict__ z,
+                   const CgMultiState* __restrict__ state, double* __restrict__ part, long long col_stride,
+                   int stride) {
+    const unsigned active = active_columns(state, k);
+    if (!active) return;
+    for (int j0 = 0; j0 < k; j0 += W) {
+        const unsigned running = (active >> j0) & ((1u << W) - 1u);
+        if (!running) continue;
+        double sums[W];
+#pragma unroll
+        for (int c = 0; c < W; ++c) sums[c] = 0.0;
+        const long long window = static_cast<long long>(j0 / W) * n * W;
+        const float* rw = r + window;
+        const float* zw = z + window;
+        for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < n;
+             i += static_cast<long long>(gridDim.x) * kBlock) {
+            float rv[W], zv[W];
+            load_own<W>(rw, W, i, 0, rv);
+            load_own<W>(zw, W, i, 0, zv);
+#pragma unroll
+            for (int c = 0; c < W; ++c) sums[c] += prod64(rv[c], zv[c]);
+        }
+        const double total = block_sum_columns<W>(sums);
+        const int c = threadIdx.x;
+        if (c < W && ((running >> c) & 1u)) {
+            part[col_stride * (j0 + c) + static_cast<long long>(stride) * blockIdx.x] = total;
+        }
+    }
+}
+
+// IC: cgm_direction_kernel with the stored z.
+template <int W>
+__global__ __launch_bounds__(kBlock)
+void cgm_ic_direction_kernel(int n, int step, int k, const float* __restrict__ z, float* __restrict__ p,
+                             CgMultiState* __restrict__ state, const double* __restrict__ part, int count) {
+    const unsigned active = active_columns(state, k);
+    if (!active) return;
+    const bool commits = blockIdx.x == 0 && threadIdx.x == 0;
+    int finished = k - __popc(active);
+    for (int j0 = 0; j0 < k; j0 += W) {
+        const unsigned running = (active >> j0) & ((1u << W) - 1u);
+        if (!running) continue;
+        double sums[2 * W];
+#pragma unroll
+        for (int c = 0; c < 2 * W; ++c) sums[c] = 0.0;
+        for (int i = threadIdx.x; i < count; i += kBlock) {
+#pragma unroll
+            for (int c = 0; c < W; ++c) {         // (all W: the array is padded)
+                const double* mine = part + 2LL * count * (j0 + c) + 2LL * i;
+                sums[2 * c] += mine[0];
+                sums[2 * c + 1] += mine[1];
+            }
+        }
+        fold_values<2 * W>(sums);
+        float beta[W];
+        unsigned m = 0;
+#pragma unroll
+        for (int c = 0; c < W; ++c) {
+            beta[c] = 0.0f;
+            if (!((running >> c) & 1u)) continue;
+            CgColumn& col = state->col[j0 + c];
+            const double rz = sums[2 * c], rr = sums[2 * c + 1];
+            const double res = sqrt(rr);
+            const bool converged = res <= col.threshold;
+            const bool breakdown = !converged && !(rz > 0.0);
+            const double rz_old = col.rz[step & 1];
+            if (commits) {
+                col.iterations = step + 1;
+                col.relative_residual = static_cast<float>(res / col.bnorm);
+                col.rz[(step + 1) & 1] = rz;
+                if (converged) col.converged = 1;
+                if (breakdown) col.breakdown = 1;
+                if (converged || breakdown) col.done = 1;
+            }
+            if (converged || breakdown) {
+                ++finished;
+            } else {
+                beta[c] = static_cast<float>(rz / rz_old);
+                m |= 1u << c;
+            }
+        }
+        if (!m) continue;
+        const long long window = static_cast<long long>(j0 / W) * n * W;
+        const float* zw = z + window;
+        float* pw = p + window;
+        for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < n;
+             i += static_cast<long long>(gridDim.x) * kBlock) {
+            float zv[W], pv[W];
+            load_own<W>(zw, W, i, 0, zv);
+            load_own<W>(pw, W, i, 0, pv);
+#pragma unroll
+            for (int c = 0; c < W; ++c) {
+                if ((m >> c) & 1u) pw[i * W + c] = __builtin_fmaf(beta[c], pv[c], zv[c]);
+            }
+        }
+    }
+    if (commits && finished == k) state->done = 1;
+}
+
 struct Shape {
     const CSRMatrix* A;
     int k;
@@ -573,8 +746,9 @@ bool spans_overlap(const float* a, long long na, const float* b, long long nb) {
            b0 < a0 + static_cast<uintptr_t>(na) * sizeof(float);
 }
 
-int solve_multi(const CSRMatrix* A, const float* d_B, int ldb, float* d_X, int ldx, int k, const CGConfig* config,
-                CGResult* results) {
+// F: the factor matrix of cg_solve_multi_ic (with_ic), not read otherwise
+int solve_multi(const CSRMatrix* A, bool with_ic, const CSRMatrix* F, const float* d_B, int ldb, float* d_X, int ldx,
+                int k, const CGConfig* config, CGResult* results) {
     const auto fail = [&](SpMVError e) {
         if (results && k >= 1 && k <= kMaxColumns) {       // a k out of range says nothing about the array's length
             for (int j = 0; j < k; ++j) results[j].error_code = code(e);
@@ -598,7 +772,7 @@ int solve_multi(const CSRMatrix* A, const float* d_B, int ldb, float* d_X, int l
     const CGConfig defaults;
     const CGConfig& cfg = config ? *config : defaults;
     if (!(cfg.tolerance >= 0.0f) || cfg.max_iterations < 0 ||
-        (cfg.preconditioner != CGConfig::NONE && cfg.preconditioner != CGConfig::JACOBI) ||
+        (!with_ic && cfg.preconditioner != CGConfig::NONE && cfg.preconditioner != CGConfig::JACOBI) ||
         cfg.engine < -1 || cfg.engine > 0) {          // the LDS-tiled engine has no k-wide form
         return fail(SpMVError::INVALID_ARGUMENT);
     }
@@ -606,10 +780,30 @@ int solve_multi(const CSRMatrix* A, const float* d_B, int ldb, float* d_X, int l
     if (spans_overlap(d_B, static_cast<long long>(n - 1) * ldb + k, d_X, static_cast<long long>(n - 1) * ldx + k)) {
         return fail(SpMVError::INVALID_ARGUMENT);
     }
+    if (with_ic) {
+        if (!F) return fail(SpMVError::INVALID_ARGUMENT);
+        if (F->num_rows != F->num_cols || F->num_rows != n) return fail(SpMVError::INVALID_DIMENSION);
+        if (F->num_rows < 0 || !F->d_row_ptrs || (F->nnz > 0 && (!F->d_col_indices || !F->d_values))) {
+            return fail(SpMVError::INVALID_FORMAT);
+        }
+    }
 
-    const TraceRange range("spmv:cg_solve_multi");
+    const TraceRange range(with_ic ? "spmv:cg_solve_multi_ic" : "spmv:cg_solve_multi");
     hipStream_t stream = current_stream();
-    const bool jacobi = cfg.preconditioner == CGConfig::JACOBI;
+    const bool jacobi = !with_ic && cfg.preconditioner == CGConfig::JACOBI;
+
+    // both schedules of F, ahead of the timed loop (a build synchronises the stream); they validate F's structure
+    // before any kernel walks it
+    std::shared_ptr<const SptrsvSchedule> lower, upper;
+    int lower_lanes = 1, upper_lanes = 1;
+    if (with_ic) {
+        float analysis_ms = 0.0f;
+        int status = sptrsv_schedule_for(F, SpTRSVConfig::LOWER, stream, &lower, &analysis_ms);
+        if (status == 0) status = sptrsv_schedule_for(F, SpTRSVConfig::UPPER, stream, &upper, &analysis_ms);
+        if (status != 0) return fail(static_cast<SpMVError>(status));
+        lower_lanes = sptrsv_lanes_for(*lower);
+        upper_lanes = sptrsv_lanes_for(*upper);
+    }
 
     const int lanes = pick_lanes_per_row(static_cast<float>(A->nnz) / n);
     const int row_grid = grid_for_rows(n, kBlock / lanes);
@@ -619,10 +813,10 @@ int solve_multi(const CSRMatrix* A, const float* d_B, int ldb, float* d_X, int l
     const size_t init_count = 3 * static_cast<size_t>(row_grid);
     const Shape sh{A, k, k <= 4 ? 4 : 8};
 
-    Workspace<CgMultiState> ws;       // R, P, Q (ceil(k / w) windows of n x w each) and dinv (JACOBI)
+    Workspace<CgMultiState> ws;       // R, P, Q (ceil(k / w) windows of n x w each) and dinv (JACOBI) or Z (IC)
     const size_t len = static_cast<size_t>(n) * static_cast<size_t>((k + sh.w - 1) / sh.w * sh.w);
     const size_t k_pad = len / static_cast<size_t>(n);       // whole windows: the folds read all W columns of one
-    if (!ws.allocate(3 * len + (jacobi ? static_cast<size_t>(n) : 0),
+    if (!ws.allocate(3 * len + (jacobi ? static_cast<size_t>(n) : with_ic ? len : 0),
                      k_pad * (pq_count + rr_count) + static_cast<size_t>(k) * init_count)) {
         return fail(SpMVError::CUDA_MALLOC);
     }
@@ -630,11 +824,20 @@ int solve_multi(const CSRMatrix* A, const float* d_B, int ldb, float* d_X, int l
     float* p = ws.vec + len;
     float* q = ws.vec + 2 * len;
     float* dinv = jacobi ? ws.vec + 3 * len : nullptr;
+    float* z = with_ic ? ws.vec + 3 * len : nullptr;
     double* pq_part = ws.part;
     double* rr_part = pq_part + k_pad * pq_count;
     double* init_part = rr_part + k_pad * rr_count;
     CgMultiState* pinned = ws.pinned;
     const bool wide = k > 4;
+    // Z = L^-T (L^-1 R) on the windowed workspace, whole windows (the padding columns are solved along and never used)
+    const auto apply_ic = [&]() -> bool {
+        const long long window = static_cast<long long>(n) * sh.w;
+        const SptrsvMultiArrays down{r, sh.w, window, z, sh.w, window, static_cast<int>(k_pad), sh.w};
+        const SptrsvMultiArrays up{z, sh.w, window, z, sh.w, window, static_cast<int>(k_pad), sh.w};
+        return launch_sptrsv_multi(*lower, F, down, SpTRSVConfig::LOWER, 0, false, lower_lanes, stream) == hipSuccess &&
+               launch_sptrsv_multi(*upper, F, up, SpTRSVConfig::UPPER, 0, false, upper_lanes, stream) == hipSuccess;
+    };
 
     // setup: the shared diagonal, R0 / P0 and their dots, the column states; one read-back
     bool ok = hipMemsetAsync(ws.state, 0, sizeof(CgMultiState), stream) == hipSuccess;
@@ -643,7 +846,22 @@ int solve_multi(const CSRMatrix* A, const float* d_B, int ldb, float* d_X, int l
                                                       ws.state);
         ok = hipGetLastError() == hipSuccess;
     }
+    if (ok && with_ic) {
+        cgm_ic_diag_kernel<<<vgrid, kBlock, 0, stream>>>(n, F->d_row_ptrs, F->d_col_indices, F->d_values, ws.state);
+        ok = hipGetLastError() == hipSuccess;
+    }
     ok = ok && init(lanes, sh, d_B, ldb, d_X, ldx, dinv, r, p, init_part, row_grid, stream) == hipSuccess;
+    if (ok && with_ic) {
+        // the init kernel left P0 = R0 and r0.r0 in the r.z slots: Z0 = M^-1 R0, the true r0.z0 over them, P0 = Z0
+        ok = apply_ic();
+        if (ok) {
+            const long long stride = 3LL * row_grid;
+            if (wide) cgm_rz_kernel<8><<<row_grid, kBlock, 0, stream>>>(n, k, r, z, ws.state, init_part, stride, 3);
+            else      cgm_rz_kernel<4><<<row_grid, kBlock, 0, stream>>>(n, k, r, z, ws.state, init_part, stride, 3);
+            ok = hipGetLastError() == hipSuccess &&
+                 hipMemcpyAsync(p, z, len * sizeof(float), hipMemcpyDeviceToDevice, stream) == hipSuccess;
+        }
+    }
     if (ok) {
         cgm_start_kernel<<<1, kBlock, 0, stream>>>(init_part, row_grid, k, cfg.tolerance, ws.state);
         ok = hipGetLastError() == hipSuccess;
@@ -670,8 +888,26 @@ int solve_multi(const CSRMatrix* A, const float* d_B, int ldb, float* d_X, int l
         for (int iter = 0; ok && iter < cfg.max_iterations; ++iter) {
             const TraceRange step_range("spmv:cg_multi_step");
             ok = spmv_dot(lanes, sh, p, q, ws.state, pq_part, row_grid, stream) == hipSuccess;
-            if (ok) {
+            if (ok && with_ic) {
                 if (wide) {
+                    cgm_ic_update_kernel<8><<<vgrid, kBlock, 0, stream>>>(n, iter, k, p, q, d_X, ldx, r, ws.state,
+                                                                          pq_part, row_grid, row_grid, rr_part);
+                } else {
+                    cgm_ic_update_kernel<4><<<vgrid, kBlock, 0, stream>>>(n, iter, k, p, q, d_X, ldx, r, ws.state,
+                                                                          pq_part, row_grid, row_grid, rr_part);
+                }
+                ok = hipGetLastError() == hipSuccess && apply_ic();
+            }
+            if (ok) {
+                if (with_ic && wide) {
+                    cgm_rz_kernel<8><<<vgrid, kBlock, 0, stream>>>(n, k, r, z, ws.state, rr_part, 2LL * vgrid, 2);
+                    cgm_ic_direction_kernel<8><<<vgrid, kBlock, 0, stream>>>(n, iter, k, z, p, ws.state, rr_part,
+                                                                             vgrid);
+                } else if (with_ic) {
+                    cgm_rz_kernel<4><<<vgrid, kBlock, 0, stream>>>(n, k, r, z, ws.state, rr_part, 2LL * vgrid, 2);
+                    cgm_ic_direction_kernel<4><<<vgrid, kBlock, 0, stream>>>(n, iter, k, z, p, ws.state, rr_part,
+                                                                             vgrid);
+                } else if (wide) {
                     cgm_update_kernel<8><<<vgrid, kBlock, 0, stream>>>(n, iter, k, p, q, dinv, d_X, ldx, r,
                                                                        ws.state, pq_part, row_grid, row_grid,
                                                                        rr_part);
@@ -728,7 +964,12 @@ int solve_multi(const CSRMatrix* A, const float* d_B, int ldb, float* d_X, int l
 
 int cg_solve_multi(const CSRMatrix* A, const float* d_B, int ldb, float* d_X, int ldx, int k,
                    const CGConfig* config, CGResult* results) {
-    return detail::solve_multi(A, d_B, ldb, d_X, ldx, k, config, results);
+    return detail::solve_multi(A, false, nullptr, d_B, ldb, d_X, ldx, k, config, results);
+}
+
+int cg_solve_multi_ic(const CSRMatrix* A, const CSRMatrix* F, const float* d_B, int ldb, float* d_X, int ldx, int k,
+                      const CGConfig* config, CGResult* results) {
+    return detail::solve_multi(A, true, F, d_B, ldb, d_X, ldx, k, config, results);
 }
 
 } // namespace spmv

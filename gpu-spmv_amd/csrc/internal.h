@@ -245,6 +245,22 @@ constexpr int kSptrsvNarrowRows = 256;
 constexpr int kSptrsvMaxRunLevels = 8192;     // levels per single-workgroup launch at most (bounds one kernel's time)
 hipError_t launch_sptrsv(const SptrsvSchedule& schedule, const CSRMatrix* A, const float* d_b, float* d_x, int uplo,
                          int unit_diagonal, bool ordered, int lanes_per_row, hipStream_t s);
+// The k-wide solve (sptrsv_multi.hip): the same launches for k columns at once.  Column c of row i lives at
+// base + (c / w) * window + i * ld + c % w, w = 4 or 8 accumulators per lane: a caller's num_rows x k array has
+// window = w, the windowed workspace of cg_multi.hip (num_rows x w arrays one after another) window = num_rows * w
+// and ld = w.  B may be X (the same ld and window): the solve in place.
+struct SptrsvMultiArrays {
+    const float* B;
+    int ldb;
+    long long b_window;
+    float* X;
+    int ldx;
+    long long x_window;
+    int k;                           // columns solved: [0, k)
+    int w;                           // 4 or 8
+};
+hipError_t launch_sptrsv_multi(const SptrsvSchedule& schedule, const CSRMatrix* A, const SptrsvMultiArrays& arrays,
+                               int uplo, int unit_diagonal, bool ordered, int lanes_per_row, hipStream_t s);
 // b and x overlap without being the same array (solver_common.h ranges_overlap; the solve in place is allowed)
 bool sptrsv_partial_overlap(const float* d_b, const float* d_x, long long n);
 // the schedule cache of sptrsv_host.cpp for the callers that solve or factor with it (ilu0_host.cpp, bicgstab.hip):

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cstdint>
 #include <vector>
 
 namespace spmv {
@@ -110,6 +111,73 @@ int sptrsv_cpu_csr(const CSRMatrix* A, const float* b, float* x, const SpTRSVCon
             }
         }
         x[i] = (b[i] - s) / (unit ? 1.0f : d);
+    }
+    return code(SpMVError::SUCCESS);
+}
+
+int sptrsv_cpu_csr_multi(const CSRMatrix* A, const float* B, int ldb, float* X, int ldx, int k,
+                         const SpTRSVConfig* config) {
+    using detail::code;
+    if (!A || !B || !X) return code(SpMVError::INVALID_ARGUMENT);
+    if (k < 1 || k > 32) return code(SpMVError::INVALID_ARGUMENT);
+    if (ldb < k || ldx < k) return code(SpMVError::INVALID_ARGUMENT);
+    if (A->num_rows != A->num_cols) return code(SpMVError::INVALID_DIMENSION);
+    const int n = A->num_rows;
+    if (n == 0) return code(SpMVError::SUCCESS);
+    if (n < 0 || !A->row_ptrs || (A->nnz > 0 && (!A->col_indices || !A->values))) {
+        return code(SpMVError::INVALID_ARGUMENT);
+    }
+    const SpTRSVConfig defaults;
+    const SpTRSVConfig& cfg = config ? *config : defaults;
+    if ((cfg.uplo != SpTRSVConfig::LOWER && cfg.uplo != SpTRSVConfig::UPPER) ||
+        (cfg.diag != SpTRSVConfig::NON_UNIT && cfg.diag != SpTRSVConfig::UNIT)) {
+        return code(SpMVError::INVALID_ARGUMENT);
+    }
+    if (!(B == X && ldb == ldx)) {
+        const uintptr_t b0 = reinterpret_cast<uintptr_t>(B), x0 = reinterpret_cast<uintptr_t>(X);
+        const uintptr_t nb = (static_cast<uintptr_t>(n - 1) * ldb + k) * sizeof(float);
+        const uintptr_t nx = (static_cast<uintptr_t>(n - 1) * ldx + k) * sizeof(float);
+        if (b0 < x0 + nx && x0 < b0 + nb) return code(SpMVError::INVALID_ARGUMENT);
+    }
+    const bool upper = cfg.uplo == SpTRSVConfig::UPPER;
+    const bool unit = cfg.diag == SpTRSVConfig::UNIT;
+    const int* ptr = A->row_ptrs;
+    const int* col = A->col_indices;
+    // everything that can fail, before X is touched
+    if (ptr[0] < 0 || ptr[n] > A->nnz) return code(SpMVError::INVALID_FORMAT);
+    for (int i = 0; i < n; ++i) {
+        if (ptr[i + 1] < ptr[i]) return code(SpMVError::INVALID_FORMAT);
+    }
+    bool every_diagonal = true;
+    for (int i = 0; i < n; ++i) {
+        bool diagonal = false;
+        for (int j = ptr[i]; j < ptr[i + 1]; ++j) {
+            if (col[j] < 0 || col[j] >= n) return code(SpMVError::INVALID_FORMAT);
+            diagonal |= col[j] == i;
+        }
+        every_diagonal &= diagonal;
+    }
+    if (!unit && !every_diagonal) return code(SpMVError::INVALID_ARGUMENT);
+
+    // sptrsv_cpu_csr's substitution with the row's entries walked once per column; the diagonal once per row
+    for (int step = 0; step < n; ++step) {
+        const int i = upper ? n - 1 - step : step;
+        float d = 0.0f;
+        for (int j = ptr[i]; j < ptr[i + 1]; ++j) {
+            if (col[j] == i) d = d + A->values[j];
+        }
+        const size_t row_b = static_cast<size_t>(i) * ldb, row_x = static_cast<size_t>(i) * ldx;
+        for (int q = 0; q < k; ++q) {
+            float s = 0.0f;
+            for (int j = ptr[i]; j < ptr[i + 1]; ++j) {
+                const int c = col[j];
+                if (c != i && (upper ? c > i : c < i)) {
+                    const float product = A->values[j] * X[static_cast<size_t>(c) * ldx + q];
+                    s = s + product;
+                }
+            }
+            X[row_x + q] = (B[row_b + q] - s) / (unit ? 1.0f : d);
+        }
     }
     return code(SpMVError::SUCCESS);
 }
@@ -251,12 +319,12 @@ int lanes_for(const SptrsvSchedule& s, bool ordered) {
     return pick_lanes_per_row(static_cast<float>(s.triangle_nnz) / static_cast<float>(s.num_rows));
 }
 
-// Everything before the launches.  On SUCCESS with *schedule null there is nothing to do (no rows).
-int prepare(const CSRMatrix* A, const float* d_b, const float* d_x, const SpTRSVConfig& cfg, hipStream_t stream,
-            ScheduleRef* schedule, float* analysis_ms) {
-    schedule->reset();
-    *analysis_ms = 0.0f;
-    if (!A || !d_b || !d_x) return code(SpMVError::INVALID_ARGUMENT);
+// Everything before the launches, from the dimension check on.  overlaps(): the arrays overlap in a way the solve
+// does not allow (asked once A's dimensions are known to be sane).  On SUCCESS with *schedule null there is nothing
+// to do (no rows).
+template <class Overlaps>
+int prepare_checked(const CSRMatrix* A, const SpTRSVConfig& cfg, hipStream_t stream, Overlaps&& overlaps,
+                    ScheduleRef* schedule, float* analysis_ms) {
     bool nothing = false;
     const int status = check_matrix(A, &nothing);
     if (status != 0 || nothing) return status;
@@ -265,7 +333,7 @@ int prepare(const CSRMatrix* A, const float* d_b, const float* d_x, const SpTRSV
         (cfg.ordered != 0 && cfg.ordered != 1)) {
         return code(SpMVError::INVALID_ARGUMENT);
     }
-    if (sptrsv_partial_overlap(d_b, d_x, A->num_rows)) return code(SpMVError::INVALID_ARGUMENT);
+    if (overlaps()) return code(SpMVError::INVALID_ARGUMENT);
     ScheduleRef found;
     const int analysed = schedule_for(A, cfg.uplo, stream, &found, analysis_ms);
     if (analysed != 0) return analysed;
@@ -274,6 +342,55 @@ int prepare(const CSRMatrix* A, const float* d_b, const float* d_x, const SpTRSV
     }
     *schedule = found;
     return code(SpMVError::SUCCESS);
+}
+
+int prepare(const CSRMatrix* A, const float* d_b, const float* d_x, const SpTRSVConfig& cfg, hipStream_t stream,
+            ScheduleRef* schedule, float* analysis_ms) {
+    schedule->reset();
+    *analysis_ms = 0.0f;
+    if (!A || !d_b || !d_x) return code(SpMVError::INVALID_ARGUMENT);
+    return prepare_checked(A, cfg, stream, [&] { return sptrsv_partial_overlap(d_b, d_x, A->num_rows); }, schedule,
+                           analysis_ms);
+}
+
+constexpr int kMaxColumns = 32;
+
+// the floats [a, a + na) and [b, b + nb) share a byte
+bool spans_overlap(const float* a, long long na, const float* b, long long nb) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + static_cast<uintptr_t>(nb) * sizeof(float) &&
+           b0 < a0 + static_cast<uintptr_t>(na) * sizeof(float);
+}
+
+// B and X of a k-wide solve (num_rows x k, leading dimensions ldb, ldx) overlap without being the solve in place
+bool multi_overlap(const float* B, int ldb, const float* X, int ldx, int k, int num_rows) {
+    if (B == X && ldb == ldx) return false;
+    const long long rows = num_rows - 1;
+    return spans_overlap(B, rows * ldb + k, X, rows * ldx + k);
+}
+
+// the checks of sptrsv_csr_multi that come before sptrsv_csr's
+int check_multi(const void* A, const void* B, int ldb, const void* X, int ldx, int k) {
+    if (!A || !B || !X) return code(SpMVError::INVALID_ARGUMENT);
+    if (k < 1 || k > kMaxColumns) return code(SpMVError::INVALID_ARGUMENT);
+    if (ldb < k || ldx < k) return code(SpMVError::INVALID_ARGUMENT);
+    return code(SpMVError::SUCCESS);
+}
+
+int prepare_multi(const CSRMatrix* A, const float* d_B, int ldb, const float* d_X, int ldx, int k,
+                  const SpTRSVConfig& cfg, hipStream_t stream, ScheduleRef* schedule, float* analysis_ms) {
+    schedule->reset();
+    *analysis_ms = 0.0f;
+    const int status = check_multi(A, d_B, ldb, d_X, ldx, k);
+    if (status != 0) return status;
+    return prepare_checked(A, cfg, stream, [&] { return multi_overlap(d_B, ldb, d_X, ldx, k, A->num_rows); },
+                           schedule, analysis_ms);
+}
+
+// a caller's arrays under sptrsv_multi.hip's addressing rule: the windows of w columns lie side by side in a row
+SptrsvMultiArrays caller_arrays(const float* d_B, int ldb, float* d_X, int ldx, int k) {
+    const int w = k <= 4 ? 4 : 8;
+    return SptrsvMultiArrays{d_B, ldb, w, d_X, ldx, w, k, w};
 }
 
 } // namespace
@@ -331,6 +448,53 @@ int sptrsv_csr_async(const CSRMatrix* A, const float* d_b, float* d_x, const SpT
     if (status != 0 || !schedule) return status;
     const hipError_t e = launch_sptrsv(*schedule, A, d_b, d_x, cfg.uplo, cfg.diag == SpTRSVConfig::UNIT,
                                        cfg.ordered == 1, lanes_for(*schedule, cfg.ordered == 1), stream);
+    return e == hipSuccess ? code(SpMVError::SUCCESS) : code(SpMVError::KERNEL_LAUNCH);
+}
+
+SpTRSVResult sptrsv_csr_multi(const CSRMatrix* A, const float* d_B, int ldb, float* d_X, int ldx, int k,
+                              const SpTRSVConfig* config) {
+    using namespace detail;
+    SpTRSVResult result;
+    const SpTRSVConfig defaults;
+    const SpTRSVConfig& cfg = config ? *config : defaults;
+    hipStream_t stream = current_stream();
+    ScheduleRef schedule;
+    result.error_code = prepare_multi(A, d_B, ldb, d_X, ldx, k, cfg, stream, &schedule, &result.analysis_ms);
+    if (result.error_code != 0 || !schedule) return result;
+
+    const TraceRange range("spmv:sptrsv_csr_multi");
+    const int lanes = lanes_for(*schedule, cfg.ordered == 1);
+    result.num_levels = schedule->num_levels;
+    result.launches = static_cast<int>(schedule->groups.size());
+    result.lanes_per_row = lanes;
+    EventPair& ev = thread_events();
+    if (!ev.start || !ev.stop || hipEventRecord(ev.start, stream) != hipSuccess) {
+        result.error_code = code(SpMVError::KERNEL_LAUNCH);
+        return result;
+    }
+    const hipError_t launched = launch_sptrsv_multi(*schedule, A, caller_arrays(d_B, ldb, d_X, ldx, k), cfg.uplo,
+                                                    cfg.diag == SpTRSVConfig::UNIT, cfg.ordered == 1, lanes, stream);
+    const hipError_t recorded = hipEventRecord(ev.stop, stream);
+    const hipError_t waited = hipEventSynchronize(ev.stop);
+    if (launched != hipSuccess || recorded != hipSuccess || waited != hipSuccess || hipGetLastError() != hipSuccess ||
+        hipEventElapsedTime(&result.elapsed_ms, ev.start, ev.stop) != hipSuccess) {
+        result.error_code = code(SpMVError::KERNEL_LAUNCH);
+    }
+    return result;
+}
+
+int sptrsv_csr_multi_async(const CSRMatrix* A, const float* d_B, int ldb, float* d_X, int ldx, int k,
+                           const SpTRSVConfig* config, hipStream_t stream) {
+    using namespace detail;
+    const SpTRSVConfig defaults;
+    const SpTRSVConfig& cfg = config ? *config : defaults;
+    ScheduleRef schedule;
+    float analysis_ms = 0.0f;
+    const int status = prepare_multi(A, d_B, ldb, d_X, ldx, k, cfg, stream, &schedule, &analysis_ms);
+    if (status != 0 || !schedule) return status;
+    const hipError_t e = launch_sptrsv_multi(*schedule, A, caller_arrays(d_B, ldb, d_X, ldx, k), cfg.uplo,
+                                             cfg.diag == SpTRSVConfig::UNIT, cfg.ordered == 1,
+                                             lanes_for(*schedule, cfg.ordered == 1), stream);
     return e == hipSuccess ? code(SpMVError::SUCCESS) : code(SpMVError::KERNEL_LAUNCH);
 }
 

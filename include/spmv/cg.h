@@ -120,6 +120,23 @@ int cg_solve_multi(const CSRMatrix* A, const float* d_B, int ldb, float* d_X, in
 CGResult cg_solve_ic(const CSRMatrix* A, const CSRMatrix* F, const float* d_b, float* d_x,
                      const CGConfig* config = nullptr);
 
+// cg_solve_ic for k right-hand sides: cg_solve_multi's layout (d_B, d_X num_rows x k row-major, ldb, ldx >= k,
+// 1 <= k <= 32, results: k CGResult) with cg_solve_ic's preconditioner M = L L^T from the factor matrix F (DESIGN.md
+// §4.19).  The contract is bitwise: X[:, j] and results[j].iterations / converged / breakdown / relative_residual /
+// error_code equal what cg_solve_ic(A, F, B[:, j], X0[:, j], config) with engine = 0 gives, whatever the other
+// columns do.  Per step the matrix is read once (cg_solve_multi's SpMV half) and the two triangular solves are ONE
+// k-wide launch sequence each (sptrsv_csr_multi's kernel on the solver's windowed workspace): the launches of a step
+// are cg_solve_ic's, whatever k.  Columns freeze as in cg_solve_multi; the triangular solves do not read `done` and
+// recompute z for every column, a frozen column's z is never read.
+//
+// Checks: cg_solve_multi's, in their order (config->preconditioner is not read; engine = 1 -> INVALID_ARGUMENT), then
+// cg_solve_ic's for F: null F -> INVALID_ARGUMENT; F not square or of another size than A -> INVALID_DIMENSION; F's
+// device arrays missing -> INVALID_FORMAT; malformed structure -> INVALID_FORMAT; a row of F whose diagonal is
+// missing, not > 0 or not finite -> INVALID_ARGUMENT (on the device, in the one setup read-back, d_X untouched).  On
+// failure, of `results` only error_code is written.  The workspace is four windowed arrays (r, p, q, z).
+int cg_solve_multi_ic(const CSRMatrix* A, const CSRMatrix* F, const float* d_B, int ldb, float* d_X, int ldx, int k,
+                      const CGConfig* config, CGResult* results);
+
 // cg_solve preconditioned by one V-cycle of the aggregation AMG hierarchy H (spmv/amg.h: amg_setup on A):
 // cg_solve_ic's iteration with z = amg_apply(r) in place of the two triangular solves.  z is a stored vector; the
 // stored-z step kernels, the SpMV half of a step, the engines, the plan caching, the stop rules and the breakdown rule

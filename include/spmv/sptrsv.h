@@ -79,6 +79,36 @@ SpTRSVResult sptrsv_csr(const CSRMatrix* A, const float* d_b, float* d_x, const 
 int sptrsv_csr_async(const CSRMatrix* A, const float* d_b, float* d_x, const SpTRSVConfig* config,
                      hipStream_t stream);
 
+// sptrsv_csr for k right-hand sides in ONE launch sequence: T X = B with d_B and d_X num_rows x k,
+// row-major, on the device, leading dimensions ldb, ldx >= k (spmv_csr_multi's layout), 1 <= k <= 32.  The contract is
+// bitwise: column j of X is what sptrsv_csr(A, B[:, j], ., config) writes at the same lanes_per_row, whatever the
+// other columns hold (with ordered = 1 therefore sptrsv_cpu_csr's bits).  The diagonal of a row is computed once and
+// shared by the columns; a zero diagonal gives each column its own IEEE quotient, and an inf or NaN of one column
+// never reaches another.  The schedule is sptrsv_csr's (same cache, same key, same invalidation: a multi call after
+// a single call reports analysis_ms == 0 and the other way round), the lanes are sptrsv_csr's, and num_levels,
+// launches and lanes_per_row of the result equal the single-column call's: the launch count does not depend on k.
+// Columns k..ldx-1 of d_X are never written; d_B is never written unless it is d_X.
+//
+// Aliasing: d_B == d_X with ldb == ldx is the solve in place.  Any other overlap of the ranges
+// d_B[0, (num_rows - 1) * ldb + k) and d_X[0, (num_rows - 1) * ldx + k) is INVALID_ARGUMENT.
+//
+// Checks, in this order, before any device work; nothing is written to d_X when one fails: null A / d_B / d_X ->
+// INVALID_ARGUMENT; k < 1 or k > 32 -> INVALID_ARGUMENT; ldb < k or ldx < k -> INVALID_ARGUMENT; then sptrsv_csr's
+// from the dimension check on, with the overlap rule above.
+SpTRSVResult sptrsv_csr_multi(const CSRMatrix* A, const float* d_B, int ldb, float* d_X, int ldx, int k,
+                              const SpTRSVConfig* config = nullptr);
+
+// The same enqueued on `stream` without timing or a final synchronisation (sptrsv_csr_async's rules).
+int sptrsv_csr_multi_async(const CSRMatrix* A, const float* d_B, int ldb, float* d_X, int ldx, int k,
+                           const SpTRSVConfig* config, hipStream_t stream);
+
+// sptrsv_cpu_csr column by column on host arrays B and X (num_rows x k row-major, ldb, ldx >= k): column j of X is
+// bit for bit sptrsv_cpu_csr on column j of B.  B == X with ldb == ldx is allowed; any other overlap of the two
+// ranges -> INVALID_ARGUMENT.  Checks: null arguments, then k, then ldb / ldx (INVALID_ARGUMENT each), then
+// sptrsv_cpu_csr's; X is untouched on any error.
+int sptrsv_cpu_csr_multi(const CSRMatrix* A, const float* B, int ldb, float* X, int ldx, int k,
+                         const SpTRSVConfig* config = nullptr);
+
 // Builds and caches the schedule of A's `uplo` triangle ahead of a timed call (on spmv_get_stream()).  Checks as
 // sptrsv_csr's for A and uplo; a missing diagonal is not an error here (a UNIT solve may follow).  num_levels,
 // launches and analysis_ms of the result are filled; analysis_ms is 0 when the schedule was already there.

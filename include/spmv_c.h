@@ -283,6 +283,12 @@ int spmv_c_cg_solve_multi(const spmv_c_csr* A, const float* d_B, int ldb, float*
 int spmv_c_cg_solve_ic(const spmv_c_csr* A, const spmv_c_csr* F, const float* d_b, float* d_x,
                        const spmv_c_cg_config* config, spmv_c_cg_result* out);
 
+/* spmv_c_cg_solve_ic for k right-hand sides (1..32) in spmv_c_cg_solve_multi's layout: one matrix pass and one k-wide
+ * launch sequence per triangular solve and step.  Column j is bit for bit spmv_c_cg_solve_ic with engine 0 on that
+ * column.  Checks and numerics as cg_solve_multi_ic in include/spmv/cg.h.  Returns the error code. */
+int spmv_c_cg_solve_multi_ic(const spmv_c_csr* A, const spmv_c_csr* F, const float* d_B, int ldb, float* d_X, int ldx,
+                             int k, const spmv_c_cg_config* config, spmv_c_cg_result* results);
+
 /* ---- Jacobi-preconditioned BiCGSTAB (extension; spmv::bicgstab_solve, include/spmv/bicgstab.h) ---- */
 /* 16 bytes; the fields, defaults and meanings of spmv_c_cg_config */
 typedef struct spmv_c_bicgstab_config {
@@ -385,6 +391,19 @@ int spmv_c_sptrsv_csr_async(const spmv_c_csr* A, const float* d_b, float* d_x, c
 int spmv_c_sptrsv_analyze(const spmv_c_csr* A, int uplo, spmv_c_sptrsv_result* out);
 /* host forward / backward substitution on A's host arrays (b and x host arrays, may be the same); returns the error code */
 int spmv_c_sptrsv_cpu_csr(const spmv_c_csr* A, const float* b, float* x, const spmv_c_sptrsv_config* config);
+/* spmv_c_sptrsv_csr for k right-hand sides (1..32) in one launch sequence: d_B and d_X are num_rows x k row-major
+ * with leading dimensions ldb, ldx >= k, and may be the same array when ldb == ldx.  Column j is bit for bit
+ * spmv_c_sptrsv_csr on that column; num_levels, launches and lanes_per_row are the single call's.  Checks and
+ * numerics as sptrsv_csr_multi in include/spmv/sptrsv.h.  The return value equals out->error_code (out may be NULL). */
+int spmv_c_sptrsv_csr_multi(const spmv_c_csr* A, const float* d_B, int ldb, float* d_X, int ldx, int k,
+                            const spmv_c_sptrsv_config* config, spmv_c_sptrsv_result* out);
+/* the same enqueued on a caller stream without timing or synchronisation (spmv_c_sptrsv_csr_async's rules) */
+int spmv_c_sptrsv_csr_multi_async(const spmv_c_csr* A, const float* d_B, int ldb, float* d_X, int ldx, int k,
+                                  const spmv_c_sptrsv_config* config, void* hip_stream);
+/* spmv_c_sptrsv_cpu_csr column by column on host arrays B and X (num_rows x k row-major; B == X with ldb == ldx is
+ * allowed); returns the error code */
+int spmv_c_sptrsv_cpu_csr_multi(const spmv_c_csr* A, const float* B, int ldb, float* X, int ldx, int k,
+                                const spmv_c_sptrsv_config* config);
 /* the level analysis as a pure host function: level_ptr[num_rows + 1], order[num_rows]; *first_missing_diagonal (may
  * be NULL) = lowest row without a stored diagonal entry, or -1 */
 int spmv_c_sptrsv_levels(int num_rows, const int32_t* row_ptrs, const int32_t* col_indices, int uplo,
