@@ -17,8 +17,11 @@
 //
 // bicgstab_solve_lu is the same loop with M = L U given as a factor matrix: the step kernels run as with NONE
 // (dinv == nullptr, no p^ / s^ outputs) and p^ = U^-1 (L^-1 p), s^ = U^-1 (L^-1 s) are two launch_sptrsv sequences each
-// (sptrsv.hip) into the stored p^ / s^ buffers, s^ after bicg_s_kernel and p^ after bicg_direction_kernel.  The solve
-// kernels do not read `done`: after it they still write p^ / s^, which nothing reads any more.
+// (TriangularPair::apply) into the stored p^ / s^ buffers, s^ after bicg_s_kernel and p^ after bicg_direction_kernel.
+// The solve kernels do not read `done`: after it they still write p^ / s^, which nothing reads any more.
+//
+// The host side is built from solver_common.h's parts (Workspace and its mirror, TriangularPair, TiledEngine,
+// diag_kernel); what is here is this solver's checks, its workspace layout, its launches and its result.
 #include "internal.h"
 #include "device_common.h"
 #include "solver_common.h"
@@ -63,29 +66,6 @@ struct BicgState {
 };
 
 __device__ __forceinline__ bool usable(double v) { return v != 0.0 && isfinite(v); }
-
-// dinv[i] = 1 / (sum of row i's stored (i,i) entries, fp32, storage order); flags rows where that is missing, zero
-// or not finite (a negative diagonal is fine).  One thread per row: setup only.
-__global__ __launch_bounds__(kBlock)
-void bicg_diag_kernel(int n, const int* __restrict__ row_ptrs, const int* __restrict__ cols,
-                      const float* __restrict__ vals, float* __restrict__ dinv, BicgState* __restrict__ state) {
-    int bad = 0;
-    for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < n;
-         i += static_cast<long long>(gridDim.x) * kBlock) {
-        float d = 0.0f;
-        int found = 0;
-        for (int j = row_ptrs[i]; j < row_ptrs[i + 1]; ++j) {
-            if (cols[j] == i) {
-                d = __fadd_rn(d, vals[j]);
-                found = 1;
-            }
-        }
-        const bool ok = found && d != 0.0f && isfinite(d);
-        dinv[i] = ok ? __fdiv_rn(1.0f, d) : 0.0f;
-        bad |= !ok;
-    }
-    if (__any(bad) && (threadIdx.x & 63) == 0) state->bad_diagonal = 1;   // every writer stores the same 1
-}
 
 // r0 = b - A x0, r^ = p0 = r0, p^0 = r0 * dinv (JACOBI), and the block partials of r.r and b.b -> part[2 * block].
 template <int LANES>
@@ -356,10 +336,6 @@ hipError_t spmv_dot(int lanes, const CSRMatrix* A, const float* w, float* y, con
     });
 }
 
-bool device_arrays(const CSRMatrix* M) {
-    return M->num_rows >= 0 && M->d_row_ptrs && (M->nnz <= 0 || (M->d_col_indices && M->d_values));
-}
-
 // bicgstab_solve (with_lu false: LU is not looked at, cfg.preconditioner picks NONE or JACOBI) and bicgstab_solve_lu
 // (with_lu true: M = L U from LU, cfg.preconditioner is not read).
 BiCGStabResult solve(const CSRMatrix* A, const CSRMatrix* LU, bool with_lu, const float* d_b, float* d_x,
@@ -394,33 +370,12 @@ BiCGStabResult solve(const CSRMatrix* A, const CSRMatrix* LU, bool with_lu, cons
     const bool jacobi = !with_lu && cfg.preconditioner == CGConfig::JACOBI;
     const bool stored = jacobi || with_lu;         // p^ and s^ are buffers of their own
 
-    // both schedules of LU, ahead of the timed loop (a build synchronises the stream); they validate LU's structure
-    // before any kernel walks it
-    std::shared_ptr<const SptrsvSchedule> lower, upper;
-    int lower_lanes = 1, upper_lanes = 1;
+    TriangularPair lu;              // M = L U: L's diagonal is the implied 1
     if (with_lu) {
-        float analysis_ms = 0.0f;
-        int status = sptrsv_schedule_for(LU, SpTRSVConfig::LOWER, stream, &lower, &analysis_ms);
-        if (status == 0) status = sptrsv_schedule_for(LU, SpTRSVConfig::UPPER, stream, &upper, &analysis_ms);
+        const int status = lu.build(LU, 1, stream);
         if (status != 0) return fail(static_cast<SpMVError>(status));
-        lower_lanes = sptrsv_lanes_for(*lower);
-        upper_lanes = sptrsv_lanes_for(*upper);
     }
-    // out = U^-1 (L^-1 in): LOWER UNIT, then UPPER NON_UNIT in place
-    const auto apply_lu = [&](const float* in, float* out) -> bool {
-        return launch_sptrsv(*lower, LU, in, out, SpTRSVConfig::LOWER, 1, false, lower_lanes, stream) == hipSuccess &&
-               launch_sptrsv(*upper, LU, out, out, SpTRSVConfig::UPPER, 0, false, upper_lanes, stream) == hipSuccess;
-    };
-
-    // engine choice (cg_solve's: -1 takes a cached plan from the start, else builds one after 4 direct steps)
-    PlanRef plan;
-    int build_plan_at = -1;
-    if (cfg.engine == 1) {
-        plan = tiled_plan_for(A, stream);
-    } else if (cfg.engine == -1) {
-        plan = tiled_plan_if_cached(A);
-        if (!plan && tiled_eligible(A)) build_plan_at = 4;
-    }
+    TiledEngine engine(A, cfg.engine, stream);
 
     const int lanes = pick_lanes_per_row(static_cast<float>(A->nnz) / n);
     const int row_grid = grid_for_rows(n, kBlock / lanes);
@@ -451,41 +406,24 @@ BiCGStabResult solve(const CSRMatrix* A, const CSRMatrix* LU, bool with_lu, cons
     double* ts_part = ss_part + ss_count;
     double* rr_part = ts_part + ts_count;
     double* init_part = rr_part + rr_count;
-    BicgState* pinned = ws.pinned;
 
-    // setup: diagonal (JACOBI; of LU, only its check: the reciprocals land in t, which the loop overwrites before it
-    // reads it), r0 / r^ / p0 / p^0 and their dots, the state; one read-back
+    // setup: diagonal (JACOBI; of LU, only its check), r0 / r^ / p0 / p^0 and their dots, the state; one read-back
     bool ok = hipMemsetAsync(ws.state, 0, sizeof(BicgState), stream) == hipSuccess;
-    if (ok && with_lu) {
-        bicg_diag_kernel<<<vgrid, kBlock, 0, stream>>>(n, LU->d_row_ptrs, LU->d_col_indices, LU->d_values, t, ws.state);
-        ok = hipGetLastError() == hipSuccess;
-    }
-    if (ok && jacobi) {
-        bicg_diag_kernel<<<vgrid, kBlock, 0, stream>>>(n, A->d_row_ptrs, A->d_col_indices, A->d_values, dinv,
-                                                       ws.state);
-        ok = hipGetLastError() == hipSuccess;
-    }
+    int* bad = &ws.state->bad_diagonal;
+    if (with_lu) ok = ok && launch_diag<DiagRule::NONZERO_FINITE>(LU, nullptr, bad, stream) == hipSuccess;
+    if (jacobi) ok = ok && launch_diag<DiagRule::NONZERO_FINITE>(A, dinv, bad, stream) == hipSuccess;
     float* phat_out = jacobi ? phat : nullptr;     // the kernels write p^ / s^ only with JACOBI
     float* shat_out = jacobi ? shat : nullptr;
     ok = ok && init(lanes, A, d_b, d_x, dinv, r, rhat, p, phat_out, init_part, row_grid, stream) == hipSuccess;
-    if (with_lu) ok = ok && apply_lu(p, phat);
+    if (with_lu) ok = ok && lu.apply(p, phat, stream);
     if (ok) {
         bicg_start_kernel<<<1, kBlock, 0, stream>>>(init_part, row_grid, cfg.tolerance, ws.state);
         ok = hipGetLastError() == hipSuccess;
     }
-    ok = ok && hipMemcpyAsync(&pinned[0], ws.state, sizeof(BicgState), hipMemcpyDeviceToHost, stream) == hipSuccess
-            && hipStreamSynchronize(stream) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        return fail(SpMVError::KERNEL_LAUNCH);
-    }
-    if (pinned[0].bad_diagonal) return fail(SpMVError::INVALID_ARGUMENT);
-    if (pinned[0].zero_b) {
-        if (hipMemsetAsync(d_x, 0, len * sizeof(float), stream) != hipSuccess ||
-            hipStreamSynchronize(stream) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(SpMVError::KERNEL_LAUNCH);
-        }
+    if (!ws.read_back(ok, stream)) return fail(SpMVError::KERNEL_LAUNCH);
+    if (ws.pinned[0].bad_diagonal) return fail(SpMVError::INVALID_ARGUMENT);
+    if (ws.pinned[0].zero_b) {
+        if (!zero_solution(d_x, len, stream)) return fail(SpMVError::KERNEL_LAUNCH);
         result.converged = 1;
         return result;
     }
@@ -494,35 +432,22 @@ BiCGStabResult solve(const CSRMatrix* A, const CSRMatrix* LU, bool with_lu, cons
     // direct kernel.  `count` receives the number of partials written.
     const auto spmv_and_dot = [&](const float* w, float* y, const float* a, int with_yy, double* part,
                                   int& count) -> bool {
-        if (plan) {
-            const hipError_t e = tiled_spmv(*plan, w, y, stream);
-            if (e == hipErrorOutOfMemory) {        // no tiled scratch for this stream: direct kernels from here on
-                (void)hipGetLastError();
-                plan.reset();
-                build_plan_at = -1;
-            } else if (e != hipSuccess) {
-                return false;
-            } else {
-                bicg_dot_kernel<<<vgrid, kBlock, 0, stream>>>(n, a, y, with_yy, ws.state, part);
-                count = vgrid;
-                return hipGetLastError() == hipSuccess;
-            }
+        const TiledEngine::Spmv spmv = engine.spmv(w, y, stream);
+        if (spmv == TiledEngine::Spmv::FAILED) return false;
+        if (spmv == TiledEngine::Spmv::TILED) {
+            bicg_dot_kernel<<<vgrid, kBlock, 0, stream>>>(n, a, y, with_yy, ws.state, part);
+            count = vgrid;
+            return hipGetLastError() == hipSuccess;
         }
         count = row_grid;
         return spmv_dot(lanes, A, w, y, a, with_yy, ws.state, part, row_grid, stream) == hipSuccess;
     };
 
-    BicgState final_state = pinned[0];
-    if (!final_state.done) {
+    if (!ws.pinned[0].done) {
         EventPair& ev = thread_events();
         ok = hipEventRecord(ev.start, stream) == hipSuccess;
         for (int iter = 0; ok && iter < cfg.max_iterations; ++iter) {
-            if (!plan && iter == build_plan_at) {
-                // enough direct steps paid: drain the queue (nothing is built for a loop that has ended), then plan
-                ok = hipStreamSynchronize(stream) == hipSuccess;
-                if (ok && iter >= 1 && pinned[(iter - 1) & 1].done) break;
-                plan = ok ? tiled_plan_for(A, stream) : nullptr;
-            }
+            if (!engine.build_if_due(iter, ws, stream, ok)) break;
             const TraceRange step_range("spmv:bicgstab_step");
             int rv_parts = 0, ts_parts = 0;
             ok = spmv_and_dot(phat, v, rhat, 0, rv_part, rv_parts);
@@ -531,34 +456,25 @@ BiCGStabResult solve(const CSRMatrix* A, const CSRMatrix* LU, bool with_lu, cons
                                                             ss_part);
                 ok = hipGetLastError() == hipSuccess;
             }
-            if (with_lu) ok = ok && apply_lu(r, shat);
+            if (with_lu) ok = ok && lu.apply(r, shat, stream);
             ok = ok && spmv_and_dot(shat, t, r, 1, ts_part, ts_parts);
             if (ok) {
                 bicg_update_kernel<<<vgrid, kBlock, 0, stream>>>(n, phat, shat, t, rhat, d_x, r, ws.state, ss_part,
                                                                  vgrid, ts_part, ts_parts, rr_part);
                 bicg_direction_kernel<<<vgrid, kBlock, 0, stream>>>(n, iter, v, r, dinv, p, phat_out, ws.state, rr_part,
                                                                     vgrid);
-                ok = hipGetLastError() == hipSuccess && (!with_lu || apply_lu(p, phat))
-                  && hipMemcpyAsync(&pinned[iter & 1], ws.state, sizeof(BicgState), hipMemcpyDeviceToHost,
-                                    stream) == hipSuccess
-                  && hipEventRecord(ws.seen[iter & 1], stream) == hipSuccess;
+                ok = hipGetLastError() == hipSuccess && (!with_lu || lu.apply(p, phat, stream))
+                  && ws.publish(iter, sizeof(BicgState), stream);
             }
             if (ok && iter >= 1) {
-                ok = hipEventSynchronize(ws.seen[(iter - 1) & 1]) == hipSuccess;
-                if (ok && pinned[(iter - 1) & 1].done) break;
+                const BicgState* seen = ws.wait_previous(iter);
+                ok = seen != nullptr;
+                if (ok && seen->done) break;
             }
         }
-        ok = ok && hipEventRecord(ev.stop, stream) == hipSuccess
-                && hipMemcpyAsync(&pinned[0], ws.state, sizeof(BicgState), hipMemcpyDeviceToHost, stream) == hipSuccess
-                && hipStreamSynchronize(stream) == hipSuccess;
-        if (!ok) {
-            (void)hipGetLastError();
-            return fail(SpMVError::KERNEL_LAUNCH);
-        }
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, ev.start, ev.stop) == hipSuccess) result.elapsed_ms = ms;
-        final_state = pinned[0];
+        if (!ws.finish_timed(ok, ev, stream, &result.elapsed_ms)) return fail(SpMVError::KERNEL_LAUNCH);
     }
+    const BicgState& final_state = ws.pinned[0];
     result.iterations = final_state.iterations;
     result.relative_residual = final_state.relative_residual;
     result.converged = final_state.converged;

@@ -4,23 +4,26 @@
 // kernel returns at once when `done` is set, and the host reads a two-deep pinned mirror of the state so that it
 // enqueues step k+1 before it looks at the outcome of step k.  Per step on the direct engine, three launches:
 //   cg_spmv_dot<LANES>  q = A p (vector CSR) and the block partials of p.q
-//   cg_update_kernel    every workgroup folds the p.q partials (same order => same alpha everywhere), then
-//                       x += alpha p, r -= alpha q, and the block partials of r.z and r.r (z = r * dinv)
-//   cg_direction_kernel every workgroup folds those partials, gets beta and the stop test, p = z + beta p
+//   cg_update_kernel<false>     every workgroup folds the p.q partials (same order => same alpha everywhere), then
+//                               x += alpha p, r -= alpha q, and the block partials of r.z and r.r (z = r * dinv)
+//   cg_direction_kernel<false>  every workgroup folds those partials, gets beta and the stop test, p = z + beta p
 // On the tiled engine tiled_spmv(plan, p, q) and cg_dot_kernel (partials of p.q) replace the first launch.
 // Dot products accumulate fp64 products of the fp32 entries; no float atomics anywhere.
 //
 // cg_solve_ic is the same loop with M = L L^T given as a factor matrix.  z is a stored vector
 // there, so the second half of a step is
-//   cg_ic_update_kernel     as cg_update_kernel, but only the block partials of r.r (z does not exist yet)
-//   launch_sptrsv x 2       z = L^-1 r (LOWER NON_UNIT), then z = L^-T z in place (UPPER NON_UNIT); they do not read
-//                           `done`: after it r no longer changes and they rewrite the same z
-//   cg_rz_kernel            the block partials of r.z
-//   cg_ic_direction_kernel  as cg_direction_kernel with z read from memory
+//   cg_update_kernel<true>     the same kernel with STORED_Z: only the block partials of r.r (z does not exist yet)
+//   TriangularPair::apply      z = L^-1 r (LOWER NON_UNIT), then z = L^-T z in place (UPPER NON_UNIT); the solves do
+//                              not read `done`: after it r no longer changes and they rewrite the same z
+//   cg_rz_kernel               the block partials of r.z
+//   cg_direction_kernel<true>  the same kernel with z read from memory
 // and the SpMV half is the one above, kernel for kernel.
 //
 // cg_solve_amg is cg_solve_ic's loop with z = one V-cycle of an AMG hierarchy on r (amg_vcycle, amg.hip, DESIGN.md
 // §4.16) in place of the two triangular solves; its kernels read `done` themselves.
+//
+// The host side is built from solver_common.h's parts (Workspace and its mirror, TriangularPair, TiledEngine,
+// diag_kernel); what is here is this solver's checks, its workspace layout, its launches and its result.
 #include "amg_impl.h"
 #include "internal.h"
 #include "device_common.h"
@@ -54,32 +57,9 @@ struct CgState {
     int    breakdown;
     int    done;              // steps after this are no-ops
     int    zero_b;            // ||b|| == 0: the host writes x = 0
-    int    bad_diagonal;      // JACOBI: some row's diagonal is missing or not > 0
+    int    bad_diagonal;      // JACOBI, IC: some row's diagonal is missing or not > 0 (IC: or not finite)
     int    reserved;
 };
-
-// dinv[i] = 1 / (sum of row i's stored (i,i) entries, fp32, storage order); flags rows where that is missing or
-// not > 0.  One thread per row: setup only.
-__global__ __launch_bounds__(kBlock)
-void cg_diag_kernel(int n, const int* __restrict__ row_ptrs, const int* __restrict__ cols,
-                    const float* __restrict__ vals, float* __restrict__ dinv, CgState* __restrict__ state) {
-    int bad = 0;
-    for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < n;
-         i += static_cast<long long>(gridDim.x) * kBlock) {
-        float d = 0.0f;
-        int found = 0;
-        for (int j = row_ptrs[i]; j < row_ptrs[i + 1]; ++j) {
-            if (cols[j] == i) {
-                d = __fadd_rn(d, vals[j]);
-                found = 1;
-            }
-        }
-        const bool ok = found && d > 0.0f;
-        dinv[i] = ok ? __fdiv_rn(1.0f, d) : 0.0f;
-        bad |= !ok;
-    }
-    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(&state->bad_diagonal, 1);
-}
 
 // r0 = b - A x0, p0 = z0 = r0 * dinv, and the block partials of r.z, r.r and b.b -> part[3 * block].
 template <int LANES>
@@ -189,7 +169,10 @@ void cg_dot_kernel(int n, const float* __restrict__ p, const float* __restrict__
     if (threadIdx.x == 0) part[blockIdx.x] = pq;
 }
 
-// alpha = rz / p.q; x += alpha p; r -= alpha q; partials of r.z and r.r -> part_out[2 * block].
+// alpha = rz / p.q; x += alpha p; r -= alpha q; partials of r.z and r.r -> part_out[2 * block] with z = r * dinv
+// (r where dinv is null).  STORED_Z (IC, AMG): z does not exist yet and dinv is not read: the partials of r.r alone ->
+// part_out[2 * block + 1]; r.z follows from cg_rz_kernel once z is there.
+template <bool STORED_Z>
 __global__ __launch_bounds__(kBlock)
 void cg_update_kernel(int n, int step, const float* __restrict__ p, const float* __restrict__ q,
                       const float* __restrict__ dinv, float* __restrict__ x, float* __restrict__ r,
@@ -214,20 +197,29 @@ void cg_update_kernel(int n, int step, const float* __restrict__ p, const float*
         x[i] = __builtin_fmaf(alpha, pi, x[i]);
         const float ri = __builtin_fmaf(-alpha, qi, r[i]);
         r[i] = ri;
-        const float zi = dinv ? __fmul_rn(ri, dinv[i]) : ri;
-        rz += prod64(ri, zi);
+        if constexpr (!STORED_Z) {
+            const float zi = dinv ? __fmul_rn(ri, dinv[i]) : ri;
+            rz += prod64(ri, zi);
+        }
         rr += prod64(ri, ri);
     }
-    block_sum2(rz, rr);
-    if (threadIdx.x == 0) {
-        part_out[2 * blockIdx.x] = rz;
-        part_out[2 * blockIdx.x + 1] = rr;
+    if constexpr (STORED_Z) {
+        block_sum2(rr, unused);
+        if (threadIdx.x == 0) part_out[2 * blockIdx.x + 1] = rr;
+    } else {
+        block_sum2(rz, rr);
+        if (threadIdx.x == 0) {
+            part_out[2 * blockIdx.x] = rz;
+            part_out[2 * blockIdx.x + 1] = rr;
+        }
     }
 }
 
-// beta = rz_new / rz_old, the stop test, p = z + beta p.  Workgroup 0 commits the step to the state.
+// beta = rz_new / rz_old, the stop test, p = z + beta p.  Workgroup 0 commits the step to the state.  zr is r and
+// z = r * dinv (r where dinv is null), or with STORED_Z it is z itself and dinv is not read.
+template <bool STORED_Z>
 __global__ __launch_bounds__(kBlock)
-void cg_direction_kernel(int n, int step, const float* __restrict__ r, const float* __restrict__ dinv,
+void cg_direction_kernel(int n, int step, const float* __restrict__ zr, const float* __restrict__ dinv,
                          float* __restrict__ p, CgState* __restrict__ state, const double* __restrict__ part,
                          int count) {
     if (state->done) return;
@@ -249,59 +241,10 @@ void cg_direction_kernel(int n, int step, const float* __restrict__ r, const flo
     const float beta = static_cast<float>(rz / rz_old);
     for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < n;
          i += static_cast<long long>(gridDim.x) * kBlock) {
-        const float ri = r[i];
-        const float zi = dinv ? __fmul_rn(ri, dinv[i]) : ri;
+        float zi = zr[i];
+        if constexpr (!STORED_Z) zi = dinv ? __fmul_rn(zi, dinv[i]) : zi;
         p[i] = __builtin_fmaf(beta, p[i], zi);
     }
-}
-
-// IC: some row of the factor has no stored diagonal, or one that is not > 0 or not finite.  One thread per row: setup.
-__global__ __launch_bounds__(kBlock)
-void cg_ic_diag_kernel(int n, const int* __restrict__ row_ptrs, const int* __restrict__ cols,
-                       const float* __restrict__ vals, CgState* __restrict__ state) {
-    int bad = 0;
-    for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < n;
-         i += static_cast<long long>(gridDim.x) * kBlock) {
-        float d = 0.0f;
-        int found = 0;
-        for (int j = row_ptrs[i]; j < row_ptrs[i + 1]; ++j) {
-            if (cols[j] == i) {
-                d = __fadd_rn(d, vals[j]);
-                found = 1;
-            }
-        }
-        bad |= !(found && d > 0.0f && isfinite(d));
-    }
-    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(&state->bad_diagonal, 1);
-}
-
-// IC: alpha = rz / p.q; x += alpha p; r -= alpha q; partials of r.r -> part_out[2 * block + 1] (cg_update_kernel's
-// slot; r.z follows from cg_rz_kernel once z is solved for).
-__global__ __launch_bounds__(kBlock)
-void cg_ic_update_kernel(int n, int step, const float* __restrict__ p, const float* __restrict__ q,
-                         float* __restrict__ x, float* __restrict__ r, CgState* __restrict__ state,
-                         const double* __restrict__ pq_part, int pq_count, double* __restrict__ part_out) {
-    if (state->done) return;
-    double pq = 0.0, unused = 0.0;
-    fold_partials(pq_part, pq_count, 1, pq, unused);
-    if (!(pq > 0.0)) {             // A is not SPD (or p.q is not finite): x stays at the last good iterate
-        if (blockIdx.x == 0 && threadIdx.x == 0) {
-            state->breakdown = 1;
-            state->done = 1;
-        }
-        return;
-    }
-    const float alpha = static_cast<float>(state->rz[step & 1] / pq);
-    double rr = 0.0;
-    for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < n;
-         i += static_cast<long long>(gridDim.x) * kBlock) {
-        x[i] = __builtin_fmaf(alpha, p[i], x[i]);
-        const float ri = __builtin_fmaf(-alpha, q[i], r[i]);
-        r[i] = ri;
-        rr += prod64(ri, ri);
-    }
-    block_sum2(rr, unused);
-    if (threadIdx.x == 0) part_out[2 * blockIdx.x + 1] = rr;
 }
 
 // IC: block partials of r.z -> part[stride * block] (stride 2 inside the loop, 3 over the init partials).
@@ -318,65 +261,23 @@ void cg_rz_kernel(int n, const float* __restrict__ r, const float* __restrict__ 
     if (threadIdx.x == 0) part[static_cast<long long>(stride) * blockIdx.x] = rz;
 }
 
-// IC: cg_direction_kernel with the stored z.
-__global__ __launch_bounds__(kBlock)
-void cg_ic_direction_kernel(int n, int step, const float* __restrict__ z, float* __restrict__ p,
-                            CgState* __restrict__ state, const double* __restrict__ part, int count) {
-    if (state->done) return;
-    double rz = 0.0, rr = 0.0;
-    fold_partials(part, count, 2, rz, rr);
-    const double res = sqrt(rr);
-    const bool converged = res <= state->threshold;
-    const bool breakdown = !converged && !(rz > 0.0);
-    const double rz_old = state->rz[step & 1];
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        state->iterations = step + 1;
-        state->relative_residual = static_cast<float>(res / state->bnorm);
-        state->rz[(step + 1) & 1] = rz;
-        if (converged) state->converged = 1;
-        if (breakdown) state->breakdown = 1;
-        if (converged || breakdown) state->done = 1;
-    }
-    if (converged || breakdown) return;
-    const float beta = static_cast<float>(rz / rz_old);
-    for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < n;
-         i += static_cast<long long>(gridDim.x) * kBlock) {
-        p[i] = __builtin_fmaf(beta, p[i], z[i]);
-    }
-}
-
-template <int LANES>
-hipError_t launch_init(const CSRMatrix* A, const float* b, const float* x, const float* dinv, float* r, float* p,
-                       double* part, int grid, hipStream_t s) {
-    cg_init_kernel<LANES><<<grid, kBlock, 0, s>>>(A->num_rows, A->nnz, A->d_row_ptrs, A->d_col_indices,
-                                                  A->d_values, b, x, dinv, r, p, part);
-    return hipGetLastError();
-}
-
-template <int LANES>
-hipError_t launch_spmv_dot(const CSRMatrix* A, const float* p, float* q, const CgState* state, double* part,
-                           int grid, hipStream_t s) {
-    cg_spmv_dot<LANES><<<grid, kBlock, 0, s>>>(A->num_rows, A->nnz, A->d_row_ptrs, A->d_col_indices, A->d_values,
-                                               p, q, state, part);
-    return hipGetLastError();
-}
-
 hipError_t init(int lanes, const CSRMatrix* A, const float* b, const float* x, const float* dinv, float* r,
                 float* p, double* part, int grid, hipStream_t s) {
     return with_lanes(lanes, [&](auto L) {
-        return launch_init<decltype(L)::value>(A, b, x, dinv, r, p, part, grid, s);
+        cg_init_kernel<decltype(L)::value><<<grid, kBlock, 0, s>>>(A->num_rows, A->nnz, A->d_row_ptrs,
+                                                                  A->d_col_indices, A->d_values, b, x, dinv, r, p,
+                                                                  part);
+        return hipGetLastError();
     });
 }
 
 hipError_t spmv_dot(int lanes, const CSRMatrix* A, const float* p, float* q, const CgState* state, double* part,
                     int grid, hipStream_t s) {
     return with_lanes(lanes, [&](auto L) {
-        return launch_spmv_dot<decltype(L)::value>(A, p, q, state, part, grid, s);
+        cg_spmv_dot<decltype(L)::value><<<grid, kBlock, 0, s>>>(A->num_rows, A->nnz, A->d_row_ptrs,
+                                                               A->d_col_indices, A->d_values, p, q, state, part);
+        return hipGetLastError();
     });
-}
-
-bool device_arrays(const CSRMatrix* M) {
-    return M->num_rows >= 0 && M->d_row_ptrs && (M->nnz <= 0 || (M->d_col_indices && M->d_values));
 }
 
 // What gives z: the diagonal inside the step kernels (cg_solve: cfg.preconditioner picks NONE or JACOBI), or a stored z
@@ -400,9 +301,7 @@ CGResult solve(const CSRMatrix* A, Precond precond, const CSRMatrix* F, const AM
         result.converged = 1;
         return result;
     }
-    if (A->num_rows < 0 || !A->d_row_ptrs || (A->nnz > 0 && (!A->d_col_indices || !A->d_values))) {
-        return fail(SpMVError::INVALID_FORMAT);
-    }
+    if (!device_arrays(A)) return fail(SpMVError::INVALID_FORMAT);
     const CGConfig defaults;
     const CGConfig& cfg = config ? *config : defaults;
     if (!(cfg.tolerance >= 0.0f) || cfg.max_iterations < 0 ||
@@ -427,29 +326,13 @@ CGResult solve(const CSRMatrix* A, Precond precond, const CSRMatrix* F, const AM
     hipStream_t stream = current_stream();
     const bool jacobi = !stored_z && cfg.preconditioner == CGConfig::JACOBI;
 
-    // both schedules of F, ahead of the timed loop (a build synchronises the stream); they validate F's structure
-    // before any kernel walks it
-    std::shared_ptr<const SptrsvSchedule> lower, upper;
-    int lower_lanes = 1, upper_lanes = 1;
+    TriangularPair ic;              // M = L L^T: the lower solve reads L's stored diagonal
     if (with_ic) {
-        float analysis_ms = 0.0f;
-        int status = sptrsv_schedule_for(F, SpTRSVConfig::LOWER, stream, &lower, &analysis_ms);
-        if (status == 0) status = sptrsv_schedule_for(F, SpTRSVConfig::UPPER, stream, &upper, &analysis_ms);
+        const int status = ic.build(F, 0, stream);
         if (status != 0) return fail(static_cast<SpMVError>(status));
-        lower_lanes = sptrsv_lanes_for(*lower);
-        upper_lanes = sptrsv_lanes_for(*upper);
     }
     const int amg_lanes = with_amg ? amg_forced_lanes() : 0;
-
-    // engine choice (pagerank()'s rule for -1: a cached plan from the start, else a build after 4 direct steps)
-    PlanRef plan;
-    int build_plan_at = -1;
-    if (cfg.engine == 1) {
-        plan = tiled_plan_for(A, stream);
-    } else if (cfg.engine == -1) {
-        plan = tiled_plan_if_cached(A);
-        if (!plan && tiled_eligible(A)) build_plan_at = 4;
-    }
+    TiledEngine engine(A, cfg.engine, stream);
 
     const int lanes = pick_lanes_per_row(static_cast<float>(A->nnz) / n);
     const int row_grid = grid_for_rows(n, kBlock / lanes);
@@ -469,25 +352,17 @@ CGResult solve(const CSRMatrix* A, Precond precond, const CSRMatrix* F, const AM
     double* pq_part = ws.part;
     double* rr_part = ws.part + pq_count;
     double* init_part = rr_part + rr_count;
-    CgState* pinned = ws.pinned;
-    // out = M^-1 in.  IC: LOWER NON_UNIT, then UPPER NON_UNIT in place.  AMG: one V-cycle, whose kernels read `done`.
+    // out = M^-1 in.  IC: both triangular solves.  AMG: one V-cycle, whose kernels read `done`.
     const auto apply_stored = [&](const float* in, float* out) -> bool {
         if (with_amg) return amg_vcycle(*H, in, out, &ws.state->done, amg_lanes, stream) == hipSuccess;
-        return launch_sptrsv(*lower, F, in, out, SpTRSVConfig::LOWER, 0, false, lower_lanes, stream) == hipSuccess &&
-               launch_sptrsv(*upper, F, out, out, SpTRSVConfig::UPPER, 0, false, upper_lanes, stream) == hipSuccess;
+        return ic.apply(in, out, stream);
     };
 
     // setup: diagonal (JACOBI; of F, only its check), r0 / p0 and their dots, the state; one read-back
     bool ok = hipMemsetAsync(ws.state, 0, sizeof(CgState), stream) == hipSuccess;
-    if (ok && with_ic) {
-        cg_ic_diag_kernel<<<vgrid, kBlock, 0, stream>>>(n, F->d_row_ptrs, F->d_col_indices, F->d_values, ws.state);
-        ok = hipGetLastError() == hipSuccess;
-    }
-    if (ok && jacobi) {
-        cg_diag_kernel<<<vec_grid(n), kBlock, 0, stream>>>(n, A->d_row_ptrs, A->d_col_indices, A->d_values, dinv,
-                                                            ws.state);
-        ok = hipGetLastError() == hipSuccess;
-    }
+    int* bad = &ws.state->bad_diagonal;
+    if (with_ic) ok = ok && launch_diag<DiagRule::POSITIVE_FINITE>(F, nullptr, bad, stream) == hipSuccess;
+    if (jacobi) ok = ok && launch_diag<DiagRule::POSITIVE>(A, dinv, bad, stream) == hipSuccess;
     ok = ok && init(lanes, A, d_b, d_x, dinv, r, p, init_part, row_grid, stream) == hipSuccess;
     if (ok && stored_z) {
         // the init kernel left p0 = r0 and r0.r0 in the r.z slot: z0 = M^-1 r0, the true r0.z0 over it, p0 = z0
@@ -502,89 +377,57 @@ CGResult solve(const CSRMatrix* A, Precond precond, const CSRMatrix* F, const AM
         cg_start_kernel<<<1, kBlock, 0, stream>>>(init_part, row_grid, cfg.tolerance, ws.state);
         ok = hipGetLastError() == hipSuccess;
     }
-    ok = ok && hipMemcpyAsync(&pinned[0], ws.state, sizeof(CgState), hipMemcpyDeviceToHost, stream) == hipSuccess
-            && hipStreamSynchronize(stream) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        return fail(SpMVError::KERNEL_LAUNCH);
-    }
-    if (pinned[0].bad_diagonal) return fail(SpMVError::INVALID_ARGUMENT);
-    if (pinned[0].zero_b) {
-        if (hipMemsetAsync(d_x, 0, len * sizeof(float), stream) != hipSuccess ||
-            hipStreamSynchronize(stream) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(SpMVError::KERNEL_LAUNCH);
-        }
+    if (!ws.read_back(ok, stream)) return fail(SpMVError::KERNEL_LAUNCH);
+    if (ws.pinned[0].bad_diagonal) return fail(SpMVError::INVALID_ARGUMENT);
+    if (ws.pinned[0].zero_b) {
+        if (!zero_solution(d_x, len, stream)) return fail(SpMVError::KERNEL_LAUNCH);
         result.converged = 1;
         return result;
     }
 
-    CgState final_state = pinned[0];
-    if (!final_state.done) {
+    if (!ws.pinned[0].done) {
         EventPair& ev = thread_events();
         ok = hipEventRecord(ev.start, stream) == hipSuccess;
         for (int iter = 0; ok && iter < cfg.max_iterations; ++iter) {
-            if (!plan && iter == build_plan_at) {
-                // enough direct steps paid: drain the queue (nothing is built for a loop that has ended), then plan
-                ok = hipStreamSynchronize(stream) == hipSuccess;
-                if (ok && iter >= 1 && pinned[(iter - 1) & 1].done) break;
-                plan = ok ? tiled_plan_for(A, stream) : nullptr;
-            }
+            if (!engine.build_if_due(iter, ws, stream, ok)) break;
             const TraceRange step_range("spmv:cg_step");
             int pq_parts = row_grid;
-            bool direct = !plan;
-            if (plan) {
-                const hipError_t e = tiled_spmv(*plan, p, q, stream);
-                if (e == hipErrorOutOfMemory) {        // no tiled scratch for this stream: direct kernels from here on
-                    (void)hipGetLastError();
-                    plan.reset();
-                    build_plan_at = -1;
-                    direct = true;
-                } else if (e != hipSuccess) {
-                    ok = false;
-                    break;
-                } else {
-                    cg_dot_kernel<<<vgrid, kBlock, 0, stream>>>(n, p, q, ws.state, pq_part);
-                    ok = hipGetLastError() == hipSuccess;
-                    pq_parts = vgrid;
-                }
+            const TiledEngine::Spmv spmv = engine.spmv(p, q, stream);
+            ok = ok && spmv != TiledEngine::Spmv::FAILED;
+            if (spmv == TiledEngine::Spmv::TILED) {
+                cg_dot_kernel<<<vgrid, kBlock, 0, stream>>>(n, p, q, ws.state, pq_part);
+                ok = hipGetLastError() == hipSuccess;
+                pq_parts = vgrid;
+            } else if (ok) {
+                ok = spmv_dot(lanes, A, p, q, ws.state, pq_part, row_grid, stream) == hipSuccess;
             }
-            if (ok && direct) ok = spmv_dot(lanes, A, p, q, ws.state, pq_part, row_grid, stream) == hipSuccess;
             if (ok && stored_z) {
-                cg_ic_update_kernel<<<vgrid, kBlock, 0, stream>>>(n, iter, p, q, d_x, r, ws.state, pq_part, pq_parts,
-                                                                  rr_part);
+                cg_update_kernel<true><<<vgrid, kBlock, 0, stream>>>(n, iter, p, q, nullptr, d_x, r, ws.state, pq_part,
+                                                                     pq_parts, rr_part);
                 ok = hipGetLastError() == hipSuccess && apply_stored(r, z);
             }
             if (ok) {
                 if (stored_z) {
                     cg_rz_kernel<<<vgrid, kBlock, 0, stream>>>(n, r, z, ws.state, rr_part, 2);
-                    cg_ic_direction_kernel<<<vgrid, kBlock, 0, stream>>>(n, iter, z, p, ws.state, rr_part, vgrid);
+                    cg_direction_kernel<true><<<vgrid, kBlock, 0, stream>>>(n, iter, z, nullptr, p, ws.state, rr_part,
+                                                                            vgrid);
                 } else {
-                    cg_update_kernel<<<vgrid, kBlock, 0, stream>>>(n, iter, p, q, dinv, d_x, r, ws.state, pq_part,
-                                                                   pq_parts, rr_part);
-                    cg_direction_kernel<<<vgrid, kBlock, 0, stream>>>(n, iter, r, dinv, p, ws.state, rr_part, vgrid);
+                    cg_update_kernel<false><<<vgrid, kBlock, 0, stream>>>(n, iter, p, q, dinv, d_x, r, ws.state,
+                                                                          pq_part, pq_parts, rr_part);
+                    cg_direction_kernel<false><<<vgrid, kBlock, 0, stream>>>(n, iter, r, dinv, p, ws.state, rr_part,
+                                                                             vgrid);
                 }
-                ok = hipGetLastError() == hipSuccess
-                  && hipMemcpyAsync(&pinned[iter & 1], ws.state, sizeof(CgState), hipMemcpyDeviceToHost,
-                                    stream) == hipSuccess
-                  && hipEventRecord(ws.seen[iter & 1], stream) == hipSuccess;
+                ok = hipGetLastError() == hipSuccess && ws.publish(iter, sizeof(CgState), stream);
             }
             if (ok && iter >= 1) {
-                ok = hipEventSynchronize(ws.seen[(iter - 1) & 1]) == hipSuccess;
-                if (ok && pinned[(iter - 1) & 1].done) break;
+                const CgState* seen = ws.wait_previous(iter);
+                ok = seen != nullptr;
+                if (ok && seen->done) break;
             }
         }
-        ok = ok && hipEventRecord(ev.stop, stream) == hipSuccess
-                && hipMemcpyAsync(&pinned[0], ws.state, sizeof(CgState), hipMemcpyDeviceToHost, stream) == hipSuccess
-                && hipStreamSynchronize(stream) == hipSuccess;
-        if (!ok) {
-            (void)hipGetLastError();
-            return fail(SpMVError::KERNEL_LAUNCH);
-        }
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, ev.start, ev.stop) == hipSuccess) result.elapsed_ms = ms;
-        final_state = pinned[0];
+        if (!ws.finish_timed(ok, ev, stream, &result.elapsed_ms)) return fail(SpMVError::KERNEL_LAUNCH);
     }
+    const CgState& final_state = ws.pinned[0];
     result.iterations = final_state.iterations;
     result.relative_residual = final_state.relative_residual;
     result.converged = final_state.converged;

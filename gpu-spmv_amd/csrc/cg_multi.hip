@@ -7,8 +7,8 @@
 // (CgColumn) and its own partials, and a header in front of the column states carries the global `done` the host
 // polls.  Per step, three launches whatever k:
 //   cgm_spmv_dot<LANES, W, NW>  Q = A P and, per column, the block partials of p.q
-//   cgm_update_kernel<W>        per column: the fold of p.q, alpha, x += alpha p, r -= alpha q, partials of r.z, r.r
-//   cgm_direction_kernel<W>     per column: the fold, beta and the stop test, p = z + beta p; workgroup 0 commits
+//   cgm_update_kernel<W, false>     per column: the fold of p.q, alpha, x += alpha p, r -= alpha q, partials of r.z, r.r
+//   cgm_direction_kernel<W, false>  per column: the fold, beta and the stop test, p = z + beta p; workgroup 0 commits
 // Column j is bit for bit cg_solve(engine = 0) on that column: a row's sum is row_partial_dot<LANES>'s walk with one
 // accumulator per column, the thread-to-row mapping and the grids are cg.hip's, a thread of the element-wise
 // kernels owns row i of the k-wide vectors where cg.hip's owns element i, and each column's partials are laid out
@@ -17,14 +17,17 @@
 //
 // cg_solve_multi_ic is cg.hip's stored-z loop, k-wide: Z is a fourth windowed array, the SpMV half
 // of a step is cgm_spmv_dot unchanged, and the second half is
-//   cgm_ic_update_kernel<W>     as cgm_update_kernel, but only the partials of r.r (z does not exist yet)
-//   launch_sptrsv_multi x 2     Z = L^-1 R (LOWER NON_UNIT), then Z = L^-T Z in place (UPPER NON_UNIT): ONE k-wide
-//                               launch sequence each (sptrsv_multi.hip on the windowed workspace, no copy)
-//   cgm_rz_kernel<W>            per column the partials of r.z
-//   cgm_ic_direction_kernel<W>  as cgm_direction_kernel with z read from memory
+//   cgm_update_kernel<W, true>     the same kernel with STORED_Z: only the partials of r.r (z does not exist yet)
+//   TriangularPair::apply          Z = L^-1 R (LOWER NON_UNIT), then Z = L^-T Z in place (UPPER NON_UNIT): ONE k-wide
+//                                  launch sequence each (sptrsv_multi.hip on the windowed workspace, no copy)
+//   cgm_rz_kernel<W>               per column the partials of r.z
+//   cgm_direction_kernel<W, true>  the same kernel with z read from memory
 // so a step has cg_solve_ic's launches whatever k.  The triangular solves do not read `done`, as cg.hip's do not: they
 // recompute Z for all k columns (the padding columns of the last window included) from an R that no longer changes
-// for a frozen column.  A frozen column's Z is never read: cgm_rz_kernel and cgm_ic_direction_kernel skip it.
+// for a frozen column.  A frozen column's Z is never read: cgm_rz_kernel and cgm_direction_kernel skip it.
+//
+// The host side is built from solver_common.h's parts (Workspace and its mirror, TriangularPair, diag_kernel) and
+// multi_window.h's with_window; there is no tiled engine here.
 #include "internal.h"
 #include "device_common.h"
 #include "multi_window.h"
@@ -145,28 +148,6 @@ __device__ __forceinline__ void row_partial_dot_multi(int begin, int end, int la
             for (int q = 0; q < W; ++q) acc[q] = mine[e] ? __builtin_fmaf(v[e], xv[e][q], acc[q]) : acc[q];
         }
     }
-}
-
-// cg.hip's cg_diag_kernel on the k-wide state: dinv is shared by the columns.
-__global__ __launch_bounds__(kBlock)
-void cgm_diag_kernel(int n, const int* __restrict__ row_ptrs, const int* __restrict__ cols,
-                     const float* __restrict__ vals, float* __restrict__ dinv, CgMultiState* __restrict__ state) {
-    int bad = 0;
-    for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < n;
-         i += static_cast<long long>(gridDim.x) * kBlock) {
-        float d = 0.0f;
-        int found = 0;
-        for (int j = row_ptrs[i]; j < row_ptrs[i + 1]; ++j) {
-            if (cols[j] == i) {
-                d = __fadd_rn(d, vals[j]);
-                found = 1;
-            }
-        }
-        const bool ok = found && d > 0.0f;
-        dinv[i] = ok ? __fdiv_rn(1.0f, d) : 0.0f;
-        bad |= !ok;
-    }
-    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(&state->bad_diagonal, 1);
 }
 
 // R0 = B - A X0, P0 = Z0 = R0 * dinv, and per column the block partials of r.z, r.r and b.b ->
@@ -351,13 +332,16 @@ void cgm_spmv_dot(int n, long long nnz, const int* __restrict__ row_ptrs, const 
 }
 
 // Per column: alpha = rz / p.q; x += alpha p; r -= alpha q; partials of r.z and r.r ->
-// part_out[(2 * gridDim.x) * column + 2 * block].  A thread owns row i of the k-wide vectors.
-template <int W>
+// part_out[(2 * gridDim.x) * column + 2 * block], z = r * dinv (r where dinv is null).  A thread owns row i of the
+// k-wide vectors.  STORED_Z (IC): z does not exist yet and dinv is not read: the partials of r.r alone, into the same
+// slot ([... + 1]); r.z follows from cgm_rz_kernel.
+template <int W, bool STORED_Z>
 __global__ __launch_bounds__(kBlock)
 void cgm_update_kernel(int n, int step, int k, const float* __restrict__ p, const float* __restrict__ q,
                        const float* __restrict__ dinv, float* __restrict__ X, long long ldx,
                        float* __restrict__ r, CgMultiState* __restrict__ state, const double* __restrict__ pq_part,
                        int pq_count, long long pq_stride, double* __restrict__ part_out) {
+    constexpr int kSums = STORED_Z ? 1 : 2;       // per column: r.r, or r.z and r.r
     const unsigned active = active_columns(state, k);
     if (!active) return;
     const long long out_stride = 2LL * gridDim.x;
@@ -390,9 +374,9 @@ void cgm_update_kernel(int n, int step, int k, const float* __restrict__ p, cons
             }
         }
         if (!m) continue;
-        double sums[2 * W];           // r.z, r.r of column j0 + c at [2 * c ..]
+        double sums[kSums * W];       // r.z, r.r of column j0 + c at [2 * c ..]; STORED_Z: r.r at [c]
 #pragma unroll
-        for (int c = 0; c < 2 * W; ++c) sums[c] = 0.0;
+        for (int c = 0; c < kSums * W; ++c) sums[c] = 0.0;
         const long long window = static_cast<long long>(j0 / W) * n * W;
         const float* pw = p + window;
         const float* qw = q + window;
@@ -403,7 +387,7 @@ void cgm_update_kernel(int n, int step, int k, const float* __restrict__ p, cons
             load_own<W>(pw, W, i, 0, pv);
             load_own<W>(qw, W, i, 0, qv);
             load_own<W>(rw, W, i, 0, rv);
-            const float di = dinv ? dinv[i] : 1.0f;
+            [[maybe_unused]] const float di = dinv ? dinv[i] : 1.0f;      // (STORED_Z: not used, no load)
 #pragma unroll
             for (int c = 0; c < W; ++c) {
                 if ((m >> c) & 1u) {
@@ -411,23 +395,30 @@ void cgm_update_kernel(int n, int step, int k, const float* __restrict__ p, cons
                     *xi = __builtin_fmaf(alpha[c], pv[c], *xi);
                     const float ri = __builtin_fmaf(-alpha[c], qv[c], rv[c]);
                     rw[i * W + c] = ri;
-                    const float zi = dinv ? __fmul_rn(ri, di) : ri;
-                    sums[2 * c] += prod64(ri, zi);
-                    sums[2 * c + 1] += prod64(ri, ri);
+                    if constexpr (STORED_Z) {
+                        sums[c] += prod64(ri, ri);
+                    } else {
+                        const float zi = dinv ? __fmul_rn(ri, di) : ri;
+                        sums[2 * c] += prod64(ri, zi);
+                        sums[2 * c + 1] += prod64(ri, ri);
+                    }
                 }
             }
         }
-        const double total = block_sum_columns<2 * W>(sums);
-        const int c = threadIdx.x / 2;
-        if (c < W && ((m >> c) & 1u)) part_out[out_stride * (j0 + c) + 2LL * blockIdx.x + threadIdx.x % 2] = total;
+        const double total = block_sum_columns<kSums * W>(sums);
+        const int c = threadIdx.x / kSums;
+        if (c < W && ((m >> c) & 1u)) {
+            part_out[out_stride * (j0 + c) + 2LL * blockIdx.x + (STORED_Z ? 1 : threadIdx.x % 2)] = total;
+        }
     }
 }
 
 // Per column: beta = rz_new / rz_old, the stop test, p = z + beta p.  Workgroup 0 commits each column's step and,
-// once no column is left, the global flag.
-template <int W>
+// once no column is left, the global flag.  zr is R and z = r * dinv (r where dinv is null), or with STORED_Z it is Z
+// itself and dinv is not read.
+template <int W, bool STORED_Z>
 __global__ __launch_bounds__(kBlock)
-void cgm_direction_kernel(int n, int step, int k, const float* __restrict__ r, const float* __restrict__ dinv,
+void cgm_direction_kernel(int n, int step, int k, const float* __restrict__ zr, const float* __restrict__ dinv,
                           float* __restrict__ p, CgMultiState* __restrict__ state,
                           const double* __restrict__ part, int count) {
     const unsigned active = active_columns(state, k);
@@ -478,115 +469,25 @@ void cgm_direction_kernel(int n, int step, int k, const float* __restrict__ r, c
         }
         if (!m) continue;
         const long long window = static_cast<long long>(j0 / W) * n * W;
-        const float* rw = r + window;
+        const float* zw = zr + window;
         float* pw = p + window;
         for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < n;
              i += static_cast<long long>(gridDim.x) * kBlock) {
-            float rv[W], pv[W];
-            load_own<W>(rw, W, i, 0, rv);
+            float zv[W], pv[W];
+            load_own<W>(zw, W, i, 0, zv);
             load_own<W>(pw, W, i, 0, pv);
-            const float di = dinv ? dinv[i] : 1.0f;
+            [[maybe_unused]] const float di = dinv ? dinv[i] : 1.0f;      // (STORED_Z: not used, no load)
 #pragma unroll
             for (int c = 0; c < W; ++c) {
                 if ((m >> c) & 1u) {
-                    const float zi = dinv ? __fmul_rn(rv[c], di) : rv[c];
+                    float zi = zv[c];
+                    if constexpr (!STORED_Z) zi = dinv ? __fmul_rn(zi, di) : zi;
                     pw[i * W + c] = __builtin_fmaf(beta[c], pv[c], zi);
                 }
             }
         }
     }
     if (commits && finished == k) state->done = 1;
-}
-
-// cg.hip's cg_ic_diag_kernel on the k-wide state: some row of the factor has no stored diagonal, or one that is not
-// > 0 or not finite.
-__global__ __launch_bounds__(kBlock)
-void cgm_ic_diag_kernel(int n, const int* __restrict__ row_ptrs, const int* __restrict__ cols,
-                        const float* __restrict__ vals, CgMultiState* __restrict__ state) {
-    int bad = 0;
-    for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < n;
-         i += static_cast<long long>(gridDim.x) * kBlock) {
-        float d = 0.0f;
-        int found = 0;
-        for (int j = row_ptrs[i]; j < row_ptrs[i + 1]; ++j) {
-            if (cols[j] == i) {
-                d = __fadd_rn(d, vals[j]);
-                found = 1;
-            }
-        }
-        bad |= !(found && d > 0.0f && isfinite(d));
-    }
-    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(&state->bad_diagonal, 1);
-}
-
-// IC: cgm_update_kernel without z: per column alpha, x += alpha p, r -= alpha q, and the partials of r.r alone ->
-// part_out[(2 * gridDim.x) * column + 2 * block + 1] (cgm_update_kernel's slot; r.z follows from cgm_rz_kernel).
-template <int W>
-__global__ __launch_bounds__(kBlock)
-void cgm_ic_update_kernel(int n, int step, int k, const float* __restrict__ p, const float* __restrict__ q,
-                          float* __restrict__ X, long long ldx, float* __restrict__ r,
-                          CgMultiState* __restrict__ state, const double* __restrict__ pq_part, int pq_count,
-                          long long pq_stride, double* __restrict__ part_out) {
-    const unsigned active = active_columns(state, k);
-    if (!active) return;
-    const long long out_stride = 2LL * gridDim.x;
-    for (int j0 = 0; j0 < k; j0 += W) {
-        const unsigned running = (active >> j0) & ((1u << W) - 1u);
-        if (!running) continue;
-        double pq[W];
-#pragma unroll
-        for (int c = 0; c < W; ++c) pq[c] = 0.0;
-        for (int i = threadIdx.x; i < pq_count; i += kBlock) {
-#pragma unroll
-            for (int c = 0; c < W; ++c) pq[c] += pq_part[pq_stride * (j0 + c) + i];   // (all W: the array is padded)
-        }
-        fold_values<W>(pq);
-        float alpha[W];
-        unsigned m = 0;
-#pragma unroll
-        for (int c = 0; c < W; ++c) {
-            alpha[c] = 0.0f;
-            if (!((running >> c) & 1u)) continue;
-            const int j = j0 + c;
-            if (!(pq[c] > 0.0)) {          // this column's A is not SPD (or p.q is not finite): its x stays as it is
-                if (blockIdx.x == 0 && threadIdx.x == 0) {
-                    state->col[j].breakdown = 1;
-                    state->col[j].done = 1;
-                }
-            } else {
-                alpha[c] = static_cast<float>(state->col[j].rz[step & 1] / pq[c]);
-                m |= 1u << c;
-            }
-        }
-        if (!m) continue;
-        double sums[W];               // r.r of column j0 + c
-#pragma unroll
-        for (int c = 0; c < W; ++c) sums[c] = 0.0;
-        const long long window = static_cast<long long>(j0 / W) * n * W;
-        const float* pw = p + window;
-        const float* qw = q + window;
-        float* rw = r + window;
-        for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < n;
-             i += static_cast<long long>(gridDim.x) * kBlock) {
-            float pv[W], qv[W], rv[W];
-            load_own<W>(pw, W, i, 0, pv);
-            load_own<W>(qw, W, i, 0, qv);
-            load_own<W>(rw, W, i, 0, rv);
-#pragma unroll
-            for (int c = 0; c < W; ++c) {
-                if ((m >> c) & 1u) {
-                    float* xi = X + i * ldx + j0 + c;
-                    *xi = __builtin_fmaf(alpha[c], pv[c], *xi);
-                    const float ri = __builtin_fmaf(-alpha[c], qv[c], rv[c]);
-                    rw[i * W + c] = ri;
-                    sums[c] += prod64(ri, ri);
-                }
-            }
-        }
-        const double total = block_sum_columns<W>(sums);
-        const int c = threadIdx.x;
-        if (c < W && ((m >> c) & 1u)) part_out[out_stride * (j0 + c) + 2LL * blockIdx.x + 1] = total;
-    }
 }
 
 // IC: per column the block partials of r.z -> part[col_stride * column + stride * block] (stride 2 and the loop's
@@ -623,89 +524,25 @@ void cgm_rz_kernel(int n, int k, const float* __restrict__ r, const float* __res
     }
 }
 
-// IC: cgm_direction_kernel with the stored z.
-template <int W>
-__global__ __launch_bounds__(kBlock)
-void cgm_ic_direction_kernel(int n, int step, int k, const float* __restrict__ z, float* __restrict__ p,
-                             CgMultiState* __restrict__ state, const double* __restrict__ part, int count) {
-    const unsigned active = active_columns(state, k);
-    if (!active) return;
-    const bool commits = blockIdx.x == 0 && threadIdx.x == 0;
-    int finished = k - __popc(active);
-    for (int j0 = 0; j0 < k; j0 += W) {
-        const unsigned running = (active >> j0) & ((1u << W) - 1u);
-        if (!running) continue;
-        double sums[2 * W];
-#pragma unroll
-        for (int c = 0; c < 2 * W; ++c) sums[c] = 0.0;
-        for (int i = threadIdx.x; i < count; i += kBlock) {
-#pragma unroll
-            for (int c = 0; c < W; ++c) {         // (all W: the array is padded)
-                const double* mine = part + 2LL * count * (j0 + c) + 2LL * i;
-                sums[2 * c] += mine[0];
-                sums[2 * c + 1] += mine[1];
-            }
-        }
-        fold_values<2 * W>(sums);
-        float beta[W];
-        unsigned m = 0;
-#pragma unroll
-        for (int c = 0; c < W; ++c) {
-            beta[c] = 0.0f;
-            if (!((running >> c) & 1u)) continue;
-            CgColumn& col = state->col[j0 + c];
-            const double rz = sums[2 * c], rr = sums[2 * c + 1];
-            const double res = sqrt(rr);
-            const bool converged = res <= col.threshold;
-            const bool breakdown = !converged && !(rz > 0.0);
-            const double rz_old = col.rz[step & 1];
-            if (commits) {
-                col.iterations = step + 1;
-                col.relative_residual = static_cast<float>(res / col.bnorm);
-                col.rz[(step + 1) & 1] = rz;
-                if (converged) col.converged = 1;
-                if (breakdown) col.breakdown = 1;
-                if (converged || breakdown) col.done = 1;
-            }
-            if (converged || breakdown) {
-                ++finished;
-            } else {
-                beta[c] = static_cast<float>(rz / rz_old);
-                m |= 1u << c;
-            }
-        }
-        if (!m) continue;
-        const long long window = static_cast<long long>(j0 / W) * n * W;
-        const float* zw = z + window;
-        float* pw = p + window;
-        for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < n;
-             i += static_cast<long long>(gridDim.x) * kBlock) {
-            float zv[W], pv[W];
-            load_own<W>(zw, W, i, 0, zv);
-            load_own<W>(pw, W, i, 0, pv);
-#pragma unroll
-            for (int c = 0; c < W; ++c) {
-                if ((m >> c) & 1u) pw[i * W + c] = __builtin_fmaf(beta[c], pv[c], zv[c]);
-            }
-        }
-    }
-    if (commits && finished == k) state->done = 1;
-}
-
 struct Shape {
     const CSRMatrix* A;
     int k;
     int w;                    // columns per window of the workspace: 4 up to k = 4, else 8
 };
 
-template <int LANES, int W, int WS>
-hipError_t launch_init(const Shape& sh, const float* B, int ldb, const float* X, int ldx, const float* dinv,
-                       float* r, float* p, double* part, int grid, hipStream_t s) {
+// windows of 4 columns of B and X at every k: with 8, the guards of the caller's B and X push scalar registers out
+hipError_t init(int lanes, const Shape& sh, const float* B, int ldb, const float* X, int ldx, const float* dinv,
+                float* r, float* p, double* part, int grid, hipStream_t s) {
     const CSRMatrix* A = sh.A;
     const bool x_vec = ldx % 4 == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
-    cgm_init_kernel<LANES, W, WS><<<grid, kBlock, 0, s>>>(A->num_rows, A->nnz, A->d_row_ptrs, A->d_col_indices,
-                                                          A->d_values, B, ldb, X, ldx, x_vec, sh.k, dinv, r, p, part);
-    return hipGetLastError();
+    return with_lanes(lanes, [&](auto L) {
+        return with_window(sh.w, [&](auto WS) {
+            cgm_init_kernel<decltype(L)::value, 4, decltype(WS)::value><<<grid, kBlock, 0, s>>>(
+                A->num_rows, A->nnz, A->d_row_ptrs, A->d_col_indices, A->d_values, B, ldb, X, ldx, x_vec, sh.k, dinv, r,
+                p, part);
+            return hipGetLastError();
+        });
+    });
 }
 
 template <int LANES, int W, int NW>
@@ -715,16 +552,6 @@ hipError_t launch_spmv_dot(const Shape& sh, const float* p, float* q, const CgMu
     cgm_spmv_dot<LANES, W, NW><<<grid, kBlock, 0, s>>>(A->num_rows, A->nnz, A->d_row_ptrs, A->d_col_indices,
                                                        A->d_values, p, q, sh.k, state, part, grid);
     return hipGetLastError();
-}
-
-hipError_t init(int lanes, const Shape& sh, const float* B, int ldb, const float* X, int ldx, const float* dinv,
-                float* r, float* p, double* part, int grid, hipStream_t s) {
-    return with_lanes(lanes, [&](auto L) {
-        constexpr int kLanes = decltype(L)::value;
-        // windows of 4 at every k: with 8, the guards of the caller's B and X push scalar registers out
-        return sh.w == 4 ? launch_init<kLanes, 4, 4>(sh, B, ldb, X, ldx, dinv, r, p, part, grid, s)
-                         : launch_init<kLanes, 4, 8>(sh, B, ldb, X, ldx, dinv, r, p, part, grid, s);
-    });
 }
 
 // windows: one of 4 columns up to k = 4, then 1, 2 or 4 of 8 columns
@@ -766,9 +593,7 @@ int solve_multi(const CSRMatrix* A, bool with_ic, const CSRMatrix* F, const floa
         }
         return code(SpMVError::SUCCESS);
     }
-    if (A->num_rows < 0 || !A->d_row_ptrs || (A->nnz > 0 && (!A->d_col_indices || !A->d_values))) {
-        return fail(SpMVError::INVALID_FORMAT);
-    }
+    if (!device_arrays(A)) return fail(SpMVError::INVALID_FORMAT);
     const CGConfig defaults;
     const CGConfig& cfg = config ? *config : defaults;
     if (!(cfg.tolerance >= 0.0f) || cfg.max_iterations < 0 ||
@@ -783,26 +608,17 @@ int solve_multi(const CSRMatrix* A, bool with_ic, const CSRMatrix* F, const floa
     if (with_ic) {
         if (!F) return fail(SpMVError::INVALID_ARGUMENT);
         if (F->num_rows != F->num_cols || F->num_rows != n) return fail(SpMVError::INVALID_DIMENSION);
-        if (F->num_rows < 0 || !F->d_row_ptrs || (F->nnz > 0 && (!F->d_col_indices || !F->d_values))) {
-            return fail(SpMVError::INVALID_FORMAT);
-        }
+        if (!device_arrays(F)) return fail(SpMVError::INVALID_FORMAT);
     }
 
     const TraceRange range(with_ic ? "spmv:cg_solve_multi_ic" : "spmv:cg_solve_multi");
     hipStream_t stream = current_stream();
     const bool jacobi = !with_ic && cfg.preconditioner == CGConfig::JACOBI;
 
-    // both schedules of F, ahead of the timed loop (a build synchronises the stream); they validate F's structure
-    // before any kernel walks it
-    std::shared_ptr<const SptrsvSchedule> lower, upper;
-    int lower_lanes = 1, upper_lanes = 1;
+    TriangularPair ic;                // M = L L^T: the lower solve reads L's stored diagonal
     if (with_ic) {
-        float analysis_ms = 0.0f;
-        int status = sptrsv_schedule_for(F, SpTRSVConfig::LOWER, stream, &lower, &analysis_ms);
-        if (status == 0) status = sptrsv_schedule_for(F, SpTRSVConfig::UPPER, stream, &upper, &analysis_ms);
+        const int status = ic.build(F, 0, stream);
         if (status != 0) return fail(static_cast<SpMVError>(status));
-        lower_lanes = sptrsv_lanes_for(*lower);
-        upper_lanes = sptrsv_lanes_for(*upper);
     }
 
     const int lanes = pick_lanes_per_row(static_cast<float>(A->nnz) / n);
@@ -829,36 +645,29 @@ int solve_multi(const CSRMatrix* A, bool with_ic, const CSRMatrix* F, const floa
     double* rr_part = pq_part + k_pad * pq_count;
     double* init_part = rr_part + k_pad * rr_count;
     CgMultiState* pinned = ws.pinned;
-    const bool wide = k > 4;
     // Z = L^-T (L^-1 R) on the windowed workspace, whole windows (the padding columns are solved along and never used)
     const auto apply_ic = [&]() -> bool {
         const long long window = static_cast<long long>(n) * sh.w;
         const SptrsvMultiArrays down{r, sh.w, window, z, sh.w, window, static_cast<int>(k_pad), sh.w};
         const SptrsvMultiArrays up{z, sh.w, window, z, sh.w, window, static_cast<int>(k_pad), sh.w};
-        return launch_sptrsv_multi(*lower, F, down, SpTRSVConfig::LOWER, 0, false, lower_lanes, stream) == hipSuccess &&
-               launch_sptrsv_multi(*upper, F, up, SpTRSVConfig::UPPER, 0, false, upper_lanes, stream) == hipSuccess;
+        return ic.apply(down, up, stream);
     };
 
     // setup: the shared diagonal, R0 / P0 and their dots, the column states; one read-back
     bool ok = hipMemsetAsync(ws.state, 0, sizeof(CgMultiState), stream) == hipSuccess;
-    if (ok && jacobi) {
-        cgm_diag_kernel<<<vgrid, kBlock, 0, stream>>>(n, A->d_row_ptrs, A->d_col_indices, A->d_values, dinv,
-                                                      ws.state);
-        ok = hipGetLastError() == hipSuccess;
-    }
-    if (ok && with_ic) {
-        cgm_ic_diag_kernel<<<vgrid, kBlock, 0, stream>>>(n, F->d_row_ptrs, F->d_col_indices, F->d_values, ws.state);
-        ok = hipGetLastError() == hipSuccess;
-    }
+    int* bad = &ws.state->bad_diagonal;
+    if (jacobi) ok = ok && launch_diag<DiagRule::POSITIVE>(A, dinv, bad, stream) == hipSuccess;
+    if (with_ic) ok = ok && launch_diag<DiagRule::POSITIVE_FINITE>(F, nullptr, bad, stream) == hipSuccess;
     ok = ok && init(lanes, sh, d_B, ldb, d_X, ldx, dinv, r, p, init_part, row_grid, stream) == hipSuccess;
     if (ok && with_ic) {
         // the init kernel left P0 = R0 and r0.r0 in the r.z slots: Z0 = M^-1 R0, the true r0.z0 over them, P0 = Z0
         ok = apply_ic();
         if (ok) {
-            const long long stride = 3LL * row_grid;
-            if (wide) cgm_rz_kernel<8><<<row_grid, kBlock, 0, stream>>>(n, k, r, z, ws.state, init_part, stride, 3);
-            else      cgm_rz_kernel<4><<<row_grid, kBlock, 0, stream>>>(n, k, r, z, ws.state, init_part, stride, 3);
-            ok = hipGetLastError() == hipSuccess &&
+            ok = with_window(sh.w, [&](auto W) {
+                cgm_rz_kernel<decltype(W)::value><<<row_grid, kBlock, 0, stream>>>(n, k, r, z, ws.state, init_part,
+                                                                                   3LL * row_grid, 3);
+                return hipGetLastError();
+            }) == hipSuccess &&
                  hipMemcpyAsync(p, z, len * sizeof(float), hipMemcpyDeviceToDevice, stream) == hipSuccess;
         }
     }
@@ -866,12 +675,7 @@ int solve_multi(const CSRMatrix* A, bool with_ic, const CSRMatrix* F, const floa
         cgm_start_kernel<<<1, kBlock, 0, stream>>>(init_part, row_grid, k, cfg.tolerance, ws.state);
         ok = hipGetLastError() == hipSuccess;
     }
-    ok = ok && hipMemcpyAsync(&pinned[0], ws.state, sizeof(CgMultiState), hipMemcpyDeviceToHost, stream) == hipSuccess
-            && hipStreamSynchronize(stream) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        return fail(SpMVError::KERNEL_LAUNCH);
-    }
+    if (!ws.read_back(ok, stream)) return fail(SpMVError::KERNEL_LAUNCH);
     if (pinned[0].bad_diagonal) return fail(SpMVError::INVALID_ARGUMENT);
     bool any_zero_b = false;
     for (int j = 0; j < k; ++j) any_zero_b = any_zero_b || pinned[0].col[j].zero_b;
@@ -889,56 +693,36 @@ int solve_multi(const CSRMatrix* A, bool with_ic, const CSRMatrix* F, const floa
             const TraceRange step_range("spmv:cg_multi_step");
             ok = spmv_dot(lanes, sh, p, q, ws.state, pq_part, row_grid, stream) == hipSuccess;
             if (ok && with_ic) {
-                if (wide) {
-                    cgm_ic_update_kernel<8><<<vgrid, kBlock, 0, stream>>>(n, iter, k, p, q, d_X, ldx, r, ws.state,
-                                                                          pq_part, row_grid, row_grid, rr_part);
-                } else {
-                    cgm_ic_update_kernel<4><<<vgrid, kBlock, 0, stream>>>(n, iter, k, p, q, d_X, ldx, r, ws.state,
-                                                                          pq_part, row_grid, row_grid, rr_part);
-                }
-                ok = hipGetLastError() == hipSuccess && apply_ic();
+                ok = with_window(sh.w, [&](auto W) {
+                    cgm_update_kernel<decltype(W)::value, true><<<vgrid, kBlock, 0, stream>>>(
+                        n, iter, k, p, q, nullptr, d_X, ldx, r, ws.state, pq_part, row_grid, row_grid, rr_part);
+                    return hipGetLastError();
+                }) == hipSuccess && apply_ic();
             }
             if (ok) {
-                if (with_ic && wide) {
-                    cgm_rz_kernel<8><<<vgrid, kBlock, 0, stream>>>(n, k, r, z, ws.state, rr_part, 2LL * vgrid, 2);
-                    cgm_ic_direction_kernel<8><<<vgrid, kBlock, 0, stream>>>(n, iter, k, z, p, ws.state, rr_part,
-                                                                             vgrid);
-                } else if (with_ic) {
-                    cgm_rz_kernel<4><<<vgrid, kBlock, 0, stream>>>(n, k, r, z, ws.state, rr_part, 2LL * vgrid, 2);
-                    cgm_ic_direction_kernel<4><<<vgrid, kBlock, 0, stream>>>(n, iter, k, z, p, ws.state, rr_part,
-                                                                             vgrid);
-                } else if (wide) {
-                    cgm_update_kernel<8><<<vgrid, kBlock, 0, stream>>>(n, iter, k, p, q, dinv, d_X, ldx, r,
-                                                                       ws.state, pq_part, row_grid, row_grid,
-                                                                       rr_part);
-                    cgm_direction_kernel<8><<<vgrid, kBlock, 0, stream>>>(n, iter, k, r, dinv, p, ws.state,
-                                                                          rr_part, vgrid);
-                } else {
-                    cgm_update_kernel<4><<<vgrid, kBlock, 0, stream>>>(n, iter, k, p, q, dinv, d_X, ldx, r,
-                                                                       ws.state, pq_part, row_grid, row_grid,
-                                                                       rr_part);
-                    cgm_direction_kernel<4><<<vgrid, kBlock, 0, stream>>>(n, iter, k, r, dinv, p, ws.state,
-                                                                          rr_part, vgrid);
-                }
                 // the host needs the global flag alone per step: the header in front of the column states
-                ok = hipGetLastError() == hipSuccess
-                  && hipMemcpyAsync(&pinned[iter & 1], ws.state, kHeaderBytes, hipMemcpyDeviceToHost,
-                                    stream) == hipSuccess
-                  && hipEventRecord(ws.seen[iter & 1], stream) == hipSuccess;
+                ok = with_window(sh.w, [&](auto WC) {
+                    constexpr int W = decltype(WC)::value;
+                    if (with_ic) {
+                        cgm_rz_kernel<W><<<vgrid, kBlock, 0, stream>>>(n, k, r, z, ws.state, rr_part, 2LL * vgrid, 2);
+                        cgm_direction_kernel<W, true><<<vgrid, kBlock, 0, stream>>>(n, iter, k, z, nullptr, p, ws.state,
+                                                                                    rr_part, vgrid);
+                    } else {
+                        cgm_update_kernel<W, false><<<vgrid, kBlock, 0, stream>>>(
+                            n, iter, k, p, q, dinv, d_X, ldx, r, ws.state, pq_part, row_grid, row_grid, rr_part);
+                        cgm_direction_kernel<W, false><<<vgrid, kBlock, 0, stream>>>(n, iter, k, r, dinv, p, ws.state,
+                                                                                     rr_part, vgrid);
+                    }
+                    return hipGetLastError();
+                }) == hipSuccess && ws.publish(iter, kHeaderBytes, stream);
             }
             if (ok && iter >= 1) {
-                ok = hipEventSynchronize(ws.seen[(iter - 1) & 1]) == hipSuccess;
-                if (ok && pinned[(iter - 1) & 1].done) break;
+                const CgMultiState* seen = ws.wait_previous(iter);
+                ok = seen != nullptr;
+                if (ok && seen->done) break;
             }
         }
-        ok = ok && hipEventRecord(ev.stop, stream) == hipSuccess;
-        if (ok) {
-            ok = hipMemcpyAsync(&pinned[0], ws.state, sizeof(CgMultiState), hipMemcpyDeviceToHost,
-                                stream) == hipSuccess
-              && hipStreamSynchronize(stream) == hipSuccess;
-            float ms = 0.0f;
-            if (ok && hipEventElapsedTime(&ms, ev.start, ev.stop) == hipSuccess) elapsed_ms = ms;
-        }
+        ok = ws.finish_timed(ok, ev, stream, &elapsed_ms);
     } else if (ok) {
         ok = hipStreamSynchronize(stream) == hipSuccess;      // the zero columns, if any
     }

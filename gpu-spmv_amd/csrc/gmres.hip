@@ -7,7 +7,7 @@
 // close kernels only while closed, so either sequence enqueued at the wrong moment changes nothing.
 //
 // A step, column j (the basis vectors v_0..v_j are ready, with JACOBI also z = v_j * dinv):
-//   [LU: z = U^-1 (L^-1 v_j), two launch_sptrsv sequences]
+//   [LU: z = U^-1 (L^-1 v_j), TriangularPair::apply's two launch_sptrsv sequences]
 //   gmres_spmv<LANES> / tiled_spmv    w = A z
 //   gmres_multidot                    one pass over w and v_0..v_j: (j+1) partials per workgroup of h1_i = v_i.w
 //   gmres_update_multidot             folds h1, w -= h1_i v_i, then the partials of h2_i = v_i.w on the updated w
@@ -25,6 +25,10 @@
 // A one-workgroup kernel is the only writer of the state, and no kernel reads a state field that a kernel of the
 // same launch writes.  The ungated launches (tiled_spmv, launch_sptrsv) write only w, u or z, which hold nothing
 // live at a step boundary.
+//
+// The host side is built from solver_common.h's parts (Workspace and its mirror, TriangularPair, TiledEngine,
+// diag_kernel); what is here is this solver's checks, its workspace layout, its launches, the cycle bookkeeping
+// and its result.
 //
 // The three orthogonalisation kernels walk the basis in compile-time groups of kGroup vectors with kGroup fp64
 // accumulators in registers; a thread's four elements of w stay in registers across the groups of an update.  No
@@ -460,33 +464,6 @@ void gmres_spmv(int n, long long nnz, const int* __restrict__ row_ptrs, const in
     }
 }
 
-// dinv[i] = 1 / (sum of row i's stored (i,i) entries, fp32, storage order); flags rows where that is missing, zero
-// or not finite (bicgstab_solve's diagonal rule).  One thread per row: setup only.
-__global__ __launch_bounds__(kBlock)
-void gmres_diag_kernel(int n, const int* __restrict__ row_ptrs, const int* __restrict__ cols,
-                       const float* __restrict__ vals, float* __restrict__ dinv, GmresState* __restrict__ st) {
-    int bad = 0;
-    for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < n;
-         i += static_cast<long long>(gridDim.x) * kBlock) {
-        float d = 0.0f;
-        int found = 0;
-        for (int j = row_ptrs[i]; j < row_ptrs[i + 1]; ++j) {
-            if (cols[j] == i) {
-                d = __fadd_rn(d, vals[j]);
-                found = 1;
-            }
-        }
-        const bool ok = found && d != 0.0f && isfinite(d);
-        dinv[i] = ok ? __fdiv_rn(1.0f, d) : 0.0f;
-        bad |= !ok;
-    }
-    if (__any(bad) && (threadIdx.x & 63) == 0) st->bad_diagonal = 1;      // every writer stores the same 1
-}
-
-bool device_arrays(const CSRMatrix* M) {
-    return M->num_rows >= 0 && M->d_row_ptrs && (M->nnz <= 0 || (M->d_col_indices && M->d_values));
-}
-
 // gmres_solve (with_lu false: cfg.preconditioner picks NONE or JACOBI) and gmres_solve_lu (with_lu true: M = L U
 // from LU, cfg.preconditioner is not read).
 GMRESResult solve(const CSRMatrix* A, const CSRMatrix* LU, bool with_lu, const float* d_b, float* d_x,
@@ -523,33 +500,12 @@ GMRESResult solve(const CSRMatrix* A, const CSRMatrix* LU, bool with_lu, const f
     const int restart = cfg.restart;
     const int max_it = cfg.max_iterations;
 
-    // both schedules of LU, ahead of the timed loop (a build synchronises the stream); they validate LU's structure
-    // before any kernel walks it
-    std::shared_ptr<const SptrsvSchedule> lower, upper;
-    int lower_lanes = 1, upper_lanes = 1;
+    TriangularPair lu;              // M = L U: L's diagonal is the implied 1
     if (with_lu) {
-        float analysis_ms = 0.0f;
-        int status = sptrsv_schedule_for(LU, SpTRSVConfig::LOWER, stream, &lower, &analysis_ms);
-        if (status == 0) status = sptrsv_schedule_for(LU, SpTRSVConfig::UPPER, stream, &upper, &analysis_ms);
+        const int status = lu.build(LU, 1, stream);
         if (status != 0) return fail(static_cast<SpMVError>(status));
-        lower_lanes = sptrsv_lanes_for(*lower);
-        upper_lanes = sptrsv_lanes_for(*upper);
     }
-    // out = U^-1 (L^-1 in): LOWER UNIT, then UPPER NON_UNIT in place
-    const auto apply_lu = [&](const float* in, float* out) -> bool {
-        return launch_sptrsv(*lower, LU, in, out, SpTRSVConfig::LOWER, 1, false, lower_lanes, stream) == hipSuccess &&
-               launch_sptrsv(*upper, LU, out, out, SpTRSVConfig::UPPER, 0, false, upper_lanes, stream) == hipSuccess;
-    };
-
-    // engine choice (bicgstab_solve's: -1 takes a cached plan from the start, else builds one after 4 direct steps)
-    PlanRef plan;
-    int build_plan_at = -1;
-    if (cfg.engine == 1) {
-        plan = tiled_plan_for(A, stream);
-    } else if (cfg.engine == -1) {
-        plan = tiled_plan_if_cached(A);
-        if (!plan && tiled_eligible(A)) build_plan_at = 4;
-    }
+    TiledEngine engine(A, cfg.engine, stream);
 
     const int lanes = pick_lanes_per_row(static_cast<float>(A->nnz) / n);
     const int row_grid = grid_for_rows(n, kBlock / lanes);
@@ -584,32 +540,17 @@ GMRESResult solve(const CSRMatrix* A, const CSRMatrix* LU, bool with_lu, const f
     sm.h1 = reinterpret_cast<float*>(sm.sn + kMaxRestart);
     sm.h2 = sm.h1 + kMaxRestart;
     sm.y = sm.h2 + kMaxRestart;
-    GmresState* pinned = ws.pinned;
     float* z_out = jacobi ? z : nullptr;           // gmres_normalize writes z only with JACOBI
 
-    // A w -> y, ungated on the tiled engine (the caller passes a y that holds nothing live)
-    const auto drop_plan = [&]() {
-        (void)hipGetLastError();
-        plan.reset();
-        build_plan_at = -1;
-    };
     // r = b - A x into w, its partials, gmres_begin, v_0: the tail of every close sequence, and the setup
     const auto residual_and_begin = [&]() -> bool {
         int count = row_grid;
-        bool direct = true;
-        if (plan) {
-            const hipError_t e = tiled_spmv(*plan, d_x, u, stream);
-            if (e == hipErrorOutOfMemory) {        // no tiled scratch for this stream: direct kernels from here on
-                drop_plan();
-            } else if (e != hipSuccess) {
-                return false;
-            } else {
-                gmres_residual_ew<<<vgrid, kBlock, 0, stream>>>(n, d_b, u, w, ws.state, res_part);
-                count = vgrid;
-                direct = false;
-            }
-        }
-        if (direct) {
+        const TiledEngine::Spmv spmv = engine.spmv(d_x, u, stream);
+        if (spmv == TiledEngine::Spmv::FAILED) return false;
+        if (spmv == TiledEngine::Spmv::TILED) {
+            gmres_residual_ew<<<vgrid, kBlock, 0, stream>>>(n, d_b, u, w, ws.state, res_part);
+            count = vgrid;
+        } else {
             const hipError_t e = with_lanes(lanes, [&](auto L) {
                 gmres_residual<decltype(L)::value><<<row_grid, kBlock, 0, stream>>>(
                     n, A->nnz, A->d_row_ptrs, A->d_col_indices, A->d_values, d_b, d_x, w, ws.state, res_part);
@@ -627,27 +568,18 @@ GMRESResult solve(const CSRMatrix* A, const CSRMatrix* LU, bool with_lu, const f
                                                     ws.state);
         if (hipGetLastError() != hipSuccess) return false;
         if (with_lu) {
-            if (!apply_lu(u, z)) return false;
+            if (!lu.apply(u, z, stream)) return false;
             gmres_add<<<vgrid, kBlock, 0, stream>>>(n, z, d_x, ws.state);
         }
         return residual_and_begin();
     };
     const auto step = [&](int j) -> bool {
         const float* vj = V + static_cast<size_t>(j) * ld;
-        if (with_lu && !apply_lu(vj, z)) return false;
+        if (with_lu && !lu.apply(vj, z, stream)) return false;
         const float* in = mode == 0 ? vj : z;
-        bool direct = true;
-        if (plan) {
-            const hipError_t e = tiled_spmv(*plan, in, w, stream);
-            if (e == hipErrorOutOfMemory) {
-                drop_plan();
-            } else if (e != hipSuccess) {
-                return false;
-            } else {
-                direct = false;
-            }
-        }
-        if (direct) {
+        const TiledEngine::Spmv spmv = engine.spmv(in, w, stream);
+        if (spmv == TiledEngine::Spmv::FAILED) return false;
+        if (spmv == TiledEngine::Spmv::DIRECT) {
             const hipError_t e = with_lanes(lanes, [&](auto L) {
                 gmres_spmv<decltype(L)::value><<<row_grid, kBlock, 0, stream>>>(
                     n, A->nnz, A->d_row_ptrs, A->d_col_indices, A->d_values, in, w, ws.state);
@@ -665,39 +597,21 @@ GMRESResult solve(const CSRMatrix* A, const CSRMatrix* LU, bool with_lu, const f
         return hipGetLastError() == hipSuccess;
     };
 
-    // setup: the diagonal (JACOBI; of LU only its check: the reciprocals land in u, which nothing reads), then the
-    // close sequence of a cycle without columns; one read-back
+    // setup: the diagonal (JACOBI; of LU only its check), then the close sequence of a cycle without columns; one
+    // read-back
     bool ok = hipMemsetAsync(ws.state, 0, sizeof(GmresState), stream) == hipSuccess;
-    if (ok && with_lu) {
-        gmres_diag_kernel<<<vgrid, kBlock, 0, stream>>>(n, LU->d_row_ptrs, LU->d_col_indices, LU->d_values, u,
-                                                        ws.state);
-        ok = hipGetLastError() == hipSuccess;
-    }
-    if (ok && jacobi) {
-        gmres_diag_kernel<<<vgrid, kBlock, 0, stream>>>(n, A->d_row_ptrs, A->d_col_indices, A->d_values, dinv,
-                                                        ws.state);
-        ok = hipGetLastError() == hipSuccess;
-    }
-    ok = ok && residual_and_begin()
-            && hipMemcpyAsync(&pinned[0], ws.state, sizeof(GmresState), hipMemcpyDeviceToHost, stream) == hipSuccess
-            && hipStreamSynchronize(stream) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        return fail(SpMVError::KERNEL_LAUNCH);
-    }
-    if (pinned[0].bad_diagonal) return fail(SpMVError::INVALID_ARGUMENT);
-    if (pinned[0].zero_b) {
-        if (hipMemsetAsync(d_x, 0, static_cast<size_t>(n) * sizeof(float), stream) != hipSuccess ||
-            hipStreamSynchronize(stream) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(SpMVError::KERNEL_LAUNCH);
-        }
+    int* bad = &ws.state->bad_diagonal;
+    if (with_lu) ok = ok && launch_diag<DiagRule::NONZERO_FINITE>(LU, nullptr, bad, stream) == hipSuccess;
+    if (jacobi) ok = ok && launch_diag<DiagRule::NONZERO_FINITE>(A, dinv, bad, stream) == hipSuccess;
+    if (!ws.read_back(ok && residual_and_begin(), stream)) return fail(SpMVError::KERNEL_LAUNCH);
+    if (ws.pinned[0].bad_diagonal) return fail(SpMVError::INVALID_ARGUMENT);
+    if (ws.pinned[0].zero_b) {
+        if (!zero_solution(d_x, static_cast<size_t>(n), stream)) return fail(SpMVError::KERNEL_LAUNCH);
         result.converged = 1;
         return result;
     }
 
-    GmresState final_state = pinned[0];
-    if (!final_state.done) {
+    if (!ws.pinned[0].done) {
         EventPair& ev = thread_events();
         ok = hipEventRecord(ev.start, stream) == hipSuccess;
         // The host follows the device's column j and step count: a cycle that closes where the host expects it
@@ -709,12 +623,7 @@ GMRESResult solve(const CSRMatrix* A, const CSRMatrix* LU, bool with_lu, const f
         long long steps = 0;
         const long long bound = 2LL * max_it + 2;
         for (long long it = 0; ok && it < bound; ++it) {
-            if (!plan && it == build_plan_at) {
-                // enough direct steps paid: drain the queue (nothing is built for a loop that has ended), then plan
-                ok = hipStreamSynchronize(stream) == hipSuccess;
-                if (ok && it >= 1 && pinned[(it - 1) & 1].done) break;
-                plan = ok ? tiled_plan_for(A, stream) : nullptr;
-            }
+            if (!engine.build_if_due(it, ws, stream, ok)) break;
             const TraceRange step_range("spmv:gmres_step");
             ok = ok && step(j);
             ++steps;
@@ -722,30 +631,20 @@ GMRESResult solve(const CSRMatrix* A, const CSRMatrix* LU, bool with_lu, const f
             if (ok && closed_here) ok = close_cycle();
             j = closed_here ? 0 : j + 1;
             if (ok && it >= 1) {
-                ok = hipEventSynchronize(ws.seen[(it - 1) & 1]) == hipSuccess;
-                const GmresState& seen = pinned[(it - 1) & 1];
-                if (ok && seen.done) break;
-                if (ok && !seen.open) {             // closed early at step it - 1: step `it` did nothing
+                const GmresState* seen = ws.wait_previous(it);
+                ok = seen != nullptr;
+                if (ok && seen->done) break;
+                if (ok && !seen->open) {            // closed early at step it - 1: step `it` did nothing
                     if (!closed_here) ok = close_cycle();
                     j = 0;
-                    steps = seen.iterations;
+                    steps = seen->iterations;
                 }
             }
-            ok = ok && hipMemcpyAsync(&pinned[it & 1], ws.state, sizeof(GmresState), hipMemcpyDeviceToHost,
-                                      stream) == hipSuccess
-                    && hipEventRecord(ws.seen[it & 1], stream) == hipSuccess;
+            ok = ok && ws.publish(it, sizeof(GmresState), stream);
         }
-        ok = ok && hipEventRecord(ev.stop, stream) == hipSuccess
-                && hipMemcpyAsync(&pinned[0], ws.state, sizeof(GmresState), hipMemcpyDeviceToHost, stream) == hipSuccess
-                && hipStreamSynchronize(stream) == hipSuccess;
-        if (!ok) {
-            (void)hipGetLastError();
-            return fail(SpMVError::KERNEL_LAUNCH);
-        }
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, ev.start, ev.stop) == hipSuccess) result.elapsed_ms = ms;
-        final_state = pinned[0];
+        if (!ws.finish_timed(ok, ev, stream, &result.elapsed_ms)) return fail(SpMVError::KERNEL_LAUNCH);
     }
+    const GmresState& final_state = ws.pinned[0];
     result.iterations = final_state.iterations;
     result.restarts = std::max(final_state.cycles - 1, 0);
     result.relative_residual = final_state.relative_residual;

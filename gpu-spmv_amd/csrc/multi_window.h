@@ -1,12 +1,15 @@
-// multi_window.h — the row slices of the k-wide kernels (cg_multi.hip, sptrsv_multi.hip): W consecutive columns of one
-// row of a row-major array, as 16-byte accesses where alignment and leading dimension allow and guarded scalar ones
-// otherwise.  Internal: not installed under include/.
+// multi_window.h — the row slices of the k-wide kernels (cg_multi.hip, sptrsv_multi.hip, pagerank_multi_vec.hip): W
+// consecutive columns of one row of a row-major array, as 16-byte accesses where alignment and leading dimension
+// allow and guarded scalar ones otherwise; and with_window, the host's pick of the kernel instantiation for a window
+// width.  Internal: not installed under include/.
 #ifndef SPMV_AMD_MULTI_WINDOW_H
 #define SPMV_AMD_MULTI_WINDOW_H
 
 #include "device_common.h"
 
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 namespace spmv {
 namespace detail {
@@ -86,6 +89,18 @@ __device__ __forceinline__ void store_window(float* V, int ld, int row, int limi
 }
 
 } // namespace dev
+
+namespace solver {
+
+// Calls launch(std::integral_constant<int, W>{}) for the window width w of a k-wide workspace: 4 (k <= 4), else 8
+// (host side; with_lanes' shape, solver_common.h).
+template <class Launch>
+hipError_t with_window(int w, Launch&& launch) {
+    if (w == 4) return launch(std::integral_constant<int, 4>{});
+    return launch(std::integral_constant<int, 8>{});
+}
+
+} // namespace solver
 } // namespace detail
 } // namespace spmv
 

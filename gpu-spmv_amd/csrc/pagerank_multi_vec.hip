@@ -19,6 +19,7 @@
 // workgroups.
 #include "internal.h"
 #include "device_common.h"
+#include "multi_window.h"
 #include "pagerank_engine.h"
 #include "solver_common.h"
 #include "spmv/pagerank.h"
@@ -63,24 +64,6 @@ struct PprState {
 };
 
 constexpr size_t kHeaderBytes = offsetof(PprState, col);
-
-// cg_multi.hip's load_window: W floats of row `row` of the caller's row-major array V from column j0 (a multiple of
-// 4) on; columns at or past `limit` come back 0.  vec: V is 16-byte aligned and ld % 4 == 0.
-template <int W>
-__device__ __forceinline__ void load_window(const float* __restrict__ V, long long ld, long long row, int j0,
-                                            int limit, bool vec, float (&out)[W]) {
-    const float* p = V + row * ld + j0;
-#pragma unroll
-    for (int g = 0; g < W; g += 4) {
-        if (vec && j0 + g + 4 <= limit) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(p + g);
-            out[g] = v[0]; out[g + 1] = v[1]; out[g + 2] = v[2]; out[g + 3] = v[3];
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) out[g + e] = j0 + g + e < limit ? p[g + e] : 0.0f;
-        }
-    }
-}
 
 // One row of one of the loop's own windows (num_rows x W, 16-byte aligned): W / 4 unconditional dwordx4 loads.
 template <int W>
@@ -614,17 +597,14 @@ int personalized(const CSRMatrix* adj, const float* d_V, int ldv, float* d_R, in
     bool ok = dangling_mask(adj, mask.get(), stream)
            && hipMemsetAsync(ws.state, 0, sizeof(PprState), stream) == hipSuccess;
     if (ok) {
-        if (w == 4) ppr_setup_kernel<4><<<vgrid, kBlock, 0, stream>>>(n, k, d_V, ldv, v_vec, mask.get(), vw, bufs[0], ws.state, ws.part);
-        else ppr_setup_kernel<8><<<vgrid, kBlock, 0, stream>>>(n, k, d_V, ldv, v_vec, mask.get(), vw, bufs[0], ws.state, ws.part);
-        ppr_start_kernel<<<1, kBlock, 0, stream>>>(ws.part, vgrid, k, ws.state);
-        ok = hipGetLastError() == hipSuccess
-          && hipMemcpyAsync(&pinned[0], ws.state, kHeaderBytes, hipMemcpyDeviceToHost, stream) == hipSuccess
-          && hipStreamSynchronize(stream) == hipSuccess;
+        ok = with_window(w, [&](auto W) {
+            ppr_setup_kernel<decltype(W)::value><<<vgrid, kBlock, 0, stream>>>(n, k, d_V, ldv, v_vec, mask.get(), vw,
+                                                                               bufs[0], ws.state, ws.part);
+            ppr_start_kernel<<<1, kBlock, 0, stream>>>(ws.part, vgrid, k, ws.state);
+            return hipGetLastError();
+        }) == hipSuccess;
     }
-    if (!ok) {
-        (void)hipGetLastError();
-        return fail(SpMVError::KERNEL_LAUNCH);
-    }
+    if (!ws.read_back(ok, stream, kHeaderBytes)) return fail(SpMVError::KERNEL_LAUNCH);
     if (pinned[0].bad) return fail(SpMVError::INVALID_ARGUMENT);
 
     float elapsed_ms = 0.0f;
@@ -636,31 +616,30 @@ int personalized(const CSRMatrix* adj, const float* d_V, int ldv, float* d_R, in
         ok = step(lanes, adj, bufs[iter & 1], bufs[(iter + 1) & 1], vw, mask.get(), cfg.damping_factor, k, ws.state,
                   ws.part, row_grid, stream) == hipSuccess;
         if (ok) {
-            if (w == 4) ppr_commit_kernel<4><<<1, kBlock, 0, stream>>>(ws.part, row_grid, 2LL * row_grid, k, iter, cfg.tolerance, ws.state);
-            else ppr_commit_kernel<8><<<1, kBlock, 0, stream>>>(ws.part, row_grid, 2LL * row_grid, k, iter, cfg.tolerance, ws.state);
             // the host needs the global flag alone per step: the header in front of the column states
-            ok = hipGetLastError() == hipSuccess
-              && hipMemcpyAsync(&pinned[iter & 1], ws.state, kHeaderBytes, hipMemcpyDeviceToHost, stream) == hipSuccess
-              && hipEventRecord(ws.seen[iter & 1], stream) == hipSuccess;
+            ok = with_window(w, [&](auto W) {
+                ppr_commit_kernel<decltype(W)::value><<<1, kBlock, 0, stream>>>(ws.part, row_grid, 2LL * row_grid, k,
+                                                                               iter, cfg.tolerance, ws.state);
+                return hipGetLastError();
+            }) == hipSuccess && ws.publish(iter, kHeaderBytes, stream);
         }
         if (ok && iter >= 1) {
-            ok = hipEventSynchronize(ws.seen[(iter - 1) & 1]) == hipSuccess;
-            if (ok && pinned[(iter - 1) & 1].done) break;
+            const PprState* seen = ws.wait_previous(iter);
+            ok = seen != nullptr;
+            if (ok && seen->done) break;
         }
     }
     if (ok && run_loop) ok = hipEventRecord(ev.stop, stream) == hipSuccess;
     if (ok) {
         // every column from the rank array it was last committed to, divided by its sum, into the caller's R
-        if (w == 4) {
-            ppr_sum_kernel<4><<<nblocks, kBlock, 0, stream>>>(n, k, bufs[0], bufs[1], ws.state, ws.part);
-            ppr_scale_kernel<4><<<nblocks, kBlock, 0, stream>>>(n, k, bufs[0], bufs[1], ws.state, ws.part, nblocks, d_R, ldr);
-        } else {
-            ppr_sum_kernel<8><<<nblocks, kBlock, 0, stream>>>(n, k, bufs[0], bufs[1], ws.state, ws.part);
-            ppr_scale_kernel<8><<<nblocks, kBlock, 0, stream>>>(n, k, bufs[0], bufs[1], ws.state, ws.part, nblocks, d_R, ldr);
-        }
-        ok = hipGetLastError() == hipSuccess
-          && hipMemcpyAsync(&pinned[0], ws.state, sizeof(PprState), hipMemcpyDeviceToHost, stream) == hipSuccess
-          && hipStreamSynchronize(stream) == hipSuccess;
+        const hipError_t e = with_window(w, [&](auto WC) {
+            constexpr int W = decltype(WC)::value;
+            ppr_sum_kernel<W><<<nblocks, kBlock, 0, stream>>>(n, k, bufs[0], bufs[1], ws.state, ws.part);
+            ppr_scale_kernel<W><<<nblocks, kBlock, 0, stream>>>(n, k, bufs[0], bufs[1], ws.state, ws.part, nblocks, d_R,
+                                                                ldr);
+            return hipGetLastError();
+        });
+        ok = ws.read_back(e == hipSuccess, stream);
         float ms = 0.0f;
         if (ok && run_loop && hipEventElapsedTime(&ms, ev.start, ev.stop) == hipSuccess) elapsed_ms = ms;
     }

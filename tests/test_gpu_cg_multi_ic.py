@@ -135,8 +135,8 @@ def columns(n, k, seed=7, first=None):
 # ------------------------------------------------------------------------------------------ 1. the IC matrices
 @pytest.mark.parametrize("name", list(MATRICES))
 def test_column_parity_on_the_ic_matrices(gpu, name):
-    """cgm_ic_update_kernel / cgm_rz_kernel / cgm_ic_direction_kernel<4 and 8> and the k-wide triangular solves on the
-    windowed workspace with one, two and four windows; F = ic0_csr over A's structure."""
+    """cgm_update_kernel<W, true> / cgm_rz_kernel<W> / cgm_direction_kernel<W, true> (W = 4 and 8) and the k-wide
+    triangular solves on the windowed workspace with one, two and four windows; F = ic0_csr over A's structure."""
     n, rp, ci, va = MATRICES[name]()
     dev = Device(gpu, n, rp, ci, va)
     try:

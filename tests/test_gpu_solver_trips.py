@@ -94,9 +94,10 @@ def assert_two_steps(dev, system, variant, what, engine=0):
 @pytest.mark.parametrize("variant", ["none", "jacobi", "ic"])
 @pytest.mark.parametrize("n,L", TRIP_CASES, ids=ids(TRIP_CASES))
 def test_cg_every_trip(gpu, n, L, variant):
-    """cg_init_kernel<1>, cg_spmv_dot<1>, cg_update_kernel, cg_direction_kernel and cg_diag_kernel below, at and past
-    V, 2 V and R_1; with "ic" the same bits through cg_ic_update_kernel, cg_rz_kernel, cg_ic_direction_kernel,
-    cg_ic_diag_kernel and sptrsv_kernel on the one wide level of the diagonal factor.
+    """cg_init_kernel<1>, cg_spmv_dot<1>, cg_update_kernel<false>, cg_direction_kernel<false> and diag_kernel<POSITIVE>
+    below, at and past V, 2 V and R_1; with "ic" the same bits through cg_update_kernel<true>, cg_rz_kernel,
+    cg_direction_kernel<true>, diag_kernel<POSITIVE_FINITE> and sptrsv_kernel on the one wide level of the diagonal
+    factor.
     From n = 2 V + 3 on both grids sit at their caps and the solve's partial-sum array is 10 240 doubles, a whole number
     of pages: cg_start_kernel once read the double past its end there (the unused neighbour of the last b.b partial),
     which faulted when the next page was not mapped."""
@@ -111,7 +112,7 @@ def test_cg_every_trip(gpu, n, L, variant):
 @pytest.mark.parametrize("n,L", TRIP_CASES, ids=ids(TRIP_CASES))
 def test_bicgstab_every_trip(gpu, n, L, variant):
     """bicg_init_kernel<1>, both bicg_spmv_dot<1> calls, bicg_s_kernel, bicg_update_kernel, bicg_direction_kernel and
-    bicg_diag_kernel at the same sizes; "lu" is L = I, U = diag(A): JACOBI's bits through the stored p^ / s^."""
+    diag_kernel<NONZERO_FINITE> at the same sizes; "lu" is L = I, U = diag(A): JACOBI's bits through the stored p^ / s^."""
     system, dev = open_system(gpu, "bicgstab", n, L, variant)
     try:
         assert_two_steps(dev, system, variant, ("bicgstab", n, L))
