@@ -182,6 +182,31 @@ class GMRESResult(Structure):
     NONE, SINGULAR, NOT_FINITE = GMRES_NO_BREAKDOWN, GMRES_SINGULAR, GMRES_NOT_FINITE
 
 
+class EigsConfig(Structure):
+    """include/spmv/eigs.h EigsConfig (24 bytes): num_values 1..32; which 0 LARGEST / 1 SMALLEST (algebraic); basis 0
+    (= min(max(2 num_values, 20), 64)) or in (num_values, 64]; engine as CGConfig"""
+    _fields_ = [("num_values", c_int32), ("which", c_int32), ("basis", c_int32), ("tolerance", c_float),
+                ("max_iterations", c_int32), ("engine", c_int32)]
+    LARGEST, SMALLEST = 0, 1
+
+    def __init__(self, num_values=1, which=0, basis=0, tolerance=1e-5, max_iterations=1000, engine=-1):
+        super().__init__(num_values, which, basis, tolerance, max_iterations, engine)
+
+
+# EigsResult.breakdown codes (include/spmv/eigs.h EigsResult::Breakdown)
+EIGS_NO_BREAKDOWN, EIGS_INVARIANT_SUBSPACE, EIGS_NOT_FINITE = 0, 1, 2
+# the default start vector of eigs_sym: synth.vector(EIGS_START_SEED, EIGS_START_TAG, n)
+EIGS_START_SEED, EIGS_START_TAG = 0x45494753, 0
+
+
+class EigsResult(Structure):
+    """include/spmv/eigs.h EigsResult (28 bytes); converged counts the returned pairs whose recomputed residual passes;
+    breakdown is one of NONE, INVARIANT_SUBSPACE, NOT_FINITE"""
+    _fields_ = [("error_code", c_int32), ("iterations", c_int32), ("restarts", c_int32), ("converged", c_int32),
+                ("breakdown", c_int32), ("max_residual", c_float), ("elapsed_ms", c_float)]
+    NONE, INVARIANT_SUBSPACE, NOT_FINITE = EIGS_NO_BREAKDOWN, EIGS_INVARIANT_SUBSPACE, EIGS_NOT_FINITE
+
+
 class SpTRSVConfig(Structure):
     """include/spmv/sptrsv.h SpTRSVConfig (16 bytes): uplo 0 LOWER / 1 UPPER; diag 0 NON_UNIT / 1 UNIT; ordered 1 = one
     lane per row in the CPU's summation order"""
@@ -337,6 +362,9 @@ _SIGNATURES = {
                                    POINTER(GMRESResult)]),
     "spmv_c_gmres_solve_lu": (c_int, [POINTER(CSRMatrix), POINTER(CSRMatrix), c_void_p, c_void_p,
                                       POINTER(GMRESConfig), POINTER(GMRESResult)]),
+    "spmv_c_eigs_sym": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                POINTER(EigsConfig), POINTER(EigsResult)]),
+    "spmv_c_sym_eig_small": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_int]),
     "spmv_c_ilu0_csr": (c_int, [POINTER(CSRMatrix), c_void_p, POINTER(ILU0Result)]),
     "spmv_c_ilu0_csr_async": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p]),
     "spmv_c_ilu0_cpu_csr": (c_int, [POINTER(CSRMatrix), c_void_p, POINTER(c_int32)]),
@@ -1007,6 +1035,29 @@ def gmres_solve_lu(A, LU, d_b, d_x, config=None) -> GMRESResult:
     lib().spmv_c_gmres_solve_lu(A, LU, _dev(d_b), _dev(d_x), byref(config) if config is not None else None,
                                 byref(out))
     return out
+
+
+def eigs_sym(A, d_values, d_vectors, ldv=None, d_residuals=None, d_v0=None, config=None) -> EigsResult:
+    """config.num_values eigenpairs at one end of the spectrum of the symmetric device matrix A by thick-restart
+    Lanczos (include/spmv/eigs.h eigs_sym): d_values holds num_values floats, vector i is num_rows floats at
+    d_vectors + i * ldv (ldv None = num_rows), d_residuals (optional) num_values floats, d_v0 (optional) the start
+    vector; all device pointers or CudaBuffers."""
+    out = EigsResult()
+    lib().spmv_c_eigs_sym(A, _dev(d_values), _dev(d_vectors), A.num_rows if ldv is None else int(ldv),
+                          _dev(d_residuals), _dev(d_v0), byref(config) if config is not None else None, byref(out))
+    return out
+
+
+def sym_eig_small(T, on_device=False):
+    """Eigen-decomposition of the dense symmetric fp64 matrix T (order <= 64) by the fixed Jacobi rule of
+    include/spmv/eigs.h: (error code, values ascending, vectors with eigenvector i in ROW i).  on_device runs the
+    one-workgroup device kernel; both forms give the same bits."""
+    T = np.ascontiguousarray(T, np.float64)
+    n = T.shape[0]
+    values = np.zeros(n, np.float64)
+    vectors = np.zeros((n, n), np.float64)
+    status = lib().spmv_c_sym_eig_small(n, _np_ptr(T), n, _np_ptr(values), _np_ptr(vectors), 1 if on_device else 0)
+    return status, values, vectors
 
 
 def ilu0_csr(A, d_lu_values) -> ILU0Result:

@@ -7,6 +7,7 @@
 #include "spmv/bandwidth.h"
 #include "spmv/bicgstab.h"
 #include "spmv/gmres.h"
+#include "spmv/eigs.h"
 #include "spmv/cg.h"
 #include "spmv/pagerank.h"
 #include "spmv/sptrsv.h"
@@ -70,6 +71,19 @@ static_assert(offsetof(spmv_c_gmres_result, iterations) == offsetof(GMRESResult,
               offsetof(spmv_c_gmres_result, converged) == offsetof(GMRESResult, converged) &&
               offsetof(spmv_c_gmres_result, breakdown) == offsetof(GMRESResult, breakdown) &&
               offsetof(spmv_c_gmres_result, elapsed_ms) == offsetof(GMRESResult, elapsed_ms), "GMRESResult layout");
+static_assert(sizeof(spmv_c_eigs_config) == sizeof(EigsConfig) && sizeof(EigsConfig) == 24, "EigsConfig layout");
+static_assert(offsetof(spmv_c_eigs_config, which) == offsetof(EigsConfig, which) &&
+              offsetof(spmv_c_eigs_config, basis) == offsetof(EigsConfig, basis) &&
+              offsetof(spmv_c_eigs_config, tolerance) == offsetof(EigsConfig, tolerance) &&
+              offsetof(spmv_c_eigs_config, max_iterations) == offsetof(EigsConfig, max_iterations) &&
+              offsetof(spmv_c_eigs_config, engine) == offsetof(EigsConfig, engine), "EigsConfig layout");
+static_assert(sizeof(spmv_c_eigs_result) == sizeof(EigsResult) && sizeof(EigsResult) == 28, "EigsResult layout");
+static_assert(offsetof(spmv_c_eigs_result, iterations) == offsetof(EigsResult, iterations) &&
+              offsetof(spmv_c_eigs_result, restarts) == offsetof(EigsResult, restarts) &&
+              offsetof(spmv_c_eigs_result, converged) == offsetof(EigsResult, converged) &&
+              offsetof(spmv_c_eigs_result, breakdown) == offsetof(EigsResult, breakdown) &&
+              offsetof(spmv_c_eigs_result, max_residual) == offsetof(EigsResult, max_residual) &&
+              offsetof(spmv_c_eigs_result, elapsed_ms) == offsetof(EigsResult, elapsed_ms), "EigsResult layout");
 static_assert(sizeof(spmv_c_bicgstab_config) == sizeof(BiCGStabConfig) && sizeof(BiCGStabConfig) == 16,
               "BiCGStabConfig layout");
 static_assert(offsetof(spmv_c_bicgstab_config, max_iterations) == offsetof(BiCGStabConfig, max_iterations) &&
@@ -568,6 +582,18 @@ int spmv_c_gmres_solve_lu(const spmv_c_csr* A, const spmv_c_csr* LU, const float
     const GMRESResult r = gmres_solve_lu(cxx(A), cxx(LU), d_b, d_x, reinterpret_cast<const GMRESConfig*>(config));
     if (out) std::memcpy(out, &r, sizeof(r));
     return r.error_code;
+}
+
+int spmv_c_eigs_sym(const spmv_c_csr* A, float* d_values, float* d_vectors, int64_t ldv, float* d_residuals,
+                    const float* d_v0, const spmv_c_eigs_config* config, spmv_c_eigs_result* out) {
+    const EigsResult r = eigs_sym(cxx(A), d_values, d_vectors, ldv, d_residuals, d_v0,
+                                  reinterpret_cast<const EigsConfig*>(config));
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
+}
+
+int spmv_c_sym_eig_small(int n, const double* T, int ld, double* values, double* vectors, int on_device) {
+    return sym_eig_small(n, T, ld, values, vectors, on_device);
 }
 
 int spmv_c_ilu0_csr(const spmv_c_csr* A, float* d_lu_values, spmv_c_ilu0_result* out) {

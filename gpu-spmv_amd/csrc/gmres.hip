@@ -30,12 +30,12 @@
 // diag_kernel); what is here is this solver's checks, its workspace layout, its launches, the cycle bookkeeping
 // and its result.
 //
-// The three orthogonalisation kernels walk the basis in compile-time groups of kGroup vectors with kGroup fp64
-// accumulators in registers; a thread's four elements of w stay in registers across the groups of an update.  No
-// per-thread array is indexed at run time: the coefficients live in LDS.
+// The three orthogonalisation kernels are made of basis_ops.h's functions (shared with eigs.hip): they walk the basis
+// in compile-time groups of kGroup vectors with kGroup fp64 accumulators in registers.
 #include "internal.h"
 #include "device_common.h"
 #include "solver_common.h"
+#include "basis_ops.h"
 #include "tiled.h"
 #include "spmv/gmres.h"
 #include "spmv/sptrsv.h"
@@ -52,11 +52,9 @@ namespace {
 
 using namespace dev;
 using namespace solver;
+using namespace basis;
 
 constexpr int kMaxRestart = 64;
-constexpr int kGroup = 8;                  // basis vectors per compile-time group
-constexpr int kChunk = 4 * kBlock;         // elements of w a workgroup holds in registers at a time
-constexpr int kOrthoBlocks = 256;          // workgroups of the basis kernels: every one folds (j+1) x this many partials
 
 // Lives in device memory and is mirrored to the host after every step.
 struct GmresState {
@@ -91,88 +89,6 @@ constexpr size_t kSmallDoubles = kMaxRestart * kMaxRestart + (kMaxRestart + 8) +
 
 __device__ __forceinline__ bool stepping(const GmresState* st) { return st->open && !st->done; }
 __device__ __forceinline__ bool closing(const GmresState* st) { return !st->open && !st->done; }
-
-// a thread's four consecutive elements of one of the solver's own vectors (16-byte aligned, padded to the leading
-// dimension); elements at or past n read as 0 whatever the padding holds
-__device__ __forceinline__ f32x4 load4_masked(const float* v, long long e, long long n) {
-    f32x4 out = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (e < n) {
-        const f32x4 raw = *reinterpret_cast<const f32x4*>(v + e);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) out[q] = e + q < n ? raw[q] : 0.0f;
-    }
-    return out;
-}
-
-__device__ __forceinline__ void store4(float* v, long long e, long long n, f32x4 val) {
-    if (e < n) *reinterpret_cast<f32x4*>(v + e) = val;      // e + 3 < the leading dimension
-}
-
-__device__ __forceinline__ double dot4(f32x4 a, f32x4 b) {
-    return (prod64(a[0], b[0]) + prod64(a[1], b[1])) + (prod64(a[2], b[2]) + prod64(a[3], b[3]));
-}
-
-// s_out[i] = fp32(sum over p < P of part[i * P + p]) for i < count, in a fixed order: wave (i mod 4) sums a fixed
-// strided subset per lane, then a butterfly.
-__device__ __forceinline__ void fold_columns(const double* __restrict__ part, int P, int count,
-                                             float* __restrict__ s_out) {
-    const int lane = threadIdx.x & 63;
-    for (int i = threadIdx.x >> 6; i < count; i += kBlock / 64) {
-        double a = 0.0;
-        for (int p = lane; p < P; p += 64) a += part[static_cast<long long>(i) * P + p];
-        for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off, 64);
-        if (lane == 0) s_out[i] = static_cast<float>(a);
-    }
-    __syncthreads();
-}
-
-// part[i * gridDim.x + block] = this workgroup's share of v_i.w for i < nv
-__device__ __forceinline__ void multidot_pass(long long n, long long ld, int nv, const float* __restrict__ V,
-                                              const float* w, double* __restrict__ part) {
-    for (int first = 0; first < nv; first += kGroup) {
-        const int count = min(kGroup, nv - first);
-        double acc[kGroup];
-#pragma unroll
-        for (int i = 0; i < kGroup; ++i) acc[i] = 0.0;
-        for (long long base = static_cast<long long>(blockIdx.x) * kChunk; base < n;
-             base += static_cast<long long>(gridDim.x) * kChunk) {
-            const long long e = base + 4 * threadIdx.x;
-            const f32x4 w4 = load4_masked(w, e, n);
-#pragma unroll
-            for (int i = 0; i < kGroup; ++i) {
-                if (i < count) acc[i] += dot4(w4, load4_masked(V + (first + i) * ld, e, n));
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < kGroup; i += 2) {
-            if (i < count) {                        // uniform over the workgroup
-                block_sum2(acc[i], acc[i + 1]);
-                if (threadIdx.x == 0) {
-                    part[static_cast<long long>(first + i) * gridDim.x + blockIdx.x] = acc[i];
-                    if (i + 1 < count) part[static_cast<long long>(first + i + 1) * gridDim.x + blockIdx.x] = acc[i + 1];
-                }
-            }
-        }
-    }
-}
-
-// w4 <- fmaf(-s_h[i], v_i, w4) for i < nv ascending, on this thread's four elements
-__device__ __forceinline__ f32x4 subtract_all(long long n, long long ld, int nv, const float* __restrict__ V,
-                                              const float* s_h, long long e, f32x4 w4) {
-    for (int first = 0; first < nv; first += kGroup) {
-        const int count = min(kGroup, nv - first);
-#pragma unroll
-        for (int i = 0; i < kGroup; ++i) {
-            if (i < count) {
-                const float h = s_h[first + i];
-                const f32x4 v4 = load4_masked(V + (first + i) * ld, e, n);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) w4[q] = __builtin_fmaf(-h, v4[q], w4[q]);
-            }
-        }
-    }
-    return w4;
-}
 
 __global__ __launch_bounds__(kBlock)
 void gmres_multidot(long long n, long long ld, int j, const float* __restrict__ V, const float* __restrict__ w,

@@ -1,4 +1,5 @@
-// solver_common.h — what the device-resident iterative solvers (cg.hip, cg_multi.hip, bicgstab.hip, gmres.hip) share.
+// solver_common.h — what the device-resident iterative solvers (cg.hip, cg_multi.hip, bicgstab.hip, gmres.hip,
+// eigs.hip) share.
 // Device side: the deterministic fp64 dot-product partials and their fixed-order fold, and diag_kernel, the one
 // setup kernel that sums every row's diagonal.  Host side: the grid sizes, the LANES dispatch of the vector-CSR
 // kernels, the argument predicates (device_arrays, ranges_overlap), and the parts every solve() is built from:

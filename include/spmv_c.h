@@ -357,6 +357,41 @@ int spmv_c_gmres_solve(const spmv_c_csr* A, const float* d_b, float* d_x, const 
 int spmv_c_gmres_solve_lu(const spmv_c_csr* A, const spmv_c_csr* LU, const float* d_b, float* d_x,
                           const spmv_c_gmres_config* config, spmv_c_gmres_result* out);
 
+/* ---- extreme eigenpairs of a symmetric matrix (extension; spmv::eigs_sym, include/spmv/eigs.h) ---- */
+/* 24 bytes; num_values in [1, 32]; which 0 LARGEST / 1 SMALLEST (algebraic); basis 0 (default) or in (num_values, 64] */
+typedef struct spmv_c_eigs_config {
+    int32_t num_values;
+    int32_t which;
+    int32_t basis;
+    float   tolerance;
+    int32_t max_iterations;
+    int32_t engine;
+} spmv_c_eigs_config;
+
+/* breakdown: 0 none, 1 INVARIANT_SUBSPACE (fewer than num_values pairs exist in the start vector's Krylov space),
+ * 2 NOT_FINITE; converged and max_residual come from A y - theta y recomputed with the returned pairs (28 bytes) */
+typedef struct spmv_c_eigs_result {
+    int32_t error_code;
+    int32_t iterations;
+    int32_t restarts;
+    int32_t converged;
+    int32_t breakdown;
+    float   max_residual;
+    float   elapsed_ms;
+} spmv_c_eigs_result;
+
+/* num_values eigenpairs at one end of the spectrum of the symmetric device matrix A by thick-restart Lanczos:
+ * d_values num_values floats, vector i num_rows floats at d_vectors + i * ldv, d_residuals (may be NULL) num_values
+ * floats, d_v0 (may be NULL) the start vector.  config NULL = defaults (1, LARGEST, 0, 1e-5, 1000, auto).  Argument
+ * checks and numerics as eigs_sym in include/spmv/eigs.h.  The return value equals out->error_code (out may be NULL). */
+int spmv_c_eigs_sym(const spmv_c_csr* A, float* d_values, float* d_vectors, int64_t ldv, float* d_residuals,
+                    const float* d_v0, const spmv_c_eigs_config* config, spmv_c_eigs_result* out);
+
+/* eigen-decomposition of the dense symmetric fp64 matrix T (host, order n <= 64, leading dimension ld) by the fixed
+ * Jacobi rule of include/spmv/eigs.h: values ascending, eigenvector i at vectors + i * ld (host).  on_device != 0 runs
+ * the one-workgroup device kernel instead of the host twin; both give the same bits.  Returns an SpMVError code. */
+int spmv_c_sym_eig_small(int n, const double* T, int ld, double* values, double* vectors, int on_device);
+
 /* ---- sparse triangular solve with level scheduling (extension; include/spmv/sptrsv.h) ---- */
 /* uplo: 0 LOWER, 1 UPPER; diag: 0 NON_UNIT, 1 UNIT; ordered: 1 = one lane per row in the CPU's summation order
  * (bit-identical to spmv_c_sptrsv_cpu_csr), 0 = 1-64 lanes per row; reserved: 0 (16 bytes) */
