@@ -238,6 +238,22 @@ class IC0Result(Structure):
                 ("elapsed_ms", c_float)]
 
 
+class ColorConfig(Structure):
+    """include/spmv/reorder.h ColorConfig (16 bytes): the seed of the vertex priorities; symmetric_pattern 1 = only A's
+    rows are walked; lanes_per_row 0 = from the mean degree, else 1, 2, 4, ... 64"""
+    _fields_ = [("seed", ctypes.c_uint32), ("symmetric_pattern", c_int32), ("lanes_per_row", c_int32),
+                ("reserved", c_int32)]
+
+    def __init__(self, seed=0, symmetric_pattern=0, lanes_per_row=0, reserved=0):
+        super().__init__(seed, symmetric_pattern, lanes_per_row, reserved)
+
+
+class ColorResult(Structure):
+    """include/spmv/reorder.h ColorResult (20 bytes)"""
+    _fields_ = [("error_code", c_int32), ("num_colors", c_int32), ("rounds", c_int32), ("launches", c_int32),
+                ("elapsed_ms", c_float)]
+
+
 class SpGEMMResult(Structure):
     """include/spmv/spgemm.h SpGEMMResult (104 bytes); symbolic_rows / numeric_rows count the rows per accumulator
     class of each pass, [0] the rows without products"""
@@ -405,6 +421,16 @@ _SIGNATURES = {
                                          c_int, POINTER(CGConfig), POINTER(CGResult)]),
     "spmv_c_sptrsv_levels": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, POINTER(c_int32),
                                      POINTER(c_int32)]),
+    "spmv_c_csr_color": (c_int, [POINTER(CSRMatrix), c_void_p, POINTER(ColorConfig), POINTER(ColorResult)]),
+    "spmv_c_csr_color_cpu": (c_int, [POINTER(CSRMatrix), c_void_p, POINTER(c_int32), POINTER(c_int32),
+                                     POINTER(ColorConfig)]),
+    "spmv_c_color_ordering": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "spmv_c_csr_permute_gpu": (c_int, [POINTER(CSRMatrix), POINTER(CSRMatrix), c_void_p, c_void_p]),
+    "spmv_c_csr_permute_cpu": (c_int, [POINTER(CSRMatrix), POINTER(CSRMatrix), c_void_p, c_void_p]),
+    "spmv_c_permute_gather": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int]),
+    "spmv_c_permute_gather_async": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "spmv_c_multicolor_reorder": (c_int, [POINTER(CSRMatrix), POINTER(CSRMatrix), c_void_p, c_void_p,
+                                          POINTER(ColorConfig), POINTER(ColorResult)]),
     "spmv_c_compute_bandwidth_csr": (c_int, [POINTER(CSRMatrix), c_float, POINTER(BandwidthMetrics)]),
     "spmv_c_compute_bandwidth_csr_multi": (c_int, [POINTER(CSRMatrix), c_int, c_float, POINTER(BandwidthMetrics)]),
     "spmv_c_compute_bandwidth_ell": (c_int, [POINTER(ELLMatrix), c_float, POINTER(BandwidthMetrics)]),
@@ -1292,6 +1318,75 @@ def sptrsv_levels(num_rows, row_ptrs, col_indices, uplo=0):
     if status != 0:
         return status, None, None, 0, -1
     return status, level_ptr[:levels.value + 1].copy(), order, levels.value, missing.value
+
+
+# ---- multicolour reordering (include/spmv/reorder.h) ----------------------------------
+def csr_color(A, d_colors, config=None) -> ColorResult:
+    """Colours the graph of the square device matrix A into d_colors (num_rows int32 on the device): the same ints as
+    csr_color_cpu (include/spmv/reorder.h csr_color)."""
+    out = ColorResult()
+    lib().spmv_c_csr_color(A, _dev(d_colors), byref(config) if config is not None else None, byref(out))
+    return out
+
+
+def csr_color_cpu(A, config=None):
+    """The colouring on A's host arrays, the definition (reorder.h csr_color_cpu): (status, colors, num_colors, rounds)
+    with rounds the synchronous round count; colors is None when the call fails."""
+    n = max(A.contents.num_rows, 0) if A else 0
+    colors = np.full(n, -7, np.int32)
+    num_colors, rounds = c_int32(-7), c_int32(-7)
+    status = lib().spmv_c_csr_color_cpu(A, _np_ptr(colors), byref(num_colors), byref(rounds),
+                                        byref(config) if config is not None else None)
+    if status != 0:
+        return status, None, 0, 0
+    return status, colors, num_colors.value, rounds.value
+
+
+def color_ordering(n, d_colors, num_colors, d_perm, d_inverse):
+    """The vertices sorted by (colour, index) on the device (reorder.h color_ordering): d_perm[new] = old,
+    d_inverse[old] = new; returns (status, color_ptr) with color_ptr the num_colors + 1 host offsets."""
+    color_ptr = np.full(max(int(num_colors), 0) + 1, -7, np.int32)
+    status = lib().spmv_c_color_ordering(int(n), _dev(d_colors), int(num_colors), _dev(d_perm), _dev(d_inverse),
+                                         _np_ptr(color_ptr))
+    return status, color_ptr
+
+
+def csr_permute_gpu(B, A, d_row_perm=None, d_col_inverse=None) -> int:
+    """B = P A Q^T on the device with sorted rows (reorder.h csr_permute_gpu): row i of B is row d_row_perm[i] of A,
+    column j renamed d_col_inverse[j]; None is the identity.  csr_from_gpu(B) fills B's host arrays."""
+    return lib().spmv_c_csr_permute_gpu(B, A, _dev(d_row_perm), _dev(d_col_inverse))
+
+
+def csr_permute_cpu(B, A, row_perm=None, col_inverse=None) -> int:
+    """The same on host arrays, the definition of the order (reorder.h csr_permute_cpu); csr_host_arrays(B) reads the
+    result."""
+    rows = None if row_perm is None else np.ascontiguousarray(row_perm, dtype=np.int32)
+    cols = None if col_inverse is None else np.ascontiguousarray(col_inverse, dtype=np.int32)
+    return lib().spmv_c_csr_permute_cpu(B, A, None if rows is None else _np_ptr(rows),
+                                        None if cols is None else _np_ptr(cols))
+
+
+def permute_gather(d_out, d_in, d_index, n, k=1, ldo=None, ldi=None) -> int:
+    """d_out[i, :k] = d_in[d_index[i], :k] for the rows of an n x k row-major array (reorder.h permute_gather)."""
+    k = int(k)
+    return lib().spmv_c_permute_gather(_dev(d_out), k if ldo is None else int(ldo), _dev(d_in),
+                                       k if ldi is None else int(ldi), _dev(d_index), int(n), k)
+
+
+def permute_gather_async(d_out, d_in, d_index, n, k=1, ldo=None, ldi=None, stream=None) -> int:
+    k = int(k)
+    return lib().spmv_c_permute_gather_async(_dev(d_out), k if ldo is None else int(ldo), _dev(d_in),
+                                             k if ldi is None else int(ldi), _dev(d_index), int(n), k,
+                                             c_void_p(stream))
+
+
+def multicolor_reorder(B, A, d_perm, d_inverse, config=None) -> ColorResult:
+    """Colours A, orders the vertices into d_perm / d_inverse (num_rows int32 each on the device) and forms
+    B = P A P^T (reorder.h multicolor_reorder)."""
+    out = ColorResult()
+    lib().spmv_c_multicolor_reorder(B, A, _dev(d_perm), _dev(d_inverse),
+                                    byref(config) if config is not None else None, byref(out))
+    return out
 
 
 def spmv_auto_config(A) -> SpMVConfig:

@@ -15,6 +15,7 @@
 #include "spmv/ilu0.h"
 #include "spmv/spgemm.h"
 #include "spmv/amg.h"
+#include "spmv/reorder.h"
 #include "spmv_c.h"
 
 #include <cstddef>
@@ -121,6 +122,16 @@ static_assert(offsetof(spmv_c_sptrsv_result, num_levels) == offsetof(SpTRSVResul
               offsetof(spmv_c_sptrsv_result, lanes_per_row) == offsetof(SpTRSVResult, lanes_per_row) &&
               offsetof(spmv_c_sptrsv_result, analysis_ms) == offsetof(SpTRSVResult, analysis_ms) &&
               offsetof(spmv_c_sptrsv_result, elapsed_ms) == offsetof(SpTRSVResult, elapsed_ms), "SpTRSVResult layout");
+
+static_assert(sizeof(spmv_c_color_config) == sizeof(ColorConfig) && sizeof(ColorConfig) == 16, "ColorConfig layout");
+static_assert(offsetof(spmv_c_color_config, symmetric_pattern) == offsetof(ColorConfig, symmetric_pattern) &&
+              offsetof(spmv_c_color_config, lanes_per_row) == offsetof(ColorConfig, lanes_per_row) &&
+              offsetof(spmv_c_color_config, reserved) == offsetof(ColorConfig, reserved), "ColorConfig layout");
+static_assert(sizeof(spmv_c_color_result) == sizeof(ColorResult) && sizeof(ColorResult) == 20, "ColorResult layout");
+static_assert(offsetof(spmv_c_color_result, num_colors) == offsetof(ColorResult, num_colors) &&
+              offsetof(spmv_c_color_result, rounds) == offsetof(ColorResult, rounds) &&
+              offsetof(spmv_c_color_result, launches) == offsetof(ColorResult, launches) &&
+              offsetof(spmv_c_color_result, elapsed_ms) == offsetof(ColorResult, elapsed_ms), "ColorResult layout");
 
 static_assert(sizeof(spmv_c_spgemm_result) == sizeof(SpGEMMResult) && sizeof(SpGEMMResult) == 104, "SpGEMMResult layout");
 static_assert(offsetof(spmv_c_spgemm_result, nnz) == offsetof(SpGEMMResult, nnz) &&
@@ -727,6 +738,50 @@ int spmv_c_sptrsv_cpu_csr_multi(const spmv_c_csr* A, const float* B, int ldb, fl
 int spmv_c_sptrsv_levels(int num_rows,const int32_t* row_ptrs, const int32_t* col_indices, int uplo,
                          int32_t* level_ptr, int32_t* order, int32_t* num_levels, int32_t* first_missing_diagonal) {
     return sptrsv_levels(num_rows, row_ptrs, col_indices, uplo, level_ptr, order, num_levels, first_missing_diagonal);
+}
+
+// ---- multicolour reordering ----
+int spmv_c_csr_color(const spmv_c_csr* A, int32_t* d_colors, const spmv_c_color_config* config,
+                     spmv_c_color_result* out) {
+    const ColorResult r = csr_color(cxx(A), d_colors, reinterpret_cast<const ColorConfig*>(config));
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
+}
+
+int spmv_c_csr_color_cpu(const spmv_c_csr* A, int32_t* colors, int32_t* num_colors, int32_t* rounds,
+                         const spmv_c_color_config* config) {
+    return csr_color_cpu(cxx(A), colors, num_colors, rounds, reinterpret_cast<const ColorConfig*>(config));
+}
+
+int spmv_c_color_ordering(int n, const int32_t* d_colors, int num_colors, int32_t* d_perm, int32_t* d_inverse,
+                          int32_t* color_ptr) {
+    return color_ordering(n, d_colors, num_colors, d_perm, d_inverse, color_ptr);
+}
+
+int spmv_c_csr_permute_gpu(spmv_c_csr* B, const spmv_c_csr* A, const int32_t* d_row_perm,
+                           const int32_t* d_col_inverse) {
+    return csr_permute_gpu(cxx(B), cxx(A), d_row_perm, d_col_inverse);
+}
+
+int spmv_c_csr_permute_cpu(spmv_c_csr* B, const spmv_c_csr* A, const int32_t* row_perm, const int32_t* col_inverse) {
+    return csr_permute_cpu(cxx(B), cxx(A), row_perm, col_inverse);
+}
+
+int spmv_c_permute_gather(float* d_out, int ldo, const float* d_in, int ldi, const int32_t* d_index, int n, int k) {
+    return permute_gather(d_out, ldo, d_in, ldi, d_index, n, k);
+}
+
+int spmv_c_permute_gather_async(float* d_out, int ldo, const float* d_in, int ldi, const int32_t* d_index, int n,
+                                int k, void* hip_stream) {
+    return permute_gather_async(d_out, ldo, d_in, ldi, d_index, n, k, as_stream(hip_stream));
+}
+
+int spmv_c_multicolor_reorder(spmv_c_csr* B, const spmv_c_csr* A, int32_t* d_perm, int32_t* d_inverse,
+                              const spmv_c_color_config* config, spmv_c_color_result* out) {
+    const ColorResult r = multicolor_reorder(cxx(B), cxx(A), d_perm, d_inverse,
+                                             reinterpret_cast<const ColorConfig*>(config));
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
 }
 
 // ---- bandwidth ----

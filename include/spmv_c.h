@@ -562,6 +562,54 @@ int spmv_c_amg_aggregate_cpu_csr(const spmv_c_csr* A, float strength, int32_t* a
 int spmv_c_cg_solve_amg(const spmv_c_csr* A, const spmv_c_amg* H, const float* d_b, float* d_x,
                         const spmv_c_cg_config* config, spmv_c_cg_result* out);
 
+/* ---- multicolour reordering (extension; include/spmv/reorder.h) ---- */
+/* seed of the vertex priorities; symmetric_pattern: 1 = only A's rows are walked (the caller's promise);
+ * lanes_per_row: 0 = from the mean degree, else 1, 2, 4, ... 64; reserved: 0 (16 bytes) */
+typedef struct spmv_c_color_config {
+    uint32_t seed;
+    int32_t  symmetric_pattern;
+    int32_t  lanes_per_row;
+    int32_t  reserved;
+} spmv_c_color_config;
+/* 20 bytes */
+typedef struct spmv_c_color_result {
+    int32_t error_code;
+    int32_t num_colors;
+    int32_t rounds;
+    int32_t launches;
+    float   elapsed_ms;
+} spmv_c_color_result;
+
+/* Colours the graph of the square device matrix A into d_colors (num_rows ints on the device): greedy first-fit in
+ * descending (fmix32(i ^ seed), i) priority, the same ints as spmv_c_csr_color_cpu.  config may be NULL (0, 0, 0, 0).
+ * Checks and algorithm as csr_color in include/spmv/reorder.h.  The return value equals out->error_code (out may be
+ * NULL). */
+int spmv_c_csr_color(const spmv_c_csr* A, int32_t* d_colors, const spmv_c_color_config* config,
+                     spmv_c_color_result* out);
+/* the definition on A's host arrays; *num_colors and *rounds (the synchronous round count) may be NULL */
+int spmv_c_csr_color_cpu(const spmv_c_csr* A, int32_t* colors, int32_t* num_colors, int32_t* rounds,
+                         const spmv_c_color_config* config);
+/* the vertices sorted by (colour, index) on the device: d_perm[new] = old, d_inverse[old] = new; color_ptr (host,
+ * num_colors + 1 ints) may be NULL */
+int spmv_c_color_ordering(int n, const int32_t* d_colors, int num_colors, int32_t* d_perm, int32_t* d_inverse,
+                          int32_t* color_ptr);
+/* B = P A Q^T on the device with sorted rows: row i of B is row d_row_perm[i] of A, column j renamed d_col_inverse[j];
+ * either array may be NULL (the identity).  B owns new device arrays afterwards (as spmv_c_csr_transpose_gpu leaves
+ * AT).  Bit for bit spmv_c_csr_permute_cpu's result.  Checks as csr_permute_gpu in include/spmv/reorder.h. */
+int spmv_c_csr_permute_gpu(spmv_c_csr* B, const spmv_c_csr* A, const int32_t* d_row_perm,
+                           const int32_t* d_col_inverse);
+/* the same on host arrays; B owns new host arrays */
+int spmv_c_csr_permute_cpu(spmv_c_csr* B, const spmv_c_csr* A, const int32_t* row_perm, const int32_t* col_inverse);
+/* d_out[i * ldo + j] = d_in[d_index[i] * ldi + j] for i < n, j < k (1..32), row-major with ldo, ldi >= k */
+int spmv_c_permute_gather(float* d_out, int ldo, const float* d_in, int ldi, const int32_t* d_index, int n, int k);
+/* the same enqueued on a caller stream without synchronisation */
+int spmv_c_permute_gather_async(float* d_out, int ldo, const float* d_in, int ldi, const int32_t* d_index, int n,
+                                int k, void* hip_stream);
+/* colouring, ordering and B = P A P^T in one call; d_perm and d_inverse: num_rows ints each on the device.  The return
+ * value equals out->error_code (out may be NULL). */
+int spmv_c_multicolor_reorder(spmv_c_csr* B, const spmv_c_csr* A, int32_t* d_perm, int32_t* d_inverse,
+                              const spmv_c_color_config* config, spmv_c_color_result* out);
+
 /* ---- bandwidth model: reference include/spmv/bandwidth.h:21-27 ---- */
 int spmv_c_compute_bandwidth_csr(const spmv_c_csr* A, float elapsed_ms, spmv_c_bandwidth* out);
 int spmv_c_compute_bandwidth_ell(const spmv_c_ell* A, float elapsed_ms, spmv_c_bandwidth* out);
