@@ -907,6 +907,20 @@ spmv_c_pr_shard* spmv_c_pr_shard_create_chunked(const spmv_c_csr* A_local, int b
         spmv_c_pr_shard_destroy(h);
         return nullptr;
     }
+    // The tiled engine's phase 2 reads the flags of a contiguous slice as bits (DanglingBits, pagerank_engine.h): derived
+    // here from the mask as it stands, and again by every spmv_c_pr_reset, for callers that fill the mask in between.
+    // (SPMV_DEBUG=dangling=bytes keeps the shard on the byte mask: the A/B switch of profiles/aligned_streams_traffic_ab.txt.)
+    if (sh.tiled && sh.local_rows > 0 && piece == 0x7fffffff && !detail::debug_is("dangling", "bytes")) {
+        hipStream_t s = detail::current_stream();
+        if (hipMalloc(reinterpret_cast<void**>(&sh.d_dangling_words),
+                      sizeof(unsigned int) * detail::pr_dangling_words(sh.local_rows)) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void**>(&sh.d_tile_dangling), sizeof(int) * static_cast<size_t>(sh.tiled->num_tiles)) != hipSuccess ||
+            detail::pr_dangling_bits(&sh, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+            (void)hipGetLastError();
+            spmv_c_pr_shard_destroy(h);
+            return nullptr;
+        }
+    }
     return h;
 }
 
@@ -918,6 +932,8 @@ void spmv_c_pr_shard_destroy(spmv_c_pr_shard* h) {
     }
     if (h->shard.d_state) (void)hipFree(h->shard.d_state);
     if (h->shard.d_block_partials) (void)hipFree(h->shard.d_block_partials);
+    if (h->shard.d_dangling_words) (void)hipFree(h->shard.d_dangling_words);
+    if (h->shard.d_tile_dangling) (void)hipFree(h->shard.d_tile_dangling);
     delete h;
 }
 
@@ -928,6 +944,7 @@ int spmv_c_pr_reset(spmv_c_pr_shard* h, float dangling_sum, void* hip_stream) {
     h->shard.expanded_strips = 0;          // a head start taken for a step that never ran is void
     h->shard.expanded_long = false;
     detail::pr_drop_pending(h->shard);     // ... and so is a commit that nobody asked to see
+    if (detail::pr_dangling_bits(&h->shard, as_stream(hip_stream)) != hipSuccess) return kLaunch;
     // pageable source: the copy is staged before the call returns
     return hipMemcpyAsync(h->shard.d_state, &fresh, sizeof(fresh), hipMemcpyHostToDevice,
                           as_stream(hip_stream)) == hipSuccess

@@ -190,6 +190,25 @@ void pr_mask_kernel(const float* __restrict__ col_sums, int n, unsigned char* __
     if ((threadIdx.x & 63) == 0 && local) atomicAdd(count, local);
 }
 
+// The mask bytes of local rows [0, rows) (mask already points at the shard's first node) as bits, and how many are set
+// in every tile of R rows.  One ballot per 64 rows; R is a multiple of 64, so a wavefront's rows lie in one tile.  The
+// counts are integer sums: their order does not matter.  tile_count is zeroed by the caller.
+__global__ __launch_bounds__(kBlock)
+void pr_dangling_bits_kernel(const unsigned char* __restrict__ mask, int rows, int R,
+                             unsigned int* __restrict__ words, int* __restrict__ tile_count) {
+    const long long padded = (static_cast<long long>(rows) + 63) / 64 * 64;
+    for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < padded;
+         i += static_cast<long long>(gridDim.x) * kBlock) {
+        const bool flag = i < rows && mask[i] != 0;
+        const unsigned long long set = __ballot(flag);
+        if ((threadIdx.x & 63) == 0) {
+            words[i >> 5] = static_cast<unsigned int>(set);
+            words[(i >> 5) + 1] = static_cast<unsigned int>(set >> 32);
+            if (set) atomicAdd(&tile_count[i / R], __popcll(set));
+        }
+    }
+}
+
 // ---- final renormalisation r /= sum(r) on the device: block partial sums in double, then every
 // block folds the partials in the same fixed order and scales its share (IEEE division) ----
 __global__ __launch_bounds__(kBlock)
@@ -323,7 +342,8 @@ hipError_t pr_step(const PrShard& sh, const float* r_old, float* r_new, float da
             const hipError_t e = tiled_pagerank_expand(*sh.tiled, done, sh.tiled->num_strips, !long_done, r_old, sh.d_state, rider, s);
             if (e != hipSuccess) return e;
         }
-        return tiled_pagerank_finish(*sh.tiled, sh.map, sh.n_global, r_old, r_new, sh.d_dangling,
+        const DanglingBits bits = sh.dangling_bits_ready ? DanglingBits{sh.d_dangling_words, sh.d_tile_dangling} : DanglingBits{};
+        return tiled_pagerank_finish(*sh.tiled, sh.map, sh.n_global, r_old, r_new, sh.d_dangling, bits,
                                      damping, sh.d_state, sh.d_block_partials, push, s);
     }
     switch (sh.lanes) {
@@ -396,6 +416,18 @@ hipError_t pr_commit_gathered(const PrShard& sh, const float* d_gathered, int wo
                               long long shard_len, float tolerance, hipStream_t s) {
     if (const hipError_t e = pr_flush(sh, s); e != hipSuccess) return e;
     pr_commit_gathered_kernel<<<1, 1, 0, s>>>(d_gathered, world, stride, shard_len, tolerance, sh.d_state);
+    return hipGetLastError();
+}
+
+hipError_t pr_dangling_bits(PrShard* sh, hipStream_t s) {
+    sh->dangling_bits_ready = false;
+    if (!sh->d_dangling_words || !sh->d_tile_dangling || !sh->tiled || sh->map.piece != 0x7fffffff || sh->local_rows <= 0) return hipSuccess;
+    const TiledPlan& plan = *sh->tiled;
+    const hipError_t e = hipMemsetAsync(sh->d_tile_dangling, 0, sizeof(int) * static_cast<size_t>(plan.num_tiles), s);
+    if (e != hipSuccess) return e;
+    pr_dangling_bits_kernel<<<grid_for(sh->local_rows, kBlock * 4), kBlock, 0, s>>>(
+        sh->d_dangling + sh->map.base, sh->local_rows, plan.tile_rows, sh->d_dangling_words, sh->d_tile_dangling);
+    sh->dangling_bits_ready = true;
     return hipGetLastError();
 }
 

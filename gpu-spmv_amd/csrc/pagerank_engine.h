@@ -5,6 +5,8 @@
 
 #include "internal.h"
 
+#include <algorithm>
+
 namespace spmv {
 namespace detail {
 
@@ -41,6 +43,17 @@ struct RowMap {
     }
 };
 
+// The dangling flags of a shard's rows as bits, for the tiled engine's phase 2 on one contiguous slice: bit i of the
+// array (word i / 32, bit i % 32) is the mask byte of LOCAL row i, so a tile's rows (R is a multiple of 64) start on a word
+// and a step reads 1.25 MB of flags for 10 M nodes, not 10 MB; tile_count[t] is the number of set bits among tile t's
+// rows, and a tile with none reads no flags at all.  Derived from the byte mask by pr_dangling_bits; the mask is a
+// property of the matrix, so this holds for the shard's life.  words == nullptr: the shard has none (bytes are read).
+struct DanglingBits {
+    const unsigned int* words = nullptr;    // [pr_dangling_words(local_rows)]
+    const int* tile_count = nullptr;        // [plan.num_tiles]
+};
+inline size_t pr_dangling_words(int local_rows) { return 2 * ((static_cast<size_t>(std::max(local_rows, 0)) + 63) / 64); }
+
 // One rank's slice of the problem: local_rows consecutive rows of the n_global x n_global matrix (CSR with
 // row_ptrs rebased to 0), whose nodes sit at map.at(0 .. local_rows - 1) of the rank vectors.
 struct PrShard {
@@ -52,6 +65,9 @@ struct PrShard {
     const int* d_cols = nullptr;
     const float* d_vals = nullptr;
     const unsigned char* d_dangling = nullptr;   // [>= n_global] 1 = dangling node
+    unsigned int* d_dangling_words = nullptr;    // see DanglingBits; both null where the shard's owner keeps none
+    int* d_tile_dangling = nullptr;
+    bool dangling_bits_ready = false;            // pr_dangling_bits has been enqueued since the arrays were set
     PrState* d_state = nullptr;
     double* d_block_partials = nullptr;          // [2 * pr_max_blocks()]
     int lanes = 4;                               // lanes per row, from the mean row length
@@ -98,6 +114,9 @@ hipError_t pr_flush(const PrShard& shard, hipStream_t s);
 inline void pr_drop_pending(const PrShard& shard) { shard.commit_pending = false; }
 hipError_t pr_commit_gathered(const PrShard& shard, const float* d_gathered, int world, long long stride,
                               long long shard_len, float tolerance, hipStream_t s);
+// Fills the shard's d_dangling_words / d_tile_dangling from d_dangling on `s` (no-op without the arrays, without a
+// tiled plan, or on a chunked map: only the contiguous-slice branch of phase 2 reads them).
+hipError_t pr_dangling_bits(PrShard* shard, hipStream_t s);
 hipError_t pr_fill(float* d_r, size_t n, float value, hipStream_t s);
 hipError_t pr_column_sums(long long nnz, const int* d_cols, const float* d_vals, int n_cols,
                           float* d_col_sums, hipStream_t s);

@@ -18,6 +18,7 @@ struct PrState;
 struct CommitRider;
 struct PushTargets;
 struct RowMap;
+struct DanglingBits;
 struct PassDesc;      // tiled_layout.h
 
 // Per-matrix bucketed copy of the entries (built once on the device, cached in the
@@ -35,13 +36,15 @@ struct TiledPlan {
     DevBuf<float>    a_val;      // [nnz]; null when the values are folded into col_weight
     DevBuf<float>    col_weight; // [num_cols] the one value every entry of a column carries, or null
     DevBuf<uint16_t> a_lcol;     // [nnz] column - strip * W
-    DevBuf<uint8_t>  a_drow;     // [nnz] row - (row of the cell's previous slot), 0..254; 255 = advance 255 rows, no entry
+    DevBuf<uint8_t>  a_drow;     // [nnz] row - (row of the cell's previous slot), 0..254; 255 = advance 255 rows, no entry.
+                                 // BUILD ONLY: the finished plan holds the same bytes in pass order (pass_word) and frees this
     DevBuf<float>    prod;       // [nnz] phase-1 output / phase-2 input, same order
     DevBuf<int>      cells_t;    // [2 * num_tiles * num_strips]: (begin, length) pairs, tile-major
     // phase 2's work, laid out at build time (tiled_cells.hip, pass_layout_kernel): the slots of wavefront w of tile t's workgroup
     // are the passes [pass_first[16 t + w], pass_first[16 t + w + 1]), one 32-byte descriptor each
     DevBuf<int>      pass_first; // [16 * num_tiles + 1]
     DevBuf<PassDesc> pass_desc;  // [num_passes]
+    DevBuf<uint32_t> pass_word;  // [64 * num_passes] the four row-delta bytes lane l of pass p adds: word 64 p + l (all kSkip past the pass's end)
     long long num_passes = 0;
 
     // phase-1 work items: (strip, begin, end), at most kItemEntries slots each
@@ -97,7 +100,7 @@ hipError_t tiled_build(const CSRMatrix* A, TiledPlan** out, hipStream_t s);
 hipError_t tiled_build(const ELLMatrix* A, TiledPlan** out, hipStream_t s);   // from the ELL slabs (no long-row path)
 void tiled_free(TiledPlan* plan);      // = delete: the plan's members own what it holds
 
-// position-weighted checksums of a_val / a_lcol / a_drow / cells_t (test aid: equal plans, equal numbers)
+// position-weighted checksums of a_val / a_lcol / pass_word / cells_t (test aid: equal plans, equal numbers)
 hipError_t tiled_checksum(const TiledPlan& plan, unsigned long long out[4], hipStream_t s);
 
 // y = A x.  hipErrorOutOfMemory: no scratch for this (additional) stream — the caller may use another kernel.
@@ -113,9 +116,11 @@ hipError_t tiled_pagerank_expand(const TiledPlan& plan, int strip_begin, int str
                                  const float* d_r_old, const PrState* d_state, const CommitRider& commit, hipStream_t s);
 // Phase 2: r_new[map.at(i)] = d * (A r_old)_i + d*s/n + (1-d)/n, block partial sums of (r_new - r_old)^2
 // and of r_new over dangling nodes -> block_partials [2 * plan.num_tiles]; no-op when state->done.
+// `bits` (may be empty): the flags of the shard's rows as bits, read instead of d_dangling by a contiguous slice
+// without push targets.
 hipError_t tiled_pagerank_finish(const TiledPlan& plan, const RowMap& map, int n_global,
                                  const float* d_r_old, float* d_r_new,
-                                 const unsigned char* d_dangling, float damping,
+                                 const unsigned char* d_dangling, const DanglingBits& bits, float damping,
                                  const PrState* d_state, double* d_block_partials,
                                  const PushTargets& push, hipStream_t s);
 

@@ -13,7 +13,8 @@
 //   layout : slots sorted by cell = (column strip, row tile), strip-major, and by (row, column)
 //        inside a cell.  Per slot: value f32, local column u16, ROW DELTA u8 (row minus the row of the
 //        cell's previous slot; 255 = "advance 255 rows, no entry" for the rare larger gaps) — 7 B
-//        against CSR's 8 — plus a 4-byte product slot.  Cells are padded to a multiple of 4 slots.
+//        against CSR's 8 — plus a 4-byte product slot.  Cells are padded to a multiple of 4 slots.  The row deltas are
+//        kept in the order phase 2 reads them, 64 four-byte words per pass (pass_word, tiled_layout.h), not slot by slot.
 //   phase 1 "expand" : a workgroup loads one x strip (W = 4 K .. 32 K columns, chosen per
 //        matrix = 16 .. 128 KiB) into LDS, streams its share of the strip's slots (value, local column) with
 //        16-byte loads, gathers x from LDS and stores the products — same order, so
@@ -180,12 +181,16 @@ template <int kExpandBlock, bool FOLD>
 __device__ __forceinline__ void expand_slots(const float* xs, int begin, int end, const float* __restrict__ a_val,
                                              const unsigned short* __restrict__ a_lcol, float* __restrict__ prod) {
     constexpr int kStride = kExpandBlock * 4;
+    // Both loops start at the 16-slot boundary at or below `begin` (16 products = one 64-byte sector): a wavefront's 1 KB
+    // of non-temporal stores then covers whole sectors, where an origin of begin & ~3 split a sector between two
+    // instructions and, as such stores do not merge, wrote it twice (profiles/aligned_streams_traffic_ab.txt).  The
+    // groups in front of `begin` are masked like those behind `end`: same products to the same slots.
     if (FOLD) {
         // four entries per lane per group, two groups a workgroup-stride apart per step: every store instruction writes
         // one contiguous KB per wavefront (round 3's eight consecutive entries per lane made each instruction write every
         // other 16 bytes; harmless with plain stores, which meet in L2, but 31 % more write traffic with the non-temporal
         // ones: WRITE_SIZE 826 against 631 MB on C5)
-        for (int q = (begin & ~3) + threadIdx.x * 4; q < end; q += 2 * kStride) {
+        for (int q = (begin & ~15) + threadIdx.x * 4; q < end; q += 2 * kStride) {
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const int g = q + u * kStride;
@@ -205,7 +210,7 @@ __device__ __forceinline__ void expand_slots(const float* xs, int begin, int end
     // per lane with all loads issued up front, and the next group's loads in flight while this one is multiplied: no gain,
     // the bunched forms lose 1-2 % — profiles/r04_kernel_ab_descriptors.txt; once a workgroup streams, phase 1 runs at the
     // rate its 10 bytes per slot allow.  What paid was the start of a workgroup's life: the staging.)
-    for (int q = (begin & ~3) + threadIdx.x * 4; q < end; q += kStride) {
+    for (int q = (begin & ~15) + threadIdx.x * 4; q < end; q += kStride) {
         if (q >= begin && q + 3 < end) {
             const u16x4 c = *reinterpret_cast<const u16x4*>(a_lcol + q);
             const f32x4 v = *reinterpret_cast<const f32x4*>(a_val + q);
@@ -281,7 +286,7 @@ struct LongSeeds {
 __device__ __forceinline__ void tile_accumulate(double* tile, int R, int tile_index,
                                                 const int* __restrict__ pass_first, const PassDesc* __restrict__ desc,
                                                 const float* __restrict__ prod,
-                                                const unsigned char* __restrict__ a_drow,
+                                                const unsigned int* __restrict__ pass_word,
                                                 const LongSeeds seeds) {
     __shared__ double spare[64];           // where a lane's slots without an entry "add" (never read)
     const long long first = static_cast<long long>(tile_index) * R;
@@ -302,9 +307,8 @@ __device__ __forceinline__ void tile_accumulate(double* tile, int R, int tile_in
 
     struct Pass {
         int lane_adj;                      // adj of the lane's segment (selected when the pass is opened: a select over struct
-        int groups;                        //  members kept for later turns into an indexed load from scratch memory)
-        f32x4 p;
-        unsigned int d;
+        f32x4 p;                           //  members kept for later turns into an indexed load from scratch memory)
+        unsigned int d;                    // the lane's four row deltas; all kSkip on the lanes past the pass's end
     };
     // descriptors 64 at a time: lane l holds pass window_first + l
     for (int window_first = pass_lo; window_first < pass_hi; window_first += 64) {
@@ -325,9 +329,12 @@ __device__ __forceinline__ void tile_accumulate(double* tile, int R, int tile_in
             const int adj2 = __builtin_amdgcn_readlane(static_cast<int>(hi.y), idx);
             const unsigned int geom = static_cast<unsigned int>(__builtin_amdgcn_readlane(static_cast<int>(hi.z), idx));
             const int start1 = static_cast<int>(geom & 0xFF), start2 = static_cast<int>((geom >> 8) & 0xFF);
-            ps.groups = static_cast<int>(geom >> 16);
-            // lanes past the pass's end re-read its last group (same cache line) and are masked in add()
-            const int at = min(lane, ps.groups - 1);
+            const int groups = static_cast<int>(geom >> 16);
+            // The row deltas come from the pass-ordered copy the builder laid out (pass_word, tiled_layout.h): one aligned
+            // 256-byte block per pass, whatever the segments.  Lanes past the pass's end find four skip markers there;
+            // their product load re-reads the pass's last group (same cache line).
+            ps.d = pass_word[(static_cast<size_t>(window_first) + idx) * 64 + lane];
+            const int at = min(lane, groups - 1);
             int base = base0, adj = adj0;
             base = at >= start1 ? base1 : base;
             adj = at >= start1 ? adj1 : adj;
@@ -336,10 +343,9 @@ __device__ __forceinline__ void tile_accumulate(double* tile, int R, int tile_in
             ps.lane_adj = adj;
             const unsigned int slot = static_cast<unsigned int>(base + 4 * at);
             ps.p = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(prod) + (static_cast<size_t>(slot) << 2));
-            ps.d = *reinterpret_cast<const unsigned int*>(a_drow + slot);
         };
         auto add = [&](const Pass& ps) {
-            const unsigned int word = lane < ps.groups ? ps.d : 0xFFFFFFFFu;
+            const unsigned int word = ps.d;
             int delta[4], upto[4], sum = 0;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -402,14 +408,14 @@ template <int kReduceBlock>
 __global__ __launch_bounds__(kReduceBlock, kReduceBlock / 128)     // two tiles per CU: 8 wavefronts per SIMD
 void tiled_reduce_kernel(int R, int num_tiles, const int* __restrict__ pass_first, const PassDesc* __restrict__ pass_desc,
                          const float* __restrict__ prod,
-                         const unsigned char* __restrict__ a_drow,
+                         const unsigned int* __restrict__ pass_word,
                          const LongSeeds seeds,
                          int num_rows, float* __restrict__ y) {
     static_assert(kReduceBlock == kReduceThreads, "the pass layout is made for this workgroup size");
     extern __shared__ double tile[];
     const int tile_index = xcd_contiguous(blockIdx.x, num_tiles);
     if (tile_index < 0) return;
-    tile_accumulate(tile, R, tile_index, pass_first, pass_desc, prod, a_drow, seeds);
+    tile_accumulate(tile, R, tile_index, pass_first, pass_desc, prod, pass_word, seeds);
     const long long first = static_cast<long long>(tile_index) * R;
     for (int i = threadIdx.x; i < R && first + i < num_rows; i += kReduceBlock) y[first + i] = static_cast<float>(tile[i]);
 }
@@ -419,18 +425,20 @@ template <int kReduceBlock>
 __global__ __launch_bounds__(kReduceBlock, kReduceBlock / 128)
 void tiled_pagerank_reduce_kernel(int R, int num_tiles, const int* __restrict__ pass_first, const PassDesc* __restrict__ pass_desc,
                                   const float* __restrict__ prod,
-                                  const unsigned char* __restrict__ a_drow,
+                                  const unsigned int* __restrict__ pass_word,
                                   const LongSeeds seeds,
                                   int local_rows, RowMap map, int n_global,
                                   const float* __restrict__ r_old, float* __restrict__ r_new,
-                                  const unsigned char* __restrict__ dangling, float damping,
+                                  const unsigned char* __restrict__ dangling, DanglingBits bits, float damping,
                                   const PrState* __restrict__ state,
                                   double* __restrict__ block_partials, PushTargets push) {
     if (state->done) return;
     extern __shared__ double tile[];
     const int tile_index = xcd_contiguous(blockIdx.x, num_tiles);
     if (tile_index < 0) return;
-    tile_accumulate(tile, R, tile_index, pass_first, pass_desc, prod, a_drow, seeds);
+    // (asked for here, a whole tile ahead of its use: behind the r_old loads below it would be one more exposed latency)
+    const int flagged_rows = bits.words ? bits.tile_count[tile_index] : 0;
+    tile_accumulate(tile, R, tile_index, pass_first, pass_desc, prod, pass_word, seeds);
 
     const float teleport = __fdiv_rn(1.0f - damping, static_cast<float>(n_global));
     const float dangling_term = __fdiv_rn(__fmul_rn(damping, state->dangling_sum),
@@ -446,13 +454,36 @@ void tiled_pagerank_reduce_kernel(int R, int num_tiles, const int* __restrict__ 
         const long long node_first = map.base + first;
         const int rows_here = static_cast<int>(min(static_cast<long long>(R), local_rows - first));     // >= 1: the tile exists
         float old_rank[kPerThread];
-        unsigned char is_dangling[kPerThread];
+        unsigned int is_dangling[kPerThread];
         // (unconditional loads at clamped rows: a guarded load is a branch, and the compiler waits for each behind its join)
 #pragma unroll
         for (int u = 0; u < kPerThread; ++u) {
             const int i = min(static_cast<int>(threadIdx.x) + u * kReduceBlock, rows_here - 1);
             old_rank[u] = r_old[node_first + i];
-            is_dangling[u] = dangling[node_first + i];
+        }
+        // The flags: one BIT per local row where the shard holds them (DanglingBits, pagerank_engine.h) — a wavefront reads
+        // the two words of its 64 rows instead of 64 bytes — and nothing at all for a tile without a dangling row, which
+        // in a web graph is most of them.  One wave-uniform branch around all of a thread's flag loads, none around each;
+        // the loads only load (the word is kept, its bit is taken below: a shift right behind each load made the compiler
+        // wait for every word before it asked for the next).  A tile starts on a multiple of 64 rows and the threads of a
+        // round are 1024 rows apart, so the bit of row i of the tile is bit threadIdx.x % 32 of its word in every round.
+        const bool packed = bits.words != nullptr;
+        const unsigned int flag_shift = packed ? threadIdx.x & 31u : 0u;
+        if (!packed) {
+#pragma unroll
+            for (int u = 0; u < kPerThread; ++u) {
+                const int i = min(static_cast<int>(threadIdx.x) + u * kReduceBlock, rows_here - 1);
+                is_dangling[u] = dangling[node_first + i];
+            }
+        } else if (flagged_rows != 0) {
+#pragma unroll
+            for (int u = 0; u < kPerThread; ++u) {
+                const long long row = first + min(static_cast<int>(threadIdx.x) + u * kReduceBlock, rows_here - 1);
+                is_dangling[u] = bits.words[row >> 5];
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < kPerThread; ++u) is_dangling[u] = 0;
         }
 #pragma unroll
         for (int u = 0; u < kPerThread; ++u) {
@@ -462,7 +493,7 @@ void tiled_pagerank_reduce_kernel(int R, int num_tiles, const int* __restrict__ 
                 r_new[node_first + i] = fresh;
                 const float diff = __fsub_rn(fresh, old_rank[u]);
                 res2 += static_cast<double>(__fmul_rn(diff, diff));
-                if (is_dangling[u]) mass += static_cast<double>(fresh);
+                if (packed ? (is_dangling[u] >> flag_shift) & 1u : is_dangling[u]) mass += static_cast<double>(fresh);
             }
         }
     } else {
@@ -565,13 +596,13 @@ hipError_t launch_reduce(const TiledPlan& plan, const Scratch& sc, float* d_y, h
     const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
     if (e != hipSuccess) return e;
     tiled_reduce_kernel<kReduceThreads><<<xcd_grid(plan.num_tiles), kReduceThreads, lds, s>>>(
-        plan.tile_rows, plan.num_tiles, plan.pass_first.get(), plan.pass_desc.get(), sc.prod, plan.a_drow.get(),
+        plan.tile_rows, plan.num_tiles, plan.pass_first.get(), plan.pass_desc.get(), sc.prod, plan.pass_word.get(),
         long_seeds(plan, sc), plan.num_rows, d_y);
     return hipGetLastError();
 }
 
 hipError_t launch_pagerank_reduce(const TiledPlan& plan, const Scratch& sc, const RowMap& map, int n_global, const float* d_r_old,
-                                  float* d_r_new, const unsigned char* d_dangling, float damping,
+                                  float* d_r_new, const unsigned char* d_dangling, const DanglingBits& bits, float damping,
                                   const PrState* d_state, double* d_block_partials,
                                   const PushTargets& push, hipStream_t s) {
     const size_t lds = static_cast<size_t>(plan.tile_rows) * sizeof(double);
@@ -579,8 +610,8 @@ hipError_t launch_pagerank_reduce(const TiledPlan& plan, const Scratch& sc, cons
     const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
     if (e != hipSuccess) return e;
     tiled_pagerank_reduce_kernel<kReduceThreads><<<xcd_grid(plan.num_tiles), kReduceThreads, lds, s>>>(
-        plan.tile_rows, plan.num_tiles, plan.pass_first.get(), plan.pass_desc.get(), sc.prod, plan.a_drow.get(),
-        long_seeds(plan, sc), plan.num_rows, map, n_global, d_r_old, d_r_new, d_dangling, damping, d_state,
+        plan.tile_rows, plan.num_tiles, plan.pass_first.get(), plan.pass_desc.get(), sc.prod, plan.pass_word.get(),
+        long_seeds(plan, sc), plan.num_rows, map, n_global, d_r_old, d_r_new, d_dangling, bits, damping, d_state,
         d_block_partials, push);
     return hipGetLastError();
 }
@@ -613,13 +644,13 @@ hipError_t tiled_pagerank_expand(const TiledPlan& plan, int strip_begin, int str
 
 hipError_t tiled_pagerank_finish(const TiledPlan& plan, const RowMap& map, int n_global,
                                  const float* d_r_old, float* d_r_new,
-                                 const unsigned char* d_dangling, float damping,
+                                 const unsigned char* d_dangling, const DanglingBits& bits, float damping,
                                  const PrState* d_state, double* d_block_partials,
                                  const PushTargets& push, hipStream_t s) {
     Scratch sc;
     const hipError_t e = scratch_for(plan, s, &sc);
     if (e != hipSuccess) return e;
-    return launch_pagerank_reduce(plan, sc, map, n_global, d_r_old, d_r_new, d_dangling, damping, d_state,
+    return launch_pagerank_reduce(plan, sc, map, n_global, d_r_old, d_r_new, d_dangling, bits, damping, d_state,
                                   d_block_partials, push, s);
 }
 

@@ -36,7 +36,7 @@ struct BuiltCells {
 // the counts that go with them (plan->long_rows too, from a CSR source: unsorted).  Synchronises the stream.
 hipError_t build_cells(const CSRMatrix* A, TiledPlan* plan, BuiltCells* out, hipStream_t s);
 hipError_t build_cells(const ELLMatrix* A, TiledPlan* plan, BuiltCells* out, hipStream_t s);   // no long-row path
-// plan->pass_desc for the finished cells
+// plan->pass_desc and plan->pass_word for the finished cells (reads a_drow, which build_plan frees afterwards)
 hipError_t layout_passes(TiledPlan* plan, hipStream_t s);
 
 } // namespace detail

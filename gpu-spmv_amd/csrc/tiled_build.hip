@@ -90,11 +90,13 @@ void weight_finish_kernel(float* __restrict__ weight, int n) {
     }
 }
 
-// position-weighted checksums of the three slot arrays and of the cell table (a debugging / test aid: two
-// builds of one matrix must give the same four numbers whatever path the builder took)
+// position-weighted checksums of the three slot streams and of the cell table (a debugging / test aid: two
+// builds of one matrix must give the same four numbers whatever path the builder took).  The row deltas are summed
+// where the finished plan keeps them: in pass order (pass_word), a function of the slots' bytes and the cell table alone.
 __global__ __launch_bounds__(kBlock)
 void plan_checksum_kernel(long long slots, const float* __restrict__ a_val, const unsigned short* __restrict__ a_lcol,
-                          const unsigned char* __restrict__ a_drow, long long table_ints, const int* __restrict__ cells_t,
+                          long long delta_words, const unsigned int* __restrict__ pass_word,
+                          long long table_ints, const int* __restrict__ cells_t,
                           unsigned long long* __restrict__ out /*[4]*/) {
     unsigned long long v = 0, c = 0, d = 0, t = 0;
     for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < slots;
@@ -102,7 +104,10 @@ void plan_checksum_kernel(long long slots, const float* __restrict__ a_val, cons
         const unsigned long long w = 2 * static_cast<unsigned long long>(i) + 1;
         if (a_val) v += w * __float_as_uint(a_val[i]);
         c += w * a_lcol[i];
-        d += w * a_drow[i];
+    }
+    for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < delta_words;
+         i += static_cast<long long>(gridDim.x) * kBlock) {
+        d += (2 * static_cast<unsigned long long>(i) + 1) * pass_word[i];
     }
     for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < table_ints;
          i += static_cast<long long>(gridDim.x) * kBlock) {
@@ -312,14 +317,18 @@ hipError_t build_plan(const Source& src, TiledPlan** out, hipStream_t s) {
     if (e == hipSuccess && fold && plan->nnz > 0) e = probe_fold(plan.get(), built.strip_begin.get(), s);
     if (e != hipSuccess) return e;
     built.strip_begin.reset();
+    // The slot-ordered row deltas have served (pass layout, fold probe): phase 2 reads the pass-ordered copy.  The free
+    // waits for the device, like the temporaries' above.
+    plan->a_drow.reset();
 
     e = dev_alloc(&plan->prod, plan->nnz + 8);
     if (e == hipSuccess) e = make_items(plan.get(), built.host_strip);
     if (e != hipSuccess) return e;
 
     trace.mark("fold probe, long rows, items");
-    plan->plan_bytes = plan->nnz * (4 /*prod*/ + 2 + 1 + (plan->a_val ? 4 : 0)) + cells * 8 +
-                       plan->num_passes * static_cast<long long>(sizeof(PassDesc)) + 4LL * (plan->num_tiles * kReduceWaves + 1) +
+    plan->plan_bytes = plan->nnz * (4 /*prod*/ + 2 + (plan->a_val ? 4 : 0)) + cells * 8 +
+                       plan->num_passes * static_cast<long long>(sizeof(PassDesc) + kPassSlots /*pass_word*/) +
+                       4LL * (plan->num_tiles * kReduceWaves + 1) +
                        (plan->col_weight ? 4LL * plan->num_cols : 0) +
                        12LL * plan->num_items + 12LL * plan->num_long_chunks;
     plan->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
@@ -356,8 +365,9 @@ hipError_t tiled_checksum(const TiledPlan& plan, unsigned long long out[4], hipS
     if (e != hipSuccess) return e;
     e = hipMemsetAsync(d_out.get(), 0, 4 * sizeof(unsigned long long), s);
     if (e == hipSuccess) {
-        plan_checksum_kernel<<<1024, kBlock, 0, s>>>(plan.nnz, plan.a_val.get(), plan.a_lcol.get(), plan.a_drow.get(),
-                                                     2LL * plan.num_strips * plan.num_tiles, plan.cells_t.get(), d_out.get());
+        plan_checksum_kernel<<<1024, kBlock, 0, s>>>(plan.nnz, plan.a_val.get(), plan.a_lcol.get(), 64 * plan.num_passes,
+                                                     plan.pass_word.get(), 2LL * plan.num_strips * plan.num_tiles,
+                                                     plan.cells_t.get(), d_out.get());
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_out.get(), 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s);

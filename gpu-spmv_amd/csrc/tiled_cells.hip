@@ -933,14 +933,16 @@ void cell_table_kernel(const int* __restrict__ offs, int num_strips, int num_til
 }
 
 // Lays out the passes of every (tile, wavefront): FILL = false counts them (-> pass_count[tile * 16 + wave]), FILL = true
-// writes their descriptors at pass_first[tile * 16 + wave].  One 1024-thread workgroup per tile, wavefront w does the share
+// writes their descriptors at pass_first[tile * 16 + wave] and, beside each, the pass's 64 row-delta words in lane order
+// (pass_word, tiled_layout.h).  One 1024-thread workgroup per tile, wavefront w does the share
 // of wavefront w of the phase-2 workgroup.  The (begin, length) records of a wavefront's runs come 64 at a time (lane l holds
 // run window_first + l, read back with v_readlane); a pass never straddles two such windows.
 template <bool FILL>
 __global__ __launch_bounds__(kReduceThreads)
 void pass_layout_kernel(int num_tiles, int num_strips, const int2* __restrict__ cells_t,
                         const unsigned char* __restrict__ a_drow,
-                        int* __restrict__ pass_count, const int* __restrict__ pass_first, PassDesc* __restrict__ desc) {
+                        int* __restrict__ pass_count, const int* __restrict__ pass_first, PassDesc* __restrict__ desc,
+                        unsigned int* __restrict__ pass_word) {
     const int tile_index = blockIdx.x;
     if (tile_index >= num_tiles) return;
     const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
@@ -986,6 +988,7 @@ void pass_layout_kernel(int num_tiles, int num_strips, const int2* __restrict__ 
 #pragma unroll
             for (int k = 1; k < kPassSegs; ++k) mine_base = at >= start[k] ? base[k] : mine_base;
             const unsigned int word = lane < groups ? *reinterpret_cast<const unsigned int*>(a_drow + mine_base + 4 * at) : 0u;
+            pass_word[out * 64 + lane] = lane < groups ? word : 0xFFFFFFFFu;     // past the end: four skip markers
             const int sum = static_cast<int>((word & 0xFF) + ((word >> 8) & 0xFF) + ((word >> 16) & 0xFF) + (word >> 24));
             const int incl = wave_inclusive_scan(sum);
             // row in front of each segment, and the delta sums in front of it
@@ -1166,7 +1169,7 @@ hipError_t build_cells_from(const Src& dev_src, bool has_long_path, TiledPlan* p
         cell_table_kernel<<<grid, kBlock, 0, s>>>(offs, S, T, cells_t, strip_begin);
         // phase 2's passes are a function of the cell table alone: counted and scanned here, beside the placing pass, so that
         // their total arrives with this function's last synchronisation (the descriptors are written by build_plan)
-        pass_layout_kernel<false><<<T, kReduceThreads, 0, s>>>(T, S, cells_t, nullptr, pass_first, nullptr, nullptr);
+        pass_layout_kernel<false><<<T, kReduceThreads, 0, s>>>(T, S, cells_t, nullptr, pass_first, nullptr, nullptr, nullptr);
         exclusive_scan_small_kernel<<<1, kScanBlock, 0, s>>>(pass_first, pass_waves);
     }
     if (plan->nnz > 0) {
@@ -1219,13 +1222,15 @@ hipError_t build_cells(const ELLMatrix* A, TiledPlan* plan, BuiltCells* out, hip
     return build_cells_from(dev_src, false, plan, out, s);
 }
 
-// phase 2's pass descriptors (pass_layout_kernel; counted and scanned beside the placing pass in build_cells)
+// phase 2's pass descriptors and pass-ordered row deltas (pass_layout_kernel; counted and scanned beside the placing
+// pass in build_cells)
 hipError_t layout_passes(TiledPlan* plan, hipStream_t s) {
-    const hipError_t e = dev_alloc(&plan->pass_desc, plan->num_passes);
+    hipError_t e = dev_alloc(&plan->pass_desc, plan->num_passes);
+    if (e == hipSuccess) e = dev_alloc(&plan->pass_word, 64 * plan->num_passes);
     if (e != hipSuccess) return e;
     pass_layout_kernel<true><<<plan->num_tiles, kReduceThreads, 0, s>>>(plan->num_tiles, plan->num_strips,
                                                                        reinterpret_cast<const int2*>(plan->cells_t.get()), plan->a_drow.get(), nullptr,
-                                                                       plan->pass_first.get(), plan->pass_desc.get());
+                                                                       plan->pass_first.get(), plan->pass_desc.get(), plan->pass_word.get());
     return hipGetLastError();
 }
 

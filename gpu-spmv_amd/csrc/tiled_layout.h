@@ -44,6 +44,17 @@ constexpr int kMaxBuildStrips = 3072;
 //              of all lanes in front of the segment: row of a slot = adj[segment] + (wave-wide exclusive prefix of the lanes'
 //              delta sums) + the in-lane prefix — no carry from pass to pass, nothing read back from the scan
 //     geom     first lane of segments 1 and 2, lanes in use
+// Beside the descriptors the builder writes the row deltas in PASS ORDER: pass_word[64 * p + l] holds the four delta
+// bytes lane l of pass p adds (the word at a_drow + base[segment of l] + 4 l), and 0xFFFFFFFF — four skip markers — on
+// the lanes past the pass's end.  A pass's deltas are then one aligned 256-byte block and a wavefront's passes are
+// contiguous, where the slot-ordered bytes were one 256-byte piece per run at an arbitrary 4-byte offset whose first and
+// last sectors were shared with the neighbouring tile's run and fetched twice whenever the two tiles did not meet in L2;
+// the load no longer waits for the segment select, and add() needs no `lane < groups` select for the deltas.  The
+// slot-ordered array (TiledPlan::a_drow) lives only while the plan is built.  Cost: the unused tail of every pass that
+// is not full — the last pass of a (tile, wavefront), and passes closed by the three-segment limit — is stored as
+// markers: for the 10 M x 16 bench plan 637 790 passes x 256 B = 163.27 MB against 161.14 MB of slot-ordered bytes
+// (plan_bytes 1 798 181 216 -> 1 800 311 232), while phase 2's reads fell from 895.3 to 888.3 MB per step
+// (profiles/aligned_streams_traffic_ab.txt; DESIGN §4.5 has the byte table).
 // The hot loop is then: 8 v_readlane per pass, two loads, one wave scan, four ds_add_f64 — and passes are independent of
 // each other, so the next ones' loads are always in flight.  Same slots, same rows, same fp64 adds as the round-3 form:
 // bit-identical results (tests/tiled_small_shapes_worker.py: ~150 awkward shapes and the hand-picked run-length patterns —
@@ -61,6 +72,14 @@ struct PassDesc {                       // 32 bytes = two 16-byte loads
     unsigned int reserved;
 };
 static_assert(sizeof(PassDesc) == 32, "a lane loads its pass descriptor as two 16-byte words");
+
+// ---- phase 1's walk of a work item ----
+// expand_slots starts at the 16-slot boundary at or below the item's first slot (begin & ~15: 16 products = one 64-byte
+// sector) and masks the groups in front of `begin` exactly as those behind `end`.  Every full store instruction of a
+// wavefront then writes 1 KB of whole sectors.  With the origin at begin & ~3 an instruction's 1 KB started at any
+// 16-byte offset, and the non-temporal product stores do not merge partial sectors: a sector split between two
+// instructions was written twice (WRITE_SIZE 653.6 -> 650.3 MB for 644.6 MB of products on the bench plan, phase 1
+// 311.6 -> 307.8 us; the remaining 5.7 MB are not explained — profiles/aligned_streams_traffic_ab.txt).
 
 // ---- device side (the host-only tiled_plan.cpp reads the constants above) ----
 #ifdef __HIP__

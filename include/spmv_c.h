@@ -670,6 +670,10 @@ typedef struct spmv_c_pr_status {                 /* device-side state, copied o
     int32_t reserved;
 } spmv_c_pr_status;
 
+/* d_dangling_mask (1 = dangling node, indexed like the rank vectors) must stay allocated for the shard's life.  It is a
+ * property of the matrix: a shard that steps through the LDS-tiled engine on one contiguous slice reads it when it is
+ * created and again at every spmv_c_pr_reset (one bit per local row is kept), so a mask filled or changed after the
+ * creation takes effect with the next reset. */
 spmv_c_pr_shard* spmv_c_pr_shard_create(const spmv_c_csr* A_local, int row_offset, int n_global,
                                         const uint8_t* d_dangling_mask);
 /* the same for a CHUNKED vector layout (the overlapped exchange of pagerank_dist.py): local row i sits at
