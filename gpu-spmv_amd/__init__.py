@@ -404,6 +404,13 @@ _SIGNATURES = {
     "spmv_c_amg_level": (c_int, [c_void_p, c_int, POINTER(CSRMatrix), POINTER(c_void_p), POINTER(c_int32)]),
     "spmv_c_amg_apply": (c_int, [c_void_p, c_void_p, c_void_p]),
     "spmv_c_amg_aggregate_cpu_csr": (c_int, [POINTER(CSRMatrix), c_float, c_void_p, POINTER(c_int32)]),
+    "spmv_c_amg_aggregate_mis2_cpu_csr": (c_int, [POINTER(CSRMatrix), c_float, ctypes.c_uint32, c_void_p, POINTER(c_int32),
+                                                  POINTER(c_int32)]),
+    "spmv_c_amg_aggregate_mis2_gpu": (c_int, [POINTER(CSRMatrix), c_float, ctypes.c_uint32, c_void_p, POINTER(c_int32),
+                                              POINTER(c_int32)]),
+    "spmv_c_amg_setup_device": (c_int, [POINTER(c_void_p), POINTER(CSRMatrix), POINTER(AMGConfig), ctypes.c_uint32,
+                                        POINTER(AMGResult)]),
+    "spmv_c_amg_setup_rounds": (c_int, [c_void_p, c_int]),
     "spmv_c_cg_solve_amg": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, c_void_p, POINTER(CGConfig),
                                     POINTER(CGResult)]),
     "spmv_c_sptrsv_csr": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(SpTRSVConfig),
@@ -1190,6 +1197,40 @@ def amg_aggregate_cpu_csr(A, strength=0.08):
     count = c_int32(-7)
     status = lib().spmv_c_amg_aggregate_cpu_csr(A, float(strength), _np_ptr(agg), byref(count))
     return status, agg, count.value
+
+
+def amg_aggregate_mis2_cpu_csr(A, strength=0.08, seed=0):
+    """(status, aggregate int32[num_rows], count, rounds): the MIS-2 aggregation of one level on A's host arrays, the
+    definition of the device's (amg.h amg_aggregate_mis2_cpu_csr); -1 marks a vertex left free, rounds is the
+    synchronous round count."""
+    agg = np.full(max(A.contents.num_rows, 0), -7, np.int32)
+    count, rounds = c_int32(-7), c_int32(-7)
+    status = lib().spmv_c_amg_aggregate_mis2_cpu_csr(A, float(strength), int(seed) & 0xFFFFFFFF, _np_ptr(agg),
+                                                     byref(count), byref(rounds))
+    return status, agg, count.value, rounds.value
+
+
+def amg_aggregate_mis2_gpu(A, d_aggregate, strength=0.08, seed=0):
+    """(status, count, rounds): the same ints into d_aggregate, num_rows ints on the device (a device address or an
+    object _dev understands) (amg.h amg_aggregate_mis2_gpu)."""
+    count, rounds = c_int32(-7), c_int32(-7)
+    status = lib().spmv_c_amg_aggregate_mis2_gpu(A, float(strength), int(seed) & 0xFFFFFFFF, _dev(d_aggregate),
+                                                 byref(count), byref(rounds))
+    return status, count.value, rounds.value
+
+
+def amg_setup_device(A, config=None, seed=0):
+    """(AMGResult, hierarchy handle or None): amg_setup with every level made on the device, aggregated by the MIS-2
+    rule with `seed` (amg.h amg_setup_device).  Release the handle with amg_destroy."""
+    out, handle = AMGResult(), c_void_p()
+    lib().spmv_c_amg_setup_device(byref(handle), A, byref(config) if config is not None else None,
+                                  int(seed) & 0xFFFFFFFF, byref(out))
+    return out, (handle.value if handle.value else None)
+
+
+def amg_setup_rounds(H, level) -> int:
+    """Rounds the root selection of level `level` took (0: the coarsest level, or a hierarchy amg_setup built)."""
+    return lib().spmv_c_amg_setup_rounds(H, int(level))
 
 
 def cg_solve_amg(A, H, d_b, d_x, config=None) -> CGResult:

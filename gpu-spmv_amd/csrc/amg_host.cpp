@@ -20,45 +20,16 @@ namespace {
 
 using detail::code;
 
-bool structure_ok(int n, long long nnz, const int* rp, const int* ci) {
-    if (rp[0] != 0 || rp[n] != nnz) return false;
-    for (int i = 0; i < n; ++i) {
-        if (rp[i + 1] < rp[i] || rp[i + 1] > nnz) return false;
-    }
-    for (long long p = 0; p < nnz; ++p) {
-        if (ci[p] < 0 || ci[p] >= n) return false;
-    }
-    return true;
-}
-
-// fp32 sum of the stored (i,i) entries in storage order; found[i] = 0 where the row stores none
-void diagonal(int n, const int* rp, const int* ci, const float* va, std::vector<float>* d, std::vector<char>* found) {
-    d->assign(static_cast<size_t>(n), 0.0f);
-    if (found) found->assign(static_cast<size_t>(n), 0);
-    for (int i = 0; i < n; ++i) {
-        float sum = 0.0f;
-        for (int p = rp[i]; p < rp[i + 1]; ++p) {
-            if (ci[p] == i) {
-                sum = sum + va[p];
-                if (found) (*found)[i] = 1;
-            }
-        }
-        (*d)[i] = sum;
-    }
-}
+using detail::amg_diagonal;
+using detail::amg_strong;
+using detail::amg_structure_ok;
 
 // the three passes of amg.h on a valid structure; returns the number of aggregates
 int aggregate(int n, const int* rp, const int* ci, const float* va, float theta, int* agg) {
     std::vector<float> d;
-    diagonal(n, rp, ci, va, &d, nullptr);
+    amg_diagonal(n, rp, ci, va, &d, nullptr);
     const double t2 = static_cast<double>(theta) * static_cast<double>(theta);
-    const auto strong = [&](int i, int p) {
-        const int j = ci[p];
-        const float v = va[p];
-        if (j == i || v == 0.0f) return false;
-        return static_cast<double>(v) * static_cast<double>(v) >=
-               t2 * std::fabs(static_cast<double>(d[i]) * static_cast<double>(d[j]));
-    };
+    const auto strong = [&](int i, int p) { return amg_strong(i, ci[p], va[p], t2, d[i], d[ci[p]]); };
     for (int i = 0; i < n; ++i) agg[i] = -1;
     int next = 0;
     for (int i = 0; i < n; ++i) {
@@ -191,7 +162,7 @@ struct Builder {
             (void)hipGetLastError();
             return fail(SpMVError::CUDA_MEMCPY);
         }
-        if (structure && l == 0 && !structure_ok(M.num_rows, M.nnz, lv.row_ptrs.data(), lv.cols.data())) {
+        if (structure && l == 0 && !amg_structure_ok(M.num_rows, M.nnz, lv.row_ptrs.data(), lv.cols.data())) {
             return fail(SpMVError::INVALID_FORMAT);
         }
         return 0;
@@ -203,7 +174,7 @@ struct Builder {
         const int n = lv.view.num_rows;
         std::vector<float> d;
         std::vector<char> found;
-        diagonal(n, lv.row_ptrs.data(), lv.cols.data(), va.data(), &d, &found);
+        amg_diagonal(n, lv.row_ptrs.data(), lv.cols.data(), va.data(), &d, &found);
         std::vector<float> wd(static_cast<size_t>(n));
         for (int i = 0; i < n; ++i) {
             if (!found[i] || !(d[i] > 0.0f) || !std::isfinite(d[i])) return fail(SpMVError::INVALID_ARGUMENT, l, i);
@@ -308,12 +279,39 @@ float ms_since(std::chrono::steady_clock::time_point start) {
 
 } // namespace
 
+namespace detail {
+
+bool amg_config_ok(const AMGConfig& cfg) {
+    return !(cfg.max_levels < 1 || cfg.coarse_rows < 1 || cfg.coarse_rows > kAmgDenseRows || !(cfg.strength >= 0.0f) ||
+             cfg.pre_sweeps < 1 || cfg.post_sweeps < 0 || !(cfg.jacobi_weight > 0.0f && cfg.jacobi_weight < 2.0f) ||
+             cfg.coarse_sweeps < 1);
+}
+
+int amg_level_workspace(AMGHierarchy& H, AMGResult& res, int l) {
+    Builder b{H, res, nullptr};
+    return b.workspace(l);
+}
+
+int amg_finish(AMGHierarchy& H, AMGResult& res, hipStream_t s) {
+    Builder b{H, res, s};
+    const int l = static_cast<int>(H.levels.size()) - 1;
+    std::vector<float> va;
+    if (H.levels[static_cast<size_t>(l)].view.num_rows <= kAmgDenseRows && b.download(l, true, &va) != 0) {
+        return res.error_code;
+    }
+    if (b.coarse_solver(va) != 0) return res.error_code;
+    b.complexities();
+    return 0;
+}
+
+} // namespace detail
+
 int amg_aggregate_cpu_csr(const CSRMatrix* A, float strength, int* aggregate_out, int* num_aggregates) {
     if (!A || !aggregate_out || !num_aggregates) return code(SpMVError::INVALID_ARGUMENT);
     if (A->num_rows != A->num_cols) return code(SpMVError::INVALID_DIMENSION);
     const int n = A->num_rows;
     if (n < 0 || A->nnz < 0 || !A->row_ptrs || (A->nnz > 0 && (!A->col_indices || !A->values)) ||
-        !structure_ok(n, A->nnz, A->row_ptrs, A->col_indices)) {
+        !amg_structure_ok(n, A->nnz, A->row_ptrs, A->col_indices)) {
         return code(SpMVError::INVALID_FORMAT);
     }
     if (!(strength >= 0.0f)) return code(SpMVError::INVALID_ARGUMENT);
@@ -348,11 +346,7 @@ AMGResult amg_setup(AMGHierarchy** out, const CSRMatrix* A, const AMGConfig* con
     if (!device_arrays(A)) return fail(SpMVError::INVALID_FORMAT);
     const AMGConfig defaults;
     const AMGConfig& cfg = config ? *config : defaults;
-    if (cfg.max_levels < 1 || cfg.coarse_rows < 1 || cfg.coarse_rows > kAmgDenseRows || !(cfg.strength >= 0.0f) ||
-        cfg.pre_sweeps < 1 || cfg.post_sweeps < 0 || !(cfg.jacobi_weight > 0.0f && cfg.jacobi_weight < 2.0f) ||
-        cfg.coarse_sweeps < 1) {
-        return fail(SpMVError::INVALID_ARGUMENT);
-    }
+    if (!detail::amg_config_ok(cfg)) return fail(SpMVError::INVALID_ARGUMENT);
     // caller-given maps: sizes and contents, on the host
     int given = 0;
     std::vector<int> given_rows;        // n_{l+1} of each used map
@@ -426,6 +420,7 @@ AMGResult amg_update(AMGHierarchy* H, const CSRMatrix* A) {
         return fail(SpMVError::INVALID_DIMENSION);
     }
     if (!device_arrays(A)) return fail(SpMVError::INVALID_FORMAT);
+    if (H->device_built) return detail::amg_update_device(H, A);
     const detail::TraceRange range("spmv:amg_update");
     H->levels[0].view = device_view(A);
     Builder b{*H, res, detail::current_stream()};
@@ -446,6 +441,11 @@ AMGResult amg_update(AMGHierarchy* H, const CSRMatrix* A) {
 }
 
 int amg_num_levels(const AMGHierarchy* H) { return H ? static_cast<int>(H->levels.size()) : 0; }
+
+int amg_setup_rounds(const AMGHierarchy* H, int level) {
+    if (!H || level < 0 || level >= static_cast<int>(H->levels.size())) return 0;
+    return H->levels[static_cast<size_t>(level)].rounds;
+}
 
 int amg_level(const AMGHierarchy* H, int level, CSRMatrix* view, const int** d_aggregate, int* num_aggregates) {
     if (!H) return code(SpMVError::INVALID_ARGUMENT);

@@ -1,5 +1,6 @@
-// amg_impl.h — the hierarchy behind spmv/amg.h, shared by amg_host.cpp (setup, update), amg.hip (the V-cycle) and
-// cg.hip (cg_solve_amg).  Internal: not installed under include/.
+// amg_impl.h — the hierarchy behind spmv/amg.h, shared by amg_host.cpp (setup, update), amg_setup.hip (the device-side
+// setup), amg_mis2_host.cpp (the MIS-2 aggregation's definition), amg.hip (the V-cycle) and cg.hip (cg_solve_amg).
+// Internal: not installed under include/.
 #ifndef SPMV_AMD_AMG_IMPL_H
 #define SPMV_AMD_AMG_IMPL_H
 
@@ -7,7 +8,14 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <vector>
+
+#if defined(__HIPCC__)
+#define SPMV_AMG_HD __host__ __device__ __forceinline__
+#else
+#define SPMV_AMG_HD inline
+#endif
 
 namespace spmv {
 
@@ -24,7 +32,9 @@ struct AMGLevel {
     int lanes = 1;                // pick_lanes_per_row of the mean row length
     float* d_wd = nullptr;        // [n] omega / d_i
     float* d_work = nullptr;      // level 0: xa, xb; below: f, sol, xa, xb (n floats each)
-    std::vector<int> row_ptrs, cols;   // host copy of the structure (diagonals, the dense coarse matrix)
+    std::vector<int> row_ptrs, cols;   // host copy of the structure (diagonals, the dense coarse matrix); a
+                                       // device-built hierarchy holds it for the coarsest level only
+    int rounds = 0;               // amg_setup_device: rounds the root selection of this level took
 };
 
 struct AMGHierarchy {
@@ -34,9 +44,54 @@ struct AMGHierarchy {
     std::vector<AMGLevel> levels;
     int coarse_solver = 0;
     float* d_cinv = nullptr;      // coarse_solver 0: [n_c * n_c] row-major
+    bool device_built = false;    // amg_setup_device made it: amg_update keeps the levels off the host
 };
 
 namespace detail {
+
+// ---- host pieces both setups and the two aggregations' definitions share ----
+inline bool amg_structure_ok(int n, long long nnz, const int* rp, const int* ci) {
+    if (rp[0] != 0 || rp[n] != nnz) return false;
+    for (int i = 0; i < n; ++i) {
+        if (rp[i + 1] < rp[i] || rp[i + 1] > nnz) return false;
+    }
+    for (long long p = 0; p < nnz; ++p) {
+        if (ci[p] < 0 || ci[p] >= n) return false;
+    }
+    return true;
+}
+
+// fp32 sum of the stored (i,i) entries in storage order; found[i] = 0 where the row stores none
+inline void amg_diagonal(int n, const int* rp, const int* ci, const float* va, std::vector<float>* d,
+                         std::vector<char>* found) {
+    d->assign(static_cast<size_t>(n), 0.0f);
+    if (found) found->assign(static_cast<size_t>(n), 0);
+    for (int i = 0; i < n; ++i) {
+        float sum = 0.0f;
+        for (int p = rp[i]; p < rp[i + 1]; ++p) {
+            if (ci[p] == i) {
+                sum = sum + va[p];
+                if (found) (*found)[i] = 1;
+            }
+        }
+        (*d)[i] = sum;
+    }
+}
+
+// amg.h's strength test on one stored entry (i,j) of value v
+SPMV_AMG_HD bool amg_strong(int i, int j, float v, double theta2, float di, float dj) {
+    if (j == i || v == 0.0f) return false;
+    return static_cast<double>(v) * static_cast<double>(v) >=
+           theta2 * __builtin_fabs(static_cast<double>(di) * static_cast<double>(dj));
+}
+
+// amg_host.cpp, for amg_setup_device / amg_update on its hierarchies (amg_setup.hip):
+bool amg_config_ok(const AMGConfig& cfg);                       // the ranges of amg.h
+int amg_level_workspace(AMGHierarchy& H, AMGResult& res, int l);          // lanes and d_work of level l
+// the coarsest level downloaded when it is inverted, its solver, the complexities; the error code left in res
+int amg_finish(AMGHierarchy& H, AMGResult& res, hipStream_t s);
+// amg_setup.hip: amg_update on a hierarchy amg_setup_device built (the argument checks have passed)
+AMGResult amg_update_device(AMGHierarchy* H, const CSRMatrix* A);
 
 // The V-cycle's launches on `s`, none synchronises.  d_done (may be null) points at a device int: every kernel returns
 // at once when it is not 0 (the `done` of a solver's state).  forced_lanes: 0, or the lane count every level takes.

@@ -687,6 +687,27 @@ int spmv_c_amg_aggregate_cpu_csr(const spmv_c_csr* A, float strength, int32_t* a
     return amg_aggregate_cpu_csr(cxx(A), strength, aggregate, num_aggregates);
 }
 
+int spmv_c_amg_aggregate_mis2_cpu_csr(const spmv_c_csr* A, float strength, uint32_t seed, int32_t* aggregate,
+                                      int32_t* num_aggregates, int32_t* rounds) {
+    return amg_aggregate_mis2_cpu_csr(cxx(A), strength, seed, aggregate, num_aggregates, rounds);
+}
+
+int spmv_c_amg_aggregate_mis2_gpu(const spmv_c_csr* A, float strength, uint32_t seed, int32_t* d_aggregate,
+                                  int32_t* num_aggregates, int32_t* rounds) {
+    return amg_aggregate_mis2_gpu(cxx(A), strength, seed, d_aggregate, num_aggregates, rounds);
+}
+
+int spmv_c_amg_setup_device(spmv_c_amg** out, const spmv_c_csr* A, const spmv_c_amg_config* config, uint32_t seed,
+                            spmv_c_amg_result* result) {
+    AMGHierarchy* H = nullptr;
+    const AMGResult r = amg_setup_device(out ? &H : nullptr, cxx(A), reinterpret_cast<const AMGConfig*>(config), seed);
+    if (out) *out = reinterpret_cast<spmv_c_amg*>(H);
+    if (result) std::memcpy(result, &r, sizeof(r));
+    return r.error_code;
+}
+
+int spmv_c_amg_setup_rounds(const spmv_c_amg* H, int level) { return amg_setup_rounds(cxx(H), level); }
+
 int spmv_c_cg_solve_amg(const spmv_c_csr* A, const spmv_c_amg* H, const float* d_b, float* d_x,
                         const spmv_c_cg_config* config, spmv_c_cg_result* out) {
     const CGResult r = cg_solve_amg(cxx(A), cxx(H), d_b, d_x, reinterpret_cast<const CGConfig*>(config));

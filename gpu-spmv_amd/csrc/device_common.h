@@ -38,6 +38,23 @@ __device__ __forceinline__ float group_sum(float v) {
     return v;
 }
 
+template <int CTRL>
+__device__ __forceinline__ unsigned dpp_u(unsigned v) {
+    return static_cast<unsigned>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), CTRL, 0xF, 0xF, true));
+}
+
+// OR over an aligned group of LANES consecutive lanes, every lane gets the result (group_sum's butterfly)
+template <int LANES>
+__device__ __forceinline__ unsigned group_or(unsigned v) {
+    if constexpr (LANES >= 2)  v |= dpp_u<0xB1>(v);
+    if constexpr (LANES >= 4)  v |= dpp_u<0x4E>(v);
+    if constexpr (LANES >= 8)  v |= dpp_u<0x141>(v);
+    if constexpr (LANES >= 16) v |= dpp_u<0x140>(v);
+    if constexpr (LANES >= 32) v |= static_cast<unsigned>(__shfl_xor(static_cast<int>(v), 16, 64));
+    if constexpr (LANES >= 64) v |= static_cast<unsigned>(__shfl_xor(static_cast<int>(v), 32, 64));
+    return v;
+}
+
 // inclusive prefix sum over the 64 lanes of a wavefront: Hillis-Steele inside each 16-lane DPP row
 // (row_shr 1, 2, 4, 8; lanes shifted in from outside the row contribute 0), then the classic wave64 tail:
 // row_bcast:15 adds lane 15 of the previous row into rows 1 and 3, row_bcast:31 adds lane 31 into rows 2, 3

@@ -193,6 +193,7 @@ void    ell_aux_drop(const void* key);
 //   spgemm_dense_groups=G      workgroups (and scratch slices) of spgemm_csr's dense class, instead of the scratch cap
 //   amg_lanes=N                lanes per row (and per aggregate) of every level of the AMG V-cycle (1, 2, 4, ... 64;
 //                              anything else is ignored)
+//   mis_lanes=N                lanes per row of the MIS-2 aggregation's kernels (1, 2, 4, ... 64; anything else is ignored)
 //   ppr_lanes=N                lanes per row of pagerank_personalized's step (1, 2, 4, ... 64; anything else is ignored)
 // Everything else the library reads from the environment is listed in INTEGRATION.md.
 bool debug_option(const char* key, long long* value = nullptr, char* text = nullptr, size_t text_size = 0);
@@ -235,6 +236,9 @@ int transpose_build(const CSRMatrix* A, TransposeArrays* out, hipStream_t s);
 // levels[1 ..] ints plus one
 std::vector<long long> device_scan_levels(long long n);
 hipError_t device_exclusive_scan(int* data, const std::vector<long long>& levels, int* sums, hipStream_t s);
+// the structure check of reorder.hip (csr_transpose_gpu's rule) for other callers (amg_setup.hip): *d_flag, zeroed by
+// the caller, becomes 1 when A's row pointers or columns are malformed; enqueued on `s`, not waited for
+hipError_t enqueue_structure_check(const CSRMatrix* A, int* d_flag, hipStream_t s);
 // spgemm_csr's accumulator classes (spgemm.hip, spgemm_host.cpp): classes 1 .. kSpgemmClasses - 1 are LDS hash tables
 // of kSpgemmSlots slots (a power of two; a row may fill half of them), the last class is the dense accumulator
 constexpr int kSpgemmClasses = 5;

@@ -28,6 +28,7 @@ namespace reorder {
 
 namespace {
 
+using dev::group_or;
 using dev::kBlock;
 using dev::kMaxResidentBlocks;
 
@@ -40,23 +41,6 @@ struct ColorState {
     int rounds;          // rounds that found something to do
     int num_colors;
 };
-
-template <int CTRL>
-__device__ __forceinline__ unsigned dpp_u(unsigned v) {
-    return static_cast<unsigned>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), CTRL, 0xF, 0xF, true));
-}
-
-// OR over an aligned group of LANES consecutive lanes, every lane gets the result (group_sum's butterfly)
-template <int LANES>
-__device__ __forceinline__ unsigned group_or(unsigned v) {
-    if constexpr (LANES >= 2)  v |= dpp_u<0xB1>(v);
-    if constexpr (LANES >= 4)  v |= dpp_u<0x4E>(v);
-    if constexpr (LANES >= 8)  v |= dpp_u<0x141>(v);
-    if constexpr (LANES >= 16) v |= dpp_u<0x140>(v);
-    if constexpr (LANES >= 32) v |= static_cast<unsigned>(__shfl_xor(static_cast<int>(v), 16, 64));
-    if constexpr (LANES >= 64) v |= static_cast<unsigned>(__shfl_xor(static_cast<int>(v), 32, 64));
-    return v;
-}
 
 __device__ __forceinline__ int wave_max(int v) {
     for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, 64));
@@ -679,6 +663,11 @@ int permute(CSRMatrix* B, const CSRMatrix* A, const int* d_row_perm, const int* 
 } // namespace
 
 } // namespace reorder
+
+hipError_t enqueue_structure_check(const CSRMatrix* A, int* d_flag, hipStream_t s) {
+    return reorder::enqueue_validate(A, d_flag, s);
+}
+
 } // namespace detail
 
 ColorResult csr_color(const CSRMatrix* A, int* d_colors, const ColorConfig* config) {

@@ -128,6 +128,59 @@ int       amg_apply(const AMGHierarchy* H, const float* d_r, float* d_z);
 // Diagonals are taken as they come (a missing one counts as 0).
 int       amg_aggregate_cpu_csr(const CSRMatrix* A_host, float strength, int* aggregate, int* num_aggregates);
 
+// ---- The device-side setup: MIS-2 aggregation (kernels in gpu-spmv_amd/csrc/amg_setup.hip) --------
+// The three passes above depend on visiting the rows in ascending order, so amg_setup runs them on the host.
+// amg_setup_device builds the same kind of hierarchy without the host: every level's diagonal, aggregation and P are
+// made on the device, and only the coarsest level is downloaded (for the Cholesky).  Its aggregation is another rule,
+// parallel but with a sequential definition (amg_aggregate_mis2_cpu_csr), as csr_color has in csr_color_cpu:
+//   Neighbourhoods.  N(i) = the columns of the strong entries of row i (diagonal and strength as above);
+//     N2(i) = (N(i) u the union of N(u) over u in N(i)) \ {i}.  Both are read from A's ROWS only (a pull): on an
+//     unsymmetric strong graph u in N2(v) does not imply v in N2(u).
+//   Priority.  That of i is the pair (fmix32(i ^ seed), i), larger first: csr_color's (spmv/reorder.h).
+//   Roots.  The vertices are visited in descending priority; v is a ROOT iff no u in N2(v) of higher priority is a
+//     ROOT (the lexicographically first distance-2 independent set).  A row without strong neighbours is a root.
+//   Numbers.  The roots are numbered by ascending row index; root r's aggregate carries r's number.
+//   Phase 1.  A non-root with a root in N(i) joins the aggregate of the first such root in storage order (on a
+//     symmetric strong graph there is exactly one).
+//   Phase 2.  A vertex still free joins the aggregate of the column of the strong entry with the largest |v| among
+//     the columns that are roots or phase-1 members (membership as of the end of phase 1), the first in storage
+//     order on a tie.
+//   Free.  A vertex still free after phase 2 (possible only on an unsymmetric strong graph) gets -1 from the two
+//     single-level functions; amg_setup_device returns INVALID_ARGUMENT with bad_level / bad_row = the first such row.
+//   Synchronous round count.  The count of a loop in which every vertex reads the others' states as they stood at
+//     the start of the round: an undecided v becomes OUT if a higher-priority vertex of N2(v) is a ROOT, else ROOT if
+//     every higher-priority vertex of N2(v) is OUT, else it waits; rounds are counted while a vertex is undecided.
+//     The device updates the states in place, sees at least what this loop sees, and never takes more rounds.
+//
+// The definition on HOST arrays: aggregate[num_rows] (-1 = free), *num_aggregates = the number of roots, *rounds (may
+// be null) = the synchronous round count.  Checks as amg_aggregate_cpu_csr, in the same order; nothing is written on
+// failure.
+int       amg_aggregate_mis2_cpu_csr(const CSRMatrix* A_host, float strength, unsigned seed, int* aggregate,
+                                     int* num_aggregates, int* rounds);
+
+// The same ints on DEVICE arrays, on every run, stream and lane count: d_aggregate holds num_rows ints on the device;
+// *rounds (may be null) = the rounds the root selection took, <= the synchronous count.  Runs on the library stream
+// and returns after completion.  Checks, in this order: null A / d_aggregate / num_aggregates -> INVALID_ARGUMENT; not
+// square -> INVALID_DIMENSION; num_rows < 0, nnz < 0 or missing device arrays -> INVALID_FORMAT; strength < 0 or NaN
+// -> INVALID_ARGUMENT; then, on the device and before anything is written, the structure (csr_transpose_gpu's rule)
+// -> INVALID_FORMAT.  SPMV_DEBUG's mis_lanes=N (1, 2, 4, ... 64) forces the lanes that share a row.
+int       amg_aggregate_mis2_gpu(const CSRMatrix* A_dev, float strength, unsigned seed, int* d_aggregate,
+                                 int* num_aggregates, int* rounds);
+
+// amg_setup without the host: the argument checks (those before the aggregates'), stopping rules, coarsest-level
+// solver, workspace and complexities of amg_setup; the aggregation is the MIS-2 rule with `seed`.  Every level is bit
+// for bit what amg_setup gives when handed, as caller-given aggregates, the maps amg_aggregate_mis2_cpu_csr produces
+// level by level.  The hierarchy is an ordinary one: amg_apply, amg_level, cg_solve_amg and amg_destroy work on it
+// unchanged, and amg_update recomputes its diagonals on the device and downloads the coarsest level only.
+// After the checks: a malformed structure -> INVALID_FORMAT; a bad diagonal (the smallest such row) or pivot ->
+// INVALID_ARGUMENT with bad_level / bad_row; a vertex left free -> INVALID_ARGUMENT with bad_level / bad_row.
+AMGResult amg_setup_device(AMGHierarchy** out, const CSRMatrix* A, const AMGConfig* config = nullptr,
+                           unsigned seed = 0);
+
+// The rounds the root selection of level `level` took; 0 for the coarsest level, a hierarchy amg_setup built, a null
+// H or a level outside the hierarchy.
+int       amg_setup_rounds(const AMGHierarchy* H, int level);
+
 } // namespace spmv
 
 #endif

@@ -557,6 +557,19 @@ int spmv_c_amg_level(const spmv_c_amg* H, int level, spmv_c_csr* view, const int
 int spmv_c_amg_apply(const spmv_c_amg* H, const float* d_r, float* d_z);
 /* the aggregation of one level on A's host arrays: aggregate[num_rows], *num_aggregates */
 int spmv_c_amg_aggregate_cpu_csr(const spmv_c_csr* A, float strength, int32_t* aggregate, int32_t* num_aggregates);
+/* the MIS-2 aggregation of one level on A's host arrays, the definition of the device's: aggregate[num_rows] (-1 = a
+ * vertex left free), *num_aggregates, *rounds (may be NULL) = the synchronous round count */
+int spmv_c_amg_aggregate_mis2_cpu_csr(const spmv_c_csr* A, float strength, uint32_t seed, int32_t* aggregate,
+                                      int32_t* num_aggregates, int32_t* rounds);
+/* the same ints on the device: d_aggregate holds num_rows ints on the device; *rounds (may be NULL) = the rounds taken */
+int spmv_c_amg_aggregate_mis2_gpu(const spmv_c_csr* A, float strength, uint32_t seed, int32_t* d_aggregate,
+                                  int32_t* num_aggregates, int32_t* rounds);
+/* amg_setup with every level's diagonal, aggregation (MIS-2 with `seed`) and P made on the device; checks and
+ * arithmetic as amg_setup_device in include/spmv/amg.h.  The return value equals result->error_code. */
+int spmv_c_amg_setup_device(spmv_c_amg** out, const spmv_c_csr* A, const spmv_c_amg_config* config, uint32_t seed,
+                            spmv_c_amg_result* result);
+/* rounds the root selection of level `level` took; 0 on the coarsest level and on a hierarchy spmv_c_amg_setup built */
+int spmv_c_amg_setup_rounds(const spmv_c_amg* H, int level);
 /* CG preconditioned by one V-cycle of H per iteration; config->preconditioner is not read.  Checks and numerics as
  * cg_solve_amg in include/spmv/cg.h. */
 int spmv_c_cg_solve_amg(const spmv_c_csr* A, const spmv_c_amg* H, const float* d_b, float* d_x,

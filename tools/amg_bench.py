@@ -1,12 +1,15 @@
-"""amg_bench.py — time to solution of cg_solve_amg against Jacobi-preconditioned cg_solve, and the cost of amg_setup.
+"""amg_bench.py — time to solution of cg_solve_amg against Jacobi-preconditioned cg_solve, and the cost of amg_setup
+and of amg_setup_device side by side.
 
 Matrices (numpy, gpu-spmv_amd/spd.py): P2D1024, the 5-point 2-D Poisson matrix at 1024^2 (1.05 M rows), and P3D128,
 the 7-point 3-D Poisson matrix at 128^3 (2.1 M rows).  Per matrix: amg_setup (--runs times after --warmup, a fresh
-hierarchy each time; AMGResult.setup_ms and the wall time of the call), then cg_solve with JACOBI and cg_solve_amg
-from x0 = 0 to tolerance 1e-6 with the default engine (-1): --runs solves after --warmup, the wall time of the call
-(setup of the solve, its read-backs and the loop) and the device-event time of the loop, each as the median, and the
-iterations.  Nothing is presumed about the winner: `faster` names whichever solve has the smaller median wall time,
-with and without one setup added to the AMG side.
+hierarchy each time; AMGResult.setup_ms and the wall time of the call), the same for amg_setup_device (seed 0) in the
+same process, with the rounds its root selection took per level; then cg_solve with JACOBI and cg_solve_amg on each of
+the two hierarchies from x0 = 0 to tolerance 1e-6 with the default engine (-1): --runs solves after --warmup, the wall
+time of the call (setup of the solve, its read-backs and the loop) and the device-event time of the loop, each as the
+median, and the iterations.  Nothing is presumed about the winner: `faster` names whichever solve has the smaller
+median wall time, with and without one setup added to the AMG side; `device_over_host_setup` is the ratio of the two
+setups' median wall times.
 
     python tools/amg_bench.py [--matrices P2D1024,P3D128] [--runs 10] [--warmup 2] [--out profiles/amg_bench.json]
 """
@@ -52,28 +55,39 @@ def main() -> int:
         b.copyFromHost(np.random.default_rng(7).uniform(-1.0, 1.0, n).astype(np.float32), n)
         zeros = np.zeros(n, np.float32)
 
-        setup_ms, setup_wall, H, info = [], [], None, None
-        for run in range(args.warmup + args.runs):
-            spmv.amg_destroy(H)
-            t0 = time.perf_counter()
-            info, H = spmv.amg_setup(A)
-            wall = (time.perf_counter() - t0) * 1e3
-            if info.error_code != 0:
-                raise RuntimeError(spmv.spmv_error_string(info.error_code))
-            if run >= args.warmup:
-                setup_ms.append(info.setup_ms)
-                setup_wall.append(wall)
-        sizes = [spmv.amg_level(H, l)[1].num_rows for l in range(info.levels)]
-        entry = {"rows": n, "nnz": int(ci.size),
-                 "amg_setup": {"setup_ms": round(statistics.median(setup_ms), 3),
-                               "wall_ms": round(statistics.median(setup_wall), 3), "levels": info.levels,
-                               "level_rows": sizes, "coarse_solver": info.coarse_solver,
-                               "grid_complexity": round(info.grid_complexity, 4),
-                               "operator_complexity": round(info.operator_complexity, 4)}}
+        def time_setup(build):
+            """(the entry, the last hierarchy): --runs builds after --warmup, a fresh hierarchy each time"""
+            setup_ms, setup_wall, H, info = [], [], None, None
+            for run in range(args.warmup + args.runs):
+                spmv.amg_destroy(H)
+                spmv.device_synchronize()
+                t0 = time.perf_counter()
+                info, H = build()
+                wall = (time.perf_counter() - t0) * 1e3
+                if info.error_code != 0:
+                    raise RuntimeError(spmv.spmv_error_string(info.error_code))
+                if run >= args.warmup:
+                    setup_ms.append(info.setup_ms)
+                    setup_wall.append(wall)
+            sizes = [spmv.amg_level(H, l)[1].num_rows for l in range(info.levels)]
+            return {"setup_ms": round(statistics.median(setup_ms), 3),
+                    "wall_ms": round(statistics.median(setup_wall), 3),
+                    "wall_ms_min_max": [round(min(setup_wall), 3), round(max(setup_wall), 3)], "levels": info.levels,
+                    "level_rows": sizes, "coarse_solver": info.coarse_solver,
+                    "grid_complexity": round(info.grid_complexity, 4),
+                    "operator_complexity": round(info.operator_complexity, 4)}, H
+
+        entry = {"rows": n, "nnz": int(ci.size)}
+        entry["amg_setup"], H = time_setup(lambda: spmv.amg_setup(A))
+        entry["amg_setup_device"], HD = time_setup(lambda: spmv.amg_setup_device(A, None, 0))
+        entry["amg_setup_device"]["rounds"] = [spmv.amg_setup_rounds(HD, l)
+                                               for l in range(entry["amg_setup_device"]["levels"])]
+        entry["device_over_host_setup"] = round(entry["amg_setup_device"]["wall_ms"] / entry["amg_setup"]["wall_ms"], 3)
 
         cfg = spmv.CGConfig(tolerance=args.tolerance, max_iterations=100000, preconditioner=1, engine=-1)
         solvers = {"cg_solve_jacobi": lambda: spmv.cg_solve(A, b, x, cfg),
-                   "cg_solve_amg": lambda: spmv.cg_solve_amg(A, H, b, x, cfg)}
+                   "cg_solve_amg": lambda: spmv.cg_solve_amg(A, H, b, x, cfg),
+                   "cg_solve_amg_device_setup": lambda: spmv.cg_solve_amg(A, HD, b, x, cfg)}
         for label, solve in solvers.items():
             wall, loop, res = [], [], None
             for run in range(args.warmup + args.runs):
@@ -96,8 +110,12 @@ def main() -> int:
         with_setup = amg + entry["amg_setup"]["wall_ms"]
         entry["faster_with_one_setup"] = "cg_solve_amg" if with_setup < jacobi else "cg_solve_jacobi"
         entry["jacobi_over_amg_wall"] = round(jacobi / amg, 3)
+        amg_device = entry["cg_solve_amg_device_setup"]["wall_ms"]
+        with_device_setup = amg_device + entry["amg_setup_device"]["wall_ms"]
+        entry["faster_with_one_device_setup"] = "cg_solve_amg" if with_device_setup < jacobi else "cg_solve_jacobi"
         result["matrices"][name] = entry
         spmv.amg_destroy(H)
+        spmv.amg_destroy(HD)
         for buf in (b, x):
             buf.release()
         spmv.csr_destroy(A)
