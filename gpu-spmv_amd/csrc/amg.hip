@@ -185,13 +185,7 @@ struct Cycle {
 
 } // namespace
 
-int amg_forced_lanes() {
-    long long forced = 0;
-    if (debug_option("amg_lanes", &forced) && forced >= 1 && forced <= 64 && (forced & (forced - 1)) == 0) {
-        return static_cast<int>(forced);
-    }
-    return 0;
-}
+int amg_forced_lanes() { return forced_lanes("amg_lanes"); }
 
 hipError_t amg_vcycle(const AMGHierarchy& H, const float* d_r, float* d_z, const int* d_done, int forced_lanes,
                       hipStream_t s) {

@@ -32,6 +32,7 @@ namespace detail {
 
 namespace {
 
+using dev::block_min;
 using dev::group_or;
 using dev::kBlock;
 using reorder::higher_priority;
@@ -47,18 +48,6 @@ struct Mis2State {
     int bad_row;         // the smallest row with a bad diagonal, or INT_MAX
     int free_row;        // the smallest row left without an aggregate, or INT_MAX
 };
-
-// min over the workgroup, valid in thread 0
-__device__ __forceinline__ int block_min(int v) {
-    __shared__ int s_min[kBlock / 64];
-    for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, 64));
-    if ((threadIdx.x & 63) == 0) s_min[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kBlock / 64; ++w) v = min(v, s_min[w]);
-    }
-    return v;
-}
 
 // min over an aligned group of LANES consecutive lanes, every lane gets the result
 template <int LANES>
@@ -288,10 +277,7 @@ __global__ __launch_bounds__(kBlock) void amg_prolongation_kernel(int n, int* __
 }
 
 int mis_lanes_for(const CSRMatrix& M) {
-    long long forced = 0;
-    if (debug_option("mis_lanes", &forced) && forced >= 1 && forced <= 64 && (forced & (forced - 1)) == 0) {
-        return static_cast<int>(forced);
-    }
+    if (int f = forced_lanes("mis_lanes")) return f;
     return pick_lanes_per_row(static_cast<float>(M.nnz) / static_cast<float>(std::max(M.num_rows, 1)));
 }
 

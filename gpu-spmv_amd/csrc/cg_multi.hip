@@ -27,7 +27,8 @@
 // for a frozen column.  A frozen column's Z is never read: cgm_rz_kernel and cgm_direction_kernel skip it.
 //
 // The host side is built from solver_common.h's parts (Workspace and its mirror, TriangularPair, diag_kernel) and
-// multi_window.h's with_window; there is no tiled engine here.
+// multi_window.h's with_window; the k-wide row sum and workgroup reductions are multi_window.h's too.  There is no
+// tiled engine here.
 #include "internal.h"
 #include "device_common.h"
 #include "multi_window.h"
@@ -73,82 +74,6 @@ struct CgMultiState {
 };
 
 constexpr size_t kHeaderBytes = offsetof(CgMultiState, col);
-
-// block_sum2's sum of N values at once behind two barriers in all: the same xor butterfly inside each wavefront,
-// then the wavefronts' totals added in wave order, so thread c (< N) returns for v[c] the very bits block_sum2 leaves
-// in thread 0.  Other threads return 0.
-template <int N>
-__device__ __forceinline__ double block_sum_columns(double (&v)[N]) {
-    static_assert(N <= kBlock, "one thread per value");
-    __shared__ double s_wave[kBlock / 64][N];
-#pragma unroll
-    for (int c = 0; c < N; ++c) {
-        for (int off = 32; off > 0; off >>= 1) v[c] += __shfl_xor(v[c], off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int c = 0; c < N; ++c) s_wave[threadIdx.x >> 6][c] = v[c];
-    }
-    __syncthreads();
-    double total = 0.0;
-    if (threadIdx.x < N) {
-        total = s_wave[0][threadIdx.x];
-        for (int w = 1; w < kBlock / 64; ++w) total += s_wave[w][threadIdx.x];
-    }
-    __syncthreads();
-    return total;
-}
-
-// fold_partials' second half for N values at once: v[c] holds this thread's strided sum (i = threadIdx.x,
-// threadIdx.x + 256, ... in that order, as fold_partials adds them); the same butterfly and wave order as block_sum2,
-// and every thread leaves with the total.  Two barriers for N values where fold_partials takes four for a pair.
-template <int N>
-__device__ __forceinline__ void fold_values(double (&v)[N]) {
-    __shared__ double s_wave[kBlock / 64][N];
-#pragma unroll
-    for (int c = 0; c < N; ++c) {
-        for (int off = 32; off > 0; off >>= 1) v[c] += __shfl_xor(v[c], off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int c = 0; c < N; ++c) s_wave[threadIdx.x >> 6][c] = v[c];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < N; ++c) {
-        v[c] = s_wave[0][c];
-        for (int w = 1; w < kBlock / 64; ++w) v[c] += s_wave[w][c];
-    }
-    __syncthreads();
-}
-
-// row_partial_dot<LANES> with W accumulators: the same walk (start, stride, load4, select-masked neighbours) and,
-// per column, the same fmaf chain; every entry's slice V[c, j0 : j0 + W] is loaded once.  OWN: V is one of the
-// solver's own arrays (load_own; limit and vec are not read).
-template <int LANES, int W, bool OWN>
-__device__ __forceinline__ void row_partial_dot_multi(int begin, int end, int lane, long long nnz,
-                                                      const int* __restrict__ cols, const float* __restrict__ vals,
-                                                      const float* __restrict__ V, long long ld, int j0, int limit,
-                                                      bool vec, float (&acc)[W]) {
-    for (long long j = (begin & ~3) + lane * 4; j < end; j += LANES * 4) {
-        i32x4 c;
-        f32x4 v;
-        load4(cols, vals, j, nnz, c, v);
-        bool mine[4];
-        float xv[4][W];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            mine[e] = j + e >= begin && j + e < end;
-            if constexpr (OWN) load_own<W>(V, ld, mine[e] ? c[e] : 0, j0, xv[e]);
-            else load_window<W>(V, ld, mine[e] ? c[e] : 0, j0, limit, vec, xv[e]);
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-#pragma unroll
-            for (int q = 0; q < W; ++q) acc[q] = mine[e] ? __builtin_fmaf(v[e], xv[e][q], acc[q]) : acc[q];
-        }
-    }
-}
 
 // R0 = B - A X0, P0 = Z0 = R0 * dinv, and per column the block partials of r.z, r.r and b.b ->
 // part[(3 * gridDim.x) * column + 3 * block].  A window of W columns of B and X at a time (setup: the matrix is
@@ -317,6 +242,8 @@ void cgm_spmv_dot(int n, long long nnz, const int* __restrict__ row_ptrs, const 
 #pragma unroll
                     for (int c = 0; c < W; ++c) pq[wi * W + c] += prod64(pv[c], acc[c]);
                     // (a frozen column inside a running window is computed along: its q and its sum are never read)
+                    // (store_own's W / 4 stores written out: through the helper, the NW = 2 instantiations come out
+                    // 60 to 72 bytes longer with the same registers)
 #pragma unroll
                     for (int g = 0; g < W; g += 4) {
                         const f32x4 v = {acc[g], acc[g + 1], acc[g + 2], acc[g + 3]};

@@ -1,9 +1,12 @@
-// device_common.h — device-side building blocks shared by kernels.hip,
-// pagerank.hip and the tiled engine (gfx950, wave64).
+// device_common.h — device-side building blocks shared by the kernel files
+// (gfx950, wave64): cross-lane and workgroup reductions, the vector-CSR row
+// walk, the binary searches, and the host's capped grid size.
 #ifndef SPMV_AMD_DEVICE_COMMON_H
 #define SPMV_AMD_DEVICE_COMMON_H
 
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
 
 namespace spmv {
 namespace detail {
@@ -141,6 +144,59 @@ __device__ __forceinline__ void block_sum2(double& a, double& b) {
         }
     }
     __syncthreads();
+}
+
+// Integer reduction over the workgroup by op (min, max: associative and commutative, so the order does not show):
+// the xor butterfly inside each wavefront, one LDS word per wavefront, and thread 0 folds the other wavefronts' words
+// into its own.  The result is valid in thread 0 ONLY, and there is no second barrier: two calls in one kernel need a
+// __syncthreads() between them, or the second call's LDS stores race with thread 0's loads of the first.
+template <class Op>
+__device__ __forceinline__ int block_reduce_int(int v, Op op) {
+    __shared__ int s_wave[kBlock / 64];
+    for (int off = 32; off > 0; off >>= 1) v = op(v, __shfl_xor(v, off, 64));
+    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kBlock / 64; ++w) v = op(v, s_wave[w]);
+    }
+    return v;
+}
+__device__ __forceinline__ int block_min(int v) {
+    return block_reduce_int(v, [](int a, int b) { return min(a, b); });
+}
+__device__ __forceinline__ int block_max(int v) {
+    return block_reduce_int(v, [](int a, int b) { return max(a, b); });
+}
+
+// ---------------------------------------------------------------------------
+// binary searches in sorted int arrays
+// ---------------------------------------------------------------------------
+// position of column `want` in cols[lo, hi) (strictly ascending), or -1
+__device__ __forceinline__ int find_column(const int* __restrict__ cols, int lo, int hi, int want) {
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        const int c = cols[mid];
+        if (c == want) return mid;
+        if (c < want) lo = mid + 1;
+        else hi = mid;
+    }
+    return -1;
+}
+
+// first index j in [lo, hi) with rp[j] > p (hi when there is none)
+__device__ __forceinline__ int upper_bound(const int* __restrict__ rp, int lo, int hi, long long p) {
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (rp[mid] > p) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+// host side: workgroups for work_items at per_block each, at least one and at most what the chip holds at once (the
+// kernels stride over the rest)
+inline int capped_grid(long long work_items, int per_block) {
+    const long long blocks = (work_items + per_block - 1) / per_block;
+    return static_cast<int>(std::max(1LL, std::min<long long>(blocks, kMaxResidentBlocks)));
 }
 
 } // namespace dev

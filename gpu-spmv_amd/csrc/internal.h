@@ -204,6 +204,15 @@ inline long long debug_number(const char* key, long long fallback) {
     return debug_option(key, &v) ? v : fallback;
 }
 bool debug_is(const char* key, const char* expected);
+// the value of one of the "..._lanes" keys where it names a lane count (1, 2, 4, ... 64); 0 where the key is absent
+// or holds anything else, and the caller makes its own pick
+inline int forced_lanes(const char* key) {
+    long long forced = 0;
+    if (debug_option(key, &forced) && forced >= 1 && forced <= 64 && (forced & (forced - 1)) == 0) {
+        return static_cast<int>(forced);
+    }
+    return 0;
+}
 
 // ---- launch layer (kernels.hip) ----
 // All return hipError_t from the launch; none synchronise.
@@ -267,23 +276,22 @@ hipError_t launch_sptrsv_multi(const SptrsvSchedule& schedule, const CSRMatrix* 
                                int uplo, int unit_diagonal, bool ordered, int lanes_per_row, hipStream_t s);
 // b and x overlap without being the same array (solver_common.h ranges_overlap; the solve in place is allowed)
 bool sptrsv_partial_overlap(const float* d_b, const float* d_x, long long n);
-// the schedule cache of sptrsv_host.cpp for the callers that solve or factor with it (ilu0_host.cpp, bicgstab.hip):
+// the schedule cache of sptrsv_host.cpp for the callers that solve or factor with it (factor0_host.cpp, bicgstab.hip):
 // checks 2-4 of sptrsv.h (not square, no rows, missing device arrays); A's `uplo` schedule, built and cached when it
 // is not there (*analysis_ms = the host time of a build, 0 for a cache hit); the lanes per row of an ordered = 0 solve
 int sptrsv_check_matrix(const CSRMatrix* A, bool* nothing_to_do);
 int sptrsv_schedule_for(const CSRMatrix* A, int uplo, hipStream_t stream, std::shared_ptr<const SptrsvSchedule>* out,
                         float* analysis_ms);
 int sptrsv_lanes_for(const SptrsvSchedule& schedule);
-// ILU(0) factorisation (ilu0.hip): the launches of one factorisation over A's LOWER schedule, in stream order, from
-// d_a (A's values) into d_lu (may be the same array); then, when d_zero_pivot is not null, the scan of the finished
-// diagonal that folds the lowest row with a zero or non-finite pivot into it (an unsigned min; preset to all ones)
-hipError_t launch_ilu0(const SptrsvSchedule& schedule, const CSRMatrix* A, const float* d_a, float* d_lu,
-                       int lanes_per_row, unsigned* d_zero_pivot, hipStream_t s);
-// IC(0) factorisation (ic0.hip): as launch_ilu0, from the lower triangle and diagonal of d_a into d_l (L on and left
-// of the diagonal, L^T right of it; may be the same array); the scan folds the lowest row whose l_ii is not > 0 or
-// not finite into d_bad_pivot
-hipError_t launch_ic0(const SptrsvSchedule& schedule, const CSRMatrix* A, const float* d_a, float* d_l,
-                      int lanes_per_row, unsigned* d_bad_pivot, hipStream_t s);
+// The zero-fill factorisations (factor0.hip): the launches of one factorisation over A's LOWER schedule, in stream
+// order, from d_a (A's values) into d_out (may be the same array); then, when d_pivot is not null, the scan of the
+// finished diagonal that folds the lowest row with a bad pivot into it (an unsigned min; preset to all ones).
+//   ILU0  the whole row: L left of the diagonal, U on and right of it; a bad pivot is zero or not finite
+//   IC0   from the lower triangle and diagonal of d_a: L on and left of the diagonal, L^T right of it; a bad pivot is
+//         not > 0 or not finite
+enum class Factor0Kind { ILU0, IC0 };
+hipError_t launch_factor0(Factor0Kind kind, const SptrsvSchedule& schedule, const CSRMatrix* A, const float* d_a,
+                          float* d_out, int lanes_per_row, unsigned* d_pivot, hipStream_t s);
 // A row of the square, valid CSR pattern (rows strictly ascending, every diagonal stored) that holds one side only of
 // some pair (i,k) / (k,i), or -1 when the pattern is structurally symmetric.  One pass: row k's upper entries must be
 // met in their stored order as the rows below it are walked downwards.

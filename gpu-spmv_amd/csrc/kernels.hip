@@ -452,11 +452,6 @@ void ell_from_csr_kernel(int num_rows, int width, const int* __restrict__ row_pt
     }
 }
 
-inline int capped_grid(long long work_items, int per_block) {
-    const long long blocks = (work_items + per_block - 1) / per_block;
-    return static_cast<int>(std::max(1LL, std::min<long long>(blocks, kMaxResidentBlocks)));
-}
-
 template <int LANES>
 hipError_t launch_vector(const CSRMatrix* A, const float* d_x, float* d_y, hipStream_t s) {
     const int grid = capped_grid(A->num_rows, kBlock / LANES);

@@ -65,100 +65,6 @@ struct PprState {
 
 constexpr size_t kHeaderBytes = offsetof(PprState, col);
 
-// One row of one of the loop's own windows (num_rows x W, 16-byte aligned): W / 4 unconditional dwordx4 loads.
-template <int W>
-__device__ __forceinline__ void load_own(const float* __restrict__ window, long long row, float (&out)[W]) {
-    const float* p = window + row * W;
-#pragma unroll
-    for (int g = 0; g < W; g += 4) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(p + g);
-        out[g] = v[0]; out[g + 1] = v[1]; out[g + 2] = v[2]; out[g + 3] = v[3];
-    }
-}
-
-template <int W>
-__device__ __forceinline__ void store_own(float* __restrict__ window, long long row, const float (&in)[W]) {
-    float* p = window + row * W;
-#pragma unroll
-    for (int g = 0; g < W; g += 4) {
-        const f32x4 v = {in[g], in[g + 1], in[g + 2], in[g + 3]};
-        *reinterpret_cast<f32x4*>(p + g) = v;
-    }
-}
-
-// block_sum2's sum of N values at once behind two barriers (cg_multi.hip's block_sum_columns): the same xor
-// butterfly inside each wavefront, then the wavefronts' totals added in wave order, so thread c (< N) returns for
-// v[c] the very bits block_sum2 leaves in thread 0.  Other threads return 0.
-template <int N>
-__device__ __forceinline__ double block_sum_columns(double (&v)[N]) {
-    static_assert(N <= kBlock, "one thread per value");
-    __shared__ double s_wave[kBlock / 64][N];
-#pragma unroll
-    for (int c = 0; c < N; ++c) {
-        for (int off = 32; off > 0; off >>= 1) v[c] += __shfl_xor(v[c], off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int c = 0; c < N; ++c) s_wave[threadIdx.x >> 6][c] = v[c];
-    }
-    __syncthreads();
-    double total = 0.0;
-    if (threadIdx.x < N) {
-        total = s_wave[0][threadIdx.x];
-        for (int w = 1; w < kBlock / 64; ++w) total += s_wave[w][threadIdx.x];
-    }
-    __syncthreads();
-    return total;
-}
-
-// pr_fold_and_commit's fold for N values at once: v[c] holds this thread's strided sum (i = threadIdx.x,
-// threadIdx.x + 256, ... in that order); block_sum2's butterfly and wave order; every thread leaves with the totals.
-template <int N>
-__device__ __forceinline__ void fold_values(double (&v)[N]) {
-    __shared__ double s_wave[kBlock / 64][N];
-#pragma unroll
-    for (int c = 0; c < N; ++c) {
-        for (int off = 32; off > 0; off >>= 1) v[c] += __shfl_xor(v[c], off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int c = 0; c < N; ++c) s_wave[threadIdx.x >> 6][c] = v[c];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < N; ++c) {
-        v[c] = s_wave[0][c];
-        for (int w = 1; w < kBlock / 64; ++w) v[c] += s_wave[w][c];
-    }
-    __syncthreads();
-}
-
-// row_partial_dot<LANES> with W accumulators on one window of the rank array: the same walk (start, stride, load4,
-// select-masked neighbours) and, per column, the same fmaf chain; every entry's slice window[c, 0 : W] is W / 4
-// 16-byte loads.
-template <int LANES, int W>
-__device__ __forceinline__ void row_partial_dot_multi(int begin, int end, int lane, long long nnz,
-                                                      const int* __restrict__ cols, const float* __restrict__ vals,
-                                                      const float* __restrict__ window, float (&acc)[W]) {
-    for (long long j = (begin & ~3) + lane * 4; j < end; j += LANES * 4) {
-        i32x4 c;
-        f32x4 v;
-        load4(cols, vals, j, nnz, c, v);
-        bool mine[4];
-        float xv[4][W];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            mine[e] = j + e >= begin && j + e < end;
-            load_own<W>(window, mine[e] ? c[e] : 0, xv[e]);
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-#pragma unroll
-            for (int q = 0; q < W; ++q) acc[q] = mine[e] ? __builtin_fmaf(v[e], xv[e][q], acc[q]) : acc[q];
-        }
-    }
-}
-
 // Setup, a thread per row of V: refuses negative and non-finite entries (bit j of state->bad_entries), copies V into
 // the loop's windows (vw, and r0 = the start vector; padding columns 0) and leaves per column the block partials of
 // the column sum and of its dangling mass -> part[(2 * gridDim.x) * column + 2 * block].
@@ -279,13 +185,15 @@ void ppr_step_kernel(int n, long long nnz, const int* __restrict__ row_ptrs, con
             float acc[W];
 #pragma unroll
             for (int c = 0; c < W; ++c) acc[c] = 0.0f;
-            if (row < n) row_partial_dot_multi<LANES, W>(begin, end, lane, nnz, cols, vals, old_w, acc);
+            if (row < n) {
+                row_partial_dot_multi<LANES, W, true>(begin, end, lane, nnz, cols, vals, old_w, W, 0, 0, true, acc);
+            }
 #pragma unroll
             for (int c = 0; c < W; ++c) acc[c] = group_sum<LANES>(acc[c]);
             if (lane == 0 && row < n) {
                 float v[W], old[W], fresh[W];
-                load_own<W>(vw + wi * window, row, v);
-                load_own<W>(old_w, row, old);
+                load_own<W>(vw + wi * window, W, row, 0, v);
+                load_own<W>(old_w, W, row, 0, old);
                 const bool dang = dangling[row] != 0;
 #pragma unroll
                 for (int c = 0; c < W; ++c) {
@@ -369,8 +277,8 @@ __device__ __forceinline__ void load_committed(const float* __restrict__ r0, con
                                                long long window_offset, long long row, unsigned parity,
                                                float (&out)[W]) {
     float a[W], b[W];
-    load_own<W>(r0 + window_offset, row, a);
-    load_own<W>(r1 + window_offset, row, b);
+    load_own<W>(r0 + window_offset, W, row, 0, a);
+    load_own<W>(r1 + window_offset, W, row, 0, b);
 #pragma unroll
     for (int c = 0; c < W; ++c) out[c] = (parity >> c) & 1u ? b[c] : a[c];
 }
@@ -514,10 +422,7 @@ bool dangling_mask(const CSRMatrix* A, unsigned char* d_mask, hipStream_t stream
 }
 
 int ppr_lanes_for(const CSRMatrix* A) {
-    long long forced = 0;
-    if (debug_option("ppr_lanes", &forced) && forced >= 1 && forced <= 64 && (forced & (forced - 1)) == 0) {
-        return static_cast<int>(forced);
-    }
+    if (int f = forced_lanes("ppr_lanes")) return f;
     return pick_lanes_per_row(static_cast<float>(A->nnz) / A->num_rows);
 }
 

@@ -28,6 +28,7 @@ namespace reorder {
 
 namespace {
 
+using dev::block_max;
 using dev::group_or;
 using dev::kBlock;
 using dev::kMaxResidentBlocks;
@@ -41,23 +42,6 @@ struct ColorState {
     int rounds;          // rounds that found something to do
     int num_colors;
 };
-
-__device__ __forceinline__ int wave_max(int v) {
-    for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
-// max over the workgroup, valid in thread 0
-__device__ __forceinline__ int block_max(int v) {
-    __shared__ int s_max[kBlock / 64];
-    v = wave_max(v);
-    if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kBlock / 64; ++w) v = max(v, s_max[w]);
-    }
-    return v;
-}
 
 // ---- structure: csr_transpose_gpu's rule; every writer stores the same 1 ----
 __global__ __launch_bounds__(kBlock) void reorder_validate_kernel(const int* __restrict__ rp, const int* __restrict__ ci,

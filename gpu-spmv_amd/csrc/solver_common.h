@@ -93,10 +93,7 @@ void diag_kernel(int n, const int* __restrict__ row_ptrs, const int* __restrict_
     if (__any(bad) && (threadIdx.x & 63) == 0) *bad_flag = 1;
 }
 
-inline int grid_for_rows(long long rows, int rows_per_block) {
-    const long long blocks = (rows + rows_per_block - 1) / rows_per_block;
-    return static_cast<int>(std::max(1LL, std::min<long long>(blocks, kMaxResidentBlocks)));
-}
+inline int grid_for_rows(long long rows, int rows_per_block) { return dev::capped_grid(rows, rows_per_block); }
 
 inline int vec_grid(long long n) {
     return static_cast<int>(std::max(1LL, std::min<long long>((n + kBlock - 1) / kBlock, kVecBlocks)));

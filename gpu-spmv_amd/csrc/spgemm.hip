@@ -26,6 +26,8 @@ namespace detail {
 
 namespace {
 
+using dev::upper_bound;
+
 constexpr int kThreads = 256;
 constexpr int kMaxGrid = 4096;                // workgroups of any launch here; one flag each
 constexpr int kSegments = kSpgemmClasses + 1; // class 0 (rows without products) .. the dense class
@@ -54,15 +56,6 @@ struct MatView {
     long long nnz;
     int ascending;    // columns strictly ascending inside each row
 };
-
-// first index j in [lo, hi) with rp[j] > p (hi when there is none)
-__device__ __forceinline__ int upper_bound(const int* __restrict__ rp, int lo, int hi, long long p) {
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (rp[mid] > p) hi = mid; else lo = mid + 1;
-    }
-    return lo;
-}
 
 __device__ bool matrix_bad(const MatView& M, long long first, long long stride) {
     bool bad = false;
@@ -517,10 +510,7 @@ MatView view_of(const CSRMatrix* M, int limit, bool ascending) {
 }
 
 int lanes_for(const CSRMatrix* B) {
-    long long forced = 0;
-    if (debug_option("spgemm_lanes", &forced) && forced >= 1 && forced <= 64 && (forced & (forced - 1)) == 0) {
-        return static_cast<int>(forced);
-    }
+    if (int f = forced_lanes("spgemm_lanes")) return f;
     return pick_lanes_per_row(static_cast<float>(B->nnz) / static_cast<float>(std::max(B->num_rows, 1)));
 }
 

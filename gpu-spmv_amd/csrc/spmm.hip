@@ -345,11 +345,6 @@ void csr_multi_zero_kernel(int num_rows, int k, float* __restrict__ Y, long long
     }
 }
 
-inline int capped_grid(long long work_items, int per_block) {
-    const long long blocks = (work_items + per_block - 1) / per_block;
-    return static_cast<int>(std::max(1LL, std::min<long long>(blocks, kMaxResidentBlocks)));
-}
-
 inline bool vec_ok(const float* X, int ldx) {
     return ldx % 4 == 0 && (reinterpret_cast<unsigned long long>(X) & 15) == 0;
 }

@@ -312,10 +312,7 @@ int check_matrix(const CSRMatrix* A, bool* nothing_to_do) {
 
 int lanes_for(const SptrsvSchedule& s, bool ordered) {
     if (ordered) return 1;
-    long long forced = 0;
-    if (debug_option("sptrsv_lanes", &forced) && forced >= 1 && forced <= 64 && (forced & (forced - 1)) == 0) {
-        return static_cast<int>(forced);
-    }
+    if (int f = forced_lanes("sptrsv_lanes")) return f;
     return pick_lanes_per_row(static_cast<float>(s.triangle_nnz) / static_cast<float>(s.num_rows));
 }
 

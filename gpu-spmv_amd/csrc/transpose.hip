@@ -23,6 +23,8 @@ namespace detail {
 
 namespace {
 
+using dev::upper_bound;
+
 constexpr int kThreads = 256;                 // 4 wavefronts per workgroup
 constexpr int kRounds = 16;                   // rounds of 256 entries per tile
 constexpr int kTile = kThreads * kRounds;     // 4096 entries per tile
@@ -88,15 +90,6 @@ __global__ __launch_bounds__(kThreads) void transpose_validate_kernel(const int*
         partial[2 * blockIdx.x] = b;
         partial[2 * blockIdx.x + 1] = static_cast<int>(d);
     }
-}
-
-// first index j in [lo, hi) with rp[j] > p (hi when there is none)
-__device__ __forceinline__ int upper_bound(const int* __restrict__ rp, int lo, int hi, long long p) {
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (rp[mid] > p) hi = mid; else lo = mid + 1;
-    }
-    return lo;
 }
 
 // row_of[p] = the row that holds entry p (row_ptrs validated: rp[0] == 0, non-decreasing, rp[rows] == nnz)

@@ -2,8 +2,8 @@
 //
 // A ~ L L^T on the pattern of A's lower triangle: L lower triangular with its diagonal stored.  The rows depend on
 // each other exactly as the rows of a LOWER triangular solve do, so the factorisation runs over the level schedule
-// sptrsv_csr keeps with the matrix (spmv/sptrsv.h; kernels in gpu-spmv_amd/csrc/ic0.hip).  The factor
-// feeds sptrsv_csr (LOWER NON_UNIT, then UPPER NON_UNIT) and cg_solve_ic (spmv/cg.h).
+// sptrsv_csr keeps with the matrix (spmv/sptrsv.h; kernels in gpu-spmv_amd/csrc/factor0.hip).  The
+// factor feeds sptrsv_csr (LOWER NON_UNIT, then UPPER NON_UNIT) and cg_solve_ic (spmv/cg.h).
 #ifndef SPMV_IC0_H
 #define SPMV_IC0_H
 

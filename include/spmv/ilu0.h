@@ -3,7 +3,7 @@
 // A ~ L U on A's own sparsity pattern: L unit lower triangular, U upper triangular, both kept in one value array laid
 // out like A's.  The rows depend on each other exactly as the rows of a LOWER triangular solve do, so the
 // factorisation runs over the level schedule sptrsv_csr keeps with the matrix (spmv/sptrsv.h; kernels in
-// gpu-spmv_amd/csrc/ilu0.hip).  The factor feeds sptrsv_csr (LOWER UNIT, then UPPER NON_UNIT) and
+// gpu-spmv_amd/csrc/factor0.hip).  The factor feeds sptrsv_csr (LOWER UNIT, then UPPER NON_UNIT) and
 // bicgstab_solve_lu (spmv/bicgstab.h).
 #ifndef SPMV_ILU0_H
 #define SPMV_ILU0_H

@@ -1,4 +1,4 @@
-// ic0_cpu_csr (include/spmv/ic0.h) under AddressSanitizer + UndefinedBehaviorSanitizer: csrc/ic0_host.cpp is compiled
+// ic0_cpu_csr (include/spmv/ic0.h) under AddressSanitizer + UndefinedBehaviorSanitizer: csrc/factor0_host.cpp is compiled
 // into this executable with the sanitizers (make -C gpu-spmv_amd sanitize-ic0), every array below is a heap
 // allocation of exactly its size, and the rejected inputs are the ones that would walk off an array if a check came
 // too late.  Run by tests/test_ic0_host.py; needs no GPU.

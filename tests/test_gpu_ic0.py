@@ -121,6 +121,32 @@ def test_device_factor_equals_the_cpu_bit_for_bit_at_every_lane_count(gpu, monke
         gpu.csr_destroy(A)
 
 
+def test_a_forced_lane_count_that_is_no_lane_count_is_ignored(gpu, monkeypatch):
+    """SPMV_DEBUG=ic0_lanes=v with v outside 1, 2, 4, ... 64 changes nothing: the library's own pick, the CPU's bits."""
+    n, rp, ci, va = spd.poisson2d(8)
+    assert n == 64
+    A = _upload(gpu, n, rp, ci, va)
+    want, _ = gpu.ic0_cpu_csr(A)
+    try:
+        monkeypatch.delenv("SPMV_DEBUG", raising=False)
+        own, got = _factor(gpu, A, va, False)
+        assert own.error_code == 0 and own.lanes_per_row in LANES
+        np.testing.assert_array_equal(_bits(got), _bits(want))
+        for value in (0, 3, 128, -4):
+            monkeypatch.setenv("SPMV_DEBUG", f"ic0_lanes={value}")
+            res, got = _factor(gpu, A, va, False)
+            assert res.error_code == 0 and res.lanes_per_row == own.lanes_per_row, value
+            np.testing.assert_array_equal(_bits(got), _bits(want), err_msg=str(value))
+        for lanes in (1, 64):                    # the ends of the range are taken
+            monkeypatch.setenv("SPMV_DEBUG", f"ic0_lanes={lanes}")
+            res, got = _factor(gpu, A, va, False)
+            assert res.error_code == 0 and res.lanes_per_row == lanes
+            np.testing.assert_array_equal(_bits(got), _bits(want))
+    finally:
+        monkeypatch.delenv("SPMV_DEBUG", raising=False)
+        gpu.csr_destroy(A)
+
+
 def test_schedule_cache_the_async_entry_and_an_output_view(gpu):
     import torch
     n, rp, ci, va = spd.poisson3d(12)

@@ -270,7 +270,7 @@ def test_cg_solve_ic_checks_before_any_device_work(spmv):
 
 # ---- the sanitized caller ------------------------------------------------------------------------------------
 def test_ic0_cpu_csr_is_clean_under_asan_and_ubsan():
-    """make -C gpu-spmv_amd sanitize-ic0 builds tests/cpp/bin/ic0_host_sanitized (csrc/ic0_host.cpp and
+    """make -C gpu-spmv_amd sanitize-ic0 builds tests/cpp/bin/ic0_host_sanitized (csrc/factor0_host.cpp and
     tests/cpp/ic0_host_sanitized.cpp under AddressSanitizer + UBSan); any sanitizer report aborts it."""
     built = subprocess.run(["make", "-C", os.path.join(ROOT, "gpu-spmv_amd"), "sanitize-ic0"], capture_output=True,
                            text=True)
