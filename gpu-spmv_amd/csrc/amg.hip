@@ -44,17 +44,9 @@ void amg_sweep_kernel(int n, long long nnz, const int* __restrict__ row_ptrs, co
                       const float* __restrict__ vals, const float* __restrict__ wd, const float* __restrict__ f,
                       const float* __restrict__ x_in, float* __restrict__ x_out, const int* __restrict__ done) {
     if (finished(done)) return;
-    constexpr int kRowsPerBlock = kBlock / LANES;
-    const int lane = threadIdx.x % LANES;
-    const int slot = threadIdx.x / LANES;
-    for (long long first = static_cast<long long>(blockIdx.x) * kRowsPerBlock; first < n;
-         first += static_cast<long long>(gridDim.x) * kRowsPerBlock) {
-        const long long row = first + slot;
-        float acc = 0.0f;
-        if (row < n) acc = row_partial_dot<LANES>(row_ptrs[row], row_ptrs[row + 1], lane, nnz, cols, vals, x_in);
-        acc = group_sum<LANES>(acc);
-        if (lane == 0 && row < n) x_out[row] = __builtin_fmaf(wd[row], __fsub_rn(f[row], acc), x_in[row]);
-    }
+    for_each_row_dot<LANES>(n, nnz, row_ptrs, cols, vals, x_in, [&](long long row, float acc) {
+        x_out[row] = __builtin_fmaf(wd[row], __fsub_rn(f[row], acc), x_in[row]);
+    });
 }
 
 // f_coarse[a] = sum over the members i of aggregate a (member_ptr / members: the structure of P^T, rows ascending) of
@@ -143,7 +135,7 @@ struct Cycle {
         const CSRMatrix& M = lv.view;
         return with_lanes(lanes, [&](auto L) {
             constexpr int kLanes = decltype(L)::value;
-            amg_sweep_kernel<kLanes><<<grid_for_rows(M.num_rows, kBlock / kLanes), kBlock, 0, s>>>(
+            amg_sweep_kernel<kLanes><<<capped_grid(M.num_rows, kBlock / kLanes), kBlock, 0, s>>>(
                 M.num_rows, M.nnz, M.d_row_ptrs, M.d_col_indices, M.d_values, lv.d_wd, f, x_in, x_out, done);
             return hipGetLastError();
         });
@@ -154,7 +146,7 @@ struct Cycle {
         const CSRMatrix& M = lv.view;
         return with_lanes(lanes, [&](auto L) {
             constexpr int kLanes = decltype(L)::value;
-            amg_restrict_kernel<kLanes><<<grid_for_rows(lv.num_aggregates, kBlock / kLanes), kBlock, 0, s>>>(
+            amg_restrict_kernel<kLanes><<<capped_grid(lv.num_aggregates, kBlock / kLanes), kBlock, 0, s>>>(
                 lv.num_aggregates, M.nnz, M.d_row_ptrs, M.d_col_indices, M.d_values, lv.PT->d_row_ptrs,
                 lv.PT->d_col_indices, f, x, f_coarse, done);
             return hipGetLastError();

@@ -4,13 +4,14 @@
 //
 //   diagonal     one thread per row: d_i (fp32, storage order), wd_i = float(double(omega) / double(d_i)) and the
 //                smallest row whose diagonal is missing, not > 0 or not finite, as one minimum per workgroup
-//   roots        Jones-Plassmann in rounds, csr_color's loop.  A round is one launch: 1-64 lanes share an undecided row
-//                v, split its strong entries and walk, for each of them, the strong entries of that neighbour's row
-//                (a direct 2-hop pull from A's rows).  Priorities are recomputed from the index; the strength test is
-//                re-evaluated from d on the fly.  The states are updated in place: v becomes OUT when it saw a
-//                higher-priority ROOT, ROOT when every higher-priority vertex it saw was OUT.  A state is written
-//                once, by one aligned 4-byte store, and both rules only act on states that are final, so which of the
-//                current round's writes a vertex happens to see changes the round it decides in, never its state.
+//   roots        Jones-Plassmann in rounds, the host loop being csr_color's (solver::run_rounds).  A round is one
+//                launch: 1-64 lanes share an undecided row v, split its strong entries and walk, for each of them,
+//                the strong entries of that neighbour's row (a direct 2-hop pull from A's rows).  Priorities are
+//                recomputed from the index; the strength test is re-evaluated from d on the fly.  The states
+//                are updated in place: v becomes OUT when it saw a higher-priority ROOT, ROOT when every
+//                higher-priority vertex it saw was OUT.  A state is written once, by one aligned 4-byte store, and
+//                both rules only act on states that are final, so which of the current round's writes a vertex
+//                happens to see changes the round it decides in, never its state.
 //                The only atomic is one add per workgroup to the count of vertices left.
 //   numbers      the root flags scanned by transpose.hip's scan
 //   phase 1, 2   lanes share a row again; phase 1 writes a second array so that phase 2 reads end-of-phase-1
@@ -33,11 +34,13 @@ namespace detail {
 namespace {
 
 using dev::block_min;
+using dev::capped_grid;
 using dev::group_or;
 using dev::kBlock;
+using dev::vec_grid;
+using dev::with_lanes;
 using reorder::higher_priority;
 
-constexpr int kRoundsPerBatch = 8;      // rounds enqueued between two looks at the count of vertices left
 constexpr int kUndecided = 0, kRoot = 1, kOut = 2;
 
 // the device state of one level's setup; remaining[r % 3] = vertices still undecided after round r
@@ -306,7 +309,7 @@ struct Scratch {
 // d (and wd, with the check, when it is given) of M, and the smallest bad row into the state; not waited for
 bool enqueue_diagonal(const CSRMatrix& M, float omega, float* d, float* wd, Scratch& sc, hipStream_t s) {
     const int n = M.num_rows;
-    const int blocks = solver::vec_grid(n);
+    const int blocks = vec_grid(n);
     amg_diag_kernel<<<blocks, kBlock, 0, s>>>(n, M.d_row_ptrs, M.d_col_indices, M.d_values, omega, d, wd,
                                               sc.partial.get());
     min_fold_kernel<<<1, kBlock, 0, s>>>(sc.partial.get(), blocks, &sc.ws.state->bad_row);
@@ -318,54 +321,29 @@ bool enqueue_diagonal(const CSRMatrix& M, float omega, float* d, float* wd, Scra
 bool aggregate_level(const CSRMatrix& M, float theta, unsigned seed, int* d_aggregate, Scratch& sc, hipStream_t s) {
     const int n = M.num_rows;
     const int lanes = mis_lanes_for(M);
-    const int grid = solver::grid_for_rows(n, kBlock / lanes);
+    const int grid = capped_grid(n, kBlock / lanes);
     const double theta2 = static_cast<double>(theta) * static_cast<double>(theta);
     const int* rp = M.d_row_ptrs;
     const int* ci = M.d_col_indices;
     const float* va = M.d_values;
     solver::Workspace<Mis2State>& ws = sc.ws;
-    mis2_init_kernel<<<solver::vec_grid(n), kBlock, 0, s>>>(n, sc.state.get(), ws.state);
+    mis2_init_kernel<<<vec_grid(n), kBlock, 0, s>>>(n, sc.state.get(), ws.state);
     bool ok = hipGetLastError() == hipSuccess;
-
-    // csr_color's loop: batches of rounds, each followed by a copy of the state; batch b + 1 is enqueued before batch
-    // b's copy is looked at.  The highest-priority undecided vertex always decides, so n rounds are enough.
-    int enqueued = 0;
-    int enqueued_at[2] = {0, 0};
-    bool done = false;
-    for (long long batch = 0; ok && !done; ++batch) {
-        const int todo = std::min(kRoundsPerBatch, n - enqueued);
-        for (int t = 0; t < todo && ok; ++t) {
-            ok = solver::with_lanes(lanes, [&](auto L) {
-                mis2_round_kernel<decltype(L)::value><<<grid, kBlock, 0, s>>>(n, rp, ci, va, sc.d.get(), theta2, seed,
-                                                                              sc.state.get(), ws.state, enqueued);
-                return hipGetLastError();
-            }) == hipSuccess;
-            ++enqueued;
-        }
-        enqueued_at[batch & 1] = enqueued;
-        ok = ok && ws.publish(batch, sizeof(Mis2State), s);
-        const bool last = enqueued >= n;
-        const long long look_at = last ? batch + 1 : batch;      // the last batch is waited for at once
-        if (ok && look_at >= 1) {
-            const Mis2State* st = ws.wait_previous(look_at);
-            ok = st != nullptr;
-            if (ok) {
-                const int seen_rounds = st->rounds;
-                done = seen_rounds < enqueued_at[(look_at - 1) & 1] ||
-                       (seen_rounds >= 1 && st->remaining[(seen_rounds - 1) % 3] == 0);
-            }
-            if (ok && last && !done) ok = false;                  // cannot happen: n rounds decide n vertices
-        }
-    }
+    ok = ok && solver::run_rounds(n, ws, s, [&](int round) {
+        return with_lanes(lanes, [&](auto L) {
+            mis2_round_kernel<decltype(L)::value><<<grid, kBlock, 0, s>>>(n, rp, ci, va, sc.d.get(), theta2, seed,
+                                                                          sc.state.get(), ws.state, round);
+            return hipGetLastError();
+        });
+    });
     if (ok) {
-        mis2_flags_kernel<<<solver::vec_grid(static_cast<long long>(n) + 1), kBlock, 0, s>>>(n, sc.state.get(),
-                                                                                             sc.rank.get());
+        mis2_flags_kernel<<<vec_grid(static_cast<long long>(n) + 1), kBlock, 0, s>>>(n, sc.state.get(), sc.rank.get());
         ok = hipGetLastError() == hipSuccess &&
              device_exclusive_scan(sc.rank.get(), device_scan_levels(static_cast<long long>(n) + 1), sc.sums.get(), s) ==
                  hipSuccess;
     }
     if (ok) {
-        ok = solver::with_lanes(lanes, [&](auto L) {
+        ok = with_lanes(lanes, [&](auto L) {
             constexpr int kLanes = decltype(L)::value;
             mis2_phase1_kernel<kLanes><<<grid, kBlock, 0, s>>>(n, rp, ci, va, sc.d.get(), theta2, sc.state.get(),
                                                                sc.rank.get(), sc.first.get());
@@ -379,25 +357,8 @@ bool aggregate_level(const CSRMatrix& M, float theta, unsigned seed, int* d_aggr
     return ws.read_back(ok, s);
 }
 
-// A's structure checked on the device and waited for: 0, INVALID_FORMAT or KERNEL_LAUNCH
-int structure_check(const CSRMatrix* A, hipStream_t s) {
-    DevBuf<int> flag;
-    if (dev_alloc(&flag, 1) != hipSuccess) {
-        (void)hipGetLastError();
-        return code(SpMVError::CUDA_MALLOC);
-    }
-    int bad = 0;
-    if (hipMemsetAsync(flag.get(), 0, sizeof(int), s) != hipSuccess ||
-        enqueue_structure_check(A, flag.get(), s) != hipSuccess ||
-        hipMemcpyAsync(&bad, flag.get(), sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {
-        (void)hipGetLastError();
-        return code(SpMVError::KERNEL_LAUNCH);
-    }
-    return bad ? code(SpMVError::INVALID_FORMAT) : 0;
-}
-
-bool device_arrays(const CSRMatrix* M) {
+// not solver::device_arrays: nnz < 0 fails here (there it counts as no entries), num_rows is the caller's to check
+bool device_arrays_nnz_checked(const CSRMatrix* M) {
     return M->nnz >= 0 && M->d_row_ptrs && (M->nnz == 0 || (M->d_col_indices && M->d_values));
 }
 
@@ -462,8 +423,8 @@ struct DeviceBuilder {
         if (dev_alloc(&p_rp, static_cast<long long>(n) + 1) != hipSuccess || dev_alloc(&p_va, n) != hipSuccess) {
             return fail(SpMVError::CUDA_MALLOC);
         }
-        amg_prolongation_kernel<<<solver::vec_grid(static_cast<long long>(n) + 1), kBlock, 0, stream>>>(n, p_rp.get(),
-                                                                                                        p_va.get());
+        amg_prolongation_kernel<<<vec_grid(static_cast<long long>(n) + 1), kBlock, 0, stream>>>(n, p_rp.get(),
+                                                                                                p_va.get());
         if (hipGetLastError() != hipSuccess) return fail(SpMVError::KERNEL_LAUNCH);
         CSRMatrix* P = new CSRMatrix{};       // device arrays only, owned: csr_destroy frees them
         P->num_rows = n;
@@ -509,7 +470,7 @@ AMGResult amg_update_device(AMGHierarchy* H, const CSRMatrix* A) {
         return res;
     }
     H->levels[0].view = device_view(A);
-    if (const int status = structure_check(A, stream)) {
+    if (const int status = structure_checked(A, stream)) {
         b.fail(static_cast<SpMVError>(status));
         return res;
     }
@@ -537,10 +498,10 @@ int amg_aggregate_mis2_gpu(const CSRMatrix* A, float strength, unsigned seed, in
     using namespace detail;
     if (!A || !d_aggregate || !num_aggregates) return code(SpMVError::INVALID_ARGUMENT);
     if (A->num_rows != A->num_cols) return code(SpMVError::INVALID_DIMENSION);
-    if (A->num_rows < 0 || !device_arrays(A)) return code(SpMVError::INVALID_FORMAT);
+    if (A->num_rows < 0 || !device_arrays_nnz_checked(A)) return code(SpMVError::INVALID_FORMAT);
     if (!(strength >= 0.0f)) return code(SpMVError::INVALID_ARGUMENT);
     hipStream_t stream = current_stream();
-    if (const int status = structure_check(A, stream)) return status;
+    if (const int status = structure_checked(A, stream)) return status;
     if (A->num_rows == 0) {
         *num_aggregates = 0;
         if (rounds) *rounds = 0;
@@ -571,7 +532,7 @@ AMGResult amg_setup_device(AMGHierarchy** out, const CSRMatrix* A, const AMGConf
     if (out) *out = nullptr;
     if (!out || !A) return fail(SpMVError::INVALID_ARGUMENT);
     if (A->num_rows != A->num_cols || A->num_rows < 1) return fail(SpMVError::INVALID_DIMENSION);
-    if (!device_arrays(A)) return fail(SpMVError::INVALID_FORMAT);
+    if (!device_arrays_nnz_checked(A)) return fail(SpMVError::INVALID_FORMAT);
     const AMGConfig defaults;
     const AMGConfig& cfg = config ? *config : defaults;
     if (!amg_config_ok(cfg)) return fail(SpMVError::INVALID_ARGUMENT);
@@ -588,7 +549,7 @@ AMGResult amg_setup_device(AMGHierarchy** out, const CSRMatrix* A, const AMGConf
     Scratch sc;
     DeviceBuilder b{*H, res, sc, stream};
     if (!sc.allocate(A->num_rows)) return fail(SpMVError::CUDA_MALLOC);
-    if (const int status = structure_check(A, stream)) return fail(static_cast<SpMVError>(status));
+    if (const int status = structure_checked(A, stream)) return fail(static_cast<SpMVError>(status));
     for (int l = 0;; ++l) {
         if (b.diagonal_of(l) != 0) return res;
         const CSRMatrix view = H->levels[static_cast<size_t>(l)].view;

@@ -74,27 +74,17 @@ void bicg_init_kernel(int n, long long nnz, const int* __restrict__ row_ptrs, co
                       const float* __restrict__ vals, const float* __restrict__ b, const float* __restrict__ x,
                       const float* __restrict__ dinv, float* __restrict__ r, float* __restrict__ rhat,
                       float* __restrict__ p, float* __restrict__ phat, double* __restrict__ part) {
-    constexpr int kRowsPerBlock = kBlock / LANES;
-    const int lane = threadIdx.x % LANES;
-    const int slot = threadIdx.x / LANES;
     double rr = 0.0, bb = 0.0;
-    for (long long first = static_cast<long long>(blockIdx.x) * kRowsPerBlock; first < n;
-         first += static_cast<long long>(gridDim.x) * kRowsPerBlock) {
-        const long long row = first + slot;
-        float acc = 0.0f;
-        if (row < n) acc = row_partial_dot<LANES>(row_ptrs[row], row_ptrs[row + 1], lane, nnz, cols, vals, x);
-        acc = group_sum<LANES>(acc);
-        if (lane == 0 && row < n) {
-            const float bi = b[row];
-            const float ri = __fsub_rn(bi, acc);
-            r[row] = ri;
-            rhat[row] = ri;
-            p[row] = ri;
-            if (dinv) phat[row] = __fmul_rn(ri, dinv[row]);
-            rr += prod64(ri, ri);
-            bb += prod64(bi, bi);
-        }
-    }
+    for_each_row_dot<LANES>(n, nnz, row_ptrs, cols, vals, x, [&](long long row, float acc) {
+        const float bi = b[row];
+        const float ri = __fsub_rn(bi, acc);
+        r[row] = ri;
+        rhat[row] = ri;
+        p[row] = ri;
+        if (dinv) phat[row] = __fmul_rn(ri, dinv[row]);
+        rr += prod64(ri, ri);
+        bb += prod64(bi, bi);
+    });
     block_sum2(rr, bb);
     if (threadIdx.x == 0) {
         part[2 * blockIdx.x] = rr;
@@ -141,22 +131,12 @@ void bicg_spmv_dot(int n, long long nnz, const int* __restrict__ row_ptrs, const
                    const float* __restrict__ a, int with_yy, const BicgState* __restrict__ state,
                    double* __restrict__ part) {
     if (state->done) return;
-    constexpr int kRowsPerBlock = kBlock / LANES;
-    const int lane = threadIdx.x % LANES;
-    const int slot = threadIdx.x / LANES;
     double ay = 0.0, yy = 0.0;
-    for (long long first = static_cast<long long>(blockIdx.x) * kRowsPerBlock; first < n;
-         first += static_cast<long long>(gridDim.x) * kRowsPerBlock) {
-        const long long row = first + slot;
-        float acc = 0.0f;
-        if (row < n) acc = row_partial_dot<LANES>(row_ptrs[row], row_ptrs[row + 1], lane, nnz, cols, vals, w);
-        acc = group_sum<LANES>(acc);
-        if (lane == 0 && row < n) {
-            y[row] = acc;
-            ay += prod64(a[row], acc);
-            yy += prod64(acc, acc);
-        }
-    }
+    for_each_row_dot<LANES>(n, nnz, row_ptrs, cols, vals, w, [&](long long row, float acc) {
+        y[row] = acc;
+        ay += prod64(a[row], acc);
+        yy += prod64(acc, acc);
+    });
     block_sum2(ay, yy);
     if (threadIdx.x == 0) {
         if (with_yy) {
@@ -378,7 +358,7 @@ BiCGStabResult solve(const CSRMatrix* A, const CSRMatrix* LU, bool with_lu, cons
     TiledEngine engine(A, cfg.engine, stream);
 
     const int lanes = pick_lanes_per_row(static_cast<float>(A->nnz) / n);
-    const int row_grid = grid_for_rows(n, kBlock / lanes);
+    const int row_grid = capped_grid(n, kBlock / lanes);
     const int vgrid = vec_grid(n);
     const size_t dot_count = static_cast<size_t>(std::max(row_grid, vgrid));
     const size_t rv_count = dot_count;

@@ -68,27 +68,17 @@ void cg_init_kernel(int n, long long nnz, const int* __restrict__ row_ptrs, cons
                     const float* __restrict__ vals, const float* __restrict__ b, const float* __restrict__ x,
                     const float* __restrict__ dinv, float* __restrict__ r, float* __restrict__ p,
                     double* __restrict__ part) {
-    constexpr int kRowsPerBlock = kBlock / LANES;
-    const int lane = threadIdx.x % LANES;
-    const int slot = threadIdx.x / LANES;
     double rz = 0.0, rr = 0.0, bb = 0.0, unused = 0.0;
-    for (long long first = static_cast<long long>(blockIdx.x) * kRowsPerBlock; first < n;
-         first += static_cast<long long>(gridDim.x) * kRowsPerBlock) {
-        const long long row = first + slot;
-        float acc = 0.0f;
-        if (row < n) acc = row_partial_dot<LANES>(row_ptrs[row], row_ptrs[row + 1], lane, nnz, cols, vals, x);
-        acc = group_sum<LANES>(acc);
-        if (lane == 0 && row < n) {
-            const float bi = b[row];
-            const float ri = __fsub_rn(bi, acc);
-            const float zi = dinv ? __fmul_rn(ri, dinv[row]) : ri;
-            r[row] = ri;
-            p[row] = zi;
-            rz += prod64(ri, zi);
-            rr += prod64(ri, ri);
-            bb += prod64(bi, bi);
-        }
-    }
+    for_each_row_dot<LANES>(n, nnz, row_ptrs, cols, vals, x, [&](long long row, float acc) {
+        const float bi = b[row];
+        const float ri = __fsub_rn(bi, acc);
+        const float zi = dinv ? __fmul_rn(ri, dinv[row]) : ri;
+        r[row] = ri;
+        p[row] = zi;
+        rz += prod64(ri, zi);
+        rr += prod64(ri, ri);
+        bb += prod64(bi, bi);
+    });
     block_sum2(rz, rr);
     if (threadIdx.x == 0) {
         part[3 * blockIdx.x] = rz;
@@ -136,21 +126,11 @@ void cg_spmv_dot(int n, long long nnz, const int* __restrict__ row_ptrs, const i
                  const float* __restrict__ vals, const float* __restrict__ p, float* __restrict__ q,
                  const CgState* __restrict__ state, double* __restrict__ part) {
     if (state->done) return;
-    constexpr int kRowsPerBlock = kBlock / LANES;
-    const int lane = threadIdx.x % LANES;
-    const int slot = threadIdx.x / LANES;
     double pq = 0.0, unused = 0.0;
-    for (long long first = static_cast<long long>(blockIdx.x) * kRowsPerBlock; first < n;
-         first += static_cast<long long>(gridDim.x) * kRowsPerBlock) {
-        const long long row = first + slot;
-        float acc = 0.0f;
-        if (row < n) acc = row_partial_dot<LANES>(row_ptrs[row], row_ptrs[row + 1], lane, nnz, cols, vals, p);
-        acc = group_sum<LANES>(acc);
-        if (lane == 0 && row < n) {
-            q[row] = acc;
-            pq += prod64(p[row], acc);
-        }
-    }
+    for_each_row_dot<LANES>(n, nnz, row_ptrs, cols, vals, p, [&](long long row, float acc) {
+        q[row] = acc;
+        pq += prod64(p[row], acc);
+    });
     block_sum2(pq, unused);
     if (threadIdx.x == 0) part[blockIdx.x] = pq;
 }
@@ -335,7 +315,7 @@ CGResult solve(const CSRMatrix* A, Precond precond, const CSRMatrix* F, const AM
     TiledEngine engine(A, cfg.engine, stream);
 
     const int lanes = pick_lanes_per_row(static_cast<float>(A->nnz) / n);
-    const int row_grid = grid_for_rows(n, kBlock / lanes);
+    const int row_grid = capped_grid(n, kBlock / lanes);
     const int vgrid = vec_grid(n);
     const size_t pq_count = static_cast<size_t>(std::max(row_grid, vgrid));
     const size_t rr_count = 2 * static_cast<size_t>(vgrid);

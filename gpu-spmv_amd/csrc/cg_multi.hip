@@ -549,7 +549,7 @@ int solve_multi(const CSRMatrix* A, bool with_ic, const CSRMatrix* F, const floa
     }
 
     const int lanes = pick_lanes_per_row(static_cast<float>(A->nnz) / n);
-    const int row_grid = grid_for_rows(n, kBlock / lanes);
+    const int row_grid = capped_grid(n, kBlock / lanes);
     const int vgrid = vec_grid(n);
     const size_t pq_count = static_cast<size_t>(row_grid);
     const size_t rr_count = 2 * static_cast<size_t>(vgrid);

@@ -1,12 +1,17 @@
-// device_common.h — device-side building blocks shared by the kernel files
-// (gfx950, wave64): cross-lane and workgroup reductions, the vector-CSR row
-// walk, the binary searches, and the host's capped grid size.
+// device_common.h — what the kernel files share (gfx950, wave64).
+// Device side: cross-lane and workgroup reductions, the vector-CSR row walk
+// (row_partial_dot) and the sweep over all rows built on it (for_each_row_dot),
+// the binary searches.
+// Host side, the launch layer: the grid sizes (capped_grid, vec_grid) and
+// with_lanes, which turns a run-time lanes-per-row count into a template
+// argument.
 #ifndef SPMV_AMD_DEVICE_COMMON_H
 #define SPMV_AMD_DEVICE_COMMON_H
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
 namespace spmv {
 namespace detail {
@@ -120,6 +125,27 @@ __device__ __forceinline__ float row_partial_dot(int begin, int end, int lane, l
     return acc;
 }
 
+// The vector-CSR sweep: the workgroup's aligned groups of LANES lanes stride over the rows, BLOCK / LANES rows per
+// workgroup and trip; row_done(row, sum) is called by lane 0 of each group, for rows < n only, with the row's dot
+// product with x (the group_sum of row_partial_dot).  Every lane of the workgroup makes every trip (group_sum is
+// cross-lane), so row_done may not leave the kernel.  BLOCK is the workgroup's size.
+template <int LANES, int BLOCK = kBlock, class RowDone>
+__device__ __forceinline__ void for_each_row_dot(int n, long long nnz, const int* __restrict__ row_ptrs,
+                                                 const int* __restrict__ cols, const float* __restrict__ vals,
+                                                 const float* __restrict__ x, RowDone&& row_done) {
+    constexpr int kRowsPerBlock = BLOCK / LANES;
+    const int lane = threadIdx.x % LANES;
+    const int slot = threadIdx.x / LANES;
+    for (long long first = static_cast<long long>(blockIdx.x) * kRowsPerBlock; first < n;
+         first += static_cast<long long>(gridDim.x) * kRowsPerBlock) {
+        const long long row = first + slot;
+        float acc = 0.0f;
+        if (row < n) acc = row_partial_dot<LANES>(row_ptrs[row], row_ptrs[row + 1], lane, nnz, cols, vals, x);
+        acc = group_sum<LANES>(acc);
+        if (lane == 0 && row < n) row_done(row, acc);
+    }
+}
+
 // block-wide sum of two doubles; result valid in thread 0
 template <int BLOCK = kBlock>
 __device__ __forceinline__ void block_sum2(double& a, double& b) {
@@ -192,11 +218,34 @@ __device__ __forceinline__ int upper_bound(const int* __restrict__ rp, int lo, i
     return lo;
 }
 
-// host side: workgroups for work_items at per_block each, at least one and at most what the chip holds at once (the
-// kernels stride over the rest)
-inline int capped_grid(long long work_items, int per_block) {
+// ---------------------------------------------------------------------------
+// host side: the launch layer
+// ---------------------------------------------------------------------------
+// workgroups for work_items at per_block each, at least one and at most `cap`: what the chip holds at once unless the
+// caller has a reason for fewer (the kernels stride over the rest)
+inline int capped_grid(long long work_items, int per_block, int cap = kMaxResidentBlocks) {
     const long long blocks = (work_items + per_block - 1) / per_block;
-    return static_cast<int>(std::max(1LL, std::min<long long>(blocks, kMaxResidentBlocks)));
+    return static_cast<int>(std::max(1LL, std::min<long long>(blocks, cap)));
+}
+
+constexpr int kVecBlocks = 1024;      // workgroups of the element-wise kernels (4 per CU)
+
+inline int vec_grid(long long n) {
+    return static_cast<int>(std::max(1LL, std::min<long long>((n + kBlock - 1) / kBlock, kVecBlocks)));
+}
+
+// Calls launch(std::integral_constant<int, LANES>{}) for the LANES pick_lanes_per_row chose (64 for anything else).
+template <class Launch>
+hipError_t with_lanes(int lanes, Launch&& launch) {
+    switch (lanes) {
+        case 1:  return launch(std::integral_constant<int, 1>{});
+        case 2:  return launch(std::integral_constant<int, 2>{});
+        case 4:  return launch(std::integral_constant<int, 4>{});
+        case 8:  return launch(std::integral_constant<int, 8>{});
+        case 16: return launch(std::integral_constant<int, 16>{});
+        case 32: return launch(std::integral_constant<int, 32>{});
+        default: return launch(std::integral_constant<int, 64>{});
+    }
 }
 
 } // namespace dev

@@ -229,17 +229,7 @@ void eigs_spmv(int n, long long nnz, const int* __restrict__ row_ptrs, const int
                const float* __restrict__ vals, const float* __restrict__ v, float* __restrict__ w, int pair,
                const EigsState* __restrict__ st) {
     if (FINISHING ? !(closing(st, FINISH) && pair < st->found) : !stepping(st)) return;
-    constexpr int kRowsPerBlock = kBlock / LANES;
-    const int lane = threadIdx.x % LANES;
-    const int slot = threadIdx.x / LANES;
-    for (long long first = static_cast<long long>(blockIdx.x) * kRowsPerBlock; first < n;
-         first += static_cast<long long>(gridDim.x) * kRowsPerBlock) {
-        const long long row = first + slot;
-        float acc = 0.0f;
-        if (row < n) acc = row_partial_dot<LANES>(row_ptrs[row], row_ptrs[row + 1], lane, nnz, cols, vals, v);
-        acc = group_sum<LANES>(acc);
-        if (lane == 0 && row < n) w[row] = acc;
-    }
+    for_each_row_dot<LANES>(n, nnz, row_ptrs, cols, vals, v, [&](long long row, float sum) { w[row] = sum; });
 }
 
 __global__ __launch_bounds__(kBlock)
@@ -584,9 +574,9 @@ EigsResult solve(const CSRMatrix* A, float* d_values, float* d_vectors, long lon
     TiledEngine engine(A, cfg.engine, stream);
 
     const int lanes = pick_lanes_per_row(static_cast<float>(A->nnz) / n);
-    const int row_grid = grid_for_rows(n, kBlock / lanes);
+    const int row_grid = capped_grid(n, kBlock / lanes);
     const int vgrid = vec_grid(n);
-    const int rgrid = grid_for_rows(n, kBlock);
+    const int rgrid = capped_grid(n, kBlock);
     const int ogrid = static_cast<int>(std::min<long long>((static_cast<long long>(n) + kChunk - 1) / kChunk,
                                                            kOrthoBlocks));
     // the basis: m + 1 vectors, leading dimension a multiple of 256 bytes; then w.  Every vector starts on a

@@ -28,7 +28,6 @@
 // endless loop (the k loop advances one stored position per turn).
 #include "internal.h"
 #include "device_common.h"
-#include "solver_common.h"
 
 #include <hip/hip_runtime.h>
 
@@ -138,7 +137,7 @@ hipError_t launch_groups(const SptrsvSchedule& sch, const CSRMatrix* A, const fl
     constexpr int kRowsPerBlock = kBlock / LANES;
     for (const SptrsvSchedule::Group& g : sch.groups) {
         // a run of levels is one workgroup (the barrier is its only ordering); one level alone takes a grid
-        const int grid = g.level_end - g.level_begin > 1 ? 1 : solver::grid_for_rows(g.rows, kRowsPerBlock);
+        const int grid = g.level_end - g.level_begin > 1 ? 1 : capped_grid(g.rows, kRowsPerBlock);
         factor0_kernel<KIND, LANES><<<grid, kBlock, 0, s>>>(A->num_rows, A->nnz, A->d_row_ptrs, A->d_col_indices, a,
                                                             f, sch.d_level_ptr, sch.d_order, g.level_begin,
                                                             g.level_end);
@@ -151,12 +150,12 @@ hipError_t launch_groups(const SptrsvSchedule& sch, const CSRMatrix* A, const fl
 template <Factor0Kind KIND>
 hipError_t launch_kind(const SptrsvSchedule& schedule, const CSRMatrix* A, const float* d_a, float* d_out,
                        int lanes_per_row, unsigned* d_pivot, hipStream_t s) {
-    const hipError_t e = solver::with_lanes(lanes_per_row, [&](auto L) {
+    const hipError_t e = with_lanes(lanes_per_row, [&](auto L) {
         return launch_groups<KIND, decltype(L)::value>(schedule, A, d_a, d_out, s);
     });
     if (e != hipSuccess || !d_pivot) return e;
-    factor0_pivot_kernel<KIND><<<solver::vec_grid(A->num_rows), kBlock, 0, s>>>(A->num_rows, A->nnz, A->d_row_ptrs,
-                                                                                A->d_col_indices, d_out, d_pivot);
+    factor0_pivot_kernel<KIND><<<vec_grid(A->num_rows), kBlock, 0, s>>>(A->num_rows, A->nnz, A->d_row_ptrs,
+                                                                        A->d_col_indices, d_out, d_pivot);
     return hipGetLastError();
 }
 

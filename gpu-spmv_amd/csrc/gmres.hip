@@ -275,24 +275,14 @@ void gmres_residual(int n, long long nnz, const int* __restrict__ row_ptrs, cons
                     const float* __restrict__ vals, const float* __restrict__ b, const float* __restrict__ x,
                     float* __restrict__ r, const GmresState* __restrict__ st, double* __restrict__ part) {
     if (!closing(st)) return;
-    constexpr int kRowsPerBlock = kBlock / LANES;
-    const int lane = threadIdx.x % LANES;
-    const int slot = threadIdx.x / LANES;
     double rr = 0.0, bb = 0.0;
-    for (long long first = static_cast<long long>(blockIdx.x) * kRowsPerBlock; first < n;
-         first += static_cast<long long>(gridDim.x) * kRowsPerBlock) {
-        const long long row = first + slot;
-        float acc = 0.0f;
-        if (row < n) acc = row_partial_dot<LANES>(row_ptrs[row], row_ptrs[row + 1], lane, nnz, cols, vals, x);
-        acc = group_sum<LANES>(acc);
-        if (lane == 0 && row < n) {
-            const float bi = b[row];
-            const float ri = __fsub_rn(bi, acc);
-            r[row] = ri;
-            rr += prod64(ri, ri);
-            bb += prod64(bi, bi);
-        }
-    }
+    for_each_row_dot<LANES>(n, nnz, row_ptrs, cols, vals, x, [&](long long row, float acc) {
+        const float bi = b[row];
+        const float ri = __fsub_rn(bi, acc);
+        r[row] = ri;
+        rr += prod64(ri, ri);
+        bb += prod64(bi, bi);
+    });
     block_sum2(rr, bb);
     if (threadIdx.x == 0) {
         part[2 * blockIdx.x] = rr;
@@ -367,17 +357,7 @@ void gmres_spmv(int n, long long nnz, const int* __restrict__ row_ptrs, const in
                 const float* __restrict__ vals, const float* __restrict__ v, float* __restrict__ w,
                 const GmresState* __restrict__ st) {
     if (!stepping(st)) return;
-    constexpr int kRowsPerBlock = kBlock / LANES;
-    const int lane = threadIdx.x % LANES;
-    const int slot = threadIdx.x / LANES;
-    for (long long first = static_cast<long long>(blockIdx.x) * kRowsPerBlock; first < n;
-         first += static_cast<long long>(gridDim.x) * kRowsPerBlock) {
-        const long long row = first + slot;
-        float acc = 0.0f;
-        if (row < n) acc = row_partial_dot<LANES>(row_ptrs[row], row_ptrs[row + 1], lane, nnz, cols, vals, v);
-        acc = group_sum<LANES>(acc);
-        if (lane == 0 && row < n) w[row] = acc;
-    }
+    for_each_row_dot<LANES>(n, nnz, row_ptrs, cols, vals, v, [&](long long row, float sum) { w[row] = sum; });
 }
 
 // gmres_solve (with_lu false: cfg.preconditioner picks NONE or JACOBI) and gmres_solve_lu (with_lu true: M = L U
@@ -424,7 +404,7 @@ GMRESResult solve(const CSRMatrix* A, const CSRMatrix* LU, bool with_lu, const f
     TiledEngine engine(A, cfg.engine, stream);
 
     const int lanes = pick_lanes_per_row(static_cast<float>(A->nnz) / n);
-    const int row_grid = grid_for_rows(n, kBlock / lanes);
+    const int row_grid = capped_grid(n, kBlock / lanes);
     const int vgrid = vec_grid(n);
     const int ogrid = static_cast<int>(std::min<long long>((static_cast<long long>(n) + kChunk - 1) / kChunk,
                                                            kOrthoBlocks));

@@ -245,9 +245,10 @@ int transpose_build(const CSRMatrix* A, TransposeArrays* out, hipStream_t s);
 // levels[1 ..] ints plus one
 std::vector<long long> device_scan_levels(long long n);
 hipError_t device_exclusive_scan(int* data, const std::vector<long long>& levels, int* sums, hipStream_t s);
-// the structure check of reorder.hip (csr_transpose_gpu's rule) for other callers (amg_setup.hip): *d_flag, zeroed by
-// the caller, becomes 1 when A's row pointers or columns are malformed; enqueued on `s`, not waited for
-hipError_t enqueue_structure_check(const CSRMatrix* A, int* d_flag, hipStream_t s);
+// the structure check of reorder.hip (csr_transpose_gpu's rule), run on `s` and waited for: 0, or the code of
+// CUDA_MALLOC (no flag word), KERNEL_LAUNCH (a call failed; the HIP error is cleared) or INVALID_FORMAT (A's row
+// pointers or columns are malformed)
+int structure_checked(const CSRMatrix* A, hipStream_t s);
 // spgemm_csr's accumulator classes (spgemm.hip, spgemm_host.cpp): classes 1 .. kSpgemmClasses - 1 are LDS hash tables
 // of kSpgemmSlots slots (a power of two; a row may fill half of them), the last class is the dense accumulator
 constexpr int kSpgemmClasses = 5;

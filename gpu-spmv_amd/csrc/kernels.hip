@@ -39,22 +39,7 @@ void csr_vector_kernel(int num_rows, long long nnz,
                        const float* __restrict__ vals,
                        const float* __restrict__ x,
                        float* __restrict__ y) {
-    constexpr int kRowsPerBlock = kBlock / LANES;
-    const int lane = threadIdx.x % LANES;
-    const int slot = threadIdx.x / LANES;
-
-    for (long long first = static_cast<long long>(blockIdx.x) * kRowsPerBlock; first < num_rows;
-         first += static_cast<long long>(gridDim.x) * kRowsPerBlock) {
-        const long long row = first + slot;
-        float acc = 0.0f;
-        if (row < num_rows) {
-            const int begin = row_ptrs[row];
-            const int end = row_ptrs[row + 1];
-            acc = row_partial_dot<LANES>(begin, end, lane, nnz, cols, vals, x);
-        }
-        acc = group_sum<LANES>(acc);
-        if (lane == 0 && row < num_rows) y[row] = acc;
-    }
+    for_each_row_dot<LANES>(num_rows, nnz, row_ptrs, cols, vals, x, [&](long long row, float sum) { y[row] = sum; });
 }
 
 // VECTOR_CSR with the whole of x resident in LDS (use_texture on matrices with at most
@@ -83,19 +68,8 @@ void csr_vector_ldsx_kernel(int num_rows, int num_cols, long long nnz,
     }
     __syncthreads();
 
-    constexpr int kRowsPerBlock = 1024 / LANES;
-    const int lane = threadIdx.x % LANES;
-    const int slot = threadIdx.x / LANES;
-    for (long long first = static_cast<long long>(blockIdx.x) * kRowsPerBlock; first < num_rows;
-         first += static_cast<long long>(gridDim.x) * kRowsPerBlock) {
-        const long long row = first + slot;
-        float acc = 0.0f;
-        if (row < num_rows) {
-            acc = row_partial_dot<LANES>(row_ptrs[row], row_ptrs[row + 1], lane, nnz, cols, vals, xs);
-        }
-        acc = group_sum<LANES>(acc);
-        if (lane == 0 && row < num_rows) y[row] = acc;
-    }
+    for_each_row_dot<LANES, 1024>(num_rows, nnz, row_ptrs, cols, vals, xs,
+                                  [&](long long row, float sum) { y[row] = sum; });
 }
 
 // ---------------------------------------------------------------------------
@@ -487,15 +461,7 @@ int vector_ldsx_grid(const CSRMatrix* A) {
 
 hipError_t launch_csr_vector_ldsx(const CSRMatrix* A, const float* d_x, float* d_y, int lanes, int grid,
                                   hipStream_t s) {
-    switch (lanes) {
-        case 1:  return launch_vector_ldsx<1>(A, d_x, d_y, grid, s);
-        case 2:  return launch_vector_ldsx<2>(A, d_x, d_y, grid, s);
-        case 4:  return launch_vector_ldsx<4>(A, d_x, d_y, grid, s);
-        case 8:  return launch_vector_ldsx<8>(A, d_x, d_y, grid, s);
-        case 16: return launch_vector_ldsx<16>(A, d_x, d_y, grid, s);
-        case 32: return launch_vector_ldsx<32>(A, d_x, d_y, grid, s);
-        default: return launch_vector_ldsx<64>(A, d_x, d_y, grid, s);
-    }
+    return with_lanes(lanes, [&](auto L) { return launch_vector_ldsx<decltype(L)::value>(A, d_x, d_y, grid, s); });
 }
 
 int pick_lanes_per_row(float avg) {
@@ -520,15 +486,7 @@ hipError_t launch_csr_scalar(const CSRMatrix* A, const float* d_x, float* d_y, h
 
 hipError_t launch_csr_vector(const CSRMatrix* A, const float* d_x, float* d_y,
                              int lanes, hipStream_t s) {
-    switch (lanes) {
-        case 1:  return launch_vector<1>(A, d_x, d_y, s);
-        case 2:  return launch_vector<2>(A, d_x, d_y, s);
-        case 4:  return launch_vector<4>(A, d_x, d_y, s);
-        case 8:  return launch_vector<8>(A, d_x, d_y, s);
-        case 16: return launch_vector<16>(A, d_x, d_y, s);
-        case 32: return launch_vector<32>(A, d_x, d_y, s);
-        default: return launch_vector<64>(A, d_x, d_y, s);
-    }
+    return with_lanes(lanes, [&](auto L) { return launch_vector<decltype(L)::value>(A, d_x, d_y, s); });
 }
 
 // the tile table of the merge-path kernels: built on first use (or ahead of a timed call), cached with the matrix

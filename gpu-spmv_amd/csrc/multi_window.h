@@ -186,7 +186,7 @@ __device__ __forceinline__ void row_partial_dot_multi(int begin, int end, int la
 namespace solver {
 
 // Calls launch(std::integral_constant<int, W>{}) for the window width w of a k-wide workspace: 4 (k <= 4), else 8
-// (host side; with_lanes' shape, solver_common.h).
+// (host side; with_lanes' shape, device_common.h).
 template <class Launch>
 hipError_t with_window(int w, Launch&& launch) {
     if (w == 4) return launch(std::integral_constant<int, 4>{});

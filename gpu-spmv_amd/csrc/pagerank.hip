@@ -58,34 +58,21 @@ void pr_step_kernel(int local_rows, RowMap map, int n_global, long long nnz,
                     PushTargets push) {                         // peers' vectors that also get the new slice
     if (state->done) return;
 
-    constexpr int kRowsPerBlock = kBlock / LANES;
-    const int lane = threadIdx.x % LANES;
-    const int slot = threadIdx.x / LANES;
-
     // same expression order as the host loop: d * y + (d * s / n) + (1 - d) / n
     const float teleport = (1.0f - damping) / n_global;
     const float dangling_term = __fdiv_rn(__fmul_rn(damping, state->dangling_sum),
                                           static_cast<float>(n_global));
 
     double res2 = 0.0, mass = 0.0;
-    for (long long first = static_cast<long long>(blockIdx.x) * kRowsPerBlock; first < local_rows;
-         first += static_cast<long long>(gridDim.x) * kRowsPerBlock) {
-        const long long row = first + slot;
-        float acc = 0.0f;
-        if (row < local_rows) {
-            acc = row_partial_dot<LANES>(row_ptrs[row], row_ptrs[row + 1], lane, nnz, cols, vals, r_old);
-        }
-        acc = group_sum<LANES>(acc);
-        if (lane == 0 && row < local_rows) {
-            const long long node = map.at(row);
-            const float fresh = __fadd_rn(__fadd_rn(__fmul_rn(damping, acc), dangling_term), teleport);
-            r_new[node] = fresh;
-            for (int p = 0; p < push.count; ++p) push.ptr[p][node] = fresh;
-            const float diff = __fsub_rn(fresh, r_old[node]);
-            res2 += static_cast<double>(__fmul_rn(diff, diff));
-            if (dangling[node]) mass += static_cast<double>(fresh);
-        }
-    }
+    for_each_row_dot<LANES>(local_rows, nnz, row_ptrs, cols, vals, r_old, [&](long long row, float acc) {
+        const long long node = map.at(row);
+        const float fresh = __fadd_rn(__fadd_rn(__fmul_rn(damping, acc), dangling_term), teleport);
+        r_new[node] = fresh;
+        for (int p = 0; p < push.count; ++p) push.ptr[p][node] = fresh;
+        const float diff = __fsub_rn(fresh, r_old[node]);
+        res2 += static_cast<double>(__fmul_rn(diff, diff));
+        if (dangling[node]) mass += static_cast<double>(fresh);
+    });
     block_sum2(res2, mass);
     if (threadIdx.x == 0) {
         block_partials[2 * blockIdx.x] = res2;
@@ -281,11 +268,6 @@ void topk_gather_kernel(const unsigned int* __restrict__ bits, size_t n, unsigne
     }
 }
 
-int grid_for(long long rows, int rows_per_block) {
-    const long long blocks = (rows + rows_per_block - 1) / rows_per_block;
-    return static_cast<int>(std::max(1LL, std::min<long long>(blocks, kMaxResidentBlocks)));
-}
-
 template <int LANES>
 hipError_t launch_step(const PrShard& sh, const float* r_old, float* r_new, float damping,
                        const PushTargets& push, hipStream_t s) {
@@ -303,7 +285,7 @@ int pr_shard_prepare(PrShard* sh, PlanRef tiled) {
     const float avg = sh->local_rows > 0 ? static_cast<float>(sh->nnz) / sh->local_rows : 0.0f;
     sh->lanes = pick_lanes_per_row(avg);
     sh->tiled = std::move(tiled);
-    sh->grid = sh->tiled ? sh->tiled->num_tiles : grid_for(sh->local_rows, kBlock / sh->lanes);
+    sh->grid = sh->tiled ? sh->tiled->num_tiles : capped_grid(sh->local_rows, kBlock / sh->lanes);
     return std::max(sh->grid, kMaxResidentBlocks);
 }
 
@@ -346,15 +328,9 @@ hipError_t pr_step(const PrShard& sh, const float* r_old, float* r_new, float da
         return tiled_pagerank_finish(*sh.tiled, sh.map, sh.n_global, r_old, r_new, sh.d_dangling, bits,
                                      damping, sh.d_state, sh.d_block_partials, push, s);
     }
-    switch (sh.lanes) {
-        case 1:  return launch_step<1>(sh, r_old, r_new, damping, push, s);
-        case 2:  return launch_step<2>(sh, r_old, r_new, damping, push, s);
-        case 4:  return launch_step<4>(sh, r_old, r_new, damping, push, s);
-        case 8:  return launch_step<8>(sh, r_old, r_new, damping, push, s);
-        case 16: return launch_step<16>(sh, r_old, r_new, damping, push, s);
-        case 32: return launch_step<32>(sh, r_old, r_new, damping, push, s);
-        default: return launch_step<64>(sh, r_old, r_new, damping, push, s);
-    }
+    return with_lanes(sh.lanes, [&](auto L) {
+        return launch_step<decltype(L)::value>(sh, r_old, r_new, damping, push, s);
+    });
 }
 
 hipError_t pr_expand(const PrShard& sh, const float* r_old, long long cols_ready, hipStream_t s) {
@@ -425,7 +401,7 @@ hipError_t pr_dangling_bits(PrShard* sh, hipStream_t s) {
     const TiledPlan& plan = *sh->tiled;
     const hipError_t e = hipMemsetAsync(sh->d_tile_dangling, 0, sizeof(int) * static_cast<size_t>(plan.num_tiles), s);
     if (e != hipSuccess) return e;
-    pr_dangling_bits_kernel<<<grid_for(sh->local_rows, kBlock * 4), kBlock, 0, s>>>(
+    pr_dangling_bits_kernel<<<capped_grid(sh->local_rows, kBlock * 4), kBlock, 0, s>>>(
         sh->d_dangling + sh->map.base, sh->local_rows, plan.tile_rows, sh->d_dangling_words, sh->d_tile_dangling);
     sh->dangling_bits_ready = true;
     return hipGetLastError();
@@ -433,21 +409,21 @@ hipError_t pr_dangling_bits(PrShard* sh, hipStream_t s) {
 
 hipError_t pr_fill(float* d_r, size_t n, float value, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    pr_fill_kernel<<<grid_for(static_cast<long long>(n), kBlock * 4), kBlock, 0, s>>>(d_r, n, value);
+    pr_fill_kernel<<<capped_grid(static_cast<long long>(n), kBlock * 4), kBlock, 0, s>>>(d_r, n, value);
     return hipGetLastError();
 }
 
 hipError_t pr_column_sums(long long nnz, const int* d_cols, const float* d_vals, int n_cols,
                           float* d_col_sums, hipStream_t s) {
     if (nnz == 0) return hipSuccess;
-    pr_colsum_kernel<<<grid_for(nnz, kBlock * 4), kBlock, 0, s>>>(nnz, d_cols, d_vals, n_cols, d_col_sums);
+    pr_colsum_kernel<<<capped_grid(nnz, kBlock * 4), kBlock, 0, s>>>(nnz, d_cols, d_vals, n_cols, d_col_sums);
     return hipGetLastError();
 }
 
 hipError_t pr_mask_from_column_sums(const float* d_col_sums, int n, unsigned char* d_mask,
                                     unsigned long long* d_count, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    pr_mask_kernel<<<grid_for(n, kBlock * 4), kBlock, 0, s>>>(d_col_sums, n, d_mask, d_count);
+    pr_mask_kernel<<<capped_grid(n, kBlock * 4), kBlock, 0, s>>>(d_col_sums, n, d_mask, d_count);
     return hipGetLastError();
 }
 
@@ -483,15 +459,6 @@ std::vector<unsigned char> dangling_mask_host(const CSRMatrix* A) {
     for (size_t c = 0; c < sums.size(); ++c) mask[c] = sums[c] == 0.0f;
     return mask;
 }
-
-template <typename T>
-struct DeviceArray {
-    T* ptr = nullptr;
-    ~DeviceArray() { if (ptr) (void)hipFree(ptr); }
-    hipError_t alloc(size_t count) {
-        return hipMalloc(reinterpret_cast<void**>(&ptr), std::max<size_t>(count, 1) * sizeof(T));
-    }
-};
 
 // SPMV_TRACE=1: wall-clock time of each host phase of a call, on stderr
 struct Trace {
@@ -750,12 +717,12 @@ PageRankResult pagerank(const CSRMatrix* adj, const PageRankConfig* config) {
             ok = hipMemcpyAsync(ws->mask, host_mask.data(), m, hipMemcpyHostToDevice, stream) == hipSuccess
               && hipStreamSynchronize(stream) == hipSuccess;
         } else if (ok) {
-            DeviceArray<float> col_sums;
-            ok = col_sums.alloc(len) == hipSuccess
-              && hipMemsetAsync(col_sums.ptr, 0, len * sizeof(float), stream) == hipSuccess
+            detail::DevBuf<float> col_sums;
+            ok = detail::dev_alloc(&col_sums, len) == hipSuccess
+              && hipMemsetAsync(col_sums.get(), 0, len * sizeof(float), stream) == hipSuccess
               && detail::pr_column_sums(adj->nnz, adj->d_col_indices, adj->d_values, adj->num_cols,
-                                        col_sums.ptr, stream) == hipSuccess
-              && detail::pr_mask_from_column_sums(col_sums.ptr, std::min(n, adj->num_cols), ws->mask,
+                                        col_sums.get(), stream) == hipSuccess
+              && detail::pr_mask_from_column_sums(col_sums.get(), std::min(n, adj->num_cols), ws->mask,
                                                   ws->dangling_count, stream) == hipSuccess
               && hipMemcpyAsync(&num_dangling, ws->dangling_count, sizeof(num_dangling),
                                 hipMemcpyDeviceToHost, stream) == hipSuccess
@@ -881,22 +848,22 @@ namespace {
 bool top_k_on_device(const float* ranks, int n, int keep, TopKNode* top_k) {
     using namespace detail;
     hipStream_t s = current_stream();
-    DeviceArray<unsigned int> bits, hist, scratch;
-    DeviceArray<TopKNode> winners;
-    if (bits.alloc(n) != hipSuccess || hist.alloc(65536) != hipSuccess || scratch.alloc(4) != hipSuccess ||
-        winners.alloc(keep) != hipSuccess) {
+    DevBuf<unsigned int> bits, hist, scratch;
+    DevBuf<TopKNode> winners;
+    if (dev_alloc(&bits, n) != hipSuccess || dev_alloc(&hist, 65536) != hipSuccess ||
+        dev_alloc(&scratch, 4) != hipSuccess || dev_alloc(&winners, keep) != hipSuccess) {
         return false;
     }
     std::vector<unsigned int> host_hist(65536);
     unsigned int host_scratch[4] = {0, 0, 0, 0};
     const int grid = 2048;
-    bool ok = hipMemcpyAsync(bits.ptr, ranks, static_cast<size_t>(n) * sizeof(float), hipMemcpyHostToDevice, s) == hipSuccess
-           && hipMemsetAsync(hist.ptr, 0, 65536 * sizeof(unsigned int), s) == hipSuccess
-           && hipMemsetAsync(scratch.ptr, 0, sizeof(host_scratch), s) == hipSuccess;
+    bool ok = hipMemcpyAsync(bits.get(), ranks, static_cast<size_t>(n) * sizeof(float), hipMemcpyHostToDevice, s) == hipSuccess
+           && hipMemsetAsync(hist.get(), 0, 65536 * sizeof(unsigned int), s) == hipSuccess
+           && hipMemsetAsync(scratch.get(), 0, sizeof(host_scratch), s) == hipSuccess;
     if (!ok) return false;
-    topk_hist_hi_kernel<<<grid, dev::kBlock, 0, s>>>(bits.ptr, n, hist.ptr, scratch.ptr + 2);
-    ok = hipMemcpyAsync(host_hist.data(), hist.ptr, 65536 * sizeof(unsigned int), hipMemcpyDeviceToHost, s) == hipSuccess
-      && hipMemcpyAsync(host_scratch, scratch.ptr, sizeof(host_scratch), hipMemcpyDeviceToHost, s) == hipSuccess
+    topk_hist_hi_kernel<<<grid, dev::kBlock, 0, s>>>(bits.get(), n, hist.get(), scratch.get() + 2);
+    ok = hipMemcpyAsync(host_hist.data(), hist.get(), 65536 * sizeof(unsigned int), hipMemcpyDeviceToHost, s) == hipSuccess
+      && hipMemcpyAsync(host_scratch, scratch.get(), sizeof(host_scratch), hipMemcpyDeviceToHost, s) == hipSuccess
       && hipStreamSynchronize(s) == hipSuccess;
     if (!ok || host_scratch[2] != 0) return false;
 
@@ -908,9 +875,9 @@ bool top_k_on_device(const float* ranks, int n, int keep, TopKNode* top_k) {
         above += host_hist[prefix];
     }
     if (prefix < 0) return false;
-    ok = hipMemsetAsync(hist.ptr, 0, 65536 * sizeof(unsigned int), s) == hipSuccess;
-    topk_hist_lo_kernel<<<grid, dev::kBlock, 0, s>>>(bits.ptr, n, static_cast<unsigned int>(prefix), hist.ptr);
-    ok = ok && hipMemcpyAsync(host_hist.data(), hist.ptr, 65536 * sizeof(unsigned int), hipMemcpyDeviceToHost, s) == hipSuccess
+    ok = hipMemsetAsync(hist.get(), 0, 65536 * sizeof(unsigned int), s) == hipSuccess;
+    topk_hist_lo_kernel<<<grid, dev::kBlock, 0, s>>>(bits.get(), n, static_cast<unsigned int>(prefix), hist.get());
+    ok = ok && hipMemcpyAsync(host_hist.data(), hist.get(), 65536 * sizeof(unsigned int), hipMemcpyDeviceToHost, s) == hipSuccess
             && hipStreamSynchronize(s) == hipSuccess;
     if (!ok) return false;
     int low = 65535;
@@ -921,12 +888,12 @@ bool top_k_on_device(const float* ranks, int n, int keep, TopKNode* top_k) {
     if (low < 0) return false;
     const unsigned int threshold = (static_cast<unsigned int>(prefix) << 16) | static_cast<unsigned int>(low);
     const unsigned int take_equal = static_cast<unsigned int>(keep - above);   // ties: any of the equals
-    topk_gather_kernel<<<grid, dev::kBlock, 0, s>>>(bits.ptr, n, threshold, take_equal, scratch.ptr, winners.ptr);
+    topk_gather_kernel<<<grid, dev::kBlock, 0, s>>>(bits.get(), n, threshold, take_equal, scratch.get(), winners.get());
     std::vector<TopKNode> host_winners(keep);
     ok = hipGetLastError() == hipSuccess
-      && hipMemcpyAsync(host_winners.data(), winners.ptr, static_cast<size_t>(keep) * sizeof(TopKNode),
+      && hipMemcpyAsync(host_winners.data(), winners.get(), static_cast<size_t>(keep) * sizeof(TopKNode),
                         hipMemcpyDeviceToHost, s) == hipSuccess
-      && hipMemcpyAsync(host_scratch, scratch.ptr, sizeof(host_scratch), hipMemcpyDeviceToHost, s) == hipSuccess
+      && hipMemcpyAsync(host_scratch, scratch.get(), sizeof(host_scratch), hipMemcpyDeviceToHost, s) == hipSuccess
       && hipStreamSynchronize(s) == hipSuccess;
     if (!ok || host_scratch[0] != static_cast<unsigned int>(keep)) return false;
     std::sort(host_winners.begin(), host_winners.end(), [](const TopKNode& a, const TopKNode& b) {

@@ -479,7 +479,7 @@ int personalized(const CSRMatrix* adj, const float* d_V, int ldv, float* d_R, in
     hipStream_t stream = current_stream();
 
     const int lanes = ppr_lanes_for(adj);
-    const int row_grid = grid_for_rows(n, kBlock / lanes);
+    const int row_grid = capped_grid(n, kBlock / lanes);
     const int vgrid = vec_grid(n);
     const int nblocks = static_cast<int>(std::min<long long>(kNormaliseBlocks, (static_cast<long long>(n) + kBlock - 1) / kBlock));
     const int w = k <= 4 ? 4 : 8;

@@ -29,11 +29,12 @@ namespace reorder {
 namespace {
 
 using dev::block_max;
+using dev::capped_grid;
 using dev::group_or;
 using dev::kBlock;
-using dev::kMaxResidentBlocks;
+using dev::vec_grid;
+using dev::with_lanes;
 
-constexpr int kRoundsPerBatch = 8;      // rounds enqueued between two looks at the count of vertices left
 constexpr int kInfoGrid = 1024;         // workgroups (and partial slots) of the reductions read back by the host
 
 // the device state of one colouring; remaining[r % 3] = vertices still uncoloured after round r
@@ -346,16 +347,11 @@ __global__ __launch_bounds__(kBlock) void gather_kernel(float* __restrict__ out,
     }
 }
 
-int grid_for(long long work, int per_block, int cap = kMaxResidentBlocks) {
-    const long long blocks = (work + per_block - 1) / per_block;
-    return static_cast<int>(std::max(1LL, std::min<long long>(blocks, cap)));
-}
-
 // A's structure checked on the device: *d_flag (zeroed by the caller) becomes 1 when it is bad; not waited for
 hipError_t enqueue_validate(const CSRMatrix* A, int* d_flag, hipStream_t s) {
     const long long work = std::max<long long>(A->nnz, static_cast<long long>(A->num_rows) + 1);
-    reorder_validate_kernel<<<grid_for(work, kBlock), kBlock, 0, s>>>(A->d_row_ptrs, A->d_col_indices, A->num_rows,
-                                                                      A->num_cols, A->nnz, d_flag);
+    reorder_validate_kernel<<<capped_grid(work, kBlock), kBlock, 0, s>>>(A->d_row_ptrs, A->d_col_indices, A->num_rows,
+                                                                         A->num_cols, A->nnz, d_flag);
     return hipGetLastError();
 }
 
@@ -390,20 +386,14 @@ int fail(ColorResult* result, SpMVError e) {
 int color(const CSRMatrix* A, int* d_colors, const ColorConfig& cfg, ColorResult* result, hipStream_t s) {
     const int n = A->num_rows;
     solver::Workspace<ColorState> ws;
-    DevBuf<int> flag, partial;
-    if (!ws.allocate(0, 0) || dev_alloc(&flag, 1) != hipSuccess || dev_alloc(&partial, solver::kVecBlocks) != hipSuccess) {
+    DevBuf<int> partial;
+    if (!ws.allocate(0, 0) || dev_alloc(&partial, dev::kVecBlocks) != hipSuccess) {
         return fail(result, SpMVError::CUDA_MALLOC);
     }
     // the device pass over the structure, before anything walks it and before d_colors is written
-    int bad = 0;
-    if (hipMemsetAsync(flag.get(), 0, sizeof(int), s) != hipSuccess ||
-        enqueue_validate(A, flag.get(), s) != hipSuccess ||
-        hipMemcpyAsync(&bad, flag.get(), sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {
-        return fail(result, SpMVError::KERNEL_LAUNCH);
-    }
-    result->launches = 1;
-    if (bad) return fail(result, SpMVError::INVALID_FORMAT);
+    const int checked = structure_checked(A, s);
+    if (checked == 0 || checked == code(SpMVError::INVALID_FORMAT)) result->launches = 1;    // the check ran
+    if (checked != 0) return fail(result, static_cast<SpMVError>(checked));
 
     TransposeArrays at;
     struct Release {
@@ -422,47 +412,22 @@ int color(const CSRMatrix* A, int* d_colors, const ColorConfig& cfg, ColorResult
     const int lanes = cfg.lanes_per_row != 0
                           ? cfg.lanes_per_row
                           : pick_lanes_per_row(static_cast<float>(A->nnz) / static_cast<float>(n));
-    const int grid = solver::grid_for_rows(n, kBlock / lanes);
+    const int grid = capped_grid(n, kBlock / lanes);
     EventPair& ev = thread_events();
     if (!ev.start || !ev.stop || hipEventRecord(ev.start, s) != hipSuccess) return fail(result, SpMVError::KERNEL_LAUNCH);
-    color_init_kernel<<<solver::vec_grid(n), kBlock, 0, s>>>(n, d_colors, ws.state);
+    color_init_kernel<<<vec_grid(n), kBlock, 0, s>>>(n, d_colors, ws.state);
     bool ok = hipGetLastError() == hipSuccess;
     ++result->launches;
-
-    // Batches of rounds, each followed by a copy of the state; batch b + 1 is enqueued before batch b's copy is looked
-    // at.  The highest-priority uncoloured vertex always colours, so n rounds are enough for any graph.
-    int enqueued = 0;
-    int enqueued_at[2] = {0, 0};
-    bool done = false;
-    for (long long batch = 0; ok && !done; ++batch) {
-        const int todo = std::min(kRoundsPerBatch, n - enqueued);
-        for (int t = 0; t < todo && ok; ++t) {
-            ok = solver::with_lanes(lanes, [&](auto L) {
-                color_round_kernel<decltype(L)::value><<<grid, kBlock, 0, s>>>(
-                    n, A->d_row_ptrs, A->d_col_indices, at.row_ptrs, at.col_indices, cfg.seed, d_colors, ws.state,
-                    enqueued);
-                return hipGetLastError();
-            }) == hipSuccess;
-            ++enqueued;
-            ++result->launches;
-        }
-        enqueued_at[batch & 1] = enqueued;
-        ok = ok && ws.publish(batch, sizeof(ColorState), s);
-        const bool last = enqueued >= n;
-        const long long look = last ? batch + 1 : batch;          // the last batch is waited for at once
-        if (ok && look >= 1) {
-            const ColorState* st = ws.wait_previous(look);
-            ok = st != nullptr;
-            if (ok) {
-                const int seen_rounds = st->rounds;
-                done = seen_rounds < enqueued_at[(look - 1) & 1] ||
-                       (seen_rounds >= 1 && st->remaining[(seen_rounds - 1) % 3] == 0);
-            }
-            if (ok && last && !done) ok = false;                  // cannot happen: n rounds colour n vertices
-        }
-    }
+    ok = ok && solver::run_rounds(n, ws, s, [&](int round) {
+        ++result->launches;
+        return with_lanes(lanes, [&](auto L) {
+            color_round_kernel<decltype(L)::value><<<grid, kBlock, 0, s>>>(
+                n, A->d_row_ptrs, A->d_col_indices, at.row_ptrs, at.col_indices, cfg.seed, d_colors, ws.state, round);
+            return hipGetLastError();
+        });
+    });
     if (ok) {
-        const int blocks = solver::vec_grid(n);
+        const int blocks = vec_grid(n);
         max_partial_kernel<<<blocks, kBlock, 0, s>>>(n, d_colors, partial.get());
         color_count_kernel<<<1, kBlock, 0, s>>>(partial.get(), blocks, ws.state);
         ok = hipGetLastError() == hipSuccess;
@@ -483,8 +448,7 @@ int ordering(int n, const int* d_colors, int num_colors, int* d_perm, int* d_inv
         (void)hipGetLastError();
         return code(SpMVError::CUDA_MALLOC);
     }
-    iota_kernel<<<solver::vec_grid(static_cast<long long>(n) + 1), kBlock, 0, s>>>(static_cast<long long>(n) + 1,
-                                                                                   iota.get());
+    iota_kernel<<<vec_grid(static_cast<long long>(n) + 1), kBlock, 0, s>>>(static_cast<long long>(n) + 1, iota.get());
     if (hipGetLastError() != hipSuccess) return code(SpMVError::KERNEL_LAUNCH);
     // the n x num_colors matrix with the entry (i, colour[i]) in row i: row c of its transpose lists the vertices of
     // colour c in ascending order.  The values are never looked at: the colours stand in for them.
@@ -499,7 +463,7 @@ int ordering(int n, const int* d_colors, int num_colors, int* d_perm, int* d_inv
     const int status = transpose_build(&byrow, &bycolor, s);
     if (status == code(SpMVError::INVALID_FORMAT)) return code(SpMVError::INVALID_ARGUMENT);    // a colour out of range
     if (status != 0) return status;
-    ordering_kernel<<<solver::vec_grid(n), kBlock, 0, s>>>(n, bycolor.col_indices, d_perm, d_inverse);
+    ordering_kernel<<<vec_grid(n), kBlock, 0, s>>>(n, bycolor.col_indices, d_perm, d_inverse);
     bool ok = hipGetLastError() == hipSuccess;
     if (ok && color_ptr) {
         ok = hipMemcpyAsync(color_ptr, bycolor.row_ptrs, (static_cast<size_t>(num_colors) + 1) * sizeof(int),
@@ -538,7 +502,7 @@ int permute(CSRMatrix* B, const CSRMatrix* A, const int* d_row_perm, const int* 
     }
 
     // ---- the device checks and the row lengths, one read-back ----
-    const int grid = grid_for(std::max<long long>(static_cast<long long>(rows) + 1, cols), kBlock, kInfoGrid);
+    const int grid = capped_grid(std::max<long long>(static_cast<long long>(rows) + 1, cols), kBlock, kInfoGrid);
     std::vector<int> info(2 + static_cast<size_t>(grid));
     DevBuf<int> d_info, seen_rows, seen_cols;
     bool got = dev_alloc(&d_info, static_cast<long long>(info.size())) == hipSuccess &&
@@ -555,7 +519,7 @@ int permute(CSRMatrix* B, const CSRMatrix* A, const int* d_row_perm, const int* 
     if (ok) {
         ok = enqueue_validate(A, d_info.get(), s) == hipSuccess;
         if (d_row_perm || d_col_inverse) {
-            permute_mark_kernel<<<grid_for(std::max(rows, cols), kBlock), kBlock, 0, s>>>(
+            permute_mark_kernel<<<capped_grid(std::max(rows, cols), kBlock), kBlock, 0, s>>>(
                 d_row_perm, rows, d_col_inverse, cols, seen_rows.get(), seen_cols.get(), d_info.get());
         }
         permute_lengths_kernel<<<grid, kBlock, 0, s>>>(A->d_row_ptrs, d_row_perm, rows, cols, seen_rows.get(),
@@ -590,16 +554,16 @@ int permute(CSRMatrix* B, const CSRMatrix* A, const int* d_row_perm, const int* 
     const unsigned* va = reinterpret_cast<const unsigned*>(A->d_values);
     unsigned* new_va = reinterpret_cast<unsigned*>(out.values);
     if (ok && nnz > 0 && longest <= kPermuteLds) {
-        permute_rows_kernel<kPermuteSlice><<<solver::grid_for_rows(rows, kBlock / kPermuteSlice), kBlock, 0, s>>>(
+        permute_rows_kernel<kPermuteSlice><<<capped_grid(rows, kBlock / kPermuteSlice), kBlock, 0, s>>>(
             rows, 0, A->d_row_ptrs, A->d_col_indices, va, d_row_perm, d_col_inverse, out.row_ptrs, out.col_indices,
             new_va);
         if (longest > kPermuteSlice) {
-            permute_rows_kernel<kPermuteWave><<<solver::grid_for_rows(rows, kBlock / kPermuteWave), kBlock, 0, s>>>(
+            permute_rows_kernel<kPermuteWave><<<capped_grid(rows, kBlock / kPermuteWave), kBlock, 0, s>>>(
                 rows, kPermuteSlice, A->d_row_ptrs, A->d_col_indices, va, d_row_perm, d_col_inverse, out.row_ptrs,
                 out.col_indices, new_va);
         }
         if (longest > kPermuteWave) {
-            permute_long_rows_kernel<<<solver::grid_for_rows(rows, kBlock), kBlock, 0, s>>>(
+            permute_long_rows_kernel<<<capped_grid(rows, kBlock), kBlock, 0, s>>>(
                 rows, A->d_row_ptrs, A->d_col_indices, va, d_row_perm, d_col_inverse, out.row_ptrs, out.col_indices,
                 new_va);
         }
@@ -608,7 +572,7 @@ int permute(CSRMatrix* B, const CSRMatrix* A, const int* d_row_perm, const int* 
         // A row past the LDS class: the whole matrix relabelled in A's storage order, then transposed twice.  The
         // stable sort of the first transpose orders every column by row, that of the second every row by (column,
         // position): the order the ranking kernels produce.
-        permute_relabel_kernel<<<solver::grid_for_rows(rows, kBlock / 64), kBlock, 0, s>>>(
+        permute_relabel_kernel<<<capped_grid(rows, kBlock / 64), kBlock, 0, s>>>(
             rows, A->d_row_ptrs, A->d_col_indices, va, d_row_perm, d_col_inverse, out.row_ptrs, out.col_indices, new_va);
         if (hipGetLastError() != hipSuccess) return code(SpMVError::KERNEL_LAUNCH);
         CSRMatrix relabelled{};
@@ -648,8 +612,21 @@ int permute(CSRMatrix* B, const CSRMatrix* A, const int* d_row_perm, const int* 
 
 } // namespace reorder
 
-hipError_t enqueue_structure_check(const CSRMatrix* A, int* d_flag, hipStream_t s) {
-    return reorder::enqueue_validate(A, d_flag, s);
+int structure_checked(const CSRMatrix* A, hipStream_t s) {
+    DevBuf<int> flag;
+    if (dev_alloc(&flag, 1) != hipSuccess) {
+        (void)hipGetLastError();
+        return code(SpMVError::CUDA_MALLOC);
+    }
+    int bad = 0;
+    if (hipMemsetAsync(flag.get(), 0, sizeof(int), s) != hipSuccess ||
+        reorder::enqueue_validate(A, flag.get(), s) != hipSuccess ||
+        hipMemcpyAsync(&bad, flag.get(), sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess) {
+        (void)hipGetLastError();
+        return code(SpMVError::KERNEL_LAUNCH);
+    }
+    return bad ? code(SpMVError::INVALID_FORMAT) : 0;
 }
 
 } // namespace detail
@@ -691,7 +668,7 @@ int permute_gather_async(float* d_out, int ldo, const float* d_in, int ldi, cons
     bool nothing = false;
     const int status = reorder::gather_check(d_out, ldo, d_in, ldi, d_index, n, k, &nothing);
     if (status != 0 || nothing) return status;
-    reorder::gather_kernel<<<reorder::grid_for(static_cast<long long>(n) * k, reorder::kBlock), reorder::kBlock, 0,
+    reorder::gather_kernel<<<dev::capped_grid(static_cast<long long>(n) * k, reorder::kBlock), reorder::kBlock, 0,
                              stream>>>(d_out, ldo, d_in, ldi, d_index, n, k);
     return hipGetLastError() == hipSuccess ? 0 : code(SpMVError::KERNEL_LAUNCH);
 }

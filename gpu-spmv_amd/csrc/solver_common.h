@@ -1,14 +1,15 @@
 // solver_common.h — what the device-resident iterative solvers (cg.hip, cg_multi.hip, bicgstab.hip, gmres.hip,
 // eigs.hip) share.
 // Device side: the deterministic fp64 dot-product partials and their fixed-order fold, and diag_kernel, the one
-// setup kernel that sums every row's diagonal.  Host side: the grid sizes, the LANES dispatch of the vector-CSR
-// kernels, the argument predicates (device_arrays, ranges_overlap), and the parts every solve() is built from:
+// setup kernel that sums every row's diagonal.  Host side: the argument predicates (device_arrays, ranges_overlap),
+// and the parts every solve() is built from:
 //   Workspace<State>   the device memory of one solve, the two-deep pinned mirror of its state (publish /
 //                      wait_previous) and the blocking read-backs (read_back, finish_timed)
+//   run_rounds         the host loop of the algorithms in rounds (csr_color, MIS-2), built on that mirror
 //   TriangularPair     M given as two triangles in one CSR matrix (IC, ILU): both schedules, then apply()
 //   TiledEngine        the LDS-tiled engine's part in one solve: when the plan is built, and when it is dropped
-// Each solver keeps its own loop and its own order of checks; nothing here calls back into one.  Internal: not
-// installed under include/.
+// Each solver keeps its own loop and its own order of checks; nothing here calls back into one.  The launch layer
+// (grid sizes, with_lanes) is device_common.h's, for every kernel file.  Internal: not installed under include/.
 #ifndef SPMV_AMD_SOLVER_COMMON_H
 #define SPMV_AMD_SOLVER_COMMON_H
 
@@ -31,8 +32,9 @@ namespace solver {
 
 using dev::kBlock;
 using dev::kMaxResidentBlocks;
-
-constexpr int kVecBlocks = 1024;      // workgroups of the element-wise kernels (4 per CU)
+using dev::capped_grid;
+using dev::vec_grid;
+using dev::with_lanes;
 
 // Sums part[i * stride] (and part[i * stride + 1] when stride > 1 and `pair`) over i < count in a fixed order,
 // broadcast to every thread: each thread folds a fixed strided subset, then block_sum2's fixed butterfly and wave
@@ -91,26 +93,6 @@ void diag_kernel(int n, const int* __restrict__ row_ptrs, const int* __restrict_
         bad |= !ok;
     }
     if (__any(bad) && (threadIdx.x & 63) == 0) *bad_flag = 1;
-}
-
-inline int grid_for_rows(long long rows, int rows_per_block) { return dev::capped_grid(rows, rows_per_block); }
-
-inline int vec_grid(long long n) {
-    return static_cast<int>(std::max(1LL, std::min<long long>((n + kBlock - 1) / kBlock, kVecBlocks)));
-}
-
-// Calls launch(std::integral_constant<int, LANES>{}) for the LANES pick_lanes_per_row chose (64 for anything else).
-template <class Launch>
-hipError_t with_lanes(int lanes, Launch&& launch) {
-    switch (lanes) {
-        case 1:  return launch(std::integral_constant<int, 1>{});
-        case 2:  return launch(std::integral_constant<int, 2>{});
-        case 4:  return launch(std::integral_constant<int, 4>{});
-        case 8:  return launch(std::integral_constant<int, 8>{});
-        case 16: return launch(std::integral_constant<int, 16>{});
-        case 32: return launch(std::integral_constant<int, 32>{});
-        default: return launch(std::integral_constant<int, 64>{});
-    }
 }
 
 inline bool ranges_overlap(const float* a, const float* b, long long n) {
@@ -227,6 +209,46 @@ struct Workspace {
         for (hipEvent_t e : seen) if (e) (void)hipEventDestroy(e);
     }
 };
+
+constexpr int kRoundsPerBatch = 8;      // rounds enqueued between two looks at the count of vertices left
+
+// The host loop of a Jones-Plassmann algorithm in rounds over n >= 1 vertices (csr_color, the MIS-2 aggregation).
+// State, the device state `ws` mirrors, holds `int remaining[3]` (remaining[r % 3] = vertices still undecided after
+// round r) and `int rounds` (rounds that found something to do); the round kernels keep both.  enqueue_round(r)
+// enqueues round r = 0, 1, ... on `s` and returns its hipError_t.
+// Batches of kRoundsPerBatch rounds, each followed by a copy of the state; batch b + 1 is enqueued before batch b's
+// copy is looked at, and the last batch is waited for at once.  The highest-priority undecided vertex always decides,
+// so n rounds are enough for any graph; a copy that shows fewer rounds than had been enqueued by then shows a round
+// that found nothing to do, which ends the loop as remaining == 0 after the last counted round does.  false when a
+// call fails.
+template <class State, class EnqueueRound>
+bool run_rounds(int n, Workspace<State>& ws, hipStream_t s, EnqueueRound&& enqueue_round) {
+    int enqueued = 0;
+    int enqueued_at[2] = {0, 0};
+    bool ok = true, done = false;
+    for (long long batch = 0; ok && !done; ++batch) {
+        const int todo = std::min(kRoundsPerBatch, n - enqueued);
+        for (int t = 0; t < todo && ok; ++t) {
+            ok = enqueue_round(enqueued) == hipSuccess;
+            ++enqueued;
+        }
+        enqueued_at[batch & 1] = enqueued;
+        ok = ok && ws.publish(batch, sizeof(State), s);
+        const bool last = enqueued >= n;
+        const long long look = last ? batch + 1 : batch;          // the last batch is waited for at once
+        if (ok && look >= 1) {
+            const State* st = ws.wait_previous(look);
+            ok = st != nullptr;
+            if (ok) {
+                const int seen_rounds = st->rounds;
+                done = seen_rounds < enqueued_at[(look - 1) & 1] ||
+                       (seen_rounds >= 1 && st->remaining[(seen_rounds - 1) % 3] == 0);
+            }
+            if (ok && last && !done) ok = false;                  // cannot happen: n rounds decide n vertices
+        }
+    }
+    return ok;
+}
 
 // The LDS-tiled engine's part in one solve of A (pagerank()'s rule): engine 1 builds the plan at once, 0 never uses
 // one, -1 takes a cached plan from the start, else builds one after 4 direct steps if A is eligible.

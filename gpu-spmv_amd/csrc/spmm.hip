@@ -371,15 +371,7 @@ hipError_t launch_split(const CSRMatrix* A, const float* X, int ldx, float* Y, i
 template <int K>
 hipError_t launch_split_lanes(const CSRMatrix* A, const float* X, int ldx, float* Y, int ldy, int lanes,
                               hipStream_t s) {
-    switch (lanes) {
-        case 1:  return launch_split<K, 1>(A, X, ldx, Y, ldy, s);
-        case 2:  return launch_split<K, 2>(A, X, ldx, Y, ldy, s);
-        case 4:  return launch_split<K, 4>(A, X, ldx, Y, ldy, s);
-        case 8:  return launch_split<K, 8>(A, X, ldx, Y, ldy, s);
-        case 16: return launch_split<K, 16>(A, X, ldx, Y, ldy, s);
-        case 32: return launch_split<K, 32>(A, X, ldx, Y, ldy, s);
-        default: return launch_split<K, 64>(A, X, ldx, Y, ldy, s);
-    }
+    return with_lanes(lanes, [&](auto L) { return launch_split<K, decltype(L)::value>(A, X, ldx, Y, ldy, s); });
 }
 
 int multi_num_tiles(const CSRMatrix* A) {

@@ -89,7 +89,7 @@ hipError_t launch_groups(const SptrsvSchedule& sch, const CSRMatrix* A, const fl
     constexpr int kRowsPerBlock = kBlock / LANES;
     for (const SptrsvSchedule::Group& g : sch.groups) {
         // a run of levels is one workgroup (the barrier is its only ordering); one level alone takes a grid
-        const int grid = g.level_end - g.level_begin > 1 ? 1 : solver::grid_for_rows(g.rows, kRowsPerBlock);
+        const int grid = g.level_end - g.level_begin > 1 ? 1 : capped_grid(g.rows, kRowsPerBlock);
         sptrsv_kernel<LANES, ORDERED><<<grid, kBlock, 0, s>>>(A->num_rows, A->nnz, A->d_row_ptrs, A->d_col_indices,
                                                              A->d_values, b, x, sch.d_level_ptr, sch.d_order,
                                                              g.level_begin, g.level_end, upper, unit);
@@ -108,7 +108,7 @@ bool sptrsv_partial_overlap(const float* d_b, const float* d_x, long long n) {
 hipError_t launch_sptrsv(const SptrsvSchedule& schedule, const CSRMatrix* A, const float* d_b, float* d_x, int uplo,
                          int unit_diagonal, bool ordered, int lanes_per_row, hipStream_t s) {
     if (ordered) return launch_groups<1, true>(schedule, A, d_b, d_x, uplo, unit_diagonal, s);
-    return solver::with_lanes(lanes_per_row, [&](auto L) {
+    return with_lanes(lanes_per_row, [&](auto L) {
         return launch_groups<decltype(L)::value, false>(schedule, A, d_b, d_x, uplo, unit_diagonal, s);
     });
 }

@@ -20,7 +20,6 @@
 #include "internal.h"
 #include "device_common.h"
 #include "multi_window.h"
-#include "solver_common.h"
 
 #include <hip/hip_runtime.h>
 
@@ -131,7 +130,7 @@ hipError_t launch_groups(const SptrsvSchedule& sch, const CSRMatrix* A, const Sp
                       (vec(a.X, a.ldx, a.x_window) ? kVecX : 0);
     for (const SptrsvSchedule::Group& g : sch.groups) {
         // a run of levels is one workgroup (the barrier is its only ordering); one level alone takes a grid
-        const int grid = g.level_end - g.level_begin > 1 ? 1 : solver::grid_for_rows(g.rows, kRowsPerBlock);
+        const int grid = g.level_end - g.level_begin > 1 ? 1 : capped_grid(g.rows, kRowsPerBlock);
         sptrsv_multi_kernel<LANES, W, WS, ORDERED><<<grid, kBlock, 0, s>>>(
             A->num_rows, A->nnz, A->d_row_ptrs, A->d_col_indices, A->d_values, a.B, a.ldb, a.b_window, a.X, a.ldx,
             a.x_window, a.k, sch.d_level_ptr, sch.d_order, g.level_begin, g.level_end, flags);
@@ -147,7 +146,7 @@ template <int WS>
 hipError_t launch_width(const SptrsvSchedule& schedule, const CSRMatrix* A, const SptrsvMultiArrays& a, int uplo,
                         int unit_diagonal, bool ordered, int lanes_per_row, hipStream_t s) {
     if (ordered) return launch_groups<1, WS, WS, true>(schedule, A, a, uplo, unit_diagonal, s);
-    return solver::with_lanes(lanes_per_row, [&](auto L) {
+    return with_lanes(lanes_per_row, [&](auto L) {
         constexpr int kLanes = decltype(L)::value;
         constexpr int kW = kLanes >= 32 ? 4 : WS;
         return launch_groups<kLanes, kW, WS, false>(schedule, A, a, uplo, unit_diagonal, s);

@@ -94,6 +94,9 @@ class Graph:
 COLOR_CASES = dict(rc.SMALL)
 COLOR_CASES.update(rc.LIBRARY)
 COLOR_CASES.update({
+    # a complete graph takes n rounds: below, at and just past one and two batches of 8 rounds of the host loop
+    "K7": lambda: rc.complete(7), "K8": lambda: rc.complete(8), "K9": lambda: rc.complete(9),
+    "K16": lambda: rc.complete(16), "K17": lambda: rc.complete(17),
     "K64": lambda: rc.complete(64), "K65": lambda: rc.complete(65), "K130": lambda: rc.complete(130),
     "star(5000)": lambda: rc.star(5000), "path(1000)": lambda: rc.path(1000),
     "upper_bidiagonal(300)": lambda: rc.upper_bidiagonal(300),
@@ -126,7 +129,8 @@ def test_color_equals_the_host_colouring(gpu, graphs, name):
 def test_known_colour_counts(gpu, graphs):
     assert graphs("single").want()[1:] == (1, 1) and graphs("diagonal_only").want()[1:] == (1, 1)
     assert graphs("edge").want()[1] == 2
-    for name, n in (("K64", 64), ("K65", 65), ("K130", 130)):       # one colour per vertex: 0, 1 and 2 window moves
+    # one colour per vertex, one vertex per round; K64, K65, K130: 0, 1 and 2 window moves
+    for name, n in (("K7", 7), ("K8", 8), ("K9", 9), ("K16", 16), ("K17", 17), ("K64", 64), ("K65", 65), ("K130", 130)):
         colors, count, rounds = graphs(name).want()
         assert count == n == rounds and sorted(colors) == list(range(n))
     for name in ("poisson2d(24)", "poisson3d(8)", "random_spd(500, 7, 3)"):
