@@ -224,6 +224,13 @@ class SpTRSVResult(Structure):
                 ("lanes_per_row", c_int32), ("analysis_ms", c_float), ("elapsed_ms", c_float)]
 
 
+class SpTRSVScheduleInfo(Structure):
+    """include/spmv/sptrsv.h SpTRSVScheduleInfo (32 bytes): what a cached level schedule holds besides its arrays"""
+    _fields_ = [("num_levels", c_int32), ("launches", c_int32), ("first_missing_diagonal", c_int32),
+                ("first_unsorted_row", c_int32), ("one_sided_row", c_int32), ("built_on_device", c_int32),
+                ("triangle_nnz", c_int64)]
+
+
 class ILU0Result(Structure):
     """include/spmv/ilu0.h ILU0Result (28 bytes); zero_pivot is the lowest row with a zero or non-finite u_ii, or -1"""
     _fields_ = [("error_code", c_int32), ("num_levels", c_int32), ("launches", c_int32),
@@ -417,6 +424,9 @@ _SIGNATURES = {
                                   POINTER(SpTRSVResult)]),
     "spmv_c_sptrsv_csr_async": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(SpTRSVConfig), c_void_p]),
     "spmv_c_sptrsv_analyze": (c_int, [POINTER(CSRMatrix), c_int, POINTER(SpTRSVResult)]),
+    "spmv_c_sptrsv_analyze_device": (c_int, [POINTER(CSRMatrix), c_int, POINTER(SpTRSVResult)]),
+    "spmv_c_sptrsv_schedule_get": (c_int, [POINTER(CSRMatrix), c_int, c_void_p, c_void_p,
+                                           POINTER(SpTRSVScheduleInfo)]),
     "spmv_c_sptrsv_cpu_csr": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(SpTRSVConfig)]),
     "spmv_c_sptrsv_csr_multi": (c_int, [POINTER(CSRMatrix), c_void_p, c_int, c_void_p, c_int, c_int,
                                         POINTER(SpTRSVConfig), POINTER(SpTRSVResult)]),
@@ -1282,6 +1292,31 @@ def sptrsv_analyze(A, uplo=0) -> SpTRSVResult:
     out = SpTRSVResult()
     lib().spmv_c_sptrsv_analyze(A, int(uplo), byref(out))
     return out
+
+
+def sptrsv_analyze_device(A, uplo=0) -> SpTRSVResult:
+    """sptrsv_analyze with the analysis run on the device: no array of A crosses the bus (include/spmv/sptrsv.h
+    sptrsv_analyze_device)."""
+    out = SpTRSVResult()
+    lib().spmv_c_sptrsv_analyze_device(A, int(uplo), byref(out))
+    return out
+
+
+def sptrsv_schedule_get(A, uplo=0, arrays=True):
+    """The cached level schedule of (A, uplo), of either origin (include/spmv/sptrsv.h sptrsv_schedule_get):
+    (status, level_ptr[num_levels + 1], order[num_rows], SpTRSVScheduleInfo); (status, None, None, None) when the call
+    is rejected (no schedule cached: INVALID_ARGUMENT).  arrays=False asks for the info alone."""
+    info = SpTRSVScheduleInfo()
+    if A is None or not arrays:
+        status = lib().spmv_c_sptrsv_schedule_get(A, int(uplo), None, None, byref(info))
+        return (status, None, None, info) if status == 0 else (status, None, None, None)
+    rows = max(int(A.contents.num_rows), 0)
+    level_ptr = np.zeros(rows + 1, dtype=np.int32)
+    order = np.zeros(rows, dtype=np.int32)
+    status = lib().spmv_c_sptrsv_schedule_get(A, int(uplo), _np_ptr(level_ptr), _np_ptr(order), byref(info))
+    if status != 0:
+        return status, None, None, None
+    return status, level_ptr[:info.num_levels + 1].copy(), order, info
 
 
 def sptrsv_cpu_csr(A, b, config=None) -> np.ndarray:

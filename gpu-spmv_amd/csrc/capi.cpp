@@ -103,6 +103,17 @@ static_assert(offsetof(spmv_c_sptrsv_config, diag) == offsetof(SpTRSVConfig, dia
               offsetof(spmv_c_sptrsv_config, ordered) == offsetof(SpTRSVConfig, ordered) &&
               offsetof(spmv_c_sptrsv_config, reserved) == offsetof(SpTRSVConfig, reserved), "SpTRSVConfig layout");
 static_assert(sizeof(spmv_c_sptrsv_result) == sizeof(SpTRSVResult) && sizeof(SpTRSVResult) == 24, "SpTRSVResult layout");
+static_assert(sizeof(spmv_c_sptrsv_schedule_info) == sizeof(SpTRSVScheduleInfo) && sizeof(SpTRSVScheduleInfo) == 32,
+              "SpTRSVScheduleInfo layout");
+static_assert(offsetof(spmv_c_sptrsv_schedule_info, launches) == offsetof(SpTRSVScheduleInfo, launches) &&
+              offsetof(spmv_c_sptrsv_schedule_info, first_missing_diagonal) ==
+                  offsetof(SpTRSVScheduleInfo, first_missing_diagonal) &&
+              offsetof(spmv_c_sptrsv_schedule_info, first_unsorted_row) ==
+                  offsetof(SpTRSVScheduleInfo, first_unsorted_row) &&
+              offsetof(spmv_c_sptrsv_schedule_info, one_sided_row) == offsetof(SpTRSVScheduleInfo, one_sided_row) &&
+              offsetof(spmv_c_sptrsv_schedule_info, built_on_device) == offsetof(SpTRSVScheduleInfo, built_on_device) &&
+              offsetof(spmv_c_sptrsv_schedule_info, triangle_nnz) == offsetof(SpTRSVScheduleInfo, triangle_nnz) &&
+              offsetof(SpTRSVScheduleInfo, triangle_nnz) == 24, "SpTRSVScheduleInfo layout");
 static_assert(sizeof(spmv_c_ilu0_result) == sizeof(ILU0Result) && sizeof(ILU0Result) == 28, "ILU0Result layout");
 static_assert(offsetof(spmv_c_ilu0_result, num_levels) == offsetof(ILU0Result, num_levels) &&
               offsetof(spmv_c_ilu0_result, launches) == offsetof(ILU0Result, launches) &&
@@ -731,6 +742,17 @@ int spmv_c_sptrsv_analyze(const spmv_c_csr* A, int uplo, spmv_c_sptrsv_result* o
     const SpTRSVResult r = sptrsv_analyze(cxx(A), uplo);
     if (out) std::memcpy(out, &r, sizeof(r));
     return r.error_code;
+}
+
+int spmv_c_sptrsv_analyze_device(const spmv_c_csr* A, int uplo, spmv_c_sptrsv_result* out) {
+    const SpTRSVResult r = sptrsv_analyze_device(cxx(A), uplo);
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
+}
+
+int spmv_c_sptrsv_schedule_get(const spmv_c_csr* A, int uplo, int32_t* level_ptr, int32_t* order,
+                               spmv_c_sptrsv_schedule_info* info) {
+    return sptrsv_schedule_get(cxx(A), uplo, level_ptr, order, reinterpret_cast<SpTRSVScheduleInfo*>(info));
 }
 
 int spmv_c_sptrsv_cpu_csr(const spmv_c_csr* A, const float* b, float* x, const spmv_c_sptrsv_config* config) {

@@ -80,6 +80,9 @@ struct SptrsvSchedule {
     // LOWER schedules of a sorted matrix with every diagonal: a row holding a stored (i,k) whose (k,i) is not stored,
     // or -1 when the pattern is structurally symmetric (ic0_csr needs that); -1 where it was not tested
     int  one_sided_row = -1;
+    // built by sptrsv_analysis.hip: the same ints, except that one_sided_row is the LOWEST row that stores an (i,k),
+    // k != i, whose (k,i) is not stored (the host pass may name another row of the same pattern; the sign agrees)
+    bool built_on_device = false;
     // what it was built from (the transpose cache's rule)
     const void* row_ptrs = nullptr;
     const void* cols = nullptr;
@@ -185,6 +188,11 @@ void    ell_aux_drop(const void* key);
 //   pr_plan_after=N            direct steps pagerank() takes before it builds a plan (default 4)
 //   pr_copy=pageable           pagerank() copies its result into a pageable array (no pinned pool)
 //   sptrsv_lanes=N             lanes per row of sptrsv_csr with ordered = 0 (1, 2, 4, ... 64; anything else is ignored)
+//   sptrsv_analysis=device     every implicit level analysis (the first solve or factorisation per matrix and triangle,
+//                              sptrsv_analyze) is built on the device, as sptrsv_analyze_device does; anything else:
+//                              on the host
+//   analysis_lanes=N           lanes per row of the device-side level analysis's kernels (1, 2, 4, ... 64; anything else
+//                              is ignored)
 //   ilu0_lanes=N               lanes per row of ilu0_csr (1, 2, 4, ... 64; anything else is ignored)
 //   ic0_lanes=N                lanes per row of ic0_csr (1, 2, 4, ... 64; anything else is ignored)
 //   spgemm_lanes=N             lanes per row of C in spgemm_csr (1, 2, 4, ... 64; anything else is ignored)
@@ -284,6 +292,13 @@ int sptrsv_check_matrix(const CSRMatrix* A, bool* nothing_to_do);
 int sptrsv_schedule_for(const CSRMatrix* A, int uplo, hipStream_t stream, std::shared_ptr<const SptrsvSchedule>* out,
                         float* analysis_ms);
 int sptrsv_lanes_for(const SptrsvSchedule& schedule);
+// The level analysis on the device (sptrsv_analysis.hip), for A that passed sptrsv_check_matrix and
+// has rows: structure_checked's rule first (INVALID_FORMAT before any kernel follows a row pointer or a column), then
+// d_level_ptr, d_order, num_levels, triangle_nnz, first_missing_diagonal, first_unsorted_row, one_sided_row and
+// built_on_device of *out, waited for on `s`; *level_ptr is the host copy of d_level_ptr the grouping needs.  On an
+// error *out owns nothing.
+int sptrsv_analysis_device(const CSRMatrix* A, int uplo, hipStream_t s, SptrsvSchedule* out,
+                           std::vector<int>* level_ptr);
 // The zero-fill factorisations (factor0.hip): the launches of one factorisation over A's LOWER schedule, in stream
 // order, from d_a (A's values) into d_out (may be the same array); then, when d_pivot is not null, the scan of the
 // finished diagonal that folds the lowest row with a bad pivot into it (an unsigned min; preset to all ones).

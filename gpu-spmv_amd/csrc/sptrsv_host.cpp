@@ -215,19 +215,9 @@ bool matches(const ScheduleRef& s, const CSRMatrix* A, int uplo) {
            s->num_rows == A->num_rows && s->num_cols == A->num_cols && s->uplo == uplo;
 }
 
-// A's schedule for `uplo` from its aux entry, built when it is not there or no longer matches A.  *analysis_ms is
-// the host time of a build, 0 for a cache hit.
-int schedule_for(const CSRMatrix* A, int uplo, hipStream_t stream, ScheduleRef* out, float* analysis_ms) {
-    *analysis_ms = 0.0f;
-    CsrAux* aux = aux_lookup(A->d_row_ptrs, true);
-    std::lock_guard<std::mutex> guard(aux->sptrsv_lock);
-    if (matches(aux->sptrsv[uplo], A, uplo)) {
-        *out = aux->sptrsv[uplo];
-        return code(SpMVError::SUCCESS);
-    }
-    aux->sptrsv[uplo].reset();
-    const TraceRange range("spmv:sptrsv_analysis");
-    const auto t0 = std::chrono::steady_clock::now();
+// The host analysis: one read-back of the structure, sptrsv_levels, the statistics, the upload.  *level_ptr is left
+// for the grouping.
+int build_on_host(const CSRMatrix* A, int uplo, hipStream_t stream, SptrsvSchedule* built, std::vector<int>* level_ptr) {
     const int n = A->num_rows;
     const size_t nnz = static_cast<size_t>(std::max(A->nnz, 0));
 
@@ -248,16 +238,15 @@ int schedule_for(const CSRMatrix* A, int uplo, hipStream_t stream, ScheduleRef* 
         if (row_ptrs[i + 1] < row_ptrs[i]) return code(SpMVError::INVALID_FORMAT);
     }
 
-    std::vector<int> level_ptr(static_cast<size_t>(n) + 1), order(static_cast<size_t>(n));
+    level_ptr->assign(static_cast<size_t>(n) + 1, 0);
+    std::vector<int> order(static_cast<size_t>(n));
     int num_levels = 0, missing = -1;
-    const int status = sptrsv_levels(n, row_ptrs.data(), cols.data(), uplo, level_ptr.data(), order.data(),
+    const int status = sptrsv_levels(n, row_ptrs.data(), cols.data(), uplo, level_ptr->data(), order.data(),
                                      &num_levels, &missing);
     if (status != 0) return status;
 
-    auto built = std::make_shared<SptrsvSchedule>();
     built->num_levels = num_levels;
     built->first_missing_diagonal = missing;
-    group_levels(level_ptr, num_levels, &built->groups);
     const bool upper = uplo == SpTRSVConfig::UPPER;
     for (int i = 0; i < n; ++i) {
         for (int j = row_ptrs[i]; j < row_ptrs[i + 1]; ++j) {
@@ -277,12 +266,38 @@ int schedule_for(const CSRMatrix* A, int uplo, hipStream_t stream, ScheduleRef* 
         (void)hipGetLastError();
         return code(SpMVError::CUDA_MALLOC);
     }
-    if (hipMemcpyAsync(built->d_level_ptr, level_ptr.data(), ptr_bytes, hipMemcpyHostToDevice, stream) != hipSuccess ||
+    if (hipMemcpyAsync(built->d_level_ptr, level_ptr->data(), ptr_bytes, hipMemcpyHostToDevice, stream) != hipSuccess ||
         hipMemcpyAsync(built->d_order, order.data(), order_bytes, hipMemcpyHostToDevice, stream) != hipSuccess ||
         hipStreamSynchronize(stream) != hipSuccess) {       // (the host vectors go away with this frame)
         (void)hipGetLastError();
         return code(SpMVError::CUDA_MEMCPY);
     }
+    return code(SpMVError::SUCCESS);
+}
+
+// A's schedule for `uplo` from its aux entry, built when it is not there or no longer matches A: on the device when
+// the caller asks for it or SPMV_DEBUG holds sptrsv_analysis=device, else on the host.  *analysis_ms is the wall time
+// of a build, 0 for a cache hit (of either origin).
+int schedule_for(const CSRMatrix* A, int uplo, hipStream_t stream, ScheduleRef* out, float* analysis_ms,
+                 bool on_device = false) {
+    *analysis_ms = 0.0f;
+    CsrAux* aux = aux_lookup(A->d_row_ptrs, true);
+    std::lock_guard<std::mutex> guard(aux->sptrsv_lock);
+    if (matches(aux->sptrsv[uplo], A, uplo)) {
+        *out = aux->sptrsv[uplo];
+        return code(SpMVError::SUCCESS);
+    }
+    aux->sptrsv[uplo].reset();
+    const TraceRange range("spmv:sptrsv_analysis");
+    const auto t0 = std::chrono::steady_clock::now();
+
+    auto built = std::make_shared<SptrsvSchedule>();
+    std::vector<int> level_ptr;
+    const int status = on_device || debug_is("sptrsv_analysis", "device")
+                           ? sptrsv_analysis_device(A, uplo, stream, built.get(), &level_ptr)
+                           : build_on_host(A, uplo, stream, built.get(), &level_ptr);
+    if (status != 0) return status;
+    group_levels(level_ptr, built->num_levels, &built->groups);
     built->row_ptrs = A->d_row_ptrs;
     built->cols = A->d_col_indices;
     built->nnz = A->nnz;
@@ -495,8 +510,11 @@ int sptrsv_csr_multi_async(const CSRMatrix* A, const float* d_B, int ldb, float*
     return e == hipSuccess ? code(SpMVError::SUCCESS) : code(SpMVError::KERNEL_LAUNCH);
 }
 
-SpTRSVResult sptrsv_analyze(const CSRMatrix* A, int uplo) {
-    using namespace detail;
+namespace detail {
+namespace {
+
+// sptrsv_analyze and sptrsv_analyze_device: the same checks in the same order, then the cache
+SpTRSVResult analyze(const CSRMatrix* A, int uplo, bool on_device) {
     SpTRSVResult result;
     if (!A) {
         result.error_code = code(SpMVError::INVALID_ARGUMENT);
@@ -510,11 +528,49 @@ SpTRSVResult sptrsv_analyze(const CSRMatrix* A, int uplo) {
         return result;
     }
     ScheduleRef schedule;
-    result.error_code = schedule_for(A, uplo, current_stream(), &schedule, &result.analysis_ms);
+    result.error_code = schedule_for(A, uplo, current_stream(), &schedule, &result.analysis_ms, on_device);
     if (result.error_code != 0) return result;
     result.num_levels = schedule->num_levels;
     result.launches = static_cast<int>(schedule->groups.size());
     return result;
+}
+
+} // namespace
+} // namespace detail
+
+SpTRSVResult sptrsv_analyze(const CSRMatrix* A, int uplo) { return detail::analyze(A, uplo, false); }
+
+SpTRSVResult sptrsv_analyze_device(const CSRMatrix* A, int uplo) { return detail::analyze(A, uplo, true); }
+
+int sptrsv_schedule_get(const CSRMatrix* A, int uplo, int* level_ptr, int* order, SpTRSVScheduleInfo* info) {
+    using namespace detail;
+    if (!A) return code(SpMVError::INVALID_ARGUMENT);
+    if (uplo != SpTRSVConfig::LOWER && uplo != SpTRSVConfig::UPPER) return code(SpMVError::INVALID_ARGUMENT);
+    ScheduleRef schedule;
+    if (CsrAux* aux = aux_lookup(A->d_row_ptrs, false)) {
+        std::lock_guard<std::mutex> guard(aux->sptrsv_lock);
+        if (matches(aux->sptrsv[uplo], A, uplo)) schedule = aux->sptrsv[uplo];
+    }
+    if (!schedule) return code(SpMVError::INVALID_ARGUMENT);
+    // (a cached schedule is complete: its build waited for the stream)
+    if ((level_ptr && hipMemcpy(level_ptr, schedule->d_level_ptr,
+                                (static_cast<size_t>(schedule->num_levels) + 1) * sizeof(int),
+                                hipMemcpyDeviceToHost) != hipSuccess) ||
+        (order && hipMemcpy(order, schedule->d_order, static_cast<size_t>(schedule->num_rows) * sizeof(int),
+                            hipMemcpyDeviceToHost) != hipSuccess)) {
+        (void)hipGetLastError();
+        return code(SpMVError::CUDA_MEMCPY);
+    }
+    if (info) {
+        info->num_levels = schedule->num_levels;
+        info->launches = static_cast<int>(schedule->groups.size());
+        info->first_missing_diagonal = schedule->first_missing_diagonal;
+        info->first_unsorted_row = schedule->first_unsorted_row;
+        info->one_sided_row = schedule->one_sided_row;
+        info->built_on_device = schedule->built_on_device ? 1 : 0;
+        info->triangle_nnz = schedule->triangle_nnz;
+    }
+    return code(SpMVError::SUCCESS);
 }
 
 } // namespace spmv

@@ -1,7 +1,7 @@
 // spmv/sptrsv.h — sparse triangular solve T x = b with level scheduling, T a triangle of a square CSR matrix.
 //
 // The primitive under Gauss-Seidel, IC(0) and ILU(0) preconditioners: rows depend on each other, so the rows are
-// sorted into dependency levels once per (matrix, triangle) on the host, and a solve is a short sequence of
+// sorted into dependency levels once per (matrix, triangle), on the host or (sptrsv_analyze_device) on the device, and a solve is a short sequence of
 // launches in which every row of a level is independent (gpu-spmv_amd/csrc/sptrsv.hip).
 #ifndef SPMV_SPTRSV_H
 #define SPMV_SPTRSV_H
@@ -56,7 +56,8 @@ struct SpTRSVResult {
 // the rows those entries name (sptrsv_levels below).  The first call per (matrix, uplo) reads row_ptrs and
 // col_indices back from the device once, computes the levels on the host, uploads the schedule and keeps it with the
 // matrix; it synchronises the stream, so make it (or sptrsv_analyze) outside a graph capture and outside a timed
-// region.  The schedule is found again by the matrix's row-pointer and column arrays, its dimensions, nnz and uplo;
+// region.  sptrsv_analyze_device (below) builds the same schedule without the read-back, and SPMV_DEBUG=
+// sptrsv_analysis=device makes every first call do so.  The schedule is found again by the matrix's row-pointer and column arrays, its dimensions, nnz and uplo;
 // LOWER and UPPER schedules live side by side.  csr_invalidate_gpu_cache / csr_free_gpu drop them.  The schedule
 // holds STRUCTURE only: the values, the diagonal included, are read from A's arrays by every solve, so rewriting
 // d_values in place (a refactorisation with the same pattern) needs no invalidation.  Rewriting d_row_ptrs or
@@ -113,6 +114,38 @@ int sptrsv_cpu_csr_multi(const CSRMatrix* A, const float* B, int ldb, float* X, 
 // sptrsv_csr's for A and uplo; a missing diagonal is not an error here (a UNIT solve may follow).  num_levels,
 // launches and analysis_ms of the result are filled; analysis_ms is 0 when the schedule was already there.
 SpTRSVResult sptrsv_analyze(const CSRMatrix* A, int uplo);
+
+// sptrsv_analyze with the analysis run on the device (gpu-spmv_amd/csrc/sptrsv_analysis.hip): no
+// array of A crosses the bus, only the level pointers (num_levels + 1 ints) and a few counters come back.  The same
+// checks in the same order and the same result fields; analysis_ms is the wall time of the build, and 0 when a
+// schedule, however built, is already cached.  The schedule goes into the same cache under the same key and
+// invalidation as the host-built one and every consumer (the solves, ilu0_csr, ic0_csr, the *_lu / *_ic solvers) finds
+// it unchanged: level pointers, order, launches and statistics are the host analysis's ints.  Two differences: the
+// structure is checked by csr_transpose_gpu's rule (row_ptrs[0] == 0 and row_ptrs[num_rows] == nnz are required, where
+// the host analysis accepts any row_ptrs inside [0, nnz]), and one_sided_row (SpTRSVScheduleInfo) may name another row.
+// Integer atomics only, none whose outcome depends on arrival order: the same arrays on every run and every stream.
+// No workgroup waits for another; the host loop enqueues at most num_rows + 1 rounds, whatever the input.
+SpTRSVResult sptrsv_analyze_device(const CSRMatrix* A, int uplo);
+
+// What the cached schedule of (A, uplo) holds besides its arrays.  32 bytes.
+struct SpTRSVScheduleInfo {
+    int num_levels;
+    int launches;                // kernel launches of one solve (groups of levels)
+    int first_missing_diagonal;  // lowest row without a stored (i,i) entry, or -1
+    int first_unsorted_row;      // lowest row whose columns are not strictly ascending, or -1
+    // LOWER schedules of a matrix with sorted rows and every diagonal: a row that stores an (i,k), k != i, whose (k,i)
+    // is not stored, or -1 when the pattern is structurally symmetric; -1 where it was not tested.  The device
+    // analysis names the lowest such row, the host analysis the first its one pass meets: only the sign is shared.
+    int one_sided_row;
+    int built_on_device;         // 1: sptrsv_analyze_device (or SPMV_DEBUG=sptrsv_analysis=device) built it
+    long long triangle_nnz;      // stored entries inside the triangle, diagonal included
+};
+
+// Copies the cached schedule of (A, uplo), of either origin, to host arrays: level_ptr (num_levels + 1 ints: give it
+// room for num_rows + 1) and order (num_rows ints: the rows by level, ascending inside a level); either may be null.
+// *info (may be null) is filled.  Builds nothing.  Checks, in this order: null A -> INVALID_ARGUMENT; uplo out of
+// range -> INVALID_ARGUMENT; no schedule cached for (A, uplo) -> INVALID_ARGUMENT, and nothing is written.
+int sptrsv_schedule_get(const CSRMatrix* A, int uplo, int* level_ptr, int* order, SpTRSVScheduleInfo* info);
 
 // Host forward (LOWER) / backward (UPPER) substitution on A's HOST arrays, the counterpart of spmv_cpu_csr and the
 // definition of the ordered solve: rows in ascending (LOWER) or descending (UPPER) order, per row s = 0.0f,

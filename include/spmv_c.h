@@ -424,6 +424,25 @@ int spmv_c_sptrsv_csr_async(const spmv_c_csr* A, const float* d_b, float* d_x, c
                             void* hip_stream);
 /* builds and caches the schedule of A's uplo triangle ahead of a timed call; fills num_levels, launches, analysis_ms */
 int spmv_c_sptrsv_analyze(const spmv_c_csr* A, int uplo, spmv_c_sptrsv_result* out);
+/* the same with the analysis run on the device: no array of A crosses the bus (sptrsv_analyze_device in
+ * include/spmv/sptrsv.h); analysis_ms is 0 when a schedule, however built, is already cached */
+int spmv_c_sptrsv_analyze_device(const spmv_c_csr* A, int uplo, spmv_c_sptrsv_result* out);
+/* what the cached schedule of (A, uplo) holds besides its arrays (32 bytes); one_sided_row: only its sign is shared
+ * between the host and the device analysis */
+typedef struct spmv_c_sptrsv_schedule_info {
+    int32_t num_levels;
+    int32_t launches;
+    int32_t first_missing_diagonal;
+    int32_t first_unsorted_row;
+    int32_t one_sided_row;
+    int32_t built_on_device;
+    int64_t triangle_nnz;
+} spmv_c_sptrsv_schedule_info;
+/* copies the cached schedule of (A, uplo), of either origin, to host arrays: level_ptr (num_levels + 1 ints; room for
+ * num_rows + 1), order (num_rows ints), info; each may be NULL.  Builds nothing: without a cached schedule it returns
+ * INVALID_ARGUMENT and writes nothing (sptrsv_schedule_get in include/spmv/sptrsv.h) */
+int spmv_c_sptrsv_schedule_get(const spmv_c_csr* A, int uplo, int32_t* level_ptr, int32_t* order,
+                               spmv_c_sptrsv_schedule_info* info);
 /* host forward / backward substitution on A's host arrays (b and x host arrays, may be the same); returns the error code */
 int spmv_c_sptrsv_cpu_csr(const spmv_c_csr* A, const float* b, float* x, const spmv_c_sptrsv_config* config);
 /* spmv_c_sptrsv_csr for k right-hand sides (1..32) in one launch sequence: d_B and d_X are num_rows x k row-major
