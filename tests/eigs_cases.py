@@ -6,8 +6,9 @@ separately, as the host twin and the device kernel round theirs, so all three gi
 eigs_sym rule for rule: fp32 vectors, fp64 dot products of the fp32 entries, classical Gram-Schmidt applied twice with
 the coefficients rounded to fp32 and applied by fmaf in ascending order, the dense projected matrix T, the Ritz
 decomposition by jacobi(), the estimates, the thick restart and the finish with RECOMPUTED residuals.  Its dot products
-sum in numpy's order and its SpMV in the order `spmv` chooses; the device has orders of its own, so runs are compared
-by measured bounds, never bit for bit.
+sum in numpy's order and its SpMV in the order `spmv` chooses; the device has orders of its own, so runs on general
+data are compared by measured bounds.  Where the data make every order give the same bits (one-hot systems up to the
+first close, the first step of an integer system) tests/test_gpu_eigs_exact.py holds the device to restate() bit for bit.
 
 Measured on the CPU (restate() against fp64 eigh, tolerance 1e-5, max_iterations 6000, the CASES and SHAPES below, both
 ends of the spectrum: 50 runs; `python tests/eigs_cases.py` prints the table and `--write-golden` records the runs in

@@ -1243,3 +1243,299 @@ def two_level_triangle(L, uplo, unit):
     rp = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=n))]).astype(np.int32)
     return dict(n=n, half=half, L=L, uplo=uplo, unit=unit, rp=rp, ci=cols.astype(np.int32), va=vals.astype(np.float32),
                 b=b.astype(np.float32), x=x.astype(np.float32))
+
+
+# ------------------------------------------------------------------------------------------ one-hot Lanczos systems
+# eigs_sym (csrc/eigs.hip) held to the bit up to its first close: the symmetric counterpart of the one-hot Krylov
+# systems.  A = D + B + B^T with B[i, (i - s) mod n] = beta_i, every stored value +- a power of two (|d| 1 or 2, |beta|
+# 1/2, 1 or 2), the link between p and (p - s) mod n removed, so that from v0 = 4 e_p the Lanczos vectors are
+# v_j = sign_j e_(q_j), q_j = (p + j s) mod n, sign_0 = +1, sign_j = sign_(j-1) sgn(beta_(q_j)): A v_j holds at most three
+# non-zeros, one per row, h1 is d_(q_j) at i = j, |beta_(q_j)| at i = j - 1 and 0.0 elsewhere (one non-zero product per
+# dot product), the updated w is sign_j beta_(q_j+1) e_(q_j+1), h2 is 0.0, w.w = beta^2 and 1 / |beta| a power of two.
+# T is the tridiagonal matrix of the walk (diagonal d_(q_j), off-diagonal |beta_(q_j+1)|) whatever the order of any
+# reduction; the Ritz decomposition is a fixed sequence of fp64 operations, the same on the host and on the device; and
+# a rotation y_i = sum_l C[i, l] v_l has one non-zero product per element.  So the values and vectors of a run that
+# finishes at its FIRST close are predictable from T alone.  The recomputed residuals are not claimed: a row of A y_i sums
+# up to three rounded fp32 products in an order the lane count decides.  After a thick restart the basis vectors are
+# dense on the walk, dot products sum many terms of mixed exponent, and the bits depend on the order (measured in
+# tests/test_exact_data.py): such runs are held to eigs_cases' bounds, with the exact claim that nothing leaves the walk.
+LANCZOS_START = 4.0                  # v0 = 2^2 e_p
+
+
+def lanczos_onehot_system(n, p, s, steps, seed, cut=None):
+    """dict(n, rp, ci, va, v0, walk, d, beta, sign, cut): the system above.  `walk` holds q_0..q_steps, asserted
+    distinct; row i stores d_i at column i, beta_i at column (i - s) mod n and beta_(i+s) at column (i + s) mod n, in an
+    order drawn per row; both entries linking p with (p - s) mod n are removed, and with cut = j both entries linking
+    q_j with q_j+1 as well (step j then finds w == 0: an invariant space of j + 1 columns).  sign[j] is v_j's sign."""
+    assert 0 <= p < n and 0 < s < n and steps + 1 <= n and (2 * s) % n != 0
+    rng = np.random.default_rng(seed)
+    walk = (p + s * np.arange(steps + 1, dtype=np.int64)) % n
+    assert np.unique(walk).size == steps + 1, "the walk revisits a position"
+    assert (p - s) % n not in set(walk.tolist())
+    d = np.ldexp(rng.choice([-1.0, 1.0], size=n), rng.integers(0, 2, size=n)).astype(np.float32)
+    beta = np.ldexp(rng.choice([-1.0, 1.0], size=n), rng.integers(-1, 2, size=n)).astype(np.float32)
+    idx = np.arange(n, dtype=np.int64)
+    rows = np.concatenate([idx, idx, (idx - s) % n])               # D, B, B^T
+    cols = np.concatenate([idx, (idx - s) % n, idx])
+    vals = np.concatenate([d, beta, beta])
+    keep = np.ones(3 * n, bool)
+    for i in [p] + ([int(walk[cut + 1])] if cut is not None else []):      # the link beta_i between i and (i - s) mod n
+        keep[n + i] = keep[2 * n + i] = False
+    rows, cols, vals = rows[keep], cols[keep], vals[keep]
+    order = np.lexsort((rng.random(rows.size), rows))              # storage order inside a row is drawn
+    rows, cols, vals = rows[order], cols[order], vals[order]
+    rp = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=n))]).astype(np.int32)
+    v0 = np.zeros(n, np.float32)
+    v0[p] = LANCZOS_START
+    sign = np.cumprod(np.concatenate([[1.0], np.sign(beta[walk[1:]])])).astype(np.float32)
+    return dict(n=n, s=s, rp=rp, ci=cols.astype(np.int32), va=vals.astype(np.float32), v0=v0, walk=walk, d=d, beta=beta,
+                sign=sign, cut=cut)
+
+
+def lanczos_onehot_compact(system):
+    """(m, rp, ci, va, v0) of the system restricted to its walk, in walk order: row j is row q_j with its entries in
+    storage order, those whose column lies off the walk dropped (every vector is 0 there from start to end)."""
+    walk = system["walk"]
+    at = {int(q): j for j, q in enumerate(walk)}
+    rp, ci, va = system["rp"], system["ci"], system["va"]
+    c_rp, c_ci, c_va = [0], [], []
+    for q in walk:
+        for e in range(int(rp[q]), int(rp[q + 1])):
+            if int(ci[e]) in at:
+                c_ci.append(at[int(ci[e])])
+                c_va.append(va[e])
+        c_rp.append(len(c_ci))
+    return (walk.size, np.array(c_rp, np.int32), np.array(c_ci, np.int32), np.array(c_va, np.float32),
+            system["v0"][walk].copy())
+
+
+def lanczos_onehot_reference(system, k, which, m, max_iterations, spmv=None):
+    """eigs_cases.restate on the walk positions only at tolerance 0, the vectors scattered back: restate's dict.
+    tests/test_exact_data.py shows that it equals restate on the whole system in every field at small n.  The walk has
+    to be longer than the basis (restate clips m to the order of the system it is given)."""
+    import eigs_cases as ec
+    order, rp, ci, va, v0 = lanczos_onehot_compact(system)
+    assert order > m and order > max_iterations
+    out = ec.restate(order, rp, ci, va, k, which, m, tol=0.0, max_iter=max_iterations, v0=v0,
+                     **({} if spmv is None else {"spmv": spmv}))
+    vectors = np.zeros((k, system["n"]), np.float32)
+    vectors[:, system["walk"]] = out["vectors"]
+    return dict(out, vectors=vectors)
+
+
+def lanczos_onehot_tridiagonal(system, c):
+    """T after c steps of the first cycle: diagonal d_(q_j), off-diagonal |beta_(q_j+1)|, in fp64."""
+    walk = system["walk"]
+    assert system["cut"] is None or c <= system["cut"] + 1
+    T = np.diag(system["d"][walk[:c]].astype(np.float64))
+    off = np.abs(system["beta"][walk[1:c]].astype(np.float64))
+    T[np.arange(c - 1), np.arange(1, c)] = off
+    T[np.arange(1, c), np.arange(c - 1)] = off
+    return T
+
+
+def lanczos_onehot_prediction(system, k, which, c):
+    """(values, vectors k x n) of a run that finishes at its first close with c columns, from T alone: values[i] =
+    fp32(theta_i), vector i = fp32(S[i, l]) sign_l at q_l for l < c and 0 elsewhere (+ 0.0: a rotation's sum starts
+    at +0, so a zero coefficient gives +0 whatever its sign); NaN / zero rows from min(k, c) on."""
+    import eigs_cases as ec
+    values, S, _ = ec.jacobi(lanczos_onehot_tridiagonal(system, c))
+    theta, S = ec.sort_ritz(values, S, which)
+    found = min(k, c)
+    out_values = np.full(k, np.nan, np.float32)
+    out_values[:found] = theta[:found].astype(np.float32)
+    vectors = np.zeros((k, system["n"]), np.float32)
+    vectors[:found, system["walk"][:c]] = (S[:found].astype(np.float32) * system["sign"][:c]) + np.float32(0.0)
+    return out_values, vectors
+
+
+def lanczos_runs(c):
+    """[(k, m, c)] for a first close with c columns: k in {1, min(c, 32), min(c + 2, 32)}.  eigs.h admits k < m only, so
+    k < c runs at the basis m = c (the cycle closes on j + 1 == m) and k >= c at the smallest basis that admits k,
+    m = k + 1, with max_iterations = c (the cycle closes on its budget): the same c columns either way."""
+    return [(k, c if k < c else k + 1, c) for k in sorted({1, min(c, 32), min(c + 2, 32)})]
+
+
+LANCZOS_BASIS_EDGES = (1, 2, 7, 8, 9, 16, 17, 63, 64)
+
+
+def _lanczos_cases():
+    cases = {}
+
+    def add(name, geometry, runs, visits=(), chunks=(), cut=None, nan_step=None):
+        g = ONEHOT_CASES[geometry]
+        steps = max(max(m, c) for _, m, c in runs) + 1
+        cases[name] = dict(name=name, n=g["n"], p=g["p"], s=g["s"], steps=steps, runs=tuple(runs), visits=tuple(visits),
+                           chunks=tuple(chunks), cut=cut, nan_step=nan_step, seed=len(cases) + 117)
+
+    # the basis edges at n = 4103 (3 mod 4): one, two, a group of eight less one, full, plus one, two groups, the cap
+    for c in LANCZOS_BASIS_EDGES:
+        add("basis_%d" % c, "restart_9", lanczos_runs(c),
+            visits=(4100, 1023) if c < 16 else (4100, 4101, 4102, 0, 1023, 1024))
+    # the host closes on the budget, one column before j + 1 == m
+    add("budget_before_basis", "restart_9", [(1, 9, 8), (8, 9, 8)], visits=(4100, 1023))
+    # vector tails at n mod 4 = 1 and 2 (n mod 4 = 3: basis_16 and up)
+    add("tail_n3077", "tail_n3077", lanczos_runs(16), visits=(3074, 3075, 3076, 0, 1023, 1024))
+    add("tail_n3074", "tail_n3074", lanczos_runs(16), visits=(3071, 3072, 3073, 0, 1023, 1024))
+    # the large geometries keep m <= 9: k = 1 and 8 at c = m = 9, and k = 5 > c = 3 (zero rows past every edge)
+    large = [(1, 9, 9), (8, 9, 9), (5, 9, 3)]
+    add("fold_second_trip", "fold_second_trip", large, visits=(5, 65545, 131085), chunks=(0, 64, 128))
+    add("grid_second_trip", "grid_second_trip", large, visits=(261125, 262148, 263171, 264194),
+        chunks=(254, 255, 256, 257, 258, 0))
+    add("rows_second_trip", "rows_second_trip", large, visits=(523268, 524291, 525314, 1022))
+    # both entries between q_5 and q_6 removed: six columns, then w == 0; the host learns of the close one step late
+    add("invariant_mid_cycle", "restart_9", [(1, 9, 19), (6, 9, 19), (8, 9, 19)], visits=(4100, 1023, 4101), cut=5)
+    # the diagonal entry of row q_2 is NaN: NaN * 0 is NaN, so the first step is NOT_FINITE; eigs_fill_failed on
+    # 525 315 rows
+    add("nan_on_the_walk", "rows_second_trip", [(3, 9, 9)], visits=(523268, 524291, 525314), nan_step=2)
+    return cases
+
+
+LANCZOS_CASES = _lanczos_cases()
+LANCZOS_NAMES = list(LANCZOS_CASES)
+# thick restarts (no bit claim): (geometry, k, m), run for 2 m + 1 steps
+LANCZOS_RESTART_CASES = [("grid_second_trip", 2, 8), ("grid_second_trip", 2, 9), ("rows_second_trip", 2, 8),
+                         ("rows_second_trip", 2, 9), ("restart_9", 4, 20)]
+_lanczos_cache = {}
+
+
+def lanczos_case(name):
+    """(case, system) of one LANCZOS_CASES member; the system is built once.  A nan_step case carries the finite
+    system; lanczos_nan_values gives the stored values with the NaN."""
+    if name not in _lanczos_cache:
+        c = LANCZOS_CASES[name]
+        _lanczos_cache[name] = (c, lanczos_onehot_system(c["n"], c["p"], c["s"], c["steps"], c["seed"], c["cut"]))
+    return _lanczos_cache[name]
+
+
+def lanczos_nan_values(case, system):
+    """The stored values with the diagonal entry of row q_(nan_step) replaced by NaN."""
+    q = int(system["walk"][case["nan_step"]])
+    va = system["va"].copy()
+    lo, hi = int(system["rp"][q]), int(system["rp"][q + 1])
+    va[lo + int(np.flatnonzero(system["ci"][lo:hi] == q)[0])] = np.nan
+    return va
+
+
+def lanczos_restart_case(geometry, k, m):
+    """(system, max_iterations) of one LANCZOS_RESTART_CASES member: 2 m + 1 steps, a walk of 2 m + 3 positions."""
+    key = ("restart", geometry, k, m)
+    if key not in _lanczos_cache:
+        g = ONEHOT_CASES[geometry]
+        seed = 400 + LANCZOS_RESTART_CASES.index((geometry, k, m))
+        _lanczos_cache[key] = (lanczos_onehot_system(g["n"], g["p"], g["s"], 2 * m + 2, seed), 2 * m + 1)
+    return _lanczos_cache[key]
+
+
+def lanczos_lambda_max(system):
+    """max |lambda| of the walk's tridiagonal matrix (the compact system, dense; asserted symmetric and tridiagonal)"""
+    m, rp, ci, va, _ = lanczos_onehot_compact(system)
+    D = np.zeros((m, m))
+    np.add.at(D, (np.repeat(np.arange(m), np.diff(rp)), ci), va.astype(np.float64))
+    assert np.array_equal(D, D.T) and not np.triu(D, 2).any()
+    return float(np.max(np.abs(np.linalg.eigvalsh(D))))
+
+
+# ------------------------------------------------------------------------------------------ Lanczos, first step
+LANCZOS_STEP_K = 5                            # 1024 rows, as GMRES_STEP_K
+LANCZOS_STEP_VALUES = 3                       # num_values of the run: one pair found, two NaN / zero rows
+LANCZOS_SEEDS = 20                            # seeds tried per system before the construction gives up
+
+
+def lanczos_first_step(rp, ci, va, v0, k):
+    """What eigs_sym returns after ONE Lanczos step (max_iterations 1, tolerance 0, num_values > 1) under eigs.h's rules,
+    for an integer matrix and a +-1 / 0 start vector with 4^k non-zeros (pm_one_rhs).  beta_0 = 2^k and v_0 = v0 / 2^k
+    exactly; w = A v0 / 2^k holds integers over 2^k; h1 = v0.A v0 / 4^k is an exact fp32 value; fmaf(-h1, v_0, w) =
+    (4^k (A v0)_i - v0_i (v0.A v0)) / 8^k with a numerator below 2^24: exact; h2 == 0; T = [h1], so theta = h1, S = [1] and
+    y_0 = v_0.  The finish: t = A y_0 = w (integers over 2^k, exact in any lane order), d = fmaf(-theta, y_0, t) the same
+    exact vector as the updated w, d.d a sum of integers over 64^k that stays below 2^53: exact in fp64 in any order; the
+    residual is fp32(sqrt(d.d)) given a correctly rounded fp64 square root.  beta = sqrt(w.w) = sqrt(d.d); the space is
+    invariant when beta <= |h1| 2^-20.  Every claim is asserted.  Returns dict(value, vector, residual (float32),
+    invariant, converged)."""
+    v0 = np.asarray(v0, np.float32)
+    check_exact(rp, ci, va, v0)
+    b64 = v0.astype(np.int64)
+    scale = 4 ** k
+    assert set(np.unique(b64).tolist()) <= {-1, 0, 1} and int(np.abs(b64).sum()) == scale == int(b64 @ b64)
+    ab = exact_reference(rp, ci, va, v0).astype(np.int64)                        # 2^k w
+    bab = int(b64 @ ab)
+    h1 = np.float32(np.float64(bab) / np.float64(scale))
+    assert np.float64(h1) * scale == bab and abs(bab) < EXACT_LIMIT             # an exact fp32 value
+    num = scale * ab - b64 * bab                                                 # 8^k (w after the first update)
+    assert int(np.abs(num).max()) < EXACT_LIMIT                                  # ... which fp32 holds: the fmaf is exact
+    assert int(b64 @ num) == 0                                                   # h2 == 0: the second update changes nothing
+    dd_int = sum(int(v) * int(v) for v in num[num != 0])                         # 64^k d.d
+    assert 0 <= dd_int < 2 ** 53
+    beta = np.sqrt(np.float64(dd_int) / np.float64(64 ** k))
+    vector = (v0.astype(np.float64) / np.float64(2 ** k)).astype(np.float32)
+    assert np.array_equal(vector.astype(np.float64) * 2 ** k, v0.astype(np.float64))
+    return dict(value=h1, vector=vector, residual=np.float32(beta), invariant=bool(beta <= abs(np.float64(h1)) * 2.0 ** -20),
+                converged=int(beta <= 0.0), ab=ab, num=num)
+
+
+def _lanczos_start(rp, ci, va, n, k, base_seed, accept):
+    """(v0, first step) from the first of LANCZOS_SEEDS seeds whose +-1 / 0 vector meets lanczos_first_step's bounds and
+    `accept`; a seed that fails a bound is passed over, as the construction allows."""
+    for t in range(LANCZOS_SEEDS):
+        v0 = pm_one_rhs(n, k, base_seed + 1000 * t)
+        try:
+            step = lanczos_first_step(rp, ci, va, v0, k)
+        except AssertionError:
+            continue
+        if accept(v0, step):
+            return v0, step
+    raise AssertionError("no seed of %d gives an exact first step" % LANCZOS_SEEDS)
+
+
+_lanczos_step_cache = {}
+
+
+def lanczos_step_system(name):
+    """(L, n, rp, ci, va, v0, first step) of solver_system(name, symmetric=True) with a +-1 / 0 start vector on 4^5
+    rows.  L1_low is the diagonal plus one symmetric pair: its start vector is drawn until A v0 == v0 (the pair's rows
+    cancel or lie outside the support), the run that ends with INVARIANT_SUBSPACE, value 1 and residual 0."""
+    if name not in _lanczos_step_cache:
+        L, n, rp, ci, va, _, _ = solver_system(name, symmetric=True)
+        accept = (lambda v0, step: step["invariant"]) if name == "L1_low" else (lambda v0, step: not step["invariant"])
+        v0, step = _lanczos_start(rp, ci, va, n, LANCZOS_STEP_K, 1500 + SOLVER_NAMES.index(name), accept)
+        _lanczos_step_cache[name] = (L, n, rp, ci, va, v0, step)
+    return _lanczos_step_cache[name]
+
+
+LANCZOS_TRIP_LANES = (2, 8, 64)               # the row loop's second trip at L > 1
+LANCZOS_TRIP_AVERAGE = {L: 3 * L for L in LANCZOS_TRIP_LANES}     # inside (2 L, 4 L]: the lane rule gives L
+
+
+def lanczos_trip_system(L):
+    """(n, rp, ci, va, v0, first step): integer_spd at n = LANE_SIZES[L] rows and an average of 3 L entries per row, the
+    start vector drawn until its support and the non-zeros of A v0 lie on both sides of row_trip(L), the first row of
+    the row loop's second trip.  k = 5 for every L (no seed had to give way to k = 4)."""
+    key = ("trip", L)
+    if key not in _lanczos_step_cache:
+        n = LANE_SIZES[L]
+        total = LANCZOS_TRIP_AVERAGE[L] * n
+        n, rp, ci, va = integer_spd(n, (total - n) // 2, seed=1600 + L)
+        edge = row_trip(L)
+
+        def accept(v0, step):
+            both = lambda mask: bool(mask[:edge].any() and mask[edge:].any())
+            return both(v0 != 0) and both(step["ab"] != 0) and not step["invariant"]
+
+        v0, step = _lanczos_start(rp, ci, va, n, LANCZOS_STEP_K, 1700 + L, accept)
+        while len(_lanczos_step_cache) >= 20:
+            _lanczos_step_cache.pop(next(iter(_lanczos_step_cache)))
+        _lanczos_step_cache[key] = (n, rp, ci, va, v0, step)
+    return _lanczos_step_cache[key]
+
+
+LANCZOS_TILED_STEP_K = 7                      # 16 384 of the 20 011 rows of entry_point_systems
+
+
+def lanczos_tiled_step_system(W):
+    """(n, rp, ci, va, v0, first step): the symmetric system of entry_point_systems(W) with a +-1 / 0 start vector."""
+    key = ("tiled", W)
+    if key not in _lanczos_step_cache:
+        n, rp, ci, va = entry_point_systems(W)[0]
+        v0, step = _lanczos_start(rp, ci, va, n, LANCZOS_TILED_STEP_K, 1800 + W, lambda v0, step: not step["invariant"])
+        _lanczos_step_cache[key] = (n, rp, ci, va, v0, step)
+    return _lanczos_step_cache[key]

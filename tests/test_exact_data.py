@@ -1034,3 +1034,270 @@ def test_two_level_triangle_has_two_wide_levels_and_an_integer_solution(spmv, L)
             dep = inside
             assert np.count_nonzero(trip_of_row[rows[dep]] != place[ci[dep]] // ed.row_trip(L)) > 0
             assert np.unique(np.diff(rp)).size >= 3
+
+
+# ------------------------------------------------------------------------------------------ one-hot Lanczos systems
+ec = importlib.import_module("eigs_cases")
+SPMVS = {"round once": gc.spmv_round_once, "sequential": gc.spmv_sequential}
+WHICH = (ec.LARGEST, ec.SMALLEST)
+
+
+def lanczos_variants(monkeypatch, run):
+    """{(dot order, SpMV order): run(spmv)} over three dot-product orders x two SpMV orders of eigs_cases.restate"""
+    outs = {}
+    for order, dot in DOTS.items():
+        monkeypatch.setattr(gc, "dot", dot)
+        for name, spmv in SPMVS.items():
+            outs[(order, name)] = run(spmv)
+    monkeypatch.setattr(gc, "dot", DOTS["numpy"])
+    return outs
+
+
+def same_pairs(got, want, residuals=False):
+    """every field of restate's dict but the residuals (unless asked for): values and vectors on the bits"""
+    fields = ("found", "converged", "iterations", "restarts", "breakdown")
+    nan_equal = lambda a, b: np.array_equal(bits(a), bits(b)) or (np.all(np.isnan(a) == np.isnan(b)) and
+                                                                  np.array_equal(bits(a[~np.isnan(a)]), bits(b[~np.isnan(b)])))
+    same = (all(got[f] == want[f] for f in fields) and nan_equal(got["values"], want["values"])
+            and np.array_equal(bits(got["vectors"]), bits(want["vectors"])))
+    if residuals:
+        same = same and nan_equal(got["residuals"], want["residuals"]) and \
+            bits(np.float32(got["max_residual"])) == bits(np.float32(want["max_residual"]))
+    return same
+
+
+def lanczos_first_cycle(system, columns):
+    """The first cycle's Lanczos steps on the walk positions, spelled out, with the module comment's claims asserted per
+    column and per dot-product order: h1 is d_(q_j) at i = j, |beta_(q_j)| at i = j - 1 and 0.0 elsewhere, the updated w
+    is one-hot at q_j+1 with sign_j beta_(q_j+1), h2 is all 0.0, sqrt(w.w) == |beta| with a power-of-two inverse and
+    v_j+1 == sign_j+1 e_(q_j+1)."""
+    m, rp, ci, va, v0 = ed.lanczos_onehot_compact(system)
+    walk, d, beta, sign = system["walk"], system["d"], system["beta"], system["sign"]
+    assert np.sqrt(gc.dot(v0, v0)) == ed.LANCZOS_START
+    V = [(v0 * np.float32(1.0 / ed.LANCZOS_START)).astype(np.float32)]
+    assert V[0][0] == 1.0 == sign[0] and np.count_nonzero(V[0]) == 1
+    for j in range(columns):
+        ws = [spmv(rp, ci, va, V[j]) for spmv in SPMVS.values()]
+        assert np.array_equal(ws[0], ws[1]) and np.count_nonzero(ws[0]) <= 3       # equal values: a zero's sign may differ
+        w = ws[0]
+        for dot in DOTS.values():
+            h1 = [np.float32(dot(v, w)) for v in V]
+            assert h1[j] == d[walk[j]] and all(h == 0.0 for h in h1[:max(j - 1, 0)])
+            assert j == 0 or h1[j - 1] == abs(beta[walk[j]])
+        for hi, v in zip(h1, V):
+            w = gc.fma(-hi, v, w)
+        if system["cut"] == j:
+            assert np.count_nonzero(w) == 0                      # the invariant space: beta == 0
+            return j + 1
+        assert np.count_nonzero(w) == 1 and w[j + 1] == sign[j] * beta[walk[j + 1]]
+        for dot in DOTS.values():
+            assert all(np.float32(dot(v, w)) == 0.0 for v in V)     # h2
+            hn = np.sqrt(dot(w, w))
+            assert hn == abs(beta[walk[j + 1]]) and np.frexp(np.float32(1.0 / hn))[0] == 0.5
+        V.append((w * np.float32(1.0 / hn)).astype(np.float32))
+        assert np.count_nonzero(V[-1]) == 1 and V[-1][j + 1] == sign[j + 1] and abs(sign[j + 1]) == 1.0
+    return columns
+
+
+@pytest.mark.parametrize("name", ed.LANCZOS_NAMES)
+def test_lanczos_case_is_what_it_claims(monkeypatch, name):
+    """No revisit, the required positions, powers of two, symmetry, L = 1, the first cycle's exactness claims column by
+    column, and per run and end of the spectrum the same bits in values and vectors from three dot-product orders x two
+    SpMV orders, equal to the prediction from the walk's tridiagonal matrix alone."""
+    c, s = ed.lanczos_case(name)
+    n, walk, rp, ci, va = s["n"], s["walk"], s["rp"], s["ci"], s["va"]
+    assert walk.size == c["steps"] + 1 == np.unique(walk).size and walk[0] == c["p"]
+    columns_wanted = max(min(cc, mm) for _, mm, cc in c["runs"])
+    reach = walk[:columns_wanted + 1]                                # the columns of the longest run and its next vector
+    assert set(c["visits"]) <= set(reach.tolist()) and set(c["chunks"]) <= set((reach // ed.ONEHOT_CHUNK).tolist())
+    assert n % 64 != 0 and n % 4 != 0
+    nnz = int(rp[-1])
+    assert nnz == 3 * n - 2 * (1 + (c["cut"] is not None)) and ed.lanes_for(nnz, n) == 1 and int(np.diff(rp).max()) == 3
+    assert np.all(np.frexp(np.abs(va))[0] == 0.5) and np.abs(np.frexp(va)[1] - 1).max() <= 1
+    assert np.count_nonzero(s["v0"]) == 1 and s["v0"][c["p"]] == ed.LANCZOS_START
+    rows = np.repeat(np.arange(n), np.diff(rp))
+    key = rows.astype(np.int64) * n + ci
+    assert np.unique(key).size == nnz                                 # distinct columns inside a row
+    mirror = np.sort(ci.astype(np.int64) * n + rows)
+    order = np.argsort(key)
+    assert np.array_equal(key[order], mirror)                         # the pattern is symmetric ...
+    assert np.array_equal(va[order], va[np.argsort(ci.astype(np.int64) * n + rows)])      # ... and so are the values
+    off = ci != rows
+    assert np.all(((ci[off] + c["s"]) % n == rows[off]) | ((ci[off] - c["s"]) % n == rows[off]))
+    assert np.array_equal(np.sort(ci[~off]), np.arange(n))
+    back = (c["p"] - c["s"]) % n
+    assert not np.any((rows == c["p"]) & (ci == back)) and not np.any((rows == back) & (ci == c["p"]))
+    if c["nan_step"] is not None:
+        bad = ed.lanczos_nan_values(c, s)
+        at = np.flatnonzero(np.isnan(bad))
+        assert at.size == 1 and rows[at[0]] == ci[at[0]] == walk[c["nan_step"]] >= ed.ONEHOT_ROW_BLOCKS * 256
+        k, m, cap = c["runs"][0]
+        out = ed.lanczos_onehot_reference(dict(s, va=bad), k, ec.LARGEST, m, cap)
+        assert (out["breakdown"], out["iterations"], out["found"]) == (ec.NOT_FINITE, 0, 0)
+        assert np.all(np.isnan(out["values"])) and not out["vectors"].any()
+        return
+    assert lanczos_first_cycle(s, columns_wanted) == (columns_wanted if c["cut"] is None else c["cut"] + 1)
+    for k, m, cap in c["runs"]:
+        assert 1 <= k < m <= ec.MAX_ORDER and k <= 32                 # what eigs.h admits
+        cols = min(cap, m) if c["cut"] is None else c["cut"] + 1
+        assert cap <= m or c["cut"] is not None                       # no restart
+        for which in WHICH:
+            outs = lanczos_variants(monkeypatch, lambda spmv: ed.lanczos_onehot_reference(s, k, which, m, cap, spmv))
+            want = outs[("numpy", "round once")]
+            for variant, out in outs.items():
+                assert same_pairs(out, want), (name, k, m, cap, which, variant)
+            found = min(k, cols)
+            assert (want["iterations"], want["restarts"], want["found"], want["converged"]) == (cols, 0, found, 0)
+            assert want["breakdown"] == (ec.INVARIANT_SUBSPACE if c["cut"] is not None and found < k else ec.NO_BREAKDOWN)
+            values, vectors = ed.lanczos_onehot_prediction(s, k, which, cols)
+            assert np.array_equal(bits(values[:found]), bits(want["values"][:found])), (name, k, m, cap, which)
+            assert np.all(np.isnan(values[found:])) and np.all(np.isnan(want["values"][found:]))
+            assert np.array_equal(bits(vectors), bits(want["vectors"])), (name, k, m, cap, which)
+            assert not vectors[:, np.setdiff1d(np.arange(n), walk[:cols])].any() and not vectors[found:].any()
+            assert np.all(want["residuals"][:found] > 0)              # tolerance 0 converges nothing
+
+
+@pytest.mark.parametrize("name", [nm for nm in ed.LANCZOS_NAMES if ed.LANCZOS_CASES[nm]["n"] < 5000])
+def test_lanczos_reference_on_the_walk_equals_the_restatement_on_the_whole_system(name):
+    c, s = ed.lanczos_case(name)
+    for k, m, cap in c["runs"]:
+        for which in WHICH:
+            full = ec.restate(s["n"], s["rp"], s["ci"], s["va"], k, which, m, tol=0.0, max_iter=cap, v0=s["v0"])
+            assert same_pairs(ed.lanczos_onehot_reference(s, k, which, m, cap), full, residuals=True), (name, k, m, which)
+
+
+def test_lanczos_catalogue_reaches_the_paths_it_names():
+    """Every edge is derived from the constants of csrc/basis_ops.h and csrc/device_common.h as restated in exact_data:
+    a changed kChunk, kOrthoBlocks, kVecBlocks or kMaxResidentBlocks fails here, not silently on the GPU."""
+    C = ed.LANCZOS_CASES
+    chunk, blocks, fold = ed.ONEHOT_CHUNK, ed.ONEHOT_ORTHO_BLOCKS, ed.ONEHOT_FOLD_LANES
+    assert chunk == 4 * 256 and ed.VEC_TRIP == 1024 * 256 and ed.ROW_TRIP_THREADS == ed.ONEHOT_ROW_BLOCKS * 256
+    columns = lambda c: max(min(cc, mm) for _, mm, cc in c["runs"])
+    # the basis edges: one column, a group of eight less one, full, plus one, two groups, plus one, the cap and one less;
+    # per edge k = 1, min(c, 32), min(c + 2, 32), run at the basis c where eigs.h admits it (k < m)
+    assert ed.LANCZOS_BASIS_EDGES == (1, 2, 7, 8, 9, 16, 17, 63, 64)
+    for c in ed.LANCZOS_BASIS_EDGES:
+        runs = C["basis_%d" % c]["runs"]
+        assert {k for k, _, _ in runs} == {1, min(c, 32), min(c + 2, 32)} and all(cc == c for _, _, cc in runs)
+        assert all((m == c) if k < c else (m == k + 1) for k, m, _ in runs)
+        assert c < 2 or any(m == c for _, m, _ in runs)               # a close on j + 1 == m at every edge but c = 1
+        assert C["basis_%d" % c]["n"] == 4103
+    assert any(k > cc for k, _, cc in C["basis_1"]["runs"]) and any(k > cc for k, _, cc in C["basis_17"]["runs"])
+    # a close on the budget, one column before the basis is full
+    assert any(cc == m - 1 and k < cc for k, m, cc in C["budget_before_basis"]["runs"])
+    # vector tails: n mod 4 = 1, 2, 3; n-1, n-2, n-3, 0 and both sides of the first chunk edge, inside the columns
+    tails = [C["tail_n3077"], C["tail_n3074"], C["basis_16"]]
+    assert sorted(c["n"] % 4 for c in tails) == [1, 2, 3]
+    for c in tails:
+        assert {c["n"] - 1, c["n"] - 2, c["n"] - 3, 0, chunk - 1, chunk} <= set(c["visits"])
+        _, s = ed.lanczos_case(c["name"])
+        assert set(c["visits"]) <= set(s["walk"][:columns(c)].tolist())
+    # fold_columns: more than 64 and at most 256 workgroups, a ragged last chunk; first, 65th and last workgroup
+    c = C["fold_second_trip"]
+    groups = -(-c["n"] // chunk)
+    assert fold * chunk < c["n"] <= blocks * chunk and c["n"] % chunk != 0
+    assert {0, fold, groups - 1} <= set(c["chunks"]) and groups - 1 >= 2 * fold
+    # the basis kernels' grid stride (ogrid = 256), the element-wise kernels (vgrid = 1024 workgroups of 256) and
+    # fold_partials with count = vgrid > 256: more than 257 chunks, both sides of the wrap, the last partial f32x4
+    c = C["grid_second_trip"]
+    assert c["n"] > (blocks + 1) * chunk and c["n"] % 4 != 0 and c["n"] > ed.VEC_TRIP
+    assert min(-(-c["n"] // 256), 1024) > 256                         # vgrid: fold_partials' count in eigs_start / eigs_verdict
+    assert {blocks - 1, blocks, -(-c["n"] // chunk) - 1} <= set(c["chunks"])
+    assert any(v >= c["n"] - c["n"] % 4 for v in c["visits"]) and any(v >= ed.VEC_TRIP for v in c["visits"])
+    assert any(v < ed.VEC_TRIP for v in c["visits"])
+    # eigs_spmv<1>, eigs_rotate<true> (2048 workgroups of 256 elements) and eigs_fill_failed: both sides of 524 288
+    edge = ed.row_trip(1)
+    for c in (C["rows_second_trip"], C["nan_on_the_walk"]):
+        assert c["n"] > edge and any(v >= edge for v in c["visits"]) and any(v < edge for v in c["visits"])
+    assert any(k > cc for k, _, cc in C["rows_second_trip"]["runs"])          # zero rows written past the edge
+    # large cases keep the small basis
+    assert all(m <= 9 for c in C.values() if c["n"] > 5000 for _, m, _ in c["runs"])
+    c = C["invariant_mid_cycle"]
+    assert all(2 <= c["cut"] + 1 < m - 1 and cap > m for _, m, cap in c["runs"])
+    assert {k for k, _, _ in c["runs"]} >= {c["cut"] + 1, c["cut"] + 3}       # k == the invariant space's order, and beyond
+    # thick restarts: elements past both edges, and the one small case
+    R = ed.LANCZOS_RESTART_CASES
+    assert {(k, m) for g, k, m in R if g == "grid_second_trip"} == {(2, 8), (2, 9)} == \
+        {(k, m) for g, k, m in R if g == "rows_second_trip"}
+    assert ("restart_9", 4, 20) in R and all(m < 64 for _, _, m in R)
+    for g, k, m in R:
+        s, cap = ed.lanczos_restart_case(g, k, m)
+        assert cap == 2 * m + 1 and s["walk"].size == cap + 2
+        if g != "restart_9":
+            limit = ed.VEC_TRIP if g == "grid_second_trip" else edge
+            assert np.any(s["walk"][:m] >= limit) and np.any(s["walk"] < limit)
+
+
+# ------------------------------------------------------------------------------------------ Lanczos, first step
+def assert_first_step(monkeypatch, n, rp, ci, va, v0, step, name):
+    """the six restatement variants agree on the bits, residuals included, and equal lanczos_first_step's prediction"""
+    k = ed.LANCZOS_STEP_VALUES
+    outs = lanczos_variants(monkeypatch, lambda spmv: ec.restate(n, rp, ci, va, k, ec.LARGEST, k + 1, tol=0.0, max_iter=1,
+                                                                 v0=v0, spmv=spmv))
+    want = outs[("numpy", "round once")]
+    for variant, out in outs.items():
+        assert same_pairs(out, want, residuals=True), (name, variant)
+    assert (want["iterations"], want["restarts"], want["found"]) == (1, 0, 1)
+    assert bits(want["values"][0]) == bits(step["value"]) and np.all(np.isnan(want["values"][1:]))
+    assert np.array_equal(bits(want["vectors"][0]), bits(step["vector"])) and not want["vectors"][1:].any()
+    assert bits(want["residuals"][0]) == bits(step["residual"]) and np.all(np.isnan(want["residuals"][1:]))
+    assert bits(np.float32(want["max_residual"])) == bits(step["residual"])
+    assert want["converged"] == step["converged"]
+    assert want["breakdown"] == (ec.INVARIANT_SUBSPACE if step["invariant"] else ec.NO_BREAKDOWN)
+
+
+@pytest.mark.parametrize("name", ed.SOLVER_NAMES)
+def test_lanczos_first_step_is_exact_per_lane_count(monkeypatch, name):
+    """exact_data.lanczos_first_step asserts its derivation; here it runs for every lane count's symmetric system, and
+    the prediction is the restatement's after one step, bit for bit in values, vectors and residuals, in six orders."""
+    L, n, rp, ci, va, v0, step = ed.lanczos_step_system(name)
+    assert ed.lanes_for(int(rp[-1]), n) == L == int(name[1:].split("_")[0])
+    assert np.count_nonzero(v0) == 4 ** ed.LANCZOS_STEP_K <= n
+    assert_first_step(monkeypatch, n, rp, ci, va, v0, step, name)
+    if name == "L1_low":                      # the diagonal and one pair: A v0 == v0
+        assert (step["invariant"], step["converged"], step["value"], step["residual"]) == (True, 1, 1.0, 0.0)
+    else:
+        assert not step["invariant"] and step["converged"] == 0 and step["residual"] > 0
+
+
+@pytest.mark.parametrize("L", ed.LANCZOS_TRIP_LANES)
+def test_lanczos_trip_system_puts_the_step_on_both_sides_of_the_row_loop(monkeypatch, L):
+    n, rp, ci, va, v0, step = ed.lanczos_trip_system(L)
+    edge = ed.row_trip(L)
+    assert n == ed.LANE_SIZES[L] > edge and ed.lanes_for(int(rp[-1]), n) == L
+    assert np.count_nonzero(v0) == 4 ** ed.LANCZOS_STEP_K
+    for mask in (v0 != 0, step["ab"] != 0, step["num"] != 0):
+        assert mask[:edge].any() and mask[edge:].any()
+    assert_first_step(monkeypatch, n, rp, ci, va, v0, step, L)
+
+
+def test_lanczos_first_tiled_step_system_is_exact(spmv, monkeypatch):
+    W, R = ed.ENTRY_POINT_GEOMETRIES[0]
+    n, rp, ci, va, v0, step = ed.lanczos_tiled_step_system(W)
+    assert np.count_nonzero(v0) == 4 ** ed.LANCZOS_TILED_STEP_K <= n == 20011
+    assert_first_step(monkeypatch, n, rp, ci, va, v0, step, "tiled")
+    monkeypatch.setenv("SPMV_DEBUG", ed.tiled_debug(W, R))
+    assert spmv.tiled_shape(n, n, int(rp[-1])) == (True, W, R)
+    assert int(np.diff(rp).max()) <= ed.default_long_row(-(-n // W))
+
+
+# ------------------------------------------------------------------------------------------ Lanczos, thick restarts
+@pytest.mark.parametrize("geometry,k,m", ed.LANCZOS_RESTART_CASES)
+def test_lanczos_restart_case_leaves_the_device_room(monkeypatch, geometry, k, m):
+    """The condition for a thick-restart case to be in the catalogue: six restatement orders agree in iterations,
+    restarts and found, and in the values within VALUE_BOUND / 2 of max |lambda|: the device's seventh order has the same
+    room again.  Prints the spread it measures."""
+    s, cap = ed.lanczos_restart_case(geometry, k, m)
+    assert ed.lanes_for(int(s["rp"][-1]), s["n"]) == 1
+    lmax = ed.lanczos_lambda_max(s)
+    for which in WHICH:
+        outs = lanczos_variants(monkeypatch, lambda spmv: ed.lanczos_onehot_reference(s, k, which, m, cap, spmv))
+        want = outs[("numpy", "round once")]
+        assert want["iterations"] == cap and want["restarts"] >= 1 and want["found"] == k
+        assert want["breakdown"] == ec.NO_BREAKDOWN and want["converged"] == 0
+        spread = 0.0
+        for variant, out in outs.items():
+            assert (out["iterations"], out["restarts"], out["found"]) == (cap, want["restarts"], k), variant
+            spread = max(spread, float(np.max(np.abs(out["values"].astype(np.float64) - want["values"]))) / lmax)
+        print(geometry, k, m, which, "restarts", want["restarts"], "spread %.2e x lambda_max" % spread)
+        assert 2 * spread <= ec.VALUE_BOUND / 2                       # any two variants lie within VALUE_BOUND / 2
