@@ -261,6 +261,23 @@ class ColorResult(Structure):
                 ("elapsed_ms", c_float)]
 
 
+class CooConfig(Structure):
+    """include/spmv/assemble.h CooConfig (8 bytes): duplicates COO_SUM (0) = equal (row, column) pairs are summed in
+    source order, COO_KEEP (1) = every triplet becomes an entry"""
+    _fields_ = [("duplicates", c_int32), ("reserved", c_int32)]
+    COO_SUM, COO_KEEP = 0, 1
+
+    def __init__(self, duplicates=0, reserved=0):
+        super().__init__(duplicates, reserved)
+
+
+class CooResult(Structure):
+    """include/spmv/assemble.h CooResult (28 bytes); tile_entries is the number of entries one workgroup sorts per
+    radix pass"""
+    _fields_ = [("error_code", c_int32), ("nnz_out", c_int32), ("combined", c_int32), ("passes", c_int32),
+                ("tile_entries", c_int32), ("launches", c_int32), ("elapsed_ms", c_float)]
+
+
 class SpGEMMResult(Structure):
     """include/spmv/spgemm.h SpGEMMResult (104 bytes); symbolic_rows / numeric_rows count the rows per accumulator
     class of each pass, [0] the rows without products"""
@@ -448,6 +465,16 @@ _SIGNATURES = {
     "spmv_c_permute_gather_async": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
     "spmv_c_multicolor_reorder": (c_int, [POINTER(CSRMatrix), POINTER(CSRMatrix), c_void_p, c_void_p,
                                           POINTER(ColorConfig), POINTER(ColorResult)]),
+    "spmv_c_csr_from_coo_cpu": (c_int, [POINTER(CSRMatrix), c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                        POINTER(CooConfig)]),
+    "spmv_c_csr_from_coo_gpu": (c_int, [POINTER(CSRMatrix), c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                        POINTER(CooConfig), POINTER(c_void_p), POINTER(CooResult)]),
+    "spmv_c_csr_coo_refill": (c_int, [c_void_p, POINTER(CSRMatrix), c_void_p]),
+    "spmv_c_csr_coo_refill_async": (c_int, [c_void_p, POINTER(CSRMatrix), c_void_p, c_void_p]),
+    "spmv_c_coo_plan_destroy": (None, [c_void_p]),
+    "spmv_c_coo_plan_info": (c_int, [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32),
+                                     POINTER(c_int32), POINTER(c_int32)]),
+    "spmv_c_csr_row_indices_gpu": (c_int, [POINTER(CSRMatrix), c_void_p]),
     "spmv_c_compute_bandwidth_csr": (c_int, [POINTER(CSRMatrix), c_float, POINTER(BandwidthMetrics)]),
     "spmv_c_compute_bandwidth_csr_multi": (c_int, [POINTER(CSRMatrix), c_int, c_float, POINTER(BandwidthMetrics)]),
     "spmv_c_compute_bandwidth_ell": (c_int, [POINTER(ELLMatrix), c_float, POINTER(BandwidthMetrics)]),
@@ -1463,6 +1490,60 @@ def multicolor_reorder(B, A, d_perm, d_inverse, config=None) -> ColorResult:
     lib().spmv_c_multicolor_reorder(B, A, _dev(d_perm), _dev(d_inverse),
                                     byref(config) if config is not None else None, byref(out))
     return out
+
+
+# ---- matrix assembly (include/spmv/assemble.h) ------------------------------------------
+COO_SUM, COO_KEEP = 0, 1
+
+
+def csr_from_coo_cpu(C, num_rows, num_cols, rows, cols, vals, config=None, n=None) -> int:
+    """The definition on host arrays (assemble.h csr_from_coo_cpu): C = the matrix of the triplets (rows[p], cols[p],
+    vals[p]); csr_host_arrays(C) reads the result.  n defaults to len(rows)."""
+    r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int32)
+    c = None if cols is None else np.ascontiguousarray(cols, dtype=np.int32)
+    v = None if vals is None else np.ascontiguousarray(vals, dtype=np.float32)
+    if n is None:
+        n = 0 if r is None else r.size
+    return lib().spmv_c_csr_from_coo_cpu(C, int(num_rows), int(num_cols), int(n), None if r is None else _np_ptr(r),
+                                         None if c is None else _np_ptr(c), None if v is None else _np_ptr(v),
+                                         byref(config) if config is not None else None)
+
+
+def csr_from_coo_gpu(C, num_rows, num_cols, n, d_rows, d_cols, d_vals, config=None, want_plan=False):
+    """C from n device triplets, on the device, bit for bit csr_from_coo_cpu's (assemble.h csr_from_coo_gpu).  Returns
+    the CooResult, or (CooResult, plan) with want_plan: the plan (None when the call failed) goes to csr_coo_refill and
+    is released with coo_plan_destroy."""
+    out = CooResult()
+    plan = c_void_p(None)
+    lib().spmv_c_csr_from_coo_gpu(C, int(num_rows), int(num_cols), int(n), _dev(d_rows), _dev(d_cols), _dev(d_vals),
+                                  byref(config) if config is not None else None,
+                                  byref(plan) if want_plan else None, byref(out))
+    return (out, plan.value) if want_plan else out
+
+
+def csr_coo_refill(plan, C, d_vals) -> int:
+    """Only C's device values again, from new values in the same triplet order (assemble.h csr_coo_refill)."""
+    return lib().spmv_c_csr_coo_refill(c_void_p(plan), C, _dev(d_vals))
+
+
+def csr_coo_refill_async(plan, C, d_vals, stream=None) -> int:
+    return lib().spmv_c_csr_coo_refill_async(c_void_p(plan), C, _dev(d_vals), c_void_p(stream))
+
+
+def coo_plan_destroy(plan) -> None:
+    lib().spmv_c_coo_plan_destroy(c_void_p(plan))
+
+
+def coo_plan_info(plan):
+    """(status, num_rows, num_cols, n, nnz_out, duplicates) of a plan."""
+    vals = [c_int32(-7) for _ in range(5)]
+    status = lib().spmv_c_coo_plan_info(c_void_p(plan), *[byref(v) for v in vals])
+    return (status,) + tuple(v.value for v in vals)
+
+
+def csr_row_indices_gpu(A, d_rows) -> int:
+    """d_rows[p] = the row of stored entry p of the device matrix A (assemble.h csr_row_indices_gpu)."""
+    return lib().spmv_c_csr_row_indices_gpu(A, _dev(d_rows))
 
 
 def spmv_auto_config(A) -> SpMVConfig:

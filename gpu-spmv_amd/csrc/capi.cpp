@@ -16,6 +16,7 @@
 #include "spmv/spgemm.h"
 #include "spmv/amg.h"
 #include "spmv/reorder.h"
+#include "spmv/assemble.h"
 #include "spmv_c.h"
 
 #include <cstddef>
@@ -134,6 +135,12 @@ static_assert(offsetof(spmv_c_sptrsv_result, num_levels) == offsetof(SpTRSVResul
               offsetof(spmv_c_sptrsv_result, analysis_ms) == offsetof(SpTRSVResult, analysis_ms) &&
               offsetof(spmv_c_sptrsv_result, elapsed_ms) == offsetof(SpTRSVResult, elapsed_ms), "SpTRSVResult layout");
 
+static_assert(sizeof(spmv_c_coo_config) == sizeof(CooConfig) && sizeof(CooConfig) == 8, "CooConfig layout");
+static_assert(offsetof(spmv_c_coo_config, reserved) == offsetof(CooConfig, reserved), "CooConfig layout");
+static_assert(sizeof(spmv_c_coo_result) == sizeof(CooResult) && sizeof(CooResult) == 28, "CooResult layout");
+static_assert(offsetof(spmv_c_coo_result, nnz_out) == offsetof(CooResult, nnz_out) &&
+              offsetof(spmv_c_coo_result, tile_entries) == offsetof(CooResult, tile_entries) &&
+              offsetof(spmv_c_coo_result, elapsed_ms) == offsetof(CooResult, elapsed_ms), "CooResult layout");
 static_assert(sizeof(spmv_c_color_config) == sizeof(ColorConfig) && sizeof(ColorConfig) == 16, "ColorConfig layout");
 static_assert(offsetof(spmv_c_color_config, symmetric_pattern) == offsetof(ColorConfig, symmetric_pattern) &&
               offsetof(spmv_c_color_config, lanes_per_row) == offsetof(ColorConfig, lanes_per_row) &&
@@ -826,6 +833,39 @@ int spmv_c_multicolor_reorder(spmv_c_csr* B, const spmv_c_csr* A, int32_t* d_per
     if (out) std::memcpy(out, &r, sizeof(r));
     return r.error_code;
 }
+
+// ---- matrix assembly ----
+int spmv_c_csr_from_coo_cpu(spmv_c_csr* C, int num_rows, int num_cols, int n, const int32_t* rows, const int32_t* cols,
+                            const float* vals, const spmv_c_coo_config* config) {
+    return csr_from_coo_cpu(cxx(C), num_rows, num_cols, n, rows, cols, vals, reinterpret_cast<const CooConfig*>(config));
+}
+
+int spmv_c_csr_from_coo_gpu(spmv_c_csr* C, int num_rows, int num_cols, int n, const int32_t* d_rows,
+                            const int32_t* d_cols, const float* d_vals, const spmv_c_coo_config* config,
+                            spmv_c_coo_plan** plan, spmv_c_coo_result* out) {
+    const CooResult r = csr_from_coo_gpu(cxx(C), num_rows, num_cols, n, d_rows, d_cols, d_vals,
+                                         reinterpret_cast<const CooConfig*>(config),
+                                         reinterpret_cast<CooPlan**>(plan));
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
+}
+
+int spmv_c_csr_coo_refill(const spmv_c_coo_plan* plan, spmv_c_csr* C, const float* d_vals) {
+    return csr_coo_refill(reinterpret_cast<const CooPlan*>(plan), cxx(C), d_vals);
+}
+
+int spmv_c_csr_coo_refill_async(const spmv_c_coo_plan* plan, spmv_c_csr* C, const float* d_vals, void* hip_stream) {
+    return csr_coo_refill_async(reinterpret_cast<const CooPlan*>(plan), cxx(C), d_vals, as_stream(hip_stream));
+}
+
+void spmv_c_coo_plan_destroy(spmv_c_coo_plan* plan) { coo_plan_destroy(reinterpret_cast<CooPlan*>(plan)); }
+
+int spmv_c_coo_plan_info(const spmv_c_coo_plan* plan, int32_t* num_rows, int32_t* num_cols, int32_t* n,
+                         int32_t* nnz_out, int32_t* duplicates) {
+    return coo_plan_info(reinterpret_cast<const CooPlan*>(plan), num_rows, num_cols, n, nnz_out, duplicates);
+}
+
+int spmv_c_csr_row_indices_gpu(const spmv_c_csr* A, int32_t* d_rows) { return csr_row_indices_gpu(cxx(A), d_rows); }
 
 // ---- bandwidth ----
 int spmv_c_compute_bandwidth_csr(const spmv_c_csr* A, float elapsed_ms, spmv_c_bandwidth* out) {

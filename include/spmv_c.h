@@ -642,6 +642,52 @@ int spmv_c_permute_gather_async(float* d_out, int ldo, const float* d_in, int ld
 int spmv_c_multicolor_reorder(spmv_c_csr* B, const spmv_c_csr* A, int32_t* d_perm, int32_t* d_inverse,
                               const spmv_c_color_config* config, spmv_c_color_result* out);
 
+/* ---- matrix assembly (extension; include/spmv/assemble.h) ---- */
+/* duplicates: 0 = equal (row, column) pairs are summed in source order, 1 = every triplet is kept; reserved: 0
+ * (8 bytes) */
+typedef struct spmv_c_coo_config {
+    int32_t duplicates;
+    int32_t reserved;
+} spmv_c_coo_config;
+/* 28 bytes; combined = n - nnz_out; passes = radix passes run; tile_entries = entries one workgroup sorts per pass */
+typedef struct spmv_c_coo_result {
+    int32_t error_code;
+    int32_t nnz_out;
+    int32_t combined;
+    int32_t passes;
+    int32_t tile_entries;
+    int32_t launches;
+    float   elapsed_ms;
+} spmv_c_coo_result;
+/* the sorted order of one assembly: 4 * n bytes on the device, plus 4 * (nnz_out + 1) when duplicates are summed */
+typedef struct spmv_c_coo_plan spmv_c_coo_plan;
+
+/* The definition on host arrays: C = the num_rows x num_cols matrix of the n triplets (rows[p], cols[p], vals[p]), in
+ * any order, repeats allowed; stable order by (row, column), equal pairs summed left to right in fp32 from the first
+ * value.  config may be NULL (0, 0).  C owns new host arrays.  Rule and checks as csr_from_coo_cpu in
+ * include/spmv/assemble.h. */
+int spmv_c_csr_from_coo_cpu(spmv_c_csr* C, int num_rows, int num_cols, int n, const int32_t* rows, const int32_t* cols,
+                            const float* vals, const spmv_c_coo_config* config);
+/* The same from device arrays on the device, bit for bit.  C owns new device arrays afterwards (as
+ * spmv_c_csr_transpose_gpu leaves AT).  *plan (plan may be NULL) receives a plan for spmv_c_csr_coo_refill on success.
+ * The return value equals out->error_code (out may be NULL).  Checks and algorithm as csr_from_coo_gpu in
+ * include/spmv/assemble.h. */
+int spmv_c_csr_from_coo_gpu(spmv_c_csr* C, int num_rows, int num_cols, int n, const int32_t* d_rows,
+                            const int32_t* d_cols, const float* d_vals, const spmv_c_coo_config* config,
+                            spmv_c_coo_plan** plan, spmv_c_coo_result* out);
+/* only C's device values again, from a new value array in the same triplet order: one launch; drops C's cached
+ * auxiliary data.  The plan does not re-check C's pattern. */
+int spmv_c_csr_coo_refill(const spmv_c_coo_plan* plan, spmv_c_csr* C, const float* d_vals);
+/* the same enqueued on a caller stream without synchronisation */
+int spmv_c_csr_coo_refill_async(const spmv_c_coo_plan* plan, spmv_c_csr* C, const float* d_vals, void* hip_stream);
+/* NULL is allowed */
+void spmv_c_coo_plan_destroy(spmv_c_coo_plan* plan);
+/* what a plan holds; any output pointer may be NULL */
+int spmv_c_coo_plan_info(const spmv_c_coo_plan* plan, int32_t* num_rows, int32_t* num_cols, int32_t* n,
+                         int32_t* nnz_out, int32_t* duplicates);
+/* d_rows[p] = the row that stores entry p of the device matrix A (nnz ints on the device): CSR back to triplets */
+int spmv_c_csr_row_indices_gpu(const spmv_c_csr* A, int32_t* d_rows);
+
 /* ---- bandwidth model: reference include/spmv/bandwidth.h:21-27 ---- */
 int spmv_c_compute_bandwidth_csr(const spmv_c_csr* A, float elapsed_ms, spmv_c_bandwidth* out);
 int spmv_c_compute_bandwidth_ell(const spmv_c_ell* A, float elapsed_ms, spmv_c_bandwidth* out);
