@@ -278,6 +278,13 @@ class CooResult(Structure):
                 ("tile_entries", c_int32), ("launches", c_int32), ("elapsed_ms", c_float)]
 
 
+class FSAIResult(Structure):
+    """include/spmv/fsai.h FSAIResult (32 bytes); bad_row is the lowest row whose g_ii is not > 0 or not finite, long_row
+    the lowest row with more than 64 pattern entries, -1 when there is none"""
+    _fields_ = [("error_code", c_int32), ("nnz", c_int32), ("max_row", c_int32), ("row_class", c_int32),
+                ("lanes_per_row", c_int32), ("bad_row", c_int32), ("long_row", c_int32), ("elapsed_ms", c_float)]
+
+
 class SpGEMMResult(Structure):
     """include/spmv/spgemm.h SpGEMMResult (104 bytes); symbolic_rows / numeric_rows count the rows per accumulator
     class of each pass, [0] the rows without products"""
@@ -415,6 +422,11 @@ _SIGNATURES = {
     "spmv_c_ic0_csr": (c_int, [POINTER(CSRMatrix), c_void_p, POINTER(IC0Result)]),
     "spmv_c_ic0_csr_async": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p]),
     "spmv_c_ic0_cpu_csr": (c_int, [POINTER(CSRMatrix), c_void_p, POINTER(c_int32)]),
+    "spmv_c_fsai_csr": (c_int, [POINTER(CSRMatrix), POINTER(CSRMatrix), POINTER(CSRMatrix), POINTER(FSAIResult)]),
+    "spmv_c_fsai_csr_numeric": (c_int, [POINTER(CSRMatrix), POINTER(CSRMatrix), POINTER(FSAIResult)]),
+    "spmv_c_fsai_cpu_csr": (c_int, [POINTER(CSRMatrix), POINTER(CSRMatrix), POINTER(CSRMatrix), POINTER(c_int32)]),
+    "spmv_c_cg_solve_fsai": (c_int, [POINTER(CSRMatrix), POINTER(CSRMatrix), POINTER(CSRMatrix), c_void_p, c_void_p,
+                                     POINTER(CGConfig), POINTER(CGResult)]),
     "spmv_c_spgemm_csr": (c_int, [POINTER(CSRMatrix), POINTER(CSRMatrix), POINTER(CSRMatrix), POINTER(SpGEMMResult)]),
     "spmv_c_spgemm_csr_numeric": (c_int, [POINTER(CSRMatrix), POINTER(CSRMatrix), POINTER(CSRMatrix),
                                           POINTER(SpGEMMResult)]),
@@ -798,6 +810,31 @@ def csr_transpose_gpu(AT, A) -> int:
     """Extension: AT = A^T built on the device, deterministic (csr_matrix.h csr_transpose_gpu); csr_from_gpu(AT)
     fills AT's host arrays."""
     return lib().spmv_c_csr_transpose_gpu(AT, A)
+
+
+def fsai_csr(G, A, S=None) -> FSAIResult:
+    """G = FSAI of the square device matrix A on the lower pattern of S (None: A) (include/spmv/fsai.h fsai_csr),
+    bit-identical to fsai_cpu_csr; G owns new device arrays afterwards and csr_from_gpu(G) fills its host arrays.
+    result.error_code is the return value."""
+    out = FSAIResult()
+    out.error_code = lib().spmv_c_fsai_csr(G, A, S, byref(out))
+    return out
+
+
+def fsai_csr_numeric(G, A) -> FSAIResult:
+    """Only G's device values again from a new A, on the pattern an earlier fsai_csr produced (fsai.h
+    fsai_csr_numeric)."""
+    out = FSAIResult()
+    out.error_code = lib().spmv_c_fsai_csr_numeric(G, A, byref(out))
+    return out
+
+
+def fsai_cpu_csr(G, A, S=None):
+    """The same operation on host arrays, the definition of the arithmetic (fsai.h fsai_cpu_csr); G gets new host
+    arrays (csr_host_arrays(G) reads them).  Returns (status, bad_row)."""
+    bad = c_int32(-1)
+    status = lib().spmv_c_fsai_cpu_csr(G, A, S, byref(bad))
+    return status, bad.value
 
 
 def spgemm_csr(C, A, B) -> SpGEMMResult:
@@ -1390,6 +1427,14 @@ def sptrsv_cpu_csr_multi(A, B, config=None) -> np.ndarray:
     if status != 0:
         raise ValueError(spmv_error_string(status))
     return X
+
+
+def cg_solve_fsai(A, G, GT, d_b, d_x, config=None) -> CGResult:
+    """CG preconditioned by M^-1 = GT G, z = GT (G r): two SpMVs per step (include/spmv/cg.h cg_solve_fsai); G is
+    usually fsai_csr's output and GT its csr_transpose_gpu.  config.preconditioner is not read."""
+    out = CGResult()
+    lib().spmv_c_cg_solve_fsai(A, G, GT, _dev(d_b), _dev(d_x), byref(config) if config is not None else None, byref(out))
+    return out
 
 
 def cg_solve_multi_ic(A, F, d_B, d_X, k, ldb=None, ldx=None, config=None) -> list:

@@ -40,6 +40,7 @@ void release(CsrAux* a) {
         if (c.val) (void)hipFree(c.val);
     }
     release_multi_merge(a);
+    if (a->d_fsai_word) (void)hipFree(a->d_fsai_word);
     a->transpose.reset();    // (frees the transpose and its own aux entry unless a call in flight still holds it)
     a->tiled.reset();        // (users still holding the plan keep it alive)
     delete a;

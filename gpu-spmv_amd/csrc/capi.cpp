@@ -12,6 +12,7 @@
 #include "spmv/pagerank.h"
 #include "spmv/sptrsv.h"
 #include "spmv/ic0.h"
+#include "spmv/fsai.h"
 #include "spmv/ilu0.h"
 #include "spmv/spgemm.h"
 #include "spmv/amg.h"
@@ -129,6 +130,14 @@ static_assert(offsetof(spmv_c_ic0_result, num_levels) == offsetof(IC0Result, num
               offsetof(spmv_c_ic0_result, bad_pivot) == offsetof(IC0Result, bad_pivot) &&
               offsetof(spmv_c_ic0_result, analysis_ms) == offsetof(IC0Result, analysis_ms) &&
               offsetof(spmv_c_ic0_result, elapsed_ms) == offsetof(IC0Result, elapsed_ms), "IC0Result layout");
+static_assert(sizeof(spmv_c_fsai_result) == sizeof(FSAIResult) && sizeof(FSAIResult) == 32, "FSAIResult layout");
+static_assert(offsetof(spmv_c_fsai_result, nnz) == offsetof(FSAIResult, nnz) &&
+              offsetof(spmv_c_fsai_result, max_row) == offsetof(FSAIResult, max_row) &&
+              offsetof(spmv_c_fsai_result, row_class) == offsetof(FSAIResult, row_class) &&
+              offsetof(spmv_c_fsai_result, lanes_per_row) == offsetof(FSAIResult, lanes_per_row) &&
+              offsetof(spmv_c_fsai_result, bad_row) == offsetof(FSAIResult, bad_row) &&
+              offsetof(spmv_c_fsai_result, long_row) == offsetof(FSAIResult, long_row) &&
+              offsetof(spmv_c_fsai_result, elapsed_ms) == offsetof(FSAIResult, elapsed_ms), "FSAIResult layout");
 static_assert(offsetof(spmv_c_sptrsv_result, num_levels) == offsetof(SpTRSVResult, num_levels) &&
               offsetof(spmv_c_sptrsv_result, launches) == offsetof(SpTRSVResult, launches) &&
               offsetof(spmv_c_sptrsv_result, lanes_per_row) == offsetof(SpTRSVResult, lanes_per_row) &&
@@ -584,6 +593,13 @@ int spmv_c_cg_solve_ic(const spmv_c_csr* A, const spmv_c_csr* F, const float* d_
     return r.error_code;
 }
 
+int spmv_c_cg_solve_fsai(const spmv_c_csr* A, const spmv_c_csr* G, const spmv_c_csr* GT, const float* d_b, float* d_x,
+                         const spmv_c_cg_config* config, spmv_c_cg_result* out) {
+    const CGResult r = cg_solve_fsai(cxx(A), cxx(G), cxx(GT), d_b, d_x, reinterpret_cast<const CGConfig*>(config));
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
+}
+
 int spmv_c_bicgstab_solve(const spmv_c_csr* A, const float* d_b, float* d_x, const spmv_c_bicgstab_config* config,
                           spmv_c_bicgstab_result* out) {
     const BiCGStabResult r = bicgstab_solve(cxx(A), d_b, d_x, reinterpret_cast<const BiCGStabConfig*>(config));
@@ -651,6 +667,22 @@ int spmv_c_ic0_csr_async(const spmv_c_csr* A, float* d_l_values, void* hip_strea
 
 int spmv_c_ic0_cpu_csr(const spmv_c_csr* A, float* l_values, int32_t* bad_pivot) {
     return ic0_cpu_csr(cxx(A), l_values, bad_pivot);
+}
+
+int spmv_c_fsai_csr(spmv_c_csr* G, const spmv_c_csr* A, const spmv_c_csr* S, spmv_c_fsai_result* out) {
+    const FSAIResult r = fsai_csr(cxx(G), cxx(A), cxx(S));
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
+}
+
+int spmv_c_fsai_csr_numeric(spmv_c_csr* G, const spmv_c_csr* A, spmv_c_fsai_result* out) {
+    const FSAIResult r = fsai_csr_numeric(cxx(G), cxx(A));
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
+}
+
+int spmv_c_fsai_cpu_csr(spmv_c_csr* G, const spmv_c_csr* A, const spmv_c_csr* S, int32_t* bad_row) {
+    return fsai_cpu_csr(cxx(G), cxx(A), cxx(S), bad_row);
 }
 
 int spmv_c_spgemm_csr(spmv_c_csr* C, const spmv_c_csr* A, const spmv_c_csr* B, spmv_c_spgemm_result* out) {

@@ -22,6 +22,9 @@
 // cg_solve_amg is cg_solve_ic's loop with z = one V-cycle of an AMG hierarchy on r (amg_vcycle, amg.hip, DESIGN.md
 // §4.16) in place of the two triangular solves; its kernels read `done` themselves.
 //
+// cg_solve_fsai is the same loop again with z = GT (G r) (include/spmv/fsai.h): two launches of the
+// direct vector-CSR kernel (launch_csr_vector, kernels.hip) through a fifth workspace vector t; they do not read `done`.
+//
 // The host side is built from solver_common.h's parts (Workspace and its mirror, TriangularPair, TiledEngine,
 // diag_kernel); what is here is this solver's checks, its workspace layout, its launches and its result.
 #include "amg_impl.h"
@@ -262,14 +265,16 @@ hipError_t spmv_dot(int lanes, const CSRMatrix* A, const float* p, float* q, con
 
 // What gives z: the diagonal inside the step kernels (cg_solve: cfg.preconditioner picks NONE or JACOBI), or a stored z
 // from M = L L^T of the factor matrix F (cg_solve_ic) or from one V-cycle of the hierarchy H (cg_solve_amg); the last
-// two do not read cfg.preconditioner.
-enum class Precond { DIAGONAL, IC, AMG };
+// two do not read cfg.preconditioner.  FSAI (cg_solve_fsai): a stored z = FT (F t), t = F r, two direct vector-CSR
+// SpMVs with F = G and FT = GT; it does not read cfg.preconditioner either.
+enum class Precond { DIAGONAL, IC, AMG, FSAI };
 
-CGResult solve(const CSRMatrix* A, Precond precond, const CSRMatrix* F, const AMGHierarchy* H, const float* d_b,
-               float* d_x, const CGConfig* config) {
+CGResult solve(const CSRMatrix* A, Precond precond, const CSRMatrix* F, const CSRMatrix* FT, const AMGHierarchy* H,
+               const float* d_b, float* d_x, const CGConfig* config) {
     const bool with_ic = precond == Precond::IC;
     const bool with_amg = precond == Precond::AMG;
-    const bool stored_z = with_ic || with_amg;
+    const bool with_fsai = precond == Precond::FSAI;
+    const bool stored_z = with_ic || with_amg || with_fsai;
     CGResult result;
     const auto fail = [&result](SpMVError e) {
         result.error_code = code(e);
@@ -301,8 +306,16 @@ CGResult solve(const CSRMatrix* A, Precond precond, const CSRMatrix* F, const AM
         if (H->num_rows != n) return fail(SpMVError::INVALID_DIMENSION);
         if (H->config.pre_sweeps != H->config.post_sweeps) return fail(SpMVError::INVALID_ARGUMENT);
     }
+    if (with_fsai) {
+        if (!F || !FT) return fail(SpMVError::INVALID_ARGUMENT);
+        for (const CSRMatrix* M : {F, FT}) {
+            if (M->num_rows != M->num_cols || M->num_rows != n) return fail(SpMVError::INVALID_DIMENSION);
+        }
+        if (!device_arrays(F) || !device_arrays(FT)) return fail(SpMVError::INVALID_FORMAT);
+    }
 
-    const TraceRange range(with_ic ? "spmv:cg_solve_ic" : with_amg ? "spmv:cg_solve_amg" : "spmv:cg_solve");
+    const TraceRange range(with_ic ? "spmv:cg_solve_ic" : with_amg ? "spmv:cg_solve_amg" :
+                           with_fsai ? "spmv:cg_solve_fsai" : "spmv:cg_solve");
     hipStream_t stream = current_stream();
     const bool jacobi = !stored_z && cfg.preconditioner == CGConfig::JACOBI;
 
@@ -321,20 +334,29 @@ CGResult solve(const CSRMatrix* A, Precond precond, const CSRMatrix* F, const AM
     const size_t rr_count = 2 * static_cast<size_t>(vgrid);
     const size_t init_count = 3 * static_cast<size_t>(row_grid);
 
-    Workspace<CgState> ws;          // r, p, q, and dinv (JACOBI) or z (IC, AMG)
+    Workspace<CgState> ws;          // r, p, q, and dinv (JACOBI) or z (IC, AMG, FSAI); FSAI: t = G r as well
     const size_t len = static_cast<size_t>(n);
-    if (!ws.allocate(4 * len, pq_count + rr_count + init_count)) return fail(SpMVError::CUDA_MALLOC);
+    if (!ws.allocate((with_fsai ? 5 : 4) * len, pq_count + rr_count + init_count)) return fail(SpMVError::CUDA_MALLOC);
     float* r = ws.vec;
     float* p = ws.vec + len;
     float* q = ws.vec + 2 * len;
     float* dinv = jacobi ? ws.vec + 3 * len : nullptr;
     float* z = stored_z ? ws.vec + 3 * len : nullptr;
+    float* t = with_fsai ? ws.vec + 4 * len : nullptr;
+    // FSAI: the lanes of each factor's own mean row length; the launches are the direct vector kernel's, not a dispatch
+    const int g_lanes = with_fsai ? pick_lanes_per_row(static_cast<float>(F->nnz) / n) : 0;
+    const int gt_lanes = with_fsai ? pick_lanes_per_row(static_cast<float>(FT->nnz) / n) : 0;
     double* pq_part = ws.part;
     double* rr_part = ws.part + pq_count;
     double* init_part = rr_part + rr_count;
-    // out = M^-1 in.  IC: both triangular solves.  AMG: one V-cycle, whose kernels read `done`.
+    // out = M^-1 in.  IC: both triangular solves.  AMG: one V-cycle, whose kernels read `done`.  FSAI: two SpMVs,
+    // which like the triangular solves do not read `done`: after it r no longer changes and they rewrite the same z.
     const auto apply_stored = [&](const float* in, float* out) -> bool {
         if (with_amg) return amg_vcycle(*H, in, out, &ws.state->done, amg_lanes, stream) == hipSuccess;
+        if (with_fsai) {
+            return launch_csr_vector(F, in, t, g_lanes, stream) == hipSuccess &&
+                   launch_csr_vector(FT, t, out, gt_lanes, stream) == hipSuccess;
+        }
         return ic.apply(in, out, stream);
     };
 
@@ -419,15 +441,20 @@ CGResult solve(const CSRMatrix* A, Precond precond, const CSRMatrix* F, const AM
 } // namespace detail
 
 CGResult cg_solve(const CSRMatrix* A, const float* d_b, float* d_x, const CGConfig* config) {
-    return detail::solve(A, detail::Precond::DIAGONAL, nullptr, nullptr, d_b, d_x, config);
+    return detail::solve(A, detail::Precond::DIAGONAL, nullptr, nullptr, nullptr, d_b, d_x, config);
 }
 
 CGResult cg_solve_ic(const CSRMatrix* A, const CSRMatrix* F, const float* d_b, float* d_x, const CGConfig* config) {
-    return detail::solve(A, detail::Precond::IC, F, nullptr, d_b, d_x, config);
+    return detail::solve(A, detail::Precond::IC, F, nullptr, nullptr, d_b, d_x, config);
 }
 
 CGResult cg_solve_amg(const CSRMatrix* A, const AMGHierarchy* H, const float* d_b, float* d_x, const CGConfig* config) {
-    return detail::solve(A, detail::Precond::AMG, nullptr, H, d_b, d_x, config);
+    return detail::solve(A, detail::Precond::AMG, nullptr, nullptr, H, d_b, d_x, config);
+}
+
+CGResult cg_solve_fsai(const CSRMatrix* A, const CSRMatrix* G, const CSRMatrix* GT, const float* d_b, float* d_x,
+                       const CGConfig* config) {
+    return detail::solve(A, detail::Precond::FSAI, G, GT, nullptr, d_b, d_x, config);
 }
 
 } // namespace spmv

@@ -206,21 +206,17 @@ int csr_transpose_gpu(CSRMatrix* AT, const CSRMatrix* A) {
     detail::TransposeArrays t;
     const int status = detail::transpose_build(A, &t, detail::current_stream());
     if (status != 0) return status;
-    const int rows = A->num_cols, cols = A->num_rows, nnz = A->nnz;     // (read before AT, maybe A, changes)
-    csr_free_gpu(AT);
-    release_host(AT);
-    AT->num_rows = rows;
-    AT->num_cols = cols;
-    AT->nnz = nnz;
-    AT->values = nnz > 0 ? new float[nnz] : nullptr;
-    AT->col_indices = nnz > 0 ? new int[nnz] : nullptr;
-    AT->row_ptrs = new int[static_cast<size_t>(rows) + 1];
-    AT->owns_host_memory = true;
-    AT->d_row_ptrs = t.row_ptrs;
-    AT->d_col_indices = t.col_indices;
-    AT->d_values = t.values;
-    AT->owns_device_memory = true;
+    detail::csr_adopt_device(AT, A->num_cols, A->num_rows, A->nnz, t);  // (the arguments are read before AT, maybe A, changes)
     return detail::code(SpMVError::SUCCESS);
+}
+
+void detail::csr_adopt_device(CSRMatrix* M, int rows, int cols, int nnz, const TransposeArrays& arrays) {
+    csr_free_gpu(M);
+    adopt_shape(M, rows, cols, nnz);
+    M->d_row_ptrs = arrays.row_ptrs;
+    M->d_col_indices = arrays.col_indices;
+    M->d_values = arrays.values;
+    M->owns_device_memory = true;
 }
 
 int csr_serialize(const CSRMatrix* mat, const char* filename) {

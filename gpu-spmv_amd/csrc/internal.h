@@ -149,6 +149,10 @@ struct CsrAux {
     // plans thrown away because another matrix over the same row-pointer array (the side table's key) wanted one: past
     // two, promotion stops building for this key — callers that alternate such matrices would rebuild on every call
     int plan_replacements = 0;
+    // fsai_csr (fsai_host.cpp), kept with the G it built for fsai_csr_numeric: the longest row of the pattern (0: not
+    // known) and the device word the bad_row scan folds into, so that a refill allocates and reads back nothing else
+    int fsai_max_row = 0;
+    unsigned* d_fsai_word = nullptr;
 };
 
 // Ski-rental promotion: the reference's own callers spell the kernel and never set use_texture
@@ -195,6 +199,9 @@ void    ell_aux_drop(const void* key);
 //                              is ignored)
 //   ilu0_lanes=N               lanes per row of ilu0_csr (1, 2, 4, ... 64; anything else is ignored)
 //   ic0_lanes=N                lanes per row of ic0_csr (1, 2, 4, ... 64; anything else is ignored)
+//   fsai_lanes=N               lanes per row of fsai_csr's numeric kernel (1, 2, 4, ... 64; anything else is ignored)
+//   fsai_class=C               LDS capacity class of that kernel (4, 8, 16, 32, 64; anything else is ignored); a class
+//                              below the longest pattern row is INVALID_ARGUMENT
 //   spgemm_lanes=N             lanes per row of C in spgemm_csr (1, 2, 4, ... 64; anything else is ignored)
 //   spgemm_class=N             accumulator class every row of spgemm_csr takes (1 .. 5); a row too large for it takes
 //                              the first class that holds it
@@ -248,6 +255,9 @@ hipError_t launch_fill_zero(float* d_y, size_t n, hipStream_t s);
 // device transpose (transpose.hip): validates A (INVALID_FORMAT before anything is allocated), then builds A^T on
 // `s` and returns after the build completed, its scratch freed.  The caller owns *out on SUCCESS.
 int transpose_build(const CSRMatrix* A, TransposeArrays* out, hipStream_t s);
+// How a builder hands its result over (csr_matrix.cpp; csr_transpose_gpu's rule for AT): M's old device arrays and
+// cached data are dropped, it owns `arrays` from now on, and its host arrays are allocated at the new size without data.
+void csr_adopt_device(CSRMatrix* M, int rows, int cols, int nnz, const TransposeArrays& arrays);
 // the scan of transpose.hip for other builders (spgemm.hip): device_scan_levels(n) gives the level sizes n,
 // ceil(n / 4096), ... 1; device_exclusive_scan scans data[0, n) in place on `s`, with `sums` holding the sum of
 // levels[1 ..] ints plus one

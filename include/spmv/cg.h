@@ -152,6 +152,22 @@ struct AMGHierarchy;
 CGResult cg_solve_amg(const CSRMatrix* A, const AMGHierarchy* H, const float* d_b, float* d_x,
                       const CGConfig* config = nullptr);
 
+// cg_solve preconditioned by a factorised sparse approximate inverse M^-1 = GT G (spmv/fsai.h): cg_solve_ic's
+// iteration with z = GT (G r), two SpMVs, in place of the two triangular solves.  The preconditioner comes in as
+// matrices: G is usually fsai_csr's output and GT csr_transpose_gpu(GT, G); entries are taken as stored, nothing tests
+// that GT is G's transpose.  config->preconditioner is not read.  z is a stored vector and t = G r a fifth workspace
+// vector; the stored-z step kernels, the SpMV half of a step, the engines for A, the plan caching, the stop rules and
+// the breakdown rule are cg_solve_ic's.  The two SpMVs are direct vector-CSR launches with the lanes per row of each
+// matrix's own mean row length: they never go through the dispatcher, so no promotion count, merge-path state or tiled
+// plan of G or GT is touched.  Per step on the direct engine six launches (SpMV + dot, update, G, GT, r.z, direction),
+// whatever the matrix.  A solve is bitwise reproducible from run to run on each engine.
+//
+// Checks, before any write to d_x: cg_solve's, in their order, then: null G or GT -> INVALID_ARGUMENT; either not
+// square or of another size than A -> INVALID_DIMENSION; device arrays of either missing -> INVALID_FORMAT.  An M that
+// is not positive definite surfaces as a breakdown, x at the last good iterate, as with cg_solve_amg.
+CGResult cg_solve_fsai(const CSRMatrix* A, const CSRMatrix* G, const CSRMatrix* GT, const float* d_b, float* d_x,
+                       const CGConfig* config = nullptr);
+
 } // namespace spmv
 
 #endif

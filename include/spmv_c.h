@@ -283,6 +283,13 @@ int spmv_c_cg_solve_multi(const spmv_c_csr* A, const float* d_B, int ldb, float*
 int spmv_c_cg_solve_ic(const spmv_c_csr* A, const spmv_c_csr* F, const float* d_b, float* d_x,
                        const spmv_c_cg_config* config, spmv_c_cg_result* out);
 
+/* the same iteration preconditioned by a factorised sparse approximate inverse M^-1 = GT G: z = GT (G r), two direct
+ * vector-CSR SpMVs per step (G usually spmv_c_fsai_csr's output, GT its spmv_c_csr_transpose_gpu).
+ * config->preconditioner is not read.  Checks and numerics as cg_solve_fsai in include/spmv/cg.h.  The return value equals out->error_code
+ * (out may be NULL). */
+int spmv_c_cg_solve_fsai(const spmv_c_csr* A, const spmv_c_csr* G, const spmv_c_csr* GT, const float* d_b, float* d_x,
+                         const spmv_c_cg_config* config, spmv_c_cg_result* out);
+
 /* spmv_c_cg_solve_ic for k right-hand sides (1..32) in spmv_c_cg_solve_multi's layout: one matrix pass and one k-wide
  * launch sequence per triangular solve and step.  Column j is bit for bit spmv_c_cg_solve_ic with engine 0 on that
  * column.  Checks and numerics as cg_solve_multi_ic in include/spmv/cg.h.  Returns the error code. */
@@ -507,6 +514,30 @@ int spmv_c_ic0_csr(const spmv_c_csr* A, float* d_l_values, spmv_c_ic0_result* ou
 int spmv_c_ic0_csr_async(const spmv_c_csr* A, float* d_l_values, void* hip_stream);
 /* the factorisation on A's host arrays (l_values: nnz floats, may be A's host values); *bad_pivot may be NULL */
 int spmv_c_ic0_cpu_csr(const spmv_c_csr* A, float* l_values, int32_t* bad_pivot);
+
+/* ---- factorised sparse approximate inverse G ~ L^-1, A = L L^T (extension; include/spmv/fsai.h) ---- */
+/* 32 bytes */
+typedef struct spmv_c_fsai_result {
+    int32_t error_code;
+    int32_t nnz;            /* stored entries of G */
+    int32_t max_row;        /* longest pattern row */
+    int32_t row_class;      /* capacity class of the kernel: 4, 8, 16, 32 or 64 */
+    int32_t lanes_per_row;
+    int32_t bad_row;        /* lowest row whose g_ii is not > 0 or not finite, or -1 */
+    int32_t long_row;       /* lowest row with more than 64 pattern entries, or -1 */
+    float   elapsed_ms;     /* structure build + numeric kernel */
+} spmv_c_fsai_result;
+
+/* G = FSAI of the square device matrix A (rows strictly ascending; only the values on and left of the diagonal are
+ * read) on the lower pattern of S (NULL: A; only S's structure is read).  G owns new device arrays afterwards (as
+ * spmv_c_csr_transpose_gpu leaves AT); spmv_c_csr_from_gpu(G) fills its host arrays.  Bit-identical to
+ * spmv_c_fsai_cpu_csr at every lane count and row class.  Checks and arithmetic as fsai_csr in include/spmv/fsai.h.
+ * The return value equals out->error_code (out may be NULL). */
+int spmv_c_fsai_csr(spmv_c_csr* G, const spmv_c_csr* A, const spmv_c_csr* S, spmv_c_fsai_result* out);
+/* only G's device values again from a new A, on the pattern an earlier spmv_c_fsai_csr produced */
+int spmv_c_fsai_csr_numeric(spmv_c_csr* G, const spmv_c_csr* A, spmv_c_fsai_result* out);
+/* the same operation on host arrays, the definition of the arithmetic; G gets new host arrays; *bad_row may be NULL */
+int spmv_c_fsai_cpu_csr(spmv_c_csr* G, const spmv_c_csr* A, const spmv_c_csr* S, int32_t* bad_row);
 
 /* ---- sparse matrix-matrix product C = A*B (extension; include/spmv/spgemm.h) ---- */
 /* 104 bytes */
