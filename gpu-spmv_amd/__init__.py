@@ -278,6 +278,13 @@ class CooResult(Structure):
                 ("tile_entries", c_int32), ("launches", c_int32), ("elapsed_ms", c_float)]
 
 
+class CsrAddResult(Structure):
+    """include/spmv/csr_ops.h CsrAddResult (32 bytes); common counts the columns found in both matrices, launches the
+    kernel launches of the call"""
+    _fields_ = [("error_code", c_int32), ("nnz", c_int32), ("common", c_int32), ("max_row_nnz", c_int32),
+                ("lanes", c_int32), ("launches", c_int32), ("symbolic_ms", c_float), ("numeric_ms", c_float)]
+
+
 class FSAIResult(Structure):
     """include/spmv/fsai.h FSAIResult (32 bytes); bad_row is the lowest row whose g_ii is not > 0 or not finite, long_row
     the lowest row with more than 64 pattern entries, -1 when there is none"""
@@ -487,6 +494,17 @@ _SIGNATURES = {
     "spmv_c_coo_plan_info": (c_int, [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32),
                                      POINTER(c_int32), POINTER(c_int32)]),
     "spmv_c_csr_row_indices_gpu": (c_int, [POINTER(CSRMatrix), c_void_p]),
+    "spmv_c_csr_add": (c_int, [POINTER(CSRMatrix), c_float, POINTER(CSRMatrix), c_float, POINTER(CSRMatrix),
+                               POINTER(CsrAddResult)]),
+    "spmv_c_csr_add_numeric": (c_int, [POINTER(CSRMatrix), c_float, POINTER(CSRMatrix), c_float, POINTER(CSRMatrix),
+                                       POINTER(CsrAddResult)]),
+    "spmv_c_csr_add_cpu": (c_int, [POINTER(CSRMatrix), c_float, POINTER(CSRMatrix), c_float, POINTER(CSRMatrix)]),
+    "spmv_c_csr_scale_gpu": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, c_void_p]),
+    "spmv_c_csr_scale_cpu": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, c_void_p]),
+    "spmv_c_csr_diagonal_gpu": (c_int, [POINTER(CSRMatrix), c_void_p]),
+    "spmv_c_csr_diagonal_cpu": (c_int, [POINTER(CSRMatrix), c_void_p]),
+    "spmv_c_csr_diag_matrix_gpu": (c_int, [POINTER(CSRMatrix), c_int, c_void_p]),
+    "spmv_c_csr_diag_matrix_cpu": (c_int, [POINTER(CSRMatrix), c_int, c_void_p]),
     "spmv_c_compute_bandwidth_csr": (c_int, [POINTER(CSRMatrix), c_float, POINTER(BandwidthMetrics)]),
     "spmv_c_compute_bandwidth_csr_multi": (c_int, [POINTER(CSRMatrix), c_int, c_float, POINTER(BandwidthMetrics)]),
     "spmv_c_compute_bandwidth_ell": (c_int, [POINTER(ELLMatrix), c_float, POINTER(BandwidthMetrics)]),
@@ -1589,6 +1607,71 @@ def coo_plan_info(plan):
 def csr_row_indices_gpu(A, d_rows) -> int:
     """d_rows[p] = the row of stored entry p of the device matrix A (assemble.h csr_row_indices_gpu)."""
     return lib().spmv_c_csr_row_indices_gpu(A, _dev(d_rows))
+
+
+def csr_add(C, alpha, A, beta, B) -> CsrAddResult:
+    """C = alpha*A + beta*B of two device matrices with strictly ascending rows (include/spmv/csr_ops.h csr_add),
+    bit-identical to csr_add_cpu; C owns new device arrays afterwards and csr_from_gpu(C) fills its host arrays.
+    result.error_code is the return value."""
+    out = CsrAddResult()
+    out.error_code = lib().spmv_c_csr_add(C, float(alpha), A, float(beta), B, byref(out))
+    return out
+
+
+def csr_add_numeric(C, alpha, A, beta, B) -> CsrAddResult:
+    """Only C's device values again, into the pattern an earlier csr_add produced (csr_ops.h csr_add_numeric)."""
+    out = CsrAddResult()
+    out.error_code = lib().spmv_c_csr_add_numeric(C, float(alpha), A, float(beta), B, byref(out))
+    return out
+
+
+def csr_add_cpu(C, alpha, A, beta, B) -> int:
+    """The sum on host arrays, the definition of the arithmetic (csr_ops.h csr_add_cpu); C gets new host arrays."""
+    return lib().spmv_c_csr_add_cpu(C, float(alpha), A, float(beta), B)
+
+
+def csr_scale_gpu(A, d_row_scale=None, d_col_scale=None, d_values_out=None) -> int:
+    """out[p] = a[p] * (r[row] * c[col]) on the device (csr_ops.h csr_scale_gpu); a scale may be None; d_values_out
+    None = in place into A's device values."""
+    return lib().spmv_c_csr_scale_gpu(A, _dev(d_row_scale), _dev(d_col_scale), _dev(d_values_out))
+
+
+def _f32_or_none(a):
+    return None if a is None else np.ascontiguousarray(a, dtype=np.float32)
+
+
+def csr_scale_cpu(A, row_scale=None, col_scale=None):
+    """(status, values) of the same scaling of A's host arrays (csr_ops.h csr_scale_cpu)."""
+    r, c = _f32_or_none(row_scale), _f32_or_none(col_scale)
+    out = np.empty(max(int(A.contents.nnz), 0), np.float32)
+    status = lib().spmv_c_csr_scale_cpu(A, None if r is None else _np_ptr(r), None if c is None else _np_ptr(c),
+                                        _np_ptr(out))
+    return status, out
+
+
+def csr_diagonal_gpu(A, d_diag) -> int:
+    """d_diag[i] = the fp32 sum of row i's stored (i, i) entries, 0 where there is none (csr_ops.h csr_diagonal_gpu)."""
+    return lib().spmv_c_csr_diagonal_gpu(A, _dev(d_diag))
+
+
+def csr_diagonal_cpu(A):
+    """(status, diag) of the same on A's host arrays (csr_ops.h csr_diagonal_cpu)."""
+    out = np.empty(max(int(A.contents.num_rows), 0), np.float32)
+    status = lib().spmv_c_csr_diagonal_cpu(A, _np_ptr(out))
+    return status, out
+
+
+def csr_diag_matrix_gpu(D, n, d_diag=None) -> int:
+    """D = the n x n diagonal matrix of the device vector d_diag, the identity when it is None (csr_ops.h
+    csr_diag_matrix_gpu); D owns new device arrays afterwards."""
+    return lib().spmv_c_csr_diag_matrix_gpu(D, int(n), _dev(d_diag))
+
+
+def csr_diag_matrix_cpu(D, n, diag=None) -> int:
+    """The same on the host: D gets new host arrays (csr_ops.h csr_diag_matrix_cpu)."""
+    d = _f32_or_none(diag)
+    assert d is None or d.size >= n
+    return lib().spmv_c_csr_diag_matrix_cpu(D, int(n), None if d is None else _np_ptr(d))
 
 
 def spmv_auto_config(A) -> SpMVConfig:

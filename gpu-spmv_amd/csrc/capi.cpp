@@ -18,6 +18,7 @@
 #include "spmv/amg.h"
 #include "spmv/reorder.h"
 #include "spmv/assemble.h"
+#include "spmv/csr_ops.h"
 #include "spmv_c.h"
 
 #include <cstddef>
@@ -150,6 +151,15 @@ static_assert(sizeof(spmv_c_coo_result) == sizeof(CooResult) && sizeof(CooResult
 static_assert(offsetof(spmv_c_coo_result, nnz_out) == offsetof(CooResult, nnz_out) &&
               offsetof(spmv_c_coo_result, tile_entries) == offsetof(CooResult, tile_entries) &&
               offsetof(spmv_c_coo_result, elapsed_ms) == offsetof(CooResult, elapsed_ms), "CooResult layout");
+static_assert(sizeof(spmv_c_csr_add_result) == sizeof(CsrAddResult) && sizeof(CsrAddResult) == 32, "CsrAddResult layout");
+static_assert(offsetof(spmv_c_csr_add_result, error_code) == offsetof(CsrAddResult, error_code) &&
+              offsetof(spmv_c_csr_add_result, nnz) == offsetof(CsrAddResult, nnz) &&
+              offsetof(spmv_c_csr_add_result, common) == offsetof(CsrAddResult, common) &&
+              offsetof(spmv_c_csr_add_result, max_row_nnz) == offsetof(CsrAddResult, max_row_nnz) &&
+              offsetof(spmv_c_csr_add_result, lanes) == offsetof(CsrAddResult, lanes) &&
+              offsetof(spmv_c_csr_add_result, launches) == offsetof(CsrAddResult, launches) &&
+              offsetof(spmv_c_csr_add_result, symbolic_ms) == offsetof(CsrAddResult, symbolic_ms) &&
+              offsetof(spmv_c_csr_add_result, numeric_ms) == offsetof(CsrAddResult, numeric_ms), "CsrAddResult layout");
 static_assert(sizeof(spmv_c_color_config) == sizeof(ColorConfig) && sizeof(ColorConfig) == 16, "ColorConfig layout");
 static_assert(offsetof(spmv_c_color_config, symmetric_pattern) == offsetof(ColorConfig, symmetric_pattern) &&
               offsetof(spmv_c_color_config, lanes_per_row) == offsetof(ColorConfig, lanes_per_row) &&
@@ -898,6 +908,45 @@ int spmv_c_coo_plan_info(const spmv_c_coo_plan* plan, int32_t* num_rows, int32_t
 }
 
 int spmv_c_csr_row_indices_gpu(const spmv_c_csr* A, int32_t* d_rows) { return csr_row_indices_gpu(cxx(A), d_rows); }
+
+// ---- CSR algebra (include/spmv/csr_ops.h) ----
+int spmv_c_csr_add(spmv_c_csr* C, float alpha, const spmv_c_csr* A, float beta, const spmv_c_csr* B,
+                   spmv_c_csr_add_result* out) {
+    CsrAddResult r;
+    const int status = csr_add(cxx(C), alpha, cxx(A), beta, cxx(B), &r);
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return status;
+}
+
+int spmv_c_csr_add_numeric(spmv_c_csr* C, float alpha, const spmv_c_csr* A, float beta, const spmv_c_csr* B,
+                           spmv_c_csr_add_result* out) {
+    CsrAddResult r;
+    const int status = csr_add_numeric(cxx(C), alpha, cxx(A), beta, cxx(B), &r);
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return status;
+}
+
+int spmv_c_csr_add_cpu(spmv_c_csr* C, float alpha, const spmv_c_csr* A, float beta, const spmv_c_csr* B) {
+    return csr_add_cpu(cxx(C), alpha, cxx(A), beta, cxx(B));
+}
+
+int spmv_c_csr_scale_gpu(spmv_c_csr* A, const float* d_row_scale, const float* d_col_scale, float* d_values_out) {
+    return csr_scale_gpu(cxx(A), d_row_scale, d_col_scale, d_values_out);
+}
+
+int spmv_c_csr_scale_cpu(const spmv_c_csr* A, const float* row_scale, const float* col_scale, float* values_out) {
+    return csr_scale_cpu(cxx(A), row_scale, col_scale, values_out);
+}
+
+int spmv_c_csr_diagonal_gpu(const spmv_c_csr* A, float* d_diag) { return csr_diagonal_gpu(cxx(A), d_diag); }
+
+int spmv_c_csr_diagonal_cpu(const spmv_c_csr* A, float* diag) { return csr_diagonal_cpu(cxx(A), diag); }
+
+int spmv_c_csr_diag_matrix_gpu(spmv_c_csr* D, int n, const float* d_diag) {
+    return csr_diag_matrix_gpu(cxx(D), n, d_diag);
+}
+
+int spmv_c_csr_diag_matrix_cpu(spmv_c_csr* D, int n, const float* diag) { return csr_diag_matrix_cpu(cxx(D), n, diag); }
 
 // ---- bandwidth ----
 int spmv_c_compute_bandwidth_csr(const spmv_c_csr* A, float elapsed_ms, spmv_c_bandwidth* out) {

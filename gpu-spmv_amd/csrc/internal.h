@@ -210,6 +210,7 @@ void    ell_aux_drop(const void* key);
 //                              anything else is ignored)
 //   mis_lanes=N                lanes per row of the MIS-2 aggregation's kernels (1, 2, 4, ... 64; anything else is ignored)
 //   ppr_lanes=N                lanes per row of pagerank_personalized's step (1, 2, 4, ... 64; anything else is ignored)
+//   add_lanes=N                lanes per row of csr_add and csr_add_numeric (1, 2, 4, ... 64; anything else is ignored)
 // Everything else the library reads from the environment is listed in INTEGRATION.md.
 bool debug_option(const char* key, long long* value = nullptr, char* text = nullptr, size_t text_size = 0);
 // the same "key=value,key" syntax for another variable's value (SPMV_MULTI_GPU); `list` may be null

@@ -719,6 +719,42 @@ int spmv_c_coo_plan_info(const spmv_c_coo_plan* plan, int32_t* num_rows, int32_t
 /* d_rows[p] = the row that stores entry p of the device matrix A (nnz ints on the device): CSR back to triplets */
 int spmv_c_csr_row_indices_gpu(const spmv_c_csr* A, int32_t* d_rows);
 
+/* ---- CSR algebra: C = alpha*A + beta*B, scaling, the diagonal in and out (extension; include/spmv/csr_ops.h) ---- */
+/* 32 bytes; common = columns found in both matrices; launches = kernel launches of the call */
+typedef struct spmv_c_csr_add_result {
+    int32_t error_code;
+    int32_t nnz;            /* entries of C */
+    int32_t common;
+    int32_t max_row_nnz;
+    int32_t lanes;          /* lanes that share one row */
+    int32_t launches;
+    float   symbolic_ms;
+    float   numeric_ms;
+} spmv_c_csr_add_result;
+
+/* C = alpha*A + beta*B of two device matrices with strictly ascending rows, bit-identical to spmv_c_csr_add_cpu: the
+ * pattern is the union, cancelled entries are kept.  C owns new device arrays afterwards (as spmv_c_csr_transpose_gpu
+ * leaves AT).  Rule and checks as csr_add in include/spmv/csr_ops.h.  The return value equals out->error_code (out
+ * may be NULL). */
+int spmv_c_csr_add(spmv_c_csr* C, float alpha, const spmv_c_csr* A, float beta, const spmv_c_csr* B,
+                   spmv_c_csr_add_result* out);
+/* only C's device values again, into the pattern an earlier spmv_c_csr_add produced: one launch; the pattern is
+ * checked; drops C's cached auxiliary data */
+int spmv_c_csr_add_numeric(spmv_c_csr* C, float alpha, const spmv_c_csr* A, float beta, const spmv_c_csr* B,
+                           spmv_c_csr_add_result* out);
+/* the sum on host arrays, the definition of the arithmetic; C gets new host arrays */
+int spmv_c_csr_add_cpu(spmv_c_csr* C, float alpha, const spmv_c_csr* A, float beta, const spmv_c_csr* B);
+/* out[p] = a[p] * (r[row] * c[col]), each product rounded to fp32; either scale may be NULL; d_values_out NULL or
+ * A's own device values = in place (drops A's cached auxiliary data) */
+int spmv_c_csr_scale_gpu(spmv_c_csr* A, const float* d_row_scale, const float* d_col_scale, float* d_values_out);
+int spmv_c_csr_scale_cpu(const spmv_c_csr* A, const float* row_scale, const float* col_scale, float* values_out);
+/* d_diag[i] = fp32 sum of row i's stored (i, i) entries in storage order, 0 where there is none (num_rows floats) */
+int spmv_c_csr_diagonal_gpu(const spmv_c_csr* A, float* d_diag);
+int spmv_c_csr_diagonal_cpu(const spmv_c_csr* A, float* diag);
+/* D = the n x n diagonal matrix of d_diag, the identity when d_diag is NULL; zeros are kept */
+int spmv_c_csr_diag_matrix_gpu(spmv_c_csr* D, int n, const float* d_diag);
+int spmv_c_csr_diag_matrix_cpu(spmv_c_csr* D, int n, const float* diag);
+
 /* ---- bandwidth model: reference include/spmv/bandwidth.h:21-27 ---- */
 int spmv_c_compute_bandwidth_csr(const spmv_c_csr* A, float elapsed_ms, spmv_c_bandwidth* out);
 int spmv_c_compute_bandwidth_ell(const spmv_c_ell* A, float elapsed_ms, spmv_c_bandwidth* out);
