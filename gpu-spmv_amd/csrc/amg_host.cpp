@@ -116,6 +116,7 @@ int dense_inverse(int n, const int* rp, const int* ci, const float* va, std::vec
     return -1;
 }
 
+// not device_arrays_strict: nnz < 0 fails here (there it counts as no entries), num_rows is the caller's to check
 bool device_arrays(const CSRMatrix* M) {
     return M->nnz >= 0 && M->d_row_ptrs && (M->nnz == 0 || (M->d_col_indices && M->d_values));
 }

@@ -13,7 +13,7 @@
 //                both rules only act on states that are final, so which of the current round's writes a vertex
 //                happens to see changes the round it decides in, never its state.
 //                The only atomic is one add per workgroup to the count of vertices left.
-//   numbers      the root flags scanned by transpose.hip's scan
+//   numbers      the root flags scanned by csr_build.hip's scan
 //   phase 1, 2   lanes share a row again; phase 1 writes a second array so that phase 2 reads end-of-phase-1
 //                membership; phase 2 folds (|v|, storage position) to the maximum, ties to the smaller position
 //   P            row_ptrs = iota, cols = the aggregate map (phase 2 writes it in place), vals = 1
@@ -292,14 +292,12 @@ struct Scratch {
     DevBuf<int> state, rank, first, partial, sums;    // partial: one slot per workgroup of the largest grid
 
     bool allocate(int rows, bool aggregation = true) {
-        const std::vector<long long> levels = device_scan_levels(static_cast<long long>(rows) + 1);
-        long long level_total = 0;
-        for (size_t l = 1; l < levels.size(); ++l) level_total += levels[l];
+        const long long scan_sums = device_scan_sums(device_scan_levels(static_cast<long long>(rows) + 1));
         bool ok = ws.allocate(0, 0) && dev_alloc(&d, rows) == hipSuccess &&
                   dev_alloc(&partial, dev::kMaxResidentBlocks) == hipSuccess;
         if (ok && aggregation) {
             ok = dev_alloc(&state, rows) == hipSuccess && dev_alloc(&rank, static_cast<long long>(rows) + 1) == hipSuccess &&
-                 dev_alloc(&first, rows) == hipSuccess && dev_alloc(&sums, level_total + 1) == hipSuccess;
+                 dev_alloc(&first, rows) == hipSuccess && dev_alloc(&sums, scan_sums) == hipSuccess;
         }
         if (!ok) (void)hipGetLastError();
         return ok;
@@ -357,7 +355,7 @@ bool aggregate_level(const CSRMatrix& M, float theta, unsigned seed, int* d_aggr
     return ws.read_back(ok, s);
 }
 
-// not solver::device_arrays: nnz < 0 fails here (there it counts as no entries), num_rows is the caller's to check
+// not device_arrays_strict: nnz < 0 fails here (there it counts as no entries), num_rows is the caller's to check
 bool device_arrays_nnz_checked(const CSRMatrix* M) {
     return M->nnz >= 0 && M->d_row_ptrs && (M->nnz == 0 || (M->d_col_indices && M->d_values));
 }

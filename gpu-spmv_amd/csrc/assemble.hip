@@ -333,50 +333,6 @@ __global__ __launch_bounds__(kBlock) void assemble_numeric_kernel(const int* __r
     }
 }
 
-// row_of[p] = the row that holds entry p (row_ptrs validated: rp[0] == 0, non-decreasing, rp[rows] == nnz)
-__global__ __launch_bounds__(kBlock) void assemble_expand_rows_kernel(const int* __restrict__ rp, int rows,
-                                                                      long long nnz, int* __restrict__ row_of) {
-    __shared__ int s_first, s_last;
-    const long long base = blockIdx.x * static_cast<long long>(kBlock);
-    if (threadIdx.x == 0) s_first = dev::upper_bound(rp, 0, rows + 1, base) - 1;
-    if (threadIdx.x == 1) s_last = dev::upper_bound(rp, 0, rows + 1, std::min(base + kBlock, nnz) - 1) - 1;
-    __syncthreads();
-    const long long p = base + threadIdx.x;
-    if (p < nnz) row_of[p] = dev::upper_bound(rp, s_first + 1, s_last + 2, p) - 1;
-}
-
-// C takes the device arrays (csr_transpose_gpu's rule for AT)
-void adopt(CSRMatrix* C, int rows, int cols, int nnz, TransposeArrays arrays) {
-    csr_free_gpu(C);
-    if (C->owns_host_memory) {
-        delete[] C->values;
-        delete[] C->col_indices;
-        delete[] C->row_ptrs;
-    }
-    C->num_rows = rows;
-    C->num_cols = cols;
-    C->nnz = nnz;
-    C->values = nnz > 0 ? new float[nnz] : nullptr;
-    C->col_indices = nnz > 0 ? new int[nnz] : nullptr;
-    C->row_ptrs = new int[static_cast<size_t>(rows) + 1];
-    C->owns_host_memory = true;
-    C->d_row_ptrs = arrays.row_ptrs;
-    C->d_col_indices = arrays.col_indices;
-    C->d_values = arrays.values;
-    C->owns_device_memory = true;
-}
-
-int fail(CooResult* result, SpMVError e) {
-    (void)hipGetLastError();
-    result->error_code = code(e);
-    return result->error_code;
-}
-
-// launches of device_exclusive_scan: a tile kernel per level below the top, an add kernel for all but the last of them
-int scan_launches(const std::vector<long long>& levels) {
-    return std::max(1, 2 * static_cast<int>(levels.size()) - 3);
-}
-
 struct Request {
     int num_rows, num_cols, n;
     const int* d_rows;
@@ -397,14 +353,12 @@ int build_sorted(CSRMatrix* C, const Request& q, const KeyLayout& layout, unsign
     const int passes = static_cast<int>(shifts.size());
     const int tiles = (n + kTileEntries - 1) / kTileEntries;
     const std::vector<long long> levels = device_scan_levels(256LL * tiles);
-    long long level_total = 0;
-    for (size_t l = 1; l < levels.size(); ++l) level_total += levels[l];
 
     DevBuf<K> keys[2];
     DevBuf<int> pos[2], counts;
     bool got = dev_alloc(&keys[0], n) == hipSuccess && dev_alloc(&pos[0], n) == hipSuccess;
     if (passes >= 2) got = got && dev_alloc(&keys[1], n) == hipSuccess && dev_alloc(&pos[1], n) == hipSuccess;
-    if (passes >= 1) got = got && dev_alloc(&counts, 256LL * tiles + level_total + 1) == hipSuccess;
+    if (passes >= 1) got = got && dev_alloc(&counts, 256LL * tiles + device_scan_sums(levels)) == hipSuccess;
     if (!got) return fail(result, SpMVError::CUDA_MALLOC);
 
     SortInput<K> in{q.d_rows, q.d_cols, layout.col_bits, nullptr, nullptr};
@@ -434,7 +388,7 @@ int build_sorted(CSRMatrix* C, const Request& q, const KeyLayout& layout, unsign
                                                                              keys[cur].get(), pos[cur].get());
         }
         ok = hipGetLastError() == hipSuccess;
-        result->launches += 2 + scan_launches(levels);
+        result->launches += 2 + device_scan_launches(levels);
         in.keys = keys[cur].get();
         in.pos = pos[cur].get();
     }
@@ -450,10 +404,8 @@ int build_sorted(CSRMatrix* C, const Request& q, const KeyLayout& layout, unsign
     const bool sum = q.duplicates == COO_SUM;
     if (sum) {
         const std::vector<long long> index_levels = device_scan_levels(static_cast<long long>(n) + 1);
-        long long index_total = 0;
-        for (size_t l = 1; l < index_levels.size(); ++l) index_total += index_levels[l];
         if (dev_alloc(&index, static_cast<long long>(n) + 1) != hipSuccess ||
-            dev_alloc(&index_sums, index_total + 1) != hipSuccess) {
+            dev_alloc(&index_sums, device_scan_sums(index_levels)) != hipSuccess) {
             (void)hipStreamSynchronize(s);
             return fail(result, SpMVError::CUDA_MALLOC);
         }
@@ -462,20 +414,15 @@ int build_sorted(CSRMatrix* C, const Request& q, const KeyLayout& layout, unsign
              device_exclusive_scan(index.get(), index_levels, index_sums.get(), s) == hipSuccess &&
              hipMemcpyAsync(&nnz_out, index.get() + n, sizeof(int), hipMemcpyDeviceToHost, s) == hipSuccess;
         ok = hipStreamSynchronize(s) == hipSuccess && ok;
-        result->launches += 1 + scan_launches(index_levels);
+        result->launches += 1 + device_scan_launches(index_levels);
         if (!ok) return fail(result, SpMVError::KERNEL_LAUNCH);
     }
 
     // ---- C's arrays and the plan's ----
-    TransposeArrays out;
-    struct Release {
-        TransposeArrays* t;
-        ~Release() { t->release(); }
-    } release_out{&out};
+    DeviceCsrArrays out;                // (nnz_out >= 1: there is a triplet)
+    const ReleaseOnExit release_out{&out};
     DevBuf<int> segments;
-    if (hipMalloc(reinterpret_cast<void**>(&out.row_ptrs), (static_cast<size_t>(q.num_rows) + 1) * sizeof(int)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&out.col_indices), static_cast<size_t>(nnz_out) * sizeof(int)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&out.values), static_cast<size_t>(nnz_out) * sizeof(float)) != hipSuccess ||
+    if (out.alloc(static_cast<long long>(q.num_rows) + 1, nnz_out) != hipSuccess ||
         (sum && dev_alloc(&segments, static_cast<long long>(nnz_out) + 1) != hipSuccess)) {
         (void)hipStreamSynchronize(s);
         return fail(result, SpMVError::CUDA_MALLOC);
@@ -497,8 +444,7 @@ int build_sorted(CSRMatrix* C, const Request& q, const KeyLayout& layout, unsign
         delete made;
         return fail(result, SpMVError::KERNEL_LAUNCH);
     }
-    adopt(C, q.num_rows, q.num_cols, nnz_out, out);
-    out = TransposeArrays();          // C owns them now
+    csr_adopt_device(C, q.num_rows, q.num_cols, nnz_out, &out);          // C owns them now
     if (made) {
         made->num_rows = q.num_rows;
         made->num_cols = q.num_cols;
@@ -517,22 +463,21 @@ int build_sorted(CSRMatrix* C, const Request& q, const KeyLayout& layout, unsign
 
 // no triplets: an all-zero row_ptrs
 int build_empty(CSRMatrix* C, const Request& q, CooPlan** plan, CooResult* result, hipStream_t s) {
-    TransposeArrays out;
+    DeviceCsrArrays out;
+    const ReleaseOnExit release_out{&out};
     DevBuf<int> segments;
     const size_t ptr_bytes = (static_cast<size_t>(q.num_rows) + 1) * sizeof(int);
     const bool sum = q.duplicates == COO_SUM;
-    if (hipMalloc(reinterpret_cast<void**>(&out.row_ptrs), ptr_bytes) != hipSuccess ||
+    if (out.alloc(static_cast<long long>(q.num_rows) + 1, 0) != hipSuccess ||
         (plan && sum && dev_alloc(&segments, 1) != hipSuccess)) {
-        out.release();
         return fail(result, SpMVError::CUDA_MALLOC);
     }
     if (hipMemsetAsync(out.row_ptrs, 0, ptr_bytes, s) != hipSuccess ||
         (segments && hipMemsetAsync(segments.get(), 0, sizeof(int), s) != hipSuccess) ||
         hipStreamSynchronize(s) != hipSuccess) {
-        out.release();
         return fail(result, SpMVError::KERNEL_LAUNCH);
     }
-    adopt(C, q.num_rows, q.num_cols, 0, out);
+    csr_adopt_device(C, q.num_rows, q.num_cols, 0, &out);
     if (plan) {
         CooPlan* made = new CooPlan();
         made->num_rows = q.num_rows;
@@ -615,11 +560,7 @@ int csr_coo_refill(const CooPlan* plan, CSRMatrix* C, const float* d_vals) {
     hipStream_t s = current_stream();
     const int status = csr_coo_refill_async(plan, C, d_vals, s);
     if (status != 0) return status;
-    if (hipStreamSynchronize(s) != hipSuccess) {
-        (void)hipGetLastError();
-        return code(SpMVError::KERNEL_LAUNCH);
-    }
-    return 0;
+    return stream_finished(s);
 }
 
 void coo_plan_destroy(CooPlan* plan) {
@@ -638,10 +579,7 @@ int csr_row_indices_gpu(const CSRMatrix* A, int* d_rows) {
     const int checked = structure_checked(A, s);
     if (checked != 0) return checked;
     if (A->nnz == 0) return 0;
-    const long long nnz = A->nnz;
-    assemble::assemble_expand_rows_kernel<<<static_cast<unsigned>((nnz + dev::kBlock - 1) / dev::kBlock), dev::kBlock,
-                                            0, s>>>(A->d_row_ptrs, A->num_rows, nnz, d_rows);
-    const bool ok = hipGetLastError() == hipSuccess;
+    const bool ok = launch_expand_rows(A->d_row_ptrs, A->num_rows, A->nnz, d_rows, s) == hipSuccess;
     if (hipStreamSynchronize(s) != hipSuccess || !ok) {
         (void)hipGetLastError();
         return code(SpMVError::KERNEL_LAUNCH);

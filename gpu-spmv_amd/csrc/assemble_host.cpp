@@ -27,6 +27,7 @@ int refill_check(const CooPlan* plan, const CSRMatrix* C, const float* d_vals) {
     if (C->num_rows != plan->num_rows || C->num_cols != plan->num_cols || C->nnz != plan->nnz_out) {
         return code(SpMVError::INVALID_DIMENSION);
     }
+    // (not device_arrays_strict: no sign check, the sizes are the plan's; not lenient: d_row_ptrs also without rows)
     if (!C->d_row_ptrs || (C->nnz > 0 && (!C->d_col_indices || !C->d_values))) {
         return code(SpMVError::INVALID_FORMAT);
     }
@@ -36,11 +37,7 @@ int refill_check(const CooPlan* plan, const CSRMatrix* C, const float* d_vals) {
 int row_indices_check(const CSRMatrix* A, const int* d_rows, bool* nothing_to_do) {
     *nothing_to_do = false;
     if (!A || (!d_rows && A->nnz > 0)) return code(SpMVError::INVALID_ARGUMENT);
-    if (A->num_rows < 0 || A->num_cols < 0 || A->nnz < 0) return code(SpMVError::INVALID_FORMAT);
-    if (A->num_rows > 0 && (!A->d_row_ptrs || (A->nnz > 0 && (!A->d_col_indices || !A->d_values)))) {
-        return code(SpMVError::INVALID_FORMAT);
-    }
-    if (A->num_rows == 0 && A->nnz != 0) return code(SpMVError::INVALID_FORMAT);
+    if (!device_arrays_lenient(A)) return code(SpMVError::INVALID_FORMAT);
     if (A->num_rows == 0) *nothing_to_do = true;
     return 0;
 }
@@ -107,19 +104,7 @@ int csr_from_coo_cpu(CSRMatrix* C, int num_rows, int num_cols, int n, const int*
     }
     for (int r = 0; r < num_rows; ++r) new_ptrs[r + 1] += new_ptrs[r];
 
-    if (C->d_row_ptrs || C->d_col_indices || C->d_values) csr_free_gpu(C);     // a device copy would be stale
-    if (C->owns_host_memory) {
-        delete[] C->values;
-        delete[] C->col_indices;
-        delete[] C->row_ptrs;
-    }
-    C->num_rows = num_rows;
-    C->num_cols = num_cols;
-    C->nnz = nnz;
-    C->values = new_vals;
-    C->col_indices = new_cols;
-    C->row_ptrs = new_ptrs;
-    C->owns_host_memory = true;
+    csr_adopt_host(C, num_rows, num_cols, nnz, new_ptrs, new_cols, new_vals);
     return code(SpMVError::SUCCESS);
 }
 

@@ -203,20 +203,47 @@ void csr_invalidate_gpu_cache(const CSRMatrix* mat) {
 // csr_from_gpu fills (they hold no data before).  AT may be A itself.
 int csr_transpose_gpu(CSRMatrix* AT, const CSRMatrix* A) {
     if (!AT || !A) return detail::code(SpMVError::INVALID_ARGUMENT);
-    detail::TransposeArrays t;
+    detail::DeviceCsrArrays t;
+    const detail::ReleaseOnExit release_t{&t};
     const int status = detail::transpose_build(A, &t, detail::current_stream());
     if (status != 0) return status;
-    detail::csr_adopt_device(AT, A->num_cols, A->num_rows, A->nnz, t);  // (the arguments are read before AT, maybe A, changes)
+    detail::csr_adopt_device(AT, A->num_cols, A->num_rows, A->nnz, &t);  // (the arguments are read before AT, maybe A, changes)
     return detail::code(SpMVError::SUCCESS);
 }
 
-void detail::csr_adopt_device(CSRMatrix* M, int rows, int cols, int nnz, const TransposeArrays& arrays) {
+// ---- the hand-over of the builders (internal.h) ----
+void detail::csr_adopt_device(CSRMatrix* M, int rows, int cols, int nnz, DeviceCsrArrays* arrays) {
     csr_free_gpu(M);
     adopt_shape(M, rows, cols, nnz);
-    M->d_row_ptrs = arrays.row_ptrs;
-    M->d_col_indices = arrays.col_indices;
-    M->d_values = arrays.values;
+    M->d_row_ptrs = arrays->row_ptrs;
+    M->d_col_indices = arrays->col_indices;
+    M->d_values = arrays->values;
     M->owns_device_memory = true;
+    *arrays = DeviceCsrArrays();
+}
+
+void detail::csr_adopt_host(CSRMatrix* M, int rows, int cols, int nnz, int* row_ptrs, int* col_indices, float* values) {
+    if (M->d_row_ptrs || M->d_col_indices || M->d_values) csr_free_gpu(M);     // a device copy would be stale
+    release_host(M);
+    M->num_rows = rows;
+    M->num_cols = cols;
+    M->nnz = nnz;
+    M->values = values;
+    M->col_indices = col_indices;
+    M->row_ptrs = row_ptrs;
+    M->owns_host_memory = true;
+}
+
+void detail::csr_adopt_host(CSRMatrix* M, int rows, int cols, const std::vector<int>& row_ptrs,
+                            const std::vector<int>& col_indices, const std::vector<float>& values) {
+    const size_t nnz = col_indices.size();
+    std::unique_ptr<float[]> new_vals(nnz > 0 ? new float[nnz] : nullptr);
+    std::unique_ptr<int[]> new_cols(nnz > 0 ? new int[nnz] : nullptr);
+    std::unique_ptr<int[]> new_ptrs(new int[row_ptrs.size()]);
+    std::copy(values.begin(), values.begin() + nnz, new_vals.get());
+    std::copy(col_indices.begin(), col_indices.end(), new_cols.get());
+    std::copy(row_ptrs.begin(), row_ptrs.end(), new_ptrs.get());
+    csr_adopt_host(M, rows, cols, static_cast<int>(nnz), new_ptrs.release(), new_cols.release(), new_vals.release());
 }
 
 int csr_serialize(const CSRMatrix* mat, const char* filename) {

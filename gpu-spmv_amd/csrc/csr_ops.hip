@@ -305,17 +305,6 @@ __global__ __launch_bounds__(kBlock) void csr_diag_matrix_kernel(int n, const fl
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------
-struct Events {
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-    bool ok = true;
-    Events() {
-        for (hipEvent_t& x : e) ok = hipEventCreate(&x) == hipSuccess && ok;
-    }
-    ~Events() {
-        for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x);
-    }
-};
-
 MatView view_of(const CSRMatrix* M) { return MatView{M->d_row_ptrs, M->d_col_indices, M->d_values, M->nnz}; }
 
 // lanes per row from the mean of the two rows' lengths together
@@ -333,17 +322,6 @@ hipError_t launch_add(int lanes, int grid, const AddArgs& args, hipStream_t s) {
     });
 }
 
-// launches of device_exclusive_scan: a tile kernel per level below the top, an add kernel for all but the last of them
-int scan_launches(const std::vector<long long>& levels) {
-    return std::max(1, 2 * static_cast<int>(levels.size()) - 3);
-}
-
-int fail(CsrAddResult* result, SpMVError e) {
-    (void)hipGetLastError();
-    result->error_code = code(e);
-    return result->error_code;
-}
-
 int add_build(CSRMatrix* C, float alpha, const CSRMatrix* A, float beta, const CSRMatrix* B, CsrAddResult* result,
               hipStream_t s) {
     *result = CsrAddResult();
@@ -357,13 +335,12 @@ int add_build(CSRMatrix* C, float alpha, const CSRMatrix* A, float beta, const C
 
     // ---- counting pass and scan; the counts become C's row pointers only after the checks passed ----
     const std::vector<long long> levels = device_scan_levels(static_cast<long long>(m) + 1);
-    long long sums = 1;
-    for (size_t l = 1; l < levels.size(); ++l) sums += levels[l];
     const size_t waves = static_cast<size_t>(grid) * kWaves;
     DevBuf<int> counts, scan_sums, flag;
     DevBuf<long long> partial;
-    if (dev_alloc(&counts, static_cast<long long>(m) + 1) != hipSuccess || dev_alloc(&scan_sums, sums) != hipSuccess ||
-        dev_alloc(&flag, 1) != hipSuccess || dev_alloc(&partial, 3LL * static_cast<long long>(waves)) != hipSuccess) {
+    if (dev_alloc(&counts, static_cast<long long>(m) + 1) != hipSuccess ||
+        dev_alloc(&scan_sums, device_scan_sums(levels)) != hipSuccess || dev_alloc(&flag, 1) != hipSuccess ||
+        dev_alloc(&partial, 3LL * static_cast<long long>(waves)) != hipSuccess) {
         return fail(result, SpMVError::CUDA_MALLOC);
     }
     Events ev;
@@ -388,7 +365,7 @@ int add_build(CSRMatrix* C, float alpha, const CSRMatrix* A, float beta, const C
                              hipMemcpyDeviceToHost, s) == hipSuccess;
     ok = hipStreamSynchronize(s) == hipSuccess && ok;
     if (!ok) return fail(result, SpMVError::KERNEL_LAUNCH);
-    result->launches = 1 + scan_launches(levels);
+    result->launches = 1 + device_scan_launches(levels);
     if (bad) return fail(result, SpMVError::INVALID_FORMAT);
     long long nnz = 0, common = 0, longest = 0;
     for (size_t w = 0; w < waves; ++w) {
@@ -400,13 +377,9 @@ int add_build(CSRMatrix* C, float alpha, const CSRMatrix* A, float beta, const C
     (void)hipEventElapsedTime(&result->symbolic_ms, ev.e[0], ev.e[1]);
 
     // ---- numeric pass ----
-    TransposeArrays c;
+    DeviceCsrArrays c;
+    if (c.alloc_entries(nnz) != hipSuccess) return fail(result, SpMVError::CUDA_MALLOC);
     if (nnz > 0) {
-        if (hipMalloc(reinterpret_cast<void**>(&c.col_indices), nnz * sizeof(int)) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&c.values), nnz * sizeof(float)) != hipSuccess) {
-            c.release();
-            return fail(result, SpMVError::CUDA_MALLOC);
-        }
         args.c_rp = counts.get();
         args.c_ci = c.col_indices;
         args.c_va = c.values;
@@ -421,7 +394,7 @@ int add_build(CSRMatrix* C, float alpha, const CSRMatrix* A, float beta, const C
         ++result->launches;
     }
     c.row_ptrs = counts.release();
-    csr_adopt_device(C, m, n, static_cast<int>(nnz), c);
+    csr_adopt_device(C, m, n, static_cast<int>(nnz), &c);
     result->nnz = static_cast<int>(nnz);
     result->common = static_cast<int>(common);
     result->max_row_nnz = static_cast<int>(longest);
@@ -470,16 +443,6 @@ int add_refill(CSRMatrix* C, float alpha, const CSRMatrix* A, float beta, const 
     return 0;
 }
 
-// the launch's error and the stream's, as a status
-int finished(hipStream_t s) {
-    const bool ok = hipGetLastError() == hipSuccess;
-    if (hipStreamSynchronize(s) != hipSuccess || !ok) {
-        (void)hipGetLastError();
-        return code(SpMVError::KERNEL_LAUNCH);
-    }
-    return 0;
-}
-
 } // namespace
 
 } // namespace csr_ops
@@ -510,7 +473,7 @@ int csr_scale_gpu(CSRMatrix* A, const float* d_row_scale, const float* d_col_sca
     if (in_place) csr_invalidate_gpu_cache(A);      // a tiled plan, transpose or schedule built from the old values
     csr_ops::csr_scale_kernel<<<dev::vec_grid(A->nnz), dev::kBlock, 0, s>>>(
         A->d_row_ptrs, A->d_col_indices, A->d_values, A->num_rows, A->nnz, d_row_scale, d_col_scale, out);
-    return csr_ops::finished(s);
+    return stream_finished(s);
 }
 
 int csr_diagonal_gpu(const CSRMatrix* A, float* d_diag) {
@@ -523,30 +486,22 @@ int csr_diagonal_gpu(const CSRMatrix* A, float* d_diag) {
     if (checked != 0) return checked;
     csr_ops::csr_diagonal_kernel<<<dev::vec_grid(A->num_rows), dev::kBlock, 0, s>>>(
         A->num_rows, A->d_row_ptrs, A->d_col_indices, A->d_values, d_diag);
-    return csr_ops::finished(s);
+    return stream_finished(s);
 }
 
 int csr_diag_matrix_gpu(CSRMatrix* D, int n, const float* d_diag) {
     using namespace detail;
     const int status = csr_ops::diag_matrix_check(D, n);
     if (status != 0) return status;
-    TransposeArrays d;
-    if (hipMalloc(reinterpret_cast<void**>(&d.row_ptrs), (static_cast<size_t>(n) + 1) * sizeof(int)) != hipSuccess ||
-        (n > 0 && (hipMalloc(reinterpret_cast<void**>(&d.col_indices), static_cast<size_t>(n) * sizeof(int)) != hipSuccess ||
-                   hipMalloc(reinterpret_cast<void**>(&d.values), static_cast<size_t>(n) * sizeof(float)) != hipSuccess))) {
-        (void)hipGetLastError();
-        d.release();
-        return code(SpMVError::CUDA_MALLOC);
-    }
+    DeviceCsrArrays d;
+    const ReleaseOnExit release_d{&d};
+    if (d.alloc(static_cast<long long>(n) + 1, n) != hipSuccess) return code(SpMVError::CUDA_MALLOC);
     hipStream_t s = current_stream();
     csr_ops::csr_diag_matrix_kernel<<<dev::vec_grid(static_cast<long long>(n) + 1), dev::kBlock, 0, s>>>(
         n, d_diag, d.row_ptrs, d.col_indices, d.values);
-    const int done = csr_ops::finished(s);
-    if (done != 0) {
-        d.release();
-        return done;
-    }
-    csr_adopt_device(D, n, n, n, d);
+    const int done = stream_finished(s);
+    if (done != 0) return done;
+    csr_adopt_device(D, n, n, n, &d);
     return 0;
 }
 

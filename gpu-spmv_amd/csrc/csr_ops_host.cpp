@@ -7,7 +7,6 @@
 
 #include <climits>
 #include <cstdint>
-#include <cstring>
 #include <vector>
 
 namespace spmv {
@@ -34,44 +33,10 @@ bool host_matrix_ok(const CSRMatrix* M, bool ascending) {
     return true;
 }
 
-// the rule of csr_transpose_gpu
-bool device_arrays_missing(const CSRMatrix* M) {
-    if (M->num_rows < 0 || M->num_cols < 0 || M->nnz < 0) return true;
-    if (M->num_rows > 0 && (!M->d_row_ptrs || (M->nnz > 0 && (!M->d_col_indices || !M->d_values)))) return true;
-    return M->num_rows == 0 && M->nnz != 0;               // row_ptrs[0] == 0 != nnz
-}
-
 bool ranges_overlap(const float* a, long long na, const float* b, long long nb) {
     if (!a || !b || na <= 0 || nb <= 0) return false;
     const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
     return a0 < b0 + static_cast<uintptr_t>(nb) * sizeof(float) && b0 < a0 + static_cast<uintptr_t>(na) * sizeof(float);
-}
-
-// M takes new host arrays; a device copy would be stale
-void adopt_host(CSRMatrix* M, int rows, int cols, const std::vector<int>& row_ptrs, const std::vector<int>& col_indices,
-                const std::vector<float>& values) {
-    const int nnz = static_cast<int>(col_indices.size());
-    float* new_vals = nnz > 0 ? new float[nnz] : nullptr;
-    int* new_cols = nnz > 0 ? new int[nnz] : nullptr;
-    int* new_ptrs = new int[static_cast<size_t>(rows) + 1];
-    if (nnz > 0) {
-        std::memcpy(new_vals, values.data(), sizeof(float) * nnz);
-        std::memcpy(new_cols, col_indices.data(), sizeof(int) * nnz);
-    }
-    std::memcpy(new_ptrs, row_ptrs.data(), sizeof(int) * (static_cast<size_t>(rows) + 1));
-    if (M->d_row_ptrs || M->d_col_indices || M->d_values) csr_free_gpu(M);
-    if (M->owns_host_memory) {
-        delete[] M->values;
-        delete[] M->col_indices;
-        delete[] M->row_ptrs;
-    }
-    M->num_rows = rows;
-    M->num_cols = cols;
-    M->nnz = nnz;
-    M->values = new_vals;
-    M->col_indices = new_cols;
-    M->row_ptrs = new_ptrs;
-    M->owns_host_memory = true;
 }
 
 } // namespace
@@ -83,10 +48,10 @@ int add_check(const CSRMatrix* C, const CSRMatrix* A, const CSRMatrix* B, bool r
     if (!C || !A || !B) return code(SpMVError::INVALID_ARGUMENT);
     if (C == A || C == B) return code(SpMVError::INVALID_ARGUMENT);
     if (A->num_rows != B->num_rows || A->num_cols != B->num_cols) return code(SpMVError::INVALID_DIMENSION);
-    if (device_arrays_missing(A) || device_arrays_missing(B)) return code(SpMVError::INVALID_FORMAT);
+    if (!device_arrays_lenient(A) || !device_arrays_lenient(B)) return code(SpMVError::INVALID_FORMAT);
     if (refill) {
         if (C->num_rows != A->num_rows || C->num_cols != A->num_cols) return code(SpMVError::INVALID_DIMENSION);
-        if (device_arrays_missing(C)) return code(SpMVError::INVALID_FORMAT);
+        if (!device_arrays_lenient(C)) return code(SpMVError::INVALID_FORMAT);
     }
     return 0;
 }
@@ -94,7 +59,7 @@ int add_check(const CSRMatrix* C, const CSRMatrix* A, const CSRMatrix* B, bool r
 int scale_check(const CSRMatrix* A, const float* d_row_scale, const float* d_col_scale, float* d_values_out,
                 float** out, bool* in_place) {
     if (!A) return code(SpMVError::INVALID_ARGUMENT);
-    if (device_arrays_missing(A)) return code(SpMVError::INVALID_FORMAT);
+    if (!device_arrays_lenient(A)) return code(SpMVError::INVALID_FORMAT);
     *out = d_values_out ? d_values_out : A->d_values;
     *in_place = *out == A->d_values;
     if (!*in_place && ranges_overlap(*out, A->nnz, A->d_values, A->nnz)) return code(SpMVError::INVALID_ARGUMENT);
@@ -106,7 +71,7 @@ int scale_check(const CSRMatrix* A, const float* d_row_scale, const float* d_col
 
 int diagonal_check(const CSRMatrix* A, const float* d_diag) {
     if (!A || (!d_diag && A->num_rows > 0)) return code(SpMVError::INVALID_ARGUMENT);
-    if (device_arrays_missing(A)) return code(SpMVError::INVALID_FORMAT);
+    if (!device_arrays_lenient(A)) return code(SpMVError::INVALID_FORMAT);
     return 0;
 }
 
@@ -153,7 +118,7 @@ int csr_add_cpu(CSRMatrix* C, float alpha, const CSRMatrix* A, float beta, const
         }
         row_ptrs[i + 1] = static_cast<int>(cols.size());
     }
-    adopt_host(C, m, n, row_ptrs, cols, vals);
+    detail::csr_adopt_host(C, m, n, row_ptrs, cols, vals);
     return code(SpMVError::SUCCESS);
 }
 
@@ -202,7 +167,7 @@ int csr_diag_matrix_cpu(CSRMatrix* D, int n, const float* diag) {
         vals[i] = diag ? diag[i] : 1.0f;
     }
     row_ptrs[n] = n;
-    adopt_host(D, n, n, row_ptrs, cols, vals);
+    detail::csr_adopt_host(D, n, n, row_ptrs, cols, vals);
     return code(SpMVError::SUCCESS);
 }
 

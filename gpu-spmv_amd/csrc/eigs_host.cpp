@@ -105,9 +105,7 @@ int eigs_check_arguments(const CSRMatrix* A, const float* d_values, const float*
         *nothing_to_do = true;
         return 0;
     }
-    if (A->num_rows < 0 || !A->d_row_ptrs || (A->nnz > 0 && (!A->d_col_indices || !A->d_values))) {
-        return code(SpMVError::INVALID_FORMAT);
-    }
+    if (!device_arrays_strict(A)) return code(SpMVError::INVALID_FORMAT);
     const int n = A->num_rows;
     const int k = cfg.num_values;
     if (k < 1 || k > kMaxValues || k > n) return code(SpMVError::INVALID_ARGUMENT);

@@ -121,6 +121,7 @@ int ell_from_csr(ELLMatrix* ell, const CSRMatrix* csr) {
 // The ELL matrix ends up device-only (host slabs released); ell_from_gpu can fetch them.
 int ell_from_csr_gpu(ELLMatrix* ell, const CSRMatrix* csr) {
     if (!ell || !csr) return detail::code(SpMVError::INVALID_ARGUMENT);
+    // (not device_arrays_lenient: no sign check and no "entries without rows" check here)
     if (csr->num_rows > 0 && (!csr->d_row_ptrs || (csr->nnz > 0 && (!csr->d_col_indices || !csr->d_values)))) {
         return detail::code(SpMVError::INVALID_FORMAT);
     }

@@ -9,7 +9,6 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <cstring>
 #include <vector>
 
 namespace spmv {
@@ -80,6 +79,7 @@ void host_row(const CSRMatrix* A, const int* P, int m, double* T, double* U, flo
     for (int p = 0; p < m; ++p) g[p] = static_cast<float>(U[p]);
 }
 
+// neither rule of internal.h: nnz < 0 fails, num_rows is the caller's to check, and a pattern needs no values
 bool structure_on_device(const CSRMatrix* M) {
     return M->nnz >= 0 && M->d_row_ptrs && (M->nnz == 0 || M->d_col_indices);
 }
@@ -149,28 +149,7 @@ int fsai_cpu_csr(CSRMatrix* G, const CSRMatrix* A, const CSRMatrix* S, int* bad_
             if (bad < 0 && !(d > 0.0f && std::isfinite(d))) bad = i;
         }
     }
-    const int nnz = static_cast<int>(cols.size());
-    float* new_vals = nnz > 0 ? new float[nnz] : nullptr;
-    int* new_cols = nnz > 0 ? new int[nnz] : nullptr;
-    int* new_ptrs = new int[row_ptrs.size()];
-    if (nnz > 0) {
-        std::memcpy(new_vals, vals.data(), sizeof(float) * nnz);
-        std::memcpy(new_cols, cols.data(), sizeof(int) * nnz);
-    }
-    std::memcpy(new_ptrs, row_ptrs.data(), sizeof(int) * row_ptrs.size());
-    if (G->d_row_ptrs || G->d_col_indices || G->d_values) csr_free_gpu(G);     // a device copy would be stale
-    if (G->owns_host_memory) {
-        delete[] G->values;
-        delete[] G->col_indices;
-        delete[] G->row_ptrs;
-    }
-    G->num_rows = n;
-    G->num_cols = n;
-    G->nnz = nnz;
-    G->values = new_vals;
-    G->col_indices = new_cols;
-    G->row_ptrs = new_ptrs;
-    G->owns_host_memory = true;
+    detail::csr_adopt_host(G, n, n, row_ptrs, cols, vals);
     if (bad_row) *bad_row = bad;
     return code(SpMVError::SUCCESS);
 }
@@ -189,28 +168,26 @@ FSAIResult fsai_csr(CSRMatrix* G, const CSRMatrix* A, const CSRMatrix* S) {
     }
     hipStream_t stream = current_stream();
     if (nothing) {
-        DevBuf<int> row_ptrs;
-        if (dev_alloc(&row_ptrs, 1) != hipSuccess) return failed(result, SpMVError::CUDA_MALLOC);
-        if (hipMemsetAsync(row_ptrs.get(), 0, sizeof(int), stream) != hipSuccess ||
+        DeviceCsrArrays empty;
+        const ReleaseOnExit release_empty{&empty};
+        if (empty.alloc(1, 0) != hipSuccess) return failed(result, SpMVError::CUDA_MALLOC);
+        if (hipMemsetAsync(empty.row_ptrs, 0, sizeof(int), stream) != hipSuccess ||
             hipStreamSynchronize(stream) != hipSuccess) {
             return failed(result, SpMVError::KERNEL_LAUNCH);
         }
-        TransposeArrays empty;
-        empty.row_ptrs = row_ptrs.release();
-        csr_adopt_device(G, 0, 0, 0, empty);
+        csr_adopt_device(G, 0, 0, 0, &empty);
         return result;
     }
 
     const TraceRange range("spmv:fsai_csr");
     // ---- structure: counts -> row pointers, and the one read-back ----
     const std::vector<long long> levels = device_scan_levels(static_cast<long long>(n) + 1);
-    long long level_total = 0;
-    for (size_t l = 1; l < levels.size(); ++l) level_total += levels[l];
-    DevBuf<int> row_ptrs, sums, cols;
-    DevBuf<float> values;
+    DeviceCsrArrays g;
+    const ReleaseOnExit release_g{&g};
+    DevBuf<int> sums;
     DevBuf<unsigned> info, word;         // kInfoWords of the structure pass; the bad_row word, kept with G
-    if (dev_alloc(&row_ptrs, static_cast<long long>(n) + 1) != hipSuccess ||
-        dev_alloc(&sums, level_total + 1) != hipSuccess || dev_alloc(&info, kInfoWords) != hipSuccess ||
+    if (g.alloc(static_cast<long long>(n) + 1, 0) != hipSuccess ||
+        dev_alloc(&sums, device_scan_sums(levels)) != hipSuccess || dev_alloc(&info, kInfoWords) != hipSuccess ||
         dev_alloc(&word, 1) != hipSuccess) {
         return failed(result, SpMVError::CUDA_MALLOC);
     }
@@ -221,10 +198,10 @@ FSAIResult fsai_csr(CSRMatrix* G, const CSRMatrix* A, const CSRMatrix* S) {
               hipMemsetAsync(info.get(), 0, kInfoWords * sizeof(unsigned), stream) == hipSuccess &&
               hipMemsetAsync(info.get() + kLongRow, 0xff, sizeof(unsigned), stream) == hipSuccess &&
               hipMemsetAsync(word.get(), 0xff, sizeof(unsigned), stream) == hipSuccess;
-    ok = ok && launch_structure_count(A, pattern, row_ptrs.get(), info.get(), stream) == hipSuccess &&
-         device_exclusive_scan(row_ptrs.get(), levels, sums.get(), stream) == hipSuccess &&
+    ok = ok && launch_structure_count(A, pattern, g.row_ptrs, info.get(), stream) == hipSuccess &&
+         device_exclusive_scan(g.row_ptrs, levels, sums.get(), stream) == hipSuccess &&
          hipMemcpyAsync(seen, info.get(), sizeof(seen), hipMemcpyDeviceToHost, stream) == hipSuccess &&
-         hipMemcpyAsync(&g_nnz, row_ptrs.get() + n, sizeof(int), hipMemcpyDeviceToHost, stream) == hipSuccess;
+         hipMemcpyAsync(&g_nnz, g.row_ptrs + n, sizeof(int), hipMemcpyDeviceToHost, stream) == hipSuccess;
     ok = hipStreamSynchronize(stream) == hipSuccess && ok;       // always drained: `seen` lives in this frame
     if (!ok) return failed(result, SpMVError::KERNEL_LAUNCH);
     if (seen[kBadFormat]) return failed(result, SpMVError::INVALID_FORMAT);
@@ -240,12 +217,10 @@ FSAIResult fsai_csr(CSRMatrix* G, const CSRMatrix* A, const CSRMatrix* S) {
     result.nnz = g_nnz;
 
     // ---- the columns and the values ----
-    if (dev_alloc(&cols, g_nnz) != hipSuccess || dev_alloc(&values, g_nnz) != hipSuccess) {
-        return failed(result, SpMVError::CUDA_MALLOC);
-    }
+    if (g.alloc_entries(g_nnz) != hipSuccess) return failed(result, SpMVError::CUDA_MALLOC);    // (g_nnz >= n >= 1)
     unsigned bad = UINT_MAX;
-    ok = launch_structure_columns(pattern, row_ptrs.get(), cols.get(), stream) == hipSuccess &&
-         launch_numeric(A, n, g_nnz, row_ptrs.get(), cols.get(), values.get(), result.row_class,
+    ok = launch_structure_columns(pattern, g.row_ptrs, g.col_indices, stream) == hipSuccess &&
+         launch_numeric(A, n, g_nnz, g.row_ptrs, g.col_indices, g.values, result.row_class,
                         result.lanes_per_row, word.get(), stream) == hipSuccess &&
          hipEventRecord(ev.stop, stream) == hipSuccess &&
          hipMemcpyAsync(&bad, word.get(), sizeof(unsigned), hipMemcpyDeviceToHost, stream) == hipSuccess;
@@ -254,11 +229,7 @@ FSAIResult fsai_csr(CSRMatrix* G, const CSRMatrix* A, const CSRMatrix* S) {
     if (!ok) return failed(result, SpMVError::KERNEL_LAUNCH);
     result.bad_row = bad == UINT_MAX ? -1 : static_cast<int>(bad);
 
-    TransposeArrays built;
-    built.row_ptrs = row_ptrs.release();
-    built.col_indices = cols.release();
-    built.values = values.release();
-    csr_adopt_device(G, n, n, g_nnz, built);
+    csr_adopt_device(G, n, n, g_nnz, &g);
     CsrAux* aux = aux_lookup(G->d_row_ptrs, true);
     aux->fsai_max_row = result.max_row;
     if (aux->d_fsai_word) (void)hipFree(aux->d_fsai_word);

@@ -55,12 +55,23 @@ struct PrWorkspace {
     void release();
 };
 
-// device arrays of a transpose built by transpose_build (transpose.hip); hipMalloc-owned
-struct TransposeArrays {
-    int*   row_ptrs = nullptr;      // [num_cols + 1] of the source
-    int*   col_indices = nullptr;   // [nnz]
-    float* values = nullptr;        // [nnz]
+// Device arrays of a CSR matrix a builder made (transpose_build, spgemm_build, csr_permute_gpu, ...);
+// hipMalloc-owned until csr_adopt_device hands them to a CSRMatrix.
+struct DeviceCsrArrays {
+    int*   row_ptrs = nullptr;      // [rows + 1]
+    int*   col_indices = nullptr;   // [nnz], null when nnz == 0
+    float* values = nullptr;        // [nnz], null when nnz == 0
+    // row_ptrs [row_ptr_count] always, the other two [nnz] only for nnz > 0.  On a failure everything held is released
+    // and the HIP error cleared; the caller maps it to its own SpMVError.
+    hipError_t alloc(long long row_ptr_count, long long nnz);
+    // the other two alone, for a builder whose row pointers come out of a scan before nnz is known
+    hipError_t alloc_entries(long long nnz);
     void release();
+};
+// releases the arrays at the end of the scope, unless they were handed over (csr_adopt_device empties them)
+struct ReleaseOnExit {
+    DeviceCsrArrays* arrays;
+    ~ReleaseOnExit() { arrays->release(); }
 };
 
 // sptrsv_csr's level schedule of one triangle (sptrsv_host.cpp): structure only, never the values.  Shared between
@@ -255,19 +266,88 @@ void release_multi_merge(CsrAux* aux);
 hipError_t launch_fill_zero(float* d_y, size_t n, hipStream_t s);
 // device transpose (transpose.hip): validates A (INVALID_FORMAT before anything is allocated), then builds A^T on
 // `s` and returns after the build completed, its scratch freed.  The caller owns *out on SUCCESS.
-int transpose_build(const CSRMatrix* A, TransposeArrays* out, hipStream_t s);
-// How a builder hands its result over (csr_matrix.cpp; csr_transpose_gpu's rule for AT): M's old device arrays and
-// cached data are dropped, it owns `arrays` from now on, and its host arrays are allocated at the new size without data.
-void csr_adopt_device(CSRMatrix* M, int rows, int cols, int nnz, const TransposeArrays& arrays);
-// the scan of transpose.hip for other builders (spgemm.hip): device_scan_levels(n) gives the level sizes n,
-// ceil(n / 4096), ... 1; device_exclusive_scan scans data[0, n) in place on `s`, with `sums` holding the sum of
-// levels[1 ..] ints plus one
+int transpose_build(const CSRMatrix* A, DeviceCsrArrays* out, hipStream_t s);
+
+// ---- the build layer: what the routines that build a CSR matrix share (csr_build.hip, csr_matrix.cpp; §4.27) ----
+// How a device builder hands its result over (csr_matrix.cpp; csr_transpose_gpu's rule for AT): M's old device arrays and
+// cached data are dropped, it owns *arrays from now on (*arrays is left empty), and its host arrays are allocated at the
+// new size without data.  The shape is passed by value: M may be the builder's input (csr_transpose_gpu(A, A)).
+void csr_adopt_device(CSRMatrix* M, int rows, int cols, int nnz, DeviceCsrArrays* arrays);
+// How a host twin hands its result over: M's device arrays, if it has any, are dropped with their cached data (a device
+// copy would be stale; csr_free_gpu is not called for a handle without device pointers, whose owns_device_memory stays
+// as it is), its old host arrays are freed when it owns them, and it owns the three new[]-allocated arrays from now on.
+void csr_adopt_host(CSRMatrix* M, int rows, int cols, int nnz, int* row_ptrs, int* col_indices, float* values);
+// the same from vectors (nnz = col_indices.size()): copied first, so a failed allocation leaves M untouched
+void csr_adopt_host(CSRMatrix* M, int rows, int cols, const std::vector<int>& row_ptrs,
+                    const std::vector<int>& col_indices, const std::vector<float>& values);
+// The hierarchical exclusive scan (tiles of 4096, 256 threads): device_scan_levels(n) gives the level sizes n,
+// ceil(n / 4096), ... 1; device_exclusive_scan scans data[0, n) in place on `s`, with `sums` holding
+// device_scan_sums(levels) ints of scratch; device_scan_launches(levels) is the number of kernels it launches
 std::vector<long long> device_scan_levels(long long n);
+long long device_scan_sums(const std::vector<long long>& levels);
+int device_scan_launches(const std::vector<long long>& levels);
 hipError_t device_exclusive_scan(int* data, const std::vector<long long>& levels, int* sums, hipStream_t s);
-// the structure check of reorder.hip (csr_transpose_gpu's rule), run on `s` and waited for: 0, or the code of
-// CUDA_MALLOC (no flag word), KERNEL_LAUNCH (a call failed; the HIP error is cleared) or INVALID_FORMAT (A's row
-// pointers or columns are malformed)
+// The structure check (csr_transpose_gpu's rule: row_ptrs[0] == 0, non-decreasing, row_ptrs[rows] == nnz, every column
+// in [0, num_cols)).  enqueue_validate: *d_flag (zeroed by the caller) becomes 1 when A is malformed; not waited for.
+// structure_checked: run on `s` and waited for: 0, or the code of CUDA_MALLOC (no flag word), KERNEL_LAUNCH (a call
+// failed; the HIP error is cleared) or INVALID_FORMAT
+hipError_t enqueue_validate(const CSRMatrix* A, int* d_flag, hipStream_t s);
 int structure_checked(const CSRMatrix* A, hipStream_t s);
+// row_of[p] = the row that holds entry p of validated row pointers, for nnz > 0 (256 entries per workgroup)
+hipError_t launch_expand_rows(const int* rp, int rows, long long nnz, int* row_of, hipStream_t s);
+// out[i] = i for i in [0, n), `grid` workgroups of 256 threads striding
+hipError_t launch_iota(long long n, int* out, int grid, hipStream_t s);
+
+// The two rules for "the matrix is on the device".  Which error a half-uploaded matrix gets is tested behaviour: a
+// site whose rule differs from both in any input keeps its own spelling, with a comment that says what differs.
+// STRICT — the solvers, eigs_sym and pagerank_personalized (their callers have returned for num_rows == 0 already):
+// d_row_ptrs always, the other two for nnz > 0; a negative nnz counts as no entries, a negative num_rows fails.
+inline bool device_arrays_strict(const CSRMatrix* M) {
+    return M->num_rows >= 0 && M->d_row_ptrs && (M->nnz <= 0 || (M->d_col_indices && M->d_values));
+}
+// LENIENT — csr_transpose_gpu's rule, for the builders that take a matrix without rows (the transpose, spgemm_csr,
+// csr_add, csr_scale_gpu, csr_diagonal_gpu, csr_row_indices_gpu): no negative size, the arrays only where there are
+// rows (and, for the other two, entries), and no entries without rows (row_ptrs[0] == 0 != nnz).
+inline bool device_arrays_lenient(const CSRMatrix* M) {
+    if (M->num_rows < 0 || M->num_cols < 0 || M->nnz < 0) return false;
+    if (M->num_rows > 0 && (!M->d_row_ptrs || (M->nnz > 0 && (!M->d_col_indices || !M->d_values)))) return false;
+    return M->num_rows > 0 || M->nnz == 0;
+}
+
+// ---- small host helpers of the builders ----
+// clears the HIP error, stores the code in the result struct and returns it
+template <typename Result>
+int fail(Result* result, SpMVError e) {
+    (void)hipGetLastError();
+    result->error_code = code(e);
+    return result->error_code;
+}
+inline int fail(SpMVError e) {
+    (void)hipGetLastError();
+    return code(e);
+}
+// four events of one call (symbolic and numeric begin / end), destroyed with it
+struct Events {
+    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool ok = true;
+    Events() {
+        for (hipEvent_t& x : e) ok = hipEventCreate(&x) == hipSuccess && ok;
+    }
+    ~Events() {
+        for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x);
+    }
+    Events(const Events&) = delete;
+    Events& operator=(const Events&) = delete;
+};
+// the last launch's error and the stream's, as a status (waits for `s`)
+inline int stream_finished(hipStream_t s) {
+    const bool ok = hipGetLastError() == hipSuccess;
+    if (hipStreamSynchronize(s) != hipSuccess || !ok) {
+        (void)hipGetLastError();
+        return code(SpMVError::KERNEL_LAUNCH);
+    }
+    return 0;
+}
 // spgemm_csr's accumulator classes (spgemm.hip, spgemm_host.cpp): classes 1 .. kSpgemmClasses - 1 are LDS hash tables
 // of kSpgemmSlots slots (a power of two; a row may fill half of them), the last class is the dense accumulator
 constexpr int kSpgemmClasses = 5;

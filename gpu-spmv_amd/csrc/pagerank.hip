@@ -639,6 +639,7 @@ PageRankResult pagerank(const CSRMatrix* adj, const PageRankConfig* config) {
 
     // The matrix must be resident on the device (csr_to_gpu), like the reference's
     // spmv_csr call requires; otherwise the loop ends at once with the start vector.
+    // (check_csr's rule: not device_arrays_strict, no sign check)
     if (!adj->d_row_ptrs || (adj->nnz > 0 && (!adj->d_col_indices || !adj->d_values))) {
         return result;
     }

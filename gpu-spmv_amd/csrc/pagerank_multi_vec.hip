@@ -447,9 +447,7 @@ int check_arguments(const CSRMatrix* adj, const void* teleport, int ldv, const f
         *nothing_to_do = true;
         return code(SpMVError::SUCCESS);
     }
-    if (adj->num_rows < 0 || !adj->d_row_ptrs || (adj->nnz > 0 && (!adj->d_col_indices || !adj->d_values))) {
-        return fail(SpMVError::INVALID_FORMAT);
-    }
+    if (!device_arrays_strict(adj)) return fail(SpMVError::INVALID_FORMAT);
     if (config) {
         const float d = config->damping_factor, tol = config->tolerance;
         if (!(d > 0.0f && d < 1.0f) || !(tol >= 0.0f) || std::isinf(tol) || config->max_iterations < 0) {

@@ -44,28 +44,6 @@ struct ColorState {
     int num_colors;
 };
 
-// ---- structure: csr_transpose_gpu's rule; every writer stores the same 1 ----
-__global__ __launch_bounds__(kBlock) void reorder_validate_kernel(const int* __restrict__ rp, const int* __restrict__ ci,
-                                                                  int rows, int cols, long long nnz,
-                                                                  int* __restrict__ bad_flag) {
-    const long long work = max(nnz, static_cast<long long>(rows) + 1);
-    bool bad = false;
-    for (long long i = blockIdx.x * static_cast<long long>(kBlock) + threadIdx.x; i < work;
-         i += static_cast<long long>(gridDim.x) * kBlock) {
-        if (i <= rows) {
-            const int v = rp[i];
-            if (i == 0 && v != 0) bad = true;
-            if (i == rows && v != nnz) bad = true;
-            if (i < rows && v > rp[i + 1]) bad = true;
-        }
-        if (i < nnz) {
-            const int c = ci[i];
-            if (c < 0 || c >= cols) bad = true;
-        }
-    }
-    if (__any(bad) && (threadIdx.x & 63) == 0) *bad_flag = 1;
-}
-
 // ---- colouring ----
 __global__ __launch_bounds__(kBlock) void color_init_kernel(int n, int* __restrict__ colors,
                                                             ColorState* __restrict__ state) {
@@ -169,13 +147,6 @@ __global__ __launch_bounds__(kBlock) void color_count_kernel(const int* __restri
 }
 
 // ---- ordering ----
-__global__ __launch_bounds__(kBlock) void iota_kernel(long long n, int* __restrict__ out) {
-    for (long long i = blockIdx.x * static_cast<long long>(kBlock) + threadIdx.x; i < n;
-         i += static_cast<long long>(gridDim.x) * kBlock) {
-        out[i] = static_cast<int>(i);
-    }
-}
-
 __global__ __launch_bounds__(kBlock) void ordering_kernel(int n, const int* __restrict__ sorted, int* __restrict__ perm,
                                                           int* __restrict__ inverse) {
     for (long long i = blockIdx.x * static_cast<long long>(kBlock) + threadIdx.x; i < n;
@@ -187,8 +158,8 @@ __global__ __launch_bounds__(kBlock) void ordering_kernel(int n, const int* __re
 }
 
 // ---- permutation ----
-// info[0]: A's structure is bad (reorder_validate_kernel); info[1]: an array is not a permutation; info[2 + b]: the
-// longest row workgroup b of permute_lengths_kernel saw
+// info[0]: A's structure is bad (enqueue_validate of csr_build.hip); info[1]: an array is not a permutation;
+// info[2 + b]: the longest row workgroup b of permute_lengths_kernel saw
 __global__ __launch_bounds__(kBlock) void permute_mark_kernel(const int* __restrict__ row_perm, int rows,
                                                               const int* __restrict__ col_inverse, int cols,
                                                               int* __restrict__ seen_rows, int* __restrict__ seen_cols,
@@ -347,41 +318,6 @@ __global__ __launch_bounds__(kBlock) void gather_kernel(float* __restrict__ out,
     }
 }
 
-// A's structure checked on the device: *d_flag (zeroed by the caller) becomes 1 when it is bad; not waited for
-hipError_t enqueue_validate(const CSRMatrix* A, int* d_flag, hipStream_t s) {
-    const long long work = std::max<long long>(A->nnz, static_cast<long long>(A->num_rows) + 1);
-    reorder_validate_kernel<<<capped_grid(work, kBlock), kBlock, 0, s>>>(A->d_row_ptrs, A->d_col_indices, A->num_rows,
-                                                                         A->num_cols, A->nnz, d_flag);
-    return hipGetLastError();
-}
-
-// B takes the device arrays (csr_transpose_gpu's rule for AT)
-void adopt(CSRMatrix* B, int rows, int cols, int nnz, TransposeArrays arrays) {
-    csr_free_gpu(B);
-    if (B->owns_host_memory) {
-        delete[] B->values;
-        delete[] B->col_indices;
-        delete[] B->row_ptrs;
-    }
-    B->num_rows = rows;
-    B->num_cols = cols;
-    B->nnz = nnz;
-    B->values = nnz > 0 ? new float[nnz] : nullptr;
-    B->col_indices = nnz > 0 ? new int[nnz] : nullptr;
-    B->row_ptrs = new int[static_cast<size_t>(rows) + 1];
-    B->owns_host_memory = true;
-    B->d_row_ptrs = arrays.row_ptrs;
-    B->d_col_indices = arrays.col_indices;
-    B->d_values = arrays.values;
-    B->owns_device_memory = true;
-}
-
-int fail(ColorResult* result, SpMVError e) {
-    (void)hipGetLastError();
-    result->error_code = code(e);
-    return result->error_code;
-}
-
 // the colouring on `s`; the checks of color_check have passed and A has rows
 int color(const CSRMatrix* A, int* d_colors, const ColorConfig& cfg, ColorResult* result, hipStream_t s) {
     const int n = A->num_rows;
@@ -395,11 +331,8 @@ int color(const CSRMatrix* A, int* d_colors, const ColorConfig& cfg, ColorResult
     if (checked == 0 || checked == code(SpMVError::INVALID_FORMAT)) result->launches = 1;    // the check ran
     if (checked != 0) return fail(result, static_cast<SpMVError>(checked));
 
-    TransposeArrays at;
-    struct Release {
-        TransposeArrays* t;
-        ~Release() { t->release(); }
-    } release_at{&at};
+    DeviceCsrArrays at;
+    const ReleaseOnExit release_at{&at};
     if (!cfg.symmetric_pattern) {
         const int status = transpose_build(A, &at, s);
         if (status != 0) {
@@ -444,12 +377,12 @@ int color(const CSRMatrix* A, int* d_colors, const ColorConfig& cfg, ColorResult
 
 int ordering(int n, const int* d_colors, int num_colors, int* d_perm, int* d_inverse, int* color_ptr, hipStream_t s) {
     DevBuf<int> iota;
-    if (dev_alloc(&iota, static_cast<long long>(n) + 1) != hipSuccess) {
+    const long long count = static_cast<long long>(n) + 1;
+    if (dev_alloc(&iota, count) != hipSuccess) {
         (void)hipGetLastError();
         return code(SpMVError::CUDA_MALLOC);
     }
-    iota_kernel<<<vec_grid(static_cast<long long>(n) + 1), kBlock, 0, s>>>(static_cast<long long>(n) + 1, iota.get());
-    if (hipGetLastError() != hipSuccess) return code(SpMVError::KERNEL_LAUNCH);
+    if (launch_iota(count, iota.get(), vec_grid(count), s) != hipSuccess) return code(SpMVError::KERNEL_LAUNCH);
     // the n x num_colors matrix with the entry (i, colour[i]) in row i: row c of its transpose lists the vertices of
     // colour c in ascending order.  The values are never looked at: the colours stand in for them.
     CSRMatrix byrow{};
@@ -459,7 +392,7 @@ int ordering(int n, const int* d_colors, int num_colors, int* d_perm, int* d_inv
     byrow.d_row_ptrs = iota.get();
     byrow.d_col_indices = const_cast<int*>(d_colors);
     byrow.d_values = reinterpret_cast<float*>(const_cast<int*>(d_colors));
-    TransposeArrays bycolor;
+    DeviceCsrArrays bycolor;
     const int status = transpose_build(&byrow, &bycolor, s);
     if (status == code(SpMVError::INVALID_FORMAT)) return code(SpMVError::INVALID_ARGUMENT);    // a colour out of range
     if (status != 0) return status;
@@ -481,23 +414,16 @@ int ordering(int n, const int* d_colors, int num_colors, int* d_perm, int* d_inv
 int permute(CSRMatrix* B, const CSRMatrix* A, const int* d_row_perm, const int* d_col_inverse, hipStream_t s) {
     const int rows = A->num_rows, cols = A->num_cols, nnz = A->nnz;
     const TraceRange range("spmv:csr_permute_gpu");
-    TransposeArrays out;
-    struct Release {
-        TransposeArrays* t;
-        ~Release() { t->release(); }
-    } release_out{&out};
+    DeviceCsrArrays out;
+    const ReleaseOnExit release_out{&out};
     const size_t ptr_bytes = (static_cast<size_t>(rows) + 1) * sizeof(int);
-    if (hipMalloc(reinterpret_cast<void**>(&out.row_ptrs), ptr_bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return code(SpMVError::CUDA_MALLOC);
-    }
+    if (out.alloc(static_cast<long long>(rows) + 1, 0) != hipSuccess) return code(SpMVError::CUDA_MALLOC);
     if (rows == 0) {                                              // (nnz == 0: permute_check)
         if (hipMemsetAsync(out.row_ptrs, 0, ptr_bytes, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
             (void)hipGetLastError();
             return code(SpMVError::KERNEL_LAUNCH);
         }
-        adopt(B, rows, cols, 0, out);
-        out = TransposeArrays();
+        csr_adopt_device(B, rows, cols, 0, &out);
         return 0;
     }
 
@@ -539,12 +465,8 @@ int permute(CSRMatrix* B, const CSRMatrix* A, const int* d_row_perm, const int* 
 
     // ---- row pointers: the scan of the lengths ----
     const std::vector<long long> levels = device_scan_levels(static_cast<long long>(rows) + 1);
-    long long level_total = 0;
-    for (size_t l = 1; l < levels.size(); ++l) level_total += levels[l];
     DevBuf<int> sums;
-    if (dev_alloc(&sums, level_total + 1) != hipSuccess ||
-        (nnz > 0 && (hipMalloc(reinterpret_cast<void**>(&out.col_indices), nnz * sizeof(int)) != hipSuccess ||
-                     hipMalloc(reinterpret_cast<void**>(&out.values), nnz * sizeof(float)) != hipSuccess))) {
+    if (dev_alloc(&sums, device_scan_sums(levels)) != hipSuccess || out.alloc_entries(nnz) != hipSuccess) {
         (void)hipGetLastError();
         return code(SpMVError::CUDA_MALLOC);
     }
@@ -582,7 +504,7 @@ int permute(CSRMatrix* B, const CSRMatrix* A, const int* d_row_perm, const int* 
         relabelled.d_row_ptrs = out.row_ptrs;
         relabelled.d_col_indices = out.col_indices;
         relabelled.d_values = out.values;
-        TransposeArrays first;
+        DeviceCsrArrays first;
         int status = transpose_build(&relabelled, &first, s);
         if (status != 0) return status;
         CSRMatrix turned{};
@@ -592,7 +514,7 @@ int permute(CSRMatrix* B, const CSRMatrix* A, const int* d_row_perm, const int* 
         turned.d_row_ptrs = first.row_ptrs;
         turned.d_col_indices = first.col_indices;
         turned.d_values = first.values;
-        TransposeArrays second;
+        DeviceCsrArrays second;
         status = transpose_build(&turned, &second, s);
         first.release();
         if (status != 0) return status;
@@ -603,31 +525,13 @@ int permute(CSRMatrix* B, const CSRMatrix* A, const int* d_row_perm, const int* 
         (void)hipGetLastError();
         return code(SpMVError::KERNEL_LAUNCH);
     }
-    adopt(B, rows, cols, nnz, out);
-    out = TransposeArrays();          // B owns them now
+    csr_adopt_device(B, rows, cols, nnz, &out);          // B owns them now
     return 0;
 }
 
 } // namespace
 
 } // namespace reorder
-
-int structure_checked(const CSRMatrix* A, hipStream_t s) {
-    DevBuf<int> flag;
-    if (dev_alloc(&flag, 1) != hipSuccess) {
-        (void)hipGetLastError();
-        return code(SpMVError::CUDA_MALLOC);
-    }
-    int bad = 0;
-    if (hipMemsetAsync(flag.get(), 0, sizeof(int), s) != hipSuccess ||
-        reorder::enqueue_validate(A, flag.get(), s) != hipSuccess ||
-        hipMemcpyAsync(&bad, flag.get(), sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {
-        (void)hipGetLastError();
-        return code(SpMVError::KERNEL_LAUNCH);
-    }
-    return bad ? code(SpMVError::INVALID_FORMAT) : 0;
-}
 
 } // namespace detail
 
@@ -678,11 +582,7 @@ int permute_gather(float* d_out, int ldo, const float* d_in, int ldi, const int*
     hipStream_t s = current_stream();
     const int status = permute_gather_async(d_out, ldo, d_in, ldi, d_index, n, k, s);
     if (status != 0 || n == 0) return status;
-    if (hipStreamSynchronize(s) != hipSuccess) {
-        (void)hipGetLastError();
-        return code(SpMVError::KERNEL_LAUNCH);
-    }
-    return 0;
+    return stream_finished(s);
 }
 
 ColorResult multicolor_reorder(CSRMatrix* B, const CSRMatrix* A, int* d_perm, int* d_inverse,

@@ -58,6 +58,7 @@ int color_check(const CSRMatrix* A, const int* d_colors, const ColorConfig& cfg,
         *nothing_to_do = true;
         return 0;
     }
+    // (not device_arrays_strict: a negative nnz fails here, there it counts as no entries)
     if (A->num_rows < 0 || A->nnz < 0 || !A->d_row_ptrs || (A->nnz > 0 && (!A->d_col_indices || !A->d_values))) {
         return code(SpMVError::INVALID_FORMAT);
     }
@@ -69,11 +70,7 @@ int color_check(const CSRMatrix* A, const int* d_colors, const ColorConfig& cfg,
 int permute_check(const CSRMatrix* B, const CSRMatrix* A) {
     if (!B || !A) return code(SpMVError::INVALID_ARGUMENT);
     if (B == A) return code(SpMVError::INVALID_ARGUMENT);
-    if (A->num_rows < 0 || A->num_cols < 0 || A->nnz < 0) return code(SpMVError::INVALID_FORMAT);
-    if (A->num_rows > 0 && (!A->d_row_ptrs || (A->nnz > 0 && (!A->d_col_indices || !A->d_values)))) {
-        return code(SpMVError::INVALID_FORMAT);
-    }
-    if (A->num_rows == 0 && A->nnz != 0) return code(SpMVError::INVALID_FORMAT);
+    if (!device_arrays_lenient(A)) return code(SpMVError::INVALID_FORMAT);
     return 0;
 }
 
@@ -212,19 +209,7 @@ int csr_permute_cpu(CSRMatrix* B, const CSRMatrix* A, const int* row_perm, const
         new_ptrs[i + 1] = out;
     }
 
-    if (B->d_row_ptrs || B->d_col_indices || B->d_values) csr_free_gpu(B);     // a device copy would be stale
-    if (B->owns_host_memory) {
-        delete[] B->values;
-        delete[] B->col_indices;
-        delete[] B->row_ptrs;
-    }
-    B->num_rows = rows;
-    B->num_cols = cols;
-    B->nnz = nnz;
-    B->values = new_vals;
-    B->col_indices = new_cols;
-    B->row_ptrs = new_ptrs;
-    B->owns_host_memory = true;
+    csr_adopt_host(B, rows, cols, nnz, new_ptrs, new_cols, new_vals);
     return code(SpMVError::SUCCESS);
 }
 

@@ -101,9 +101,8 @@ inline bool ranges_overlap(const float* a, const float* b, long long n) {
     return a0 < b0 + bytes && b0 < a0 + bytes;
 }
 
-inline bool device_arrays(const CSRMatrix* M) {
-    return M->num_rows >= 0 && M->d_row_ptrs && (M->nnz <= 0 || (M->d_col_indices && M->d_values));
-}
+// the solvers' name for the strict rule of internal.h
+inline bool device_arrays(const CSRMatrix* M) { return device_arrays_strict(M); }
 
 template <DiagRule RULE>
 hipError_t launch_diag(const CSRMatrix* M, float* dinv, int* bad_flag, hipStream_t s) {

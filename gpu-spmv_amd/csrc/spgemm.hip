@@ -488,23 +488,6 @@ struct Scratch {
     }
 };
 
-struct Events {
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-    bool ok = true;
-    Events() {
-        for (hipEvent_t& x : e) ok = hipEventCreate(&x) == hipSuccess && ok;
-    }
-    ~Events() {
-        for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x);
-    }
-};
-
-bool arrays_missing(const CSRMatrix* M) {
-    if (M->num_rows < 0 || M->num_cols < 0 || M->nnz < 0) return true;
-    if (M->num_rows > 0 && (!M->d_row_ptrs || (M->nnz > 0 && (!M->d_col_indices || !M->d_values)))) return true;
-    return M->num_rows == 0 && M->nnz != 0;               // row_ptrs[0] == 0 != nnz
-}
-
 MatView view_of(const CSRMatrix* M, int limit, bool ascending) {
     return MatView{M->d_row_ptrs, M->d_col_indices, M->d_values, M->num_rows, limit, M->nnz, ascending ? 1 : 0};
 }
@@ -532,9 +515,7 @@ struct Job {
 
 bool job_alloc(Job& job, Scratch& scratch) {
     job.levels = device_scan_levels(static_cast<long long>(kSegments) * job.m + 1);
-    long long sums = 1;
-    for (size_t l = 1; l < job.levels.size(); ++l) sums += job.levels[l];
-    return scratch.get(&job.work, job.m) && scratch.get(&job.data, job.levels[0] + sums) &&
+    return scratch.get(&job.work, job.m) && scratch.get(&job.data, job.levels[0] + device_scan_sums(job.levels)) &&
            scratch.get(&job.lists, job.m) && scratch.get(&job.bounds, kSegments + 1) &&
            scratch.get(&job.flags, kMaxGrid) && scratch.get(&job.part_sum, kMaxGrid) &&
            scratch.get(&job.part_max, kMaxGrid) &&
@@ -673,12 +654,6 @@ int validate(const CSRMatrix* A, const CSRMatrix* B, const CSRMatrix* C, hipStre
     return code(SpMVError::SUCCESS);
 }
 
-int fail(SpGEMMResult* result, SpMVError e) {
-    (void)hipGetLastError();
-    result->error_code = code(e);
-    return result->error_code;
-}
-
 // checks 1 - 5 of spgemm.h, then the products per row: what both entry points start with
 int begin(Job& job, Scratch& scratch, const CSRMatrix* C, bool refill, const CSRMatrix* A, const CSRMatrix* B,
           SpGEMMResult* result, bool* nothing_to_do) {
@@ -689,7 +664,7 @@ int begin(Job& job, Scratch& scratch, const CSRMatrix* C, bool refill, const CSR
     if (refill && (C->num_rows != A->num_rows || C->num_cols != B->num_cols)) {
         return fail(result, SpMVError::INVALID_DIMENSION);
     }
-    if (arrays_missing(A) || arrays_missing(B) || (refill && arrays_missing(C))) {
+    if (!device_arrays_lenient(A) || !device_arrays_lenient(B) || (refill && !device_arrays_lenient(C))) {
         return fail(result, SpMVError::INVALID_FORMAT);
     }
     const int status = validate(A, B, refill ? C : nullptr, job.s);
@@ -724,9 +699,9 @@ int begin(Job& job, Scratch& scratch, const CSRMatrix* C, bool refill, const CSR
 
 } // namespace
 
-int spgemm_build(const CSRMatrix* C, const CSRMatrix* A, const CSRMatrix* B, TransposeArrays* out, int* out_nnz,
+int spgemm_build(const CSRMatrix* C, const CSRMatrix* A, const CSRMatrix* B, DeviceCsrArrays* out, int* out_nnz,
                  SpGEMMResult* result, hipStream_t s) {
-    *out = TransposeArrays();
+    *out = DeviceCsrArrays();
     *out_nnz = 0;
     *result = SpGEMMResult();
     Scratch scratch;
@@ -737,10 +712,8 @@ int spgemm_build(const CSRMatrix* C, const CSRMatrix* A, const CSRMatrix* B, Tra
     const TraceRange range("spmv:spgemm_csr");
     const int m = A->num_rows;
 
-    TransposeArrays c;
-    if (hipMalloc(reinterpret_cast<void**>(&c.row_ptrs), (static_cast<size_t>(m) + 1) * sizeof(int)) != hipSuccess) {
-        return fail(result, SpMVError::CUDA_MALLOC);
-    }
+    DeviceCsrArrays c;
+    if (c.alloc(static_cast<long long>(m) + 1, 0) != hipSuccess) return fail(result, SpMVError::CUDA_MALLOC);
     bool ok = hipMemsetAsync(c.row_ptrs, 0, (static_cast<size_t>(m) + 1) * sizeof(int), s) == hipSuccess;
     if (nothing) {
         ok = ok && hipStreamSynchronize(s) == hipSuccess;
@@ -785,11 +758,7 @@ int spgemm_build(const CSRMatrix* C, const CSRMatrix* A, const CSRMatrix* B, Tra
     (void)hipEventElapsedTime(&result->symbolic_ms, ev.e[0], ev.e[1]);
 
     // ---- numeric ----
-    if (nnz > 0 && (hipMalloc(reinterpret_cast<void**>(&c.col_indices), nnz * sizeof(int)) != hipSuccess ||
-                    hipMalloc(reinterpret_cast<void**>(&c.values), nnz * sizeof(float)) != hipSuccess)) {
-        c.release();
-        return fail(result, SpMVError::CUDA_MALLOC);
-    }
+    if (c.alloc_entries(nnz) != hipSuccess) return fail(result, SpMVError::CUDA_MALLOC);
     ok = hipEventRecord(ev.e[2], s) == hipSuccess &&
          good(launch_pass<NUMERIC>(job, scratch, nullptr, c.row_ptrs, c.col_indices, c.values, &oom)) &&
          hipEventRecord(ev.e[3], s) == hipSuccess;
@@ -836,28 +805,12 @@ int spgemm_refill(CSRMatrix* C, const CSRMatrix* A, const CSRMatrix* B, SpGEMMRe
 int spgemm_csr(CSRMatrix* C, const CSRMatrix* A, const CSRMatrix* B, SpGEMMResult* result) {
     SpGEMMResult local;
     SpGEMMResult* r = result ? result : &local;
-    detail::TransposeArrays c;
+    detail::DeviceCsrArrays c;
+    const detail::ReleaseOnExit release_c{&c};
     int nnz = 0;
     const int status = detail::spgemm_build(C, A, B, &c, &nnz, r, detail::current_stream());
     if (status != 0) return status;
-    const int rows = A->num_rows, cols = B->num_cols;
-    csr_free_gpu(C);
-    if (C->owns_host_memory) {
-        delete[] C->values;
-        delete[] C->col_indices;
-        delete[] C->row_ptrs;
-    }
-    C->num_rows = rows;
-    C->num_cols = cols;
-    C->nnz = nnz;
-    C->values = nnz > 0 ? new float[nnz] : nullptr;
-    C->col_indices = nnz > 0 ? new int[nnz] : nullptr;
-    C->row_ptrs = new int[static_cast<size_t>(rows) + 1];
-    C->owns_host_memory = true;
-    C->d_row_ptrs = c.row_ptrs;
-    C->d_col_indices = c.col_indices;
-    C->d_values = c.values;
-    C->owns_device_memory = true;
+    detail::csr_adopt_device(C, A->num_rows, B->num_cols, nnz, &c);
     return 0;
 }
 

@@ -6,7 +6,6 @@
 
 #include <algorithm>
 #include <climits>
-#include <cstring>
 #include <vector>
 
 namespace spmv {
@@ -82,28 +81,7 @@ int spgemm_cpu_csr(CSRMatrix* C, const CSRMatrix* A, const CSRMatrix* B) {
         row_ptrs[i + 1] = static_cast<int>(cols.size());
     }
 
-    const int nnz = static_cast<int>(cols.size());
-    float* new_vals = nnz > 0 ? new float[nnz] : nullptr;
-    int* new_cols = nnz > 0 ? new int[nnz] : nullptr;
-    int* new_ptrs = new int[static_cast<size_t>(m) + 1];
-    if (nnz > 0) {
-        std::memcpy(new_vals, vals.data(), sizeof(float) * nnz);
-        std::memcpy(new_cols, cols.data(), sizeof(int) * nnz);
-    }
-    std::memcpy(new_ptrs, row_ptrs.data(), sizeof(int) * (static_cast<size_t>(m) + 1));
-    if (C->d_row_ptrs || C->d_col_indices || C->d_values) csr_free_gpu(C);     // a device copy would be stale
-    if (C->owns_host_memory) {
-        delete[] C->values;
-        delete[] C->col_indices;
-        delete[] C->row_ptrs;
-    }
-    C->num_rows = m;
-    C->num_cols = n;
-    C->nnz = nnz;
-    C->values = new_vals;
-    C->col_indices = new_cols;
-    C->row_ptrs = new_ptrs;
-    C->owns_host_memory = true;
+    detail::csr_adopt_host(C, m, n, row_ptrs, cols, vals);
     return code(SpMVError::SUCCESS);
 }
 

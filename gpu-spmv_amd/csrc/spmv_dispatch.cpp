@@ -74,6 +74,7 @@ int check_csr(const CSRMatrix* A, const float* d_x, float* d_y, int vec_size, bo
     if (vec_size >= 0 && !spmv_validate_dimensions(A->num_cols, vec_size)) {
         return code(SpMVError::INVALID_DIMENSION);
     }
+    // (not device_arrays_strict: no sign check, a negative num_rows passes as in the reference)
     if (!A->d_row_ptrs || (A->nnz > 0 && (!A->d_col_indices || !A->d_values))) {
         return code(SpMVError::INVALID_FORMAT);
     }
@@ -148,6 +149,7 @@ int check_csr_multi(const CSRMatrix* A, const float* d_X, int ldx, const float* 
         return code(SpMVError::INVALID_DIMENSION);
     }
     if (ldx < k || ldy < k) return code(SpMVError::INVALID_DIMENSION);
+    // (check_csr's rule: not device_arrays_strict, no sign check)
     if (!A->d_row_ptrs || (A->nnz > 0 && (!A->d_col_indices || !A->d_values))) {
         return code(SpMVError::INVALID_FORMAT);
     }
@@ -189,6 +191,7 @@ int check_csr_transpose(const CSRMatrix* A, const float* d_x, const float* d_y, 
     if (vec_size >= 0 && !spmv_validate_dimensions(A->num_rows, vec_size)) {
         return code(SpMVError::INVALID_DIMENSION);
     }
+    // (not device_arrays_lenient: entries without rows pass here and come out as y = 0)
     if (A->num_rows < 0 || A->num_cols < 0 || A->nnz < 0 ||
         (A->num_rows > 0 && (!A->d_row_ptrs || (A->nnz > 0 && (!A->d_col_indices || !A->d_values))))) {
         return code(SpMVError::INVALID_FORMAT);
@@ -210,7 +213,7 @@ int transpose_for(const CSRMatrix* A, hipStream_t stream, std::shared_ptr<CSRMat
     }
     aux->transpose.reset();
     const TraceRange range("spmv:transpose_build");
-    TransposeArrays t;
+    DeviceCsrArrays t;
     const int status = transpose_build(A, &t, stream);
     if (status != 0) return status;
     CSRMatrix* at = new CSRMatrix{};

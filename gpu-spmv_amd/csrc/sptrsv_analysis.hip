@@ -297,23 +297,11 @@ void analysis_peel_run_kernel(int n, int upper, const int* __restrict__ trp, con
     }
 }
 
-__global__ __launch_bounds__(kBlock) void analysis_iota_kernel(long long n, int* __restrict__ out) {
-    for (long long i = blockIdx.x * static_cast<long long>(kBlock) + threadIdx.x; i < n;
-         i += static_cast<long long>(gridDim.x) * kBlock) {
-        out[i] = static_cast<int>(i);
-    }
-}
-
 // lanes per row for rows of `mean` entries walked one entry per lane and step
 int lanes_for_mean(double mean) {
     int lanes = 1;
     while (lanes < 64 && lanes < mean) lanes <<= 1;
     return lanes;
-}
-
-int failed(SpMVError e) {
-    (void)hipGetLastError();
-    return code(e);
 }
 
 } // namespace
@@ -332,7 +320,7 @@ int sptrsv_analysis_device(const CSRMatrix* A, int uplo, hipStream_t s, SptrsvSc
     DevBuf<int> dep, level, queue;
     if (!ws.allocate(0, 0) || dev_alloc(&dep, n) != hipSuccess || dev_alloc(&level, n) != hipSuccess ||
         dev_alloc(&queue, static_cast<long long>(n) + 1) != hipSuccess) {
-        return failed(SpMVError::CUDA_MALLOC);
+        return fail(SpMVError::CUDA_MALLOC);
     }
     PeelState* state = ws.state;
 
@@ -346,13 +334,10 @@ int sptrsv_analysis_device(const CSRMatrix* A, int uplo, hipStream_t s, SptrsvSc
             n, upper, A->d_row_ptrs, A->d_col_indices, dep.get(), level.get(), queue.get(), state);
         return hipGetLastError();
     }) == hipSuccess;
-    if (!ok) return failed(SpMVError::KERNEL_LAUNCH);
+    if (!ok) return fail(SpMVError::KERNEL_LAUNCH);
 
-    TransposeArrays at;
-    struct Release {
-        TransposeArrays* t;
-        ~Release() { t->release(); }
-    } release_at{&at};
+    DeviceCsrArrays at;
+    const ReleaseOnExit release_at{&at};
     const int transposed = transpose_build(A, &at, s);            // (waits for the stream)
     if (transposed != 0) return transposed;
 
@@ -364,7 +349,7 @@ int sptrsv_analysis_device(const CSRMatrix* A, int uplo, hipStream_t s, SptrsvSc
             return hipGetLastError();
         }) == hipSuccess;
     }
-    if (!ws.read_back(ok, s)) return failed(SpMVError::KERNEL_LAUNCH);
+    if (!ws.read_back(ok, s)) return fail(SpMVError::KERNEL_LAUNCH);
     const long long triangle_nnz = static_cast<long long>(ws.pinned[0].triangle_nnz);
 
     // ---- the rounds: pairs of (run of narrow rounds, one wide round), in batches with a look at the state between.
@@ -400,17 +385,16 @@ int sptrsv_analysis_device(const CSRMatrix* A, int uplo, hipStream_t s, SptrsvSc
     }
     if (!ws.read_back(ok, s)) {                                   // (every launch has ended: the transpose may go)
         (void)hipStreamSynchronize(s);
-        return failed(SpMVError::KERNEL_LAUNCH);
+        return fail(SpMVError::KERNEL_LAUNCH);
     }
     const PeelState result = ws.pinned[0];
     at.release();
-    if (!result.done || result.levels < 1 || result.levels > n) return failed(SpMVError::KERNEL_LAUNCH);
+    if (!result.done || result.levels < 1 || result.levels > n) return fail(SpMVError::KERNEL_LAUNCH);
 
     // ---- rows by level: row l of the transpose of the n x levels matrix with (i, level[i]) lists level l's rows in
     // ascending order; the values are never looked at ----
-    analysis_iota_kernel<<<vec_grid(static_cast<long long>(n) + 1), kBlock, 0, s>>>(static_cast<long long>(n) + 1,
-                                                                                    queue.get());
-    if (hipGetLastError() != hipSuccess) return failed(SpMVError::KERNEL_LAUNCH);
+    const long long count = static_cast<long long>(n) + 1;
+    if (launch_iota(count, queue.get(), vec_grid(count), s) != hipSuccess) return fail(SpMVError::KERNEL_LAUNCH);
     CSRMatrix byrow{};
     byrow.num_rows = n;
     byrow.num_cols = result.levels;
@@ -418,15 +402,15 @@ int sptrsv_analysis_device(const CSRMatrix* A, int uplo, hipStream_t s, SptrsvSc
     byrow.d_row_ptrs = queue.get();
     byrow.d_col_indices = level.get();
     byrow.d_values = reinterpret_cast<float*>(level.get());
-    TransposeArrays bylevel;
+    DeviceCsrArrays bylevel;
     const int sorted = transpose_build(&byrow, &bylevel, s);
-    if (sorted != 0) return sorted == code(SpMVError::INVALID_FORMAT) ? failed(SpMVError::KERNEL_LAUNCH) : sorted;
+    if (sorted != 0) return sorted == code(SpMVError::INVALID_FORMAT) ? fail(SpMVError::KERNEL_LAUNCH) : sorted;
     level_ptr->assign(static_cast<size_t>(result.levels) + 1, 0);
     if (hipMemcpyAsync(level_ptr->data(), bylevel.row_ptrs, level_ptr->size() * sizeof(int), hipMemcpyDeviceToHost,
                        s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess) {
         bylevel.release();
-        return failed(SpMVError::CUDA_MEMCPY);
+        return fail(SpMVError::CUDA_MEMCPY);
     }
     (void)hipFree(bylevel.values);
     out->d_level_ptr = bylevel.row_ptrs;                          // the schedule owns them now

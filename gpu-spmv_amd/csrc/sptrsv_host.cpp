@@ -319,6 +319,7 @@ int check_matrix(const CSRMatrix* A, bool* nothing_to_do) {
         *nothing_to_do = true;
         return code(SpMVError::SUCCESS);
     }
+    // (not device_arrays_strict: a negative nnz fails here, there it counts as no entries)
     if (A->num_rows < 0 || A->nnz < 0 || !A->d_row_ptrs || (A->nnz > 0 && (!A->d_col_indices || !A->d_values))) {
         return code(SpMVError::INVALID_FORMAT);
     }

@@ -6,8 +6,10 @@
 //   validate    one kernel: row_ptrs[0] == 0, non-decreasing, row_ptrs[rows] == nnz, every column in
 //               [0, num_cols); per workgroup a flag and the OR of (column ^ column[0]) — digits whose bits never
 //               differ are constant and their passes are skipped.  The host reads these before it allocates.
-//   expand      the row of every entry (binary search in row_ptrs, narrowed to the workgroup's row range)
-//   per pass    digit counts per 4096-entry tile, stored digit-major; an exclusive scan of them; a stable
+//   expand      the row of every entry (binary search in row_ptrs, narrowed to the workgroup's row range;
+//               launch_expand_rows of csr_build.hip)
+//   per pass    digit counts per 4096-entry tile, stored digit-major; an exclusive scan of them
+//               (device_exclusive_scan of csr_build.hip); a stable
 //               scatter of (key, row, value) that ranks inside a wavefront by ballot + mbcnt and across the
 //               wavefronts and rounds of a tile through LDS.  The last pass writes AT's arrays directly.
 //   row_ptrs    AT.row_ptrs[c] = lower_bound(sorted keys, c): one thread per column, empty columns included.
@@ -23,12 +25,9 @@ namespace detail {
 
 namespace {
 
-using dev::upper_bound;
-
 constexpr int kThreads = 256;                 // 4 wavefronts per workgroup
 constexpr int kRounds = 16;                   // rounds of 256 entries per tile
 constexpr int kTile = kThreads * kRounds;     // 4096 entries per tile
-constexpr int kScanTile = 4096;               // elements per workgroup of the scan
 constexpr int kValidateGrid = 2048;
 
 __device__ __forceinline__ unsigned lanes_below(unsigned long long mask) {
@@ -90,18 +89,6 @@ __global__ __launch_bounds__(kThreads) void transpose_validate_kernel(const int*
         partial[2 * blockIdx.x] = b;
         partial[2 * blockIdx.x + 1] = static_cast<int>(d);
     }
-}
-
-// row_of[p] = the row that holds entry p (row_ptrs validated: rp[0] == 0, non-decreasing, rp[rows] == nnz)
-__global__ __launch_bounds__(kThreads) void transpose_expand_rows_kernel(const int* __restrict__ rp, int rows,
-                                                                         long long nnz, int* __restrict__ row_of) {
-    __shared__ int s_first, s_last;
-    const long long base = blockIdx.x * static_cast<long long>(kThreads);
-    if (threadIdx.x == 0) s_first = upper_bound(rp, 0, rows + 1, base) - 1;
-    if (threadIdx.x == 1) s_last = upper_bound(rp, 0, rows + 1, std::min(base + kThreads, nnz) - 1) - 1;
-    __syncthreads();
-    const long long p = base + threadIdx.x;
-    if (p < nnz) row_of[p] = upper_bound(rp, s_first + 1, s_last + 2, p) - 1;
 }
 
 // counts[d * num_tiles + t] = entries of tile t whose digit is d
@@ -178,46 +165,6 @@ __global__ __launch_bounds__(kThreads) void transpose_scatter_kernel(
     }
 }
 
-// exclusive scan of data[b*kScanTile ...] in place per workgroup b; sums[b] = the tile's total
-__global__ __launch_bounds__(kThreads) void transpose_scan_tiles_kernel(int* __restrict__ data, long long n,
-                                                                        int* __restrict__ sums) {
-    constexpr int kPer = kScanTile / kThreads;
-    __shared__ int s[kScanTile];
-    __shared__ int s_tot[kThreads];
-    const long long base = blockIdx.x * static_cast<long long>(kScanTile);
-    for (int j = threadIdx.x; j < kScanTile; j += kThreads) s[j] = base + j < n ? data[base + j] : 0;
-    __syncthreads();
-    int mine = 0;
-#pragma unroll
-    for (int j = 0; j < kPer; ++j) mine += s[threadIdx.x * kPer + j];
-    s_tot[threadIdx.x] = mine;
-    __syncthreads();
-    for (int off = 1; off < kThreads; off <<= 1) {          // inclusive scan of the thread totals
-        const int add = threadIdx.x >= off ? s_tot[threadIdx.x - off] : 0;
-        __syncthreads();
-        s_tot[threadIdx.x] += add;
-        __syncthreads();
-    }
-    int run = s_tot[threadIdx.x] - mine;
-#pragma unroll
-    for (int j = 0; j < kPer; ++j) {
-        const int v = s[threadIdx.x * kPer + j];
-        s[threadIdx.x * kPer + j] = run;
-        run += v;
-    }
-    if (threadIdx.x == kThreads - 1) sums[blockIdx.x] = run;
-    __syncthreads();
-    for (int j = threadIdx.x; j < kScanTile; j += kThreads) {
-        if (base + j < n) data[base + j] = s[j];
-    }
-}
-
-__global__ __launch_bounds__(kThreads) void transpose_scan_add_kernel(int* __restrict__ data, long long n,
-                                                                      const int* __restrict__ sums) {
-    const long long i = blockIdx.x * static_cast<long long>(kThreads) + threadIdx.x;
-    if (i < n) data[i] += sums[i / kScanTile];
-}
-
 // AT.row_ptrs[c] = number of sorted keys < c, for c in [0, cols]
 __global__ __launch_bounds__(kThreads) void transpose_row_ptrs_kernel(const int* __restrict__ keys, long long n,
                                                                       int cols, int* __restrict__ at_rp) {
@@ -232,24 +179,6 @@ __global__ __launch_bounds__(kThreads) void transpose_row_ptrs_kernel(const int*
 }
 
 unsigned blocks_for(long long n, long long per) { return static_cast<unsigned>((n + per - 1) / per); }
-
-// scan levels: sizes n, ceil(n / kScanTile), ... down to one element
-std::vector<long long> scan_levels(long long n) {
-    std::vector<long long> sizes{n};
-    while (sizes.back() > 1) sizes.push_back((sizes.back() + kScanTile - 1) / kScanTile);
-    return sizes;
-}
-
-hipError_t exclusive_scan(int* data, const std::vector<long long>& sizes, size_t level, int* sums, hipStream_t s) {
-    const long long n = sizes[level];
-    const unsigned tiles = blocks_for(n, kScanTile);
-    transpose_scan_tiles_kernel<<<tiles, kThreads, 0, s>>>(data, n, sums);
-    if (tiles == 1) return hipGetLastError();
-    const hipError_t e = exclusive_scan(sums, sizes, level + 1, sums + sizes[level + 1], s);
-    if (e != hipSuccess) return e;
-    transpose_scan_add_kernel<<<blocks_for(n, kThreads), kThreads, 0, s>>>(data, n, sums);
-    return hipGetLastError();
-}
 
 // the build's scratch, freed when it goes out of scope (after the build has completed)
 struct Scratch {
@@ -273,29 +202,12 @@ struct Scratch {
 
 } // namespace
 
-std::vector<long long> device_scan_levels(long long n) { return scan_levels(n); }
-
-hipError_t device_exclusive_scan(int* data, const std::vector<long long>& levels, int* sums, hipStream_t s) {
-    return exclusive_scan(data, levels, 0, sums, s);
-}
-
-void TransposeArrays::release() {
-    if (row_ptrs) (void)hipFree(row_ptrs);
-    if (col_indices) (void)hipFree(col_indices);
-    if (values) (void)hipFree(values);
-    *this = TransposeArrays();
-}
-
-int transpose_build(const CSRMatrix* A, TransposeArrays* out, hipStream_t s) {
-    *out = TransposeArrays();
+int transpose_build(const CSRMatrix* A, DeviceCsrArrays* out, hipStream_t s) {
+    *out = DeviceCsrArrays();
     if (!A) return code(SpMVError::INVALID_ARGUMENT);
+    if (!device_arrays_lenient(A)) return code(SpMVError::INVALID_FORMAT);
     const int rows = A->num_rows, cols = A->num_cols;
     const long long nnz = A->nnz;
-    if (rows < 0 || cols < 0 || nnz < 0) return code(SpMVError::INVALID_FORMAT);
-    if (rows > 0 && (!A->d_row_ptrs || (nnz > 0 && (!A->d_col_indices || !A->d_values)))) {
-        return code(SpMVError::INVALID_FORMAT);
-    }
-    if (rows == 0 && nnz != 0) return code(SpMVError::INVALID_FORMAT);      // row_ptrs[0] == 0 != nnz
 
     // ---- validation: one kernel, one read of its per-workgroup flags, before anything is allocated ----
     unsigned diff = 0;
@@ -323,14 +235,8 @@ int transpose_build(const CSRMatrix* A, TransposeArrays* out, hipStream_t s) {
     }
 
     // ---- AT's arrays ----
-    TransposeArrays at;
-    if (hipMalloc(reinterpret_cast<void**>(&at.row_ptrs), (static_cast<size_t>(cols) + 1) * sizeof(int)) != hipSuccess ||
-        (nnz > 0 && (hipMalloc(reinterpret_cast<void**>(&at.col_indices), nnz * sizeof(int)) != hipSuccess ||
-                     hipMalloc(reinterpret_cast<void**>(&at.values), nnz * sizeof(float)) != hipSuccess))) {
-        (void)hipGetLastError();
-        at.release();
-        return code(SpMVError::CUDA_MALLOC);
-    }
+    DeviceCsrArrays at;
+    if (at.alloc(static_cast<long long>(cols) + 1, nnz) != hipSuccess) return code(SpMVError::CUDA_MALLOC);
 
     // passes: the digits (of four) in which some column differs from column[0]
     std::vector<int> shifts;
@@ -343,15 +249,13 @@ int transpose_build(const CSRMatrix* A, TransposeArrays* out, hipStream_t s) {
     {
         Scratch scratch;
         const long long tiles = (nnz + kTile - 1) / kTile;
-        const std::vector<long long> levels = scan_levels(256 * tiles);
-        long long level_total = 0;
-        for (size_t l = 1; l < levels.size(); ++l) level_total += levels[l];
+        const std::vector<long long> levels = device_scan_levels(256 * tiles);
         int *keys_a = nullptr, *keys_b = nullptr, *rows_b = nullptr, *counts = nullptr;
         unsigned* vals_b = nullptr;
         const bool got = passes == 0 ||
             (scratch.get(&keys_a, nnz) && scratch.get(&rows_b, nnz) &&
              (passes < 2 || (scratch.get(&keys_b, nnz) && scratch.get(&vals_b, nnz))) &&
-             scratch.get(&counts, 256 * tiles + level_total + 1));
+             scratch.get(&counts, 256 * tiles + device_scan_sums(levels)));
         if (!got) {
             at.release();
             return code(SpMVError::CUDA_MALLOC);
@@ -360,8 +264,7 @@ int transpose_build(const CSRMatrix* A, TransposeArrays* out, hipStream_t s) {
             // pass j writes set A = (keys_a, AT.col_indices, AT.values) when passes - j is even, set B otherwise;
             // the first pass reads the expanded rows from the set it does not write
             int* row_of = passes % 2 == 1 ? rows_b : at.col_indices;
-            transpose_expand_rows_kernel<<<blocks_for(nnz, kThreads), kThreads, 0, s>>>(rp, rows, nnz, row_of);
-            launched = launched && hipGetLastError() == hipSuccess;
+            launched = launched && launch_expand_rows(rp, rows, nnz, row_of, s) == hipSuccess;
             if (passes == 0) {
                 launched = launched && hipMemcpyAsync(at.values, A->d_values, nnz * sizeof(float),
                                                       hipMemcpyDeviceToDevice, s) == hipSuccess;
@@ -378,7 +281,7 @@ int transpose_build(const CSRMatrix* A, TransposeArrays* out, hipStream_t s) {
                 transpose_count_kernel<<<static_cast<unsigned>(tiles), kThreads, 0, s>>>(
                     k_in, nnz, shift, static_cast<int>(tiles), counts);
                 launched = hipGetLastError() == hipSuccess &&
-                           exclusive_scan(counts, levels, 0, counts + levels[0], s) == hipSuccess;
+                           device_exclusive_scan(counts, levels, counts + levels[0], s) == hipSuccess;
                 transpose_scatter_kernel<<<static_cast<unsigned>(tiles), kThreads, 0, s>>>(
                     k_in, r_in, v_in, nnz, shift, static_cast<int>(tiles), counts, k_out, r_out, v_out);
                 launched = launched && hipGetLastError() == hipSuccess;
