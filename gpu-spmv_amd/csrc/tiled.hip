@@ -251,6 +251,8 @@ void tiled_expand_kernel(const int* __restrict__ items, int first_item, int num_
     // workgroup above may set it before or after that read.  Either order gives the same result: this launch
     // writes scratch only (products, long-row chunk sums), which nothing reads after `done` is set — this
     // step's phase 2 starts after this launch has completed, sees `done` and returns, as does every later step.
+    // (The item record requested together with `done`, one scalar wait for both instead of one behind the other: the
+    // kernel +0.3 +- 0.8 us on C5 over 28 interleaved pairs, nothing — profiles/step_ends_ab.txt.)
     if (state && state->done) return;
     const int head_blocks = commit_blocks + long_blocks;
     if (static_cast<int>(blockIdx.x) < head_blocks) {     // the long-row workgroups go first (latency-bound)
@@ -283,12 +285,9 @@ struct LongSeeds {
 // accumulates in DOUBLE: every fp32 product is added exactly as often as fp64 allows (products of one row rarely span
 // more than 29 binades), so the row sums do not depend on the order in which the wavefronts' adds meet, and they are
 // rounded to fp32 once, on the way out.
-__device__ __forceinline__ void tile_accumulate(double* tile, int R, int tile_index,
-                                                const int* __restrict__ pass_first, const PassDesc* __restrict__ desc,
-                                                const float* __restrict__ prod,
-                                                const unsigned int* __restrict__ pass_word,
-                                                const LongSeeds seeds) {
-    __shared__ double spare[64];           // where a lane's slots without an entry "add" (never read)
+// In two pieces, tile_seed and tile_stream, so that the PageRank form can ask for the wavefront's pass range before the
+// first of them (the start of a tile's life, below); tile_accumulate is both, as the plain reduce runs them.
+__device__ __forceinline__ void tile_seed(double* tile, int R, int tile_index, const LongSeeds seeds) {
     const long long first = static_cast<long long>(tile_index) * R;
     for (int i = threadIdx.x; i < R; i += kReduceThreads) tile[i] = 0.0;
     if (seeds.tile_first) {
@@ -300,10 +299,14 @@ __device__ __forceinline__ void tile_accumulate(double* tile, int R, int tile_in
         }
     }
     __syncthreads();
+}
 
-    const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+// The calling wavefront's passes [pass_lo, pass_hi) added into the seeded tile, and the barrier that closes the tile.
+__device__ __forceinline__ void tile_stream(double* tile, int pass_lo, int pass_hi, const PassDesc* __restrict__ desc,
+                                            const float* __restrict__ prod,
+                                            const unsigned int* __restrict__ pass_word) {
+    __shared__ double spare[64];           // where a lane's slots without an entry "add" (never read)
     const int lane = threadIdx.x & 63;
-    const int pass_lo = pass_first[tile_index * kReduceWaves + wave], pass_hi = pass_first[tile_index * kReduceWaves + wave + 1];
 
     struct Pass {
         int lane_adj;                      // adj of the lane's segment (selected when the pass is opened: a select over struct
@@ -403,6 +406,17 @@ __device__ __forceinline__ void tile_accumulate(double* tile, int R, int tile_in
     __syncthreads();
 }
 
+__device__ __forceinline__ void tile_accumulate(double* tile, int R, int tile_index,
+                                                const int* __restrict__ pass_first, const PassDesc* __restrict__ desc,
+                                                const float* __restrict__ prod,
+                                                const unsigned int* __restrict__ pass_word,
+                                                const LongSeeds seeds) {
+    tile_seed(tile, R, tile_index, seeds);
+    const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+    const int pass_lo = pass_first[tile_index * kReduceWaves + wave], pass_hi = pass_first[tile_index * kReduceWaves + wave + 1];
+    tile_stream(tile, pass_lo, pass_hi, desc, prod, pass_word);
+}
+
 // The tile (R doubles, R = plan.tile_rows: any multiple of 64) lives in dynamic LDS.
 template <int kReduceBlock>
 __global__ __launch_bounds__(kReduceBlock, kReduceBlock / 128)     // two tiles per CU: 8 wavefronts per SIMD
@@ -432,16 +446,29 @@ void tiled_pagerank_reduce_kernel(int R, int num_tiles, const int* __restrict__ 
                                   const unsigned char* __restrict__ dangling, DanglingBits bits, float damping,
                                   const PrState* __restrict__ state,
                                   double* __restrict__ block_partials, PushTargets push) {
-    if (state->done) return;
     extern __shared__ double tile[];
     const int tile_index = xcd_contiguous(blockIdx.x, num_tiles);
     if (tile_index < 0) return;
-    // (asked for here, a whole tile ahead of its use: behind the r_old loads below it would be one more exposed latency)
-    const int flagged_rows = bits.words ? bits.tile_count[tile_index] : 0;
-    tile_accumulate(tile, R, tile_index, pass_first, pass_desc, prod, pass_word, seeds);
+    // The start of a tile's life.  Everything it reads through the scalar path is asked for here, together, and waited
+    // for once: `done`, the dangling mass (on the same line; first read behind the tile's closing barrier it was one more
+    // exposed latency there), the tile's flagged-row count and the wavefront's pass range (first read behind the cleared
+    // tile's barrier).  Read one behind the other they were four dependent waits per tile, and a uniform matrix brings all
+    // 512 resident workgroups to them together: moments at which the whole chip streams nothing.  C5's step kernel
+    // 0.7 us shorter by itself, 1.1 us on top of the non-temporal r_new stores below (profiles/step_ends_ab.txt).
+    // Without flag words the count's load reads `done` again: no branch around a load.
+    const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+    const int* range = pass_first + tile_index * kReduceWaves + wave;
+    const int* count_word = bits.words ? bits.tile_count + tile_index : &state->done;
+    int done = state->done, mass_bits = __float_as_int(state->dangling_sum), pass_lo = range[0], pass_hi = range[1];
+    int flagged = *count_word;
+    asm volatile("; tile head settled" : "+s"(done), "+s"(mass_bits), "+s"(pass_lo), "+s"(pass_hi), "+s"(flagged));
+    if (done) return;
+    const int flagged_rows = bits.words ? flagged : 0;
+    tile_seed(tile, R, tile_index, seeds);
+    tile_stream(tile, pass_lo, pass_hi, pass_desc, prod, pass_word);
 
     const float teleport = __fdiv_rn(1.0f - damping, static_cast<float>(n_global));
-    const float dangling_term = __fdiv_rn(__fmul_rn(damping, state->dangling_sum),
+    const float dangling_term = __fdiv_rn(__fmul_rn(damping, __int_as_float(mass_bits)),
                                           static_cast<float>(n_global));
     double res2 = 0.0, mass = 0.0;
     const long long first = static_cast<long long>(tile_index) * R;
@@ -450,6 +477,9 @@ void tiled_pagerank_reduce_kernel(int R, int num_tiles, const int* __restrict__ 
         // rows: read inside the loop they were one full memory latency per row and thread, ten in a row (the loop below waits
         // vmcnt(0) in every iteration: +22 us per step on C5, 182 against 160 us for the plain reduce); here all of a
         // thread's loads go out together, in front of the arithmetic.  Same operations in the same order: same bits.
+        // (Issued one step earlier still, behind a wavefront's last add and in front of the tile's closing barrier, so that
+        // they fly while the slower wavefronts drain: +0.1 +- 0.16 us by itself, -0.5 +- 0.3 on top of what is here now —
+        // nothing to tell from the noise, profiles/step_ends_ab.txt.)
         constexpr int kPerThread = (kMaxTileRows + kReduceBlock - 1) / kReduceBlock;
         const long long node_first = map.base + first;
         const int rows_here = static_cast<int>(min(static_cast<long long>(R), local_rows - first));     // >= 1: the tile exists
@@ -490,7 +520,10 @@ void tiled_pagerank_reduce_kernel(int R, int num_tiles, const int* __restrict__ 
             const int i = threadIdx.x + u * kReduceBlock;
             if (i < rows_here) {
                 const float fresh = __fadd_rn(__fadd_rn(__fmul_rn(damping, static_cast<float>(tile[i])), dangling_term), teleport);
-                r_new[node_first + i] = fresh;
+                // Non-temporal, like the products: nothing reads r_new through this XCD's L2 before the next launch, and
+                // stored plain a round's tiles leave ~20 MB of dirty lines there for the kernel's end to write back
+                // (C5: the kernel 3.1 us shorter, phase 1 of the next step — which reads the vector — unchanged).
+                __builtin_nontemporal_store(fresh, &r_new[node_first + i]);
                 const float diff = __fsub_rn(fresh, old_rank[u]);
                 res2 += static_cast<double>(__fmul_rn(diff, diff));
                 if (packed ? (is_dangling[u] >> flag_shift) & 1u : is_dangling[u]) mass += static_cast<double>(fresh);
