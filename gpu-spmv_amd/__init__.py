@@ -261,6 +261,27 @@ class ColorResult(Structure):
                 ("elapsed_ms", c_float)]
 
 
+class RcmConfig(Structure):
+    """include/spmv/reorder.h RcmConfig (16 bytes): symmetric_pattern 1 = only A's rows are walked; peripheral 1 = a
+    pseudo-peripheral start per component; lanes_per_row 0 = from the mean degree, else 1, 2, 4, ... 64"""
+    _fields_ = [("symmetric_pattern", c_int32), ("peripheral", c_int32), ("lanes_per_row", c_int32),
+                ("reserved", c_int32)]
+
+    def __init__(self, symmetric_pattern=0, peripheral=1, lanes_per_row=0, reserved=0):
+        super().__init__(symmetric_pattern, peripheral, lanes_per_row, reserved)
+
+
+class RcmResult(Structure):
+    """include/spmv/reorder.h RcmResult (24 bytes)"""
+    _fields_ = [("error_code", c_int32), ("components", c_int32), ("levels", c_int32), ("sweeps", c_int32),
+                ("launches", c_int32), ("elapsed_ms", c_float)]
+
+
+class CsrBand(Structure):
+    """include/spmv/reorder.h CsrBand (16 bytes): max(i - j), max(j - i) over the stored entries and the profile"""
+    _fields_ = [("lower", c_int32), ("upper", c_int32), ("profile", ctypes.c_int64)]
+
+
 class CooConfig(Structure):
     """include/spmv/assemble.h CooConfig (8 bytes): duplicates COO_SUM (0) = equal (row, column) pairs are summed in
     source order, COO_KEEP (1) = every triplet becomes an entry"""
@@ -484,6 +505,13 @@ _SIGNATURES = {
     "spmv_c_permute_gather_async": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
     "spmv_c_multicolor_reorder": (c_int, [POINTER(CSRMatrix), POINTER(CSRMatrix), c_void_p, c_void_p,
                                           POINTER(ColorConfig), POINTER(ColorResult)]),
+    "spmv_c_csr_rcm": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(RcmConfig), POINTER(RcmResult)]),
+    "spmv_c_csr_rcm_cpu": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(c_int32), POINTER(c_int32),
+                                   POINTER(RcmConfig)]),
+    "spmv_c_rcm_reorder": (c_int, [POINTER(CSRMatrix), POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(RcmConfig),
+                                   POINTER(RcmResult)]),
+    "spmv_c_csr_band_gpu": (c_int, [POINTER(CSRMatrix), POINTER(CsrBand)]),
+    "spmv_c_csr_band_cpu": (c_int, [POINTER(CSRMatrix), POINTER(CsrBand)]),
     "spmv_c_csr_from_coo_cpu": (c_int, [POINTER(CSRMatrix), c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                         POINTER(CooConfig)]),
     "spmv_c_csr_from_coo_gpu": (c_int, [POINTER(CSRMatrix), c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
@@ -1553,6 +1581,53 @@ def multicolor_reorder(B, A, d_perm, d_inverse, config=None) -> ColorResult:
     lib().spmv_c_multicolor_reorder(B, A, _dev(d_perm), _dev(d_inverse),
                                     byref(config) if config is not None else None, byref(out))
     return out
+
+
+# ---- reverse Cuthill-McKee reordering (include/spmv/reorder.h) ---------------------------
+def csr_rcm(A, d_perm, d_inverse, config=None) -> RcmResult:
+    """The reverse Cuthill-McKee ordering of the square device matrix A into d_perm[new] = old and d_inverse[old] = new
+    (num_rows int32 each on the device): the same ints as csr_rcm_cpu (reorder.h csr_rcm)."""
+    out = RcmResult()
+    lib().spmv_c_csr_rcm(A, _dev(d_perm), _dev(d_inverse), byref(config) if config is not None else None, byref(out))
+    return out
+
+
+def csr_rcm_cpu(A, config=None, perm=None, inverse=None):
+    """The ordering on A's host arrays, the definition (reorder.h csr_rcm_cpu): (status, perm, inverse, components,
+    levels); perm and inverse are None when the call fails.  perm / inverse: int32 arrays to write into (the tests'
+    poisoned ones), allocated here when not given."""
+    n = max(A.contents.num_rows, 0) if A else 0
+    perm = np.full(n, -7, np.int32) if perm is None else perm
+    inverse = np.full(n, -7, np.int32) if inverse is None else inverse
+    components, levels = c_int32(-7), c_int32(-7)
+    status = lib().spmv_c_csr_rcm_cpu(A, _np_ptr(perm), _np_ptr(inverse), byref(components), byref(levels),
+                                      byref(config) if config is not None else None)
+    if status != 0:
+        return status, None, None, 0, 0
+    return status, perm, inverse, components.value, levels.value
+
+
+def rcm_reorder(B, A, d_perm, d_inverse, config=None) -> RcmResult:
+    """csr_rcm, then B = P A P^T on the device (reorder.h rcm_reorder)."""
+    out = RcmResult()
+    lib().spmv_c_rcm_reorder(B, A, _dev(d_perm), _dev(d_inverse), byref(config) if config is not None else None,
+                             byref(out))
+    return out
+
+
+def csr_band_gpu(A):
+    """(status, lower, upper, profile) of A's device arrays (reorder.h csr_band_gpu); the figures are None when the
+    call fails"""
+    out = CsrBand(-7, -7, -7)
+    status = lib().spmv_c_csr_band_gpu(A, byref(out))
+    return (status, out.lower, out.upper, out.profile) if status == 0 else (status, None, None, None)
+
+
+def csr_band_cpu(A):
+    """the same of A's host arrays (reorder.h csr_band_cpu)"""
+    out = CsrBand(-7, -7, -7)
+    status = lib().spmv_c_csr_band_cpu(A, byref(out))
+    return (status, out.lower, out.upper, out.profile) if status == 0 else (status, None, None, None)
 
 
 # ---- matrix assembly (include/spmv/assemble.h) ------------------------------------------

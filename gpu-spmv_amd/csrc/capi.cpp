@@ -164,6 +164,19 @@ static_assert(sizeof(spmv_c_color_config) == sizeof(ColorConfig) && sizeof(Color
 static_assert(offsetof(spmv_c_color_config, symmetric_pattern) == offsetof(ColorConfig, symmetric_pattern) &&
               offsetof(spmv_c_color_config, lanes_per_row) == offsetof(ColorConfig, lanes_per_row) &&
               offsetof(spmv_c_color_config, reserved) == offsetof(ColorConfig, reserved), "ColorConfig layout");
+static_assert(sizeof(spmv_c_rcm_config) == sizeof(RcmConfig) && sizeof(RcmConfig) == 16, "RcmConfig layout");
+static_assert(offsetof(spmv_c_rcm_config, peripheral) == offsetof(RcmConfig, peripheral) &&
+              offsetof(spmv_c_rcm_config, lanes_per_row) == offsetof(RcmConfig, lanes_per_row) &&
+              offsetof(spmv_c_rcm_config, reserved) == offsetof(RcmConfig, reserved), "RcmConfig layout");
+static_assert(sizeof(spmv_c_rcm_result) == sizeof(RcmResult) && sizeof(RcmResult) == 24, "RcmResult layout");
+static_assert(offsetof(spmv_c_rcm_result, components) == offsetof(RcmResult, components) &&
+              offsetof(spmv_c_rcm_result, levels) == offsetof(RcmResult, levels) &&
+              offsetof(spmv_c_rcm_result, sweeps) == offsetof(RcmResult, sweeps) &&
+              offsetof(spmv_c_rcm_result, launches) == offsetof(RcmResult, launches) &&
+              offsetof(spmv_c_rcm_result, elapsed_ms) == offsetof(RcmResult, elapsed_ms), "RcmResult layout");
+static_assert(sizeof(spmv_c_csr_band) == sizeof(CsrBand) && sizeof(CsrBand) == 16 &&
+              offsetof(spmv_c_csr_band, upper) == offsetof(CsrBand, upper) &&
+              offsetof(spmv_c_csr_band, profile) == offsetof(CsrBand, profile), "CsrBand layout");
 static_assert(sizeof(spmv_c_color_result) == sizeof(ColorResult) && sizeof(ColorResult) == 20, "ColorResult layout");
 static_assert(offsetof(spmv_c_color_result, num_colors) == offsetof(ColorResult, num_colors) &&
               offsetof(spmv_c_color_result, rounds) == offsetof(ColorResult, rounds) &&
@@ -874,6 +887,34 @@ int spmv_c_multicolor_reorder(spmv_c_csr* B, const spmv_c_csr* A, int32_t* d_per
                                              reinterpret_cast<const ColorConfig*>(config));
     if (out) std::memcpy(out, &r, sizeof(r));
     return r.error_code;
+}
+
+// ---- reverse Cuthill-McKee reordering ----
+int spmv_c_csr_rcm(const spmv_c_csr* A, int32_t* d_perm, int32_t* d_inverse, const spmv_c_rcm_config* config,
+                   spmv_c_rcm_result* out) {
+    const RcmResult r = csr_rcm(cxx(A), d_perm, d_inverse, reinterpret_cast<const RcmConfig*>(config));
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
+}
+
+int spmv_c_csr_rcm_cpu(const spmv_c_csr* A, int32_t* perm, int32_t* inverse, int32_t* components, int32_t* levels,
+                       const spmv_c_rcm_config* config) {
+    return csr_rcm_cpu(cxx(A), perm, inverse, components, levels, reinterpret_cast<const RcmConfig*>(config));
+}
+
+int spmv_c_rcm_reorder(spmv_c_csr* B, const spmv_c_csr* A, int32_t* d_perm, int32_t* d_inverse,
+                       const spmv_c_rcm_config* config, spmv_c_rcm_result* out) {
+    const RcmResult r = rcm_reorder(cxx(B), cxx(A), d_perm, d_inverse, reinterpret_cast<const RcmConfig*>(config));
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
+}
+
+int spmv_c_csr_band_gpu(const spmv_c_csr* A, spmv_c_csr_band* out) {
+    return csr_band_gpu(cxx(A), reinterpret_cast<CsrBand*>(out));
+}
+
+int spmv_c_csr_band_cpu(const spmv_c_csr* A, spmv_c_csr_band* out) {
+    return csr_band_cpu(cxx(A), reinterpret_cast<CsrBand*>(out));
 }
 
 // ---- matrix assembly ----

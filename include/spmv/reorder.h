@@ -7,6 +7,8 @@
 // dependency level of either triangle is a whole colour class: the level count falls to the number of colours.
 // Nothing in the solvers, factorisations or schedules changes; they are handed a better-ordered matrix
 // (gpu-spmv_amd/csrc/reorder.hip, reorder_host.cpp; the recipe is in INTEGRATION.md).
+// The second half of the file is the ordering for the opposite need, locality: reverse Cuthill-McKee (csr_rcm,
+// rcm_reorder) and the band statistics that show what it bought (csr_band_gpu).
 #ifndef SPMV_REORDER_H
 #define SPMV_REORDER_H
 
@@ -114,6 +116,99 @@ int permute_gather_async(float* d_out, int ldo, const float* d_in, int ldi, cons
 // B == A -> INVALID_ARGUMENT; then csr_color's.
 ColorResult multicolor_reorder(CSRMatrix* B, const CSRMatrix* A, int* d_perm, int* d_inverse,
                                const ColorConfig* config = nullptr);
+
+// ---- reverse Cuthill-McKee: the ordering for locality (gpu-spmv_amd/csrc/rcm.hip, rcm_host.cpp) ----
+// The multicolour ordering above shortens level schedules and pays with locality.  This one does the opposite: it
+// pulls the entries of P A P^T towards the diagonal, so that the x gather of a row stays inside a few cache lines and
+// the ILU(0) / IC(0) factors of a mesh that arrived in an arbitrary numbering are those of a banded matrix.
+
+struct RcmConfig {
+    int symmetric_pattern;   // as ColorConfig: 1 = only A's rows are walked (the caller promises a symmetric pattern)
+    int peripheral;          // 1: a George-Liu pseudo-peripheral start per component; 0: start at the rule's minimum vertex
+    int lanes_per_row;       // lanes that share a row: 0 = from the mean degree, else 1, 2, 4, ... 64
+    int reserved;            // 0
+    RcmConfig() : symmetric_pattern(0), peripheral(1), lanes_per_row(0), reserved(0) {}
+};
+
+struct RcmResult {           // 24 bytes
+    int   error_code;    // SpMVError as int
+    int   components;    // components numbered, every isolated vertex one of them
+    int   levels;        // levels of the final level structures, summed over the components
+    int   sweeps;        // level structures the device built, the search's included (isolated vertices need none)
+    int   launches;      // kernel launches of the call's own loop (the builders of the symmetrised matrix not counted)
+    float elapsed_ms;    // device-event time of that loop
+    RcmResult() : error_code(0), components(0), levels(0), sweeps(0), launches(0), elapsed_ms(0.0f) {}
+};
+
+// The reverse Cuthill-McKee ordering of the square matrix A (resident on the device): d_perm[new] = old and
+// d_inverse[old] = new (num_rows ints each on the device), color_ordering's conventions, so csr_permute_gpu and
+// permute_gather take them unchanged.
+//
+// Input: every row's columns strictly ascending (csr_add's rule; csr_row_indices_gpu + csr_from_coo_gpu of
+// spmv/assemble.h normalise a matrix that is not).  The values are never read.
+// Graph: adj(v) = the columns u != v stored in row v and, with symmetric_pattern = 0, also the rows u != v that store
+// v.  deg(v) = |adj(v)|, key(v) = (deg(v), v), compared lexicographically, smaller first.
+// Rule (csr_rcm_cpu computes exactly this, sequentially, and is the definition): while some vertex is unnumbered, let
+// r be the unnumbered vertex of smallest key.  With peripheral = 1: build the rooted level structure L(r) over the
+// unnumbered vertices, let c be the vertex of smallest key in its last level, and if L(c) has more levels than L(r)
+// set r = c and repeat; otherwise stop.  Then Cuthill-McKee from r: a queue that starts as (r); when u is dequeued its
+// unnumbered neighbours are appended in ascending key.  The vertices are numbered in queue order, after those of the
+// earlier components; the final order is the reverse of the whole sequence.  An isolated vertex is a component of its
+// own, and the isolated vertices come first in index order (last after the reversal).  With symmetric_pattern = 1 and a
+// pattern that is not symmetric the same words apply to the directed graph: the result is what csr_rcm_cpu gives, a
+// permutation that need not reduce anything.
+// csr_rcm gives the same ints on every input, every run, every stream and every lanes_per_row.
+//
+// Device algorithm: S = the pattern of A + A^T (csr_transpose_gpu, csr_add; A itself with symmetric_pattern = 1);
+// D = the vertices by key, a stable counting sort by degree (color_ordering); S' = D S D^T (csr_permute_gpu), in whose
+// numbering the smallest key is the smallest index and every row lists its neighbours in key order.  A level structure
+// is then built level by level: an integer atomicMin gives every vertex of the next level its parent, the earliest
+// position of the level before that stores it; every parent counts its children, a scan of the counts in position
+// order gives each parent its slice of the next level, and a child's rank inside the slice is the count of its
+// parent's children to its left in the row.  That is the queue order.  Runs of levels of at most 256 vertices are
+// numbered by one workgroup in one launch, wider levels by four grid-wide launches each.  No workgroup waits for
+// another.  Rounds are enqueued in batches and a small state is read back after each; the search's decisions are taken
+// on the device.  Cost: the loop runs per component and per level, so a matrix with very many non-trivial components,
+// or a very long thin one, costs launches and round trips in proportion; result.components and result.launches
+// report it.  Nothing of size n or nnz crosses the bus.
+//
+// Checks, in this order; nothing is written to d_perm or d_inverse when one fails: null A / d_perm / d_inverse ->
+// INVALID_ARGUMENT; num_rows != num_cols -> INVALID_DIMENSION; num_rows == 0 -> SUCCESS; missing device arrays ->
+// INVALID_FORMAT; lanes_per_row not 0 or a power of two <= 64 -> INVALID_ARGUMENT; peripheral not 0 or 1 ->
+// INVALID_ARGUMENT; reserved != 0 -> INVALID_ARGUMENT; then on the device: csr_color's structure rule, and every
+// column strictly above its left neighbour, else INVALID_FORMAT.  A loop that stops making progress (it cannot) gives
+// KERNEL_LAUNCH, never a hang.  Runs on the library stream and returns after the ordering completed.
+RcmResult csr_rcm(const CSRMatrix* A, int* d_perm, int* d_inverse, const RcmConfig* config = nullptr);
+
+// The definition, on A's HOST arrays: perm[num_rows], inverse[num_rows]; *components and *levels (either may be null)
+// as in RcmResult.  config->lanes_per_row is checked and otherwise ignored.  Checks: null A / perm / inverse ->
+// INVALID_ARGUMENT; not square -> INVALID_DIMENSION; no rows -> SUCCESS; missing host arrays -> INVALID_ARGUMENT;
+// lanes_per_row, peripheral, reserved as above; malformed arrays or a row that is not strictly ascending ->
+// INVALID_FORMAT.  perm and inverse are untouched on any error.
+int csr_rcm_cpu(const CSRMatrix* A, int* perm, int* inverse, int* components, int* levels,
+                const RcmConfig* config = nullptr);
+
+// csr_rcm, then B = P A P^T (csr_permute_gpu).  The result is csr_rcm's; error_code is that of the first step that
+// failed, and B is untouched unless both succeeded (d_perm and d_inverse have been written when only the permutation
+// failed).  Checks: null B / A / d_perm / d_inverse -> INVALID_ARGUMENT; B == A -> INVALID_ARGUMENT; then csr_rcm's.
+RcmResult rcm_reorder(CSRMatrix* B, const CSRMatrix* A, int* d_perm, int* d_inverse, const RcmConfig* config = nullptr);
+
+// How far the stored entries of A lie from the diagonal: lower = max(i - j) and upper = max(j - i) over the stored
+// entries (i, j) (0 without any), profile = the sum over the rows of i - min(i, smallest stored column of row i) (a
+// row without entries adds 0).  A may be rectangular and its rows unsorted.  Integers throughout: the two calls agree
+// exactly.  (Not to be confused with spmv/bandwidth.h, which models bytes moved.)
+struct CsrBand {             // 16 bytes
+    int lower;
+    int upper;
+    long long profile;
+};
+// A on the device.  Checks: null A or out -> INVALID_ARGUMENT; missing device arrays (csr_transpose_gpu's rule) ->
+// INVALID_FORMAT; then the structure on the device -> INVALID_FORMAT; *out is written on SUCCESS only.  Runs on the
+// library stream and returns after it completed.
+int csr_band_gpu(const CSRMatrix* A, CsrBand* out);
+// A's host arrays.  Checks: null A or out, negative sizes, missing host arrays -> INVALID_ARGUMENT; malformed arrays
+// -> INVALID_FORMAT.
+int csr_band_cpu(const CSRMatrix* A, CsrBand* out);
 
 } // namespace spmv
 

@@ -673,6 +673,47 @@ int spmv_c_permute_gather_async(float* d_out, int ldo, const float* d_in, int ld
 int spmv_c_multicolor_reorder(spmv_c_csr* B, const spmv_c_csr* A, int32_t* d_perm, int32_t* d_inverse,
                               const spmv_c_color_config* config, spmv_c_color_result* out);
 
+/* ---- reverse Cuthill-McKee reordering (extension; include/spmv/reorder.h) ---- */
+/* symmetric_pattern: 1 = only A's rows are walked (the caller's promise); peripheral: 1 = a pseudo-peripheral start
+ * per component, 0 = the vertex of smallest (degree, index); lanes_per_row: 0 = from the mean degree, else 1, 2, 4,
+ * ... 64; reserved: 0 (16 bytes).  NULL stands for (0, 1, 0, 0). */
+typedef struct spmv_c_rcm_config {
+    int32_t symmetric_pattern;
+    int32_t peripheral;
+    int32_t lanes_per_row;
+    int32_t reserved;
+} spmv_c_rcm_config;
+/* 24 bytes */
+typedef struct spmv_c_rcm_result {
+    int32_t error_code;
+    int32_t components;
+    int32_t levels;
+    int32_t sweeps;
+    int32_t launches;
+    float   elapsed_ms;
+} spmv_c_rcm_result;
+/* 16 bytes: max(i - j), max(j - i) over the stored entries, sum over the rows of i - min(i, smallest stored column) */
+typedef struct spmv_c_csr_band {
+    int32_t lower;
+    int32_t upper;
+    int64_t profile;
+} spmv_c_csr_band;
+
+/* The reverse Cuthill-McKee ordering of the square device matrix A (rows strictly ascending): d_perm[new] = old,
+ * d_inverse[old] = new, num_rows ints each on the device; the same ints as spmv_c_csr_rcm_cpu.  Checks and algorithm as
+ * csr_rcm in include/spmv/reorder.h.  The return value equals out->error_code (out may be NULL). */
+int spmv_c_csr_rcm(const spmv_c_csr* A, int32_t* d_perm, int32_t* d_inverse, const spmv_c_rcm_config* config,
+                   spmv_c_rcm_result* out);
+/* the definition on A's host arrays; *components and *levels may be NULL */
+int spmv_c_csr_rcm_cpu(const spmv_c_csr* A, int32_t* perm, int32_t* inverse, int32_t* components, int32_t* levels,
+                       const spmv_c_rcm_config* config);
+/* spmv_c_csr_rcm, then B = P A P^T (spmv_c_csr_permute_gpu) */
+int spmv_c_rcm_reorder(spmv_c_csr* B, const spmv_c_csr* A, int32_t* d_perm, int32_t* d_inverse,
+                       const spmv_c_rcm_config* config, spmv_c_rcm_result* out);
+/* the band statistics of A's device arrays / host arrays: the same integers */
+int spmv_c_csr_band_gpu(const spmv_c_csr* A, spmv_c_csr_band* out);
+int spmv_c_csr_band_cpu(const spmv_c_csr* A, spmv_c_csr_band* out);
+
 /* ---- matrix assembly (extension; include/spmv/assemble.h) ---- */
 /* duplicates: 0 = equal (row, column) pairs are summed in source order, 1 = every triplet is kept; reserved: 0
  * (8 bytes) */
