@@ -306,6 +306,21 @@ class CsrAddResult(Structure):
                 ("lanes", c_int32), ("launches", c_int32), ("symbolic_ms", c_float), ("numeric_ms", c_float)]
 
 
+class BSRMatrix(Structure):
+    """include/spmv/bsr_matrix.h BSRMatrix (80 bytes): square block_dim x block_dim blocks, row-major inside a block"""
+    _fields_ = [("num_rows", c_int32), ("num_cols", c_int32), ("block_dim", c_int32), ("num_block_rows", c_int32),
+                ("num_block_cols", c_int32), ("num_blocks", c_int32),
+                ("values", POINTER(c_float)), ("block_cols", POINTER(c_int32)), ("block_row_ptrs", POINTER(c_int32)),
+                ("d_values", c_void_p), ("d_block_cols", c_void_p), ("d_block_row_ptrs", c_void_p),
+                ("owns_host_memory", c_uint8), ("owns_device_memory", c_uint8)]
+
+
+class BsrBuildResult(Structure):
+    """include/spmv/bsr.h BsrBuildResult (32 bytes); fill = nnz / positions of the blocks that lie inside the matrix"""
+    _fields_ = [("error_code", c_int32), ("num_blocks", c_int32), ("fill", c_float), ("max_block_row", c_int32),
+                ("lanes", c_int32), ("launches", c_int32), ("symbolic_ms", c_float), ("numeric_ms", c_float)]
+
+
 class FSAIResult(Structure):
     """include/spmv/fsai.h FSAIResult (32 bytes); bad_row is the lowest row whose g_ii is not > 0 or not finite, long_row
     the lowest row with more than 64 pattern entries, -1 when there is none"""
@@ -527,6 +542,24 @@ _SIGNATURES = {
     "spmv_c_csr_add_numeric": (c_int, [POINTER(CSRMatrix), c_float, POINTER(CSRMatrix), c_float, POINTER(CSRMatrix),
                                        POINTER(CsrAddResult)]),
     "spmv_c_csr_add_cpu": (c_int, [POINTER(CSRMatrix), c_float, POINTER(CSRMatrix), c_float, POINTER(CSRMatrix)]),
+    "spmv_c_bsr_create": (POINTER(BSRMatrix), [c_int, c_int, c_int, c_int]),
+    "spmv_c_bsr_destroy": (None, [POINTER(BSRMatrix)]),
+    "spmv_c_bsr_to_gpu": (c_int, [POINTER(BSRMatrix)]),
+    "spmv_c_bsr_from_gpu": (c_int, [POINTER(BSRMatrix)]),
+    "spmv_c_bsr_free_gpu": (None, [POINTER(BSRMatrix)]),
+    "spmv_c_bsr_invalidate_gpu_cache": (None, [POINTER(BSRMatrix)]),
+    "spmv_c_bsr_wrap_device": (POINTER(BSRMatrix), [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "spmv_c_bsr_from_csr_cpu": (c_int, [POINTER(BSRMatrix), POINTER(CSRMatrix), c_int]),
+    "spmv_c_bsr_from_csr_gpu": (c_int, [POINTER(BSRMatrix), POINTER(CSRMatrix), c_int, POINTER(BsrBuildResult)]),
+    "spmv_c_bsr_from_csr_numeric": (c_int, [POINTER(BSRMatrix), POINTER(CSRMatrix), POINTER(BsrBuildResult)]),
+    "spmv_c_csr_block_count_gpu": (c_int, [POINTER(CSRMatrix), c_int, POINTER(c_int64)]),
+    "spmv_c_bsr_to_csr_gpu": (c_int, [POINTER(CSRMatrix), POINTER(BSRMatrix), c_int]),
+    "spmv_c_bsr_to_csr_cpu": (c_int, [POINTER(CSRMatrix), POINTER(BSRMatrix), c_int]),
+    "spmv_c_cpu_bsr": (None, [POINTER(BSRMatrix), c_void_p, c_void_p]),
+    "spmv_c_spmv_bsr": (c_int, [POINTER(BSRMatrix), c_void_p, c_void_p, POINTER(SpMVConfig), c_int,
+                                POINTER(SpMVResult)]),
+    "spmv_c_spmv_bsr_async": (c_int, [POINTER(BSRMatrix), c_void_p, c_void_p, POINTER(SpMVConfig), c_int, c_void_p]),
+    "spmv_c_compute_bandwidth_bsr": (c_int, [POINTER(BSRMatrix), c_float, POINTER(BandwidthMetrics)]),
     "spmv_c_csr_scale_gpu": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, c_void_p]),
     "spmv_c_csr_scale_cpu": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, c_void_p]),
     "spmv_c_csr_diagonal_gpu": (c_int, [POINTER(CSRMatrix), c_void_p]),
@@ -1703,6 +1736,128 @@ def csr_add_numeric(C, alpha, A, beta, B) -> CsrAddResult:
 def csr_add_cpu(C, alpha, A, beta, B) -> int:
     """The sum on host arrays, the definition of the arithmetic (csr_ops.h csr_add_cpu); C gets new host arrays."""
     return lib().spmv_c_csr_add_cpu(C, float(alpha), A, float(beta), B)
+
+
+# ---- block CSR (include/spmv/bsr_matrix.h, include/spmv/bsr.h) -----------------------------------------------
+def bsr_create(rows, cols, block_dim, num_blocks):
+    p = lib().spmv_c_bsr_create(rows, cols, block_dim, num_blocks)
+    return p if p else None
+
+
+def bsr_destroy(mat) -> None:
+    if mat:
+        lib().spmv_c_bsr_destroy(mat)
+
+
+def bsr_to_gpu(mat) -> int:
+    return lib().spmv_c_bsr_to_gpu(mat)
+
+
+def bsr_from_gpu(mat) -> int:
+    return lib().spmv_c_bsr_from_gpu(mat)
+
+
+def bsr_free_gpu(mat) -> None:
+    lib().spmv_c_bsr_free_gpu(mat)
+
+
+def bsr_invalidate_gpu_cache(mat) -> None:
+    lib().spmv_c_bsr_invalidate_gpu_cache(mat)
+
+
+def bsr_wrap_device(rows, cols, block_dim, num_blocks, d_block_row_ptrs, d_block_cols, d_values):
+    """Header over caller-owned device arrays (bsr_matrix.h bsr_wrap_device); None for a shape no BSR matrix has."""
+    p = lib().spmv_c_bsr_wrap_device(rows, cols, block_dim, num_blocks, c_void_p(d_block_row_ptrs),
+                                     c_void_p(d_block_cols), c_void_p(d_values))
+    return p if p else None
+
+
+def bsr_from_arrays(num_rows, num_cols, block_dim, block_row_ptrs, block_cols, values):
+    """Convenience: bsr_create + fill of the host arrays."""
+    block_row_ptrs = np.ascontiguousarray(block_row_ptrs, dtype=np.int32)
+    block_cols = np.ascontiguousarray(block_cols, dtype=np.int32)
+    values = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+    mat = bsr_create(num_rows, num_cols, block_dim, int(block_cols.size))
+    m = mat.contents
+    assert block_row_ptrs.size == m.num_block_rows + 1 and values.size == block_cols.size * block_dim * block_dim
+    ctypes.memmove(m.block_row_ptrs, _np_ptr(block_row_ptrs), block_row_ptrs.nbytes)
+    if block_cols.size:
+        ctypes.memmove(m.block_cols, _np_ptr(block_cols), block_cols.nbytes)
+        ctypes.memmove(m.values, _np_ptr(values), values.nbytes)
+    return mat
+
+
+def bsr_host_arrays(mat):
+    """(block_row_ptrs, block_cols, values) numpy copies of the host arrays; values is flat."""
+    m = mat.contents
+    rp = np.ctypeslib.as_array(m.block_row_ptrs, shape=(m.num_block_rows + 1,)).copy()
+    if m.num_blocks > 0:
+        bc = np.ctypeslib.as_array(m.block_cols, shape=(m.num_blocks,)).copy()
+        va = np.ctypeslib.as_array(m.values, shape=(m.num_blocks * m.block_dim * m.block_dim,)).copy()
+    else:
+        bc, va = np.empty(0, np.int32), np.empty(0, np.float32)
+    return rp, bc, va
+
+
+def bsr_from_csr_cpu(B, A, block_dim) -> int:
+    """CSR (strictly ascending rows) to BSR on host arrays: the definition of the conversion (bsr.h)."""
+    return lib().spmv_c_bsr_from_csr_cpu(B, A, int(block_dim))
+
+
+def bsr_from_csr_gpu(B, A, block_dim) -> BsrBuildResult:
+    """The same on the device, bit for bit (bsr.h bsr_from_csr_gpu); B owns new device arrays afterwards and
+    bsr_from_gpu(B) fills its host arrays.  result.error_code is the return value."""
+    out = BsrBuildResult()
+    out.error_code = lib().spmv_c_bsr_from_csr_gpu(B, A, int(block_dim), byref(out))
+    return out
+
+
+def bsr_from_csr_numeric(B, A) -> BsrBuildResult:
+    """Only B's device values again from a new A over the same pattern (bsr.h bsr_from_csr_numeric)."""
+    out = BsrBuildResult()
+    out.error_code = lib().spmv_c_bsr_from_csr_numeric(B, A, byref(out))
+    return out
+
+
+def csr_block_count_gpu(A, block_dim):
+    """(status, blocks) of the counting pass alone (bsr.h csr_block_count_gpu)."""
+    blocks = c_int64(-1)
+    status = lib().spmv_c_csr_block_count_gpu(A, int(block_dim), byref(blocks))
+    return status, int(blocks.value)
+
+
+def bsr_to_csr_gpu(A, B, keep_zeros=0) -> int:
+    return lib().spmv_c_bsr_to_csr_gpu(A, B, int(keep_zeros))
+
+
+def bsr_to_csr_cpu(A, B, keep_zeros=0) -> int:
+    return lib().spmv_c_bsr_to_csr_cpu(A, B, int(keep_zeros))
+
+
+def spmv_cpu_bsr(A, x) -> np.ndarray:
+    """The ordered sum on host arrays (bsr.h spmv_cpu_bsr)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    y = np.zeros(A.contents.num_rows, dtype=np.float32)
+    lib().spmv_c_cpu_bsr(A, _np_ptr(x), _np_ptr(y))
+    return y
+
+
+def spmv_bsr(A, d_x, d_y, config=None, vec_size=-1) -> SpMVResult:
+    out = SpMVResult()
+    out.error_code = lib().spmv_c_spmv_bsr(A, _dev(d_x), _dev(d_y), byref(config) if config is not None else None,
+                                           vec_size, byref(out))
+    return out
+
+
+def spmv_bsr_async(A, d_x, d_y, config=None, vec_size=-1, stream=None) -> int:
+    return lib().spmv_c_spmv_bsr_async(A, _dev(d_x), _dev(d_y), byref(config) if config is not None else None,
+                                       vec_size, c_void_p(stream))
+
+
+def compute_bandwidth_bsr(A, elapsed_ms) -> BandwidthMetrics:
+    out = BandwidthMetrics()
+    lib().spmv_c_compute_bandwidth_bsr(A, float(elapsed_ms), byref(out))
+    return out
 
 
 def csr_scale_gpu(A, d_row_scale=None, d_col_scale=None, d_values_out=None) -> int:

@@ -78,4 +78,14 @@ BandwidthMetrics compute_bandwidth_ell(const ELLMatrix* A, float elapsed_ms) {
     return from_bytes(bytes, elapsed_ms);
 }
 
+BandwidthMetrics compute_bandwidth_bsr(const BSRMatrix* A, float elapsed_ms) {
+    if (!A || elapsed_ms <= 0.0f) return BandwidthMetrics();
+    const double b = A->block_dim;
+    const double bytes = static_cast<double>(A->num_blocks) * (b * b * sizeof(float) + sizeof(int))   // blocks + block_cols
+                       + (static_cast<double>(A->num_block_rows) + 1) * sizeof(int)                    // block_row_ptrs
+                       + static_cast<double>(A->num_cols) * sizeof(float)                              // x, counted once
+                       + static_cast<double>(A->num_rows) * sizeof(float);                             // y
+    return from_bytes(bytes, elapsed_ms);
+}
+
 } // namespace spmv

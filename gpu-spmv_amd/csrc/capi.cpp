@@ -19,6 +19,7 @@
 #include "spmv/reorder.h"
 #include "spmv/assemble.h"
 #include "spmv/csr_ops.h"
+#include "spmv/bsr.h"
 #include "spmv_c.h"
 
 #include <cstddef>
@@ -34,6 +35,23 @@ static_assert(offsetof(spmv_c_csr, d_values) == offsetof(CSRMatrix, d_values), "
 static_assert(offsetof(spmv_c_csr, owns_host_memory) == offsetof(CSRMatrix, owns_host_memory), "CSRMatrix layout");
 static_assert(offsetof(spmv_c_csr, owns_device_memory) == offsetof(CSRMatrix, owns_device_memory), "CSRMatrix layout");
 static_assert(sizeof(spmv_c_ell) == sizeof(ELLMatrix) && sizeof(ELLMatrix) == 56, "ELLMatrix layout");
+static_assert(sizeof(spmv_c_bsr) == sizeof(BSRMatrix) && sizeof(BSRMatrix) == 80, "BSRMatrix layout");
+static_assert(offsetof(spmv_c_bsr, num_blocks) == offsetof(BSRMatrix, num_blocks) &&
+              offsetof(spmv_c_bsr, values) == offsetof(BSRMatrix, values) &&
+              offsetof(spmv_c_bsr, block_row_ptrs) == offsetof(BSRMatrix, block_row_ptrs) &&
+              offsetof(spmv_c_bsr, d_values) == offsetof(BSRMatrix, d_values) &&
+              offsetof(spmv_c_bsr, d_block_row_ptrs) == offsetof(BSRMatrix, d_block_row_ptrs) &&
+              offsetof(spmv_c_bsr, owns_host_memory) == offsetof(BSRMatrix, owns_host_memory) &&
+              offsetof(spmv_c_bsr, owns_device_memory) == offsetof(BSRMatrix, owns_device_memory), "BSRMatrix layout");
+static_assert(sizeof(spmv_c_bsr_build_result) == sizeof(BsrBuildResult) && sizeof(BsrBuildResult) == 32, "BsrBuildResult layout");
+static_assert(offsetof(spmv_c_bsr_build_result, error_code) == offsetof(BsrBuildResult, error_code) &&
+              offsetof(spmv_c_bsr_build_result, num_blocks) == offsetof(BsrBuildResult, num_blocks) &&
+              offsetof(spmv_c_bsr_build_result, fill) == offsetof(BsrBuildResult, fill) &&
+              offsetof(spmv_c_bsr_build_result, max_block_row) == offsetof(BsrBuildResult, max_block_row) &&
+              offsetof(spmv_c_bsr_build_result, lanes) == offsetof(BsrBuildResult, lanes) &&
+              offsetof(spmv_c_bsr_build_result, launches) == offsetof(BsrBuildResult, launches) &&
+              offsetof(spmv_c_bsr_build_result, symbolic_ms) == offsetof(BsrBuildResult, symbolic_ms) &&
+              offsetof(spmv_c_bsr_build_result, numeric_ms) == offsetof(BsrBuildResult, numeric_ms), "BsrBuildResult layout");
 static_assert(offsetof(spmv_c_ell, d_col_indices) == offsetof(ELLMatrix, d_col_indices), "ELLMatrix layout");
 static_assert(offsetof(spmv_c_ell, owns_host_memory) == offsetof(ELLMatrix, owns_host_memory), "ELLMatrix layout");
 static_assert(sizeof(spmv_c_config) == sizeof(SpMVConfig) && sizeof(SpMVConfig) == 12, "SpMVConfig layout");
@@ -211,6 +229,8 @@ inline AMGHierarchy* cxx(spmv_c_amg* h) { return reinterpret_cast<AMGHierarchy*>
 inline const AMGHierarchy* cxx(const spmv_c_amg* h) { return reinterpret_cast<const AMGHierarchy*>(h); }
 inline CSRMatrix* cxx(spmv_c_csr* m) { return reinterpret_cast<CSRMatrix*>(m); }
 inline const CSRMatrix* cxx(const spmv_c_csr* m) { return reinterpret_cast<const CSRMatrix*>(m); }
+inline BSRMatrix* cxx(spmv_c_bsr* m) { return reinterpret_cast<BSRMatrix*>(m); }
+inline const BSRMatrix* cxx(const spmv_c_bsr* m) { return reinterpret_cast<const BSRMatrix*>(m); }
 inline ELLMatrix* cxx(spmv_c_ell* m) { return reinterpret_cast<ELLMatrix*>(m); }
 inline const ELLMatrix* cxx(const spmv_c_ell* m) { return reinterpret_cast<const ELLMatrix*>(m); }
 inline const SpMVConfig* cxx(const spmv_c_config* c) { return reinterpret_cast<const SpMVConfig*>(c); }
@@ -1007,6 +1027,65 @@ float spmv_c_get_gpu_peak_bandwidth(void) { return get_gpu_peak_bandwidth(); }
 int spmv_c_compute_bandwidth_csr_multi(const spmv_c_csr* A, int k, float elapsed_ms, spmv_c_bandwidth* out) {
     if (!out) return kInvalidArgument;
     const BandwidthMetrics m = compute_bandwidth_csr_multi(cxx(A), k, elapsed_ms);
+    std::memcpy(out, &m, sizeof(m));
+    return 0;
+}
+
+// ---- block CSR ----
+spmv_c_bsr* spmv_c_bsr_create(int rows, int cols, int block_dim, int num_blocks) {
+    return reinterpret_cast<spmv_c_bsr*>(bsr_create(rows, cols, block_dim, num_blocks));
+}
+void spmv_c_bsr_destroy(spmv_c_bsr* mat) { bsr_destroy(cxx(mat)); }
+int spmv_c_bsr_to_gpu(spmv_c_bsr* mat) { return bsr_to_gpu(cxx(mat)); }
+int spmv_c_bsr_from_gpu(spmv_c_bsr* mat) { return bsr_from_gpu(cxx(mat)); }
+void spmv_c_bsr_free_gpu(spmv_c_bsr* mat) { bsr_free_gpu(cxx(mat)); }
+void spmv_c_bsr_invalidate_gpu_cache(const spmv_c_bsr* mat) { bsr_invalidate_gpu_cache(cxx(mat)); }
+spmv_c_bsr* spmv_c_bsr_wrap_device(int rows, int cols, int block_dim, int num_blocks, const int32_t* d_block_row_ptrs,
+                                   const int32_t* d_block_cols, const float* d_values) {
+    return reinterpret_cast<spmv_c_bsr*>(bsr_wrap_device(rows, cols, block_dim, num_blocks, d_block_row_ptrs,
+                                                         d_block_cols, d_values));
+}
+int spmv_c_bsr_from_csr_cpu(spmv_c_bsr* B, const spmv_c_csr* A, int block_dim) {
+    return bsr_from_csr_cpu(cxx(B), cxx(A), block_dim);
+}
+int spmv_c_bsr_from_csr_gpu(spmv_c_bsr* B, const spmv_c_csr* A, int block_dim, spmv_c_bsr_build_result* out) {
+    BsrBuildResult r;
+    const int status = bsr_from_csr_gpu(cxx(B), cxx(A), block_dim, &r);
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return status;
+}
+int spmv_c_bsr_from_csr_numeric(spmv_c_bsr* B, const spmv_c_csr* A, spmv_c_bsr_build_result* out) {
+    BsrBuildResult r;
+    const int status = bsr_from_csr_numeric(cxx(B), cxx(A), &r);
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return status;
+}
+int spmv_c_csr_block_count_gpu(const spmv_c_csr* A, int block_dim, int64_t* blocks) {
+    long long count = 0;
+    const int status = csr_block_count_gpu(cxx(A), block_dim, blocks ? &count : nullptr);
+    if (status == 0) *blocks = count;
+    return status;
+}
+int spmv_c_bsr_to_csr_gpu(spmv_c_csr* A, const spmv_c_bsr* B, int keep_zeros) {
+    return bsr_to_csr_gpu(cxx(A), cxx(B), keep_zeros);
+}
+int spmv_c_bsr_to_csr_cpu(spmv_c_csr* A, const spmv_c_bsr* B, int keep_zeros) {
+    return bsr_to_csr_cpu(cxx(A), cxx(B), keep_zeros);
+}
+void spmv_c_cpu_bsr(const spmv_c_bsr* A, const float* x, float* y) { spmv_cpu_bsr(cxx(A), x, y); }
+int spmv_c_spmv_bsr(const spmv_c_bsr* A, const float* d_x, float* d_y, const spmv_c_config* config, int vec_size,
+                    spmv_c_result* out) {
+    const SpMVResult r = spmv_bsr(cxx(A), d_x, d_y, cxx(config), vec_size);
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
+}
+int spmv_c_spmv_bsr_async(const spmv_c_bsr* A, const float* d_x, float* d_y, const spmv_c_config* config,
+                          int vec_size, void* hip_stream) {
+    return spmv_bsr_async(cxx(A), d_x, d_y, cxx(config), vec_size, as_stream(hip_stream));
+}
+int spmv_c_compute_bandwidth_bsr(const spmv_c_bsr* A, float elapsed_ms, spmv_c_bandwidth* out) {
+    if (!out) return kInvalidArgument;
+    const BandwidthMetrics m = compute_bandwidth_bsr(cxx(A), elapsed_ms);
     std::memcpy(out, &m, sizeof(m));
     return 0;
 }

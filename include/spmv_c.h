@@ -796,6 +796,68 @@ int spmv_c_csr_diagonal_cpu(const spmv_c_csr* A, float* diag);
 int spmv_c_csr_diag_matrix_gpu(spmv_c_csr* D, int n, const float* d_diag);
 int spmv_c_csr_diag_matrix_cpu(spmv_c_csr* D, int n, const float* diag);
 
+/* ---- block CSR (BSR): container, CSR <-> BSR, SpMV (extension; include/spmv/bsr_matrix.h, include/spmv/bsr.h) ---- */
+/* 80 bytes; square block_dim x block_dim blocks (2, 3, 4 or 8), row-major inside a block, block columns strictly
+ * ascending inside a block row; positions outside the matrix hold +0.0f */
+typedef struct spmv_c_bsr {
+    int32_t  num_rows;
+    int32_t  num_cols;
+    int32_t  block_dim;
+    int32_t  num_block_rows;
+    int32_t  num_block_cols;
+    int32_t  num_blocks;
+    float*   values;            /* [num_blocks * block_dim * block_dim] */
+    int32_t* block_cols;        /* [num_blocks] */
+    int32_t* block_row_ptrs;    /* [num_block_rows + 1] */
+    float*   d_values;
+    int32_t* d_block_cols;
+    int32_t* d_block_row_ptrs;
+    uint8_t  owns_host_memory;
+    uint8_t  owns_device_memory;
+} spmv_c_bsr;
+
+/* 32 bytes; fill = nnz / positions of the blocks inside the matrix; launches = kernel launches of the call */
+typedef struct spmv_c_bsr_build_result {
+    int32_t error_code;
+    int32_t num_blocks;
+    float   fill;
+    int32_t max_block_row;
+    int32_t lanes;          /* lanes that share one block row */
+    int32_t launches;
+    float   symbolic_ms;
+    float   numeric_ms;
+} spmv_c_bsr_build_result;
+
+/* NULL on a negative size or an unsupported block_dim */
+spmv_c_bsr* spmv_c_bsr_create(int rows, int cols, int block_dim, int num_blocks);
+void spmv_c_bsr_destroy(spmv_c_bsr* mat);
+int spmv_c_bsr_to_gpu(spmv_c_bsr* mat);
+int spmv_c_bsr_from_gpu(spmv_c_bsr* mat);
+void spmv_c_bsr_free_gpu(spmv_c_bsr* mat);
+void spmv_c_bsr_invalidate_gpu_cache(const spmv_c_bsr* mat);
+/* a matrix header over device arrays the caller owns (no host arrays) */
+spmv_c_bsr* spmv_c_bsr_wrap_device(int rows, int cols, int block_dim, int num_blocks, const int32_t* d_block_row_ptrs,
+                                   const int32_t* d_block_cols, const float* d_values);
+/* CSR (strictly ascending rows) to BSR: the host twin is the definition, the device build has its ints and bits at
+ * every lane count; B owns new arrays afterwards.  Rule and checks as bsr_from_csr_gpu in include/spmv/bsr.h.  The
+ * return value equals out->error_code (out may be NULL). */
+int spmv_c_bsr_from_csr_cpu(spmv_c_bsr* B, const spmv_c_csr* A, int block_dim);
+int spmv_c_bsr_from_csr_gpu(spmv_c_bsr* B, const spmv_c_csr* A, int block_dim, spmv_c_bsr_build_result* out);
+/* only B's device values again from a new A over the same pattern; an entry without a block is INVALID_FORMAT */
+int spmv_c_bsr_from_csr_numeric(spmv_c_bsr* B, const spmv_c_csr* A, spmv_c_bsr_build_result* out);
+/* the counting pass alone: *blocks = the blocks the build would store */
+int spmv_c_csr_block_count_gpu(const spmv_c_csr* A, int block_dim, int64_t* blocks);
+/* BSR back to CSR with sorted rows; keep_zeros == 0 drops the positions that hold +-0.0f */
+int spmv_c_bsr_to_csr_gpu(spmv_c_csr* A, const spmv_c_bsr* B, int keep_zeros);
+int spmv_c_bsr_to_csr_cpu(spmv_c_csr* A, const spmv_c_bsr* B, int keep_zeros);
+void spmv_c_cpu_bsr(const spmv_c_bsr* A, const float* x, float* y);        /* spmv_cpu_bsr */
+/* y = A x; SCALAR_CSR / ELL_KERNEL / NULL config: spmv_c_cpu_bsr's bits; VECTOR_CSR / MERGE_PATH: the lane-group kernel */
+int spmv_c_spmv_bsr(const spmv_c_bsr* A, const float* d_x, float* d_y, const spmv_c_config* config, int vec_size,
+                    spmv_c_result* out);
+int spmv_c_spmv_bsr_async(const spmv_c_bsr* A, const float* d_x, float* d_y, const spmv_c_config* config,
+                          int vec_size, void* hip_stream);
+int spmv_c_compute_bandwidth_bsr(const spmv_c_bsr* A, float elapsed_ms, spmv_c_bandwidth* out);
+
 /* ---- bandwidth model: reference include/spmv/bandwidth.h:21-27 ---- */
 int spmv_c_compute_bandwidth_csr(const spmv_c_csr* A, float elapsed_ms, spmv_c_bandwidth* out);
 int spmv_c_compute_bandwidth_ell(const spmv_c_ell* A, float elapsed_ms, spmv_c_bandwidth* out);
