@@ -560,6 +560,11 @@ _SIGNATURES = {
                                 POINTER(SpMVResult)]),
     "spmv_c_spmv_bsr_async": (c_int, [POINTER(BSRMatrix), c_void_p, c_void_p, POINTER(SpMVConfig), c_int, c_void_p]),
     "spmv_c_compute_bandwidth_bsr": (c_int, [POINTER(BSRMatrix), c_float, POINTER(BandwidthMetrics)]),
+    "spmv_c_bsr_diag_inverse_cpu": (c_int, [POINTER(BSRMatrix), c_void_p]),
+    "spmv_c_bsr_diag_inverse_gpu": (c_int, [POINTER(BSRMatrix), c_void_p]),
+    "spmv_c_bsr_diag_apply_cpu": (None, [POINTER(BSRMatrix), c_void_p, c_void_p, c_void_p]),
+    "spmv_c_bsr_diag_apply": (c_int, [POINTER(BSRMatrix), c_void_p, c_void_p, c_void_p]),
+    "spmv_c_cg_solve_bsr": (c_int, [POINTER(BSRMatrix), c_void_p, c_void_p, POINTER(CGConfig), POINTER(CGResult)]),
     "spmv_c_csr_scale_gpu": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, c_void_p]),
     "spmv_c_csr_scale_cpu": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, c_void_p]),
     "spmv_c_csr_diagonal_gpu": (c_int, [POINTER(CSRMatrix), c_void_p]),
@@ -1857,6 +1862,42 @@ def spmv_bsr_async(A, d_x, d_y, config=None, vec_size=-1, stream=None) -> int:
 def compute_bandwidth_bsr(A, elapsed_ms) -> BandwidthMetrics:
     out = BandwidthMetrics()
     lib().spmv_c_compute_bandwidth_bsr(A, float(elapsed_ms), byref(out))
+    return out
+
+
+def bsr_diag_inverse_cpu(A):
+    """(status, inv): the fp32 inverses of A's diagonal blocks on host arrays, num_block_rows * b * b floats (bsr.h
+    bsr_diag_inverse_cpu: the definition of the block-Jacobi factor)."""
+    c = A.contents
+    count = c.num_block_rows * c.block_dim * c.block_dim
+    inv = np.zeros(max(count, 1), np.float32)
+    status = lib().spmv_c_bsr_diag_inverse_cpu(A, _np_ptr(inv))
+    return status, inv[:count]
+
+
+def bsr_diag_inverse_gpu(A, d_inv) -> int:
+    """The same bits into a device array (bsr.h bsr_diag_inverse_gpu)."""
+    return lib().spmv_c_bsr_diag_inverse_gpu(A, _dev(d_inv))
+
+
+def bsr_diag_apply_cpu(A, inv, r) -> np.ndarray:
+    """z = D^-1 r by the ordered sum on host arrays (bsr.h bsr_diag_apply_cpu)."""
+    inv = np.ascontiguousarray(inv, np.float32)
+    r = np.ascontiguousarray(r, np.float32)
+    z = np.zeros(max(A.contents.num_rows, 1), np.float32)
+    lib().spmv_c_bsr_diag_apply_cpu(A, _np_ptr(inv), _np_ptr(r), _np_ptr(z))
+    return z[:A.contents.num_rows]
+
+
+def bsr_diag_apply(A, d_inv, d_r, d_z) -> int:
+    """The same on device arrays (bsr.h bsr_diag_apply)."""
+    return lib().spmv_c_bsr_diag_apply(A, _dev(d_inv), _dev(d_r), _dev(d_z))
+
+
+def cg_solve_bsr(A, d_b, d_x, config=None) -> CGResult:
+    """CG on a BSR matrix with preconditioner 0 NONE, 1 JACOBI or 2 BLOCK_JACOBI (include/spmv/cg.h cg_solve_bsr)."""
+    out = CGResult()
+    lib().spmv_c_cg_solve_bsr(A, _dev(d_b), _dev(d_x), byref(config) if config is not None else None, byref(out))
     return out
 
 

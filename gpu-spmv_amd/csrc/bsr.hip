@@ -23,6 +23,7 @@
 // multiple of four and the value array is 16-byte aligned; B = 3 and misaligned views take dword loads), holds B
 // accumulators, and group_sum folds each of them.  At B*B flops per 4 B of index the kernel stays far below the
 // machine balance, so no MFMA (the argument at the head of kernels.hip).
+#include "bsr_device.h"
 #include "bsr_impl.h"
 #include "device_common.h"
 #include "internal.h"
@@ -45,17 +46,6 @@ using dev::group_sum;
 using dev::kBlock;
 
 constexpr int kWaves = kBlock / 64;
-
-// Calls launch(std::integral_constant<int, B>{}) for a supported block size (bsr_block_dim_supported).
-template <class Launch>
-hipError_t with_block_dim(int block_dim, Launch&& launch) {
-    switch (block_dim) {
-        case 2:  return launch(std::integral_constant<int, 2>{});
-        case 3:  return launch(std::integral_constant<int, 3>{});
-        case 4:  return launch(std::integral_constant<int, 4>{});
-        default: return launch(std::integral_constant<int, 8>{});
-    }
-}
 
 // the bits of this lane's group in a wavefront ballot
 template <int LANES>
@@ -352,82 +342,16 @@ __global__ __launch_bounds__(kBlock) void bsr_rows_kernel(const int* __restrict_
     }
 }
 
-// the B*B values of one block: 16-byte loads (WIDE: B*B % 4 == 0 and a 16-byte aligned array), else dwords
-template <int B, bool WIDE>
-__device__ __forceinline__ void load_block(const float* __restrict__ block, float (&v)[B * B]) {
-    if constexpr (WIDE) {
-        const f32x4* q = reinterpret_cast<const f32x4*>(block);
-#pragma unroll
-        for (int k = 0; k < B * B / 4; ++k) {
-            const f32x4 t = q[k];
-            v[4 * k] = t[0];
-            v[4 * k + 1] = t[1];
-            v[4 * k + 2] = t[2];
-            v[4 * k + 3] = t[3];
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < B * B; ++k) v[k] = block[k];
-    }
-}
-
-// A group of LANES lanes per block row; lane l takes blocks l, l + LANES, ... of it.
+// A group of LANES lanes per block row (for_each_block_row_dot, bsr_device.h).
 template <int B, int LANES, bool WIDE>
 __global__ __launch_bounds__(kBlock) void bsr_lanes_kernel(const int* __restrict__ brp, const int* __restrict__ bc,
                                                            const float* __restrict__ bv, const float* __restrict__ x,
                                                            float* __restrict__ y, int m, int n, int block_rows) {
-    constexpr int kRowsPerBlock = kBlock / LANES;
-    const int lane = threadIdx.x % LANES;
-    const int slot = threadIdx.x / LANES;
-    for (long long first = static_cast<long long>(blockIdx.x) * kRowsPerBlock; first < block_rows;
-         first += static_cast<long long>(gridDim.x) * kRowsPerBlock) {
-        const long long I = first + slot;
-        float acc[B];
-#pragma unroll
-        for (int r = 0; r < B; ++r) acc[r] = 0.0f;
-        if (I < block_rows) {
-            const int end = brp[I + 1];
-            for (int p = brp[I] + lane; p < end; p += LANES) {
-                const int c0 = bc[p] * B;
-                float v[B * B];
-                load_block<B, WIDE>(bv + static_cast<long long>(p) * (B * B), v);
-                if (c0 + B <= n) {
-                    float xv[B];
-#pragma unroll
-                    for (int c = 0; c < B; ++c) xv[c] = x[c0 + c];
-#pragma unroll
-                    for (int r = 0; r < B; ++r) {
-#pragma unroll
-                        for (int c = 0; c < B; ++c) acc[r] = __builtin_fmaf(v[r * B + c], xv[c], acc[r]);
-                    }
-                } else {                         // the last block column of a matrix whose width is no multiple of B:
-#pragma unroll                                   // positions past num_cols are skipped by select, x is not read there
-                    for (int c = 0; c < B; ++c) {
-                        const bool inside = c0 + c < n;
-                        const float xc = inside ? x[c0 + c] : 0.0f;
-#pragma unroll
-                        for (int r = 0; r < B; ++r) acc[r] = inside ? __builtin_fmaf(v[r * B + c], xc, acc[r]) : acc[r];
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < B; ++r) acc[r] = group_sum<LANES>(acc[r]);
-        if (I < block_rows) {
-#pragma unroll
-            for (int r = 0; r < B; ++r) {        // lanes 0 .. B-1 store (a group narrower than B: lane r % LANES)
-                const long long row = I * B + r;
-                if (r % LANES == lane && row < m) y[row] = acc[r];
-            }
-        }
-    }
+    for_each_block_row_dot<B, LANES, WIDE>(brp, bc, bv, x, m, n, block_rows,
+                                           [&](long long row, float sum) { y[row] = sum; });
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------
-int lanes_for(long long items, int block_rows) {
-    if (int f = forced_lanes("bsr_lanes")) return f;
-    return pick_lanes_per_row(static_cast<float>(items) / static_cast<float>(std::max(block_rows, 1)));
-}
 
 template <int MODE>
 hipError_t launch_symbolic(int block_dim, int lanes, int grid, const ConvArgs& args, hipStream_t s) {
@@ -679,8 +603,6 @@ int to_csr(CSRMatrix* A, const BSRMatrix* B, int keep_zeros, hipStream_t s) {
 }
 
 // ---- SpMV launchers ----
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 hipError_t launch_rows(const BSRMatrix* A, const float* d_x, float* d_y, hipStream_t s) {
     return with_block_dim(A->block_dim, [&](auto Bc) {
         bsr_rows_kernel<decltype(Bc)::value><<<capped_grid(A->num_rows, kBlock), kBlock, 0, s>>>(
@@ -713,9 +635,7 @@ bool block_size_ok(const SpMVConfig* config) { return config->block_size > 0 && 
 hipError_t enqueue(const BSRMatrix* A, const float* d_x, float* d_y, const SpMVConfig* config, hipStream_t s) {
     if (A->num_blocks == 0) return launch_fill_zero(d_y, A->num_rows, s);
     if (config->kernel_type == SpMVConfig::VECTOR_CSR || config->kernel_type == SpMVConfig::MERGE_PATH) {
-        // a lane takes a whole block per step: the smallest group with 2 * LANES >= the mean blocks per block row, i.e.
-        // about two steps per block row, measured best or within 6 % of it on every stencil of §4.29's table
-        return launch_lanes(A, d_x, d_y, lanes_for(2LL * A->num_blocks, A->num_block_rows), s);
+        return launch_lanes(A, d_x, d_y, product_lanes(A), s);
     }
     return launch_rows(A, d_x, d_y, s);
 }

@@ -1089,6 +1089,20 @@ int spmv_c_compute_bandwidth_bsr(const spmv_c_bsr* A, float elapsed_ms, spmv_c_b
     std::memcpy(out, &m, sizeof(m));
     return 0;
 }
+int spmv_c_bsr_diag_inverse_cpu(const spmv_c_bsr* A, float* inv) { return bsr_diag_inverse_cpu(cxx(A), inv); }
+int spmv_c_bsr_diag_inverse_gpu(const spmv_c_bsr* A, float* d_inv) { return bsr_diag_inverse_gpu(cxx(A), d_inv); }
+void spmv_c_bsr_diag_apply_cpu(const spmv_c_bsr* A, const float* inv, const float* r, float* z) {
+    bsr_diag_apply_cpu(cxx(A), inv, r, z);
+}
+int spmv_c_bsr_diag_apply(const spmv_c_bsr* A, const float* d_inv, const float* d_r, float* d_z) {
+    return bsr_diag_apply(cxx(A), d_inv, d_r, d_z);
+}
+int spmv_c_cg_solve_bsr(const spmv_c_bsr* A, const float* d_b, float* d_x, const spmv_c_cg_config* config,
+                        spmv_c_cg_result* out) {
+    const CGResult r = cg_solve_bsr(cxx(A), d_b, d_x, reinterpret_cast<const CGConfig*>(config));
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
+}
 
 // ---- PageRank ----
 int spmv_c_pagerank(const spmv_c_csr* adj, const spmv_c_pagerank_config* config,

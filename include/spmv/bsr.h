@@ -1,6 +1,7 @@
 // spmv/bsr.h — block CSR (BSR): conversion from and to CSR on the device and on the host, bit for bit the same, a
 // values-only refill, and y = A x on a BSRMatrix (kernels in gpu-spmv_amd/csrc/bsr.hip, host twins and argument checks
-// in bsr_host.cpp; when to convert is in INTEGRATION.md).
+// in bsr_host.cpp; when to convert is in INTEGRATION.md), and the inverses of the diagonal blocks
+// with their apply, the block-Jacobi preconditioner of cg_solve_bsr (cg_bsr.hip, bsr_diag_host.cpp).
 //
 // Everything is fp32 values and int32 indices; the container and its layout are in spmv/bsr_matrix.h.
 //
@@ -126,6 +127,36 @@ int        spmv_bsr_async(const BSRMatrix* A, const float* d_x, float* d_y, cons
                           hipStream_t stream);
 
 // (the byte model of the GB/s figure is compute_bandwidth_bsr in spmv/bandwidth.h)
+
+// ---- the diagonal blocks: block-Jacobi (the solver that uses them is cg_solve_bsr in spmv/cg.h) ----
+// inv (num_block_rows * b * b floats; block I row-major) = fl32(D_I^-1), D_I the stored block (I, I) of a square A, of
+// which only the lower triangle (r >= c) is read.  bsr_diag_inverse_cpu (host arrays) is the definition, in fp64 with
+// every product, sum, division and root rounded on its own (no fused multiply-add):
+//   Cholesky D = L L^T row by row: w = d_pq - sum_{k<q} l_pk l_qk, k ascending, each product subtracted in turn;
+//       l_pp = sqrt(w), l_pq = w / l_qq
+//   W = L^-1 by forward substitution: w_jj = 1 / l_jj; w_ij = -(sum_{k=j..i-1} l_ik w_kj) / l_ii, k ascending from +0
+//   D^-1_ij = sum_{k >= max(i,j)} w_ki w_kj, k ascending from +0, then ONE rounding to fp32; computed for i >= j and
+//       stored at (i,j) and (j,i): the result is symmetric bit for bit
+// When num_rows is no multiple of b the last block is its leading (num_rows - I*b)-square part; the other rows and
+// columns of its inverse are +0.0f.
+// Checks, in this order: null A / inv -> INVALID_ARGUMENT; A not square -> INVALID_DIMENSION; a bad shape or missing
+// arrays (host arrays for _cpu, device arrays for _gpu) -> INVALID_FORMAT; a block row without a stored diagonal block,
+// or a pivot w that is not > 0 or not finite -> INVALID_ARGUMENT, with inv unspecified.  Block columns must be strictly
+// ascending inside a block row (the container's rule): the diagonal block is found by a binary search.
+int bsr_diag_inverse_cpu(const BSRMatrix* A, float* inv);
+// The same bits on the device on every run: one launch, one lane per block row, the block in registers.  d_inv is a
+// device array (any 4-byte offset).  The last check is made on the device, in one flag word and one read-back.  Runs
+// on the library stream and returns after completion.
+int bsr_diag_inverse_gpu(const BSRMatrix* A, float* d_inv);
+
+// z = D^-1 r block by block.  bsr_diag_apply_cpu is the definition of the ordered sum: for row i = I*b + k,
+//     s = +0.0f;  for c = 0 .. b-1 with I*b + c < num_rows:  s = fl(s + fl(inv[I][k][c] * r[I*b + c]))
+// multiply and add rounded separately.  Only A's shape is read.  Nothing is checked on the host path.
+void bsr_diag_apply_cpu(const BSRMatrix* A, const float* inv, const float* r, float* z);
+// The device path, bit for bit the same: one thread per scalar row, d_r and d_z distinct arrays of num_rows floats.
+// Checks: null A / d_inv / d_r / d_z -> INVALID_ARGUMENT; A not square -> INVALID_DIMENSION; a bad shape ->
+// INVALID_FORMAT.  Runs on the library stream and returns after completion.
+int  bsr_diag_apply(const BSRMatrix* A, const float* d_inv, const float* d_r, float* d_z);
 
 } // namespace spmv
 

@@ -7,13 +7,14 @@
 #ifndef SPMV_CG_H
 #define SPMV_CG_H
 
+#include "bsr_matrix.h"
 #include "common.h"
 #include "csr_matrix.h"
 
 namespace spmv {
 
 struct CGConfig {
-    enum Preconditioner { NONE = 0, JACOBI = 1 };
+    enum Preconditioner { NONE = 0, JACOBI = 1, BLOCK_JACOBI = 2 };   // BLOCK_JACOBI: cg_solve_bsr only
     float tolerance;       // stop when ||r_k||_2 <= tolerance * ||b||_2 (recurrence residual)
     int   max_iterations;
     int   preconditioner;  // Preconditioner
@@ -167,6 +168,27 @@ CGResult cg_solve_amg(const CSRMatrix* A, const AMGHierarchy* H, const float* d_
 // is not positive definite surfaces as a breakdown, x at the last good iterate, as with cg_solve_amg.
 CGResult cg_solve_fsai(const CSRMatrix* A, const CSRMatrix* G, const CSRMatrix* GT, const float* d_b, float* d_x,
                        const CGConfig* config = nullptr);
+
+// cg_solve on a block CSR matrix (spmv/bsr.h): the same iteration, numerics, stop rules, breakdown
+// rule, ||b|| == 0 rule and checks, in cg_solve's order, with "nothing written to d_x when one fails".  The
+// preconditioner is NONE, JACOBI or BLOCK_JACOBI:
+//   JACOBI        dinv = 1 / the (k,k) entry of the stored diagonal block of row I*b + k; a missing diagonal block or an
+//                 entry that is not > 0 -> INVALID_ARGUMENT (on the device, in the one setup read-back)
+//   BLOCK_JACOBI  M = the block diagonal of A: z = D^-1 r by bsr_diag_apply's ordered sum with the inverses of
+//                 bsr_diag_inverse_gpu (spmv/bsr.h), built in one setup launch; a missing diagonal block or a pivot that
+//                 is not > 0 or not finite -> INVALID_ARGUMENT, in the same read-back
+// engine must be -1 or 0: there is no tiled BSR engine, engine = 1 -> INVALID_ARGUMENT (cg_solve_multi's rule).
+// cg_solve, cg_solve_multi and every other entry point keep rejecting BLOCK_JACOBI.
+//
+// q = A p is the lane-group product of spmv_bsr (VECTOR_CSR), its lane count (SPMV_DEBUG=bsr_lanes=N forces one) and
+// its bits, fused with the partials of p.q.  z is a stored vector; per step THREE launches whatever b and whatever the
+// preconditioner: product + p.q; the update of x and r with z = M^-1 r and the partials of r.z and r.r in one kernel
+// (one thread per scalar row, the block's new r exchanged through LDS); the direction step.  Setup takes up to seven:
+// the inverses or the diagonal, r0 with r.r and b.b, z0, r.z, the copy p0 = z0, the state.  A solve is bitwise
+// reproducible from run to run at a fixed lane count.  The workspace is r, p, q, z and n floats (JACOBI) or
+// num_block_rows * b * b floats (BLOCK_JACOBI).  A is only read: no cache on it is built, used or dropped.  Runs on
+// spmv_get_stream() and returns after the solve; call it outside a graph capture.
+CGResult cg_solve_bsr(const BSRMatrix* A, const float* d_b, float* d_x, const CGConfig* config = nullptr);
 
 } // namespace spmv
 

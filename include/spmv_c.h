@@ -857,6 +857,16 @@ int spmv_c_spmv_bsr(const spmv_c_bsr* A, const float* d_x, float* d_y, const spm
 int spmv_c_spmv_bsr_async(const spmv_c_bsr* A, const float* d_x, float* d_y, const spmv_c_config* config,
                           int vec_size, void* hip_stream);
 int spmv_c_compute_bandwidth_bsr(const spmv_c_bsr* A, float elapsed_ms, spmv_c_bandwidth* out);
+/* the inverses of the diagonal blocks (num_block_rows * b * b floats, block I row-major) and z = D^-1 r by the ordered
+ * sum; host twins and device paths give the same bits.  Rules and checks as in include/spmv/bsr.h. */
+int spmv_c_bsr_diag_inverse_cpu(const spmv_c_bsr* A, float* inv);
+int spmv_c_bsr_diag_inverse_gpu(const spmv_c_bsr* A, float* d_inv);
+void spmv_c_bsr_diag_apply_cpu(const spmv_c_bsr* A, const float* inv, const float* r, float* z);
+int spmv_c_bsr_diag_apply(const spmv_c_bsr* A, const float* d_inv, const float* d_r, float* d_z);
+/* CG on a BSR matrix; config->preconditioner 0 NONE, 1 JACOBI, 2 BLOCK_JACOBI (this entry point only); engine -1 or 0.
+ * Checks and numerics as cg_solve_bsr in include/spmv/cg.h.  Returns out->error_code (out may be NULL). */
+int spmv_c_cg_solve_bsr(const spmv_c_bsr* A, const float* d_b, float* d_x, const spmv_c_cg_config* config,
+                        spmv_c_cg_result* out);
 
 /* ---- bandwidth model: reference include/spmv/bandwidth.h:21-27 ---- */
 int spmv_c_compute_bandwidth_csr(const spmv_c_csr* A, float elapsed_ms, spmv_c_bandwidth* out);
