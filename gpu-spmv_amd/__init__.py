@@ -565,6 +565,16 @@ _SIGNATURES = {
     "spmv_c_bsr_diag_apply_cpu": (None, [POINTER(BSRMatrix), c_void_p, c_void_p, c_void_p]),
     "spmv_c_bsr_diag_apply": (c_int, [POINTER(BSRMatrix), c_void_p, c_void_p, c_void_p]),
     "spmv_c_cg_solve_bsr": (c_int, [POINTER(BSRMatrix), c_void_p, c_void_p, POINTER(CGConfig), POINTER(CGResult)]),
+    "spmv_c_bsr_ic0_cpu": (c_int, [POINTER(BSRMatrix), c_void_p, POINTER(c_int32)]),
+    "spmv_c_bsr_ic0": (c_int, [POINTER(BSRMatrix), c_void_p, POINTER(IC0Result)]),
+    "spmv_c_bsr_ic0_async": (c_int, [POINTER(BSRMatrix), c_void_p, c_void_p]),
+    "spmv_c_sptrsv_cpu_bsr": (c_int, [POINTER(BSRMatrix), c_void_p, c_void_p, POINTER(SpTRSVConfig)]),
+    "spmv_c_sptrsv_bsr": (c_int, [POINTER(BSRMatrix), c_void_p, c_void_p, POINTER(SpTRSVConfig),
+                          POINTER(SpTRSVResult)]),
+    "spmv_c_sptrsv_bsr_async": (c_int, [POINTER(BSRMatrix), c_void_p, c_void_p, POINTER(SpTRSVConfig), c_void_p]),
+    "spmv_c_sptrsv_analyze_bsr": (c_int, [POINTER(BSRMatrix), c_int, POINTER(SpTRSVResult)]),
+    "spmv_c_cg_solve_bsr_ic": (c_int, [POINTER(BSRMatrix), POINTER(BSRMatrix), c_void_p, c_void_p, POINTER(CGConfig),
+                               POINTER(CGResult)]),
     "spmv_c_csr_scale_gpu": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, c_void_p]),
     "spmv_c_csr_scale_cpu": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, c_void_p]),
     "spmv_c_csr_diagonal_gpu": (c_int, [POINTER(CSRMatrix), c_void_p]),
@@ -1898,6 +1908,69 @@ def cg_solve_bsr(A, d_b, d_x, config=None) -> CGResult:
     """CG on a BSR matrix with preconditioner 0 NONE, 1 JACOBI or 2 BLOCK_JACOBI (include/spmv/cg.h cg_solve_bsr)."""
     out = CGResult()
     lib().spmv_c_cg_solve_bsr(A, _dev(d_b), _dev(d_x), byref(config) if config is not None else None, byref(out))
+    return out
+
+
+# ---- block IC(0) and the block triangular solves (include/spmv/bsr_factor.h) ---------------------------------
+def bsr_ic0_cpu(A):
+    """Block IC(0) on A's host arrays (bsr_factor.h bsr_ic0_cpu, the definition of the arithmetic): returns
+    (f_values, bad_pivot), f_values in the factor format of bsr_factor.h; raises ValueError with the library's error
+    string when the call is rejected."""
+    c = A.contents
+    f = np.zeros(max(c.num_blocks * c.block_dim * c.block_dim, 1), np.float32)
+    pivot = c_int32(-1)
+    status = lib().spmv_c_bsr_ic0_cpu(A, _np_ptr(f), byref(pivot))
+    if status != 0:
+        raise ValueError(spmv_error_string(status))
+    return f[:c.num_blocks * c.block_dim * c.block_dim], pivot.value
+
+
+def bsr_ic0(A, d_f_values) -> IC0Result:
+    """Block IC(0) of the square device BSR matrix A into d_f_values, num_blocks * b * b floats in A's block pattern
+    (bsr_factor.h bsr_ic0; may be A's own device values: in place).  lanes_per_row and bad_pivot count BLOCK rows.
+    bsr_wrap_device over A's structure arrays and d_f_values is the factor matrix of sptrsv_bsr and cg_solve_bsr_ic."""
+    out = IC0Result()
+    lib().spmv_c_bsr_ic0(A, _dev(d_f_values), byref(out))
+    return out
+
+
+def bsr_ic0_async(A, d_f_values, stream=None) -> int:
+    return lib().spmv_c_bsr_ic0_async(A, _dev(d_f_values), c_void_p(stream))
+
+
+def sptrsv_cpu_bsr(F, b, x=None, config=None):
+    """(status, x): T x = b on host arrays, T the config.uplo block triangle of F in the factor format (bsr_factor.h
+    sptrsv_cpu_bsr, the definition of the ordered solve).  x: the array solved into (b itself solves in place)."""
+    b = np.ascontiguousarray(b, np.float32) if x is not b else b
+    if x is None:
+        x = np.zeros(max(F.contents.num_rows, 1), np.float32)
+    status = lib().spmv_c_sptrsv_cpu_bsr(F, _np_ptr(b), _np_ptr(x), byref(config) if config is not None else None)
+    return status, x[:F.contents.num_rows]
+
+
+def sptrsv_bsr(F, d_b, d_x, config=None) -> SpTRSVResult:
+    """The block triangular solve on the device (bsr_factor.h sptrsv_bsr); d_b may be d_x (in place)."""
+    out = SpTRSVResult()
+    lib().spmv_c_sptrsv_bsr(F, _dev(d_b), _dev(d_x), byref(config) if config is not None else None, byref(out))
+    return out
+
+
+def sptrsv_bsr_async(F, d_b, d_x, config=None, stream=None) -> int:
+    return lib().spmv_c_sptrsv_bsr_async(F, _dev(d_b), _dev(d_x), byref(config) if config is not None else None,
+                                         c_void_p(stream))
+
+
+def sptrsv_analyze_bsr(A, uplo=0) -> SpTRSVResult:
+    """Builds and caches the level schedule of the `uplo` triangle of A's block pattern ahead of a timed call."""
+    out = SpTRSVResult()
+    lib().spmv_c_sptrsv_analyze_bsr(A, int(uplo), byref(out))
+    return out
+
+
+def cg_solve_bsr_ic(A, F, d_b, d_x, config=None) -> CGResult:
+    """CG on a BSR matrix preconditioned with the block IC(0) factor matrix F (include/spmv/cg.h cg_solve_bsr_ic)."""
+    out = CGResult()
+    lib().spmv_c_cg_solve_bsr_ic(A, F, _dev(d_b), _dev(d_x), byref(config) if config is not None else None, byref(out))
     return out
 
 

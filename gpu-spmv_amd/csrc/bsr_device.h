@@ -1,4 +1,5 @@
-// bsr_device.h — what the kernel files that walk a BSR matrix share (bsr.hip, cg_bsr.hip):
+// bsr_device.h — what the kernel files that walk a BSR matrix share (bsr.hip, cg_bsr.hip, bsr_tri.hip; DESIGN.md §4.29 -
+// §4.31):
 // the block-size dispatch, the lane rule of the lane-group product, the block load and the block-row walk with a
 // sink, which is to BSR what for_each_row_dot (device_common.h) is to CSR.  Internal: not installed under include/.
 #ifndef SPMV_AMD_BSR_DEVICE_H
@@ -59,6 +60,51 @@ __device__ __forceinline__ void load_block(const float* __restrict__ block, floa
     }
 }
 
+// One block row's part of the walk: lane `lane` of a group of LANES takes the blocks begin + lane, begin + lane + LANES,
+// ... of [begin, end) and adds their products with x into its B accumulators.  n is the number of columns: x is not read
+// at or past it.  FILTER (the triangular solves, bsr_tri.hip): only the blocks whose block column lies in [lo, hi) are
+// taken, the prefix or the suffix of a block row with ascending block columns.  ORDERED: product and sum rounded
+// separately (spmv_cpu_bsr's sum when LANES == 1), else fused.  x carries no __restrict__: a solve reads and writes it.
+template <int B, int LANES, bool WIDE, bool FILTER = false, bool ORDERED = false>
+__device__ __forceinline__ void block_row_partial_dot(const int* __restrict__ bc, const float* __restrict__ bv,
+                                                      const float* x, int n, int begin, int end, int lane, int lo,
+                                                      int hi, float (&acc)[B]) {
+    for (int p = begin + lane; p < end; p += LANES) {
+        const int J = bc[p];
+        if constexpr (FILTER) {
+            if (J < lo || J >= hi) continue;
+        }
+        const int c0 = J * B;
+        float v[B * B];
+        load_block<B, WIDE>(bv + static_cast<long long>(p) * (B * B), v);
+        if (c0 + B <= n) {
+            float xv[B];
+#pragma unroll
+            for (int c = 0; c < B; ++c) xv[c] = x[c0 + c];
+#pragma unroll
+            for (int r = 0; r < B; ++r) {
+#pragma unroll
+                for (int c = 0; c < B; ++c) {
+                    acc[r] = ORDERED ? __fadd_rn(acc[r], __fmul_rn(v[r * B + c], xv[c]))
+                                     : __builtin_fmaf(v[r * B + c], xv[c], acc[r]);
+                }
+            }
+        } else {                                 // the last block column of a matrix whose width is no multiple of B:
+#pragma unroll                                   // positions past num_cols are skipped by select, x is not read there
+            for (int c = 0; c < B; ++c) {
+                const bool inside = c0 + c < n;
+                const float xc = inside ? x[c0 + c] : 0.0f;
+#pragma unroll
+                for (int r = 0; r < B; ++r) {
+                    const float next = ORDERED ? __fadd_rn(acc[r], __fmul_rn(v[r * B + c], xc))
+                                               : __builtin_fmaf(v[r * B + c], xc, acc[r]);
+                    acc[r] = inside ? next : acc[r];
+                }
+            }
+        }
+    }
+}
+
 // The block-row sweep: a group of LANES lanes per block row, lane l takes blocks l, l + LANES, ... of it, holds B
 // accumulators, and group_sum folds each of them.  row_done(row, sum) is called for every scalar row < m with the row's
 // dot product with x, by lane r % LANES of the group for row I * B + r: lanes 0 .. B-1, or every lane in turn in a
@@ -77,32 +123,7 @@ __device__ __forceinline__ void for_each_block_row_dot(const int* __restrict__ b
         float acc[B];
 #pragma unroll
         for (int r = 0; r < B; ++r) acc[r] = 0.0f;
-        if (I < block_rows) {
-            const int end = brp[I + 1];
-            for (int p = brp[I] + lane; p < end; p += LANES) {
-                const int c0 = bc[p] * B;
-                float v[B * B];
-                load_block<B, WIDE>(bv + static_cast<long long>(p) * (B * B), v);
-                if (c0 + B <= n) {
-                    float xv[B];
-#pragma unroll
-                    for (int c = 0; c < B; ++c) xv[c] = x[c0 + c];
-#pragma unroll
-                    for (int r = 0; r < B; ++r) {
-#pragma unroll
-                        for (int c = 0; c < B; ++c) acc[r] = __builtin_fmaf(v[r * B + c], xv[c], acc[r]);
-                    }
-                } else {                         // the last block column of a matrix whose width is no multiple of B:
-#pragma unroll                                   // positions past num_cols are skipped by select, x is not read there
-                    for (int c = 0; c < B; ++c) {
-                        const bool inside = c0 + c < n;
-                        const float xc = inside ? x[c0 + c] : 0.0f;
-#pragma unroll
-                        for (int r = 0; r < B; ++r) acc[r] = inside ? __builtin_fmaf(v[r * B + c], xc, acc[r]) : acc[r];
-                    }
-                }
-            }
-        }
+        if (I < block_rows) block_row_partial_dot<B, LANES, WIDE>(bc, bv, x, n, brp[I], brp[I + 1], lane, 0, 0, acc);
 #pragma unroll
         for (int r = 0; r < B; ++r) acc[r] = dev::group_sum<LANES>(acc[r]);
         if (I < block_rows) {

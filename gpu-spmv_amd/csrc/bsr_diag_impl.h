@@ -54,20 +54,12 @@ BSR_DIAG_HD int find_block(const int* cols, int lo, int hi, int want) {
     return -1;
 }
 
-// out (B * B floats, row-major) = fl32(D^-1) for the leading size x size part D of the stored block `block`, of which
-// only the lower triangle is read; the other rows and columns of out are +0.0f.  1 <= size <= B.  In fp64:
-//   Cholesky D = L L^T, row by row, w = d_pq - sum_{k<q} l_pk l_qk (k ascending), l_pp = sqrt(w), l_pq = w / l_qq
-//   W = L^-1 column by column: w_jj = 1 / l_jj, w_ij = -(sum_{k=j..i-1} l_ik w_kj) / l_ii (k ascending, from +0)
-//   D^-1_ij = sum_{k >= max(i,j)} w_ki w_kj (k ascending, from +0), computed for i >= j and mirrored
-// all in one packed triangle T.  false, with out unspecified, when a pivot w is not > 0 or not finite.
+// The first two stages of diag_block_inverse, on the packed triangle T (fp64, every operation rounded on its own), for
+// the callers that need the factor's inverse itself (bsr_tri_impl.h: block IC(0) stores fl32(L^-1)).  Rows and columns
+// >= size are left as they are.
+// Cholesky D = L L^T over T, row by row; false when a pivot w is not > 0 or not finite (the IEEE results are in T).
 template <int B>
-BSR_DIAG_HD bool diag_block_inverse(const float* block, int size, float* out) {
-    double T[B * (B + 1) / 2];
-#pragma unroll
-    for (int p = 0; p < B; ++p) {
-#pragma unroll
-        for (int q = 0; q <= p; ++q) T[tri(p, q)] = p < size ? static_cast<double>(block[p * B + q]) : 0.0;
-    }
+BSR_DIAG_HD bool packed_cholesky(double* T, int size) {
     bool ok = true;
 #pragma unroll
     for (int p = 0; p < B; ++p) {
@@ -86,9 +78,13 @@ BSR_DIAG_HD bool diag_block_inverse(const float* block, int size, float* out) {
             }
         }
     }
-    if (!ok) return false;
-    // W over L, column j ascending: column j of L is last read when column j of W is written over it, and l_ii when
-    // column i is
+    return ok;
+}
+
+// W = L^-1 over L, column j ascending: column j of L is last read when column j of W is written over it, and l_ii when
+// column i is
+template <int B>
+BSR_DIAG_HD void packed_lower_inverse(double* T, int size) {
 #pragma unroll
     for (int j = 0; j < B; ++j) {
         if (j < size) {
@@ -104,6 +100,24 @@ BSR_DIAG_HD bool diag_block_inverse(const float* block, int size, float* out) {
             }
         }
     }
+}
+
+// out (B * B floats, row-major) = fl32(D^-1) for the leading size x size part D of the stored block `block`, of which
+// only the lower triangle is read; the other rows and columns of out are +0.0f.  1 <= size <= B.  In fp64:
+//   Cholesky D = L L^T, row by row, w = d_pq - sum_{k<q} l_pk l_qk (k ascending), l_pp = sqrt(w), l_pq = w / l_qq
+//   W = L^-1 column by column: w_jj = 1 / l_jj, w_ij = -(sum_{k=j..i-1} l_ik w_kj) / l_ii (k ascending, from +0)
+//   D^-1_ij = sum_{k >= max(i,j)} w_ki w_kj (k ascending, from +0), computed for i >= j and mirrored
+// all in one packed triangle T.  false, with out unspecified, when a pivot w is not > 0 or not finite.
+template <int B>
+BSR_DIAG_HD bool diag_block_inverse(const float* block, int size, float* out) {
+    double T[B * (B + 1) / 2];
+#pragma unroll
+    for (int p = 0; p < B; ++p) {
+#pragma unroll
+        for (int q = 0; q <= p; ++q) T[tri(p, q)] = p < size ? static_cast<double>(block[p * B + q]) : 0.0;
+    }
+    if (!packed_cholesky<B>(T, size)) return false;
+    packed_lower_inverse<B>(T, size);
 #pragma unroll
     for (int i = 0; i < B; ++i) {
 #pragma unroll

@@ -65,7 +65,11 @@ BSRMatrix* bsr_create(int rows, int cols, int block_dim, int num_blocks) {
 void bsr_destroy(BSRMatrix* mat) {
     if (!mat) return;
     release_host(mat);
-    if (mat->owns_device_memory) bsr_free_gpu(mat);
+    if (mat->owns_device_memory) {
+        bsr_free_gpu(mat);
+    } else if (mat->d_block_row_ptrs) {
+        detail::aux_drop(mat->d_block_row_ptrs);   // wrapped device arrays: drop only our side table
+    }
     delete mat;
 }
 
@@ -115,6 +119,7 @@ int bsr_from_gpu(BSRMatrix* mat) {
 
 void bsr_free_gpu(BSRMatrix* mat) {
     if (!mat) return;
+    if (mat->d_block_row_ptrs) detail::aux_drop(mat->d_block_row_ptrs);      // the schedules of the block pattern
     if (mat->owns_device_memory) {
         if (mat->d_values)         (void)hipFree(mat->d_values);
         if (mat->d_block_cols)     (void)hipFree(mat->d_block_cols);
@@ -137,7 +142,9 @@ BSRMatrix* bsr_wrap_device(int rows, int cols, int block_dim, int num_blocks, co
     return m;
 }
 
-void bsr_invalidate_gpu_cache(const BSRMatrix*) {}
+void bsr_invalidate_gpu_cache(const BSRMatrix* mat) {
+    if (mat && mat->d_block_row_ptrs) detail::aux_drop(mat->d_block_row_ptrs);
+}
 
 // ---- the hand-over of the builders (bsr_impl.h) ----
 void detail::bsr::adopt_device(BSRMatrix* B, int rows, int cols, int block_dim, int num_blocks, int* d_block_row_ptrs,

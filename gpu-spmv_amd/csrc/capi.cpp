@@ -20,6 +20,7 @@
 #include "spmv/assemble.h"
 #include "spmv/csr_ops.h"
 #include "spmv/bsr.h"
+#include "spmv/bsr_factor.h"
 #include "spmv_c.h"
 
 #include <cstddef>
@@ -149,6 +150,9 @@ static_assert(offsetof(spmv_c_ic0_result, num_levels) == offsetof(IC0Result, num
               offsetof(spmv_c_ic0_result, bad_pivot) == offsetof(IC0Result, bad_pivot) &&
               offsetof(spmv_c_ic0_result, analysis_ms) == offsetof(IC0Result, analysis_ms) &&
               offsetof(spmv_c_ic0_result, elapsed_ms) == offsetof(IC0Result, elapsed_ms), "IC0Result layout");
+static_assert(sizeof(BsrIC0Result) == sizeof(IC0Result) && offsetof(BsrIC0Result, bad_pivot) == offsetof(IC0Result, bad_pivot) &&
+              offsetof(BsrIC0Result, analysis_ms) == offsetof(IC0Result, analysis_ms) &&
+              offsetof(BsrIC0Result, elapsed_ms) == offsetof(IC0Result, elapsed_ms), "BsrIC0Result layout");
 static_assert(sizeof(spmv_c_fsai_result) == sizeof(FSAIResult) && sizeof(FSAIResult) == 32, "FSAIResult layout");
 static_assert(offsetof(spmv_c_fsai_result, nnz) == offsetof(FSAIResult, nnz) &&
               offsetof(spmv_c_fsai_result, max_row) == offsetof(FSAIResult, max_row) &&
@@ -1100,6 +1104,41 @@ int spmv_c_bsr_diag_apply(const spmv_c_bsr* A, const float* d_inv, const float* 
 int spmv_c_cg_solve_bsr(const spmv_c_bsr* A, const float* d_b, float* d_x, const spmv_c_cg_config* config,
                         spmv_c_cg_result* out) {
     const CGResult r = cg_solve_bsr(cxx(A), d_b, d_x, reinterpret_cast<const CGConfig*>(config));
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
+}
+int spmv_c_bsr_ic0_cpu(const spmv_c_bsr* A, float* f_values, int* bad_pivot) {
+    return bsr_ic0_cpu(cxx(A), f_values, bad_pivot);
+}
+int spmv_c_bsr_ic0(const spmv_c_bsr* A, float* d_f_values, spmv_c_ic0_result* out) {
+    const BsrIC0Result r = bsr_ic0(cxx(A), d_f_values);
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
+}
+int spmv_c_bsr_ic0_async(const spmv_c_bsr* A, float* d_f_values, void* hip_stream) {
+    return bsr_ic0_async(cxx(A), d_f_values, as_stream(hip_stream));
+}
+int spmv_c_sptrsv_cpu_bsr(const spmv_c_bsr* F, const float* b, float* x, const spmv_c_sptrsv_config* config) {
+    return sptrsv_cpu_bsr(cxx(F), b, x, reinterpret_cast<const SpTRSVConfig*>(config));
+}
+int spmv_c_sptrsv_bsr(const spmv_c_bsr* F, const float* d_b, float* d_x, const spmv_c_sptrsv_config* config,
+                      spmv_c_sptrsv_result* out) {
+    const SpTRSVResult r = sptrsv_bsr(cxx(F), d_b, d_x, reinterpret_cast<const SpTRSVConfig*>(config));
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
+}
+int spmv_c_sptrsv_bsr_async(const spmv_c_bsr* F, const float* d_b, float* d_x, const spmv_c_sptrsv_config* config,
+                            void* hip_stream) {
+    return sptrsv_bsr_async(cxx(F), d_b, d_x, reinterpret_cast<const SpTRSVConfig*>(config), as_stream(hip_stream));
+}
+int spmv_c_sptrsv_analyze_bsr(const spmv_c_bsr* A, int uplo, spmv_c_sptrsv_result* out) {
+    const SpTRSVResult r = sptrsv_analyze_bsr(cxx(A), uplo);
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
+}
+int spmv_c_cg_solve_bsr_ic(const spmv_c_bsr* A, const spmv_c_bsr* F, const float* d_b, float* d_x,
+                           const spmv_c_cg_config* config, spmv_c_cg_result* out) {
+    const CGResult r = cg_solve_bsr_ic(cxx(A), cxx(F), d_b, d_x, reinterpret_cast<const CGConfig*>(config));
     if (out) std::memcpy(out, &r, sizeof(r));
     return r.error_code;
 }

@@ -27,8 +27,8 @@
 //
 // The host side is built from solver_common.h's parts (Workspace and its mirror, TriangularPair, TiledEngine,
 // diag_kernel); what is here is this solver's checks, its workspace layout, its launches and its result.  The state and
-// the kernels that do not read the matrix (cg_start_kernel, cg_rz_kernel, cg_direction_kernel) are cg_impl.h's, shared
-// with cg_bsr.hip.
+// the kernels that do not read the matrix (cg_start_kernel, cg_update_kernel, cg_rz_kernel, cg_direction_kernel) are
+// cg_impl.h's, shared with cg_bsr.hip.
 #include "amg_impl.h"
 #include "cg_impl.h"
 #include "internal.h"
@@ -106,52 +106,6 @@ void cg_dot_kernel(int n, const float* __restrict__ p, const float* __restrict__
     }
     block_sum2(pq, unused);
     if (threadIdx.x == 0) part[blockIdx.x] = pq;
-}
-
-// alpha = rz / p.q; x += alpha p; r -= alpha q; partials of r.z and r.r -> part_out[2 * block] with z = r * dinv
-// (r where dinv is null).  STORED_Z (IC, AMG): z does not exist yet and dinv is not read: the partials of r.r alone ->
-// part_out[2 * block + 1]; r.z follows from cg_rz_kernel once z is there.
-template <bool STORED_Z>
-__global__ __launch_bounds__(kBlock)
-void cg_update_kernel(int n, int step, const float* __restrict__ p, const float* __restrict__ q,
-                      const float* __restrict__ dinv, float* __restrict__ x, float* __restrict__ r,
-                      CgState* __restrict__ state, const double* __restrict__ pq_part, int pq_count,
-                      double* __restrict__ part_out) {
-    if (state->done) return;
-    double pq = 0.0, unused = 0.0;
-    fold_partials(pq_part, pq_count, 1, pq, unused);
-    if (!(pq > 0.0)) {             // A is not SPD (or p.q is not finite): x stays at the last good iterate
-        if (blockIdx.x == 0 && threadIdx.x == 0) {
-            state->breakdown = 1;
-            state->done = 1;
-        }
-        return;
-    }
-    const float alpha = static_cast<float>(state->rz[step & 1] / pq);
-    double rz = 0.0, rr = 0.0;
-    for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < n;
-         i += static_cast<long long>(gridDim.x) * kBlock) {
-        const float pi = p[i];
-        const float qi = q[i];
-        x[i] = __builtin_fmaf(alpha, pi, x[i]);
-        const float ri = __builtin_fmaf(-alpha, qi, r[i]);
-        r[i] = ri;
-        if constexpr (!STORED_Z) {
-            const float zi = dinv ? __fmul_rn(ri, dinv[i]) : ri;
-            rz += prod64(ri, zi);
-        }
-        rr += prod64(ri, ri);
-    }
-    if constexpr (STORED_Z) {
-        block_sum2(rr, unused);
-        if (threadIdx.x == 0) part_out[2 * blockIdx.x + 1] = rr;
-    } else {
-        block_sum2(rz, rr);
-        if (threadIdx.x == 0) {
-            part_out[2 * blockIdx.x] = rz;
-            part_out[2 * blockIdx.x + 1] = rr;
-        }
-    }
 }
 
 hipError_t init(int lanes, const CSRMatrix* A, const float* b, const float* x, const float* dinv, float* r,

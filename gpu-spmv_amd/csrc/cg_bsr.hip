@@ -1,5 +1,6 @@
 // cg_bsr.hip — conjugate gradients on a BSRMatrix with a block-Jacobi preconditioner (include/spmv/cg.h cg_solve_bsr,
-// include/spmv/bsr.h bsr_diag_inverse_gpu / bsr_diag_apply).
+// include/spmv/bsr.h bsr_diag_inverse_gpu / bsr_diag_apply) or with a block IC(0) factor
+// (cg_solve_bsr_ic: cg.hip's stored-z step on this file's product, the solves of bsr_tri.hip).
 //
 // The loop is cg.hip's: the scalars live in a device CgState, every loop kernel returns at once when `done` is set, and
 // the host reads the two-deep pinned mirror of the state.  z = M^-1 r is a stored vector for every preconditioner, so
@@ -20,6 +21,7 @@
 #include "bsr_device.h"
 #include "bsr_diag_impl.h"
 #include "bsr_impl.h"
+#include "bsr_tri_impl.h"
 #include "cg_impl.h"
 #include "device_common.h"
 #include "internal.h"
@@ -281,24 +283,52 @@ hipError_t launch_update(const BSRMatrix* A, int grid, int step, const float* p,
     });
 }
 
-CGResult solve(const BSRMatrix* A, const float* d_b, float* d_x, const CGConfig* config) {
+// F == nullptr: cg_solve_bsr, M^-1 from cfg.preconditioner.  with_ic: cg_solve_bsr_ic, z = L^-T (L^-1 r) by the two block
+// triangular solves with the factor matrix F (bsr_tri.hip), a stored z between cg.hip's update and r.z kernels.
+CGResult solve(const BSRMatrix* A, bool with_ic, const BSRMatrix* F, const float* d_b, float* d_x,
+               const CGConfig* config) {
     CGResult result;
     const auto fail = [&result](SpMVError e) {
         result.error_code = code(e);
         return result;
     };
     const CGConfig defaults;
-    const CGConfig& cfg = config ? *config : defaults;
+    CGConfig cfg = config ? *config : defaults;
+    if (with_ic) cfg.preconditioner = CGConfig::NONE;      // not read: the factor is the preconditioner
     bool nothing = false;
-    const int status = cg_check(A, d_b, d_x, cfg, &nothing);
+    int status = cg_check(A, d_b, d_x, cfg, &nothing);
     if (status != 0) return fail(static_cast<SpMVError>(status));
     if (nothing) {
         result.converged = 1;
         return result;
     }
+    if (with_ic) {
+        status = cg_ic_check(A, F);
+        if (status != 0) return fail(static_cast<SpMVError>(status));
+    }
 
-    const TraceRange range("spmv:cg_solve_bsr");
+    const TraceRange range(with_ic ? "spmv:cg_solve_bsr_ic" : "spmv:cg_solve_bsr");
     hipStream_t stream = current_stream();
+    // M = L L^T: both schedules of F's block pattern, which validate it before any kernel walks it
+    ScheduleRef lower, upper;
+    int lower_lanes = 1, upper_lanes = 1;
+    if (with_ic) {
+        float analysis_ms = 0.0f;
+        status = tri_schedule_for(F, SpTRSVConfig::LOWER, stream, &lower, &analysis_ms);
+        if (status == 0) status = tri_schedule_for(F, SpTRSVConfig::UPPER, stream, &upper, &analysis_ms);
+        if (status != 0) return fail(static_cast<SpMVError>(status));
+        if (lower->first_missing_diagonal >= 0 || lower->first_unsorted_row >= 0) {
+            return fail(SpMVError::INVALID_ARGUMENT);
+        }
+        lower_lanes = tri_lanes(*lower, false);
+        upper_lanes = tri_lanes(*upper, false);
+    }
+    // z = L^-T (L^-1 in): LOWER into out, then UPPER in place.  Like cg.hip's triangular solves they do not read `done`:
+    // after it r no longer changes and they rewrite the same z.
+    const auto apply_factor = [&](const float* in, float* out) {
+        return launch_sptrsv_bsr(*lower, F, in, out, SpTRSVConfig::LOWER, 0, false, lower_lanes, stream) == hipSuccess &&
+               launch_sptrsv_bsr(*upper, F, out, out, SpTRSVConfig::UPPER, 0, false, upper_lanes, stream) == hipSuccess;
+    };
     const int n = A->num_rows, b = A->block_dim, block_rows = A->num_block_rows;
     const bool jacobi = cfg.preconditioner == CGConfig::JACOBI;
     const bool block_jacobi = cfg.preconditioner == CGConfig::BLOCK_JACOBI;
@@ -308,7 +338,7 @@ CGResult solve(const BSRMatrix* A, const float* d_b, float* d_x, const CGConfig*
     const int update_grid = capped_grid(n, kBlock - kBlock % b, kVecBlocks);
     const int vgrid = vec_grid(n);
     const size_t pq_count = static_cast<size_t>(row_grid);
-    const size_t rr_count = 2 * static_cast<size_t>(update_grid);
+    const size_t rr_count = 2 * static_cast<size_t>(std::max(update_grid, vgrid));
     const size_t init_count = 3 * static_cast<size_t>(row_grid);
 
     Workspace<CgState> ws;          // r, p, q, z, and dinv (JACOBI) or the block inverses (BLOCK_JACOBI)
@@ -330,12 +360,13 @@ CGResult solve(const BSRMatrix* A, const float* d_b, float* d_x, const CGConfig*
     int* bad = &ws.state->bad_diagonal;
     if (block_jacobi) ok = ok && launch_inverse(A, inv, bad, stream) == hipSuccess;
     if (jacobi) ok = ok && launch_scalar_diag(A, dinv, bad, stream) == hipSuccess;
+    if (with_ic) ok = ok && launch_factor_diag_check(F, bad, stream) == hipSuccess;
     ok = ok && with_walk(A, lanes, [&](auto Bc, auto L, auto W) {
         cg_bsr_init<decltype(Bc)::value, decltype(L)::value, decltype(W)::value><<<row_grid, kBlock, 0, stream>>>(
             A->d_block_row_ptrs, A->d_block_cols, A->d_values, n, block_rows, d_b, d_x, r, init_part);
         return hipGetLastError();
     }) == hipSuccess;
-    ok = ok && launch_apply<true>(b, n, inv, dinv, r, z, stream) == hipSuccess;
+    ok = ok && (with_ic ? apply_factor(r, z) : launch_apply<true>(b, n, inv, dinv, r, z, stream) == hipSuccess);
     if (ok) {
         cg_rz_kernel<<<row_grid, kBlock, 0, stream>>>(n, r, z, ws.state, init_part, 3);
         ok = hipGetLastError() == hipSuccess &&
@@ -364,11 +395,18 @@ CGResult solve(const BSRMatrix* A, const float* d_b, float* d_x, const CGConfig*
                                                       q, ws.state, pq_part);
                 return hipGetLastError();
             }) == hipSuccess;
-            ok = ok && launch_update(A, update_grid, iter, p, q, inv, dinv, d_x, r, z, ws.state, pq_part, row_grid,
-                                     rr_part, stream) == hipSuccess;
+            if (ok && with_ic) {
+                cg_update_kernel<true><<<vgrid, kBlock, 0, stream>>>(n, iter, p, q, nullptr, d_x, r, ws.state, pq_part,
+                                                                     row_grid, rr_part);
+                ok = hipGetLastError() == hipSuccess && apply_factor(r, z);
+                if (ok) cg_rz_kernel<<<vgrid, kBlock, 0, stream>>>(n, r, z, ws.state, rr_part, 2);
+            } else {
+                ok = ok && launch_update(A, update_grid, iter, p, q, inv, dinv, d_x, r, z, ws.state, pq_part, row_grid,
+                                         rr_part, stream) == hipSuccess;
+            }
             if (ok) {
                 cg_direction_kernel<true><<<vgrid, kBlock, 0, stream>>>(n, iter, z, nullptr, p, ws.state, rr_part,
-                                                                        update_grid);
+                                                                        with_ic ? vgrid : update_grid);
                 ok = hipGetLastError() == hipSuccess && ws.publish(iter, sizeof(CgState), stream);
             }
             if (ok && iter >= 1) {
@@ -425,7 +463,11 @@ int bsr_diag_apply(const BSRMatrix* A, const float* d_inv, const float* d_r, flo
 }
 
 CGResult cg_solve_bsr(const BSRMatrix* A, const float* d_b, float* d_x, const CGConfig* config) {
-    return detail::bsr::solve(A, d_b, d_x, config);
+    return detail::bsr::solve(A, false, nullptr, d_b, d_x, config);
+}
+
+CGResult cg_solve_bsr_ic(const BSRMatrix* A, const BSRMatrix* F, const float* d_b, float* d_x, const CGConfig* config) {
+    return detail::bsr::solve(A, true, F, d_b, d_x, config);
 }
 
 } // namespace spmv

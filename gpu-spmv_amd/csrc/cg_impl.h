@@ -1,7 +1,8 @@
-// cg_impl.h — what the CG kernel files (cg.hip, cg_bsr.hip) share: the device state of one solve and the three
-// kernels that do not depend on the matrix format — the start of the state, the r.z partials of a stored z and the
-// direction step.  The kernels sit in an unnamed namespace, as they did in cg.hip: each file that includes this header
-// gets its own copy under the same name, and nothing else can call them.  Internal: not installed under include/.
+// cg_impl.h — what the CG kernel files (cg.hip, cg_bsr.hip) share: the device state of one solve and the four
+// kernels that do not depend on the matrix format — the start of the state, the update of x and r, the r.z partials
+// of a stored z and the direction step.  The kernels sit in an unnamed namespace, as they did in cg.hip: each file
+// that includes this header gets its own copy under the same name, and nothing else can call them.  Internal: not
+// installed under include/.
 #ifndef SPMV_AMD_CG_IMPL_H
 #define SPMV_AMD_CG_IMPL_H
 
@@ -91,6 +92,52 @@ void cg_direction_kernel(int n, int step, const float* __restrict__ zr, const fl
         float zi = zr[i];
         if constexpr (!STORED_Z) zi = dinv ? __fmul_rn(zi, dinv[i]) : zi;
         p[i] = __builtin_fmaf(beta, p[i], zi);
+    }
+}
+
+// alpha = rz / p.q; x += alpha p; r -= alpha q; partials of r.z and r.r -> part_out[2 * block] with z = r * dinv
+// (r where dinv is null).  STORED_Z (IC, AMG): z does not exist yet and dinv is not read: the partials of r.r alone ->
+// part_out[2 * block + 1]; r.z follows from cg_rz_kernel once z is there.
+template <bool STORED_Z>
+__global__ __launch_bounds__(dev::kBlock)
+void cg_update_kernel(int n, int step, const float* __restrict__ p, const float* __restrict__ q,
+                      const float* __restrict__ dinv, float* __restrict__ x, float* __restrict__ r,
+                      CgState* __restrict__ state, const double* __restrict__ pq_part, int pq_count,
+                      double* __restrict__ part_out) {
+    if (state->done) return;
+    double pq = 0.0, unused = 0.0;
+    solver::fold_partials(pq_part, pq_count, 1, pq, unused);
+    if (!(pq > 0.0)) {             // A is not SPD (or p.q is not finite): x stays at the last good iterate
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            state->breakdown = 1;
+            state->done = 1;
+        }
+        return;
+    }
+    const float alpha = static_cast<float>(state->rz[step & 1] / pq);
+    double rz = 0.0, rr = 0.0;
+    for (long long i = static_cast<long long>(blockIdx.x) * dev::kBlock + threadIdx.x; i < n;
+         i += static_cast<long long>(gridDim.x) * dev::kBlock) {
+        const float pi = p[i];
+        const float qi = q[i];
+        x[i] = __builtin_fmaf(alpha, pi, x[i]);
+        const float ri = __builtin_fmaf(-alpha, qi, r[i]);
+        r[i] = ri;
+        if constexpr (!STORED_Z) {
+            const float zi = dinv ? __fmul_rn(ri, dinv[i]) : ri;
+            rz += solver::prod64(ri, zi);
+        }
+        rr += solver::prod64(ri, ri);
+    }
+    if constexpr (STORED_Z) {
+        dev::block_sum2(rr, unused);
+        if (threadIdx.x == 0) part_out[2 * blockIdx.x + 1] = rr;
+    } else {
+        dev::block_sum2(rz, rr);
+        if (threadIdx.x == 0) {
+            part_out[2 * blockIdx.x] = rz;
+            part_out[2 * blockIdx.x + 1] = rr;
+        }
     }
 }
 

@@ -224,6 +224,8 @@ void    ell_aux_drop(const void* key);
 //   add_lanes=N                lanes per row of csr_add and csr_add_numeric (1, 2, 4, ... 64; anything else is ignored)
 //   bsr_lanes=N                lanes per block row of bsr_from_csr_gpu, bsr_from_csr_numeric, csr_block_count_gpu and
 //                              of spmv_bsr's lane-group kernel (1, 2, 4, ... 64; anything else is ignored)
+//   bsr_tri_lanes=N            lanes per block row of bsr_ic0 and of sptrsv_bsr with ordered = 0, cg_solve_bsr_ic's solves
+//                              included (1, 2, 4, ... 64; anything else is ignored)
 // Everything else the library reads from the environment is listed in INTEGRATION.md.
 bool debug_option(const char* key, long long* value = nullptr, char* text = nullptr, size_t text_size = 0);
 // the same "key=value,key" syntax for another variable's value (SPMV_MULTI_GPU); `list` may be null

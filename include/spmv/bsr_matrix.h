@@ -53,8 +53,10 @@ void bsr_free_gpu(BSRMatrix* mat);
 // frees the header only.
 BSRMatrix* bsr_wrap_device(int rows, int cols, int block_dim, int num_blocks, const int* d_block_row_ptrs,
                            const int* d_block_cols, const float* d_values);
-// After writing into the device arrays in place.  Nothing is cached per BSR matrix today, so this does nothing; it
-// is declared (and called by bsr_from_csr_numeric) so that the refill rule reads the same as for CSR.
+// After writing into the device arrays in place (bsr_from_csr_numeric calls it): drops what the library keeps per BSR
+// matrix in its side table under d_block_row_ptrs, the level schedules of the block pattern (sptrsv_bsr, bsr_ic0,
+// cg_solve_bsr_ic; spmv/bsr_factor.h), which every matrix over the same structure arrays shares.  bsr_free_gpu and every
+// rebuild into an existing matrix drop them too: the CSR rules.
 void bsr_invalidate_gpu_cache(const BSRMatrix* mat);
 
 } // namespace spmv

@@ -190,6 +190,23 @@ CGResult cg_solve_fsai(const CSRMatrix* A, const CSRMatrix* G, const CSRMatrix* 
 // spmv_get_stream() and returns after the solve; call it outside a graph capture.
 CGResult cg_solve_bsr(const BSRMatrix* A, const float* d_b, float* d_x, const CGConfig* config = nullptr);
 
+// cg_solve_ic's iteration on cg_solve_bsr's kernels: M = L L^T given as the block factor matrix F of
+// spmv/bsr_factor.h, usually bsr_ic0's output wrapped over A's structure arrays:
+//     bsr_wrap_device(n, n, b, num_blocks, A->d_block_row_ptrs, A->d_block_cols, d_f_values).
+// One step: the product fused with p.q (cg_solve_bsr's, so q has spmv_bsr's bits); the update of x and r with the r.r
+// partials; z = L^-T (L^-1 r) by a LOWER solve from r into z and an UPPER solve in place (sptrsv_bsr, ordered = 0); r.z;
+// the direction step: 4 + launches(LOWER) + launches(UPPER) launches.  Numerics, stop rules, breakdown rule, the
+// ||b|| == 0 rule and the engine rule are cg_solve_bsr's.
+// Checks, in this order, nothing written to d_x when one fails: cg_solve_bsr's (config->preconditioner is not read);
+// null F -> INVALID_ARGUMENT; F not square, or of another size or block_dim than A -> INVALID_DIMENSION; missing device
+// arrays of F -> INVALID_FORMAT; a malformed block pattern of F -> INVALID_FORMAT; a block row of F whose block columns
+// are not strictly ascending -> INVALID_ARGUMENT; a diagonal block of F missing, or with a diagonal entry that is not
+// > 0 or not finite -> INVALID_ARGUMENT (on the device, in the one setup read-back).
+// The schedules of F's block pattern are the cached ones of sptrsv_bsr (built, and the stream synchronised, by the
+// first use per pattern and triangle).
+CGResult cg_solve_bsr_ic(const BSRMatrix* A, const BSRMatrix* F, const float* d_b, float* d_x,
+                         const CGConfig* config = nullptr);
+
 } // namespace spmv
 
 #endif

@@ -867,6 +867,24 @@ int spmv_c_bsr_diag_apply(const spmv_c_bsr* A, const float* d_inv, const float* 
  * Checks and numerics as cg_solve_bsr in include/spmv/cg.h.  Returns out->error_code (out may be NULL). */
 int spmv_c_cg_solve_bsr(const spmv_c_bsr* A, const float* d_b, float* d_x, const spmv_c_cg_config* config,
                         spmv_c_cg_result* out);
+/* Block IC(0) and the block triangular solves (include/spmv/bsr_factor.h, which holds the factor format, the arithmetic
+ * and the checks).  f_values / d_f_values: num_blocks * b * b floats in A's block pattern, may be A's own values (in
+ * place); spmv_c_bsr_wrap_device over A's structure arrays and d_f_values is the factor matrix F of both solves.  The
+ * result of the factorisation has spmv_c_ic0_result's layout: lanes_per_row counts the lanes of a BLOCK row and
+ * bad_pivot is a BLOCK row.  The device factor is bit for bit spmv_c_bsr_ic0_cpu; the solve with ordered = 1 is bit for
+ * bit spmv_c_sptrsv_cpu_bsr.  Return values equal out->error_code (out may be NULL). */
+int spmv_c_bsr_ic0_cpu(const spmv_c_bsr* A, float* f_values, int* bad_pivot);
+int spmv_c_bsr_ic0(const spmv_c_bsr* A, float* d_f_values, spmv_c_ic0_result* out);
+int spmv_c_bsr_ic0_async(const spmv_c_bsr* A, float* d_f_values, void* hip_stream);
+int spmv_c_sptrsv_cpu_bsr(const spmv_c_bsr* F, const float* b, float* x, const spmv_c_sptrsv_config* config);
+int spmv_c_sptrsv_bsr(const spmv_c_bsr* F, const float* d_b, float* d_x, const spmv_c_sptrsv_config* config,
+                      spmv_c_sptrsv_result* out);
+int spmv_c_sptrsv_bsr_async(const spmv_c_bsr* F, const float* d_b, float* d_x, const spmv_c_sptrsv_config* config,
+                            void* hip_stream);
+int spmv_c_sptrsv_analyze_bsr(const spmv_c_bsr* A, int uplo, spmv_c_sptrsv_result* out);
+/* CG preconditioned with the block factor F (cg_solve_bsr_ic in include/spmv/cg.h); config->preconditioner is not read. */
+int spmv_c_cg_solve_bsr_ic(const spmv_c_bsr* A, const spmv_c_bsr* F, const float* d_b, float* d_x,
+                           const spmv_c_cg_config* config, spmv_c_cg_result* out);
 
 /* ---- bandwidth model: reference include/spmv/bandwidth.h:21-27 ---- */
 int spmv_c_compute_bandwidth_csr(const spmv_c_csr* A, float elapsed_ms, spmv_c_bandwidth* out);
