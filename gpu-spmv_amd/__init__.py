@@ -429,6 +429,7 @@ _SIGNATURES = {
     "spmv_c_csr_tiled_checksum": (c_int, [POINTER(CSRMatrix), POINTER(c_uint64)]),
     "spmv_c_csr_tiled_folded": (c_int, [POINTER(CSRMatrix)]),
     "spmv_c_csr_tiled_items": (c_int, [POINTER(CSRMatrix)]),
+    "spmv_c_csr_tiled_col_bytes": (c_int64, [POINTER(CSRMatrix)]),
     "spmv_c_ell_tiled_info": (c_int, [POINTER(ELLMatrix), POINTER(c_int64)]),
     "spmv_c_csr_transpose_tiled_info": (c_int, [POINTER(CSRMatrix), POINTER(c_int64)]),
     "spmv_c_spmv_csr_async": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(SpMVConfig), c_int,
@@ -1098,6 +1099,8 @@ def csr_tiled_info(A):
         info["build_ms"] = round(float(stats[0]), 3)
         info["plan_bytes"] = int(stats[1])
         info["entries_in_cells"] = int(stats[3])
+    # the local columns as the plan holds them; plan_bytes counts them at two bytes a slot either way
+    info["col_bytes"] = int(lib().spmv_c_csr_tiled_col_bytes(A))
     return info
 
 

@@ -541,6 +541,13 @@ int spmv_c_csr_tiled_folded(const spmv_c_csr* A_c) {
     return aux && aux->tiled && aux->tiled->col_weight ? 1 : 0;
 }
 
+int64_t spmv_c_csr_tiled_col_bytes(const spmv_c_csr* A_c) {
+    const CSRMatrix* A = cxx(A_c);
+    if (!A || !A->d_row_ptrs) return -1;
+    detail::CsrAux* aux = detail::aux_lookup(A->d_row_ptrs, false);
+    return aux && aux->tiled ? aux->tiled->col_bytes : -1;
+}
+
 int spmv_c_csr_tiled_items(const spmv_c_csr* A_c) {
     const CSRMatrix* A = cxx(A_c);
     if (!A || !A->d_row_ptrs) return -1;

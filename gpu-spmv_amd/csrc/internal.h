@@ -198,6 +198,8 @@ void    ell_aux_drop(const void* key);
 //   min_cols=N, min_nnz=N      size thresholds of the LDS-tiled engine (tests push small matrices through it)
 //   strip=W, tile=R, item=N    plan shape overrides: strip columns (4096..32768), tile rows (multiple of 64), slots per phase-1 item
 //   long_factor=N, long_cap=N  long-row limit = min(long_cap, long_factor * strips)
+//   cols=u16                   the plan keeps its local columns as u16 per slot on every strip width (default: packed to
+//                              14 bits wherever strip columns <= 16384, tiled_layout.h)
 //   rank=plain                 ranking pass of the plan build by comparison (no stable binning)
 //   place=scattered            placing pass of the plan build entry by entry (no LDS staging)
 //   pr_plan_after=N            direct steps pagerank() takes before it builds a plan (default 4)

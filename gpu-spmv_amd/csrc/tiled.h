@@ -35,7 +35,9 @@ struct TiledPlan {
     // Every cell's length is a multiple of 4 slots.
     DevBuf<float>    a_val;      // [nnz]; null when the values are folded into col_weight
     DevBuf<float>    col_weight; // [num_cols] the one value every entry of a column carries, or null
-    DevBuf<uint16_t> a_lcol;     // [nnz] column - strip * W
+    DevBuf<uint16_t> a_lcol;     // [nnz] column - strip * W.  BUILD ONLY where strip_cols <= 16384: the finished plan then
+                                 // holds the columns as a_cols14 and frees this (SPMV_DEBUG=cols=u16 keeps it instead)
+    DevBuf<uint8_t>  a_cols14;   // the same columns, 14 bits a slot in 448-byte blocks of 256 slots (tiled_layout.h), or null
     DevBuf<uint8_t>  a_drow;     // [nnz] row - (row of the cell's previous slot), 0..254; 255 = advance 255 rows, no entry.
                                  // BUILD ONLY: the finished plan holds the same bytes in pass order (pass_word) and frees this
     DevBuf<float>    prod;       // [nnz] phase-1 output / phase-2 input, same order
@@ -82,7 +84,8 @@ struct TiledPlan {
 
     // what the build cost (reported by bench.py)
     double    build_ms = 0.0;       // host wall clock of the build, allocations and syncs included
-    long long plan_bytes = 0;       // device memory the plan holds
+    long long plan_bytes = 0;       // device memory the plan holds, its local columns counted as u16 (an upper bound where packed)
+    long long col_bytes = 0;        // of which local columns, as held: 2 * nnz, or the packed array's bytes (a_cols14)
 };
 
 // the (strip columns, tile rows) the engine would pick for a matrix of this shape, and whether it

@@ -15,6 +15,8 @@
 //        cell's previous slot; 255 = "advance 255 rows, no entry" for the rare larger gaps) — 7 B
 //        against CSR's 8 — plus a 4-byte product slot.  Cells are padded to a multiple of 4 slots.  The row deltas are
 //        kept in the order phase 2 reads them, 64 four-byte words per pass (pass_word, tiled_layout.h), not slot by slot.
+//        Where a strip has at most 16384 columns the finished plan holds the local columns packed to 14 bits, 256 slots
+//        in 448 bytes (a_cols14, tiled_layout.h): 1.75 B per slot instead of 2.
 //   phase 1 "expand" : a workgroup loads one x strip (W = 4 K .. 32 K columns, chosen per
 //        matrix = 16 .. 128 KiB) into LDS, streams its share of the strip's slots (value, local column) with
 //        16-byte loads, gathers x from LDS and stores the products — same order, so
@@ -43,7 +45,7 @@
 //        the placing pass writes every entry straight to its slot.  No global atomics anywhere, so the layout
 //        is a pure function of the matrix.
 //
-// HBM traffic per slot: 6 B read + 4 B written in phase 1, 5 B read in phase 2 (15 B vs CSR's 8 B per entry) —
+// HBM traffic per slot: 6 B read (5.75 with packed columns) + 4 B written in phase 1, 5 B read in phase 2 (15 B vs CSR's 8 B per entry) —
 // but all of it is streamed, which beats one 64-byte random fetch per entry by a wide margin once x leaves L2.
 // Reproducibility: layout and long-row sums are order-free; inside a tile the products of a row meet in
 // scheduling order, but they are added as doubles (every fp32 product is exact there, the sum of a row's
@@ -176,15 +178,76 @@ __device__ __forceinline__ void stage_strip(float* xs, const float* __restrict__
     }
 }
 
+// The local columns of the four slots q .. q + 3 of a plan with PACKED columns (tiled_layout.h: 14 bits a slot, 256 slots
+// in a 448-byte block): one aligned dword of the block's low plane and the 24 bits of its high field that start at byte
+// 3 * lane — the wavefront walks one block per iteration, so the lane's group is group `lane` of the block.
+struct Cols14 {
+    unsigned int lo, hi;
+    __device__ __forceinline__ int at(int e) const { return static_cast<int>(((lo >> (8 * e)) & 0xFFu) | (((hi >> (6 * e)) & 0x3Fu) << 8)); }
+};
+// The high bits: one 4-byte load at a byte address (a single global_load_dword; gfx950 takes the unaligned address), whose
+// top byte is the next lane's, or the slack behind the array.  (The other form — 48 lanes load the field's aligned
+// dwords, two ds_bpermute and a v_alignbyte hand every lane its 24 bits — made the kernel 30 to 34 us SLOWER than the
+// u16 plan on C5, where this one is faster: the permutes queue behind the LDS gathers.  profiles/packed_cols_ab.txt.)
+__device__ __forceinline__ unsigned int cols14_high(const unsigned char* __restrict__ block, int lane) {
+    unsigned int hi;
+    __builtin_memcpy(&hi, block + kColLowBytes + 3 * lane, sizeof(hi));
+    return hi;
+}
+
 // The products of the slots [begin, end) of the staged strip: value, local column -> value * xs[column], same order.
-template <int kExpandBlock, bool FOLD>
+// PACKED: a_cols is the plan's a_cols14, else its a_lcol (u16 per slot).
+template <int kExpandBlock, bool FOLD, bool PACKED>
 __device__ __forceinline__ void expand_slots(const float* xs, int begin, int end, const float* __restrict__ a_val,
-                                             const unsigned short* __restrict__ a_lcol, float* __restrict__ prod) {
+                                             const void* __restrict__ a_cols, float* __restrict__ prod) {
     constexpr int kStride = kExpandBlock * 4;
+    const unsigned short* __restrict__ a_lcol = PACKED ? nullptr : static_cast<const unsigned short*>(a_cols);
+    const unsigned char* __restrict__ cols14 = PACKED ? static_cast<const unsigned char*>(a_cols) : nullptr;
     // Both loops start at the 16-slot boundary at or below `begin` (16 products = one 64-byte sector): a wavefront's 1 KB
     // of non-temporal stores then covers whole sectors, where an origin of begin & ~3 split a sector between two
     // instructions and, as such stores do not merge, wrote it twice (profiles/aligned_streams_traffic_ab.txt).  The
     // groups in front of `begin` are masked like those behind `end`: same products to the same slots.
+    if (PACKED) {
+        // The same walk from the 256-slot boundary at or below `begin`: kStride is a multiple of 256, so the 256 slots of a
+        // wavefront's iteration are exactly one column block.  The loop runs on the wavefront's first slot, a scalar, and
+        // so does the block's address; the groups outside [begin, end) are masked as above.  FOLD takes two groups a
+        // workgroup-stride apart per step, as below.
+        static_assert(kStride % kColBlockSlots == 0, "a wavefront's 256 slots are one column block");
+        constexpr int kGroups = FOLD ? 2 : 1;
+        const int lane = threadIdx.x & 63;
+        const int wave_first = __builtin_amdgcn_readfirstlane((begin & ~(kColBlockSlots - 1)) + (static_cast<int>(threadIdx.x) - lane) * 4);
+        for (int w = wave_first; w < end; w += kGroups * kStride) {
+#pragma unroll
+            for (int u = 0; u < kGroups; ++u) {
+                const int first = w + u * kStride;
+                if (first >= end) break;
+                const unsigned char* block = cols14 + col_block_byte(first);
+                const int q = first + 4 * lane;
+                if (q >= begin && q + 3 < end) {
+                    Cols14 c;
+                    c.lo = reinterpret_cast<const unsigned int*>(block)[lane];
+                    c.hi = cols14_high(block, lane);
+                    f32x4 p;
+                    if (FOLD) {
+                        p[0] = xs[c.at(0)]; p[1] = xs[c.at(1)]; p[2] = xs[c.at(2)]; p[3] = xs[c.at(3)];
+                    } else {
+                        const f32x4 v = *reinterpret_cast<const f32x4*>(a_val + q);
+                        p[0] = v[0] * xs[c.at(0)];
+                        p[1] = v[1] * xs[c.at(1)];
+                        p[2] = v[2] * xs[c.at(2)];
+                        p[3] = v[3] * xs[c.at(3)];
+                    }
+                    store_product(reinterpret_cast<f32x4*>(prod + q), p);
+                } else {
+                    for (int k = max(q, begin); k < min(q + 4, end); ++k) {
+                        const float xk = xs[lcol_at(a_lcol, cols14, k)];
+                        prod[k] = FOLD ? xk : a_val[k] * xk;
+                    }
+                }
+            }
+        }
+        return;
+    }
     if (FOLD) {
         // four entries per lane per group, two groups a workgroup-stride apart per step: every store instruction writes
         // one contiguous KB per wavefront (round 3's eight consecutive entries per lane made each instruction write every
@@ -200,7 +263,7 @@ __device__ __forceinline__ void expand_slots(const float* xs, int begin, int end
                     p[0] = xs[c[0]]; p[1] = xs[c[1]]; p[2] = xs[c[2]]; p[3] = xs[c[3]];
                     store_product(reinterpret_cast<f32x4*>(prod + g), p);
                 } else {
-                    for (int k = max(g, begin); k < min(g + 4, end); ++k) prod[k] = xs[a_lcol[k]];
+                    for (int k = max(g, begin); k < min(g + 4, end); ++k) prod[k] = xs[lcol_at(a_lcol, cols14, k)];
                 }
             }
         }
@@ -221,7 +284,7 @@ __device__ __forceinline__ void expand_slots(const float* xs, int begin, int end
             p[3] = v[3] * xs[c[3]];
             store_product(reinterpret_cast<f32x4*>(prod + q), p);
         } else {
-            for (int k = max(q, begin); k < min(q + 4, end); ++k) prod[k] = a_val[k] * xs[a_lcol[k]];
+            for (int k = max(q, begin); k < min(q + 4, end); ++k) prod[k] = a_val[k] * xs[lcol_at(a_lcol, cols14, k)];
         }
     }
 }
@@ -230,11 +293,12 @@ __device__ __forceinline__ void expand_slots(const float* xs, int begin, int end
 // as w_j * x_j and an entry's product is a plain LDS read (the same rounded product as a_ij * x_j).
 // One workgroup per work item.  (Round 4 tried 2 / 3 / 5 CONSECUTIVE items per workgroup, staging a strip only when it changes:
 // 347 / 359 / 433 against 320 us on C5 — fewer, longer workgroups balance worse than their saved strip loads are worth.)
-template <int W, int kExpandBlock, bool FOLD>
+// PACKED: the plan's local columns are the 14-bit blocks of tiled_layout.h (a_cols = a_cols14), else u16 per slot (a_lcol).
+template <int W, int kExpandBlock, bool FOLD, bool PACKED>
 __global__ __launch_bounds__(kExpandBlock)
 void tiled_expand_kernel(const int* __restrict__ items, int first_item, int num_items, int commit_blocks, int long_blocks,
                          const float* __restrict__ a_val,
-                         const unsigned short* __restrict__ a_lcol,
+                         const void* __restrict__ a_cols,
                          const float* __restrict__ col_weight,
                          const float* __restrict__ x, int num_cols,
                          float* __restrict__ prod, LongRows long_rows,
@@ -269,7 +333,7 @@ void tiled_expand_kernel(const int* __restrict__ items, int first_item, int num_
     const int end = items[3 * item + 2];
     stage_strip<W, kExpandBlock, FOLD>(xs, x, col_weight, static_cast<long long>(strip) * W, num_cols);
     __syncthreads();
-    expand_slots<kExpandBlock, FOLD>(xs, begin, end, a_val, a_lcol, prod);
+    expand_slots<kExpandBlock, FOLD, PACKED>(xs, begin, end, a_val, a_cols, prod);
 }
 
 // ------------------------------------------------------------------------ phase 2 ----
@@ -598,14 +662,21 @@ hipError_t launch_expand_as(const TiledPlan& plan, const Scratch& sc, int first_
     const int commit_blocks = commit.partials ? kXcds : 0;
     const int grid = commit_blocks + long_blocks + xcd_grid(num_items);
     if (grid == 0) return hipSuccess;
+    auto launch = [&](auto fold, auto packed) {
+        constexpr bool FOLD = decltype(fold)::value, PACKED = decltype(packed)::value;
+        const void* cols = PACKED ? static_cast<const void*>(plan.a_cols14.get()) : static_cast<const void*>(plan.a_lcol.get());
+        tiled_expand_kernel<W, BLOCK, FOLD, PACKED><<<grid, BLOCK, 0, s>>>(
+            plan.items.get(), first_item, num_items, commit_blocks, long_blocks, plan.a_val.get(), cols, plan.col_weight.get(), d_x,
+            plan.num_cols, sc.prod, lr, d_state, commit);
+    };
+    // (a 32768-column strip never packs: no such instantiation)
+    const bool packed = W <= kPackedStripCols && plan.a_cols14 != nullptr;
     if (plan.col_weight) {
-        tiled_expand_kernel<W, BLOCK, true><<<grid, BLOCK, 0, s>>>(
-            plan.items.get(), first_item, num_items, commit_blocks, long_blocks, nullptr, plan.a_lcol.get(), plan.col_weight.get(), d_x, plan.num_cols, sc.prod, lr,
-            d_state, commit);
+        if (packed) launch(std::true_type{}, std::integral_constant<bool, (W <= kPackedStripCols)>{});
+        else launch(std::true_type{}, std::false_type{});
     } else {
-        tiled_expand_kernel<W, BLOCK, false><<<grid, BLOCK, 0, s>>>(
-            plan.items.get(), first_item, num_items, commit_blocks, long_blocks, plan.a_val.get(), plan.a_lcol.get(), nullptr, d_x, plan.num_cols, sc.prod, lr,
-            d_state, commit);
+        if (packed) launch(std::false_type{}, std::integral_constant<bool, (W <= kPackedStripCols)>{});
+        else launch(std::false_type{}, std::false_type{});
     }
     return hipGetLastError();
 }

@@ -20,6 +20,8 @@ namespace {
 
 using namespace dev;
 
+typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
+
 constexpr int kMaxItemEntries = 16384;   // phase-1 work item size bounds (entries).  Round 4: 65536 -> 16384 — with the strip staging
                                          // pipelined, many short workgroups balance better than few long ones (C5 phase 1: 321.7 us with
                                          // ~53 K-slot items, 332.6 with 44 K (7.16 rounds of 512), 315.9 with 29 K, 315.2 with 22 K, 310.8-311.4 with
@@ -90,11 +92,47 @@ void weight_finish_kernel(float* __restrict__ weight, int n) {
     }
 }
 
+// The last step of the build on plans with strip_cols <= kPackedStripCols: the local columns, u16 per slot, into the
+// 14-bit blocks phase 1 reads (tiled_layout.h).  One wavefront per block of 256 slots: lane l holds the slots
+// 256 b + 4 l .. + 3 (zeros past the last slot), stores their low bytes as dword l of the low plane and hands its 24 high
+// bits to the lanes that store the high field's 48 dwords — dword d is bits 32 d .. 32 d + 31 of the field, lane k's
+// bits are 24 k .. 24 k + 23, so dword d takes the bits from 8 (4 d % 3) up of lane 4 d / 3 and the rest from the next lane.
+__global__ __launch_bounds__(kBlock)
+void pack_cols_kernel(long long slots, long long blocks, const unsigned short* __restrict__ a_lcol,
+                      unsigned char* __restrict__ cols14) {
+    const int lane = threadIdx.x & 63;
+    for (long long b = static_cast<long long>(blockIdx.x) * (kBlock / 64) + (threadIdx.x >> 6); b < blocks;
+         b += static_cast<long long>(gridDim.x) * (kBlock / 64)) {
+        const long long q = b * kColBlockSlots + 4 * lane;
+        unsigned int lo = 0, hi = 0;
+        u16x4 mine = {0, 0, 0, 0};
+        if (q + 3 < slots) {
+            mine = *reinterpret_cast<const u16x4*>(a_lcol + q);
+        } else {
+            for (int e = 0; e < 4 && q + e < slots; ++e) mine[e] = a_lcol[q + e];
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const unsigned int c = mine[e];
+            lo |= (c & 0xFFu) << (8 * e);
+            hi |= ((c >> 8) & 0x3Fu) << (6 * e);
+        }
+        unsigned char* block = cols14 + col_block_byte(q);
+        reinterpret_cast<unsigned int*>(block)[lane] = lo;
+        const int d = min(lane, 47);
+        const int from = 4 * d / 3, off = 8 * (4 * d % 3);
+        const unsigned int a = __shfl(hi, from, 64), next = __shfl(hi, from + 1, 64);
+        if (lane < 48) reinterpret_cast<unsigned int*>(block + kColLowBytes)[lane] = (a >> off) | (next << (24 - off));
+    }
+}
+
 // position-weighted checksums of the three slot streams and of the cell table (a debugging / test aid: two
 // builds of one matrix must give the same four numbers whatever path the builder took).  The row deltas are summed
 // where the finished plan keeps them: in pass order (pass_word), a function of the slots' bytes and the cell table alone.
+// The local columns are decoded where the plan holds them packed (cols14): the same number as over the u16 array.
 __global__ __launch_bounds__(kBlock)
 void plan_checksum_kernel(long long slots, const float* __restrict__ a_val, const unsigned short* __restrict__ a_lcol,
+                          const unsigned char* __restrict__ cols14,
                           long long delta_words, const unsigned int* __restrict__ pass_word,
                           long long table_ints, const int* __restrict__ cells_t,
                           unsigned long long* __restrict__ out /*[4]*/) {
@@ -103,7 +141,7 @@ void plan_checksum_kernel(long long slots, const float* __restrict__ a_val, cons
          i += static_cast<long long>(gridDim.x) * kBlock) {
         const unsigned long long w = 2 * static_cast<unsigned long long>(i) + 1;
         if (a_val) v += w * __float_as_uint(a_val[i]);
-        c += w * a_lcol[i];
+        c += w * static_cast<unsigned long long>(lcol_at(a_lcol, cols14, i));
     }
     for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < delta_words;
          i += static_cast<long long>(gridDim.x) * kBlock) {
@@ -324,8 +362,29 @@ hipError_t build_plan(const Source& src, TiledPlan** out, hipStream_t s) {
     e = dev_alloc(&plan->prod, plan->nnz + 8);
     if (e == hipSuccess) e = make_items(plan.get(), built.host_strip);
     if (e != hipSuccess) return e;
-
     trace.mark("fold probe, long rows, items");
+
+    // The local columns have served as u16 (placing passes, fold probe): phase 1 reads them packed to 14 bits wherever a
+    // strip has no more than 16384 columns (tiled_layout.h).  SPMV_DEBUG=cols=u16 keeps the u16 array: the A/B switch.
+    if (plan->strip_cols <= kPackedStripCols && plan->nnz > 0 && !debug_is("cols", "u16")) {
+        const long long blocks = (plan->nnz + kColBlockSlots - 1) / kColBlockSlots;
+        e = dev_alloc(&plan->a_cols14, packed_col_bytes(plan->nnz));
+        if (e != hipSuccess) return e;
+        // (the slack behind the last block is only ever loaded, never used: cleared so that no run reads unwritten memory)
+        e = hipMemsetAsync(plan->a_cols14.get() + blocks * kColBlockBytes, 0, kColSlackBytes, s);
+        if (e != hipSuccess) return e;
+        const int grid = static_cast<int>(std::min<long long>((blocks + kBlock / 64 - 1) / (kBlock / 64), 1 << 16));
+        pack_cols_kernel<<<grid, kBlock, 0, s>>>(plan->nnz, blocks, plan->a_lcol.get(), plan->a_cols14.get());
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return e;
+        plan->a_lcol.reset();
+        trace.mark("local columns packed");
+    }
+    // plan_bytes keeps its accounting, two bytes of local column per slot: the tests' host model of the plan
+    // (tests/tiled_model.py) holds the builder to that number.  For a packed plan it is an upper bound; col_bytes is
+    // what the plan holds of columns, so its footprint is plan_bytes - 2 * nnz + col_bytes.
+    plan->col_bytes = plan->a_cols14 ? packed_col_bytes(plan->nnz) : 2 * plan->nnz;
     plan->plan_bytes = plan->nnz * (4 /*prod*/ + 2 + (plan->a_val ? 4 : 0)) + cells * 8 +
                        plan->num_passes * static_cast<long long>(sizeof(PassDesc) + kPassSlots /*pass_word*/) +
                        4LL * (plan->num_tiles * kReduceWaves + 1) +
@@ -365,7 +424,7 @@ hipError_t tiled_checksum(const TiledPlan& plan, unsigned long long out[4], hipS
     if (e != hipSuccess) return e;
     e = hipMemsetAsync(d_out.get(), 0, 4 * sizeof(unsigned long long), s);
     if (e == hipSuccess) {
-        plan_checksum_kernel<<<1024, kBlock, 0, s>>>(plan.nnz, plan.a_val.get(), plan.a_lcol.get(), 64 * plan.num_passes,
+        plan_checksum_kernel<<<1024, kBlock, 0, s>>>(plan.nnz, plan.a_val.get(), plan.a_lcol.get(), plan.a_cols14.get(), 64 * plan.num_passes,
                                                      plan.pass_word.get(), 2LL * plan.num_strips * plan.num_tiles,
                                                      plan.cells_t.get(), d_out.get());
         e = hipGetLastError();

@@ -3,6 +3,7 @@
 #ifndef SPMV_AMD_TILED_LAYOUT_H
 #define SPMV_AMD_TILED_LAYOUT_H
 
+#include <cstddef>
 #include <type_traits>
 
 namespace spmv {
@@ -80,9 +81,54 @@ static_assert(sizeof(PassDesc) == 32, "a lane loads its pass descriptor as two 1
 // 16-byte offset, and the non-temporal product stores do not merge partial sectors: a sector split between two
 // instructions was written twice (WRITE_SIZE 653.6 -> 650.3 MB for 644.6 MB of products on the bench plan, phase 1
 // 311.6 -> 307.8 us; the remaining 5.7 MB are not explained — profiles/aligned_streams_traffic_ab.txt).
+// On a plan with packed columns (below) the origin is the 256-slot boundary at or below the first slot (begin & ~255):
+// still a whole sector, and a wavefront's 256 slots are then one column block.
+
+// ---- the local columns of a finished plan: 14 bits a slot in 448-byte blocks ----
+// A local column is below strip_cols, so on every plan with strip_cols <= kPackedStripCols it has 14 bits, and phase 1
+// reads it once per slot and step.  The placing passes, the fold probe and the pass layout work on the u16 array
+// (TiledPlan::a_lcol); pack_cols_kernel (tiled_build.hip) then packs it as the last step of the build and the u16 array
+// is freed, as a_drow is once pass_word holds its bytes.  The packed array (TiledPlan::a_cols14) is a sequence of BLOCKS
+// of kColBlockSlots = 256 slots in kColBlockBytes = 448 bytes, seven whole 64-byte sectors; block b starts at byte 448 b:
+//     bytes   0 .. 255   LOW plane: the low 8 bits of slot 256 b + i at byte i
+//     bytes 256 .. 447   HIGH field: the high 6 bits of slot 256 b + i at bits 6 i .. 6 i + 5 of these 192 bytes,
+//                        little-endian (bit k of the field is bit k % 8 of its byte k / 8)
+// A lane of phase 1 owns the four slots q .. q + 3, q a multiple of 4: their low bytes are the aligned dword at byte
+// (q & 255) of the block, their high bits the 24 bits that start at byte 256 + 3 ((q & 255) >> 2) — a 4-byte load at
+// that (unaligned) address, of which the top byte belongs to the next lane.  A wavefront of phase 1 (64 lanes, 4 slots
+// each) walks exactly one block per iteration.  Slots past the plan's last one hold zeros, and the allocation ends
+// kColSlackBytes behind the last block, so that the 4-byte load of the last lane's high bits stays inside it.
+// strip_cols == 32768 needs 15 bits: those plans keep the u16 array, as does every plan built under
+// SPMV_DEBUG=cols=u16 (the A/B switch, and the tests' comparator).
+constexpr int kPackedStripCols = 16384;
+constexpr int kColBlockSlots = 256;
+constexpr int kColBlockBytes = 448;
+constexpr int kColLowBytes = 256;
+constexpr int kColSlackBytes = 8;
+inline long long packed_col_bytes(long long slots) {
+    return (slots + kColBlockSlots - 1) / kColBlockSlots * kColBlockBytes + kColSlackBytes;
+}
 
 // ---- device side (the host-only tiled_plan.cpp reads the constants above) ----
 #ifdef __HIP__
+// byte at which the block of slot q starts / one slot's local column, decoded (edge loops, checksum: not the hot path)
+__device__ __forceinline__ size_t col_block_byte(long long q) {
+    return static_cast<size_t>(q >> 8) * kColBlockBytes;
+}
+__device__ __forceinline__ int packed_col_at(const unsigned char* __restrict__ cols14, long long k) {
+    const unsigned char* block = cols14 + col_block_byte(k);
+    const int i = static_cast<int>(k & (kColBlockSlots - 1));
+    const int bit = 6 * i, shift = bit & 7;
+    unsigned int field = block[kColLowBytes + (bit >> 3)];
+    if (shift > 2) field |= static_cast<unsigned int>(block[kColLowBytes + (bit >> 3) + 1]) << 8;
+    return static_cast<int>(block[i] | (((field >> shift) & 0x3Fu) << 8));
+}
+// the same for either form: exactly one of the two pointers is set
+__device__ __forceinline__ int lcol_at(const unsigned short* __restrict__ a_lcol, const unsigned char* __restrict__ cols14,
+                                       long long k) {
+    return cols14 ? packed_col_at(cols14, k) : a_lcol[k];
+}
+
 // Workgroups are dealt round-robin over the 8 XCDs (blocks b and b + 8 share one, each XCD has its
 // own L2).  Both phases hand every XCD a CONTIGUOUS range of the work list, walked in order:
 // neighbours in the list then run on one XCD at about the same time and share what they both

@@ -207,7 +207,8 @@ int spmv_c_tiled_shape(int64_t rows, int64_t cols, int64_t nnz, int32_t* strip_c
  * long-row limit; returns 0 if none */
 int spmv_c_csr_tiled_info(const spmv_c_csr* A, int64_t out[8]);
 /* extension: what the plan cost — out[4] = build time in ms (host wall clock, allocations included),
- * device bytes held, slots in cells, matrix entries in cells; returns 0 if the matrix has no plan */
+ * device bytes held (the local columns counted at two bytes a slot: see spmv_c_csr_tiled_col_bytes), slots in cells,
+ * matrix entries in cells; returns 0 if the matrix has no plan */
 int spmv_c_csr_tiled_stats(const spmv_c_csr* A, double out[4]);
 /* position-weighted checksums of the plan's slot arrays (values, local columns, row deltas) and its cell table:
  * two builds of one matrix give the same four numbers (the layout is a pure function of the matrix).  1 = filled. */
@@ -219,6 +220,11 @@ int spmv_c_csr_tiled_folded(const spmv_c_csr* A);
 /* extension: the number of phase-1 work items of the matrix's plan (every strip's slots cut into equal pieces of
  * at most the item size; SPMV_DEBUG=item=N sets that size); -1 without a plan.  Read-only, for boundary-case tests. */
 int spmv_c_csr_tiled_items(const spmv_c_csr* A);
+/* extension: the device bytes the matrix's plan holds of local columns: 2 per slot, or, where the plan packed them to
+ * 14 bits (strips of at most 16384 columns, unless SPMV_DEBUG=cols=u16), 448 for every 256 slots begun plus 8; -1
+ * without a plan.  spmv_c_csr_tiled_stats counts two bytes per slot in its "bytes held" either way, so a packed plan's
+ * footprint is that number - 2 * slots + this one. */
+int64_t spmv_c_csr_tiled_col_bytes(const spmv_c_csr* A);
 /* extension: the plan the LDS-tiled engine built from an ELL matrix's slabs (spmv_ell with use_texture), and the one
  * owned by the cached transpose of A (spmv_csr_transpose with use_texture) — out[10] = the eight numbers of
  * spmv_c_csr_tiled_info, then values folded (0 / 1) and the phase-1 item count; returns 0 if there is none (not
