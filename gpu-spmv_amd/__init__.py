@@ -346,6 +346,14 @@ class AMGConfig(Structure):
         super().__init__(max_levels, coarse_rows, strength, pre_sweeps, post_sweeps, jacobi_weight, coarse_sweeps)
 
 
+class AMGSmoothing(Structure):
+    """include/spmv/amg.h AMGSmoothing (8 bytes), with its defaults"""
+    _fields_ = [("prolongator_weight", c_float), ("strength_decay", c_float)]
+
+    def __init__(self, prolongator_weight=2.0 / 3.0, strength_decay=0.5):
+        super().__init__(prolongator_weight, strength_decay)
+
+
 class AMGResult(Structure):
     """include/spmv/amg.h AMGResult (48 bytes); bad_level / bad_row name the row a diagonal or pivot check failed at"""
     _fields_ = [("error_code", c_int32), ("levels", c_int32), ("coarse_solver", c_int32), ("bad_row", c_int32),
@@ -491,6 +499,15 @@ _SIGNATURES = {
     "spmv_c_amg_setup_device": (c_int, [POINTER(c_void_p), POINTER(CSRMatrix), POINTER(AMGConfig), ctypes.c_uint32,
                                         POINTER(AMGResult)]),
     "spmv_c_amg_setup_rounds": (c_int, [c_void_p, c_int]),
+    "spmv_c_amg_setup_smoothed": (c_int, [POINTER(c_void_p), POINTER(CSRMatrix), POINTER(AMGConfig),
+                                          POINTER(AMGSmoothing), c_int, POINTER(c_void_p), POINTER(AMGResult)]),
+    "spmv_c_amg_setup_smoothed_device": (c_int, [POINTER(c_void_p), POINTER(CSRMatrix), POINTER(AMGConfig),
+                                                 POINTER(AMGSmoothing), ctypes.c_uint32, POINTER(AMGResult)]),
+    "spmv_c_amg_is_smoothed": (c_int, [c_void_p]),
+    "spmv_c_amg_level_transfer": (c_int, [c_void_p, c_int, POINTER(CSRMatrix), POINTER(CSRMatrix)]),
+    "spmv_c_amg_prolongator_cpu_csr": (c_int, [POINTER(CSRMatrix), POINTER(CSRMatrix), c_void_p, c_int, c_float]),
+    "spmv_c_amg_restrict": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "spmv_c_amg_prolong": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "spmv_c_cg_solve_amg": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, c_void_p, POINTER(CGConfig),
                                     POINTER(CGResult)]),
     "spmv_c_sptrsv_csr": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(SpTRSVConfig),
@@ -1402,6 +1419,59 @@ def amg_setup_device(A, config=None, seed=0):
 def amg_setup_rounds(H, level) -> int:
     """Rounds the root selection of level `level` took (0: the coarsest level, or a hierarchy amg_setup built)."""
     return lib().spmv_c_amg_setup_rounds(H, int(level))
+
+
+def amg_setup_smoothed(A, config=None, smoothing=None, aggregates=None):
+    """(AMGResult, hierarchy handle or None): amg_setup with smoothed prolongators (amg.h amg_setup_smoothed);
+    smoothing: an AMGSmoothing or None (the defaults)."""
+    out, handle = AMGResult(), c_void_p()
+    maps, table = None, None
+    if aggregates is not None:
+        maps = [np.ascontiguousarray(a, dtype=np.int32) for a in aggregates]
+        table = (c_void_p * max(len(maps), 1))(*[a.ctypes.data for a in maps])
+    lib().spmv_c_amg_setup_smoothed(byref(handle), A, byref(config) if config is not None else None,
+                                    byref(smoothing) if smoothing is not None else None,
+                                    len(maps) if maps is not None else 0, table, byref(out))
+    return out, (handle.value if handle.value else None)
+
+
+def amg_setup_smoothed_device(A, config=None, smoothing=None, seed=0):
+    """(AMGResult, hierarchy handle or None): amg_setup_device with smoothed prolongators (amg.h
+    amg_setup_smoothed_device)."""
+    out, handle = AMGResult(), c_void_p()
+    lib().spmv_c_amg_setup_smoothed_device(byref(handle), A, byref(config) if config is not None else None,
+                                           byref(smoothing) if smoothing is not None else None,
+                                           int(seed) & 0xFFFFFFFF, byref(out))
+    return out, (handle.value if handle.value else None)
+
+
+def amg_is_smoothed(H) -> int:
+    return lib().spmv_c_amg_is_smoothed(H)
+
+
+def amg_level_transfer(H, level):
+    """(status, P_view, PT_view): the prolongator of level `level` and its transpose as CSRMatrix headers over device
+    arrays that own nothing (amg.h amg_level_transfer)."""
+    p_view, pt_view = CSRMatrix(), CSRMatrix()
+    status = lib().spmv_c_amg_level_transfer(H, int(level), byref(p_view), byref(pt_view))
+    return status, p_view, pt_view
+
+
+def amg_prolongator_cpu_csr(P, A, aggregate, num_aggregates, weight=2.0 / 3.0) -> int:
+    """P = the smoothed prolongator of one level from A's host arrays and the aggregate map, the host definition
+    (amg.h amg_prolongator_cpu_csr)."""
+    agg = np.ascontiguousarray(aggregate, dtype=np.int32)
+    return lib().spmv_c_amg_prolongator_cpu_csr(P, A, _np_ptr(agg), int(num_aggregates), float(weight))
+
+
+def amg_restrict(H, level, d_f, d_x, d_f_coarse) -> int:
+    """d_f_coarse = P^T (d_f - A_l d_x) on level `level` (amg.h amg_restrict)."""
+    return lib().spmv_c_amg_restrict(H, int(level), _dev(d_f), _dev(d_x), _dev(d_f_coarse))
+
+
+def amg_prolong(H, level, d_e, d_x) -> int:
+    """d_x += P d_e on level `level`, in place (amg.h amg_prolong)."""
+    return lib().spmv_c_amg_prolong(H, int(level), _dev(d_e), _dev(d_x))
 
 
 def cg_solve_amg(A, H, d_b, d_x, config=None) -> CGResult:

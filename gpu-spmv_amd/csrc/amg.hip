@@ -7,6 +7,10 @@
 // `done` of the CG state inside cg_solve_amg) and returns at once when it is set.  The rows of a level are spread over
 // groups of LANES lanes as in cg_spmv_dot; the restriction gives one group to an aggregate, which walks its member
 // rows one after another and adds their residuals in fp32 in member order, so the fine residual is never stored.
+//
+// A smoothed hierarchy has real matrices for both transfers: its levels take, in place of the two
+// launches above, one amg_residual_kernel (r = f - A x, stored), one amg_restrict_weighted_kernel (PT r) and one
+// amg_prolong_kernel (x += P e), each the same row sweep over its own matrix at its own lane count.
 #include "amg_impl.h"
 #include "internal.h"
 #include "device_common.h"
@@ -98,6 +102,43 @@ void amg_correct_kernel(int n, const int* __restrict__ aggregate, const float* _
     }
 }
 
+// r_i = f_i - (A x)_i, stored for the weighted restriction
+template <int LANES>
+__global__ __launch_bounds__(kBlock)
+void amg_residual_kernel(int n, long long nnz, const int* __restrict__ row_ptrs, const int* __restrict__ cols,
+                         const float* __restrict__ vals, const float* __restrict__ f, const float* __restrict__ x,
+                         float* __restrict__ r, const int* __restrict__ done) {
+    if (finished(done)) return;
+    for_each_row_dot<LANES>(n, nnz, row_ptrs, cols, vals, x, [&](long long row, float acc) {
+        r[row] = __fsub_rn(f[row], acc);
+    });
+}
+
+// f_coarse[a] = (PT r)_a: PT's arrays, one lane group per aggregate
+template <int LANES>
+__global__ __launch_bounds__(kBlock)
+void amg_restrict_weighted_kernel(int num_aggregates, long long nnz, const int* __restrict__ row_ptrs,
+                                  const int* __restrict__ cols, const float* __restrict__ vals,
+                                  const float* __restrict__ r, float* __restrict__ f_coarse,
+                                  const int* __restrict__ done) {
+    if (finished(done)) return;
+    for_each_row_dot<LANES>(num_aggregates, nnz, row_ptrs, cols, vals, r, [&](long long row, float acc) {
+        f_coarse[row] = acc;
+    });
+}
+
+// x_out_i = x_in_i + (P e)_i: P's arrays; x_out may be x_in itself (each element is read and written by one lane)
+template <int LANES>
+__global__ __launch_bounds__(kBlock)
+void amg_prolong_kernel(int n, long long nnz, const int* __restrict__ row_ptrs, const int* __restrict__ cols,
+                        const float* __restrict__ vals, const float* __restrict__ e, const float* x_in, float* x_out,
+                        const int* __restrict__ done) {
+    if (finished(done)) return;
+    for_each_row_dot<LANES>(n, nnz, row_ptrs, cols, vals, e, [&](long long row, float acc) {
+        x_out[row] = __fadd_rn(x_in[row], acc);
+    });
+}
+
 // z_i = sum_j cinv[i * n + j] * f_j: one wavefront per row, lane t takes j = t, t + 64, ... in fp64 (the products
 // are exact), the lanes are folded by the xor butterfly 32, 16, ... 1, and the sum is rounded once
 __global__ __launch_bounds__(kBlock)
@@ -139,6 +180,52 @@ struct Cycle {
                 M.num_rows, M.nnz, M.d_row_ptrs, M.d_col_indices, M.d_values, lv.d_wd, f, x_in, x_out, done);
             return hipGetLastError();
         });
+    }
+
+    // the row sweep of one of the three kernels below over M: kernel<LANES>(rows, nnz, M's arrays, args..., done)
+    template <class Launch>
+    hipError_t row_sweep(const CSRMatrix& M, int lanes, Launch&& launch) const {
+        return with_lanes(forced ? forced : lanes, [&](auto L) {
+            constexpr int kLanes = decltype(L)::value;
+            launch(L, capped_grid(M.num_rows, kBlock / kLanes));
+            return hipGetLastError();
+        });
+    }
+
+    hipError_t residual(const AMGLevel& lv, const float* f, const float* x, float* r) const {
+        const CSRMatrix& M = lv.view;
+        return row_sweep(M, lv.lanes, [&](auto L, int grid) {
+            amg_residual_kernel<decltype(L)::value><<<grid, kBlock, 0, s>>>(
+                M.num_rows, M.nnz, M.d_row_ptrs, M.d_col_indices, M.d_values, f, x, r, done);
+        });
+    }
+
+    hipError_t restrict_weighted(const AMGLevel& lv, const float* r, float* f_coarse) const {
+        const CSRMatrix& M = *lv.PT;
+        return row_sweep(M, lv.pt_lanes, [&](auto L, int grid) {
+            amg_restrict_weighted_kernel<decltype(L)::value><<<grid, kBlock, 0, s>>>(
+                M.num_rows, M.nnz, M.d_row_ptrs, M.d_col_indices, M.d_values, r, f_coarse, done);
+        });
+    }
+
+    hipError_t prolong(const AMGLevel& lv, const float* e, const float* x_in, float* x_out) const {
+        const CSRMatrix& M = *lv.P;
+        return row_sweep(M, lv.p_lanes, [&](auto L, int grid) {
+            amg_prolong_kernel<decltype(L)::value><<<grid, kBlock, 0, s>>>(
+                M.num_rows, M.nnz, M.d_row_ptrs, M.d_col_indices, M.d_values, e, x_in, x_out, done);
+        });
+    }
+
+    // f_coarse = the restricted residual of (f, x), by the hierarchy's kind
+    hipError_t down(const AMGLevel& lv, const float* f, const float* x, float* f_coarse) const {
+        if (!H.smoothed) return restrict_to(lv, f, x, f_coarse);
+        const hipError_t e = residual(lv, f, x, lv.d_res);
+        return e == hipSuccess ? restrict_weighted(lv, lv.d_res, f_coarse) : e;
+    }
+
+    // x_out = x_in + the prolonged e, by the hierarchy's kind
+    hipError_t up(const AMGLevel& lv, const float* e, const float* x_in, float* x_out) const {
+        return H.smoothed ? prolong(lv, e, x_in, x_out) : correct(lv, e, x_in, x_out);
     }
 
     hipError_t restrict_to(const AMGLevel& lv, const float* f, const float* x, float* f_coarse) const {
@@ -200,7 +287,7 @@ hipError_t amg_vcycle(const AMGHierarchy& H, const float* d_r, float* d_z, const
     for (int l = 0; e == hipSuccess && l < coarsest; ++l) {
         const AMGLevel& lv = H.levels[l];
         e = cycle.sweeps_from_zero(lv, f_of(l), H.config.pre_sweeps, xa_of(l), xb_of(l), nullptr, &x_at[l]);
-        if (e == hipSuccess) e = cycle.restrict_to(lv, f_of(l), x_at[l], H.levels[l + 1].d_work);
+        if (e == hipSuccess) e = cycle.down(lv, f_of(l), x_at[l], H.levels[l + 1].d_work);
     }
     if (e != hipSuccess) return e;
     // the coarsest level
@@ -225,10 +312,10 @@ hipError_t amg_vcycle(const AMGHierarchy& H, const float* d_r, float* d_z, const
         const float* err = out_of(l + 1);
         float* cur = const_cast<float*>(x_at[l]);
         if (post == 0) {
-            e = cycle.correct(lv, err, cur, out_of(l));
+            e = cycle.up(lv, err, cur, out_of(l));
             continue;
         }
-        e = cycle.correct(lv, err, cur, cur);
+        e = cycle.up(lv, err, cur, cur);
         for (int k = 0; e == hipSuccess && k < post; ++k) {
             float* next = k == post - 1 ? out_of(l) : (cur == xa_of(l) ? xb_of(l) : xa_of(l));
             e = cycle.sweep(lv, f_of(l), cur, next);
@@ -252,6 +339,60 @@ int amg_apply(const AMGHierarchy* H, const float* d_r, float* d_z) {
         return code(SpMVError::KERNEL_LAUNCH);
     }
     return 0;
+}
+
+namespace {
+
+// the checks amg_restrict and amg_prolong share; 0, or an SpMVError code
+int transfer_level_checked(const AMGHierarchy* H, int level, bool pointers_ok) {
+    using namespace detail;
+    if (!H || !pointers_ok || H->levels.empty()) return code(SpMVError::INVALID_ARGUMENT);
+    if (level < 0 || level + 1 >= static_cast<int>(H->levels.size())) return code(SpMVError::INVALID_DIMENSION);
+    return 0;
+}
+
+// [a, a + na) and [b, b + nb) floats share a byte
+bool floats_overlap(const float* a, long long na, const float* b, long long nb) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + static_cast<uintptr_t>(nb) * sizeof(float) && b0 < a0 + static_cast<uintptr_t>(na) * sizeof(float);
+}
+
+int transfer_finished(hipError_t e, hipStream_t stream) {
+    using namespace detail;
+    if (e != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
+        (void)hipGetLastError();
+        return code(SpMVError::KERNEL_LAUNCH);
+    }
+    return 0;
+}
+
+} // namespace
+
+int amg_restrict(const AMGHierarchy* H, int level, const float* d_f, const float* d_x, float* d_f_coarse) {
+    using namespace detail;
+    if (const int status = transfer_level_checked(H, level, d_f && d_x && d_f_coarse)) return status;
+    const AMGLevel& lv = H->levels[static_cast<size_t>(level)];
+    const long long n = lv.view.num_rows, nc = lv.num_aggregates;
+    if (floats_overlap(d_f_coarse, nc, d_f, n) || floats_overlap(d_f_coarse, nc, d_x, n)) {
+        return code(SpMVError::INVALID_ARGUMENT);
+    }
+    const TraceRange range("spmv:amg_restrict");
+    hipStream_t stream = current_stream();
+    const Cycle cycle{*H, nullptr, amg_forced_lanes(), stream};
+    return transfer_finished(cycle.down(lv, d_f, d_x, d_f_coarse), stream);
+}
+
+int amg_prolong(const AMGHierarchy* H, int level, const float* d_e, float* d_x) {
+    using namespace detail;
+    if (const int status = transfer_level_checked(H, level, d_e && d_x)) return status;
+    const AMGLevel& lv = H->levels[static_cast<size_t>(level)];
+    if (floats_overlap(d_e, lv.num_aggregates, d_x, lv.view.num_rows)) {
+        return code(SpMVError::INVALID_ARGUMENT);
+    }
+    const TraceRange range("spmv:amg_prolong");
+    hipStream_t stream = current_stream();
+    const Cycle cycle{*H, nullptr, amg_forced_lanes(), stream};
+    return transfer_finished(cycle.up(lv, d_e, d_x, d_x), stream);
 }
 
 } // namespace spmv

@@ -1,9 +1,11 @@
 // amg_host.cpp — the setup of the aggregation AMG (include/spmv/amg.h): argument checks, the host
 // aggregation (amg_aggregate_cpu_csr is its definition), the Galerkin products through csr_transpose_gpu and
 // spgemm_csr, the diagonals, and the fp64 Cholesky inverse of the coarsest level.  Setup runs once per matrix and is
-// not the hot path; the V-cycle's kernels are in amg.hip.
+// not the hot path; the V-cycle's kernels are in amg.hip.  amg_setup_smoothed shares the builder: its coarsening step
+// is detail::amg_smooth_coarsen (amg_setup.hip), and amg_prolongator_cpu_csr here is that step's P on host arrays.
 #include "amg_impl.h"
 #include "internal.h"
+#include "spmv/csr_ops.h"
 #include "spmv/spgemm.h"
 
 #include <hip/hip_runtime.h>
@@ -142,6 +144,7 @@ struct Builder {
     AMGHierarchy& H;
     AMGResult& res;
     hipStream_t stream;
+    std::vector<float> diag{};    // diagonal_of's d of the level it ran on last
 
     int fail(SpMVError e, int level = -1, int row = -1) {
         res.error_code = code(e);
@@ -173,7 +176,7 @@ struct Builder {
     int diagonal_of(int l, const std::vector<float>& va) {
         AMGLevel& lv = H.levels[static_cast<size_t>(l)];
         const int n = lv.view.num_rows;
-        std::vector<float> d;
+        std::vector<float>& d = diag;
         std::vector<char> found;
         amg_diagonal(n, lv.row_ptrs.data(), lv.cols.data(), va.data(), &d, &found);
         std::vector<float> wd(static_cast<size_t>(n));
@@ -225,16 +228,23 @@ struct Builder {
         CSRMatrix* PT = csr_create(0, 0, 0);
         CSRMatrix* AP = csr_create(0, 0, 0);
         CSRMatrix* next = csr_create(0, 0, 0);
+        CSRMatrix* AT = H.smoothed ? csr_create(0, 0, 0) : nullptr;
+        CSRMatrix* smoothed_P = H.smoothed ? csr_create(0, 0, 0) : nullptr;
         {
             AMGLevel& lv = H.levels[static_cast<size_t>(l)];     // owners first: every exit frees them with H
             lv.P = P;
             lv.PT = PT;
             lv.AP = AP;
             lv.num_aggregates = count;
+            if (H.smoothed) {                                    // the unit P built below is the tentative one
+                lv.T = P;
+                lv.P = smoothed_P;
+                lv.AT = AT;
+            }
         }
         H.levels.emplace_back();
         H.levels.back().A = next;
-        if (!P || !PT || !AP || !next) return fail(SpMVError::OUT_OF_MEMORY);
+        if (!P || !PT || !AP || !next || (H.smoothed && (!AT || !smoothed_P))) return fail(SpMVError::OUT_OF_MEMORY);
         for (int i = 0; i < n; ++i) {
             P->row_ptrs[i] = i;
             P->col_indices[i] = agg[static_cast<size_t>(i)];
@@ -242,12 +252,36 @@ struct Builder {
         }
         P->row_ptrs[n] = n;
         int status = csr_to_gpu(P);
+        if (H.smoothed) {
+            if (status == 0) status = smooth(l, false);
+            if (status != 0) return fail(static_cast<SpMVError>(status));
+            H.levels.back().view = device_view(next);
+            return 0;
+        }
         if (status == 0) status = csr_transpose_gpu(PT, P);
         if (status == 0) status = spgemm_csr(AP, &H.levels[static_cast<size_t>(l)].view, P);
         if (status == 0) status = spgemm_csr(next, PT, AP);
         if (status != 0) return fail(static_cast<SpMVError>(status));
         H.levels.back().view = device_view(next);
         return 0;
+    }
+
+    // the smoothed-aggregation step of level l with diagonal_of's d uploaded; an SpMVError code
+    int smooth(int l, bool refill) {
+        float* d_diag = nullptr;
+        if (hipMalloc(reinterpret_cast<void**>(&d_diag), diag.size() * sizeof(float)) != hipSuccess) {
+            (void)hipGetLastError();
+            return code(SpMVError::CUDA_MALLOC);
+        }
+        int status = 0;
+        if (hipMemcpyAsync(d_diag, diag.data(), diag.size() * sizeof(float), hipMemcpyHostToDevice, stream) != hipSuccess ||
+            hipStreamSynchronize(stream) != hipSuccess) {
+            (void)hipGetLastError();
+            status = code(SpMVError::CUDA_MEMCPY);
+        }
+        if (status == 0) status = detail::amg_smooth_coarsen(H, l, d_diag, refill, stream);
+        (void)hipFree(d_diag);
+        return status;
     }
 
     int workspace(int l) {
@@ -281,6 +315,11 @@ float ms_since(std::chrono::steady_clock::time_point start) {
 } // namespace
 
 namespace detail {
+
+bool amg_smoothing_ok(const AMGSmoothing& sm) {
+    return sm.prolongator_weight > 0.0f && sm.prolongator_weight < 2.0f && sm.strength_decay > 0.0f &&
+           sm.strength_decay <= 1.0f;
+}
 
 bool amg_config_ok(const AMGConfig& cfg) {
     return !(cfg.max_levels < 1 || cfg.coarse_rows < 1 || cfg.coarse_rows > kAmgDenseRows || !(cfg.strength >= 0.0f) ||
@@ -327,6 +366,10 @@ void amg_destroy(AMGHierarchy* H) {
         if (lv.P) csr_destroy(lv.P);
         if (lv.PT) csr_destroy(lv.PT);
         if (lv.AP) csr_destroy(lv.AP);
+        if (lv.T) csr_destroy(lv.T);
+        if (lv.AT) csr_destroy(lv.AT);
+        if (lv.d_s) (void)hipFree(lv.d_s);
+        if (lv.d_res) (void)hipFree(lv.d_res);
         if (lv.d_wd) (void)hipFree(lv.d_wd);
         if (lv.d_work) (void)hipFree(lv.d_work);
     }
@@ -334,7 +377,11 @@ void amg_destroy(AMGHierarchy* H) {
     delete H;
 }
 
-AMGResult amg_setup(AMGHierarchy** out, const CSRMatrix* A, const AMGConfig* config, const AMGAggregates* aggregates) {
+namespace {
+
+// amg_setup (smoothing == nullptr) and amg_setup_smoothed
+AMGResult setup(AMGHierarchy** out, const CSRMatrix* A, const AMGConfig* config, const AMGSmoothing* smoothing,
+                const AMGAggregates* aggregates) {
     const auto start = std::chrono::steady_clock::now();
     AMGResult res;
     const auto fail = [&res](SpMVError e) {
@@ -348,6 +395,7 @@ AMGResult amg_setup(AMGHierarchy** out, const CSRMatrix* A, const AMGConfig* con
     const AMGConfig defaults;
     const AMGConfig& cfg = config ? *config : defaults;
     if (!detail::amg_config_ok(cfg)) return fail(SpMVError::INVALID_ARGUMENT);
+    if (smoothing && !detail::amg_smoothing_ok(*smoothing)) return fail(SpMVError::INVALID_ARGUMENT);
     // caller-given maps: sizes and contents, on the host
     int given = 0;
     std::vector<int> given_rows;        // n_{l+1} of each used map
@@ -375,9 +423,14 @@ AMGResult amg_setup(AMGHierarchy** out, const CSRMatrix* A, const AMGConfig* con
         }
     }
 
-    const detail::TraceRange range("spmv:amg_setup");
+    const detail::TraceRange range(smoothing ? "spmv:amg_setup_smoothed" : "spmv:amg_setup");
     std::unique_ptr<AMGHierarchy, void (*)(AMGHierarchy*)> H(new AMGHierarchy, amg_destroy);
     H->config = cfg;
+    if (smoothing) {
+        H->smoothed = true;
+        H->smoothing = *smoothing;
+    }
+    float theta = cfg.strength;      // theta_l: constant on a plain hierarchy
     H->num_rows = A->num_rows;
     H->nnz = A->nnz;
     H->levels.emplace_back();
@@ -397,16 +450,76 @@ AMGResult amg_setup(AMGHierarchy** out, const CSRMatrix* A, const AMGConfig* con
         } else {
             if (n <= cfg.coarse_rows || l + 1 == cfg.max_levels) break;
             agg.resize(static_cast<size_t>(n));
-            count = aggregate(n, lv.row_ptrs.data(), lv.cols.data(), va.data(), cfg.strength, agg.data());
+            count = aggregate(n, lv.row_ptrs.data(), lv.cols.data(), va.data(), theta, agg.data());
             if (count == n) break;                      // nothing is strong any more
         }
         if (b.coarsen(l, agg, count) != 0) return res;
+        if (smoothing) theta = theta * smoothing->strength_decay;
     }
     if (b.coarse_solver(va) != 0) return res;
     b.complexities();
     res.setup_ms = ms_since(start);
     *out = H.release();
     return res;
+}
+
+} // namespace
+
+AMGResult amg_setup(AMGHierarchy** out, const CSRMatrix* A, const AMGConfig* config, const AMGAggregates* aggregates) {
+    return setup(out, A, config, nullptr, aggregates);
+}
+
+AMGResult amg_setup_smoothed(AMGHierarchy** out, const CSRMatrix* A, const AMGConfig* config,
+                             const AMGSmoothing* smoothing, const AMGAggregates* aggregates) {
+    const AMGSmoothing defaults;
+    return setup(out, A, config, smoothing ? smoothing : &defaults, aggregates);
+}
+
+int amg_is_smoothed(const AMGHierarchy* H) { return H && H->smoothed ? 1 : 0; }
+
+int amg_level_transfer(const AMGHierarchy* H, int level, CSRMatrix* P_view, CSRMatrix* PT_view) {
+    if (!H) return code(SpMVError::INVALID_ARGUMENT);
+    if (level < 0 || level + 1 >= static_cast<int>(H->levels.size())) return code(SpMVError::INVALID_DIMENSION);
+    const AMGLevel& lv = H->levels[static_cast<size_t>(level)];
+    if (P_view) *P_view = device_view(lv.P);
+    if (PT_view) *PT_view = device_view(lv.PT);
+    return 0;
+}
+
+int amg_prolongator_cpu_csr(CSRMatrix* P, const CSRMatrix* A, const int* aggregate_map, int num_aggregates,
+                            float weight) {
+    if (!P || !A || !aggregate_map) return code(SpMVError::INVALID_ARGUMENT);
+    if (A->num_rows != A->num_cols) return code(SpMVError::INVALID_DIMENSION);
+    const int n = A->num_rows;
+    if (n < 0 || A->nnz < 0 || !A->row_ptrs || (A->nnz > 0 && (!A->col_indices || !A->values)) ||
+        !amg_structure_ok(n, A->nnz, A->row_ptrs, A->col_indices)) {
+        return code(SpMVError::INVALID_FORMAT);
+    }
+    if (!(weight > 0.0f && weight < 2.0f) || num_aggregates < 1) return code(SpMVError::INVALID_ARGUMENT);
+    for (int i = 0; i < n; ++i) {
+        if (aggregate_map[i] < 0 || aggregate_map[i] >= num_aggregates) return code(SpMVError::INVALID_ARGUMENT);
+    }
+    std::vector<float> d;
+    std::vector<char> found;
+    amg_diagonal(n, A->row_ptrs, A->col_indices, A->values, &d, &found);
+    std::vector<float> scale(static_cast<size_t>(n));
+    for (int i = 0; i < n; ++i) {
+        if (!found[i] || !(d[i] > 0.0f) || !std::isfinite(d[i])) return code(SpMVError::INVALID_ARGUMENT);
+        scale[i] = static_cast<float>(-static_cast<double>(weight) / static_cast<double>(d[i]));
+    }
+    const std::unique_ptr<CSRMatrix, void (*)(CSRMatrix*)> T(csr_create(n, num_aggregates, n), csr_destroy),
+        AT(csr_create(0, 0, 0), csr_destroy);
+    if (!T || !AT) return code(SpMVError::OUT_OF_MEMORY);
+    for (int i = 0; i < n; ++i) {
+        T->row_ptrs[i] = i;
+        T->col_indices[i] = aggregate_map[i];
+        T->values[i] = 1.0f;
+    }
+    T->row_ptrs[n] = n;
+    int status = spgemm_cpu_csr(AT.get(), A, T.get());
+    if (status == 0) status = csr_scale_cpu(AT.get(), scale.data(), nullptr, AT->values);     // S, in place
+    if (status == 0) status = csr_add_cpu(P, 1.0f, T.get(), 1.0f, AT.get());
+    return status;
 }
 
 AMGResult amg_update(AMGHierarchy* H, const CSRMatrix* A) {
@@ -431,8 +544,13 @@ AMGResult amg_update(AMGHierarchy* H, const CSRMatrix* A) {
         if (b.download(l, l == 0, &va) != 0 || b.diagonal_of(l, va) != 0) return res;
         if (l + 1 == levels) break;
         AMGLevel& lv = H->levels[static_cast<size_t>(l)];
-        int status = spgemm_csr_numeric(lv.AP, &lv.view, lv.P);
-        if (status == 0) status = spgemm_csr_numeric(H->levels[static_cast<size_t>(l) + 1].A, lv.PT, lv.AP);
+        int status = 0;
+        if (H->smoothed) {
+            status = b.smooth(l, true);
+        } else {
+            status = spgemm_csr_numeric(lv.AP, &lv.view, lv.P);
+            if (status == 0) status = spgemm_csr_numeric(H->levels[static_cast<size_t>(l) + 1].A, lv.PT, lv.AP);
+        }
         if (status != 0) return fail(static_cast<SpMVError>(status));
     }
     if (b.coarse_solver(va) != 0) return res;
@@ -453,7 +571,8 @@ int amg_level(const AMGHierarchy* H, int level, CSRMatrix* view, const int** d_a
     if (level < 0 || level >= static_cast<int>(H->levels.size())) return code(SpMVError::INVALID_DIMENSION);
     const AMGLevel& lv = H->levels[static_cast<size_t>(level)];
     if (view) *view = lv.view;
-    if (d_aggregate) *d_aggregate = lv.P ? lv.P->d_col_indices : nullptr;
+    const CSRMatrix* tentative = lv.T ? lv.T : lv.P;
+    if (d_aggregate) *d_aggregate = tentative ? tentative->d_col_indices : nullptr;
     if (num_aggregates) *num_aggregates = lv.num_aggregates;
     return 0;
 }

@@ -28,6 +28,12 @@ struct AMGLevel {
     CSRMatrix* P = nullptr;       // n_l x n_{l+1}, one unit entry per row; its column array is the aggregate map
     CSRMatrix* PT = nullptr;      // its transpose: the member list of each aggregate, rows ascending
     CSRMatrix* AP = nullptr;      // A_l P_l, kept for amg_update's refill
+    // a smoothed hierarchy only (amg_setup_smoothed): P above is the smoothed prolongator, PT its transpose with values
+    CSRMatrix* T = nullptr;       // the tentative prolongator (what P is on a plain hierarchy): its columns are the map
+    CSRMatrix* AT = nullptr;      // A_l T_l, kept for the refill
+    float* d_s = nullptr;         // [n] s_i = float(-double(omega_p) / double(d_i)), then [nnz(AT)] S = diag(s) AT
+    float* d_res = nullptr;       // [n] the residual the weighted restriction reads
+    int p_lanes = 1, pt_lanes = 1;     // pick_lanes_per_row of P's and of PT's mean row length
     int num_aggregates = 0;
     int lanes = 1;                // pick_lanes_per_row of the mean row length
     float* d_wd = nullptr;        // [n] omega / d_i
@@ -45,6 +51,8 @@ struct AMGHierarchy {
     int coarse_solver = 0;
     float* d_cinv = nullptr;      // coarse_solver 0: [n_c * n_c] row-major
     bool device_built = false;    // amg_setup_device made it: amg_update keeps the levels off the host
+    bool smoothed = false;        // amg_setup_smoothed / amg_setup_smoothed_device made it
+    AMGSmoothing smoothing;
 };
 
 namespace detail {
@@ -92,6 +100,14 @@ int amg_level_workspace(AMGHierarchy& H, AMGResult& res, int l);          // lan
 int amg_finish(AMGHierarchy& H, AMGResult& res, hipStream_t s);
 // amg_setup.hip: amg_update on a hierarchy amg_setup_device built (the argument checks have passed)
 AMGResult amg_update_device(AMGHierarchy* H, const CSRMatrix* A);
+bool amg_smoothing_ok(const AMGSmoothing& sm);                  // the ranges of amg.h
+// amg_setup.hip: the smoothed-aggregation step of level l, for both builders.  lv.T holds the tentative prolongator on
+// the device, lv.P / PT / AP / AT and level l + 1's A exist (empty at setup, filled by it for a refill), d_diag is the
+// level's diagonal on the device (n floats, checked).  In this order: AT = A_l T, s, S = diag(s) AT, P = T + S,
+// PT = P^T, AP = A_l P, A_{l+1} = PT AP.  refill: the values alone through the *_numeric forms, except PT, which is
+// transposed again (csr_transpose_gpu has no values-only form: PT's arrays are released and allocated anew).
+// Returns 0 or the SpMVError code of the call that failed.
+int amg_smooth_coarsen(AMGHierarchy& H, int l, const float* d_diag, bool refill, hipStream_t s);
 
 // The V-cycle's launches on `s`, none synchronises.  d_done (may be null) points at a device int: every kernel returns
 // at once when it is not 0 (the `done` of a solver's state).  forced_lanes: 0, or the lane count every level takes.

@@ -17,10 +17,13 @@
 //   phase 1, 2   lanes share a row again; phase 1 writes a second array so that phase 2 reads end-of-phase-1
 //                membership; phase 2 folds (|v|, storage position) to the maximum, ties to the smaller position
 //   P            row_ptrs = iota, cols = the aggregate map (phase 2 writes it in place), vals = 1
+//   smoothing    amg_smooth_coarsen, the coarsening step of a smoothed hierarchy for this builder and amg_host.cpp's:
+//                P = T + diag(s) (A T) through spgemm_csr, csr_scale_gpu and csr_add, then P^T and the two products
 // No kernel here waits for another workgroup; none uses an atomic on a value.
 #include "amg_impl.h"
 #include "reorder_impl.h"
 #include "solver_common.h"
+#include "spmv/csr_ops.h"
 #include "spmv/spgemm.h"
 
 #include <chrono>
@@ -279,6 +282,15 @@ __global__ __launch_bounds__(kBlock) void amg_prolongation_kernel(int n, int* __
     }
 }
 
+// s_i = float(-double(omega_p) / double(d_i)): the row scale of the smoothed prolongator
+__global__ __launch_bounds__(kBlock) void amg_smoothing_scale_kernel(int n, float omega_p, const float* __restrict__ d,
+                                                                     float* __restrict__ scale) {
+    for (long long i = blockIdx.x * static_cast<long long>(kBlock) + threadIdx.x; i < n;
+         i += static_cast<long long>(gridDim.x) * kBlock) {
+        scale[i] = static_cast<float>(-static_cast<double>(omega_p) / static_cast<double>(d[i]));
+    }
+}
+
 int mis_lanes_for(const CSRMatrix& M) {
     if (int f = forced_lanes("mis_lanes")) return f;
     return pick_lanes_per_row(static_cast<float>(M.nnz) / static_cast<float>(std::max(M.num_rows, 1)));
@@ -435,16 +447,30 @@ struct DeviceBuilder {
         CSRMatrix* PT = csr_create(0, 0, 0);
         CSRMatrix* AP = csr_create(0, 0, 0);
         CSRMatrix* next = csr_create(0, 0, 0);
+        CSRMatrix* AT = H.smoothed ? csr_create(0, 0, 0) : nullptr;
+        CSRMatrix* smoothed_P = H.smoothed ? csr_create(0, 0, 0) : nullptr;
         {
             AMGLevel& lv = H.levels[static_cast<size_t>(l)];     // owners first: every exit frees them with H
             lv.P = P;
             lv.PT = PT;
             lv.AP = AP;
             lv.num_aggregates = count;
+            if (H.smoothed) {                                    // the unit P made above is the tentative one
+                lv.T = P;
+                lv.P = smoothed_P;
+                lv.AT = AT;
+            }
         }
         H.levels.emplace_back();
         H.levels.back().A = next;
-        if (!PT || !AP || !next) return fail(SpMVError::OUT_OF_MEMORY);
+        if (!PT || !AP || !next || (H.smoothed && (!AT || !smoothed_P))) return fail(SpMVError::OUT_OF_MEMORY);
+        if (H.smoothed) {
+            if (const int status = amg_smooth_coarsen(H, l, sc.d.get(), false, stream)) {
+                return fail(static_cast<SpMVError>(status));
+            }
+            H.levels.back().view = device_view(next);
+            return 0;
+        }
         int status = csr_transpose_gpu(PT, P);
         if (status == 0) status = spgemm_csr(AP, &H.levels[static_cast<size_t>(l)].view, P);
         if (status == 0) status = spgemm_csr(next, PT, AP);
@@ -455,6 +481,35 @@ struct DeviceBuilder {
 };
 
 } // namespace
+
+int amg_smooth_coarsen(AMGHierarchy& H, int l, const float* d_diag, bool refill, hipStream_t s) {
+    AMGLevel& lv = H.levels[static_cast<size_t>(l)];
+    CSRMatrix* next = H.levels[static_cast<size_t>(l) + 1].A;
+    const int n = lv.view.num_rows;
+    int status = refill ? spgemm_csr_numeric(lv.AT, &lv.view, lv.T) : spgemm_csr(lv.AT, &lv.view, lv.T);
+    if (status != 0) return status;
+    if (!refill) {
+        const size_t floats = static_cast<size_t>(n) + static_cast<size_t>(lv.AT->nnz);
+        if (hipMalloc(reinterpret_cast<void**>(&lv.d_s), floats * sizeof(float)) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void**>(&lv.d_res), static_cast<size_t>(n) * sizeof(float)) != hipSuccess) {
+            (void)hipGetLastError();
+            return code(SpMVError::CUDA_MALLOC);
+        }
+    }
+    amg_smoothing_scale_kernel<<<vec_grid(n), kBlock, 0, s>>>(n, H.smoothing.prolongator_weight, d_diag, lv.d_s);
+    if (hipGetLastError() != hipSuccess) return code(SpMVError::KERNEL_LAUNCH);
+    CSRMatrix S = device_view(lv.AT);                      // AT's structure around its own values
+    S.d_values = lv.d_s + n;
+    status = csr_scale_gpu(lv.AT, lv.d_s, nullptr, S.d_values);
+    if (status == 0) status = refill ? csr_add_numeric(lv.P, 1.0f, lv.T, 1.0f, &S) : csr_add(lv.P, 1.0f, lv.T, 1.0f, &S);
+    if (status == 0) status = csr_transpose_gpu(lv.PT, lv.P);
+    if (status == 0) status = refill ? spgemm_csr_numeric(lv.AP, &lv.view, lv.P) : spgemm_csr(lv.AP, &lv.view, lv.P);
+    if (status == 0) status = refill ? spgemm_csr_numeric(next, lv.PT, lv.AP) : spgemm_csr(next, lv.PT, lv.AP);
+    if (status != 0) return status;
+    lv.p_lanes = pick_lanes_per_row(static_cast<float>(lv.P->nnz) / static_cast<float>(std::max(lv.P->num_rows, 1)));
+    lv.pt_lanes = pick_lanes_per_row(static_cast<float>(lv.PT->nnz) / static_cast<float>(std::max(lv.PT->num_rows, 1)));
+    return 0;
+}
 
 AMGResult amg_update_device(AMGHierarchy* H, const CSRMatrix* A) {
     const auto start = std::chrono::steady_clock::now();
@@ -477,8 +532,13 @@ AMGResult amg_update_device(AMGHierarchy* H, const CSRMatrix* A) {
         if (b.diagonal_of(l) != 0 || b.diagonal_checked(l) != 0) return res;
         if (l + 1 == levels) break;
         AMGLevel& lv = H->levels[static_cast<size_t>(l)];
-        int status = spgemm_csr_numeric(lv.AP, &lv.view, lv.P);
-        if (status == 0) status = spgemm_csr_numeric(H->levels[static_cast<size_t>(l) + 1].A, lv.PT, lv.AP);
+        int status = 0;
+        if (H->smoothed) {
+            status = amg_smooth_coarsen(*H, l, sc.d.get(), true, stream);
+        } else {
+            status = spgemm_csr_numeric(lv.AP, &lv.view, lv.P);
+            if (status == 0) status = spgemm_csr_numeric(H->levels[static_cast<size_t>(l) + 1].A, lv.PT, lv.AP);
+        }
         if (status != 0) {
             b.fail(static_cast<SpMVError>(status));
             return res;
@@ -519,8 +579,12 @@ int amg_aggregate_mis2_gpu(const CSRMatrix* A, float strength, unsigned seed, in
     return 0;
 }
 
-AMGResult amg_setup_device(AMGHierarchy** out, const CSRMatrix* A, const AMGConfig* config, unsigned seed) {
-    using namespace detail;
+namespace detail {
+namespace {
+
+// amg_setup_device (smoothing == nullptr) and amg_setup_smoothed_device
+AMGResult setup_device(AMGHierarchy** out, const CSRMatrix* A, const AMGConfig* config, const AMGSmoothing* smoothing,
+                       unsigned seed) {
     const auto start = std::chrono::steady_clock::now();
     AMGResult res;
     const auto fail = [&res](SpMVError e) {
@@ -534,14 +598,20 @@ AMGResult amg_setup_device(AMGHierarchy** out, const CSRMatrix* A, const AMGConf
     const AMGConfig defaults;
     const AMGConfig& cfg = config ? *config : defaults;
     if (!amg_config_ok(cfg)) return fail(SpMVError::INVALID_ARGUMENT);
+    if (smoothing && !amg_smoothing_ok(*smoothing)) return fail(SpMVError::INVALID_ARGUMENT);
 
-    const TraceRange range("spmv:amg_setup_device");
+    const TraceRange range(smoothing ? "spmv:amg_setup_smoothed_device" : "spmv:amg_setup_device");
     hipStream_t stream = current_stream();
     std::unique_ptr<AMGHierarchy, void (*)(AMGHierarchy*)> H(new AMGHierarchy, amg_destroy);
     H->config = cfg;
     H->num_rows = A->num_rows;
     H->nnz = A->nnz;
     H->device_built = true;
+    if (smoothing) {
+        H->smoothed = true;
+        H->smoothing = *smoothing;
+    }
+    float theta = cfg.strength;      // theta_l: constant on a plain hierarchy
     H->levels.emplace_back();
     H->levels[0].view = device_view(A);
     Scratch sc;
@@ -561,7 +631,7 @@ AMGResult amg_setup_device(AMGHierarchy** out, const CSRMatrix* A, const AMGConf
             b.fail(SpMVError::CUDA_MALLOC);
             return res;
         }
-        if (!aggregate_level(view, cfg.strength, seed, map.get(), sc, stream)) {
+        if (!aggregate_level(view, theta, seed, map.get(), sc, stream)) {
             b.fail(SpMVError::KERNEL_LAUNCH);
             return res;
         }
@@ -575,11 +645,25 @@ AMGResult amg_setup_device(AMGHierarchy** out, const CSRMatrix* A, const AMGConf
         if (count == n) break;                          // nothing is strong any more
         H->levels[static_cast<size_t>(l)].rounds = st.rounds;
         if (b.coarsen(l, map, count) != 0) return res;
+        if (smoothing) theta = theta * smoothing->strength_decay;
     }
     if (amg_finish(*H, res, stream) != 0) return res;
     res.setup_ms = ms_since(start);
     *out = H.release();
     return res;
+}
+
+} // namespace
+} // namespace detail
+
+AMGResult amg_setup_device(AMGHierarchy** out, const CSRMatrix* A, const AMGConfig* config, unsigned seed) {
+    return detail::setup_device(out, A, config, nullptr, seed);
+}
+
+AMGResult amg_setup_smoothed_device(AMGHierarchy** out, const CSRMatrix* A, const AMGConfig* config,
+                                    const AMGSmoothing* smoothing, unsigned seed) {
+    const AMGSmoothing defaults;
+    return detail::setup_device(out, A, config, smoothing ? smoothing : &defaults, seed);
 }
 
 } // namespace spmv

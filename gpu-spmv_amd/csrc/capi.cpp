@@ -221,6 +221,9 @@ static_assert(offsetof(spmv_c_amg_config, strength) == offsetof(AMGConfig, stren
               offsetof(spmv_c_amg_config, post_sweeps) == offsetof(AMGConfig, post_sweeps) &&
               offsetof(spmv_c_amg_config, jacobi_weight) == offsetof(AMGConfig, jacobi_weight) &&
               offsetof(spmv_c_amg_config, coarse_sweeps) == offsetof(AMGConfig, coarse_sweeps), "AMGConfig layout");
+static_assert(sizeof(spmv_c_amg_smoothing) == sizeof(AMGSmoothing) && sizeof(AMGSmoothing) == 8 &&
+              offsetof(spmv_c_amg_smoothing, strength_decay) == offsetof(AMGSmoothing, strength_decay),
+              "AMGSmoothing layout");
 static_assert(sizeof(spmv_c_amg_result) == sizeof(AMGResult) && sizeof(AMGResult) == 48, "AMGResult layout");
 static_assert(offsetof(spmv_c_amg_result, bad_level) == offsetof(AMGResult, bad_level) &&
               offsetof(spmv_c_amg_result, grid_complexity) == offsetof(AMGResult, grid_complexity) &&
@@ -811,6 +814,48 @@ int spmv_c_amg_setup_device(spmv_c_amg** out, const spmv_c_csr* A, const spmv_c_
 }
 
 int spmv_c_amg_setup_rounds(const spmv_c_amg* H, int level) { return amg_setup_rounds(cxx(H), level); }
+
+int spmv_c_amg_setup_smoothed(spmv_c_amg** out, const spmv_c_csr* A, const spmv_c_amg_config* config,
+                              const spmv_c_amg_smoothing* smoothing, int aggregate_levels,
+                              const int32_t* const* aggregates, spmv_c_amg_result* result) {
+    const AMGAggregates given{aggregate_levels, aggregates};
+    AMGHierarchy* H = nullptr;
+    const AMGResult r = amg_setup_smoothed(out ? &H : nullptr, cxx(A), reinterpret_cast<const AMGConfig*>(config),
+                                           reinterpret_cast<const AMGSmoothing*>(smoothing),
+                                           aggregates ? &given : nullptr);
+    if (out) *out = reinterpret_cast<spmv_c_amg*>(H);
+    if (result) std::memcpy(result, &r, sizeof(r));
+    return r.error_code;
+}
+
+int spmv_c_amg_setup_smoothed_device(spmv_c_amg** out, const spmv_c_csr* A, const spmv_c_amg_config* config,
+                                     const spmv_c_amg_smoothing* smoothing, uint32_t seed, spmv_c_amg_result* result) {
+    AMGHierarchy* H = nullptr;
+    const AMGResult r = amg_setup_smoothed_device(out ? &H : nullptr, cxx(A), reinterpret_cast<const AMGConfig*>(config),
+                                                  reinterpret_cast<const AMGSmoothing*>(smoothing), seed);
+    if (out) *out = reinterpret_cast<spmv_c_amg*>(H);
+    if (result) std::memcpy(result, &r, sizeof(r));
+    return r.error_code;
+}
+
+int spmv_c_amg_is_smoothed(const spmv_c_amg* H) { return amg_is_smoothed(cxx(H)); }
+
+int spmv_c_amg_level_transfer(const spmv_c_amg* H, int level, spmv_c_csr* P_view, spmv_c_csr* PT_view) {
+    return amg_level_transfer(cxx(H), level, cxx(P_view), cxx(PT_view));
+}
+
+int spmv_c_amg_prolongator_cpu_csr(spmv_c_csr* P, const spmv_c_csr* A, const int32_t* aggregate, int num_aggregates,
+                                   float weight) {
+    return amg_prolongator_cpu_csr(cxx(P), cxx(A), aggregate, num_aggregates, weight);
+}
+
+int spmv_c_amg_restrict(const spmv_c_amg* H, int level, const float* d_f, const float* d_x, float* d_f_coarse) {
+    return amg_restrict(cxx(H), level, d_f, d_x, d_f_coarse);
+}
+
+int spmv_c_amg_prolong(const spmv_c_amg* H, int level, const float* d_e, float* d_x) {
+    return amg_prolong(cxx(H), level, d_e, d_x);
+}
 
 int spmv_c_cg_solve_amg(const spmv_c_csr* A, const spmv_c_amg* H, const float* d_b, float* d_x,
                         const spmv_c_cg_config* config, spmv_c_cg_result* out) {

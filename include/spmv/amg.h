@@ -1,7 +1,8 @@
 // spmv/amg.h — plain (unsmoothed) aggregation algebraic multigrid for a symmetric positive definite CSR matrix: a
 // hierarchy built once per matrix (amg_setup), refilled when only the values change (amg_update), and one symmetric
 // V-cycle on the device per application (amg_apply).  cg_solve_amg (spmv/cg.h) uses it as the preconditioner of the
-// device-resident CG loop.  Kernels in gpu-spmv_amd/csrc/amg.hip, setup in amg_host.cpp, DESIGN.md §4.16.
+// device-resident CG loop.  Kernels in gpu-spmv_amd/csrc/amg.hip, setup in amg_host.cpp, DESIGN.md §4.16.  The
+// smoothed-aggregation variant (amg_setup_smoothed, at the end of this header) builds on everything below.
 //
 // Hierarchy.  Level 0 is A.  Below the coarsest level, level l has an aggregate map agg_l (row i of level l belongs
 // to aggregate agg_l[i]); P_l is the n_l x n_{l+1} matrix with the single entry P_l[i, agg_l[i]] = 1, and
@@ -180,6 +181,69 @@ AMGResult amg_setup_device(AMGHierarchy** out, const CSRMatrix* A, const AMGConf
 // The rounds the root selection of level `level` took; 0 for the coarsest level, a hierarchy amg_setup built, a null
 // H or a level outside the hierarchy.
 int       amg_setup_rounds(const AMGHierarchy* H, int level);
+
+// ---- Smoothed aggregation (setup step in amg_setup.hip, kernels in amg.hip) ------------------------
+// One damped-Jacobi step applied to the tentative prolongator.  Per level l below the coarsest, with A_l, its diagonal
+// d (the rule above) and the aggregate map:
+//     T   = the tentative prolongator (the P of the plain hierarchy)
+//     AT  = spgemm(A_l, T)
+//     s_i = float(-double(omega_p) / double(d_i))
+//     S   = csr_scale(AT, rows = s)
+//     P   = csr_add(1, T, 1, S)        AT's pattern (row i of AT always stores column agg_i: it holds a_ii and spgemm
+//                                      keeps cancelled entries): fl(1 + fl(s_i at)) at column agg_i, fl(s_i at) elsewhere
+//     PT  = csr_transpose(P)           csr_transpose_gpu's stable order
+//     AP  = spgemm(A_l, P),   A_{l+1} = spgemm(PT, AP)
+// so every level matrix and every P is bit for bit the same chain through spgemm_cpu_csr, csr_scale_cpu and
+// csr_add_cpu; amg_prolongator_cpu_csr is that chain for one level's P.
+// Strength.  theta_0 = config.strength, theta_{l+1} = fl32(theta_l * strength_decay): the smoothed coarse operators
+// are denser and their entries relatively smaller, so a fixed theta stalls the coarsening (Vanek's rule halves it).
+// Each theta_l goes to the level's aggregation; it is not used with caller-given maps.
+// V-cycle on a smoothed level: the pre-sweeps as above; r_i = f_i - (A x)_i, stored; f_{l+1}[a] = (PT r)_a; the cycle
+// on level l + 1; x_i = x_i + (P e)_i; the post-sweeps.  Every (M v)_i is the vector-CSR row sum described above; P
+// and PT take their own lane counts from their own mean row lengths (SPMV_DEBUG's amg_lanes=N forces all of them).
+// pre + 2 + 1 + post launches per level.  The residual is stored because rows of PT overlap: recomputing it per
+// aggregate would cost nnz(P) / n passes over A_l, scattering it would need float atomics.
+struct AMGSmoothing {            // 8 bytes
+    float prolongator_weight;    // omega_p in (0, 2)
+    float strength_decay;        // in (0, 1]
+    AMGSmoothing() : prolongator_weight(2.0f / 3.0f), strength_decay(0.5f) {}
+};
+
+// amg_setup with smoothed prolongators.  Checks, stopping rules, coarsest-level solver, complexities and workspace are
+// amg_setup's (every level below the coarsest holds one more n-vector, the residual); smoothing == nullptr:
+// AMGSmoothing(); a weight outside (0, 2), a decay outside (0, 1] or a NaN -> INVALID_ARGUMENT, checked after the
+// config and before the aggregates.  The hierarchy is used like any other: amg_apply, cg_solve_amg, amg_level,
+// amg_update (which leaves every level and every P bit for bit what a fresh setup on the new values gives; it
+// transposes P again, so PT's arrays are released and allocated anew) and amg_destroy.
+AMGResult amg_setup_smoothed(AMGHierarchy** out, const CSRMatrix* A, const AMGConfig* config = nullptr,
+                             const AMGSmoothing* smoothing = nullptr, const AMGAggregates* aggregates = nullptr);
+// amg_setup_device with smoothed prolongators: the MIS-2 aggregation with `seed` and theta_l per level.
+AMGResult amg_setup_smoothed_device(AMGHierarchy** out, const CSRMatrix* A, const AMGConfig* config = nullptr,
+                                    const AMGSmoothing* smoothing = nullptr, unsigned seed = 0);
+int       amg_is_smoothed(const AMGHierarchy* H);                       // 0 for null
+
+// P and P^T of level `level` as non-owning device views (either may be null).  On a plain hierarchy they are the unit
+// P and its transpose.  null H -> INVALID_ARGUMENT; level outside [0, levels - 1) -> INVALID_DIMENSION.  A view of PT
+// is stale after amg_update on a smoothed hierarchy.
+int       amg_level_transfer(const AMGHierarchy* H, int level, CSRMatrix* P_view, CSRMatrix* PT_view);
+
+// The host definition of one level's smoothed P from HOST arrays: aggregate[num_rows] with values in
+// [0, num_aggregates).  Checks, in this order, P untouched by every failure: null P / A_host / aggregate ->
+// INVALID_ARGUMENT; not square -> INVALID_DIMENSION; missing host arrays, malformed row pointers or a column out of
+// range -> INVALID_FORMAT; weight outside (0, 2) or NaN, num_aggregates < 1, a map entry outside [0, num_aggregates),
+// a diagonal that is missing, not > 0 or not finite -> INVALID_ARGUMENT.  On success P owns new host arrays.
+int       amg_prolongator_cpu_csr(CSRMatrix* P, const CSRMatrix* A_host, const int* aggregate, int num_aggregates,
+                                  float weight);
+
+// The two transfers of level `level` on their own (device vectors), for cycles other than the V-cycle:
+//   amg_restrict   d_f_coarse[a] = (PT (f - A_l x))_a     n_l, n_l and n_{l+1} floats
+//   amg_prolong    d_x_i = d_x_i + (P e)_i, in place       n_{l+1} and n_l floats
+// On a plain hierarchy they run the member-list restriction and the gather of the plain cycle.  They use the
+// hierarchy's residual vector: one stream at a time, as amg_apply.  Run on the library stream, return after
+// completion.  Null pointers, d_f_coarse overlapping d_f or d_x, d_e overlapping d_x -> INVALID_ARGUMENT; level
+// outside [0, levels - 1) -> INVALID_DIMENSION.
+int       amg_restrict(const AMGHierarchy* H, int level, const float* d_f, const float* d_x, float* d_f_coarse);
+int       amg_prolong(const AMGHierarchy* H, int level, const float* d_e, float* d_x);
 
 } // namespace spmv
 

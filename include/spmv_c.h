@@ -626,6 +626,28 @@ int spmv_c_amg_setup_device(spmv_c_amg** out, const spmv_c_csr* A, const spmv_c_
                             spmv_c_amg_result* result);
 /* rounds the root selection of level `level` took; 0 on the coarsest level and on a hierarchy spmv_c_amg_setup built */
 int spmv_c_amg_setup_rounds(const spmv_c_amg* H, int level);
+/* ---- smoothed aggregation (include/spmv/amg.h, "Smoothed aggregation") ---- */
+/* 8 bytes; the defaults of AMGSmoothing are 2/3, 0.5 */
+typedef struct spmv_c_amg_smoothing {
+    float prolongator_weight;   /* omega_p in (0, 2) */
+    float strength_decay;       /* in (0, 1]: theta_{l+1} = theta_l * strength_decay */
+} spmv_c_amg_smoothing;
+/* spmv_c_amg_setup with smoothed prolongators; smoothing may be NULL (the defaults) */
+int spmv_c_amg_setup_smoothed(spmv_c_amg** out, const spmv_c_csr* A, const spmv_c_amg_config* config,
+                              const spmv_c_amg_smoothing* smoothing, int aggregate_levels,
+                              const int32_t* const* aggregates, spmv_c_amg_result* result);
+/* spmv_c_amg_setup_device with smoothed prolongators */
+int spmv_c_amg_setup_smoothed_device(spmv_c_amg** out, const spmv_c_csr* A, const spmv_c_amg_config* config,
+                                     const spmv_c_amg_smoothing* smoothing, uint32_t seed, spmv_c_amg_result* result);
+int spmv_c_amg_is_smoothed(const spmv_c_amg* H);   /* 0 for NULL */
+/* P and P^T of level `level` as non-owning device views (either may be NULL) */
+int spmv_c_amg_level_transfer(const spmv_c_amg* H, int level, spmv_c_csr* P_view, spmv_c_csr* PT_view);
+/* the host definition of one level's smoothed P: aggregate[num_rows] in [0, num_aggregates) */
+int spmv_c_amg_prolongator_cpu_csr(spmv_c_csr* P, const spmv_c_csr* A, const int32_t* aggregate, int num_aggregates,
+                                   float weight);
+/* d_f_coarse = P^T (d_f - A_l d_x) and d_x += P d_e on level `level`, device vectors */
+int spmv_c_amg_restrict(const spmv_c_amg* H, int level, const float* d_f, const float* d_x, float* d_f_coarse);
+int spmv_c_amg_prolong(const spmv_c_amg* H, int level, const float* d_e, float* d_x);
 /* CG preconditioned by one V-cycle of H per iteration; config->preconditioner is not read.  Checks and numerics as
  * cg_solve_amg in include/spmv/cg.h. */
 int spmv_c_cg_solve_amg(const spmv_c_csr* A, const spmv_c_amg* H, const float* d_b, float* d_x,

@@ -11,7 +11,13 @@ median, and the iterations.  Nothing is presumed about the winner: `faster` name
 median wall time, with and without one setup added to the AMG side; `device_over_host_setup` is the ratio of the two
 setups' median wall times.
 
+With --smoothed the same is measured, in the same process, for amg_setup_smoothed and amg_setup_smoothed_device
+(default AMGSmoothing) and for cg_solve_amg on their hierarchies, and every smoothed row is compared with the plain row
+of this very run: `smoothed_over_plain_*` are ratios of median wall times (below 1: smoothed is faster), with nothing
+and with one setup added to both sides.
+
     python tools/amg_bench.py [--matrices P2D1024,P3D128] [--runs 10] [--warmup 2] [--out profiles/amg_bench.json]
+    python tools/amg_bench.py --smoothed --out profiles/amg_smoothed_bench.json
 """
 from __future__ import annotations
 
@@ -33,6 +39,7 @@ def main() -> int:
     ap.add_argument("--runs", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--tolerance", type=float, default=1e-6)
+    ap.add_argument("--smoothed", action="store_true", help="add the smoothed-aggregation rows")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "amg_bench.json"))
     args = ap.parse_args()
 
@@ -70,10 +77,11 @@ def main() -> int:
                     setup_ms.append(info.setup_ms)
                     setup_wall.append(wall)
             sizes = [spmv.amg_level(H, l)[1].num_rows for l in range(info.levels)]
+            entries = [spmv.amg_level(H, l)[1].nnz for l in range(info.levels)]
             return {"setup_ms": round(statistics.median(setup_ms), 3),
                     "wall_ms": round(statistics.median(setup_wall), 3),
                     "wall_ms_min_max": [round(min(setup_wall), 3), round(max(setup_wall), 3)], "levels": info.levels,
-                    "level_rows": sizes, "coarse_solver": info.coarse_solver,
+                    "level_rows": sizes, "level_nnz": entries, "coarse_solver": info.coarse_solver,
                     "grid_complexity": round(info.grid_complexity, 4),
                     "operator_complexity": round(info.operator_complexity, 4)}, H
 
@@ -88,6 +96,13 @@ def main() -> int:
         solvers = {"cg_solve_jacobi": lambda: spmv.cg_solve(A, b, x, cfg),
                    "cg_solve_amg": lambda: spmv.cg_solve_amg(A, H, b, x, cfg),
                    "cg_solve_amg_device_setup": lambda: spmv.cg_solve_amg(A, HD, b, x, cfg)}
+        if args.smoothed:
+            entry["amg_setup_smoothed"], HS = time_setup(lambda: spmv.amg_setup_smoothed(A))
+            entry["amg_setup_smoothed_device"], HSD = time_setup(lambda: spmv.amg_setup_smoothed_device(A, None, None, 0))
+            entry["amg_setup_smoothed_device"]["rounds"] = [
+                spmv.amg_setup_rounds(HSD, l) for l in range(entry["amg_setup_smoothed_device"]["levels"])]
+            solvers["cg_solve_amg_smoothed"] = lambda: spmv.cg_solve_amg(A, HS, b, x, cfg)
+            solvers["cg_solve_amg_smoothed_device_setup"] = lambda: spmv.cg_solve_amg(A, HSD, b, x, cfg)
         for label, solve in solvers.items():
             wall, loop, res = [], [], None
             for run in range(args.warmup + args.runs):
@@ -113,6 +128,19 @@ def main() -> int:
         amg_device = entry["cg_solve_amg_device_setup"]["wall_ms"]
         with_device_setup = amg_device + entry["amg_setup_device"]["wall_ms"]
         entry["faster_with_one_device_setup"] = "cg_solve_amg" if with_device_setup < jacobi else "cg_solve_jacobi"
+        if args.smoothed:
+            for solve, setup, plain_solve, plain_setup in (
+                    ("cg_solve_amg_smoothed", "amg_setup_smoothed", "cg_solve_amg", "amg_setup"),
+                    ("cg_solve_amg_smoothed_device_setup", "amg_setup_smoothed_device", "cg_solve_amg_device_setup",
+                     "amg_setup_device")):
+                smoothed, plain = entry[solve]["wall_ms"], entry[plain_solve]["wall_ms"]
+                entry["smoothed_over_plain_" + solve] = {
+                    "per_solve": round(smoothed / plain, 3),
+                    "with_one_setup": round((smoothed + entry[setup]["wall_ms"]) / (plain + entry[plain_setup]["wall_ms"]), 3),
+                    "setup": round(entry[setup]["wall_ms"] / entry[plain_setup]["wall_ms"], 3),
+                    "ms_per_iteration": round(entry[solve]["ms_per_iteration"] / entry[plain_solve]["ms_per_iteration"], 3)}
+            spmv.amg_destroy(HS)
+            spmv.amg_destroy(HSD)
         result["matrices"][name] = entry
         spmv.amg_destroy(H)
         spmv.amg_destroy(HD)
