@@ -1,8 +1,6 @@
 // bsr_tri.hip — the kernels of block IC(0) and of the block triangular solve (include/spmv/bsr_factor.h, DESIGN.md
-// §4.31).  Both walk a level schedule of the BLOCK pattern with sptrsv.hip's two launch shapes: a grid over one wide
-// level, or one workgroup over a run of narrow levels with __syncthreads() in between (workgroup-scope release /
-// acquire; the waves of a workgroup share their CU's write-through vector L1, so what a level stored is what the next
-// level's plain loads return).  The order between launches is stream order.  No workgroup waits for another one.
+// §4.31).  Both walk a level schedule of the BLOCK pattern through the level layer of device_common.h
+// (for_each_level_row, launch_level_groups), which also says why a level's plain loads see the previous level's stores.
 //
 // A group of LANES lanes (1 .. 64, inside one wavefront) owns a block row.
 //
@@ -61,133 +59,124 @@ void bsr_ic0_kernel(int n, int block_rows, int num_blocks, const int* __restrict
                     const float* a, float* f, const int* __restrict__ level_ptr, const int* __restrict__ order,
                     int level_begin, int level_end, unsigned* pivot) {
     constexpr int BB = B * B;
-    constexpr int kRowsPerBlock = kBlock / LANES;
-    const int lane = threadIdx.x % LANES;
-    const int slot = threadIdx.x / LANES;
-    for (int level = level_begin; level < level_end; ++level) {
-        const int first = level_ptr[level];
-        const int last = min(level_ptr[level + 1], block_rows);
-        for (long long base = first + static_cast<long long>(blockIdx.x) * kRowsPerBlock; base < last;
-             base += static_cast<long long>(gridDim.x) * kRowsPerBlock) {
-            const long long k = base + slot;
-            if (k < 0 || k >= last) continue;        // the whole LANES group leaves together: no shuffle reads it
-            const int I = min(max(order[k], 0), block_rows - 1);
-            const int begin = max(brp[I], 0);
-            const int end = min(brp[I + 1], num_blocks);
-            const int di = find_block(bc, begin, end, I);
-            if (di < 0) continue;
-            const int size = min(B, n - I * B);      // scalar rows of this block row inside the matrix
-            const int units = (di - begin + 1) * B;  // rows of the blocks on and left of the diagonal
-            if (a != f) {                            // the owner's first touch of its rows: A's values
-                for (int u = lane; u < units; u += LANES) {
-                    const long long at = static_cast<long long>(begin + u / B) * BB + (u % B) * B;
+    for_each_level_row<LANES>(level_ptr, order, level_begin, level_end, block_rows,
+                              [=](bool live, auto row, int lane) {
+        if (!live) return;
+        const int I = row();
+        const int begin = max(brp[I], 0);
+        const int end = min(brp[I + 1], num_blocks);
+        const int di = find_block(bc, begin, end, I);
+        if (di < 0) return;
+        const int size = min(B, n - I * B);      // scalar rows of this block row inside the matrix
+        const int units = (di - begin + 1) * B;  // rows of the blocks on and left of the diagonal
+        if (a != f) {                            // the owner's first touch of its rows: A's values
+            for (int u = lane; u < units; u += LANES) {
+                const long long at = static_cast<long long>(begin + u / B) * BB + (u % B) * B;
 #pragma unroll
-                    for (int c = 0; c < B; ++c) f[at + c] = a[at + c];
+                for (int c = 0; c < B; ++c) f[at + c] = a[at + c];
+            }
+        }
+        for (int pk = begin; pk < di; ++pk) {
+            const int K = bc[pk];
+            if (K >= I || K < 0) break;          // block columns ascend: the strict lower part is a prefix
+            const int kb = max(brp[K], 0);
+            const int ke = min(brp[K + 1], num_blocks);
+            const int kd = find_block(bc, kb, ke, K);
+            const int mirror = find_block(bc, kb, ke, I);          // (K,I): L^T for the rows below and the solves
+            const int u0 = (pk - begin) * B;     // unit of row 0 of block pk
+            float V[BB];                         // the finished block (K,K); only m <= c of row c is used
+#pragma unroll
+            for (int c = 0; c < B; ++c) {
+#pragma unroll
+                for (int m = 0; m < B; ++m) {
+                    V[c * B + m] = (m <= c && kd >= 0) ? f[static_cast<long long>(kd) * BB + c * B + m] : 0.0f;
                 }
             }
-            for (int pk = begin; pk < di; ++pk) {
-                const int K = bc[pk];
-                if (K >= I || K < 0) break;          // block columns ascend: the strict lower part is a prefix
-                const int kb = max(brp[K], 0);
-                const int ke = min(brp[K + 1], num_blocks);
-                const int kd = find_block(bc, kb, ke, K);
-                const int mirror = find_block(bc, kb, ke, I);          // (K,I): L^T for the rows below and the solves
-                const int u0 = (pk - begin) * B;     // unit of row 0 of block pk
-                float V[BB];                         // the finished block (K,K); only m <= c of row c is used
+            // step 1: the owners of block pk's rows finish them, store them and their mirror
+            float L[BB];
 #pragma unroll
-                for (int c = 0; c < B; ++c) {
+            for (int r = 0; r < B; ++r) {
+                float l[B];
 #pragma unroll
-                    for (int m = 0; m < B; ++m) {
-                        V[c * B + m] = (m <= c && kd >= 0) ? f[static_cast<long long>(kd) * BB + c * B + m] : 0.0f;
-                    }
-                }
-                // step 1: the owners of block pk's rows finish them, store them and their mirror
-                float L[BB];
-#pragma unroll
-                for (int r = 0; r < B; ++r) {
-                    float l[B];
-#pragma unroll
-                    for (int c = 0; c < B; ++c) l[c] = 0.0f;
-                    if ((u0 + r) % LANES == lane) {
-                        const long long at = static_cast<long long>(pk) * BB + r * B;
-                        if (r < size) {
-                            float w[B];
-#pragma unroll
-                            for (int c = 0; c < B; ++c) w[c] = f[at + c];
-                            ic_scale_row<B>(w, V, l);
-                        }
-#pragma unroll
-                        for (int c = 0; c < B; ++c) f[at + c] = l[c];
-                        if (mirror >= 0) {
-#pragma unroll
-                            for (int c = 0; c < B; ++c) f[static_cast<long long>(mirror) * BB + c * B + r] = l[c];
-                        }
-                    }
-#pragma unroll
-                    for (int c = 0; c < B; ++c) {
-                        if constexpr (LANES > 1) L[r * B + c] = __shfl(l[c], (u0 + r) % LANES, LANES);
-                        else L[r * B + c] = l[c];
-                    }
-                }
-                // steps 2 and 3: this lane's rows right of block pk
-                int u = lane;
-                if (u < u0 + B) u += ((u0 + B - 1 - u) / LANES + 1) * LANES;
-                for (; u < units; u += LANES) {
-                    const int t = begin + u / B;
-                    const int r = u % B;
-                    if (r >= size) continue;
-                    float l[B];
-                    select_row<B>(L, r, l);
-                    const long long at = static_cast<long long>(t) * BB + r * B;
-                    if (t == di) {
+                for (int c = 0; c < B; ++c) l[c] = 0.0f;
+                if ((u0 + r) % LANES == lane) {
+                    const long long at = static_cast<long long>(pk) * BB + r * B;
+                    if (r < size) {
                         float w[B];
 #pragma unroll
                         for (int c = 0; c < B; ++c) w[c] = f[at + c];
-                        ic_diag_row<B>(l, L, r, w);
-#pragma unroll
-                        for (int c = 0; c < B; ++c) f[at + c] = w[c];
-                        continue;
+                        ic_scale_row<B>(w, V, l);
                     }
-                    const int q = find_block(bc, kb, ke, bc[t]);
-                    if (q < 0) continue;
-                    float Fq[BB], w[B];
 #pragma unroll
-                    for (int e = 0; e < BB; ++e) Fq[e] = f[static_cast<long long>(q) * BB + e];
+                    for (int c = 0; c < B; ++c) f[at + c] = l[c];
+                    if (mirror >= 0) {
+#pragma unroll
+                        for (int c = 0; c < B; ++c) f[static_cast<long long>(mirror) * BB + c * B + r] = l[c];
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < B; ++c) {
+                    if constexpr (LANES > 1) L[r * B + c] = __shfl(l[c], (u0 + r) % LANES, LANES);
+                    else L[r * B + c] = l[c];
+                }
+            }
+            // steps 2 and 3: this lane's rows right of block pk
+            int u = lane;
+            if (u < u0 + B) u += ((u0 + B - 1 - u) / LANES + 1) * LANES;
+            for (; u < units; u += LANES) {
+                const int t = begin + u / B;
+                const int r = u % B;
+                if (r >= size) continue;
+                float l[B];
+                select_row<B>(L, r, l);
+                const long long at = static_cast<long long>(t) * BB + r * B;
+                if (t == di) {
+                    float w[B];
 #pragma unroll
                     for (int c = 0; c < B; ++c) w[c] = f[at + c];
-                    ic_update_row<B>(l, Fq, w);
+                    ic_diag_row<B>(l, L, r, w);
 #pragma unroll
                     for (int c = 0; c < B; ++c) f[at + c] = w[c];
+                    continue;
                 }
+                const int q = find_block(bc, kb, ke, bc[t]);
+                if (q < 0) continue;
+                float Fq[BB], w[B];
+#pragma unroll
+                for (int e = 0; e < BB; ++e) Fq[e] = f[static_cast<long long>(q) * BB + e];
+#pragma unroll
+                for (int c = 0; c < B; ++c) w[c] = f[at + c];
+                ic_update_row<B>(l, Fq, w);
+#pragma unroll
+                for (int c = 0; c < B; ++c) f[at + c] = w[c];
             }
-            // the diagonal stage: gather W_II's lower triangle from the owners of its rows, fp64 on every lane's copy
-            const int ud = (di - begin) * B;
-            double T[B * (B + 1) / 2];
-#pragma unroll
-            for (int r = 0; r < B; ++r) {
-                const bool mine = (ud + r) % LANES == lane;
-#pragma unroll
-                for (int c = 0; c <= r; ++c) {
-                    float w = 0.0f;
-                    if (mine && r < size) w = f[static_cast<long long>(di) * BB + r * B + c];
-                    if constexpr (LANES > 1) w = __shfl(w, (ud + r) % LANES, LANES);
-                    T[tri(r, c)] = static_cast<double>(w);
-                }
-            }
-            const bool ok = ic_diag_stage<B>(T, size);
-#pragma unroll
-            for (int r = 0; r < B; ++r) {
-                if ((ud + r) % LANES == lane) {
-#pragma unroll
-                    for (int c = 0; c < B; ++c) {
-                        f[static_cast<long long>(di) * BB + r * B + c] = ic_v_entry<B>(T, r, c, size);
-                    }
-                }
-            }
-            if (!ok && lane == 0 && pivot) atomicMin(pivot, static_cast<unsigned>(I));
         }
-        if (level + 1 < level_end) __syncthreads();
-    }
+        // the diagonal stage: gather W_II's lower triangle from the owners of its rows, fp64 on every lane's copy
+        const int ud = (di - begin) * B;
+        double T[B * (B + 1) / 2];
+#pragma unroll
+        for (int r = 0; r < B; ++r) {
+            const bool mine = (ud + r) % LANES == lane;
+#pragma unroll
+            for (int c = 0; c <= r; ++c) {
+                float w = 0.0f;
+                if (mine && r < size) w = f[static_cast<long long>(di) * BB + r * B + c];
+                if constexpr (LANES > 1) w = __shfl(w, (ud + r) % LANES, LANES);
+                T[tri(r, c)] = static_cast<double>(w);
+            }
+        }
+        const bool ok = ic_diag_stage<B>(T, size);
+#pragma unroll
+        for (int r = 0; r < B; ++r) {
+            if ((ud + r) % LANES == lane) {
+#pragma unroll
+                for (int c = 0; c < B; ++c) {
+                    f[static_cast<long long>(di) * BB + r * B + c] = ic_v_entry<B>(T, r, c, size);
+                }
+            }
+        }
+        if (!ok && lane == 0 && pivot) atomicMin(pivot, static_cast<unsigned>(I));
+    });
 }
 
 // ORDERED (LANES == 1): sptrsv_cpu_bsr's order and roundings.  Otherwise bsr_device.h's walk over the triangle's blocks
@@ -200,56 +189,46 @@ void bsr_sptrsv_kernel(int n, int block_rows, int num_blocks, const int* __restr
                        int level_end, int upper, int unit) {
     static_assert(!ORDERED || LANES == 1, "the ordered solve is one lane per block row");
     constexpr int BB = B * B;
-    constexpr int kRowsPerBlock = kBlock / LANES;
-    const int lane = threadIdx.x % LANES;
-    const int slot = threadIdx.x / LANES;
-    for (int level = level_begin; level < level_end; ++level) {
-        const int first = level_ptr[level];
-        const int last = min(level_ptr[level + 1], block_rows);
-        for (long long base = first + static_cast<long long>(blockIdx.x) * kRowsPerBlock; base < last;
-             base += static_cast<long long>(gridDim.x) * kRowsPerBlock) {
-            const long long k = base + slot;
-            const bool live = k >= 0 && k < last;
-            int I = 0, begin = 0, end = 0;
-            float acc[B];
+    for_each_level_row<LANES>(level_ptr, order, level_begin, level_end, block_rows,
+                              [=](bool live, auto row, int lane) {
+        int I = 0, begin = 0, end = 0;
+        float acc[B];
 #pragma unroll
-            for (int r = 0; r < B; ++r) acc[r] = 0.0f;
-            if (live) {
-                I = min(max(order[k], 0), block_rows - 1);
-                begin = max(brp[I], 0);
-                end = min(brp[I + 1], num_blocks);
-                // the triangle's side of I; a block column at or past block_rows would start at or past n
-                block_row_partial_dot<B, LANES, WIDE, true, ORDERED>(bc, bv, x, n, begin, end, lane,
-                                                                     upper ? I + 1 : 0, upper ? block_rows : I, acc);
+        for (int r = 0; r < B; ++r) acc[r] = 0.0f;
+        if (live) {
+            I = row();
+            begin = max(brp[I], 0);
+            end = min(brp[I + 1], num_blocks);
+            // the triangle's side of I; a block column at or past block_rows would start at or past n
+            block_row_partial_dot<B, LANES, WIDE, true, ORDERED>(bc, bv, x, n, begin, end, lane,
+                                                                 upper ? I + 1 : 0, upper ? block_rows : I, acc);
+        }
+        if constexpr (LANES > 1) {
+#pragma unroll
+            for (int r = 0; r < B; ++r) acc[r] = group_sum<LANES>(acc[r]);
+        }
+        if (live && lane == 0) {
+            const int size = min(B, n - I * B);
+            float t[B];
+#pragma unroll
+            for (int r = 0; r < B; ++r) t[r] = r < size ? __fsub_rn(b[I * B + r], acc[r]) : 0.0f;
+            if (!unit) {
+                const int d = find_block(bc, begin, end, I);
+                float V[BB];
+#pragma unroll
+                for (int e = 0; e < BB; ++e) V[e] = d >= 0 ? bv[static_cast<long long>(d) * BB + e] : 0.0f;
+                float u[B];
+#pragma unroll
+                for (int r = 0; r < B; ++r) u[r] = tri_diag_row<B>(V, t, r, size, upper != 0);
+#pragma unroll
+                for (int r = 0; r < B; ++r) t[r] = u[r];
             }
-            if constexpr (LANES > 1) {
 #pragma unroll
-                for (int r = 0; r < B; ++r) acc[r] = group_sum<LANES>(acc[r]);
-            }
-            if (live && lane == 0) {
-                const int size = min(B, n - I * B);
-                float t[B];
-#pragma unroll
-                for (int r = 0; r < B; ++r) t[r] = r < size ? __fsub_rn(b[I * B + r], acc[r]) : 0.0f;
-                if (!unit) {
-                    const int d = find_block(bc, begin, end, I);
-                    float V[BB];
-#pragma unroll
-                    for (int e = 0; e < BB; ++e) V[e] = d >= 0 ? bv[static_cast<long long>(d) * BB + e] : 0.0f;
-                    float u[B];
-#pragma unroll
-                    for (int r = 0; r < B; ++r) u[r] = tri_diag_row<B>(V, t, r, size, upper != 0);
-#pragma unroll
-                    for (int r = 0; r < B; ++r) t[r] = u[r];
-                }
-#pragma unroll
-                for (int r = 0; r < B; ++r) {
-                    if (r < size) x[I * B + r] = t[r];
-                }
+            for (int r = 0; r < B; ++r) {
+                if (r < size) x[I * B + r] = t[r];
             }
         }
-        if (level + 1 < level_end) __syncthreads();
-    }
+    });
 }
 
 // one thread per scalar row: the diagonal entry (k,k) of the stored block (I,I) of F must be > 0 and finite
@@ -272,32 +251,21 @@ void bsr_factor_diag_check_kernel(const int* __restrict__ brp, const int* __rest
 template <int B, int LANES>
 hipError_t launch_ic0_groups(const SptrsvSchedule& sch, const BSRMatrix* A, const float* a, float* f, unsigned* pivot,
                              hipStream_t s) {
-    constexpr int kRowsPerBlock = kBlock / LANES;
-    for (const SptrsvSchedule::Group& g : sch.groups) {
-        // a run of levels is one workgroup (the barrier is its only ordering); one level alone takes a grid
-        const int grid = g.level_end - g.level_begin > 1 ? 1 : capped_grid(g.rows, kRowsPerBlock);
+    return launch_level_groups<LANES>(sch, [&](int grid, int level_begin, int level_end) {
         bsr_ic0_kernel<B, LANES><<<grid, kBlock, 0, s>>>(A->num_rows, A->num_block_rows, A->num_blocks,
                                                          A->d_block_row_ptrs, A->d_block_cols, a, f, sch.d_level_ptr,
-                                                         sch.d_order, g.level_begin, g.level_end, pivot);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+                                                         sch.d_order, level_begin, level_end, pivot);
+    });
 }
 
 template <int B, int LANES, bool WIDE, bool ORDERED>
 hipError_t launch_solve_groups(const SptrsvSchedule& sch, const BSRMatrix* F, const float* b, float* x, int upper,
                                int unit, hipStream_t s) {
-    constexpr int kRowsPerBlock = kBlock / LANES;
-    for (const SptrsvSchedule::Group& g : sch.groups) {
-        const int grid = g.level_end - g.level_begin > 1 ? 1 : capped_grid(g.rows, kRowsPerBlock);
+    return launch_level_groups<LANES>(sch, [&](int grid, int level_begin, int level_end) {
         bsr_sptrsv_kernel<B, LANES, WIDE, ORDERED><<<grid, kBlock, 0, s>>>(
             F->num_rows, F->num_block_rows, F->num_blocks, F->d_block_row_ptrs, F->d_block_cols, F->d_values, b, x,
-            sch.d_level_ptr, sch.d_order, g.level_begin, g.level_end, upper, unit);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+            sch.d_level_ptr, sch.d_order, level_begin, level_end, upper, unit);
+    });
 }
 
 } // namespace

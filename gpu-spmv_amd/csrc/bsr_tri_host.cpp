@@ -6,9 +6,9 @@
 #include "bsr_impl.h"
 #include "bsr_tri_impl.h"
 #include "internal.h"
+#include "level_driver.h"
 
 #include <algorithm>
-#include <climits>
 #include <cstdint>
 #include <cstring>
 #include <vector>
@@ -21,13 +21,6 @@ namespace {
 
 size_t value_count(const BSRMatrix* M) {
     return static_cast<size_t>(M->num_blocks) * M->block_dim * M->block_dim;
-}
-
-// [a, a + count) and [b, b + count) share a byte without being the same array
-bool partial_overlap(const float* a, const float* b, long long count) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    const uintptr_t bytes = static_cast<uintptr_t>(count) * sizeof(float);
-    return a != b && a0 < b0 + bytes && b0 < a0 + bytes;
 }
 
 bool host_arrays(const BSRMatrix* M) {
@@ -56,12 +49,6 @@ int check_front(const BSRMatrix* M, const void* p, const void* q, bool* nothing_
     if (M->num_rows != M->num_cols) return code(SpMVError::INVALID_DIMENSION);
     if (M->num_rows == 0) *nothing_to_do = true;
     return 0;
-}
-
-bool config_ok(const SpTRSVConfig& cfg) {
-    return (cfg.uplo == SpTRSVConfig::LOWER || cfg.uplo == SpTRSVConfig::UPPER) &&
-           (cfg.diag == SpTRSVConfig::NON_UNIT || cfg.diag == SpTRSVConfig::UNIT) &&
-           (cfg.ordered == 0 || cfg.ordered == 1);
 }
 
 template <int B>
@@ -166,52 +153,69 @@ int device_matrix_check(const BSRMatrix* M) {
     return device_arrays_ok(M) ? 0 : code(SpMVError::INVALID_FORMAT);
 }
 
-// Everything before the launches of a solve.  On SUCCESS with *schedule null there is nothing to do (no rows).
-int prepare_solve(const BSRMatrix* F, const float* d_b, const float* d_x, const SpTRSVConfig& cfg, hipStream_t stream,
-                  ScheduleRef* schedule, float* analysis_ms) {
-    schedule->reset();
-    *analysis_ms = 0.0f;
-    bool nothing = false;
-    int status = check_front(F, d_b, d_x, &nothing);
-    if (status != 0 || nothing) return status;
-    status = device_matrix_check(F);
-    if (status != 0) return status;
-    if (!config_ok(cfg)) return code(SpMVError::INVALID_ARGUMENT);
-    if (partial_overlap(d_b, d_x, F->num_rows)) return code(SpMVError::INVALID_ARGUMENT);
-    ScheduleRef found;
-    status = tri_schedule_for(F, cfg.uplo, stream, &found, analysis_ms);
-    if (status != 0) return status;
-    // NON_UNIT reads the diagonal block, which the kernel finds by a binary search: the block columns must ascend
-    if (cfg.diag == SpTRSVConfig::NON_UNIT &&
-        (found->first_missing_diagonal >= 0 || found->first_unsorted_row >= 0)) {
-        return code(SpMVError::INVALID_ARGUMENT);
+// sptrsv_bsr and sptrsv_bsr_async as an Op of level_driver.h
+struct BlockSolve {
+    const BSRMatrix* F;
+    const float* d_b;
+    float* d_x;
+    SpTRSVConfig cfg;
+    int prepare(hipStream_t stream, ScheduleRef* schedule, float* analysis_ms) const {
+        schedule->reset();
+        *analysis_ms = 0.0f;
+        bool nothing = false;
+        int status = check_front(F, d_b, d_x, &nothing);
+        if (status != 0 || nothing) return status;
+        status = device_matrix_check(F);
+        if (status != 0) return status;
+        if (!config_ok(cfg)) return code(SpMVError::INVALID_ARGUMENT);
+        if (partial_overlap(d_b, d_x, F->num_rows)) return code(SpMVError::INVALID_ARGUMENT);
+        ScheduleRef found;
+        status = tri_schedule_for(F, cfg.uplo, stream, &found, analysis_ms);
+        if (status != 0) return status;
+        // NON_UNIT reads the diagonal block, which the kernel finds by a binary search: the block columns must ascend
+        if (cfg.diag == SpTRSVConfig::NON_UNIT &&
+            (found->first_missing_diagonal >= 0 || found->first_unsorted_row >= 0)) {
+            return code(SpMVError::INVALID_ARGUMENT);
+        }
+        *schedule = found;
+        return 0;
     }
-    *schedule = found;
-    return 0;
-}
+    int lanes(const SptrsvSchedule& schedule) const { return tri_lanes(schedule, cfg.ordered == 1); }
+    hipError_t launch(const SptrsvSchedule& schedule, int lanes, hipStream_t stream) const {
+        return launch_sptrsv_bsr(schedule, F, d_b, d_x, cfg.uplo, cfg.diag == SpTRSVConfig::UNIT, cfg.ordered == 1,
+                                 lanes, stream);
+    }
+};
 
-// Everything before the launches of a factorisation.
-int prepare_factor(const BSRMatrix* A, const float* d_f, hipStream_t stream, ScheduleRef* schedule,
-                   float* analysis_ms) {
-    schedule->reset();
-    *analysis_ms = 0.0f;
-    bool nothing = false;
-    int status = check_front(A, d_f, d_f, &nothing);
-    if (status != 0 || nothing) return status;
-    status = device_matrix_check(A);
-    if (status != 0) return status;
-    if (partial_overlap(A->d_values, d_f, static_cast<long long>(value_count(A)))) {
-        return code(SpMVError::INVALID_ARGUMENT);
+// bsr_ic0 and bsr_ic0_async
+struct BlockFactor {
+    const BSRMatrix* A;
+    float* d_f;
+    int prepare(hipStream_t stream, ScheduleRef* schedule, float* analysis_ms) const {
+        schedule->reset();
+        *analysis_ms = 0.0f;
+        bool nothing = false;
+        int status = check_front(A, d_f, d_f, &nothing);
+        if (status != 0 || nothing) return status;
+        status = device_matrix_check(A);
+        if (status != 0) return status;
+        if (partial_overlap(A->d_values, d_f, static_cast<long long>(value_count(A)))) {
+            return code(SpMVError::INVALID_ARGUMENT);
+        }
+        ScheduleRef found;
+        status = tri_schedule_for(A, SpTRSVConfig::LOWER, stream, &found, analysis_ms);
+        if (status != 0) return status;
+        if (found->first_unsorted_row >= 0 || found->first_missing_diagonal >= 0 || found->one_sided_row >= 0) {
+            return code(SpMVError::INVALID_ARGUMENT);
+        }
+        *schedule = found;
+        return 0;
     }
-    ScheduleRef found;
-    status = tri_schedule_for(A, SpTRSVConfig::LOWER, stream, &found, analysis_ms);
-    if (status != 0) return status;
-    if (found->first_unsorted_row >= 0 || found->first_missing_diagonal >= 0 || found->one_sided_row >= 0) {
-        return code(SpMVError::INVALID_ARGUMENT);
+    int lanes(const SptrsvSchedule& schedule) const { return tri_lanes(schedule, false); }
+    hipError_t launch(const SptrsvSchedule& schedule, int lanes, hipStream_t stream, unsigned* d_pivot) const {
+        return launch_bsr_ic0(schedule, A, A->d_values, d_f, lanes, d_pivot, stream);
     }
-    *schedule = found;
-    return 0;
-}
+};
 
 } // namespace
 
@@ -293,8 +297,7 @@ int sptrsv_cpu_bsr(const BSRMatrix* F, const float* b, float* x, const SpTRSVCon
     const int status = check_front(F, b, x, &nothing);
     if (status != 0 || nothing) return status;
     if (!host_arrays(F)) return code(SpMVError::INVALID_FORMAT);
-    const SpTRSVConfig defaults;
-    const SpTRSVConfig& cfg = config ? *config : defaults;
+    const SpTRSVConfig cfg = config_or_default(config);
     if (!config_ok(cfg)) return code(SpMVError::INVALID_ARGUMENT);
     if (partial_overlap(b, x, F->num_rows)) return code(SpMVError::INVALID_ARGUMENT);
     if (!host_pattern_ok(F)) return code(SpMVError::INVALID_FORMAT);
@@ -323,120 +326,35 @@ int sptrsv_cpu_bsr(const BSRMatrix* F, const float* b, float* x, const SpTRSVCon
 
 BsrIC0Result bsr_ic0(const BSRMatrix* A, float* d_f_values) {
     using namespace detail;
-    using namespace detail::bsr;
-    BsrIC0Result result;
-    hipStream_t stream = current_stream();
-    ScheduleRef schedule;
-    result.error_code = prepare_factor(A, d_f_values, stream, &schedule, &result.analysis_ms);
-    if (result.error_code != 0 || !schedule) return result;
-
-    const TraceRange range("spmv:bsr_ic0");
-    const int lanes = tri_lanes(*schedule, false);
-    result.num_levels = schedule->num_levels;
-    result.launches = static_cast<int>(schedule->groups.size());
-    result.lanes_per_row = lanes;
-    DevBuf<unsigned> d_pivot;          // lowest bad block row as an unsigned minimum; all ones = none
-    if (dev_alloc(&d_pivot, 1) != hipSuccess) {
-        (void)hipGetLastError();
-        result.error_code = code(SpMVError::CUDA_MALLOC);
-        return result;
-    }
-    EventPair& ev = thread_events();
-    unsigned pivot = UINT_MAX;
-    bool ok = hipMemsetAsync(d_pivot.get(), 0xff, sizeof(unsigned), stream) == hipSuccess &&
-              ev.start && ev.stop && hipEventRecord(ev.start, stream) == hipSuccess;
-    ok = ok && launch_bsr_ic0(*schedule, A, A->d_values, d_f_values, lanes, d_pivot.get(), stream) == hipSuccess;
-    ok = ok && hipEventRecord(ev.stop, stream) == hipSuccess &&
-         hipMemcpyAsync(&pivot, d_pivot.get(), sizeof(unsigned), hipMemcpyDeviceToHost, stream) == hipSuccess;
-    // always drained: `pivot` lives in this frame
-    ok = (hipStreamSynchronize(stream) == hipSuccess) && ok && hipGetLastError() == hipSuccess &&
-         hipEventElapsedTime(&result.elapsed_ms, ev.start, ev.stop) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        result.error_code = code(SpMVError::KERNEL_LAUNCH);
-        return result;
-    }
-    result.bad_pivot = pivot == UINT_MAX ? -1 : static_cast<int>(pivot);
-    return result;
+    return factor_result(timed_factor("spmv:bsr_ic0", bsr::BlockFactor{A, d_f_values}), &BsrIC0Result::bad_pivot);
 }
 
 int bsr_ic0_async(const BSRMatrix* A, float* d_f_values, hipStream_t stream) {
-    using namespace detail;
-    using namespace detail::bsr;
-    ScheduleRef schedule;
-    float analysis_ms = 0.0f;
-    const int status = prepare_factor(A, d_f_values, stream, &schedule, &analysis_ms);
-    if (status != 0 || !schedule) return status;
-    const hipError_t e = launch_bsr_ic0(*schedule, A, A->d_values, d_f_values, tri_lanes(*schedule, false), nullptr,
-                                        stream);
-    return e == hipSuccess ? code(SpMVError::SUCCESS) : code(SpMVError::KERNEL_LAUNCH);
+    return detail::launch_factor_async(detail::bsr::BlockFactor{A, d_f_values}, stream);
 }
 
 SpTRSVResult sptrsv_bsr(const BSRMatrix* F, const float* d_b, float* d_x, const SpTRSVConfig* config) {
     using namespace detail;
-    using namespace detail::bsr;
-    SpTRSVResult result;
-    const SpTRSVConfig defaults;
-    const SpTRSVConfig& cfg = config ? *config : defaults;
-    hipStream_t stream = current_stream();
-    ScheduleRef schedule;
-    result.error_code = prepare_solve(F, d_b, d_x, cfg, stream, &schedule, &result.analysis_ms);
-    if (result.error_code != 0 || !schedule) return result;
-
-    const TraceRange range("spmv:sptrsv_bsr");
-    const int lanes = tri_lanes(*schedule, cfg.ordered == 1);
-    result.num_levels = schedule->num_levels;
-    result.launches = static_cast<int>(schedule->groups.size());
-    result.lanes_per_row = lanes;
-    EventPair& ev = thread_events();
-    if (!ev.start || !ev.stop || hipEventRecord(ev.start, stream) != hipSuccess) {
-        result.error_code = code(SpMVError::KERNEL_LAUNCH);
-        return result;
-    }
-    const hipError_t launched = launch_sptrsv_bsr(*schedule, F, d_b, d_x, cfg.uplo, cfg.diag == SpTRSVConfig::UNIT,
-                                                  cfg.ordered == 1, lanes, stream);
-    const hipError_t recorded = hipEventRecord(ev.stop, stream);
-    const hipError_t waited = hipEventSynchronize(ev.stop);
-    if (launched != hipSuccess || recorded != hipSuccess || waited != hipSuccess || hipGetLastError() != hipSuccess ||
-        hipEventElapsedTime(&result.elapsed_ms, ev.start, ev.stop) != hipSuccess) {
-        result.error_code = code(SpMVError::KERNEL_LAUNCH);
-    }
-    return result;
+    return timed_solve("spmv:sptrsv_bsr", bsr::BlockSolve{F, d_b, d_x, config_or_default(config)});
 }
 
 int sptrsv_bsr_async(const BSRMatrix* F, const float* d_b, float* d_x, const SpTRSVConfig* config, hipStream_t stream) {
     using namespace detail;
-    using namespace detail::bsr;
-    const SpTRSVConfig defaults;
-    const SpTRSVConfig& cfg = config ? *config : defaults;
-    ScheduleRef schedule;
-    float analysis_ms = 0.0f;
-    const int status = prepare_solve(F, d_b, d_x, cfg, stream, &schedule, &analysis_ms);
-    if (status != 0 || !schedule) return status;
-    const hipError_t e = launch_sptrsv_bsr(*schedule, F, d_b, d_x, cfg.uplo, cfg.diag == SpTRSVConfig::UNIT,
-                                           cfg.ordered == 1, tri_lanes(*schedule, cfg.ordered == 1), stream);
-    return e == hipSuccess ? code(SpMVError::SUCCESS) : code(SpMVError::KERNEL_LAUNCH);
+    return launch_async(bsr::BlockSolve{F, d_b, d_x, config_or_default(config)}, stream);
 }
 
 SpTRSVResult sptrsv_analyze_bsr(const BSRMatrix* A, int uplo) {
     using namespace detail;
     using namespace detail::bsr;
-    SpTRSVResult result;
-    bool nothing = false;
-    result.error_code = check_front(A, A, A, &nothing);
-    if (result.error_code != 0 || nothing) return result;
-    result.error_code = device_matrix_check(A);
-    if (result.error_code != 0) return result;
-    if (uplo != SpTRSVConfig::LOWER && uplo != SpTRSVConfig::UPPER) {
-        result.error_code = code(SpMVError::INVALID_ARGUMENT);
-        return result;
-    }
-    ScheduleRef schedule;
-    result.error_code = tri_schedule_for(A, uplo, current_stream(), &schedule, &result.analysis_ms);
-    if (result.error_code != 0) return result;
-    result.num_levels = schedule->num_levels;
-    result.launches = static_cast<int>(schedule->groups.size());
-    return result;
+    return analyze_levels(
+        uplo,
+        [&](bool* nothing) {
+            const int status = check_front(A, A, A, nothing);
+            return status != 0 || *nothing ? status : device_matrix_check(A);
+        },
+        [&](hipStream_t stream, ScheduleRef* schedule, float* analysis_ms) {
+            return tri_schedule_for(A, uplo, stream, schedule, analysis_ms);
+        });
 }
 
 } // namespace spmv

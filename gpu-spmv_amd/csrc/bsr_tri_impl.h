@@ -81,8 +81,6 @@ BSR_DIAG_HD float tri_diag_row(const float* V, const float* t, int r, int size, 
 }
 
 // ---- the launch layer (bsr_tri.hip) and the drivers' shared front (bsr_tri_host.cpp) ----
-using ScheduleRef = std::shared_ptr<const SptrsvSchedule>;
-
 // the `uplo` schedule of M's block pattern: a CSR header over the block structure arrays handed to sptrsv_schedule_for,
 // so the side table entry under d_block_row_ptrs serves every matrix over those arrays
 int tri_schedule_for(const BSRMatrix* M, int uplo, hipStream_t stream, ScheduleRef* out, float* analysis_ms);

@@ -1,12 +1,16 @@
 // device_common.h — what the kernel files share (gfx950, wave64).
 // Device side: cross-lane and workgroup reductions, the vector-CSR row walk
 // (row_partial_dot) and the sweep over all rows built on it (for_each_row_dot),
-// the binary searches.
-// Host side, the launch layer: the grid sizes (capped_grid, vec_grid) and
+// the walk over the rows of a level schedule (for_each_level_row), the binary
+// searches.
+// Host side, the launch layer: the grid sizes (capped_grid, vec_grid),
 // with_lanes, which turns a run-time lanes-per-row count into a template
-// argument.
+// argument, and launch_level_groups, the launches of one pass over a level
+// schedule.
 #ifndef SPMV_AMD_DEVICE_COMMON_H
 #define SPMV_AMD_DEVICE_COMMON_H
+
+#include "internal.h"
 
 #include <hip/hip_runtime.h>
 
@@ -146,6 +150,44 @@ __device__ __forceinline__ void for_each_row_dot(int n, long long nnz, const int
     }
 }
 
+// The level layer, device side: the walk over the levels [level_begin, level_end) of a level schedule (SptrsvSchedule:
+// order[level_ptr[l] .. level_ptr[l + 1]) are the rows of level l, independent of each other), one aligned group of
+// LANES lanes per row, kBlock / LANES rows per workgroup and trip.  launch_level_groups below launches it in two shapes:
+//   * one wide level: a grid strides over the level's rows;
+//   * a run of narrow levels (each at most kSptrsvNarrowRows rows): ONE workgroup walks them in order with
+//     __syncthreads() in between (none after the last).  __syncthreads() is a workgroup-scope release, the barrier, and
+//     a workgroup-scope acquire; the waves of a workgroup share their CU's vector L1, which their own write-through
+//     stores keep current, so what a level stored is what the next level's plain loads return.  (Another CU would need
+//     an agent-scope acquire; nothing reads another workgroup's stores inside a launch.)
+// The order between launches is stream order.  No workgroup waits for another one: no flags, no spinning.
+// Every thread calls body(live, row, lane) on every trip, so that body may use cross-lane operations and every thread
+// reaches every barrier: body may not leave the kernel.  live: the group has a row; row() is order[] clamped to
+// [0, rows), so a schedule that went stale gives wrong numbers, never an out-of-bounds access.  A dead group does not
+// read order[] and gets row 0.  A body that writes `if (!live) return;` is sound: the whole LANES group leaves
+// together, no shuffle reads it.
+// Call row() inside the body's own `if (live)` and capture by value ([=]): every other form costs registers
+// (profiles/level_layer_resources.txt).  The block kernels of bsr_tri.hip walk through this helper; sptrsv_kernel,
+// sptrsv_multi_kernel and factor0_kernel write the same walk out: through the helper they measured 0.4 to 0.9 % slower
+// with equal resources (profiles/level_layer_ab.txt).  A change here is a change there.
+template <int LANES, class Body>
+__device__ __forceinline__ void for_each_level_row(const int* level_ptr, const int* order, int level_begin,
+                                                   int level_end, int rows, Body&& body) {
+    constexpr int kRowsPerBlock = kBlock / LANES;
+    const int lane = threadIdx.x % LANES;
+    const int slot = threadIdx.x / LANES;
+    for (int level = level_begin; level < level_end; ++level) {
+        const int first = level_ptr[level];
+        const int last = min(level_ptr[level + 1], rows);
+        for (long long base = first + static_cast<long long>(blockIdx.x) * kRowsPerBlock; base < last;
+             base += static_cast<long long>(gridDim.x) * kRowsPerBlock) {
+            const long long k = base + slot;
+            const bool live = k >= 0 && k < last;
+            body(live, [&] { return live ? min(max(order[k], 0), rows - 1) : 0; }, lane);
+        }
+        if (level + 1 < level_end) __syncthreads();
+    }
+}
+
 // block-wide sum of two doubles; result valid in thread 0
 template <int BLOCK = kBlock>
 __device__ __forceinline__ void block_sum2(double& a, double& b) {
@@ -246,6 +288,20 @@ hipError_t with_lanes(int lanes, Launch&& launch) {
         case 32: return launch(std::integral_constant<int, 32>{});
         default: return launch(std::integral_constant<int, 64>{});
     }
+}
+
+// The level layer, host side: one launch per group of the schedule, in stream order; launch(grid, level_begin,
+// level_end) starts a kernel that walks those levels with for_each_level_row<LANES>.  The first error ends it.
+template <int LANES, class Launch>
+hipError_t launch_level_groups(const SptrsvSchedule& schedule, Launch&& launch) {
+    for (const SptrsvSchedule::Group& g : schedule.groups) {
+        // a run of levels is one workgroup (the barrier is its only ordering); one level alone takes a grid
+        const int grid = g.level_end - g.level_begin > 1 ? 1 : capped_grid(g.rows, kBlock / LANES);
+        launch(grid, g.level_begin, g.level_end);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 } // namespace dev

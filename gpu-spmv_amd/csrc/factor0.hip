@@ -3,9 +3,10 @@
 // an `if constexpr (KIND == IC0)` branch inside it.
 //
 // Row i of the factor needs the finished rows k < i of its own pattern: the dependency graph of a LOWER triangular
-// solve, so the factorisation walks sptrsv_csr's LOWER level schedule with sptrsv.hip's two launch shapes (a grid over
-// one wide level; one workgroup over a run of narrow levels with __syncthreads() in between, whose workgroup-scope
-// release / acquire and the CU's write-through vector L1 make a level's stores the next level's plain loads).
+// solve, so the factorisation walks sptrsv_csr's LOWER level schedule, launched by the level layer of device_common.h
+// (launch_level_groups).  The walk is for_each_level_row's, written out (through the helper ilu0_csr measured 0.8 %
+// slower on a 4 M-row matrix with every resource equal: profiles/level_layer_ab.txt); the helper's comment says why a
+// level's plain loads see the previous level's stores.
 //
 // Inside a row, LANES lanes share the entries (IC: those on and left of the diagonal): entry t belongs to lane
 // (t - begin) % LANES for the whole row, and only that lane ever loads or stores it, so no lane depends on another
@@ -134,17 +135,10 @@ void factor0_pivot_kernel(int n, int nnz, const int* __restrict__ row_ptrs, cons
 
 template <Factor0Kind KIND, int LANES>
 hipError_t launch_groups(const SptrsvSchedule& sch, const CSRMatrix* A, const float* a, float* f, hipStream_t s) {
-    constexpr int kRowsPerBlock = kBlock / LANES;
-    for (const SptrsvSchedule::Group& g : sch.groups) {
-        // a run of levels is one workgroup (the barrier is its only ordering); one level alone takes a grid
-        const int grid = g.level_end - g.level_begin > 1 ? 1 : capped_grid(g.rows, kRowsPerBlock);
-        factor0_kernel<KIND, LANES><<<grid, kBlock, 0, s>>>(A->num_rows, A->nnz, A->d_row_ptrs, A->d_col_indices, a,
-                                                            f, sch.d_level_ptr, sch.d_order, g.level_begin,
-                                                            g.level_end);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return launch_level_groups<LANES>(sch, [&](int grid, int level_begin, int level_end) {
+        factor0_kernel<KIND, LANES><<<grid, kBlock, 0, s>>>(A->num_rows, A->nnz, A->d_row_ptrs, A->d_col_indices, a, f,
+                                                            sch.d_level_ptr, sch.d_order, level_begin, level_end);
+    });
 }
 
 template <Factor0Kind KIND>

@@ -4,12 +4,12 @@
 // kernels are in factor0.hip.  Built without FMA contraction: the fused multiply-adds below are the explicit
 // std::fmaf calls and nothing else.
 #include "internal.h"
+#include "level_driver.h"
 #include "spmv/ic0.h"
 #include "spmv/ilu0.h"
 #include "spmv/sptrsv.h"
 
 #include <algorithm>
-#include <climits>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -154,127 +154,62 @@ int ic0_cpu_csr(const CSRMatrix* A, float* l_values, int* bad_pivot) {
 namespace detail {
 namespace {
 
-using ScheduleRef = std::shared_ptr<const SptrsvSchedule>;
-
-int lanes_for(Factor0Kind kind, const SptrsvSchedule& s) {
-    if (int f = forced_lanes(kind == Factor0Kind::IC0 ? "ic0_lanes" : "ilu0_lanes")) return f;
-    return pick_lanes_per_row(static_cast<float>(s.nnz) / static_cast<float>(s.num_rows));
-}
-
-// Everything before the launches.  On SUCCESS with *schedule null there is nothing to do (no rows).
-int prepare(Factor0Kind kind, const CSRMatrix* A, const float* d_out, hipStream_t stream, ScheduleRef* schedule,
-            float* analysis_ms) {
-    schedule->reset();
-    *analysis_ms = 0.0f;
-    if (!A || !d_out) return code(SpMVError::INVALID_ARGUMENT);
-    bool nothing = false;
-    const int status = sptrsv_check_matrix(A, &nothing);
-    if (status != 0 || nothing) return status;
-    if (sptrsv_partial_overlap(A->d_values, d_out, A->nnz)) return code(SpMVError::INVALID_ARGUMENT);
-    ScheduleRef found;
-    const int analysed = sptrsv_schedule_for(A, SpTRSVConfig::LOWER, stream, &found, analysis_ms);
-    if (analysed != 0) return analysed;
-    if (found->first_unsorted_row >= 0 || found->first_missing_diagonal >= 0 ||
-        (kind == Factor0Kind::IC0 && found->one_sided_row >= 0)) {
-        return code(SpMVError::INVALID_ARGUMENT);
+// ilu0_csr / ic0_csr and their async forms as an Op of level_driver.h
+struct CsrFactor {
+    Factor0Kind kind;
+    const CSRMatrix* A;
+    float* d_out;
+    int prepare(hipStream_t stream, ScheduleRef* schedule, float* analysis_ms) const {
+        schedule->reset();
+        *analysis_ms = 0.0f;
+        if (!A || !d_out) return code(SpMVError::INVALID_ARGUMENT);
+        bool nothing = false;
+        const int status = sptrsv_check_matrix(A, &nothing);
+        if (status != 0 || nothing) return status;
+        if (partial_overlap(A->d_values, d_out, A->nnz)) return code(SpMVError::INVALID_ARGUMENT);
+        ScheduleRef found;
+        const int analysed = sptrsv_schedule_for(A, SpTRSVConfig::LOWER, stream, &found, analysis_ms);
+        if (analysed != 0) return analysed;
+        if (found->first_unsorted_row >= 0 || found->first_missing_diagonal >= 0 ||
+            (kind == Factor0Kind::IC0 && found->one_sided_row >= 0)) {
+            return code(SpMVError::INVALID_ARGUMENT);
+        }
+        *schedule = found;
+        return code(SpMVError::SUCCESS);
     }
-    *schedule = found;
-    return code(SpMVError::SUCCESS);
-}
-
-// what ilu0_csr and ic0_csr report, under the names they share
-struct Factor0Run {
-    int error_code = 0;
-    int num_levels = 0, launches = 0, lanes_per_row = 0;
-    int pivot = -1;                    // lowest row with a bad pivot, or -1
-    float analysis_ms = 0.0f, elapsed_ms = 0.0f;
+    int lanes(const SptrsvSchedule& s) const {
+        if (int f = forced_lanes(kind == Factor0Kind::IC0 ? "ic0_lanes" : "ilu0_lanes")) return f;
+        return pick_lanes_per_row(static_cast<float>(s.nnz) / static_cast<float>(s.num_rows));
+    }
+    // d_pivot null: the launches alone, no pivot scan
+    hipError_t launch(const SptrsvSchedule& schedule, int lanes, hipStream_t stream, unsigned* d_pivot) const {
+        return launch_factor0(kind, schedule, A, A->d_values, d_out, lanes, d_pivot, stream);
+    }
 };
-
-// the blocking, timed factorisation
-Factor0Run factor0_csr(Factor0Kind kind, const char* trace_name, const CSRMatrix* A, float* d_out) {
-    Factor0Run result;
-    hipStream_t stream = current_stream();
-    ScheduleRef schedule;
-    result.error_code = prepare(kind, A, d_out, stream, &schedule, &result.analysis_ms);
-    if (result.error_code != 0 || !schedule) return result;
-
-    const TraceRange range(trace_name);
-    const int lanes = lanes_for(kind, *schedule);
-    result.num_levels = schedule->num_levels;
-    result.launches = static_cast<int>(schedule->groups.size());
-    result.lanes_per_row = lanes;
-    unsigned* d_pivot = nullptr;       // lowest bad row as an unsigned minimum; all ones = none
-    if (hipMalloc(reinterpret_cast<void**>(&d_pivot), sizeof(unsigned)) != hipSuccess) {
-        (void)hipGetLastError();
-        result.error_code = code(SpMVError::CUDA_MALLOC);
-        return result;
-    }
-    EventPair& ev = thread_events();
-    unsigned pivot = UINT_MAX;
-    bool ok = hipMemsetAsync(d_pivot, 0xff, sizeof(unsigned), stream) == hipSuccess &&
-              ev.start && ev.stop && hipEventRecord(ev.start, stream) == hipSuccess;
-    ok = ok && launch_factor0(kind, *schedule, A, A->d_values, d_out, lanes, d_pivot, stream) == hipSuccess;
-    ok = ok && hipEventRecord(ev.stop, stream) == hipSuccess &&
-         hipMemcpyAsync(&pivot, d_pivot, sizeof(unsigned), hipMemcpyDeviceToHost, stream) == hipSuccess;
-    // always drained: `pivot` lives in this frame
-    ok = (hipStreamSynchronize(stream) == hipSuccess) && ok && hipGetLastError() == hipSuccess &&
-         hipEventElapsedTime(&result.elapsed_ms, ev.start, ev.stop) == hipSuccess;
-    (void)hipFree(d_pivot);
-    if (!ok) {
-        (void)hipGetLastError();
-        result.error_code = code(SpMVError::KERNEL_LAUNCH);
-        return result;
-    }
-    result.pivot = pivot == UINT_MAX ? -1 : static_cast<int>(pivot);
-    return result;
-}
-
-// the launches alone, on the caller's stream: no pivot scan, nothing read back
-int factor0_csr_async(Factor0Kind kind, const CSRMatrix* A, float* d_out, hipStream_t stream) {
-    ScheduleRef schedule;
-    float analysis_ms = 0.0f;
-    const int status = prepare(kind, A, d_out, stream, &schedule, &analysis_ms);
-    if (status != 0 || !schedule) return status;
-    const hipError_t e = launch_factor0(kind, *schedule, A, A->d_values, d_out, lanes_for(kind, *schedule), nullptr,
-                                        stream);
-    return e == hipSuccess ? code(SpMVError::SUCCESS) : code(SpMVError::KERNEL_LAUNCH);
-}
 
 } // namespace
 } // namespace detail
 
 ILU0Result ilu0_csr(const CSRMatrix* A, float* d_lu_values) {
-    const detail::Factor0Run run = detail::factor0_csr(detail::Factor0Kind::ILU0, "spmv:ilu0_csr", A, d_lu_values);
-    ILU0Result result;
-    result.error_code = run.error_code;
-    result.num_levels = run.num_levels;
-    result.launches = run.launches;
-    result.lanes_per_row = run.lanes_per_row;
-    result.zero_pivot = run.pivot;
-    result.analysis_ms = run.analysis_ms;
-    result.elapsed_ms = run.elapsed_ms;
-    return result;
+    using namespace detail;
+    return factor_result(timed_factor("spmv:ilu0_csr", CsrFactor{Factor0Kind::ILU0, A, d_lu_values}),
+                         &ILU0Result::zero_pivot);
 }
 
 IC0Result ic0_csr(const CSRMatrix* A, float* d_l_values) {
-    const detail::Factor0Run run = detail::factor0_csr(detail::Factor0Kind::IC0, "spmv:ic0_csr", A, d_l_values);
-    IC0Result result;
-    result.error_code = run.error_code;
-    result.num_levels = run.num_levels;
-    result.launches = run.launches;
-    result.lanes_per_row = run.lanes_per_row;
-    result.bad_pivot = run.pivot;
-    result.analysis_ms = run.analysis_ms;
-    result.elapsed_ms = run.elapsed_ms;
-    return result;
+    using namespace detail;
+    return factor_result(timed_factor("spmv:ic0_csr", CsrFactor{Factor0Kind::IC0, A, d_l_values}),
+                         &IC0Result::bad_pivot);
 }
 
 int ilu0_csr_async(const CSRMatrix* A, float* d_lu_values, hipStream_t stream) {
-    return detail::factor0_csr_async(detail::Factor0Kind::ILU0, A, d_lu_values, stream);
+    using namespace detail;
+    return launch_factor_async(CsrFactor{Factor0Kind::ILU0, A, d_lu_values}, stream);
 }
 
 int ic0_csr_async(const CSRMatrix* A, float* d_l_values, hipStream_t stream) {
-    return detail::factor0_csr_async(detail::Factor0Kind::IC0, A, d_l_values, stream);
+    using namespace detail;
+    return launch_factor_async(CsrFactor{Factor0Kind::IC0, A, d_l_values}, stream);
 }
 
 } // namespace spmv

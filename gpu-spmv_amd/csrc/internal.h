@@ -101,6 +101,7 @@ struct SptrsvSchedule {
     int num_rows = 0, num_cols = 0, uplo = 0;
     ~SptrsvSchedule();
 };
+using ScheduleRef = std::shared_ptr<const SptrsvSchedule>;
 
 struct CsrAux {
     PrWorkspace pagerank;
@@ -358,8 +359,10 @@ inline int stream_finished(hipStream_t s) {
 // of kSpgemmSlots slots (a power of two; a row may fill half of them), the last class is the dense accumulator
 constexpr int kSpgemmClasses = 5;
 constexpr int kSpgemmSlots[kSpgemmClasses - 1] = {32, 256, 2048, 16384};
-// sparse triangular solve (sptrsv.hip): the launches of one solve, one per group of the schedule, in stream order;
-// kSptrsvNarrowRows is the widest level a single workgroup takes inside a run of levels
+// sparse triangular solve (sptrsv.hip): the launches of one solve, one per group of the schedule, in stream order
+// (device_common.h launch_level_groups); kSptrsvNarrowRows is the widest level a single workgroup takes inside a run
+// of levels.  What the drivers over a schedule share (predicates, the timed, async and analyze shapes) is in
+// level_driver.h.
 constexpr int kSptrsvNarrowRows = 256;
 constexpr int kSptrsvMaxRunLevels = 8192;     // levels per single-workgroup launch at most (bounds one kernel's time)
 hipError_t launch_sptrsv(const SptrsvSchedule& schedule, const CSRMatrix* A, const float* d_b, float* d_x, int uplo,
@@ -380,14 +383,11 @@ struct SptrsvMultiArrays {
 };
 hipError_t launch_sptrsv_multi(const SptrsvSchedule& schedule, const CSRMatrix* A, const SptrsvMultiArrays& arrays,
                                int uplo, int unit_diagonal, bool ordered, int lanes_per_row, hipStream_t s);
-// b and x overlap without being the same array (solver_common.h ranges_overlap; the solve in place is allowed)
-bool sptrsv_partial_overlap(const float* d_b, const float* d_x, long long n);
 // the schedule cache of sptrsv_host.cpp for the callers that solve or factor with it (factor0_host.cpp, bicgstab.hip):
 // checks 2-4 of sptrsv.h (not square, no rows, missing device arrays); A's `uplo` schedule, built and cached when it
 // is not there (*analysis_ms = the host time of a build, 0 for a cache hit); the lanes per row of an ordered = 0 solve
 int sptrsv_check_matrix(const CSRMatrix* A, bool* nothing_to_do);
-int sptrsv_schedule_for(const CSRMatrix* A, int uplo, hipStream_t stream, std::shared_ptr<const SptrsvSchedule>* out,
-                        float* analysis_ms);
+int sptrsv_schedule_for(const CSRMatrix* A, int uplo, hipStream_t stream, ScheduleRef* out, float* analysis_ms);
 int sptrsv_lanes_for(const SptrsvSchedule& schedule);
 // The level analysis on the device (sptrsv_analysis.hip), for A that passed sptrsv_check_matrix and
 // has rows: structure_checked's rule first (INVALID_FORMAT before any kernel follows a row pointer or a column), then

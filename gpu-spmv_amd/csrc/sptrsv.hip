@@ -1,19 +1,14 @@
 // sptrsv.hip — solve kernels of the sparse triangular solve (include/spmv/sptrsv.h).
 //
-// One kernel, two ways to launch it.  The schedule (sptrsv_host.cpp) sorts the rows into dependency levels; the
-// rows of one level are independent.  A launch covers the levels [level_begin, level_end):
-//   * one wide level: a grid over order[level_ptr[l] .. level_ptr[l + 1]), LANES lanes per row;
-//   * a run of narrow levels (each at most kSptrsvNarrowRows rows): ONE workgroup walks them in order with
-//     __syncthreads() in between.  __syncthreads() is a workgroup-scope release, the barrier, and a workgroup-scope
-//     acquire; the waves of a workgroup share their CU's vector L1, which their own write-through stores keep
-//     current, so the x a level wrote is what the next level's plain loads return.  (Another CU would need an
-//     agent-scope acquire; nothing here reads another workgroup's x inside a launch.)
-// The order between launches is stream order.  No workgroup waits for another one: no flags, no spinning.
+// One kernel, launched per group of the schedule by the level layer of device_common.h (launch_level_groups: a grid
+// per wide level, one workgroup per run of narrow levels).  The walk over the levels is for_each_level_row's, written
+// out: through the helper the instantiations with more than one lane came out with another block layout and a split
+// DPP add, 0.7 to 0.9 % on a preconditioned CG step (profiles/level_layer_ab.txt).  Why a level sees the previous
+// level's x is said at the helper.
 //
 // x and b are deliberately not __restrict__: they may be the same array, and x is read and written in one launch.
 #include "internal.h"
 #include "device_common.h"
-#include "solver_common.h"
 
 #include <hip/hip_runtime.h>
 
@@ -86,24 +81,14 @@ void sptrsv_kernel(int n, int nnz, const int* __restrict__ row_ptrs, const int* 
 template <int LANES, bool ORDERED>
 hipError_t launch_groups(const SptrsvSchedule& sch, const CSRMatrix* A, const float* b, float* x, int upper, int unit,
                          hipStream_t s) {
-    constexpr int kRowsPerBlock = kBlock / LANES;
-    for (const SptrsvSchedule::Group& g : sch.groups) {
-        // a run of levels is one workgroup (the barrier is its only ordering); one level alone takes a grid
-        const int grid = g.level_end - g.level_begin > 1 ? 1 : capped_grid(g.rows, kRowsPerBlock);
+    return launch_level_groups<LANES>(sch, [&](int grid, int level_begin, int level_end) {
         sptrsv_kernel<LANES, ORDERED><<<grid, kBlock, 0, s>>>(A->num_rows, A->nnz, A->d_row_ptrs, A->d_col_indices,
                                                              A->d_values, b, x, sch.d_level_ptr, sch.d_order,
-                                                             g.level_begin, g.level_end, upper, unit);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+                                                             level_begin, level_end, upper, unit);
+    });
 }
 
 } // namespace
-
-bool sptrsv_partial_overlap(const float* d_b, const float* d_x, long long n) {
-    return d_b != d_x && solver::ranges_overlap(d_b, d_x, n);
-}
 
 hipError_t launch_sptrsv(const SptrsvSchedule& schedule, const CSRMatrix* A, const float* d_b, float* d_x, int uplo,
                          int unit_diagonal, bool ordered, int lanes_per_row, hipStream_t s) {

@@ -2,6 +2,7 @@
 // analysis, the schedule kept with the matrix, the host substitution sptrsv_cpu_csr and the entry points.  The
 // kernels are in sptrsv.hip.  Built without FMA contraction: sptrsv_cpu_csr rounds the product, then the sum.
 #include "internal.h"
+#include "level_driver.h"
 #include "spmv/sptrsv.h"
 
 #include <algorithm>
@@ -11,11 +12,24 @@
 
 namespace spmv {
 
+namespace detail {
+namespace {
+
+// B and X of a k-wide solve (num_rows x k, leading dimensions ldb, ldx) overlap without being the solve in place
+bool multi_overlap(const float* B, int ldb, const float* X, int ldx, int k, int num_rows) {
+    if (B == X && ldb == ldx) return false;
+    const long long rows = num_rows - 1;
+    return spans_overlap(B, rows * ldb + k, X, rows * ldx + k);
+}
+
+} // namespace
+} // namespace detail
+
 int sptrsv_levels(int num_rows, const int* row_ptrs, const int* col_indices, int uplo, int* level_ptr, int* order,
                   int* num_levels, int* first_missing_diagonal) {
     using detail::code;
     if (num_rows < 0 || !row_ptrs || !level_ptr || !num_levels || (num_rows > 0 && !order) ||
-        (uplo != SpTRSVConfig::LOWER && uplo != SpTRSVConfig::UPPER)) {
+        !detail::uplo_ok(uplo)) {
         return code(SpMVError::INVALID_ARGUMENT);
     }
     const int n = num_rows;
@@ -71,12 +85,8 @@ int sptrsv_cpu_csr(const CSRMatrix* A, const float* b, float* x, const SpTRSVCon
     if (n < 0 || !A->row_ptrs || (A->nnz > 0 && (!A->col_indices || !A->values))) {
         return code(SpMVError::INVALID_ARGUMENT);
     }
-    const SpTRSVConfig defaults;
-    const SpTRSVConfig& cfg = config ? *config : defaults;
-    if ((cfg.uplo != SpTRSVConfig::LOWER && cfg.uplo != SpTRSVConfig::UPPER) ||
-        (cfg.diag != SpTRSVConfig::NON_UNIT && cfg.diag != SpTRSVConfig::UNIT)) {
-        return code(SpMVError::INVALID_ARGUMENT);
-    }
+    const SpTRSVConfig cfg = detail::config_or_default(config);
+    if (!detail::uplo_ok(cfg.uplo) || !detail::diag_ok(cfg.diag)) return code(SpMVError::INVALID_ARGUMENT);
     const bool upper = cfg.uplo == SpTRSVConfig::UPPER;
     const bool unit = cfg.diag == SpTRSVConfig::UNIT;
     const int* ptr = A->row_ptrs;
@@ -127,18 +137,9 @@ int sptrsv_cpu_csr_multi(const CSRMatrix* A, const float* B, int ldb, float* X, 
     if (n < 0 || !A->row_ptrs || (A->nnz > 0 && (!A->col_indices || !A->values))) {
         return code(SpMVError::INVALID_ARGUMENT);
     }
-    const SpTRSVConfig defaults;
-    const SpTRSVConfig& cfg = config ? *config : defaults;
-    if ((cfg.uplo != SpTRSVConfig::LOWER && cfg.uplo != SpTRSVConfig::UPPER) ||
-        (cfg.diag != SpTRSVConfig::NON_UNIT && cfg.diag != SpTRSVConfig::UNIT)) {
-        return code(SpMVError::INVALID_ARGUMENT);
-    }
-    if (!(B == X && ldb == ldx)) {
-        const uintptr_t b0 = reinterpret_cast<uintptr_t>(B), x0 = reinterpret_cast<uintptr_t>(X);
-        const uintptr_t nb = (static_cast<uintptr_t>(n - 1) * ldb + k) * sizeof(float);
-        const uintptr_t nx = (static_cast<uintptr_t>(n - 1) * ldx + k) * sizeof(float);
-        if (b0 < x0 + nx && x0 < b0 + nb) return code(SpMVError::INVALID_ARGUMENT);
-    }
+    const SpTRSVConfig cfg = detail::config_or_default(config);
+    if (!detail::uplo_ok(cfg.uplo) || !detail::diag_ok(cfg.diag)) return code(SpMVError::INVALID_ARGUMENT);
+    if (detail::multi_overlap(B, ldb, X, ldx, k, n)) return code(SpMVError::INVALID_ARGUMENT);
     const bool upper = cfg.uplo == SpTRSVConfig::UPPER;
     const bool unit = cfg.diag == SpTRSVConfig::UNIT;
     const int* ptr = A->row_ptrs;
@@ -190,8 +191,6 @@ SptrsvSchedule::~SptrsvSchedule() {
 }
 
 namespace {
-
-using ScheduleRef = std::shared_ptr<const SptrsvSchedule>;
 
 // One launch per group: a level wider than kSptrsvNarrowRows alone, consecutive narrower ones together.
 void group_levels(const std::vector<int>& level_ptr, int num_levels, std::vector<SptrsvSchedule::Group>* groups) {
@@ -341,11 +340,7 @@ int prepare_checked(const CSRMatrix* A, const SpTRSVConfig& cfg, hipStream_t str
     bool nothing = false;
     const int status = check_matrix(A, &nothing);
     if (status != 0 || nothing) return status;
-    if ((cfg.uplo != SpTRSVConfig::LOWER && cfg.uplo != SpTRSVConfig::UPPER) ||
-        (cfg.diag != SpTRSVConfig::NON_UNIT && cfg.diag != SpTRSVConfig::UNIT) ||
-        (cfg.ordered != 0 && cfg.ordered != 1)) {
-        return code(SpMVError::INVALID_ARGUMENT);
-    }
+    if (!config_ok(cfg)) return code(SpMVError::INVALID_ARGUMENT);
     if (overlaps()) return code(SpMVError::INVALID_ARGUMENT);
     ScheduleRef found;
     const int analysed = schedule_for(A, cfg.uplo, stream, &found, analysis_ms);
@@ -357,61 +352,60 @@ int prepare_checked(const CSRMatrix* A, const SpTRSVConfig& cfg, hipStream_t str
     return code(SpMVError::SUCCESS);
 }
 
-int prepare(const CSRMatrix* A, const float* d_b, const float* d_x, const SpTRSVConfig& cfg, hipStream_t stream,
-            ScheduleRef* schedule, float* analysis_ms) {
-    schedule->reset();
-    *analysis_ms = 0.0f;
-    if (!A || !d_b || !d_x) return code(SpMVError::INVALID_ARGUMENT);
-    return prepare_checked(A, cfg, stream, [&] { return sptrsv_partial_overlap(d_b, d_x, A->num_rows); }, schedule,
-                           analysis_ms);
-}
-
 constexpr int kMaxColumns = 32;
 
-// the floats [a, a + na) and [b, b + nb) share a byte
-bool spans_overlap(const float* a, long long na, const float* b, long long nb) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + static_cast<uintptr_t>(nb) * sizeof(float) &&
-           b0 < a0 + static_cast<uintptr_t>(na) * sizeof(float);
-}
+// sptrsv_csr and sptrsv_csr_async as an Op of level_driver.h
+struct CsrSolve {
+    const CSRMatrix* A;
+    const float* d_b;
+    float* d_x;
+    SpTRSVConfig cfg;
+    int prepare(hipStream_t stream, ScheduleRef* schedule, float* analysis_ms) const {
+        schedule->reset();
+        *analysis_ms = 0.0f;
+        if (!A || !d_b || !d_x) return code(SpMVError::INVALID_ARGUMENT);
+        return prepare_checked(A, cfg, stream, [&] { return partial_overlap(d_b, d_x, A->num_rows); }, schedule,
+                               analysis_ms);
+    }
+    int lanes(const SptrsvSchedule& schedule) const { return lanes_for(schedule, cfg.ordered == 1); }
+    hipError_t launch(const SptrsvSchedule& schedule, int lanes, hipStream_t stream) const {
+        return launch_sptrsv(schedule, A, d_b, d_x, cfg.uplo, cfg.diag == SpTRSVConfig::UNIT, cfg.ordered == 1, lanes,
+                             stream);
+    }
+};
 
-// B and X of a k-wide solve (num_rows x k, leading dimensions ldb, ldx) overlap without being the solve in place
-bool multi_overlap(const float* B, int ldb, const float* X, int ldx, int k, int num_rows) {
-    if (B == X && ldb == ldx) return false;
-    const long long rows = num_rows - 1;
-    return spans_overlap(B, rows * ldb + k, X, rows * ldx + k);
-}
-
-// the checks of sptrsv_csr_multi that come before sptrsv_csr's
-int check_multi(const void* A, const void* B, int ldb, const void* X, int ldx, int k) {
-    if (!A || !B || !X) return code(SpMVError::INVALID_ARGUMENT);
-    if (k < 1 || k > kMaxColumns) return code(SpMVError::INVALID_ARGUMENT);
-    if (ldb < k || ldx < k) return code(SpMVError::INVALID_ARGUMENT);
-    return code(SpMVError::SUCCESS);
-}
-
-int prepare_multi(const CSRMatrix* A, const float* d_B, int ldb, const float* d_X, int ldx, int k,
-                  const SpTRSVConfig& cfg, hipStream_t stream, ScheduleRef* schedule, float* analysis_ms) {
-    schedule->reset();
-    *analysis_ms = 0.0f;
-    const int status = check_multi(A, d_B, ldb, d_X, ldx, k);
-    if (status != 0) return status;
-    return prepare_checked(A, cfg, stream, [&] { return multi_overlap(d_B, ldb, d_X, ldx, k, A->num_rows); },
-                           schedule, analysis_ms);
-}
-
-// a caller's arrays under sptrsv_multi.hip's addressing rule: the windows of w columns lie side by side in a row
-SptrsvMultiArrays caller_arrays(const float* d_B, int ldb, float* d_X, int ldx, int k) {
-    const int w = k <= 4 ? 4 : 8;
-    return SptrsvMultiArrays{d_B, ldb, w, d_X, ldx, w, k, w};
-}
+// sptrsv_csr_multi and sptrsv_csr_multi_async
+struct CsrMultiSolve {
+    const CSRMatrix* A;
+    const float* d_B;
+    int ldb;
+    float* d_X;
+    int ldx, k;
+    SpTRSVConfig cfg;
+    int prepare(hipStream_t stream, ScheduleRef* schedule, float* analysis_ms) const {
+        schedule->reset();
+        *analysis_ms = 0.0f;
+        // the checks that come before sptrsv_csr's
+        if (!A || !d_B || !d_X) return code(SpMVError::INVALID_ARGUMENT);
+        if (k < 1 || k > kMaxColumns) return code(SpMVError::INVALID_ARGUMENT);
+        if (ldb < k || ldx < k) return code(SpMVError::INVALID_ARGUMENT);
+        return prepare_checked(A, cfg, stream, [&] { return multi_overlap(d_B, ldb, d_X, ldx, k, A->num_rows); },
+                               schedule, analysis_ms);
+    }
+    int lanes(const SptrsvSchedule& schedule) const { return lanes_for(schedule, cfg.ordered == 1); }
+    hipError_t launch(const SptrsvSchedule& schedule, int lanes, hipStream_t stream) const {
+        // the caller's arrays under sptrsv_multi.hip's addressing rule: the windows of w columns lie side by side in a row
+        const int w = k <= 4 ? 4 : 8;
+        return launch_sptrsv_multi(schedule, A, SptrsvMultiArrays{d_B, ldb, w, d_X, ldx, w, k, w}, cfg.uplo,
+                                   cfg.diag == SpTRSVConfig::UNIT, cfg.ordered == 1, lanes, stream);
+    }
+};
 
 } // namespace
 
 int sptrsv_check_matrix(const CSRMatrix* A, bool* nothing_to_do) { return check_matrix(A, nothing_to_do); }
 
-int sptrsv_schedule_for(const CSRMatrix* A, int uplo, hipStream_t stream, std::shared_ptr<const SptrsvSchedule>* out,
-                        float* analysis_ms) {
+int sptrsv_schedule_for(const CSRMatrix* A, int uplo, hipStream_t stream, ScheduleRef* out, float* analysis_ms) {
     return schedule_for(A, uplo, stream, out, analysis_ms);
 }
 
@@ -421,94 +415,25 @@ int sptrsv_lanes_for(const SptrsvSchedule& schedule) { return lanes_for(schedule
 
 SpTRSVResult sptrsv_csr(const CSRMatrix* A, const float* d_b, float* d_x, const SpTRSVConfig* config) {
     using namespace detail;
-    SpTRSVResult result;
-    const SpTRSVConfig defaults;
-    const SpTRSVConfig& cfg = config ? *config : defaults;
-    hipStream_t stream = current_stream();
-    ScheduleRef schedule;
-    result.error_code = prepare(A, d_b, d_x, cfg, stream, &schedule, &result.analysis_ms);
-    if (result.error_code != 0 || !schedule) return result;
-
-    const TraceRange range("spmv:sptrsv_csr");
-    const int lanes = lanes_for(*schedule, cfg.ordered == 1);
-    result.num_levels = schedule->num_levels;
-    result.launches = static_cast<int>(schedule->groups.size());
-    result.lanes_per_row = lanes;
-    EventPair& ev = thread_events();
-    if (!ev.start || !ev.stop || hipEventRecord(ev.start, stream) != hipSuccess) {
-        result.error_code = code(SpMVError::KERNEL_LAUNCH);
-        return result;
-    }
-    const hipError_t launched = launch_sptrsv(*schedule, A, d_b, d_x, cfg.uplo, cfg.diag == SpTRSVConfig::UNIT,
-                                              cfg.ordered == 1, lanes, stream);
-    const hipError_t recorded = hipEventRecord(ev.stop, stream);
-    const hipError_t waited = hipEventSynchronize(ev.stop);
-    if (launched != hipSuccess || recorded != hipSuccess || waited != hipSuccess || hipGetLastError() != hipSuccess ||
-        hipEventElapsedTime(&result.elapsed_ms, ev.start, ev.stop) != hipSuccess) {
-        result.error_code = code(SpMVError::KERNEL_LAUNCH);
-    }
-    return result;
+    return timed_solve("spmv:sptrsv_csr", CsrSolve{A, d_b, d_x, config_or_default(config)});
 }
 
 int sptrsv_csr_async(const CSRMatrix* A, const float* d_b, float* d_x, const SpTRSVConfig* config,
                      hipStream_t stream) {
     using namespace detail;
-    const SpTRSVConfig defaults;
-    const SpTRSVConfig& cfg = config ? *config : defaults;
-    ScheduleRef schedule;
-    float analysis_ms = 0.0f;
-    const int status = prepare(A, d_b, d_x, cfg, stream, &schedule, &analysis_ms);
-    if (status != 0 || !schedule) return status;
-    const hipError_t e = launch_sptrsv(*schedule, A, d_b, d_x, cfg.uplo, cfg.diag == SpTRSVConfig::UNIT,
-                                       cfg.ordered == 1, lanes_for(*schedule, cfg.ordered == 1), stream);
-    return e == hipSuccess ? code(SpMVError::SUCCESS) : code(SpMVError::KERNEL_LAUNCH);
+    return launch_async(CsrSolve{A, d_b, d_x, config_or_default(config)}, stream);
 }
 
 SpTRSVResult sptrsv_csr_multi(const CSRMatrix* A, const float* d_B, int ldb, float* d_X, int ldx, int k,
                               const SpTRSVConfig* config) {
     using namespace detail;
-    SpTRSVResult result;
-    const SpTRSVConfig defaults;
-    const SpTRSVConfig& cfg = config ? *config : defaults;
-    hipStream_t stream = current_stream();
-    ScheduleRef schedule;
-    result.error_code = prepare_multi(A, d_B, ldb, d_X, ldx, k, cfg, stream, &schedule, &result.analysis_ms);
-    if (result.error_code != 0 || !schedule) return result;
-
-    const TraceRange range("spmv:sptrsv_csr_multi");
-    const int lanes = lanes_for(*schedule, cfg.ordered == 1);
-    result.num_levels = schedule->num_levels;
-    result.launches = static_cast<int>(schedule->groups.size());
-    result.lanes_per_row = lanes;
-    EventPair& ev = thread_events();
-    if (!ev.start || !ev.stop || hipEventRecord(ev.start, stream) != hipSuccess) {
-        result.error_code = code(SpMVError::KERNEL_LAUNCH);
-        return result;
-    }
-    const hipError_t launched = launch_sptrsv_multi(*schedule, A, caller_arrays(d_B, ldb, d_X, ldx, k), cfg.uplo,
-                                                    cfg.diag == SpTRSVConfig::UNIT, cfg.ordered == 1, lanes, stream);
-    const hipError_t recorded = hipEventRecord(ev.stop, stream);
-    const hipError_t waited = hipEventSynchronize(ev.stop);
-    if (launched != hipSuccess || recorded != hipSuccess || waited != hipSuccess || hipGetLastError() != hipSuccess ||
-        hipEventElapsedTime(&result.elapsed_ms, ev.start, ev.stop) != hipSuccess) {
-        result.error_code = code(SpMVError::KERNEL_LAUNCH);
-    }
-    return result;
+    return timed_solve("spmv:sptrsv_csr_multi", CsrMultiSolve{A, d_B, ldb, d_X, ldx, k, config_or_default(config)});
 }
 
 int sptrsv_csr_multi_async(const CSRMatrix* A, const float* d_B, int ldb, float* d_X, int ldx, int k,
                            const SpTRSVConfig* config, hipStream_t stream) {
     using namespace detail;
-    const SpTRSVConfig defaults;
-    const SpTRSVConfig& cfg = config ? *config : defaults;
-    ScheduleRef schedule;
-    float analysis_ms = 0.0f;
-    const int status = prepare_multi(A, d_B, ldb, d_X, ldx, k, cfg, stream, &schedule, &analysis_ms);
-    if (status != 0 || !schedule) return status;
-    const hipError_t e = launch_sptrsv_multi(*schedule, A, caller_arrays(d_B, ldb, d_X, ldx, k), cfg.uplo,
-                                             cfg.diag == SpTRSVConfig::UNIT, cfg.ordered == 1,
-                                             lanes_for(*schedule, cfg.ordered == 1), stream);
-    return e == hipSuccess ? code(SpMVError::SUCCESS) : code(SpMVError::KERNEL_LAUNCH);
+    return launch_async(CsrMultiSolve{A, d_B, ldb, d_X, ldx, k, config_or_default(config)}, stream);
 }
 
 namespace detail {
@@ -516,24 +441,12 @@ namespace {
 
 // sptrsv_analyze and sptrsv_analyze_device: the same checks in the same order, then the cache
 SpTRSVResult analyze(const CSRMatrix* A, int uplo, bool on_device) {
-    SpTRSVResult result;
-    if (!A) {
-        result.error_code = code(SpMVError::INVALID_ARGUMENT);
-        return result;
-    }
-    bool nothing = false;
-    result.error_code = check_matrix(A, &nothing);
-    if (result.error_code != 0 || nothing) return result;
-    if (uplo != SpTRSVConfig::LOWER && uplo != SpTRSVConfig::UPPER) {
-        result.error_code = code(SpMVError::INVALID_ARGUMENT);
-        return result;
-    }
-    ScheduleRef schedule;
-    result.error_code = schedule_for(A, uplo, current_stream(), &schedule, &result.analysis_ms, on_device);
-    if (result.error_code != 0) return result;
-    result.num_levels = schedule->num_levels;
-    result.launches = static_cast<int>(schedule->groups.size());
-    return result;
+    return analyze_levels(
+        uplo,
+        [&](bool* nothing) { return A ? check_matrix(A, nothing) : code(SpMVError::INVALID_ARGUMENT); },
+        [&](hipStream_t stream, ScheduleRef* schedule, float* analysis_ms) {
+            return schedule_for(A, uplo, stream, schedule, analysis_ms, on_device);
+        });
 }
 
 } // namespace
@@ -546,7 +459,7 @@ SpTRSVResult sptrsv_analyze_device(const CSRMatrix* A, int uplo) { return detail
 int sptrsv_schedule_get(const CSRMatrix* A, int uplo, int* level_ptr, int* order, SpTRSVScheduleInfo* info) {
     using namespace detail;
     if (!A) return code(SpMVError::INVALID_ARGUMENT);
-    if (uplo != SpTRSVConfig::LOWER && uplo != SpTRSVConfig::UPPER) return code(SpMVError::INVALID_ARGUMENT);
+    if (!uplo_ok(uplo)) return code(SpMVError::INVALID_ARGUMENT);
     ScheduleRef schedule;
     if (CsrAux* aux = aux_lookup(A->d_row_ptrs, false)) {
         std::lock_guard<std::mutex> guard(aux->sptrsv_lock);
@@ -563,8 +476,7 @@ int sptrsv_schedule_get(const CSRMatrix* A, int uplo, int* level_ptr, int* order
         return code(SpMVError::CUDA_MEMCPY);
     }
     if (info) {
-        info->num_levels = schedule->num_levels;
-        info->launches = static_cast<int>(schedule->groups.size());
+        copy_counts(*schedule, info);
         info->first_missing_diagonal = schedule->first_missing_diagonal;
         info->first_unsorted_row = schedule->first_unsorted_row;
         info->one_sided_row = schedule->one_sided_row;

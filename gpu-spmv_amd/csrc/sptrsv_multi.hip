@@ -1,10 +1,11 @@
 // sptrsv_multi.hip — the sparse triangular solve for k right-hand sides in one launch sequence
 // (include/spmv/sptrsv.h sptrsv_csr_multi).
 //
-// sptrsv.hip's kernel, k-wide: the same schedule, the same two ways to launch (a grid per wide level, one workgroup
-// with __syncthreads() between the levels of a narrow run), the same thread-to-row mapping, the same clamps of row
-// pointers, column indices and the order array.  No flags, no spinning, no workgroup waiting for another.  A lane
-// keeps W accumulators (4 up to k = 4, else 8; 4 at 32 and 64 lanes per row), walks the entries begin + lane,
+// sptrsv.hip's kernel, k-wide: the same schedule, the same launches (device_common.h launch_level_groups), the same
+// walk over the levels, written out as there (through for_each_level_row the W = 8 kernels measured 0.4 to 0.5 %
+// slower on the upper solves: profiles/level_layer_ab.txt), the same clamps of row pointers, column indices and the
+// order array.
+// A lane keeps W accumulators (4 up to k = 4, else 8; 4 at 32 and 64 lanes per row), walks the entries begin + lane,
 // begin + lane + LANES, ... as the single kernel does, loads the slice X[c, j0 : j0 + W] of each entry once and
 // applies the single kernel's operation per column in entry order; the partial sums fold with group_sum<LANES> per
 // accumulator.  So column j is bit for bit sptrsv_kernel<LANES, ORDERED> on that column.  For k > W the further
@@ -121,23 +122,17 @@ void sptrsv_multi_kernel(int n, int nnz, const int* __restrict__ row_ptrs, const
 template <int LANES, int W, int WS, bool ORDERED>
 hipError_t launch_groups(const SptrsvSchedule& sch, const CSRMatrix* A, const SptrsvMultiArrays& a, int upper,
                          int unit, hipStream_t s) {
-    constexpr int kRowsPerBlock = kBlock / LANES;
     // 16-byte accesses: the base and every window and row offset are multiples of 16 bytes
     const auto vec = [](const float* p, long long ld, long long window) {
         return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && ld % 4 == 0 && window % 4 == 0;
     };
     const int flags = (upper ? kUpper : 0) | (unit ? kUnit : 0) | (vec(a.B, a.ldb, a.b_window) ? kVecB : 0) |
                       (vec(a.X, a.ldx, a.x_window) ? kVecX : 0);
-    for (const SptrsvSchedule::Group& g : sch.groups) {
-        // a run of levels is one workgroup (the barrier is its only ordering); one level alone takes a grid
-        const int grid = g.level_end - g.level_begin > 1 ? 1 : capped_grid(g.rows, kRowsPerBlock);
+    return launch_level_groups<LANES>(sch, [&](int grid, int level_begin, int level_end) {
         sptrsv_multi_kernel<LANES, W, WS, ORDERED><<<grid, kBlock, 0, s>>>(
             A->num_rows, A->nnz, A->d_row_ptrs, A->d_col_indices, A->d_values, a.B, a.ldb, a.b_window, a.X, a.ldx,
-            a.x_window, a.k, sch.d_level_ptr, sch.d_order, g.level_begin, g.level_end, flags);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+            a.x_window, a.k, sch.d_level_ptr, sch.d_order, level_begin, level_end, flags);
+    });
 }
 
 // WS: the layout's window.  Eight accumulators per lane at 32 and 64 lanes per row push scalar registers out (the

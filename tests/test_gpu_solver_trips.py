@@ -1,4 +1,5 @@
-"""cg_solve, cg_solve_ic, bicgstab_solve, bicgstab_solve_lu and sptrsv_csr past the grid caps, every step to the bit.
+"""cg_solve, cg_solve_ic, bicgstab_solve, bicgstab_solve_lu and sptrsv_csr past the grid caps, every step to the bit;
+and one level schedule through both launch shapes of the level walk (the last section).
 
 csrc/solver_common.h caps the element-wise kernels of the Krylov solvers at 1024 workgroups (V = 262 144 elements a
 trip) and the row kernels, sptrsv_kernel on a wide level among them, at 2048 workgroups (R_L = 524 288 / L rows a
@@ -17,12 +18,15 @@ import numpy as np
 import pytest
 
 import exact_data as ed
+import precond_trip_cases as pt
 
 pytestmark = pytest.mark.gpu
 
 cg_tests = importlib.import_module("test_gpu_cg")
 bicg_tests = importlib.import_module("test_gpu_bicgstab")
 sptrsv_tests = importlib.import_module("test_gpu_sptrsv")
+multi_tests = importlib.import_module("test_gpu_sptrsv_multi")
+ic0_tests = importlib.import_module("test_gpu_ic0")
 assert_bits = importlib.import_module("test_gpu_lane_sweep").assert_bits
 
 NONE, JACOBI = 0, 1
@@ -190,3 +194,68 @@ def test_sptrsv_two_wide_levels_past_the_grid_cap(gpu, monkeypatch, L, uplo, uni
                 assert_bits(case["rp"], got, case["x"], what)
     finally:
         gpu.csr_destroy(A)
+
+
+# ------------------------------------------------------------------------------------------ both launch shapes
+MIXED_CHAINS = 5                                 # rows of every narrow level
+MIXED_K = 5
+
+
+def narrow_wide_narrow(L, seed=23):
+    """(n, rp, ci, va, wide): a symmetric, diagonally dominant forest whose LOWER levels are, in this order, a run of 3
+    narrow levels (MIXED_CHAINS rows each), one wide level of kMaxResidentBlocks * (256 / L) + 1 rows and a run of 2
+    narrow levels: 3 launches, the first and the last one workgroup each, the wide level's grid at its cap with a
+    second trip in which exactly one group is live (its last row, on which a row of the fifth level hangs).
+    Every row stores one entry left of the diagonal at most, so IC(0) has no fill to drop and a row's sum is a single
+    product: the unordered solves round as the ordered one does, whatever the lane count."""
+    m = MIXED_CHAINS
+    wide = pt.ROW_BLOCKS * (pt.BLOCK // L) + 1
+    head = 3 * m
+    n = head + wide + 2 * m
+    child = np.arange(m, n, dtype=np.int64)
+    parent = child - m                                                  # the chains of levels 0-2, and level 5 on 4
+    leaves = np.arange(wide)
+    parent[head - m:head - m + wide] = 2 * m + leaves % m               # the wide level hangs on level 2
+    parent[head - m + wide:head + wide] = head + np.linspace(0, wide - 1, m).astype(np.int64)   # level 4 on the wide one
+    rng = np.random.default_rng(seed)
+    a = rng.uniform(0.25, 1.0, child.size) * rng.choice([-1.0, 1.0], child.size)
+    idx = np.arange(n, dtype=np.int64)
+    diag = 1.0 + np.bincount(child, np.abs(a), n) + np.bincount(parent, np.abs(a), n)
+    return pt._assemble(n, [child, parent, idx], [parent, child, idx], [a, a, diag]) + (wide,)
+
+
+@pytest.mark.parametrize("L", (64, 1))
+def test_a_narrow_run_a_wide_level_and_a_narrow_run_in_one_schedule(gpu, monkeypatch, L):
+    """One schedule, both launch shapes of for_each_level_row in one solve or factorisation (narrow_wide_narrow):
+    sptrsv_csr ordered (and unordered, which runs at the L lanes that give the wide level its second trip),
+    sptrsv_csr_multi at k = 5 and ic0_csr at L forced lanes per row, each bit for bit its CPU twin.  8193 wide rows
+    at 64 lanes, 524 289 at one lane."""
+    n, rp, ci, va, wide = narrow_wide_narrow(L)
+    assert wide == {64: 8193, 1: 524289}[L]
+    rng = np.random.default_rng(L)
+    B = rng.uniform(-1.0, 1.0, (n, MIXED_K)).astype(np.float32)
+    dev = multi_tests.Device(gpu, n, rp, ci, va)
+    try:
+        monkeypatch.setenv("SPMV_DEBUG", "sptrsv_lanes=%d,ic0_lanes=%d" % (L, L))
+        shape = lambda res: (res.error_code, res.num_levels, res.launches)
+        for ordered in (1, 0):                   # ordered: one lane whatever L; unordered: L lanes, the second trip
+            cfg = gpu.SpTRSVConfig(uplo=0, diag=0, ordered=ordered)
+            what = ("sptrsv_csr", L, ordered)
+            cpu = gpu.sptrsv_cpu_csr(dev.A, B[:, 0], cfg)
+            res, x = sptrsv_tests._solve(gpu, dev.A, B[:, 0], cfg, sentinel=np.nan)
+            assert shape(res) == (0, 6, 3) and res.lanes_per_row == (1 if ordered else L), what
+            assert_bits(rp, x, cpu, what)
+        cfg = gpu.SpTRSVConfig(uplo=0, diag=0, ordered=0)
+        cpu = np.stack([gpu.sptrsv_cpu_csr(dev.A, B[:, j], cfg) for j in range(MIXED_K)], axis=1)
+        res, X = dev.multi(B, cfg)
+        what = ("sptrsv_csr_multi", L, res.lanes_per_row)
+        assert shape(res) == (0, 6, 3) and res.lanes_per_row == L, what
+        np.testing.assert_array_equal(X.view(np.uint32), cpu.view(np.uint32), err_msg=str(what))
+        cpu, cpu_pivot = gpu.ic0_cpu_csr(dev.A)
+        assert cpu_pivot == -1
+        res, got = ic0_tests._factor(gpu, dev.A, va, False)
+        what = ("ic0_csr", L, res.lanes_per_row, res.bad_pivot)
+        assert shape(res) == (0, 6, 3) and res.lanes_per_row == L and res.bad_pivot == -1, what
+        np.testing.assert_array_equal(got.view(np.uint32), cpu.view(np.uint32), err_msg=str(what))
+    finally:
+        dev.close()
