@@ -20,8 +20,12 @@ def diag32(n, rp, ci, va):
     """fp32 sum of the stored (i,i) entries in storage order (0 where a row has none)"""
     d = np.zeros(n, np.float32)
     rows = rows_of(n, rp)
-    for j in np.flatnonzero(np.asarray(ci) == rows):
-        d[rows[j]] = np.float32(d[rows[j]] + np.float32(va[j]))
+    where = np.flatnonzero(np.asarray(ci) == rows)
+    owner = rows[where]                                         # ascending: a row's stored diagonals lie together
+    nth = np.arange(where.size) - np.searchsorted(owner, owner)
+    for k in range(int(nth.max(initial=-1)) + 1):               # the k-th stored diagonal of every row that has one
+        pick = nth == k
+        d[owner[pick]] = d[owner[pick]] + np.asarray(va, np.float32)[where[pick]]
     return d
 
 

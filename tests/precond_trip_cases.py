@@ -27,14 +27,20 @@ workgroup of a single row.  An element-wise case has VEC_TRIP + 257 elements.
                     the vectorised twin of amg_cases.Prover in int64 fixed point; JacobiProver adds the Jacobi
                     coarsest level to the Fraction prover, and the host test holds the twin to it.
 5. AMG setup        the shapes that put the MIS-2 grid at its cap and the element-wise kernels past theirs.
+6. Smoothed AMG     the same family with omega_p = 1: P averages (1/2, 1/2), the Galerkin matrix has 1/2 on its whole
+                    diagonal, -1/4 at distance two and a stored 0 at distance one, wd is 1/4 and 1, and the weighted
+                    cycle is dyadic throughout.  SmoothedProver is FastProver on the CSR arrays of the levels, of P
+                    and of PT as read from the host twins (no closed form); SmoothedFractions is its Fraction twin.
+                    PT has half of A's rows, so the three row sweeps pass their caps at different n.
 
-Nothing here had to be changed to be admitted: every V-cycle case of the issue is exact as stated (the host test
-prints the widths)."""
+Nothing here had to be changed to be admitted: every V-cycle case of the issues is exact as stated (the host tests
+print the widths)."""
 from fractions import Fraction
 
 import numpy as np
 
 import amg_cases as ac
+import amg_smoothed_cases as sc
 import exact_data as ed
 import fsai_cases as fc
 from exact_data import EXACT_LIMIT, ROW_TRIP_THREADS, VEC_TRIP, row_trip
@@ -495,8 +501,209 @@ def prove_vcycle_fast(n, coarsest, r, omega, pre, post, coarse_sweeps=None):
 
 
 # ------------------------------------------------------------------------------------------ 5. AMG setup on the device
-MIS_CAP_GRID = 96                             # poisson2d(96): 9216 rows, 2304 workgroups of 4 rows asked for at 64 lanes
+MIS_CAP_GRID = 96                            # poisson2d(96): 9216 rows, 2304 workgroups of 4 rows asked for at 64 lanes
 MIS_L8_GRID = 257                             # poisson2d(257): 66 049 rows, just past row_trip(8)
 MIS_SEEDS = (0, 0xDEADBEEF)
 SETUP_BAD_ROW = VEC_TRIP + 77                 # the zero diagonal of the rejected variant: the second trip of workgroup 0
 SETUP_LAST_PARTIAL_ROW = VEC_TRIP - 3         # and of a second one: workgroup 1023, the last partial min_fold_kernel reads
+
+
+# ------------------------------------------------------------------------------------------ 6. smoothed AMG V-cycle
+SMOOTHED_WEIGHT = 1.0                         # omega_p: at 1/2 the coarse diagonal is 5/8 and the cycle rounds
+# name: (n, forced amg_lanes or None, [(pre, coarse, post)]).  A has n rows, P has n, PT and level 1 have n / 2.
+# "below", "at" and "above" put PT's rows one under, at and one over row_trip(64) while A and P are in their third trip.
+# Nothing had to be narrowed to be admitted: the right-hand side is amg_cases.exact_rhs (integers in [-8, 8]) and the
+# widest sum of any case takes 18 bits (the host test prints them).
+SMOOTHED_CASES = {
+    "L64": (2 * (row_trip(64) + 5), 64, [(1, 1, 1), (2, 2, 2), (2, 4, 0)]),
+    "L8": (2 * (row_trip(8) + 33), 8, [(1, 4, 1)]),
+    "below": (2 * (row_trip(64) - 1), 64, [(1, 1, 1)]),
+    "at": (2 * row_trip(64), 64, [(1, 1, 1)]),
+    "above": (2 * (row_trip(64) + 1), 64, [(1, 1, 1)]),
+    "vec": (2 * VEC_ROWS, None, [(1, 1, 1), (2, 4, 0)]),
+}
+SMOOTHED_TWIN_ROWS = 2 * (ac.DENSE_ROWS + 8)  # the smallest family member whose coarsest level is Jacobi-solved
+SMOOTHED_TWIN_CHECKS = [(1, 1, 1), (2, 2, 2), (2, 4, 0), (1, 4, 1)]    # sweep counts of the comparison with Fractions
+
+
+def dyadic(values):
+    """(ints, shift) with values == ints * 2^-shift exactly, for the smallest shift up to 30"""
+    v = np.asarray(values, np.float64)
+    for shift in range(31):
+        scaled = v * float(1 << shift)
+        if (scaled == np.rint(scaled)).all():
+            ints = np.rint(scaled).astype(np.int64)
+            if int(np.abs(ints).max(initial=0)) >= 1 << 30:
+                break
+            return ints, shift
+    raise ac.NotExact("a coefficient is no short dyadic number")
+
+
+class SmoothedProver(FastProver):
+    """FastProver's fixed point and rule for the weighted cycle on level matrices, P and PT given as CSR arrays: no
+    closed form.  A coefficient (a matrix entry, wd_i) is an integer times 2^-shift (dyadic); a product with a value
+    must stay inside the fixed point.  row_total() is total() for the sums of a row sweep, one sum per row: the
+    terms are the row's products and, where the kernel's epilogue adds one, the row's own term (f_i of the residual,
+    x_i of the prolongation).  The dot product and the epilogue are held as ONE sum, which covers both."""
+
+    @staticmethod
+    def times(coefficient, v):
+        ints, shift = coefficient
+        if int(np.abs(ints).max(initial=0)).bit_length() + int(np.abs(v).max(initial=0)).bit_length() > 62:
+            raise ac.NotExact("a product past int64")
+        product = ints * v
+        if (product & ((1 << shift) - 1)).any():
+            raise ac.NotExact("finer than 2^-%d" % FastProver.SHIFT)
+        return product >> shift
+
+    @staticmethod
+    def matrix(rows, csr):
+        rp, ci, va = csr
+        rp = np.asarray(rp, np.int64)
+        assert rp.size == rows + 1 and rp[0] == 0 and rp[-1] == len(ci) and (np.diff(rp) >= 0).all()
+        return dict(rows=rows, rp=rp, ci=np.asarray(ci, np.int64), va=dyadic(va), full=rp[1:] > rp[:-1])
+
+    def row_total(self, M, x, own=None, sign=1):
+        """per row i: own_i + sign * sum_j m_ij x_j, every row's sum admitted by total()'s rule"""
+        terms = sign * self.times(M["va"], x[M["ci"]])
+        mag = np.abs(terms)
+        starts = M["rp"][:-1][M["full"]]
+        total, size, low = (np.zeros(M["rows"], np.int64) for _ in range(3))
+        if terms.size:
+            total[M["full"]] = np.add.reduceat(terms, starts)
+            size[M["full"]] = np.add.reduceat(mag, starts)
+            low[M["full"]] = np.bitwise_or.reduceat(mag, starts)
+        if own is not None:
+            total, size, low = total + own, size + np.abs(own), low | np.abs(own)
+        if int(size.max(initial=0)) >= 1 << 58:
+            raise ac.NotExact("a row of 2^%d" % (int(size.max()).bit_length() - 1 - self.SHIFT))
+        quantum = np.where(low == 0, 1 << self.SHIFT, np.minimum(low & -low, 1 << self.SHIFT))
+        units = int((size // quantum).max(initial=0))
+        self.bits = max(self.bits, units.bit_length())
+        if units >= EXACT_LIMIT:
+            raise ac.NotExact("a sum needs %d bits" % units.bit_length())
+        return total
+
+    # the three kernels of a smoothed level
+    def residual_of(self, A, f, x):
+        return self.row_total(A, x, own=f, sign=-1)
+
+    def restricted(self, PT, res):
+        return self.row_total(PT, res)
+
+    def prolonged(self, P, x, e):
+        return self.row_total(P, e, own=x)
+
+    def jacobi(self, A, wd, f, count):
+        """`count` damped Jacobi sweeps from a zero guess: wd_i f_i, then fmaf(wd_i, f_i - (A x)_i, x_i)"""
+        x = self.total(self.times(wd, f))
+        for _ in range(count - 1):
+            x = self.total(self.times(wd, self.residual_of(A, f, x)), x)
+        return x
+
+    def smoothed_cycle(self, levels, l, f, omega, pre, post, coarse_sweeps):
+        level = levels[l]
+        n = level["n"]
+        assert f.size == n
+        A = self.matrix(n, (level["rp"], level["ci"], level["va"]))
+        d = ac.diag32(n, level["rp"], level["ci"], level["va"]).astype(np.float64)
+        wd = dyadic((np.float64(np.float32(omega)) / d).astype(np.float32))       # the fp32 array the library stores
+        if l == len(levels) - 1:
+            if n <= ac.DENSE_ROWS:
+                raise ac.NotExact("a dense coarsest level")
+            return self.jacobi(A, wd, f, coarse_sweeps)
+        P, PT = self.matrix(n, level["P"]), self.matrix(level["count"], level["PT"])
+        x = self.jacobi(A, wd, f, pre)
+        coarse = self.restricted(PT, self.residual_of(A, f, x))
+        e = self.smoothed_cycle(levels, l + 1, coarse, omega, pre, post, coarse_sweeps)
+        x = self.prolonged(P, x, e)
+        for _ in range(post):
+            x = self.total(self.times(wd, self.residual_of(A, f, x)), x)
+        return x
+
+    def as_float32(self, v):
+        assert (np.abs(v) < 1 << 53).all()
+        exact = v.astype(np.float64) / float(1 << self.SHIFT)          # |v| < 2^53 units: the quotient is exact
+        out = exact.astype(np.float32)
+        assert (out.astype(np.float64) == exact).all()
+        return out
+
+    def fixed(self, vector):
+        v = np.asarray(vector, np.float64)
+        assert (v == np.rint(v)).all()
+        return np.rint(v).astype(np.int64) << self.SHIFT
+
+
+def prove_smoothed_vcycle_fast(levels, r, omega, pre, post, coarse_sweeps):
+    """(z as float32, bits) when every sum of the weighted cycle on `levels` (amg_smoothed_cases.hierarchy's dicts, or
+    what the device gives back in that form) is exact in fp32 whatever order the lanes take, else (None, reason):
+    the Jacobi sweeps, r = f - A x, PT r, the coarse sweeps from a zero guess, x + P e and the post-sweeps."""
+    prover = SmoothedProver()
+    try:
+        z = prover.smoothed_cycle(levels, 0, prover.fixed(r), omega, pre, post, coarse_sweeps)
+    except ac.NotExact as why:
+        return None, str(why)
+    return prover.as_float32(z), prover.bits
+
+
+def prove_smoothed_transfers_fast(level, f, x, e):
+    """amg_smoothed_cases.prove_transfers, vectorised, with the residual as well: (residual, f_coarse, x_out, bits)
+    as float32 arrays, or (None, None, None, reason)"""
+    prover = SmoothedProver()
+    n, count = level["n"], level["count"]
+    try:
+        A = prover.matrix(n, (level["rp"], level["ci"], level["va"]))
+        res = prover.residual_of(A, prover.fixed(f), prover.fixed(x))
+        coarse = prover.restricted(prover.matrix(count, level["PT"]), res)
+        out = prover.prolonged(prover.matrix(n, level["P"]), prover.fixed(x), prover.fixed(e))
+    except ac.NotExact as why:
+        return None, None, None, str(why)
+    return prover.as_float32(res), prover.as_float32(coarse), prover.as_float32(out), prover.bits
+
+
+def smoothed_hierarchy(spmv, n):
+    """tridiag(-1, 2, -1) of n rows, pair aggregates, omega_p = 1: the two levels through the host twins"""
+    return sc.hierarchy(spmv, *tridiagonal(n), maps=ac.pair_maps(n, n // 2), weight=SMOOTHED_WEIGHT)
+
+
+class SmoothedFractions(ac.Prover):
+    """The same cycle by amg_cases.Prover's total() on Fractions, a row at a time: what SmoothedProver is held to"""
+
+    def sweep_rows(self, rows, x, own=None, sign=1):
+        return [self.total(([own[i]] if own is not None else []) + [sign * a * x[j] for j, a in row])
+                for i, row in enumerate(rows)]
+
+    def jacobi(self, A, wd, f, count):
+        x = [self.total([w * v]) for w, v in zip(wd, f)]
+        for _ in range(count - 1):
+            x = [self.total([w * r, v]) for w, r, v in zip(wd, self.sweep_rows(A, x, f, -1), x)]
+        return x
+
+    def smoothed_cycle(self, levels, l, f, omega, pre, post, coarse_sweeps):
+        level = levels[l]
+        n = level["n"]
+        A = sc._rows(n, (level["rp"], level["ci"], level["va"]))
+        d = ac.diag32(n, level["rp"], level["ci"], level["va"]).astype(np.float64)
+        wd = [Fraction(float(w)) for w in (np.float64(np.float32(omega)) / d).astype(np.float32)]
+        if l == len(levels) - 1:
+            assert n > ac.DENSE_ROWS
+            return self.jacobi(A, wd, f, coarse_sweeps)
+        x = self.jacobi(A, wd, f, pre)
+        coarse = self.sweep_rows(sc._rows(level["count"], level["PT"]), self.sweep_rows(A, x, f, -1))
+        e = self.smoothed_cycle(levels, l + 1, coarse, omega, pre, post, coarse_sweeps)
+        x = self.sweep_rows(sc._rows(n, level["P"]), e, x)
+        for _ in range(post):
+            x = [self.total([w * r, v]) for w, r, v in zip(wd, self.sweep_rows(A, x, f, -1), x)]
+        return x
+
+
+def prove_smoothed_vcycle_fractions(levels, r, omega, pre, post, coarse_sweeps):
+    """(z as float32, bits) or (None, reason) by the Fraction prover"""
+    prover = SmoothedFractions()
+    try:
+        z = prover.smoothed_cycle(levels, 0, [Fraction(int(v)) for v in r], omega, pre, post, coarse_sweeps)
+    except ac.NotExact as why:
+        return None, str(why)
+    out = np.array([float(v) for v in z], np.float32)
+    assert all(Fraction(float(a)) == b for a, b in zip(out, z))
+    return out, prover.bits

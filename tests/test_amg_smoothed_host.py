@@ -1,8 +1,10 @@
 """The smoothed-aggregation part of include/spmv/amg.h on the host side (no GPU): the exported names and the layout of
 AMGSmoothing; amg_prolongator_cpu_csr against the restated chain of host twins, entry for entry, and against
 Fractions where the smoothed prolongator is 3/4 and 1/4; every check that needs no device, with fake device addresses
-that must never be dereferenced; the transfer prover's verdicts on the cases the GPU tests run; and the sanitized
-caller."""
+that must never be dereferenced; the transfer prover's verdicts on the cases the GPU tests run; the exact family of
+tests/test_gpu_amg_smoothed_trips.py (precond_trip_cases.SMOOTHED_CASES: the caps each case passes, the coarse
+diagonal of 1/2, the vectorised cycle prover against its Fraction twin and against both numpy cycles); and the
+sanitized caller."""
 import ctypes
 import importlib
 import os
@@ -15,7 +17,10 @@ import pytest
 
 import amg_cases as ac
 import amg_smoothed_cases as sc
+import exact_data as ed
+import precond_trip_cases as pt
 from amg_cases import bits
+from exact_data import VEC_TRIP, row_trip
 from conftest import ROOT
 
 spd = importlib.import_module("gpu-spmv_amd.spd")
@@ -162,6 +167,107 @@ def test_theta_decays_per_level_in_the_restatement(spmv):
     assert all(lv["theta"] == np.float32(0.08) for lv in fixed)
     print("poisson3d(8): halved", [lv["n"] for lv in halved], "fixed", [lv["n"] for lv in fixed])
     assert [lv["n"] for lv in halved] != [lv["n"] for lv in fixed]
+
+
+# ---- the exact cycle past the grid caps -------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def trip_levels(spmv):
+    """name -> the two levels of a case of precond_trip_cases.SMOOTHED_CASES through the host twins, built once"""
+    built = {}
+
+    def get(name):
+        if name not in built:
+            built[name] = pt.smoothed_hierarchy(spmv, pt.SMOOTHED_CASES[name][0])
+        return built[name]
+    return get
+
+
+def test_the_fast_smoothed_prover_is_the_fraction_prover(spmv):
+    n = pt.SMOOTHED_TWIN_ROWS
+    levels = pt.smoothed_hierarchy(spmv, n)
+    assert [lv["n"] for lv in levels] == [n, n // 2] and n // 2 > ac.DENSE_ROWS
+    r = ac.exact_rhs(n)
+    for pre, coarse, post in pt.SMOOTHED_TWIN_CHECKS:
+        want, width = pt.prove_smoothed_vcycle_fractions(levels, r, pt.AMG_OMEGA, pre, post, coarse)
+        got, got_width = pt.prove_smoothed_vcycle_fast(levels, r, pt.AMG_OMEGA, pre, post, coarse)
+        assert want is not None and got is not None, (pre, coarse, post, width, got_width)
+        assert got_width == width
+        np.testing.assert_array_equal(bits(got), bits(want))
+    # both refuse a right-hand side too wide for fp32, and the weight at which the coarse diagonal is 5/8
+    wide = r * np.float32(1 << 20)
+    assert pt.prove_smoothed_vcycle_fast(levels, wide, pt.AMG_OMEGA, 1, 1, 1)[0] is None
+    assert pt.prove_smoothed_vcycle_fractions(levels, wide, pt.AMG_OMEGA, 1, 1, 1)[0] is None
+    half = sc.hierarchy(spmv, *pt.tridiagonal(n), maps=ac.pair_maps(n, n // 2), weight=0.5)
+    assert half[1]["va"][half[1]["ci"] == ac.rows_of(n // 2, half[1]["rp"])][5] == np.float32(0.625)
+    assert pt.prove_smoothed_vcycle_fast(half, r, pt.AMG_OMEGA, 1, 1, 1)[0] is None
+    assert pt.prove_smoothed_vcycle_fractions(half, r, pt.AMG_OMEGA, 1, 1, 1)[0] is None
+    # the transfers alone: amg_smoothed_cases.prove_transfers' vectors and width on its three cases
+    for name, level in transfer_levels(spmv):
+        f, x, e = sc.exact_vectors(level)
+        want_fc, want_x, width = sc.prove_transfers(level, f, x, e)
+        res, fc, out, got_width = pt.prove_smoothed_transfers_fast(level, f, x, e)
+        assert want_fc is not None and fc is not None and got_width == width, (name, width, got_width)
+        np.testing.assert_array_equal(bits(fc), bits(want_fc), err_msg=name)
+        np.testing.assert_array_equal(bits(out), bits(want_x), err_msg=name)
+        np.testing.assert_array_equal(res.astype(np.float64), f - ac._spmv(level, x.astype(np.float64), np.float64))
+    assert pt.prove_smoothed_transfers_fast(level, f * np.float32(1 << 22), x, e)[0] is None
+
+
+@pytest.mark.parametrize("name", list(pt.SMOOTHED_CASES))
+def test_every_smoothed_trip_case_is_admitted_and_passes_its_caps(trip_levels, name):
+    n, lanes, sweep_counts = pt.SMOOTHED_CASES[name]
+    levels = trip_levels(name)
+    fine, coarse = levels
+    count = n // 2
+    assert n % 2 == 0 and [lv["n"] for lv in levels] == [n, count] == [fine["n"], fine["count"]]
+    assert count > ac.DENSE_ROWS                                        # Jacobi-solved: no dense inverse
+    # the caps: A and P have n rows, PT and level 1 have n / 2
+    if name in ("L64", "L8"):
+        assert pt.trips(n, row_trip(lanes)) == 3 and pt.trips(count, row_trip(lanes)) == 2
+        assert pt.row_grid(count, 256 // lanes) == pt.ROW_BLOCKS and count - row_trip(lanes) == (5 if lanes == 64 else 33)
+    elif name == "vec":
+        assert count == pt.VEC_ROWS and pt.trips(n, VEC_TRIP) == 3 and pt.trips(count, VEC_TRIP) == 2
+        # the library's own lane counts (pick_lanes_per_row, restated by exact_data.lanes_for): one lane for A, P and
+        # PT, so the sweeps over A and P make a second trip of row_trip(1) rows; two lanes on level 1
+        picked = [ed.lanes_for(m[1].size, rows) for m, rows in (((fine["rp"], fine["ci"]), n), (fine["P"], n),
+                                                               (fine["PT"], count), ((coarse["rp"], coarse["ci"]), count))]
+        assert picked == [1, 1, 1, 2] and pt.trips(n, row_trip(1)) == 2 and pt.trips(count, row_trip(2)) == 2
+    else:
+        assert lanes == 64 and count - row_trip(64) == {"below": -1, "at": 0, "above": 1}[name]
+        assert pt.trips(n, row_trip(64)) == (2 if name == "below" else 3 if name == "above" else 2)
+        assert n > row_trip(64) and pt.row_grid(count, 4) == pt.ROW_BLOCKS
+        assert pt.trips(count, row_trip(64)) == (2 if name == "above" else 1)
+    # what the issue worked out by hand, read from the host twins
+    p_rp, p_ci, p_va = fine["P"]
+    assert (p_va == np.float32(0.5)).all() and np.array_equal(np.diff(p_rp), np.r_[1, np.full(n - 2, 2), 1])
+    rows = ac.rows_of(count, coarse["rp"])
+    distance = np.abs(coarse["ci"] - rows)
+    diagonal = coarse["va"][distance == 0]
+    print(f"{name}: coarse diagonal in [{diagonal.min()}, {diagonal.max()}], {diagonal.size} rows")
+    assert diagonal.size == count and (diagonal == np.float32(0.5)).all()
+    assert (coarse["va"][distance == 1] == 0).all() and (coarse["va"][distance == 2] == np.float32(-0.25)).all()
+    assert distance.max() == 2 and np.count_nonzero(distance == 1) == 2 * (count - 1)
+    assert np.array_equal(ac.diag32(count, coarse["rp"], coarse["ci"], coarse["va"]), np.full(count, 0.5, np.float32))
+    # the transfer test's vectors: integers in [-8, 8] for f, x and e
+    f, x, e = sc.exact_vectors(fine)
+    res, fc, out, width = pt.prove_smoothed_transfers_fast(fine, f, x, e)
+    print(f"{name}: the transfers on integer f, x, e: " + (f"{width} bits" if res is not None else f"not admitted ({width})"))
+    assert res is not None and width < 24, (name, width)
+    np.testing.assert_array_equal(res.astype(np.float64), f - ac._spmv(fine, x.astype(np.float64), np.float64))
+    np.testing.assert_array_equal(fc.astype(np.float64), sc._matvec(count, fine["PT"], res.astype(np.float64), np.float64))
+    np.testing.assert_array_equal(out.astype(np.float64), x + sc._matvec(n, fine["P"], e.astype(np.float64), np.float64))
+    r = ac.exact_rhs(n)
+    for pre, coarse_sweeps, post in sweep_counts:
+        z, width = pt.prove_smoothed_vcycle_fast(levels, r, pt.AMG_OMEGA, pre, post, coarse_sweeps)
+        print(f"{name}: n = {n}, (pre, coarse, post) = {(pre, coarse_sweeps, post)}: " +
+              (f"{width} bits" if z is not None else f"not admitted ({width})"))
+        assert z is not None, (name, pre, coarse_sweeps, post, width)
+        assert width < 24 and np.abs(z).max() > 0
+        # everything is exact, so any order of evaluation gives the same floats: both numpy cycles
+        for dtype in (np.float32, np.float64):
+            other = sc.vcycle(levels, r, pt.AMG_OMEGA, pre, post, coarse_sweeps, dtype)
+            np.testing.assert_array_equal(bits(other.astype(np.float32)), bits(z), err_msg=f"{name} {dtype.__name__}")
+            np.testing.assert_array_equal(other.astype(np.float64), z.astype(np.float64))
 
 
 # ---- rejections without a device -------------------------------------------------------------------------------

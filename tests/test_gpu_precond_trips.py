@@ -34,7 +34,10 @@ mis2_init_kernel, mis2_flags_kernel,     tridiag(-1, 2, -1) of V + 257 rows     
 the device scan, amg_prolongation_kernel                                                      takes the end slot)
 amg_diag_kernel, min_fold_kernel         the same with a zero diagonal in a row >= V          257; 1024 partials
 
-The FSAI exact tier repeats one period proved by fsai_cases.prove_exact (precond_trip_cases' docstring says why)."""
+The FSAI exact tier repeats one period proved by fsai_cases.prove_exact (precond_trip_cases' docstring says why).
+The smoothed-aggregation AMG (amg_residual_kernel, amg_restrict_weighted_kernel, amg_prolong_kernel,
+amg_smoothing_scale_kernel and the refill of amg_update) has the same pass in tests/test_gpu_amg_smoothed_trips.py,
+which lists its kernels and caps."""
 import contextlib
 import functools
 import importlib
