@@ -1,6 +1,8 @@
-"""Shared helpers of tests/test_amg_mis2_host.py and tests/test_gpu_amg_setup_device.py: a numpy restatement of the
+"""Shared helpers of tests/test_amg_mis2_host.py, tests/test_gpu_amg_setup_device.py and
+tests/test_gpu_amg_mis2_trips.py: a numpy restatement of the
 MIS-2 aggregation of include/spmv/amg.h, written rule for rule in amg_cases.aggregate's style; the checker of its
-properties on a symmetric strong graph; the inputs; the restated hierarchy and its fp32 PCG; and what
+properties on a symmetric strong graph; the inputs, those past the grid caps included; the restated hierarchy and its
+fp32 PCG; and what
 tests/golden/mis2_restate.json records (tests/golden/make_mis2_golden.py writes it).  A plain module, not a
 conftest."""
 import importlib
@@ -10,6 +12,7 @@ import os
 import numpy as np
 
 import amg_cases as ac
+import exact_data as ed
 
 spd = importlib.import_module("gpu-spmv_amd.spd")
 
@@ -65,6 +68,11 @@ def neighbourhoods(n, rp, ci, strong):
 
 def aggregate(n, rp, ci, va, theta, seed):
     """amg.h's MIS-2 rule, restated; (aggregate int32[n] with -1 = free, count, synchronous rounds)"""
+    return aggregate_parts(n, rp, ci, va, theta, seed)[:3]
+
+
+def aggregate_parts(n, rp, ci, va, theta, seed):
+    """aggregate's three results, then the root flags and `first`, the map as phase 1 leaves it (-1 = phase 2's)"""
     rp = np.asarray(rp, np.int64)
     ci = np.asarray(ci, np.int64)
     va = np.asarray(va, np.float32)
@@ -112,7 +120,7 @@ def aggregate(n, rp, ci, va, theta, seed):
                 new[v] = ROOT
         state = new
     assert np.array_equal(state == ROOT, root)
-    return agg.astype(np.int32), count, rounds
+    return agg.astype(np.int32), count, rounds, root, first
 
 
 def check_properties(n, rp, ci, va, theta, agg, count, root):
@@ -208,6 +216,105 @@ SYMMETRIC = {
 }
 UNSYMMETRIC = {"unsymmetric": unsymmetric}
 CASES = dict(SYMMETRIC, **UNSYMMETRIC)
+
+
+# ---- inputs past the grid caps (tests/test_gpu_amg_mis2_trips.py); vectorised numpy only -------------------------
+# A row kernel at L lanes covers ed.row_trip(L) rows a trip of its capped grid, an element-wise kernel ed.VEC_TRIP
+# elements.  test_amg_mis2_host.py settles on the CPU what each case claims.
+HUB_SPOKES = 300
+TRIP_PAIRS = ((0.08, 0), (0.0, 0xDEADBEEF))            # the (theta, seed) every case past a cap is aggregated with
+HUB_SEED = 5                                           # of the base matrix spd.random_spd(n, k, HUB_SEED)
+
+
+def _rows_sorted(n, rows, cols, vals):
+    """CSR of triplets, storage order kept inside a row (a stable sort by row)"""
+    order = np.argsort(rows, kind="stable")
+    rp = np.zeros(n + 1, np.int32)
+    np.cumsum(np.bincount(rows, minlength=n), out=rp[1:])
+    return n, rp, cols[order].astype(np.int32), np.asarray(vals, np.float32)[order]
+
+
+def cap_hub(n, k, seed=HUB_SEED):
+    """spd.random_spd(n, k, seed) (rows unsorted, columns repeated) with the last row made a hub: HUB_SPOKES spokes to
+    np.linspace(0, n - 2, HUB_SPOKES), -1 both ways and stored after the base entries of their rows, every base entry
+    between the hub and a spoke removed first, the hub's diagonal 4.0 (star's rule: nothing solves with it).  The hub
+    row lies in the last trip of every row kernel, is longer than a lane group and gives each leaf more than 64 two-hop
+    neighbours; its leaves are spread over every trip."""
+    _, rp, ci, va = spd.random_spd(n, k, seed)
+    rows, ci, va = ac.rows_of(n, rp), np.asarray(ci, np.int64), np.asarray(va, np.float32).copy()
+    hub = n - 1
+    spokes = np.unique(np.linspace(0, n - 2, HUB_SPOKES).astype(np.int64))
+    assert spokes.size == HUB_SPOKES
+    is_spoke = np.zeros(n, bool)
+    is_spoke[spokes] = True
+    keep = ~(((rows == hub) & is_spoke[ci]) | ((ci == hub) & is_spoke[rows]))
+    va[(rows == hub) & (ci == hub)] = 4.0
+    minus = np.full(HUB_SPOKES, -1.0, np.float32)
+    return _rows_sorted(n, np.concatenate([rows[keep], np.full(HUB_SPOKES, hub), spokes]),
+                        np.concatenate([ci[keep], spokes, np.full(HUB_SPOKES, hub)]),
+                        np.concatenate([va[keep], minus, minus]))
+
+
+def cap_unsymmetric(n, k, seed=HUB_SEED):
+    """spd.random_spd(n, k, seed) with each off-diagonal entry dropped independently with probability 1/4: pattern and
+    values both unsymmetric, N2 not symmetric"""
+    _, rp, ci, va = spd.random_spd(n, k, seed)
+    rows = ac.rows_of(n, rp)
+    keep = (rows == ci) | (np.random.default_rng(seed + 1).random(ci.size) >= 0.25)
+    return _rows_sorted(n, rows[keep], np.asarray(ci, np.int64)[keep], np.asarray(va, np.float32)[keep])
+
+
+def priority_chain(m, seed):
+    """A path with -1 off and 2 on the diagonal that visits the m vertices in descending priority under `seed`.  The
+    synchronous loop decides its first vertex in round 1 and three more every two rounds: ceil(2 m / 3) rounds."""
+    order = np.argsort(priorities(m, seed))[::-1].astype(np.int64)
+    i = np.arange(m, dtype=np.int64)
+    return _rows_sorted(m, np.concatenate([order[:-1], order[1:], i]), np.concatenate([order[1:], order[:-1], i]),
+                        np.concatenate([np.full(2 * (m - 1), -1.0), np.full(m, 2.0)]).astype(np.float32))
+
+
+def chain_rounds(m):
+    return -(-2 * m // 3)
+
+
+def _hub_k(n):
+    return 7 if n <= ed.row_trip(8) else 3
+
+
+# Seeds other than HUB_SEED, chosen so that the case meets test_amg_mis2_host.py's condition on its last trip: the five
+# rows of the third trip at 64 lanes hold a root, a phase-1 member and a phase-2 member under both TRIP_PAIRS; the one
+# row of the unsymmetric case's second trip is a root under the first pair and phase 2's under the second.
+CASE_SEEDS = {("hub", 2 * ed.row_trip(64) + 5): 27, ("unsymmetric", ed.row_trip(64) + 1): 75}
+
+
+def _row_cases():
+    """name -> (forced mis_lanes, n, builder)"""
+    cases = {}
+    for L in (64, 8):
+        R = ed.row_trip(L)
+        for n in (R - 1, R, R + 1, 2 * R + 5):
+            cases["hub L%d n=%d" % (L, n)] = (
+                L, n, lambda n=n: cap_hub(n, _hub_k(n), CASE_SEEDS.get(("hub", n), HUB_SEED)))
+        cases["unsymmetric L%d n=%d" % (L, R + 1)] = (
+            L, R + 1, lambda n=R + 1: cap_unsymmetric(n, _hub_k(n), CASE_SEEDS.get(("unsymmetric", n), HUB_SEED)))
+    for L in ed.LANES[1:]:
+        if L not in (64, 8):
+            n = ed.LANE_SIZES[L]
+            cases["hub L%d n=%d" % (L, n)] = (L, n, lambda n=n: cap_hub(n, _hub_k(n)))
+    return cases
+
+
+ROW_CASES = _row_cases()
+VEC_CASES = {"hub L2 n=%d" % n: (2, n, lambda n=n: cap_hub(n, 3))
+             for n in (ed.VEC_TRIP - 1, ed.VEC_TRIP, ed.VEC_TRIP + 1)}
+CHAIN_CASES = (12, 13, 24, 25, 40)                     # around one and two batches of kRoundsPerBatch = 8, and past two
+RESTATED_ROWS = 2 * ed.row_trip(64) + 5                # up to here the restatement's Python loops are affordable
+
+
+def last_trip(L, n):
+    """the rows of the last trip of a row kernel at L lanes over n rows"""
+    R = ed.row_trip(L)
+    return np.arange((n - 1) // R * R, n)
 
 
 # ---- the restated hierarchy and its PCG ------------------------------------------------------------------------

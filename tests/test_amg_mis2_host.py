@@ -8,10 +8,13 @@ import json
 import os
 import re
 import subprocess
+import time
 
 import numpy as np
 import pytest
 
+import amg_cases as ac
+import exact_data as ed
 import mis2_cases as mc
 from conftest import ROOT
 
@@ -117,6 +120,140 @@ def test_phase_two_takes_the_largest_entry_and_the_first_on_a_tie(spmv):
         if found == 3:
             break
     assert found == 3
+
+
+# ---- the cases past the grid caps (tests/test_gpu_amg_mis2_trips.py) ---------------------------------------------
+TRIP_CASES = dict(mc.ROW_CASES, **mc.VEC_CASES)
+RESTATED = [name for name, case in TRIP_CASES.items() if case[1] <= mc.RESTATED_ROWS]
+
+
+def define(spmv, n, rp, ci, va, theta, seed):
+    A = spmv.csr_from_arrays(n, n, rp, ci, va)
+    try:
+        start = time.perf_counter()
+        status, agg, count, rounds = spmv.amg_aggregate_mis2_cpu_csr(A, theta, seed)
+        return status, agg, count, rounds, time.perf_counter() - start
+    finally:
+        spmv.csr_destroy(A)
+
+
+def test_the_case_lists_are_the_caps_neighbours():
+    assert len(mc.ROW_CASES) == 14 and len(mc.VEC_CASES) == 3 and len(TRIP_CASES) == 17
+    sizes = {}
+    for name, (L, n, _) in mc.ROW_CASES.items():
+        sizes.setdefault((name.split()[0], L), []).append(n)
+    for L in (64, 8):
+        R = ed.row_trip(L)
+        assert sizes["hub", L] == [R - 1, R, R + 1, 2 * R + 5] and sizes["unsymmetric", L] == [R + 1]
+    assert ed.row_trip(64) == 8192 and ed.row_trip(2) == ed.VEC_TRIP
+    for L in (2, 4, 16, 32):
+        assert sizes["hub", L] == [ed.LANE_SIZES[L]] and ed.row_trip(L) < ed.LANE_SIZES[L] < 2 * ed.row_trip(L)
+    assert [(L, n) for L, n, _ in mc.VEC_CASES.values()] == [(2, ed.VEC_TRIP + off) for off in (-1, 0, 1)]
+    assert mc.RESTATED_ROWS == 16389 and len(RESTATED) == 5
+
+
+def test_the_hub_and_the_dropped_entries_are_what_the_cases_claim():
+    """cap_hub at the issue's n = 8197: a symmetric pattern with unsorted rows and repeated columns, the hub row of 316
+    entries with 4.0 on its diagonal, every spoke stored once and -1 both ways, a leaf in every trip at 64 lanes;
+    cap_unsymmetric: a quarter of the off-diagonal entries gone, pattern unsymmetric, the diagonal whole."""
+    n, rp, ci, va = mc.cap_hub(8197, 7)
+    rows, hub = ac.rows_of(n, rp), n - 1
+    assert rp[n] - rp[hub] == 316
+    pairs = set(zip(rows.tolist(), ci.tolist()))
+    assert all((j, i) in pairs for i, j in pairs)
+    spokes = np.linspace(0, n - 2, mc.HUB_SPOKES).astype(np.int64)
+    hub_row, hub_vals = ci[rp[hub]:], va[rp[hub]:]
+    for s in spokes:
+        assert (hub_row == s).sum() == 1 and hub_vals[hub_row == s][0] == -1.0
+        mine = ci[rp[s]:rp[s + 1]] == hub
+        assert mine.sum() == 1 and va[rp[s]:rp[s + 1]][mine][0] == -1.0
+    assert va[(rows == hub) & (ci == hub)].tolist() == [4.0]
+    assert set((spokes // ed.row_trip(64)).tolist()) == {0, 1} and hub // ed.row_trip(64) == 1
+    lens = np.diff(rp)
+    assert any((np.diff(ci[rp[i]:rp[i + 1]]) < 0).any() for i in range(200))
+    assert any(np.unique(ci[rp[i]:rp[i + 1]]).size < lens[i] for i in range(n))
+    _, base_rp, base_ci, _ = mc.spd.random_spd(8197, 7, mc.HUB_SEED)
+    n, rp, ci, va = mc.cap_unsymmetric(8197, 7)
+    rows = ac.rows_of(n, rp)
+    dropped = (base_ci.size - ci.size) / (base_ci.size - n)
+    assert 0.23 < dropped < 0.27 and (rows == ci).sum() == n
+    pairs = set(zip(rows.tolist(), ci.tolist()))
+    assert sum((j, i) not in pairs for i, j in pairs) > 1000
+
+
+def test_the_numbers_the_cases_were_designed_on(spmv):
+    """n = 8197 = exact_data.LANE_SIZES[64], k = 7, seed 5, under both TRIP_PAIRS: (aggregates, synchronous rounds)"""
+    for build, want in ((mc.cap_hub, [(997, 15), (202, 15)]), (mc.cap_unsymmetric, [(1524, 10), (348, 12)])):
+        got = []
+        for theta, seed in mc.TRIP_PAIRS:
+            status, agg, count, rounds, _ = define(spmv, *build(8197, 7), theta, seed)
+            assert status == 0 and agg.min() >= 0
+            got.append((count, rounds))
+        assert got == want, (build.__name__, got)
+
+
+@pytest.mark.parametrize("name", list(TRIP_CASES))
+def test_the_definition_leaves_nobody_free_past_the_caps(spmv, name):
+    """what the device test relies on: status 0, no -1, 1 < count < n, in a time a GPU test can afford (printed)"""
+    L, n, build = TRIP_CASES[name]
+    matrix = build()
+    assert matrix[0] == n
+    for theta, seed in mc.TRIP_PAIRS:
+        status, agg, count, rounds, took = define(spmv, *matrix, theta, seed)
+        print(f"{name} theta={theta} seed={seed:#x}: {count} aggregates, {rounds} rounds, {took:.2f} s")
+        assert status == 0 and agg.min() >= 0 and agg.max() == count - 1 and 1 < count < n, (name, theta, seed, count)
+        assert 1 <= rounds <= n
+
+
+def kinds_of(root, first, rows):
+    """(roots, phase-1 members, phase-2 members) among `rows`"""
+    return (int(root[rows].sum()), int((~root[rows] & (first[rows] != -1)).sum()), int((first[rows] == -1).sum()))
+
+
+@pytest.mark.parametrize("name", RESTATED)
+def test_restatement_and_last_trip_of_the_cases_up_to_three_trips_at_64_lanes(spmv, name):
+    """The restatement equals the definition entry for entry, and the rows of the LAST trip of the row kernels hold a
+    root, a phase-1 member and a phase-2 member (first == -1 before phase 2) under both TRIP_PAIRS, so that a last
+    trip that is dropped, or reads stale states, changes ints of every kind.  A last trip of ONE row (n = R_64 + 1)
+    cannot hold three kinds: there the hub case's row, the hub itself, is a phase-1 member under both pairs, and the
+    unsymmetric case's seed makes its row a root under the first pair and phase 2's under the second."""
+    L, n, build = TRIP_CASES[name]
+    matrix = build()
+    rows = mc.last_trip(L, n)
+    assert rows[-1] == n - 1 and rows.size == (n - 1) % ed.row_trip(L) + 1
+    found = []
+    for theta, seed in mc.TRIP_PAIRS:
+        status, agg, count, rounds, _ = define(spmv, *matrix, theta, seed)
+        want, want_count, want_rounds, root, first = mc.aggregate_parts(*matrix, theta, seed)
+        assert (status, count, rounds) == (0, want_count, want_rounds), (name, theta, seed)
+        np.testing.assert_array_equal(agg, want, err_msg=str((name, theta, seed)))
+        found.append(kinds_of(root, first, rows))
+    print(name, "roots, phase-1 and phase-2 members in the last trip of", rows.size, "rows:", found)
+    if rows.size > 1:
+        assert all(min(k) >= 1 for k in found), (name, found)
+    elif name.startswith("hub"):
+        assert found == [(0, 1, 0), (0, 1, 0)], (name, found)
+    else:
+        assert found == [(1, 0, 0), (0, 0, 1)], (name, found)
+    if name.startswith("hub"):
+        _, rp, _, _ = matrix
+        assert n - 1 in rows and rp[n] - rp[n - 1] > 64
+
+
+@pytest.mark.parametrize("m", mc.CHAIN_CASES + (26,))
+def test_priority_chains_take_two_rounds_per_three_vertices(spmv, m):
+    want = {12: 8, 13: 9, 24: 16, 25: 17, 26: 18, 40: 27}[m]
+    assert mc.chain_rounds(m) == want
+    for seed in (0, 1, 0xDEADBEEF):
+        n, rp, ci, va = mc.priority_chain(m, seed)
+        assert n == m and rp[m] == 3 * m - 2 and sorted(np.diff(rp).tolist()) == [2, 2] + [3] * (m - 2)
+        status, agg, count, rounds, _ = define(spmv, n, rp, ci, va, 0.08, seed)
+        restated = mc.aggregate(n, rp, ci, va, 0.08, seed)
+        assert (status, rounds, restated[2]) == (0, want, want), (m, seed, rounds, restated[2])
+        assert count == restated[1] == -(-m // 3) and np.array_equal(agg, restated[0]) and agg.min() >= 0
+    # another seed's priorities do not walk the path in order: the chain is the slow case, not the usual one
+    n, rp, ci, va = mc.priority_chain(m, 0)
+    assert define(spmv, n, rp, ci, va, 0.08, 1)[3] < want
 
 
 # ---- the golden ----------------------------------------------------------------------------------------------
