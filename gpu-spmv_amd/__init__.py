@@ -182,6 +182,31 @@ class GMRESResult(Structure):
     NONE, SINGULAR, NOT_FINITE = GMRES_NO_BREAKDOWN, GMRES_SINGULAR, GMRES_NOT_FINITE
 
 
+class MinresConfig(Structure):
+    """include/spmv/minres.h MinresConfig (20 bytes): solves (A - shift I) x = b; preconditioner 0 NONE / 1 JACOBI
+    (M = |diag(A - shift I)|); the other fields as CGConfig"""
+    _fields_ = [("tolerance", c_float), ("max_iterations", c_int32), ("preconditioner", c_int32),
+                ("engine", c_int32), ("shift", c_float)]
+    NONE, JACOBI = 0, 1
+
+    def __init__(self, tolerance=1e-6, max_iterations=1000, preconditioner=1, engine=-1, shift=0.0):
+        super().__init__(tolerance, max_iterations, preconditioner, engine, shift)
+
+
+# MinresResult.breakdown codes (include/spmv/minres.h MinresResult::Breakdown)
+MINRES_NO_BREAKDOWN, MINRES_PRECONDITIONER, MINRES_NOT_FINITE, MINRES_SINGULAR = 0, 1, 2, 3
+
+
+class MinresResult(Structure):
+    """include/spmv/minres.h MinresResult (28 bytes); relative_residual is the recurrence's (M^-1-norm),
+    true_relative_residual the recomputed 2-norm one; breakdown is one of NONE, PRECONDITIONER, NOT_FINITE, SINGULAR"""
+    _fields_ = [("error_code", c_int32), ("iterations", c_int32), ("relative_residual", c_float),
+                ("true_relative_residual", c_float), ("converged", c_int32), ("breakdown", c_int32),
+                ("elapsed_ms", c_float)]
+    NONE, PRECONDITIONER, NOT_FINITE, SINGULAR = (MINRES_NO_BREAKDOWN, MINRES_PRECONDITIONER, MINRES_NOT_FINITE,
+                                                  MINRES_SINGULAR)
+
+
 class EigsConfig(Structure):
     """include/spmv/eigs.h EigsConfig (24 bytes): num_values 1..32; which 0 LARGEST / 1 SMALLEST (algebraic); basis 0
     (= min(max(2 num_values, 20), 64)) or in (num_values, 64]; engine as CGConfig"""
@@ -461,6 +486,10 @@ _SIGNATURES = {
                                    POINTER(GMRESResult)]),
     "spmv_c_gmres_solve_lu": (c_int, [POINTER(CSRMatrix), POINTER(CSRMatrix), c_void_p, c_void_p,
                                       POINTER(GMRESConfig), POINTER(GMRESResult)]),
+    "spmv_c_minres_solve": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, POINTER(MinresConfig),
+                                    POINTER(MinresResult)]),
+    "spmv_c_minres_solve_ic": (c_int, [POINTER(CSRMatrix), POINTER(CSRMatrix), c_void_p, c_void_p,
+                                       POINTER(MinresConfig), POINTER(MinresResult)]),
     "spmv_c_eigs_sym": (c_int, [POINTER(CSRMatrix), c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                 POINTER(EigsConfig), POINTER(EigsResult)]),
     "spmv_c_sym_eig_small": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_int]),
@@ -1255,6 +1284,26 @@ def gmres_solve_lu(A, LU, d_b, d_x, config=None) -> GMRESResult:
     out = GMRESResult()
     lib().spmv_c_gmres_solve_lu(A, LU, _dev(d_b), _dev(d_x), byref(config) if config is not None else None,
                                 byref(out))
+    return out
+
+
+def minres_solve(A, d_b, d_x, config=None) -> MinresResult:
+    """Preconditioned MINRES for (A - shift I) x = b, A square and symmetric, definite or not, on the device
+    (include/spmv/minres.h minres_solve): d_b and d_x hold num_rows floats, d_x is the initial guess on entry and the
+    solution on exit.  relative_residual and converged are the recurrence's (M^-1-norm); true_relative_residual is
+    recomputed from the returned x."""
+    out = MinresResult()
+    lib().spmv_c_minres_solve(A, _dev(d_b), _dev(d_x), byref(config) if config is not None else None, byref(out))
+    return out
+
+
+def minres_solve_ic(A, F, d_b, d_x, config=None) -> MinresResult:
+    """MINRES preconditioned by M = L L^T, the lower and the upper triangle of the device factor matrix F
+    (include/spmv/minres.h minres_solve_ic); F is usually ic0_csr's output for an SPD sibling of A, wrapped by
+    csr_wrap_device.  config.preconditioner is not read."""
+    out = MinresResult()
+    lib().spmv_c_minres_solve_ic(A, F, _dev(d_b), _dev(d_x), byref(config) if config is not None else None,
+                                 byref(out))
     return out
 
 

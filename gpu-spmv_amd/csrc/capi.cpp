@@ -7,6 +7,7 @@
 #include "spmv/bandwidth.h"
 #include "spmv/bicgstab.h"
 #include "spmv/gmres.h"
+#include "spmv/minres.h"
 #include "spmv/eigs.h"
 #include "spmv/cg.h"
 #include "spmv/pagerank.h"
@@ -94,6 +95,21 @@ static_assert(offsetof(spmv_c_gmres_result, iterations) == offsetof(GMRESResult,
               offsetof(spmv_c_gmres_result, converged) == offsetof(GMRESResult, converged) &&
               offsetof(spmv_c_gmres_result, breakdown) == offsetof(GMRESResult, breakdown) &&
               offsetof(spmv_c_gmres_result, elapsed_ms) == offsetof(GMRESResult, elapsed_ms), "GMRESResult layout");
+static_assert(sizeof(spmv_c_minres_config) == sizeof(MinresConfig) && sizeof(MinresConfig) == 20,
+              "MinresConfig layout");
+static_assert(offsetof(spmv_c_minres_config, max_iterations) == offsetof(MinresConfig, max_iterations) &&
+              offsetof(spmv_c_minres_config, preconditioner) == offsetof(MinresConfig, preconditioner) &&
+              offsetof(spmv_c_minres_config, engine) == offsetof(MinresConfig, engine) &&
+              offsetof(spmv_c_minres_config, shift) == offsetof(MinresConfig, shift), "MinresConfig layout");
+static_assert(sizeof(spmv_c_minres_result) == sizeof(MinresResult) && sizeof(MinresResult) == 28,
+              "MinresResult layout");
+static_assert(offsetof(spmv_c_minres_result, iterations) == offsetof(MinresResult, iterations) &&
+              offsetof(spmv_c_minres_result, relative_residual) == offsetof(MinresResult, relative_residual) &&
+              offsetof(spmv_c_minres_result, true_relative_residual) ==
+                  offsetof(MinresResult, true_relative_residual) &&
+              offsetof(spmv_c_minres_result, converged) == offsetof(MinresResult, converged) &&
+              offsetof(spmv_c_minres_result, breakdown) == offsetof(MinresResult, breakdown) &&
+              offsetof(spmv_c_minres_result, elapsed_ms) == offsetof(MinresResult, elapsed_ms), "MinresResult layout");
 static_assert(sizeof(spmv_c_eigs_config) == sizeof(EigsConfig) && sizeof(EigsConfig) == 24, "EigsConfig layout");
 static_assert(offsetof(spmv_c_eigs_config, which) == offsetof(EigsConfig, which) &&
               offsetof(spmv_c_eigs_config, basis) == offsetof(EigsConfig, basis) &&
@@ -682,6 +698,20 @@ int spmv_c_gmres_solve(const spmv_c_csr* A, const float* d_b, float* d_x, const 
 int spmv_c_gmres_solve_lu(const spmv_c_csr* A, const spmv_c_csr* LU, const float* d_b, float* d_x,
                           const spmv_c_gmres_config* config, spmv_c_gmres_result* out) {
     const GMRESResult r = gmres_solve_lu(cxx(A), cxx(LU), d_b, d_x, reinterpret_cast<const GMRESConfig*>(config));
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
+}
+
+int spmv_c_minres_solve(const spmv_c_csr* A, const float* d_b, float* d_x, const spmv_c_minres_config* config,
+                        spmv_c_minres_result* out) {
+    const MinresResult r = minres_solve(cxx(A), d_b, d_x, reinterpret_cast<const MinresConfig*>(config));
+    if (out) std::memcpy(out, &r, sizeof(r));
+    return r.error_code;
+}
+
+int spmv_c_minres_solve_ic(const spmv_c_csr* A, const spmv_c_csr* F, const float* d_b, float* d_x,
+                           const spmv_c_minres_config* config, spmv_c_minres_result* out) {
+    const MinresResult r = minres_solve_ic(cxx(A), cxx(F), d_b, d_x, reinterpret_cast<const MinresConfig*>(config));
     if (out) std::memcpy(out, &r, sizeof(r));
     return r.error_code;
 }

@@ -370,6 +370,43 @@ int spmv_c_gmres_solve(const spmv_c_csr* A, const float* d_b, float* d_x, const 
 int spmv_c_gmres_solve_lu(const spmv_c_csr* A, const spmv_c_csr* LU, const float* d_b, float* d_x,
                           const spmv_c_gmres_config* config, spmv_c_gmres_result* out);
 
+/* ---- MINRES for symmetric indefinite systems (extension; spmv::minres_solve, include/spmv/minres.h) ---- */
+/* 20 bytes; solves (A - shift I) x = b; preconditioner 0 NONE / 1 JACOBI (M = |diag(A - shift I)|); the other fields
+ * as spmv_c_cg_config */
+typedef struct spmv_c_minres_config {
+    float   tolerance;
+    int32_t max_iterations;
+    int32_t preconditioner;
+    int32_t engine;
+    float   shift;
+} spmv_c_minres_config;
+
+/* breakdown: 0 none, 1 PRECONDITIONER (r.M^-1 r < 0), 2 NOT_FINITE, 3 SINGULAR (gamma == 0).  relative_residual is the
+ * recurrence's, in the M^-1-norm; true_relative_residual is ||b - (A - shift I) x||_2 / ||b||_2 recomputed from the
+ * returned x (28 bytes) */
+typedef struct spmv_c_minres_result {
+    int32_t error_code;
+    int32_t iterations;
+    float   relative_residual;
+    float   true_relative_residual;
+    int32_t converged;
+    int32_t breakdown;
+    float   elapsed_ms;
+} spmv_c_minres_result;
+
+/* Solves (A - shift I) x = b for a square symmetric A, definite or not, on the device by preconditioned MINRES; d_b
+ * and d_x hold num_rows floats, d_x is the initial guess on entry and the solution on exit.  config NULL = defaults
+ * (1e-6, 1000, JACOBI, auto, 0).  Argument checks and numerics as minres_solve in include/spmv/minres.h.  The return
+ * value equals out->error_code (out may be NULL). */
+int spmv_c_minres_solve(const spmv_c_csr* A, const float* d_b, float* d_x, const spmv_c_minres_config* config,
+                        spmv_c_minres_result* out);
+
+/* the same iteration preconditioned by M = L L^T from the factor matrix F as spmv_c_cg_solve_ic.
+ * config->preconditioner is not read.  Checks and numerics as minres_solve_ic in include/spmv/minres.h.  The return
+ * value equals out->error_code (out may be NULL). */
+int spmv_c_minres_solve_ic(const spmv_c_csr* A, const spmv_c_csr* F, const float* d_b, float* d_x,
+                           const spmv_c_minres_config* config, spmv_c_minres_result* out);
+
 /* ---- extreme eigenpairs of a symmetric matrix (extension; spmv::eigs_sym, include/spmv/eigs.h) ---- */
 /* 24 bytes; num_values in [1, 32]; which 0 LARGEST / 1 SMALLEST (algebraic); basis 0 (default) or in (num_values, 64] */
 typedef struct spmv_c_eigs_config {
